@@ -119,9 +119,17 @@ def parse_args(argv=None):
     ap.add_argument("--backend", choices=["nccl", "gloo"], default="nccl", help="gloo: CPU rehearsal of the multi-rank path (needs --rehearsal-tiles)")
     ap.add_argument("--rehearsal-tiles", default=None, help="directory with tile_<rank>.npy (rows x W x 4 float32): used INSTEAD of rendering")
     ap.add_argument("--dump-frame", default=None, help="rank 0 writes the last gathered frame here (.npy)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 writes what every timed renderer returned for its last timed frame to DIR/<renderer>_<output>.npy "
+                         "(float32 / float64, at most 64 MB in all: a fixed, seeded sample of pixels where the full frames do not fit)")
     ap.add_argument("--dump-pmc", default=None, help="write the raw counter sums of the live --pmc passes here (JSON; profiles/r03_pmc_bench.json is one)")
     ap.add_argument("--pmc-child", default=None, help=argparse.SUPPRESS)  # comma-separated renderers: one untimed frame each, the process rocprofv3 wraps
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    return args
 
 
 # ---- the launcher: N > 1 without an external one ----------------------------------------------------------------------------------
@@ -157,9 +165,6 @@ def main() -> int:
         sys.stdout.flush()
         _JSON_FD = os.dup(1)
         os.dup2(2, 1)
-    # HIP serves streams from GPU_MAX_HW_QUEUES hardware queues (4 by default): the per-bounce renderers' three lane streams, the frame's stream
-    # and torch's own would share them and run one after the other (rt_frame.hip: wf_stream_lanes). Before torch or the library touch HIP:
-    os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
     if args.pmc_child:
         return pmc_child(args)
     if args.stats_child:
@@ -247,6 +252,7 @@ def main() -> int:
         cam = Camera.for_scene(sd, (W, H))
 
     last_buffer = [0]  # the strip buffer of the last frame rendered (rank 0's gathered frame lives in that FrameGatherer)
+    outputs = {}       # --dump-outputs: {renderer: {output: array}} of each renderer's last timed frame (rank 0)
 
     def make_renderer(name):
         cls = MegakernelRenderer if name == "megakernel" else WavefrontRenderer
@@ -270,7 +276,7 @@ def main() -> int:
         NB = len(fgs)
         if rs:
             assert fg.rows == rs[0].local_rows
-        tot = {"rays": 0, "hot_ms": 0.0, "hot_launches": 0, "dev_ms": 0.0, "gather_s": 0.0, "kernel_ms": {}, "kernels": {}, "lanes": 0}
+        tot = {"rays": 0, "last_rays": 0, "hot_ms": 0.0, "hot_launches": 0, "dev_ms": 0.0, "gather_s": 0.0, "kernel_ms": {}, "kernels": {}, "lanes": 0}
 
         def collect(k, b):
             """wait for renderer k's frame in strip buffer b, START its exchange (gather of the per-GPU strip buffers; the de-interleave on
@@ -294,6 +300,7 @@ def main() -> int:
             fgs[b].gather_begin()
             tot["gather_s"] += time.perf_counter() - t
             tot["rays"] += rays
+            tot["last_rays"] = rays
 
         def run(n):
             """n frames; with --frames-in-flight F > 1 frame i+1..i+F-1 are already enqueued (each in its own renderer and
@@ -326,6 +333,12 @@ def main() -> int:
         barrier()
         elapsed = time.perf_counter() - t0
         rows = fg.rows
+        dump = args.dump_outputs and rank == 0 and name not in outputs  # (not again in the informational two-frames leg)
+        if dump:  # the last timed frame, before anything below renders into the same buffers
+            last = fgs[last_buffer[0]]
+            outputs[name] = {"rgba_f32": last.frame.cpu().numpy()}
+            if world == 1:  # the unorm8 image stays on the rank that rendered it: with one rank it is the whole frame's
+                outputs[name]["rgba_u8"] = last.local_u8[:rows].cpu().numpy()
         kernel_frames = args.steps
         if rs and name.startswith("wavefront_per_bounce"):  # the per-kernel durations: one profiled frame outside the timed region
             rs[0].set_profiling(True)
@@ -339,11 +352,14 @@ def main() -> int:
         if use_dist:
             mx = torch.tensor([elapsed], dtype=torch.float64, device=dev)
             dist.all_reduce(mx, op=dist.ReduceOp.MAX)
-            sm = torch.tensor([float(tot["rays"])], dtype=torch.float64, device=dev)
+            sm = torch.tensor([float(tot["rays"]), float(tot["last_rays"])], dtype=torch.float64, device=dev)
             dist.all_reduce(sm, op=dist.ReduceOp.SUM)
             each = [torch.zeros(1, dtype=torch.float64, device=dev) for _ in range(world)]
             dist.all_gather(each, torch.tensor([own_ms], dtype=torch.float64, device=dev))
             elapsed, rays_all, per_rank_ms = float(mx[0]), float(sm[0]), [round(float(e[0]), 3) for e in each]
+            tot["last_rays"] = float(sm[1])
+        if dump:
+            outputs[name]["rays"] = np.array([tot["last_rays"]], dtype=np.float64)
         res = {"renderer": name, "value": round(rays_all / elapsed / 1e6, 3), "unit": "Mrays/s",
                "ms_per_step": round(elapsed / args.steps * 1e3, 3), "rays_per_frame": int(rays_all / args.steps),
                "device_ms_per_step": round(tot["dev_ms"] / args.steps, 3),
@@ -418,6 +434,8 @@ def main() -> int:
             out["cpu_baseline"] = cpu_baseline(sd, W, H, args.depth, args.cpu_spp, best["renderer"])
         if args.dump_frame:
             np.save(args.dump_frame, fgs[last_buffer[0]].frame.cpu().numpy())
+        if args.dump_outputs:
+            write_outputs(Path(args.dump_outputs), outputs)
         sys.stdout.flush()
         emit(json.dumps(out))
     if scene is not None:
@@ -425,6 +443,33 @@ def main() -> int:
     if use_dist:
         dist.destroy_process_group()
     return 0
+
+
+DUMP_BYTES = 64_000_000       # --dump-outputs: at most this many bytes of arrays in all
+DUMP_SAMPLE_PIXELS = 1 << 18  # pixels per frame kept where the full frames do not fit (1080p: one in eight), the same for every renderer
+DUMP_SEED = 1234
+
+
+def write_outputs(directory: Path, outputs: dict) -> None:
+    """--dump-outputs: DIR/<renderer>_rgba_f32.npy (the gathered fp32 frame), DIR/<renderer>_rgba_u8.npy (the unorm8 image, as float32; one
+    rank only) and DIR/<renderer>_rays.npy (rays traced in the frame, all ranks, float64). Frames are (H, W, 4) when every renderer's fit in
+    DUMP_BYTES together; otherwise each is cut to the same DUMP_SAMPLE_PIXELS pixels, a seeded choice written as DIR/pixel_index.npy
+    (row-major pixel numbers, float64), and the arrays are (DUMP_SAMPLE_PIXELS, 4)."""
+    import numpy as np
+    directory.mkdir(parents=True, exist_ok=True)
+    frames = [a for outs in outputs.values() for k, a in outs.items() if k != "rays"]
+    index = None
+    if sum(a.size * 4 for a in frames) > DUMP_BYTES:
+        n_pixels = frames[0].shape[0] * frames[0].shape[1]
+        index = np.sort(np.random.default_rng(DUMP_SEED).choice(n_pixels, size=min(DUMP_SAMPLE_PIXELS, n_pixels), replace=False))
+        np.save(directory / "pixel_index.npy", index.astype(np.float64))
+    for name, outs in outputs.items():
+        for k, a in outs.items():
+            if k != "rays":
+                a = a.astype(np.float32)
+                if index is not None:
+                    a = a.reshape(-1, a.shape[-1])[index]
+            np.save(directory / f"{name}_{k}.npy", a)
 
 
 def shared_scene(args, rank, world, use_dist):

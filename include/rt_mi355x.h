@@ -217,8 +217,8 @@ int rt_renderer_set_russian_roulette(rt_renderer* r, uint32_t start_bounce);
  *   samples_per_launch  samples of a pixel one k_wf_finish launch renders. 0 = all of them: ONE launch per frame (default).
  *   stream_lanes        interleaved sub-tiles rendered on HIP streams of their own. 0 = automatic (1 for the one-launch
  *                       schedule, 3 for a launch or launch pair per bounce all the way down, 2 otherwise). HIP serves streams from
- *                       GPU_MAX_HW_QUEUES hardware queues (default 4). The library never changes the environment: the HOST sets the
- *                       variable (8) before its first HIP call; the library reads it once, when the process's first renderer is
+ *                       GPU_MAX_HW_QUEUES hardware queues (default 4). The library never changes the environment: a HOST may set the
+ *                       variable before its first HIP call; the library reads it once, when the process's first renderer is
  *                       created, and resolves an automatic lane count down to lanes + 2 <= queues (rt_stats.hw_queues / .stream_lanes).
  *                       Renderers of one device share their lane streams: drive them from one host thread.
  *   requeue             with samples_per_launch > 1: 1 = a pixel between two samples goes through a device-wide dynamic queue

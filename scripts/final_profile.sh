@@ -10,7 +10,6 @@
 # usage: bash scripts/final_profile.sh [part ...]   (parts: bench ktrace tables tilepmc stats misc; default: all)
 set -e
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-export GPU_MAX_HW_QUEUES=8
 out=gpurun_out/r05/final; mkdir -p $out
 parts=${@:-bench ktrace tables tilepmc stats misc}
 for part in $parts; do case $part in

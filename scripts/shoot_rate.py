@@ -1,13 +1,11 @@
 """The per-bounce fused kernel (SHOOT: k_wf_finish limited to one bounce, one launch per sample and bounce) against the number of rays a launch holds
 (the pipeline is bound by launch granularity, not by its kernels): the atrium at depth 10, 8 spp, at frame sizes from 960x540 to
 7680x4320 — rays per launch, Mrays/s, and the one-launch schedule of the same renderer beside it.   usage: shoot_rate.py [spp]"""
-import os
 import sys
 from pathlib import Path
 
 REPO = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(REPO)); sys.path.insert(0, str(REPO / "sycl-ray-tracer_amd"))
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 from rtamd import abi, scenes
 from rtamd.renderer import Camera, Scene, WavefrontRenderer
 

@@ -1,13 +1,11 @@
 """Pixel slices (rt_schedule::pixel_slices) on 1/N tiles of the bench frame: ms, Mrays/s, the slice count that ran and a digest of the fp32 tile
 (every setting must render the same bits).   usage: slice_probe.py [worlds, e.g. 1,2,4,8] [settings, e.g. 0,-1,2,3,4,8] [spp] [mega|wave]"""
 import hashlib
-import os
 import sys
 from pathlib import Path
 
 REPO = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(REPO)); sys.path.insert(0, str(REPO / "sycl-ray-tracer_amd"))
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 from rtamd import scenes
 from rtamd.renderer import Camera, MegakernelRenderer, Scene, WavefrontRenderer
 

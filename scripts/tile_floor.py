@@ -2,13 +2,11 @@
 1/32, 1/64 — are ONE generation of pixel chains on ever fewer waves per SIMD (4, 2, 2 on 150 CUs, 2 on 75 CUs): the time of the small tiles is the time
 of the frame's longest pixel chains with (nearly) a SIMD to themselves. With RT_KERNEL_STATS=1 the kernel reports cycles per wave step and the wave
 residency (mean / max).   usage: tile_floor.py [SPP] [worlds]"""
-import os
 import sys
 from pathlib import Path
 
 REPO = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(REPO)); sys.path.insert(0, str(REPO / "sycl-ray-tracer_amd"))
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 from rtamd import scenes
 from rtamd.renderer import Camera, MegakernelRenderer, Scene
 

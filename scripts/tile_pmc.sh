@@ -5,7 +5,6 @@
 set -e
 TAG=${1:-tile}; R=${2:-mega}; WORLDS=${3:-"8 1"}
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-export GPU_MAX_HW_QUEUES=8
 O=gpurun_out/r05/pmc_$TAG
 mkdir -p $O
 for WORLD in $WORLDS; do

@@ -2,13 +2,11 @@
    usage: tile_scaling.py SPP [mega|wave] [worlds, default 1,2,4,8] [frames in flight, default 1,2]
 With F = 2 frames in flight (two renderers, each with its own tile buffers; rt_render_frame_begin / _end) the figure is the time per frame of a
 steady stream of frames — what a render farm of N GPUs sees — not one frame's latency."""
-import os
 import sys
 from pathlib import Path
 
 REPO = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(REPO)); sys.path.insert(0, str(REPO / "sycl-ray-tracer_amd"))
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 import time
 
 from rtamd import abi, scenes

@@ -98,8 +98,8 @@ bool wf_one_launch(const rt_renderer* r) { return r->sched.samples_per_launch ==
 // The frame's stream, three lane streams and the host framework's own stream are five: two lanes then share a queue and their launches run one
 // after the other (measured: the split pipeline on three lanes 314 ms per frame with 4 queues, 191 ms with 8). The library never touches the
 // process environment (round 3 set the variable from a constructor: a side effect of dlopen, and void when HIP was already up). It READS what the
-// host configured when a renderer is created, and resolves an automatic lane count down to what the queues can serve: lanes + 2 <= queues. The
-// host (bench.py, the raytracer CLI) sets GPU_MAX_HW_QUEUES=8 itself before HIP starts; rt_stats reports both numbers.
+// host configured when a renderer is created, and resolves an automatic lane count down to what the queues can serve: lanes + 2 <= queues.
+// bench.py, the raytracer CLI and the tests leave the variable as the environment has it; rt_stats reports both numbers.
 uint32_t hw_queues_from_env() { // read ONCE per process, at the library's first renderer: HIP latched the value at its own initialisation, and a
     static const uint32_t queues = [] { // host that changes the variable later must not make the library report queues HIP does not serve
         const char* e = std::getenv("GPU_MAX_HW_QUEUES");

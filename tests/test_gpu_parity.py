@@ -28,6 +28,21 @@ RMSE_TOL = 1e-4  # north-star tolerance; the tests below demand 0 and report the
 KINDS = [(MegakernelRenderer, abi.RT_RENDERER_MEGAKERNEL), (WavefrontRenderer, abi.RT_RENDERER_WAVEFRONT)]
 
 
+def _hw_queues() -> int:
+    """GPU_MAX_HW_QUEUES as the library reads it (rt_frame.hip: hw_queues_from_env): a positive number, else HIP's default of 4."""
+    try:
+        v = int(os.environ.get("GPU_MAX_HW_QUEUES", ""))
+    except ValueError:
+        v = 0
+    return v if v > 0 else 4
+
+
+HW_QUEUES = _hw_queues()
+# the automatic lane count of a launch (pair) per bounce all the way down, or of one fused kernel per bounce: 3, resolved down to
+# lanes + 2 <= queues (rt_frame.hip: wf_stream_lanes)
+PER_BOUNCE_LANES = 3 if HW_QUEUES >= 5 else 2
+
+
 @pytest.fixture(scope="module")
 def gpu(rtlib):
     n = rtlib.rt_device_count()
@@ -448,9 +463,11 @@ def test_wavefront_schedule_knobs_keep_the_frame(gpu_scenes, oracle, sched):
         back = r.get_schedule()
         assert all(getattr(back, k) == int(v) for k, v in sched.items())
         got = r.render_frame(cam)
-        # automatic: 1 for the one-launch schedule, 3 for a launch (pair) per bounce all the way down or one fused kernel per bounce, else 2
+        # automatic: 1 for the one-launch schedule, PER_BOUNCE_LANES for a launch (pair) per bounce all the way down or one fused kernel per
+        # bounce, else 2
         lanes = sched.get("stream_lanes", 0) or (1 if sched.get("samples_per_launch", 0) == 0 and sched.get("finish_depth", 0) == 0
-                                                else 3 if sched.get("fused_bounce") or sched.get("finish_depth", 0) >= depth else 2)
+                                                else PER_BOUNCE_LANES if sched.get("fused_bounce") or sched.get("finish_depth", 0) >= depth else 2)
+        assert got.hw_queues == HW_QUEUES
         assert got.stream_lanes == lanes and got.finish_depth == min(sched.get("finish_depth", 0), depth)
         assert got.kernels["wf_init"] == got.kernels["wf_resolve"] == lanes
         fused = bool(sched.get("fused_bounce"))  # one SHOOT launch per bounce instead of the EXTEND + SHADE pair
@@ -479,7 +496,7 @@ def test_schedule_environment_shim_maps_onto_the_api(dev_scenes, gpu_scenes, ora
     w, h, depth, spp = 96, 64, 6, 4
     cam = Camera.for_scene(sd, (w, h))
     f, b, rays = _oracle_frame(oracle, sd, w, h, abi.RT_RENDERER_WAVEFRONT, depth, spp)
-    cases = [({"RT_WF_FINISH_DEPTH": "99", "RT_WF_REORDER": "1"}, dict(finish_depth=99, reorder=1), ("wf_shade_reorder", 3 * spp * depth)),
+    cases = [({"RT_WF_FINISH_DEPTH": "99", "RT_WF_REORDER": "1"}, dict(finish_depth=99, reorder=1), ("wf_shade_reorder", PER_BOUNCE_LANES * spp * depth)),
              ({"RT_WF_STREAMS": "3"}, dict(stream_lanes=3, samples_per_launch=1), ("wf_finish", 3 * spp)),
              ({"RT_WF_REQUEUE": "0"}, dict(requeue=0, samples_per_launch=1), ("wf_finish", 2 * spp)),
              ({"RT_WF_SAMPLES_PER_LAUNCH": "2"}, dict(samples_per_launch=2), ("wf_finish_requeue", 2 * 2)),
@@ -541,10 +558,11 @@ def test_failed_reallocation_leaves_a_renderer_that_says_so(dev_scenes, oracle, 
 
 
 def test_library_loaded_after_hip_is_up_resolves_its_stream_lanes(gpu_scenes, oracle):
-    """A host that initialised HIP before it loaded the library and never set GPU_MAX_HW_QUEUES has HIP's four hardware queues. The library
-    does not touch the environment (round 3 did, from a constructor): it reads the host's setting, resolves the per-bounce schedules'
-    automatic three stream lanes down to two (lanes + 2 <= queues), says so in rt_stats, and renders the same frame. Run in a child process
-    (this one has its queue count fixed by conftest.py): torch brings HIP up first, THEN the library is loaded."""
+    """A host that initialised HIP before it loaded the library, with the hardware queues its environment gives it (HIP's four when
+    GPU_MAX_HW_QUEUES is not set). The library does not touch the environment (round 3 did, from a constructor): it reads the host's
+    setting, resolves the per-bounce schedules' automatic three stream lanes down to what the queues serve (lanes + 2 <= queues), says so in
+    rt_stats, and renders the same frame. Run in a child process (this one has loaded the library already): torch brings HIP up first,
+    THEN the library is loaded."""
     gs = gpu_scenes("cornell")
     sd = gs.desc
     w, h, depth, spp = 96, 64, 6, 4
@@ -567,16 +585,15 @@ for name, kw in (('split', dict(finish_depth=abi.RT_SCHED_ALL_BOUNCES)), ('fused
     r.close()
 print('RESULT ' + json.dumps(out))
 """
-    env = {k: v for k, v in os.environ.items() if k != "GPU_MAX_HW_QUEUES"}
-    p = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=600)
+    p = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     out = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("RESULT ")][0][7:])
     want_f32, want_u8 = hashlib.sha1(f.tobytes()).hexdigest(), hashlib.sha1(b.tobytes()).hexdigest()
     for name, o in out.items():
-        assert o["queues"] == 4, (name, o)                       # what the library saw: HIP's default
-        assert o["lanes"] == (3 if name == "asked3" else 2), (name, o)  # automatic: resolved down; explicit: the caller's business
+        assert o["queues"] == HW_QUEUES, (name, o)               # what the library saw: the host's setting, or HIP's default
+        assert o["lanes"] == (3 if name == "asked3" else PER_BOUNCE_LANES), (name, o)  # automatic: resolved down; explicit: the caller's business
         assert (o["rays"], o["f32"], o["u8"]) == (rays, want_f32, want_u8), (name, o)
-    assert out["split"]["extend"] == 2 * spp * depth and out["fused"]["shoot"] == 2 * spp * depth
+    assert out["split"]["extend"] == PER_BOUNCE_LANES * spp * depth and out["fused"]["shoot"] == PER_BOUNCE_LANES * spp * depth
 
 
 @pytest.mark.parametrize("env", [{"RT_WF_SHOOT_TAIL": "0"}, {"RT_WF_SHOOT_TAIL": "0", "RT_WF_SHOOT_CHUNK": "32"}, {"RT_WF_SHOOT_STATIC_PCT": "0", "RT_WF_SHOOT_CHUNK": "16"},
@@ -620,7 +637,8 @@ def test_wavefront_finish_depth_keeps_the_frame(gpu_scenes, oracle, finish_depth
         r.set_schedule(finish_depth=finish_depth)
         got = r.render_frame(cam)
         d0 = min(finish_depth, depth)
-        lanes = 1 if finish_depth == 0 else 3 if finish_depth >= depth else 2
+        lanes = 1 if finish_depth == 0 else PER_BOUNCE_LANES if finish_depth >= depth else 2
+        assert got.hw_queues == HW_QUEUES
         assert got.finish_depth == d0 and got.stream_lanes == lanes
         assert got.kernels["wf_extend"] == got.kernels["wf_shade"] == lanes * spp * d0
         assert got.kernels["wf_finish"] == (0 if d0 == depth else lanes * (spp if d0 else 1))

@@ -88,8 +88,9 @@ def test_bench_launches_its_own_ranks(tmp_path, oracle, world):
         np.save(tmp_path / f"tile_{rank}.npy", f)
     full, _, _ = sc.render(cam, 1, 4, 2)
     out = tmp_path / "frame.npy"
+    dump = tmp_path / "outputs"
     p = _bench(["--gpus", world, "--steps", 3, "--warmup", 1, "--width", w, "--height", h, "--backend", "gloo", "--rehearsal-tiles", tmp_path, "--dump-frame", out,
-                "--detail", 1])
+                "--dump-outputs", dump, "--detail", 1])
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-2000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, p.stdout
@@ -104,6 +105,48 @@ def test_bench_launches_its_own_ranks(tmp_path, oracle, world):
     assert len(d["setup_s_per_rank"]) == world and all(r["scene_s"] > 0 for r in d["setup_s_per_rank"])
     # (3 frames through 3 strip buffers with the exchange of frame i overlapping frame i + 1: the last frame's gather is the dumped one)
     np.testing.assert_array_equal(np.load(out), full)
+    # --dump-outputs: the same frame as float32 (small enough to be whole) and the rays of the last frame over all ranks (none: tiles from
+    # files); the unorm8 image stays on the ranks
+    assert sorted(f.name for f in dump.iterdir()) == ["rehearsal_rays.npy", "rehearsal_rgba_f32.npy"]
+    f32, rays = np.load(dump / "rehearsal_rgba_f32.npy"), np.load(dump / "rehearsal_rays.npy")
+    assert f32.dtype == np.float32 and rays.dtype == np.float64
+    np.testing.assert_array_equal(f32, full)
+    np.testing.assert_array_equal(rays, [0.0])
+
+
+def test_bench_dump_outputs_stay_within_their_budget(tmp_path):
+    """--dump-outputs writes float32 / float64 only and at most 64 MB in all: frames too large together are cut to one seeded sample of
+    pixels, the same for every renderer and every run; `--steps` below one is refused (ms_per_step divides by it)."""
+    sys.path.insert(0, str(REPO))
+    import bench
+    h, w = 1080, 1920
+    rng = np.random.default_rng(5)
+    frame = rng.random((h, w, 4), dtype=np.float32)
+    image = rng.integers(0, 256, (h, w, 4), dtype=np.uint8)
+    outputs = {name: {"rgba_f32": frame, "rgba_u8": image, "rays": np.array([1e9 + 1.0])} for name in bench.RENDERERS}
+    for run in ("a", "b"):
+        bench.write_outputs(tmp_path / run, outputs)
+    files = sorted((tmp_path / "a").iterdir())
+    assert sum(f.stat().st_size for f in files) <= bench.DUMP_BYTES
+    index = np.load(tmp_path / "a" / "pixel_index.npy")
+    assert index.dtype == np.float64 and index.size == bench.DUMP_SAMPLE_PIXELS and (np.diff(index) > 0).all() and index[-1] < h * w
+    pix = index.astype(np.int64)
+    for name in bench.RENDERERS:
+        f32, u8 = np.load(tmp_path / "a" / f"{name}_rgba_f32.npy"), np.load(tmp_path / "a" / f"{name}_rgba_u8.npy")
+        assert f32.dtype == u8.dtype == np.float32
+        np.testing.assert_array_equal(f32, frame.reshape(-1, 4)[pix])
+        np.testing.assert_array_equal(u8, image.reshape(-1, 4)[pix])
+        assert np.load(tmp_path / "a" / f"{name}_rays.npy").tolist() == [1e9 + 1.0]
+    for f in files:  # the same arguments, the same files
+        assert (tmp_path / "b" / f.name).read_bytes() == f.read_bytes()
+    small = {"megakernel": {"rgba_f32": frame[:36, :64], "rgba_u8": image[:36, :64], "rays": np.array([7.0])}}
+    bench.write_outputs(tmp_path / "small", small)  # whole frames where they fit
+    np.testing.assert_array_equal(np.load(tmp_path / "small" / "megakernel_rgba_f32.npy"), frame[:36, :64])
+    assert not (tmp_path / "small" / "pixel_index.npy").exists()
+    for bad in (["--steps", "0"], ["--warmup", "-1"]):
+        with pytest.raises(SystemExit):
+            bench.parse_args(bad)
+    assert bench.parse_args(["--steps", "7"]).steps == 7
 
 
 def test_bench_launcher_reports_a_failing_rank(tmp_path):

@@ -1,12 +1,20 @@
 """The loader's image path against the REFERENCE's own decoder and resizer.
 
-oracle/_ref/libref_stb.so is built from the reference's vendored stb_image.h / stb_image_resize2.h where they lie
-under /root/reference (`make -C oracle ref`; recipe and wrapper in oracle/, binary git-ignored). It does exactly what
+oracle/_ref/libref_stb.so is built from the reference's vendored stb_image.h / stb_image_resize2.h where the reference's
+sources are at hand (`make -C oracle ref`; recipe and wrapper in oracle/, binary git-ignored). It does exactly what
 the reference does with an embedded glTF image: stbi_load_from_memory(..., 4) (deps/include/tiny_gltf.h:2603-2634)
-and stbir_resize_uint8_srgb(..., 512, 512, 0, STBIR_RGBA) (src/image_manager.hpp:52-62). Skipped where the library
-was never built."""
+and stbir_resize_uint8_srgb(..., 512, 512, 0, STBIR_RGBA) (src/image_manager.hpp:52-62).
+
+Where that library was never built, the tests compare against what it returned for the same inputs, stored in
+tests/golden/ref_stb/ref_stb.npz (tests/golden/make_ref_stb.py): every decoded image by its SHA-256, every baked layer by its
+SHA-256 and a fixed sample of its texels, each under the SHA-256 of its input. An input the stored vectors do not hold
+(an image encoder of another version wrote other bytes) is skipped. Where the library is built, the stored vectors are
+checked against it."""
 import ctypes as C
+import hashlib
 import io
+import os
+import zlib
 from pathlib import Path
 
 import numpy as np
@@ -17,29 +25,140 @@ from rtamd import abi
 REPO = Path(__file__).resolve().parent.parent
 REF = REPO / "oracle" / "_ref" / "libref_stb.so"
 HOST = REPO / "sycl-ray-tracer_amd" / "host" / "build" / "librt_host.so"
+STORED = Path(__file__).resolve().parent / "golden" / "ref_stb" / "ref_stb.npz"  # (its own directory: tests/golden/*.npz are the render fixtures)
+RECORD_ENV = "RT_REF_STB_RECORD"  # set by tests/golden/make_ref_stb.py: the file the live library's results are written to
+LAYER = (512, 512, 4)
+LAYER_TEXELS = np.sort(np.random.default_rng(512).choice(512 * 512, size=4096, replace=False))  # the stored sample of a baked layer
 
-pytestmark = pytest.mark.skipif(not REF.exists(), reason="oracle/_ref/libref_stb.so not built (no /root/reference)")
+
+def _sha(*parts) -> bytes:
+    h = hashlib.sha256()
+    for p in parts:
+        h.update(p if isinstance(p, bytes) else np.ascontiguousarray(p).tobytes())
+    return h.digest()
+
+
+class StoredImage:
+    """A decoded image as the stored vectors keep it: shape and SHA-256 of the RGBA8 texels."""
+    def __init__(self, shape, digest):
+        self.shape, self.digest = tuple(int(s) for s in shape), bytes(digest)
+
+
+class StoredLayer:
+    """A baked 512x512 layer as the stored vectors keep it: SHA-256 of the layer and its texels at LAYER_TEXELS."""
+    def __init__(self, digest, texels):
+        self.digest, self.texels = bytes(digest), np.asarray(texels, np.uint8)
+
+
+class Reference:
+    """The reference's decoder and resizer: live (oracle/_ref/libref_stb.so) or as stored in tests/golden/ref_stb/ref_stb.npz."""
+
+    def __init__(self):
+        self.lib = C.CDLL(str(REF)) if REF.exists() else None
+        self.recording = bool(os.environ.get(RECORD_ENV))
+        if self.recording and self.lib is None:
+            raise RuntimeError(f"{RECORD_ENV} needs {REF} (make -C oracle ref)")
+        if self.lib is not None:
+            self.lib.ref_decode_rgba8.argtypes = [C.POINTER(C.c_uint8), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_uint8), C.c_size_t]
+            self.lib.ref_resize_to_layer.argtypes = [C.POINTER(C.c_uint8), C.c_int, C.c_int, C.POINTER(C.c_uint8)]
+        self.images, self.layers = {}, {}
+        if STORED.exists() and not self.recording:
+            z = np.load(STORED)
+            for k, shape, d in zip(z["image_in"], z["image_shape"], z["image_sha"]):
+                self.images[k.tobytes()] = None if shape[0] < 0 else StoredImage(shape, d.tobytes())
+            for k, d, t in zip(z["layer_in"], z["layer_sha"], z["layer_texels"]):
+                self.layers[k.tobytes()] = StoredLayer(d.tobytes(), t)
+
+    def _stored(self, table, key, what):
+        if key not in table:
+            pytest.skip(f"oracle/_ref/libref_stb.so not built, and tests/golden/ref_stb/ref_stb.npz holds no {what} for these input bytes")
+        return table[key]
+
+    def _keep(self, table, key, seen, what):
+        """the live result: recorded, or checked against the stored one"""
+        if self.recording:
+            table[key] = seen
+        elif key in table:
+            kept = table[key]
+            same = (kept is None) == (seen is None) and (seen is None or kept.digest == seen.digest)
+            assert same and (seen is None or not isinstance(seen, StoredImage) or kept.shape == seen.shape), \
+                f"tests/golden/ref_stb/ref_stb.npz disagrees with the reference's {what}"
+
+    def _live_layer(self, key, img):
+        img = np.ascontiguousarray(img)
+        out = np.zeros(LAYER, np.uint8)
+        assert self.lib.ref_resize_to_layer(abi.u8ptr(img), img.shape[1], img.shape[0], abi.u8ptr(out)) == 0
+        self._keep(self.layers, key, StoredLayer(_sha(out), out.reshape(-1, 4)[LAYER_TEXELS]), "resizer")
+        return out
+
+    def decode(self, blob: bytes):
+        """stbi_load_from_memory(blob, 4): (h, w, 4) uint8 (a StoredImage without the library), or None where it refuses the blob."""
+        key = _sha(b"decode", blob)
+        if self.lib is None:
+            return self._stored(self.images, key, "decoded image")
+        data = np.frombuffer(blob, np.uint8)
+        w, h = C.c_int(), C.c_int()
+        out = np.zeros(2048 * 2048 * 4, np.uint8)
+        rc = self.lib.ref_decode_rgba8(abi.u8ptr(data), data.size, C.byref(w), C.byref(h), abi.u8ptr(out), out.size)
+        img = None if rc != 0 else out[: w.value * h.value * 4].reshape(h.value, w.value, 4).copy()
+        self._keep(self.images, key, None if img is None else StoredImage(img.shape, _sha(img)), "decoder")
+        return img
+
+    def layer(self, img: np.ndarray):
+        """stbir_resize_uint8_srgb of an (h, w, 4) uint8 image to one 512x512 layer (a StoredLayer without the library)."""
+        key = _sha(b"layer", np.array(img.shape, np.int64), img)
+        if self.lib is None:
+            return self._stored(self.layers, key, "baked layer")
+        return self._live_layer(key, img)
+
+    def decoded_layer(self, blob: bytes):
+        """The layer the reference bakes from an embedded image: decoded, then resized (a StoredLayer without the library)."""
+        key = _sha(b"decoded_layer", blob)
+        if self.lib is None:
+            return self._stored(self.layers, key, "baked layer")
+        img = self.decode(blob)
+        assert img is not None
+        return self._live_layer(key, img)
+
+    def save(self, path):
+        images, layers = list(self.images.items()), list(self.layers.items())
+        np.savez_compressed(
+            path,
+            image_in=np.array([np.frombuffer(k, np.uint8) for k, _ in images], np.uint8).reshape(-1, 32),
+            image_shape=np.array([(-1, -1, -1) if v is None else v.shape for _, v in images], np.int32).reshape(-1, 3),
+            image_sha=np.array([np.zeros(32, np.uint8) if v is None else np.frombuffer(v.digest, np.uint8) for _, v in images], np.uint8).reshape(-1, 32),
+            layer_in=np.array([np.frombuffer(k, np.uint8) for k, _ in layers], np.uint8).reshape(-1, 32),
+            layer_sha=np.array([np.frombuffer(v.digest, np.uint8) for _, v in layers], np.uint8).reshape(-1, 32),
+            layer_texels=np.array([v.texels for _, v in layers], np.uint8).reshape(-1, LAYER_TEXELS.size, 4))
+
+
+def assert_same_image(ours, ref):
+    """ours is texel for texel the reference's decode (of a StoredImage: the same shape and SHA-256)."""
+    assert ours is not None and ref is not None
+    if isinstance(ref, StoredImage):
+        assert (ours.shape, _sha(ours)) == (ref.shape, ref.digest), f"differs from the reference's decode, shape {ref.shape} (stored SHA-256)"
+    else:
+        np.testing.assert_array_equal(ours, ref)
+
+
+def layer_difference(ours, ref):
+    """|ours - reference| of a baked layer, texel channel by texel channel: everywhere, or at LAYER_TEXELS for a StoredLayer; and whether
+    the two layers are identical as a whole."""
+    if isinstance(ref, StoredLayer):
+        return np.abs(ours.reshape(-1, 4)[LAYER_TEXELS].astype(np.int32) - ref.texels.astype(np.int32)), _sha(ours) == ref.digest
+    d = np.abs(ours.astype(np.int32) - ref.astype(np.int32))
+    return d, bool(d.max() == 0)
 
 
 @pytest.fixture(scope="module")
 def libs(rtlib):
-    ref, host = C.CDLL(str(REF)), C.CDLL(str(HOST))
-    ref.ref_decode_rgba8.argtypes = [C.POINTER(C.c_uint8), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_uint8), C.c_size_t]
-    ref.ref_resize_to_layer.argtypes = [C.POINTER(C.c_uint8), C.c_int, C.c_int, C.POINTER(C.c_uint8)]
+    ref, host = Reference(), C.CDLL(str(HOST))
     host.rth_last_error.restype = C.c_char_p
     host.rth_decode_image.argtypes = [C.POINTER(C.c_uint8), C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint8), C.c_size_t]
     host.rth_resize_to_layer.argtypes = [C.POINTER(C.c_uint8), C.c_uint32, C.c_uint32, C.POINTER(C.c_uint8)]
-    return ref, host
-
-
-def ref_decode(ref, blob: bytes):
-    data = np.frombuffer(blob, np.uint8)
-    w, h = C.c_int(), C.c_int()
-    out = np.zeros(2048 * 2048 * 4, np.uint8)
-    rc = ref.ref_decode_rgba8(abi.u8ptr(data), data.size, C.byref(w), C.byref(h), abi.u8ptr(out), out.size)
-    if rc != 0:
-        return None
-    return out[: w.value * h.value * 4].reshape(h.value, w.value, 4).copy()
+    yield ref, host
+    if ref.recording:
+        ref.save(os.environ[RECORD_ENV])
 
 
 def our_decode(host, blob: bytes):
@@ -65,13 +184,13 @@ def _picture(rng, h, w):
 def test_png_decoder_equals_the_references(libs, mode, size):
     from PIL import Image
     ref, host = libs
-    rng = np.random.default_rng(hash((mode, size)) & 0xFFFF)
+    rng = np.random.default_rng(zlib.crc32(f"{mode} {size}".encode()) & 0xFFFF)  # (hash() of a str differs from process to process)
     img = rng.integers(0, 256, size + (4,), dtype=np.uint8)
     buf = io.BytesIO()
     Image.fromarray(img, "RGBA").convert(mode).save(buf, format="PNG")
-    a, r = our_decode(host, buf.getvalue()), ref_decode(ref, buf.getvalue())
+    a, r = our_decode(host, buf.getvalue()), ref.decode(buf.getvalue())
     assert a is not None and r is not None
-    np.testing.assert_array_equal(a, r)
+    assert_same_image(a, r)
 
 
 @pytest.mark.parametrize("name,shape", [("same", (512, 512)), ("half", (1024, 1024)), ("wide", (512, 1024)), ("odd", (200, 300)),
@@ -89,12 +208,11 @@ def test_texture_baker_follows_the_references_resize(libs, name, shape, alpha):
         img[..., 3] = rng.integers(0, 256, shape, dtype=np.uint8)
         img[: max(1, shape[0] // 4), :, 3] = 0  # a fully transparent band
     img = np.ascontiguousarray(img)
-    a, r = np.zeros((512, 512, 4), np.uint8), np.zeros((512, 512, 4), np.uint8)
+    a = np.zeros((512, 512, 4), np.uint8)
     host.rth_resize_to_layer(abi.u8ptr(img), shape[1], shape[0], abi.u8ptr(a))
-    assert ref.ref_resize_to_layer(abi.u8ptr(img), shape[1], shape[0], abi.u8ptr(r)) == 0
-    d = np.abs(a.astype(np.int32) - r.astype(np.int32))
+    d, identical = layer_difference(a, ref.layer(img))
     if shape == (512, 512):
-        assert d.max() == 0
+        assert identical
     else:
         assert d.max() <= 1 and (d > 0).mean() < 0.015
 
@@ -133,11 +251,11 @@ def test_jpeg_decoder_equals_the_references(libs, name, size, opts, grey):
         opts = {k: v for k, v in opts.items() if k != "subsampling"}
     buf = io.BytesIO()
     img.save(buf, format="JPEG", **opts)
-    a, r = our_decode(host, buf.getvalue()), ref_decode(ref, buf.getvalue())
+    a, r = our_decode(host, buf.getvalue()), ref.decode(buf.getvalue())
     assert r is not None
     assert a is not None, host.rth_last_error()
     assert a.shape == (h, w, 4)
-    np.testing.assert_array_equal(a, r)
+    assert_same_image(a, r)
     # and both are the picture PIL decodes, up to the usual decoder-to-decoder differences
     pil = np.asarray(Image.open(io.BytesIO(buf.getvalue())).convert("RGB")).astype(np.int32)
     assert np.abs(a[..., :3].astype(np.int32) - pil).mean() < (1.5 if min(w, h) >= 16 else 8.0)
@@ -193,10 +311,10 @@ def test_interlaced_png_decodes_like_the_references(libs, w, h, c, depth16):
     rng = np.random.default_rng(w * 100 + h + c)
     img = rng.integers(0, 256, (h, w, c), dtype=np.uint8)
     blob = _adam7_png(img, depth16)
-    a, r = our_decode(host, blob), ref_decode(ref, blob)
+    a, r = our_decode(host, blob), ref.decode(blob)
     assert r is not None and r.shape == (h, w, 4)
     assert a is not None, host.rth_last_error()
-    np.testing.assert_array_equal(a, r)
+    assert_same_image(a, r)
     want = np.concatenate([np.repeat(img, 3, -1) if c == 1 else img[..., :3], img[..., 3:4] if c == 4 else np.full((h, w, 1), 255, np.uint8)], -1)
     np.testing.assert_array_equal(a, want)
 
@@ -217,10 +335,10 @@ def test_four_component_jpeg_decodes_like_the_references(libs, transform, opts):
     at = blob.find(b"Adobe")
     assert at > 0 and blob[at + 11] == 0  # APP14: "Adobe", version (2), flags0 (2), flags1 (2), transform
     blob[at + 11] = transform
-    a, r = our_decode(host, bytes(blob)), ref_decode(ref, bytes(blob))
+    a, r = our_decode(host, bytes(blob)), ref.decode(bytes(blob))
     assert r is not None and r.shape == (40, 56, 4)
     assert a is not None, host.rth_last_error()
-    np.testing.assert_array_equal(a, r)
+    assert_same_image(a, r)
 
 
 def test_glb_with_jpeg_textures_bakes_the_references_layers(libs, scene_cache, tmp_path):
@@ -250,11 +368,9 @@ def test_glb_with_jpeg_textures_bakes_the_references_layers(libs, scene_cache, t
         assert im["mimeType"] == "image/jpeg"
         v = js["bufferViews"][im["bufferView"]]
         blob = raw[bin0 + v["byteOffset"]: bin0 + v["byteOffset"] + v["byteLength"]]
-        dec = ref_decode(ref, blob)
+        dec = ref.decode(blob)
         assert dec.shape == (640, 640, 4)
-        want = np.zeros((512, 512, 4), np.uint8)
-        assert ref.ref_resize_to_layer(abi.u8ptr(np.ascontiguousarray(dec)), 640, 640, abi.u8ptr(want)) == 0
-        d = np.abs(layers[i].astype(np.int32) - want.astype(np.int32))
+        d, _ = layer_difference(layers[i], ref.decoded_layer(blob))
         assert d.max() <= 1 and (d > 0).mean() < 0.015
 
 
@@ -269,4 +385,4 @@ def test_png_written_by_the_host_adapter_reads_back_in_the_references_decoder(li
         img[..., 3] = 255
         path = tmp_path / f"o_{w}x{h}.png"
         assert host.rth_write_png(str(path).encode(), w, h, abi.u8ptr(img)) == 0
-        np.testing.assert_array_equal(ref_decode(ref, path.read_bytes()), img)
+        assert_same_image(img, ref.decode(path.read_bytes()))

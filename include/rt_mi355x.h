@@ -233,12 +233,15 @@ int rt_renderer_set_russian_roulette(rt_renderer* r, uint32_t start_bounce);
  *                       compacts the survivors into the next queue — shoot_rays as the reference has it (src/render_wavefront.cpp:222-312)
  *                       — instead of the EXTEND + SHADE pair with its hit-record round trip. reorder / matsort act in k_wf_shade and
  *                       are ignored then.
- *   pixel_slices        MEGAKERNEL renderers (the only field they use). A pixel's samples are a sequential chain (one RNG word), but not
- *                       bound to one lane: the chain is cut into slices of decreasing length, all first slices are rendered, then all
- *                       second ones ..., the pixel's colour sum and RNG word travelling through memory in between, so that the frame
- *                       drains over its last, short slices instead of over whole pixels (bit-identical frame). -1 = automatic (as many
- *                       as the tile's size calls for; one for a tile of at most ~1.25 pixels per resident lane), 0 or 1 = off,
- *                       2 .. 8 = that many. rt_stats.pixel_slices reports what ran.
+ *   pixel_slices        Both renderers (the only field MEGAKERNEL renderers use). A pixel's samples are a sequential chain (one RNG
+ *                       word), but not bound to one lane: the chain is cut into slices of decreasing length, all first slices are
+ *                       rendered, then all second ones ..., the pixel's colour sum and RNG word travelling through memory in between, so
+ *                       that the frame drains over its last, short slices instead of over whole pixels (bit-identical frame). -1 =
+ *                       automatic (as many as the tile's size calls for; one for a tile of at most ~1.25 pixels per resident lane), 0 or
+ *                       1 = off, 2 .. 8 = that many, whatever the tile's size (at most one slice per sample; above 64 samples per unit of
+ *                       2, 4, ... samples). The wavefront renderer slices its one-launch schedule (samples_per_launch 0, finish_depth 0)
+ *                       only, and not with hip_graph, more than one stream lane, or cost_order = 1. rt_stats.pixel_slices reports what
+ *                       ran.
  * Environment: the library reads GPU_MAX_HW_QUEUES (above), RT_PROFILE_KERNELS=1 (rt_renderer_set_profiling at creation) and
  * RT_KERNEL_STATS=1 (the instrumented kernel instantiations; their report goes to stderr) — and nothing else. Sweep knobs and test
  * hooks (RT_WF_*, RT_MEGA_*, RT_BVH_*, RT_INJECT_ALLOC_FAILURE) exist in the developer build only: `make -C csrc dev` ->
@@ -254,7 +257,7 @@ typedef struct rt_schedule {
     int32_t cost_order;
     uint32_t hip_graph;
     uint32_t fused_bounce;
-    int32_t pixel_slices; /* (ABI 8) megakernel */
+    int32_t pixel_slices; /* (ABI 8) both renderers (the wavefront renderer's one-launch schedule) */
 } rt_schedule;
 /* Megakernel renderers accept the call and use pixel_slices only. No frame may be in flight; the tile's queues are re-allocated. */
 int rt_renderer_set_schedule(rt_renderer* r, const rt_schedule* s);
@@ -300,7 +303,7 @@ typedef struct rt_stats {
      * renderer was created, 4 (HIP's default) when unset. The library never changes the environment; an automatic stream-lane count is resolved
      * down to lanes + 2 <= hw_queues (the frame's stream and one stream of the host framework beside the lanes'), see stream_lanes above. */
     uint32_t hw_queues;
-    uint32_t pixel_slices; /* (ABI 8) megakernel: slices a pixel's samples were rendered in (1 = every pixel on one lane) */
+    uint32_t pixel_slices; /* (ABI 8) slices a pixel's samples were rendered in (1 = every pixel on one lane, an empty tile, an unsliced schedule) */
 } rt_stats;
 
 /* == IRenderer::render_frame(camera, scene) (src/render_megakernel.cpp:75-187,

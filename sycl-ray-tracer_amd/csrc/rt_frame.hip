@@ -302,20 +302,24 @@ int alloc_tile_buffers(rt_renderer* r) {
 // as slices shrink by less than G from one to the next — by G / 1.5 here, at most 4, for the spread of the pixels' costs. The frame drains
 // over its LAST slice (about 1/16 of the samples), instead of over a whole pixel.
 //   G <= 1.25 : one slice — nothing is handed out after the first generation, a slice would only wait for the one before it
-//   forced    : rt_schedule::pixel_slices >= 2 slices of that geometry whatever G is (tests, sweeps)
-SliceDev mega_slices(const rt_renderer* r, uint32_t grid, uint32_t n_slots, uint32_t tag0) { // grid: workgroups of kMegaBlock threads the launch keeps resident
-    SliceDev sl{};
-    sl.state = r->d_slice_state, sl.n_slices = 1, sl.tag0 = tag0, sl.wait_cap = kSliceWaitCap;
-    if (const char* e = dev_knob("RT_SLICE_WAIT_CAP")) sl.wait_cap = (uint32_t)std::strtoul(e, nullptr, 10); // tests: give up after that many looks
-    for (uint32_t k = 0; k < kMaxSlices; ++k) sl.bound[k] = r->spp;
-    const int32_t want = r->sched.pixel_slices;
-    const double G = (double)n_slots / ((double)grid * kMegaBlock);
-    if (!r->d_slice_state || want == 0 || want == 1 || r->spp < 2 || (want < 0 && G <= 1.25)) return sl;
+//   forced    : rt_schedule::pixel_slices >= 2 slices of that geometry whatever G is (tests, sweeps; at most one per unit of samples)
+// slice_plan is the geometry alone, (spp, pixel_slices, G) -> slices (the developer build exports it to the CPU tests: rt_dev_slice_plan);
+// mega_slices adds the renderer's side — no state buffer, no slices — and the developer knobs.
+struct SlicePlan {
+    uint32_t n_slices, shift;
+    unsigned long long cuts;
+    uint32_t bound[kMaxSlices]; // as SliceDev::bound
+};
+SlicePlan slice_plan(uint32_t spp, int32_t want, double G) {
+    SlicePlan p{};
+    p.n_slices = 1;
+    for (uint32_t k = 0; k < kMaxSlices; ++k) p.bound[k] = spp;
+    if (want == 0 || want == 1 || spp < 2 || (want < 0 && G <= 1.25)) return p;
     // a slice ends at a multiple of 2^shift samples: the kernel finds the ends in a 64-bit mask, bit k = "a slice ends before sample k << shift"
     uint32_t shift = 0;
-    while (((r->spp - 1u) >> shift) >= 64u) shift++;
-    const uint32_t unit = 1u << shift, units = (r->spp + unit - 1u) / unit; // the last unit may be a short one
-    if (units < 2) return sl;
+    while (((spp - 1u) >> shift) >= 64u) shift++;
+    const uint32_t unit = 1u << shift, units = (spp + unit - 1u) / unit; // the last unit may be a short one
+    if (units < 2) return p;
     const double ratio = std::min(4.0, std::max(1.0, G / 1.5));
     // (measured, atrium 1080p 64 spp, profiles/r05_slice_sweep.txt: slices from 48, 60 on 111.7 ms, from 46, 59, 63 on 112.7, from 56 on 114.9, unsliced
     // 119.9; half the frame: from 32, 48, 56, 60 on 57.4 ms, unsliced 67.0; a quarter: eight equal slices 32.7 ms, unsliced 42.5 — a last slice
@@ -338,16 +342,28 @@ SliceDev mega_slices(const rt_renderer* r, uint32_t grid, uint32_t n_slots, uint
     uint32_t b = 0;
     for (uint32_t i = 0; i + 1 < n; ++i) {
         b += size[i];
-        sl.bound[i] = b * unit; // (< spp: at least one unit follows)
-        sl.cuts |= 1ull << b;
+        p.bound[i] = b * unit; // (< spp: at least one unit follows)
+        p.cuts |= 1ull << b;
     }
-    sl.shift = shift;
-    sl.n_slices = n;
+    p.shift = shift;
+    p.n_slices = n;
+    return p;
+}
+
+SliceDev mega_slices(const rt_renderer* r, uint32_t grid, uint32_t n_slots, uint32_t tag0) { // grid: workgroups of kMegaBlock threads the launch keeps resident
+    SliceDev sl{};
+    sl.state = r->d_slice_state, sl.tag0 = tag0, sl.wait_cap = kSliceWaitCap;
+    if (const char* e = dev_knob("RT_SLICE_WAIT_CAP")) sl.wait_cap = (uint32_t)std::strtoul(e, nullptr, 10); // tests: give up after that many looks
+    const double G = (double)n_slots / ((double)grid * kMegaBlock);
+    const SlicePlan plan = slice_plan(r->spp, r->d_slice_state ? r->sched.pixel_slices : 0, G);
+    sl.n_slices = plan.n_slices, sl.shift = plan.shift, sl.cuts = plan.cuts;
+    for (uint32_t k = 0; k < kMaxSlices; ++k) sl.bound[k] = plan.bound[k];
+    if (sl.n_slices == 1) return sl;
     if (const char* e = dev_knob("RT_MEGA_SLICE_BOUNDS")) { // sweeps: the samples slices 1, 2, ... start with, ascending, e.g. "48,60,63" (shift 0 only)
         sl.cuts = 0, sl.n_slices = 1;
         for (uint32_t k = 0; k < kMaxSlices; ++k) sl.bound[k] = r->spp;
         uint32_t prev = 0;
-        for (const char* p = e; *p && sl.n_slices < kMaxSlices && shift == 0;) {
+        for (const char* p = e; *p && sl.n_slices < kMaxSlices && plan.shift == 0;) {
             const uint32_t v = (uint32_t)std::strtoul(p, const_cast<char**>(&p), 10);
             if (*p == ',') ++p;
             if (v <= prev || v >= r->spp) break;
@@ -635,8 +651,8 @@ int enqueue_frame(rt_renderer* r, const rt_camera* cam, float* d_f32, uint8_t* d
     const SceneDev& S = r->scene->dev;
     LaunchCount launches;
     *n_hot_events = 0;
-    if (r->n_local == 0) {
-        if (stats) stats->launches = 0;
+    if (r->n_local == 0) { // an empty tile (more ranks than strips): no launch, and no pixel to slice
+        if (stats) stats->launches = 0, stats->pixel_slices = 1;
         return RT_OK;
     }
     if (r->kind == RT_RENDERER_MEGAKERNEL) {
@@ -820,7 +836,7 @@ int frame_end(rt_renderer* r, rt_stats* stats) {
                 if (!L.n_local) continue;
                 HIPCHK(hipMemcpy(L.h_counts.data(), L.d_counts, L.h_counts.size() * 4, hipMemcpyDeviceToHost));
                 HIPCHK(hipMemcpy(L.h_extra.data(), L.d_extra, L.h_extra.size() * 8, hipMemcpyDeviceToHost));
-                if (L.h_extra[r->spp]) return fail(RT_ERR_HIP, "k_wf_finish: a queue hand-over stalled or overflowed (internal error word " + std::to_string((unsigned long long)L.h_extra[r->spp]) + ": 1 / 2 dynamic queue, 3 SHOOT's slot allocator, 4 pixel-slice hand-over)");
+                if (L.h_extra[r->spp]) return fail(RT_ERR_HIP, "k_wf_finish: a queue hand-over stalled or overflowed (internal error word " + std::to_string((unsigned long long)L.h_extra[r->spp]) + ": 1 / 2 dynamic queue, 3 SHOOT's slot allocator, 4 pixel-slice hand-over, 5 pixel-slice slot past the queue)");
                 const bool shoot_frame = r->sched.fused_bounce && std::min(D, r->sched.finish_depth) > 0; // SHOOT queues have holes: counted on the device
                 for (uint32_t s = 0; s < r->spp; ++s) {
                     if (!shoot_frame)
@@ -877,3 +893,57 @@ int render_impl(rt_renderer* r, const rt_camera* cam, float* d_f32, uint8_t* d_u
 }
 
 } // namespace rtlib
+
+#ifdef RT_DEVELOPER_KNOBS
+// Host-only models of the pixel slices for the CPU tests (tests/test_slices.py), in the developer library only: the slice plan the renderers use,
+// and a replay of the sliced cursor through the kernels' own mapping (SliceCursor).
+extern "C" {
+
+// slice_plan: bound[] receives kMaxSlices entries
+int rt_dev_slice_plan(uint32_t spp, int32_t want, double G, uint32_t* n_slices, uint32_t* shift, unsigned long long* cuts, uint32_t* bound) {
+    if (!n_slices || !shift || !cuts || !bound) return fail(RT_ERR_INVALID, "null argument");
+    const SlicePlan p = slice_plan(spp, want, G);
+    *n_slices = p.n_slices, *shift = p.shift, *cuts = p.cuts;
+    for (uint32_t k = 0; k < kMaxSlices; ++k) bound[k] = p.bound[k];
+    return RT_OK;
+}
+
+// n_waves waves, each with its own forward-only slice, claim 1..64 slots at a time from one cursor over n x n_slices slots, in an order drawn
+// from `seed`, until the cursor has passed the last slot; every slot claimed is mapped as the kernels map it and recorded as (pixel slot, first
+// sample) in out_slot / out_first (`capacity` entries; *n_out of them written). bound: kMaxSlices entries, as SliceDev::bound. capped = 0 claims
+// without SliceCursor::claim_width — the cursor as it was before the cap.
+int rt_dev_slice_replay(uint32_t n, uint32_t n_slices, const uint32_t* bound, uint32_t n_waves, unsigned long long seed, int capped,
+                        uint32_t* out_slot, uint32_t* out_first, uint32_t capacity, uint32_t* n_out) {
+    if (!bound || !out_slot || !out_first || !n_out) return fail(RT_ERR_INVALID, "null argument");
+    if (n == 0 || n_slices == 0 || n_slices > kMaxSlices || n_waves == 0 || (uint64_t)n * n_slices >= (1ull << 31))
+        return fail(RT_ERR_INVALID, "n, n_slices (1..8) and n_waves must be positive, n x n_slices < 2^31");
+    auto next = [&seed]() { // splitmix64
+        unsigned long long z = (seed += 0x9E3779B97F4A7C15ull);
+        z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+        z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+        return z ^ (z >> 31);
+    };
+    const uint32_t total = n * n_slices;
+    std::vector<uint32_t> slice_j(n_waves, 0u);
+    uint32_t cursor = 0, written = 0;
+    while (cursor < total) {
+        const unsigned long long z = next();
+        uint32_t& j = slice_j[(uint32_t)(z % n_waves)];
+        const uint32_t idle = 1u + (uint32_t)((z >> 32) % 64u);
+        const uint32_t w = capped ? SliceCursor::claim_width(idle, n) : idle;
+        const uint32_t base = cursor, end = std::min(base + w, total);
+        cursor += w;
+        j = SliceCursor::advance(j, n_slices, base, n);
+        const uint32_t first_here = j ? bound[j - 1u] : 0u, first_next = bound[j];
+        for (uint32_t q = base; q < end; ++q) {
+            if (written == capacity) return fail(RT_ERR_INVALID, "more slots than `capacity`");
+            const SliceSlot m = SliceCursor::map(q, j, n, first_here, first_next);
+            out_slot[written] = m.slot, out_first[written] = m.first, written++;
+        }
+    }
+    *n_out = written;
+    return RT_OK;
+}
+
+} // extern "C"
+#endif

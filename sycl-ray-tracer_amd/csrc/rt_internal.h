@@ -126,7 +126,7 @@ struct rt_renderer {
     MegaFrame* h_frame = nullptr;
     int stats_level = 2;                   // RT_KERNEL_STATS: 2 = the full counters (=1), 1 = the megakernel's timing-only instantiation (=2)
     uint32_t last_slices = 1;              // slices the wavefront renderer's last enqueued frame used (rt_stats.pixel_slices)
-    uint32_t slice_tag = 0;                // tag0 of the last frame (grows by kMaxSlices per frame)
+    uint32_t slice_tag = 0;                // tag0 of the last frame (grows by spp + 1 per frame: a tag is tag0 + the first sample of a slice)
     uint32_t rr_start = 0;                 // Russian roulette from this bounce on (0 = off, the reference's behaviour)
     unsigned long long* d_stats = nullptr; // RT_KERNEL_STATS=1: wave scheduling statistics (diagnostic)
     // wavefront: the tile is rendered as K interleaved sub-tiles ("lanes"), each with its own queues and

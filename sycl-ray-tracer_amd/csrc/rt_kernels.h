@@ -295,23 +295,25 @@ __global__ void __launch_bounds__(kMegaBlock, kMegaWaves) k_megakernel(SceneDev 
             const unsigned long long idle_m = __ballot(!live);
             const uint32_t cnt = (uint32_t)__popcll(idle_m);
             if (cnt >= refill.threshold()) {
+                const uint32_t w = SLICED ? SliceCursor::claim_width(cnt, n_slots) : cnt; // (n_slots >= 64: w == cnt)
                 uint32_t base = 0;
-                if (lane == 0) base = atomicAdd(pixel_cursor, cnt);
+                if (lane == 0) base = atomicAdd(pixel_cursor, w);
                 base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
                 uint32_t first_here = 0, first_next = 0; // first samples of the slice the claim starts in and of the one after it
                 if (SLICED) {
-                    while (slice_j + 1u < n_slices && base >= (slice_j + 1u) * n_slots) slice_j++; // (the cursor only moves forward)
+                    slice_j = SliceCursor::advance(slice_j, n_slices, base, n_slots);
                     if (slice_j) first_here = frame_slice_bound(frame, slice_j - 1u);
                     first_next = frame_slice_bound(frame, slice_j);
                 }
-                const uint32_t slice_base = SLICED ? slice_j * n_slots : 0u, total_slots = SLICED ? n_slots * n_slices : n_slots;
+                const uint32_t total_slots = SLICED ? n_slots * n_slices : n_slots;
                 const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(idle_m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)idle_m, 0u));
                 const uint32_t q = base + rank;
-                if (!live && q < total_slots) {
-                    const bool next = SLICED && q - slice_base >= n_slots; // a claim of at most 64 slots crosses at most one slice boundary
-                    take_slot(next ? q - slice_base - n_slots : q - slice_base, next ? first_next : first_here);
+                if (!live && q < total_slots && rank < w) {
+                    // a claim of at most n_slots slots crosses at most one slice boundary (SliceCursor)
+                    const SliceSlot m = SLICED ? SliceCursor::map(q, slice_j, n_slots, first_here, first_next) : SliceSlot{q, 0u};
+                    take_slot(m.slot, m.first);
                 }
-                if (base + cnt >= total_slots) {
+                if (base + w >= total_slots) {
                     exhausted = true;
                     if (STATS >= 2) wall_exhausted = wall_clock64();
                 }
@@ -863,6 +865,10 @@ __global__ void __launch_bounds__(kMegaBlock, kMegaWaves) k_wf_finish(SceneDev S
     __shared__ unsigned long long out_word;
     __shared__ uint32_t out_exited;
     if (LIMIT && threadIdx.x == 0) out_word = (unsigned long long)kOutBlock, out_exited = 0u; // "no block yet": used == kOutBlock (before the LDS barrier below)
+    // SLICED: set when a lane's claimed slot mapped past the queue (a logic error, SliceCursor); the wave reports it as it leaves (error word 5: the
+    // host's RT_ERR_HIP). Through LDS: the error word's store at the claim itself cost the kernel four more spilled scalar registers.
+    __shared__ uint32_t slot_lost;
+    if (SLICED && threadIdx.x == 0) slot_lost = 0u;
     WaveStats ws;
     const uint32_t n = *count_in;
     const uint32_t lane = threadIdx.x & 63u;
@@ -988,7 +994,8 @@ __global__ void __launch_bounds__(kMegaBlock, kMegaWaves) k_wf_finish(SceneDev S
                         // through when the other waves have left. Single paths are short: there a chunk per atomic is right.
                         // (SHOOT with guided chunk sizes — a share of what is left, 512 ... 64 slots, to save cursor atomics — was measured slower:
                         // 58.6 -> 66.2 ms at 16 spp; a wave that starts a long private chunk near the end sets the launch's tail.)
-                        uint32_t w = !REQ && n_samples > 1u ? cnt : chunk_slots;
+                        // SLICED: at most n slots, or a claim could cross two slice boundaries (SliceCursor)
+                        uint32_t w = SLICED ? SliceCursor::claim_width(cnt, n) : !REQ && n_samples > 1u ? cnt : chunk_slots;
                         if (tail_guided) {
                             const uint32_t left = n > seen ? n - seen : 0u;
                             const uint32_t share = (uint32_t)(((unsigned long long)left * inv_waves) >> 16);
@@ -1024,10 +1031,9 @@ __global__ void __launch_bounds__(kMegaBlock, kMegaWaves) k_wf_finish(SceneDev S
                     const uint32_t avail = chunk_end - chunk_pos;
                     const uint32_t take = cnt < avail ? cnt : avail;
                     const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(idle_m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)idle_m, 0u));
-                    uint32_t first_here = 0, first_next = 0, slice_base = 0; // SLICED: first samples of the slice the chunk starts in and of the next, that slice's first slot
+                    uint32_t first_here = 0, first_next = 0; // SLICED: first samples of the slice the chunk starts in and of the next
                     if (SLICED) {
-                        while (slice_j + 1u < n_slices && chunk_pos >= (slice_j + 1u) * n) slice_j++; // (chunks only move forward)
-                        slice_base = slice_j * n;
+                        slice_j = SliceCursor::advance(slice_j, n_slices, chunk_pos, n);
                         if (slice_j) first_here = frame_slice_bound(slices, slice_j - 1u);
                         first_next = frame_slice_bound(slices, slice_j);
                     }
@@ -1037,26 +1043,30 @@ __global__ void __launch_bounds__(kMegaBlock, kMegaWaves) k_wf_finish(SceneDev S
                             waiting = true;
                         } else {
                             uint32_t slot = chunk_pos + rank, first = 0; // `first`: the sample the lane's slice starts with
-                            if (SLICED) {
-                                const bool next = slot - slice_base >= n; // (a claim of at most 64 slots crosses at most one slice boundary)
-                                slot = next ? slot - slice_base - n : slot - slice_base, first = next ? first_next : first_here;
+                            if (SLICED) { // (a claim of at most n slots crosses at most one slice boundary: SliceCursor)
+                                const SliceSlot m = SliceCursor::map(slot, slice_j, n, first_here, first_next);
+                                slot = m.slot, first = m.first;
                             }
-                            id = queue_load(qin, slot, r);
-                            if (SLICED && first != 0u) { // a later slice: the ray in the queue is sample 0's; the pixel's state comes from the lane that renders the slice before (below)
-                                depth = kPend;
-                                samples_left = n_samples - first, first_counted = false;
-                                live = true;
-                            } else if (!(holes && id == kNoRay)) { // (a hole: the slot is consumed, the lane stays idle until the next refill)
-                                rng = rng_buf[id]; // ScopedRng load (src/render_wavefront.cpp:15-32): held in a register until the lane lets the pixel go
-                                depth = first_depth;
-                                samples_left = n_samples, first_counted = !holes;
-                                if (SLICED) *sum_r = 0.0f, *sum_g = 0.0f, *sum_b = 0.0f; // (k_wf_init left the accumulator at zero)
-                                if (!REQ && n_samples > 1u && xg_packed) { // the pixel's coordinates for its later camera rays: two divisions ONCE per pixel
-                                    const uint32_t w = (uint32_t)camp->width;
-                                    *xg_word() = (id % w) | ((uint32_t)tile_global_row(tile, (int)(id / w)) << 16);
+                            if (SLICED && slot >= n) { // a mapping error: the lane stays idle — no load past the queue, no store through its id
+                                slot_lost = 1u;
+                            } else {
+                                id = queue_load(qin, slot, r);
+                                if (SLICED && first != 0u) { // a later slice: the ray in the queue is sample 0's; the pixel's state comes from the lane that renders the slice before (below)
+                                    depth = kPend;
+                                    samples_left = n_samples - first, first_counted = false;
+                                    live = true;
+                                } else if (!(holes && id == kNoRay)) { // (a hole: the slot is consumed, the lane stays idle until the next refill)
+                                    rng = rng_buf[id]; // ScopedRng load (src/render_wavefront.cpp:15-32): held in a register until the lane lets the pixel go
+                                    depth = first_depth;
+                                    samples_left = n_samples, first_counted = !holes;
+                                    if (SLICED) *sum_r = 0.0f, *sum_g = 0.0f, *sum_b = 0.0f; // (k_wf_init left the accumulator at zero)
+                                    if (!REQ && n_samples > 1u && xg_packed) { // the pixel's coordinates for its later camera rays: two divisions ONCE per pixel
+                                        const uint32_t w = (uint32_t)camp->width;
+                                        *xg_word() = (id % w) | ((uint32_t)tile_global_row(tile, (int)(id / w)) << 16);
+                                    }
+                                    trav_begin(T, r.org, ray_dir(r), stack);
+                                    live = true;
                                 }
-                                trav_begin(T, r.org, ray_dir(r), stack);
-                                live = true;
                             }
                         }
                     }
@@ -1188,12 +1198,14 @@ __global__ void __launch_bounds__(kMegaBlock, kMegaWaves) k_wf_finish(SceneDev S
                 depth = 0, first_counted = false;
                 ends = false;
             }
-            if (ends && cost_out) cost_out[id] = (uint8_t)(depth < 255u ? depth : 255u); // rays of this path: what the cost ordering sorts by
+            // SLICED: only the lane that finishes the pixel writes its words in memory — a lane that hands it on stores nothing there, or several
+            // lanes, on different XCDs, would write the same word with plain stores (the next slice's lane carries the RNG word on)
+            if (ends && !handed && cost_out) cost_out[id] = (uint8_t)(depth < 255u ? depth : 255u); // rays of this path: what the cost ordering sorts by
             if (SLICED && ends && !handed) accum[id] = make_float4(*sum_r, *sum_g, *sum_b, 0.0f); // the pixel's last sample: the accumulator, written once
             if (ends) {
                 live = false, slot_finished = true;
                 if (REQ) requeue = samples_left > 1u;
-                if (!requeue) rng_buf[id] = rng; // ScopedRng store (the next launch reads it; inside this launch the word travels in the entry)
+                if (!requeue && !handed) rng_buf[id] = rng; // ScopedRng store (the next launch reads it; inside this launch the word travels in the entry)
             } else if (LIMIT && depth - first_depth >= bounce_limit) {
                 hand_on = true, live = false, slot_finished = true; // the survivor goes to the next bounce's queue (below)
             } else {
@@ -1257,6 +1269,7 @@ __global__ void __launch_bounds__(kMegaBlock, kMegaWaves) k_wf_finish(SceneDev S
         }
         __builtin_amdgcn_s_setprio(2);
     }
+    if (SLICED && lane == 0 && slot_lost && fq.error) __hip_atomic_store(fq.error, 5u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (lane == 0 && wave_rays) atomicAdd(extra_rays, wave_rays);
     if (STATS && lane == 0) {
         atomicAdd(stats_out + 0, (unsigned long long)ws.inner_steps), atomicAdd(stats_out + 1, (unsigned long long)ws.inner_lanes);

@@ -42,7 +42,7 @@ constexpr uint32_t kMegaWaves = 6;     // waves per SIMD the kernels are compile
 //           16-byte stores and read with two sc1 loads: "the data is the flag" (cdna_hip_programming.md §6, Guideline 16, R2). A reader
 //           takes the state only if ALL FOUR tags say "written for the slice of this frame that starts with sample s" (tag0 + s; tag0
 //           grows by more than spp from frame to frame, the buffer is never cleared): no flag, no fence, no ordering between the stores.
-//   order : slot q of the cursor = slice q / n_slots of pixel slot q % n_slots, so slice j of a pixel is handed out a whole sweep of the
+//   order : slot q of the cursor = slice q / n_slots of pixel slot q % n_slots (SliceCursor, below), so slice j of a pixel is handed out a whole sweep of the
 //           cursor after slice j - 1 was; the host sizes the slices so that a sweep takes longer than the slice before it
 //           (mega_slices). A lane whose slice is not ready yet (never seen at full size; small tiles) looks again in its wave's next
 //           shading round. No lane ever waits for a LATER slot: nothing can deadlock.
@@ -61,6 +61,33 @@ struct SliceDev {
     uint32_t wait_cap;          // looks of a wave with nothing but waiting lanes before it gives up (above)
 };
 constexpr uint32_t kSliceWaitCap = 1u << 22; // x ~3.4 us of sleep + the look itself: > 15 s
+// The cursor of a sliced launch, for n pixel slots (k_megakernel: the tile's 8x8 blocks x 64; k_wf_finish<.., SLICED>: the queue's length).
+// A wave claims consecutive slots with one atomic and maps each with the first samples of two slices only — the slice its claim starts in
+// (`slice_j`, wave-uniform, forward only) and the one after it, both scalar loads of bound[] in the kernels. That is right only while a claim
+// crosses at most ONE slice boundary, i.e. holds at most n slots: the claim is capped at n. (k_megakernel: n >= 64 >= a wave's idle lanes, the
+// cap never bites. k_wf_finish: a tile may have fewer pixels than a wave has idle lanes — uncapped, 64 slots of a 16-pixel tile in 4 slices
+// mapped slots 32..63 to pixel slots 16..47, past the queue.) The kernels and the host's replay of the cursor (rt_dev_slice_replay, the CPU
+// tests) run these same functions.
+struct SliceSlot {
+    uint32_t slot;  // pixel slot (k_wf_finish: queue slot)
+    uint32_t first; // the sample its slice starts with
+};
+struct SliceCursor {
+    // slots a wave with `idle` idle lanes claims
+    __host__ __device__ __forceinline__ static uint32_t claim_width(uint32_t idle, uint32_t n) { return idle < n ? idle : n; }
+    // the slice a claim that starts at slot `pos` starts in (from the wave's previous one: the cursor only moves forward)
+    __host__ __device__ __forceinline__ static uint32_t advance(uint32_t slice_j, uint32_t n_slices, uint32_t pos, uint32_t n) {
+        while (slice_j + 1u < n_slices && pos >= (slice_j + 1u) * n) slice_j++;
+        return slice_j;
+    }
+    // slot q of a claim that starts in slice `slice_j`; first_here / first_next: the first samples of slice_j and slice_j + 1
+    // (bound[slice_j - 1] or 0, bound[slice_j])
+    __host__ __device__ __forceinline__ static SliceSlot map(uint32_t q, uint32_t slice_j, uint32_t n, uint32_t first_here, uint32_t first_next) {
+        const uint32_t p = q - slice_j * n;
+        const bool next = p >= n;
+        return SliceSlot{next ? p - n : p, next ? first_next : first_here};
+    }
+};
 // The frame's constants that only a shading round or a refill reads — the camera's twelve floats, the slices — live in DEVICE memory and are
 // loaded where they are used (scalar loads, hot in the scalar cache): as kernel arguments hipcc kept them in ~35 scalar registers through the
 // traversal loop, in a kernel that has none to spare (with the slices on top: 38 scalar registers spilled into vector lanes, 46 vector

@@ -230,8 +230,24 @@ def load_developer_library() -> C.CDLL:
     (Scene(..., lib=...)); the product library reads GPU_MAX_HW_QUEUES, RT_PROFILE_KERNELS and RT_KERNEL_STATS only."""
     global _dev_lib
     if _dev_lib is None:
-        _dev_lib = load_library(DEV_LIB_PATH)
+        lib = load_library(DEV_LIB_PATH)
+        for name, (res, args) in DEV_PROTOTYPES.items():
+            fn = getattr(lib, name)
+            fn.restype = res
+            fn.argtypes = args
+        _dev_lib = lib
     return _dev_lib
+
+
+# host-only models the developer build exports beside the product's ABI (csrc/rt_frame.hip, tests/test_slices.py)
+DEV_PROTOTYPES = {
+    # (spp, pixel_slices, G, out n_slices, out shift, out cuts, out bound[8]): the slice plan of the renderers
+    "rt_dev_slice_plan": (C.c_int, [C.c_uint32, C.c_int32, C.c_double, _P(C.c_uint32), _P(C.c_uint32), _P(C.c_uint64),
+                                    _P(C.c_uint32)]),
+    # (n, n_slices, bound[8], n_waves, seed, capped, out slot[], out first[], capacity, out count): the sliced cursor replayed
+    "rt_dev_slice_replay": (C.c_int, [C.c_uint32, C.c_uint32, _P(C.c_uint32), C.c_uint32, C.c_uint64, C.c_int,
+                                      _P(C.c_uint32), _P(C.c_uint32), C.c_uint32, _P(C.c_uint32)]),
+}
 
 
 def fptr(a):

@@ -107,7 +107,7 @@ class Frame:
     cost_ordered: bool = False
     kernel_ms: dict = None       # with profiling: summed launch durations per kernel family (hipEvents on the launches' own streams)
     hw_queues: int = 0           # GPU_MAX_HW_QUEUES as the library read it (4 = HIP's default): bounds the automatic stream lanes
-    pixel_slices: int = 0        # megakernel: slices a pixel's samples were rendered in (1 = every pixel on one lane)
+    pixel_slices: int = 0        # slices a pixel's samples were rendered in (1 = every pixel on one lane, an empty tile, an unsliced schedule)
 
     @classmethod
     def from_stats(cls, f, b, st):
@@ -152,7 +152,9 @@ class IRenderer:
                      fused_bounce: bool = False, pixel_slices: int = -1) -> None:
         """rt_renderer_set_schedule: which of the wavefront renderer's schedules renders the frame (same frame bit for bit; the
         reference has one: a launch per bounce, src/render_wavefront.cpp:396-417 = finish_depth=abi.RT_SCHED_ALL_BOUNCES).
-        Frame.kernels reports what ran. The megakernel uses pixel_slices only (-1 automatic, 0 / 1 off, 2 .. 8: rt_mi355x.h)."""
+        Frame.kernels reports what ran. pixel_slices (-1 automatic, 0 / 1 off, 2 .. 8: rt_mi355x.h) is the only field the megakernel uses;
+        the wavefront renderer slices its one-launch schedule (samples_per_launch 0, finish_depth 0) and not with hip_graph, more than
+        one stream lane or cost_order=1. Frame.pixel_slices reports what ran."""
         sc = abi.rt_schedule(int(finish_depth), int(samples_per_launch), int(stream_lanes), int(requeue), int(bool(reorder)),
                              int(bool(matsort)), int(cost_order), int(bool(hip_graph)), int(bool(fused_bounce)), int(pixel_slices))
         abi.check(self._lib.rt_renderer_set_schedule(self.h, C.byref(sc)), self._lib)

@@ -1383,6 +1383,84 @@ def test_pixel_slices_keep_the_frame_where_every_slice_has_to_wait(gpu_scenes, o
     r.close()
 
 
+def _slice_units(spp):
+    """Units of samples a slice is made of (csrc/rt_frame.hip: slice_plan): forced slices are cut down to one unit each."""
+    shift = 0
+    while (spp - 1) >> shift >= 64:
+        shift += 1
+    return -(-spp // (1 << shift))
+
+
+SLICE_FRAME_LIMIT_S = 5.0  # a lost hand-over waits ~15 s (kSliceWaitCap) before the frame fails: a slow frame is a failure, not a slow pass
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("w,h", [(1, 1), (3, 5), (8, 4), (7, 9), (8, 8), (13, 5), (11, 12)])  # 1 ... 132 pixels: tiles below, at and above a wave
+@pytest.mark.parametrize("spp", [4, 67, 130])  # slices end at multiples of 1, 2 (a short last unit) and 4 samples
+@pytest.mark.parametrize("cls,kind", KINDS)
+def test_pixel_slices_on_tiles_smaller_than_a_wave(gpu_scenes, oracle, scene_cache, cls, kind, w, h, spp):
+    """Forced slices on tiles of fewer pixels than a wave has lanes. The wavefront renderer's cursor has as many slots per slice as the tile has
+    pixels, and a wave's claim of up to 64 idle lanes once crossed two slice boundaries of such a tile: lanes then mapped to slots past the
+    queue and the frame's later slices were never handed out (csrc/rt_launch.h: SliceCursor caps the claim). Three frames in a row each, as tags
+    tell frames apart; every frame bit-exact and well inside the wait cap."""
+    sd = scene_cache("cornell")
+    gs = gpu_scenes("cornell")
+    depth = 5
+    f, b, rays = _oracle_frame(oracle, sd, w, h, kind, depth, spp)
+    cam = Camera.for_scene(sd, (w, h))
+    r = cls(gs, (w, h), depth, spp)
+    for slices in (2, 3, 4, 8):
+        r.set_schedule(pixel_slices=slices)
+        for frame in range(3):
+            t0 = time.perf_counter()
+            got = r.render_frame(cam)
+            dt = time.perf_counter() - t0
+            what = f"{cls.__name__} {w}x{h} {spp} spp, {slices} slices, frame {frame}"
+            assert dt < SLICE_FRAME_LIMIT_S, f"{what}: {dt:.1f} s"
+            assert got.pixel_slices == min(slices, _slice_units(spp)), what
+            _assert_frames_equal(got.rgba_f32, got.rgba_u8, got.rays, f, b, rays, what)
+    r.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("w,h,world,strip", [(5, 40, 8, 8),   # five tiles of 40 pixels; ranks 5 .. 7 have no rows
+                                             (24, 20, 3, 8),  # the last rank has 4 rows
+                                             (7, 9, 3, 8)])   # 56 pixels, 7 pixels, no rows
+@pytest.mark.parametrize("cls,kind", KINDS)
+def test_pixel_slices_on_split_tiles(gpu_scenes, oracle, scene_cache, cls, kind, w, h, world, strip):
+    """Sliced tiles of a split frame, some below 64 pixels and some empty: assembled, they are the oracle's frame and each is its own
+    renderer's unsliced tile; an empty tile renders without error and reports one slice."""
+    sd = scene_cache("cornell")
+    gs = gpu_scenes("cornell")
+    depth, spp = 5, 67
+    f, b, rays = _oracle_frame(oracle, sd, w, h, kind, depth, spp)
+    cam = Camera.for_scene(sd, (w, h))
+    r = cls(gs, (w, h), depth, spp)
+    for slices in (2, 8):
+        parts_f, parts_b, total = [], [], 0
+        for rank in range(world):
+            r.set_tile(rank, world, strip)
+            rows = r.global_rows()
+            assert all((y // strip) % world == rank for y in rows) and len(rows) == r.local_rows
+            r.set_schedule(pixel_slices=0)
+            plain = r.render_frame(cam)
+            r.set_schedule(pixel_slices=slices)
+            t0 = time.perf_counter()
+            got = r.render_frame(cam)
+            dt = time.perf_counter() - t0
+            what = f"{cls.__name__} {w}x{h} tile {rank}/{world}, {slices} slices"
+            assert dt < SLICE_FRAME_LIMIT_S, f"{what}: {dt:.1f} s"
+            assert got.pixel_slices == (min(slices, _slice_units(spp)) if len(rows) else 1), what
+            assert got.rays == plain.rays, what
+            np.testing.assert_array_equal(got.rgba_f32, plain.rgba_f32, err_msg=what)
+            np.testing.assert_array_equal(got.rgba_u8, plain.rgba_u8, err_msg=what)
+            parts_f.append(got.rgba_f32), parts_b.append(got.rgba_u8)
+            total += got.rays
+        _assert_frames_equal(assemble_tiles(parts_f, h, world, strip), assemble_tiles(parts_b, h, world, strip), total, f, b, rays,
+                             f"{cls.__name__} {w}x{h} over {world} tiles, {slices} slices")
+    r.close()
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("cls,kind", KINDS)
 def test_a_lost_slice_hand_over_becomes_an_error_code_not_a_hung_gpu(dev_scenes, oracle, monkeypatch, cls, kind):

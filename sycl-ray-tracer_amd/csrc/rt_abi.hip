@@ -333,3 +333,28 @@ int rt_render_frame_end(rt_renderer* r, rt_stats* stats) {
 }
 
 } // extern "C"
+
+#ifdef RT_DEVELOPER_KNOBS
+// Developer library only: how a scene's shading tables came out (the packed shading word, the distinct-matrix table, what the shading
+// kernels stage in LDS), for the tests that must show which path of shade_hit (rt_device.h) a scene takes.
+extern "C" {
+
+// packed_mat: ShadeRec::instance carries the material (rt_types.h); lds_nm / lds_mats: entries staged in LDS (0 for a host-only scene:
+// only device scenes stage); n_rows: rows of the device's instance table — distinct normal matrices when packed, else one per instance.
+// rows: 9 floats per row, the first `capacity` rows (may be null); words: ShadeRec::instance of every triangle in rt_scene_desc order
+// (n_triangles entries, may be null).
+int rt_dev_scene_tables(const rt_scene* s, uint32_t* packed_mat, uint32_t* lds_nm, uint32_t* lds_mats, uint32_t* n_rows, float* rows,
+                        uint32_t capacity, uint32_t* words) {
+    if (!s || !packed_mat || !lds_nm || !lds_mats || !n_rows) return fail(RT_ERR_INVALID, "null argument");
+    *packed_mat = s->hs.packed_mat ? 1u : 0u;
+    *lds_nm = s->dev.lds_nm, *lds_mats = s->dev.lds_mats;
+    *n_rows = (uint32_t)s->hs.inst.size();
+    if (rows)
+        for (size_t k = 0; k < std::min<size_t>(capacity, s->hs.inst.size()); ++k) std::memcpy(rows + 9 * k, s->hs.inst[k].normal_mat, 36);
+    if (words)
+        for (size_t t = 0; t < s->hs.shade.size(); ++t) words[t] = s->hs.shade[t].instance;
+    return RT_OK;
+}
+
+} // extern "C"
+#endif

@@ -247,6 +247,10 @@ DEV_PROTOTYPES = {
     # (n, n_slices, bound[8], n_waves, seed, capped, out slot[], out first[], capacity, out count): the sliced cursor replayed
     "rt_dev_slice_replay": (C.c_int, [C.c_uint32, C.c_uint32, _P(C.c_uint32), C.c_uint32, C.c_uint64, C.c_int,
                                       _P(C.c_uint32), _P(C.c_uint32), C.c_uint32, _P(C.c_uint32)]),
+    # (scene, out packed_mat, out lds_nm, out lds_mats, out n_rows, out rows[9 x capacity] | NULL, capacity, out words[n_triangles] | NULL):
+    # the scene's shading tables as built (csrc/rt_abi.hip; tests/test_gpu_parity.py, tests/test_host.py)
+    "rt_dev_scene_tables": (C.c_int, [C.c_void_p, _P(C.c_uint32), _P(C.c_uint32), _P(C.c_uint32), _P(C.c_uint32), _P(C.c_float), C.c_uint32,
+                                      _P(C.c_uint32)]),
 }
 
 

@@ -78,6 +78,20 @@ class Scene:
                                              abi.u32ptr(seeds), abi.u8ptr(ok), abi.fptr(od), abi.fptr(oa), abi.u32ptr(so)), self._lib)
         return ok, od, oa, so
 
+    def shading_tables(self) -> dict:
+        """rt_dev_scene_tables, for a scene built by the DEVELOPER library (Scene(..., lib=abi.load_developer_library())): whether the
+        shading word is packed, the normal matrices and materials the shading kernels stage in LDS (0 in a host-only scene), the device's
+        instance table as (n_rows, 9) float32 rows and every triangle's shading word (ShadeRec::instance) in scene order."""
+        if not hasattr(self._lib, "rt_dev_scene_tables"):
+            raise RuntimeError("shading_tables() needs a scene of the developer library")
+        packed, lds_nm, lds_mats, n_rows = (C.c_uint32() for _ in range(4))
+        args = (C.byref(packed), C.byref(lds_nm), C.byref(lds_mats), C.byref(n_rows))
+        abi.check(self._lib.rt_dev_scene_tables(self.h, *args, None, 0, None), self._lib)
+        rows = np.zeros((n_rows.value, 9), np.float32)
+        words = np.zeros(self.desc.n_triangles, np.uint32)
+        abi.check(self._lib.rt_dev_scene_tables(self.h, *args, abi.fptr(rows), n_rows.value, abi.u32ptr(words)), self._lib)
+        return dict(packed_mat=packed.value, lds_nm=lds_nm.value, lds_mats=lds_mats.value, rows=rows, words=words)
+
     def close(self):
         if self.h:
             self._lib.rt_scene_destroy(self.h)

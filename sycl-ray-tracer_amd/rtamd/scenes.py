@@ -169,10 +169,11 @@ class SceneDesc:
         self.textures = np.ascontiguousarray(self.textures, np.uint8)
         n_inst = int(self.transforms.shape[0])
         insts = (abi.rt_instance * max(n_inst, 1))()
-        for i in range(n_inst):
-            insts[i].transform[:] = [float(v) for v in self.transforms[i]]
-            insts[i].normal_mat[:] = [float(v) for v in self.normal_mats[i]]
-            insts[i].material = int(self.inst_material[i])
+        if n_inst:  # filled through a numpy view of the array: 26 words per instance, transform | normal_mat | material
+            words = np.frombuffer(insts, np.float32).reshape(-1, 26)
+            words[:n_inst, :16] = np.asarray(self.transforms, f32).reshape(n_inst, 16)
+            words[:n_inst, 16:25] = np.asarray(self.normal_mats, f32).reshape(n_inst, 9)
+            words.view(np.uint32)[:n_inst, 25] = np.asarray(self.inst_material, np.uint32)
         mats = (abi.rt_material * max(len(self.materials), 1))()
         for i, m in enumerate(self.materials):
             mats[i].type = m.type
@@ -979,7 +980,65 @@ def atrium_tilted_scene(detail: int = 4, coarse: bool = True) -> SceneDesc:
     return rotate_scene(atrium_scene(detail, coarse=coarse), quat_axis_angle((0.3, 1.0, 0.2), 0.58))
 
 
+TABLE_KINDS = (  # (type, texture layer or None, roughness, ior, emissive): the material of index m is TABLE_KINDS[m % 16]
+    (abi.RT_MAT_DIFFUSE, None, 0.0, 1.5, False), (abi.RT_MAT_DIFFUSE, 0, 0.0, 1.5, False),
+    (abi.RT_MAT_METALLIC, None, 0.0, 1.5, False), (abi.RT_MAT_METALLIC, 0, 0.3, 1.5, False),
+    (abi.RT_MAT_METALLIC, None, 1.0, 1.5, False), (abi.RT_MAT_METALLIC, 1, 1.7, 1.5, False),
+    (abi.RT_MAT_DIELECTRIC, None, 0.0, 0.7, False), (abi.RT_MAT_DIELECTRIC, None, 0.0, 1.0, False),
+    (abi.RT_MAT_DIELECTRIC, None, 0.0, 1.5, False), (abi.RT_MAT_DIELECTRIC, None, 0.0, 2.4, False),
+    (abi.RT_MAT_DIFFUSE, None, 0.0, 1.5, True), (abi.RT_MAT_METALLIC, None, 0.3, 1.5, False),
+    (abi.RT_MAT_METALLIC, 1, 0.0, 1.5, False), (abi.RT_MAT_METALLIC, None, 1.7, 1.5, False),
+    (abi.RT_MAT_METALLIC, 0, 1.0, 1.5, False), (abi.RT_MAT_DIFFUSE, 1, 0.0, 1.5, False),
+)
+
+
+def table_material_order(n_mats: int) -> list[int]:
+    """The materials of table_scene's instances in instance order: 0, n-1, 1, n-2, ... — the lowest and the highest indices alternate."""
+    return [k // 2 if k % 2 == 0 else n_mats - 1 - k // 2 for k in range(n_mats)]
+
+
+def table_scene(n_mats: int = 25, n_rows: int = 9, n_inst: int | None = None, seed: int = 5) -> SceneDesc:
+    """A grid of small boxes facing the camera with a chosen number of materials (`n_mats`), of distinct instance normal matrices
+    (`n_rows`) and of instances (`n_inst`, one box of 12 triangles each; default max(n_mats, n_rows), at most 192). The shading kernels
+    stage the first 24 materials and 8 normal matrices in LDS and read every other from memory, and a scene of more than 4096 materials or
+    2^20 instances has no packed shading word (csrc/rt_types.h): this scene puts a frame on either side of those limits.
+
+    Box k sits in grid cell k (row-major from the top left, 4:3 like the frame) and has material table_material_order(n_mats)[k], so that
+    neighbouring boxes alternate between staged and unstaged materials; with fewer instances than materials the middle of the range is
+    unused. Its normal matrix is pattern k % n_rows: a rotation and a non-uniform scale of its own, so no two patterns share a bit pattern.
+    Materials run through TABLE_KINDS: diffuse with a colour or a texture, metallic with either at roughness 0, 0.3, 1 and 1.7,
+    dielectric at ior 0.7, 1, 1.5 and 2.4, an emissive diffuse. The boxes turn, so paths bounce between neighbours."""
+    n_inst = min(max(n_mats, n_rows), 192) if n_inst is None else n_inst
+    assert n_mats >= 1 and 1 <= n_rows <= n_inst
+    rng = np.random.default_rng(seed)
+    sb = SceneBuilder(f"tables_{n_mats}_{n_rows}_{n_inst}")
+    sb.add_texture(texture("checker", seed, (0.9, 0.7, 0.4)))
+    sb.add_texture(texture("bricks", seed + 1))
+    colours = rng.uniform(0.2, 0.95, (n_mats, 3))
+    for m in range(n_mats):
+        kind, layer, rough, ior, emits = TABLE_KINDS[m % len(TABLE_KINDS)]
+        c = tuple(float(v) for v in colours[m])
+        sb.add_material(Material(kind, c, layer, tuple(4.0 * v for v in c) if emits else (0.0, 0.0, 0.0), rough, ior))
+    gy = max(1, int(round(math.sqrt(n_inst * 3.0 / 4.0))))
+    gx = -(-n_inst // gy)
+    cell = min(4.0 / gx, 3.0 / gy)  # the camera below sees 4 x 3 at z = 0
+    patterns = []
+    for _ in range(n_rows):
+        q = quat_axis_angle(rng.normal(size=3), float(rng.uniform(0.15, 0.6)))
+        s = np.array([rng.uniform(0.55, 0.95), rng.uniform(0.55, 0.95), rng.uniform(0.5, 1.5)]) * (0.5 * cell)
+        patterns.append(mat4_mul(mat4_from_quat(q), mat4_scale(s)))
+    box = sb.add_mesh(*mesh_box())
+    order = table_material_order(n_mats)
+    for k in range(n_inst):
+        m = patterns[k % n_rows].copy()  # the translation set in place: the normal matrix of a pattern is the same bits in every cell
+        m[12], m[13] = f32((k % gx - (gx - 1) / 2.0) * cell), f32(((gy - 1) / 2.0 - k // gx) * cell)
+        sb.add_instance(box, order[k % n_mats], m)
+    sb.camera = CameraPose((0.0, 0.0, 3.0), (0.0, 0.0, -1.0), 2.0)
+    return sb.build()
+
+
 SCENES = {
+    "tables": table_scene,
     "voxel": voxel_scene,
     "atrium_tilted": atrium_tilted_scene,
     "triangle": triangle_scene,

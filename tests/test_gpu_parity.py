@@ -1554,3 +1554,115 @@ def test_pixel_slices_in_the_instrumented_kernel_and_with_roulette(gpu_scenes, o
     got = r.render_frame(cam)
     _assert_frames_equal(got.rgba_f32, got.rgba_u8, got.rays, f, b, rays, "roulette, 3 slices")
     r.close()
+
+
+# ---- shading past the LDS-staged tables and without the packed shading word ------------------------------------------------------
+# shade_hit (csrc/rt_device.h) reads a hit's material and normal matrix from the head of both tables staged in LDS (the megakernel and
+# k_wf_finish: kLdsMats = 24 materials, kLdsNm = 8 distinct matrices) only when every hit of the round is inside it; any other round reads them
+# from memory, and a scene of more than 4096 materials (or 2^20 instances) has no packed shading word: the material then comes through the
+# instance record. rtamd.scenes.table_scene puts frames on either side of those limits, and the developer library says which side
+# (rt_dev_scene_tables; the product library builds the same tables from the same host code).
+TABLE_W, TABLE_H, TABLE_SPP, TABLE_DEPTH = 96, 72, 3, 6
+TABLE_CASES = [  # (id, table_scene arguments, (packed_mat, lds_nm, lds_mats) of the device scene)
+    ("staged", dict(n_mats=24, n_rows=8), (1, 8, 24)),
+    ("one_past", dict(n_mats=25, n_rows=9), (1, 8, 24)),
+    ("many", dict(n_mats=300, n_rows=64, n_inst=300), (1, 8, 24)),
+    ("packed_4096", dict(n_mats=4096, n_rows=12), (1, 8, 24)),
+    ("unpacked_4097", dict(n_mats=4097, n_rows=12), (0, 0, 0)),
+]
+TABLE_SCHEDULES = [  # (what, renderer, schedule)
+    ("megakernel", MegakernelRenderer, dict(pixel_slices=0)),
+    ("megakernel, 3 slices", MegakernelRenderer, dict(pixel_slices=3)),
+    ("wavefront, one launch", WavefrontRenderer, dict(pixel_slices=0, cost_order=0)),
+    ("wavefront, one launch, 3 slices", WavefrontRenderer, dict(pixel_slices=3, cost_order=0)),
+    ("per bounce", WavefrontRenderer, dict(finish_depth=ALL_BOUNCES)),
+    ("per bounce, fused", WavefrontRenderer, dict(finish_depth=ALL_BOUNCES, fused_bounce=True)),
+    ("per bounce, reorder + matsort", WavefrontRenderer, dict(finish_depth=ALL_BOUNCES, reorder=True, matsort=True)),
+]
+
+
+def _table_hits(oracle, sd, packed):
+    """(material, table row or None) of the hit under every pixel centre of the TABLE_W x TABLE_H frame that hits, mapped on the host:
+    triangle -> instance -> material, and the row through the scene's shading words."""
+    cam = oracle.camera(TABLE_W, TABLE_H, sd.camera.position, sd.camera.direction, sd.camera.focal_length)
+    x, y = np.meshgrid(np.arange(TABLE_W, dtype=np.float32), np.arange(TABLE_H, dtype=np.float32))
+    p00, du, dv, c = (np.array(v, np.float32) for v in (cam.pixel00, cam.delta_u, cam.delta_v, cam.center))
+    d = p00 + x.reshape(-1, 1) * du + y.reshape(-1, 1) * dv - c
+    tri = oracle.OracleScene(sd).intersect(np.broadcast_to(c, d.shape), d, use_bvh=False)[3]
+    tri = tri[tri != NO_TRI]
+    return sd.inst_material[sd.tri_instance[tri]].astype(np.int64), (packed["words"][tri] & 0xFFFFF).astype(np.int64) if packed else None
+
+
+def _assert_table_schedule_ran(got, cls, sched, what):
+    k = got.kernels
+    if "finish_depth" not in sched:  # one launch per frame
+        assert got.pixel_slices == (3 if sched["pixel_slices"] == 3 else 1), what
+        if cls is MegakernelRenderer:
+            assert k["megakernel"] == 1, (what, k)
+            return
+        assert got.stream_lanes == 1 and k["wf_finish"] == 1 and k["wf_extend"] == k["wf_shade"] == k["wf_shoot"] == 0, (what, k)
+    else:  # a launch (pair) per bounce all the way down
+        lanes = got.stream_lanes
+        pairs = lanes * TABLE_SPP * TABLE_DEPTH
+        assert lanes == PER_BOUNCE_LANES and got.finish_depth == TABLE_DEPTH and k["wf_finish"] == 0, (what, k)
+        fused = bool(sched.get("fused_bounce"))
+        assert k["wf_extend"] == k["wf_shade"] == (0 if fused else pairs) and k["wf_shoot"] == (pairs if fused else 0), (what, k)
+        assert k["wf_shade_reorder"] == (pairs if sched.get("reorder") else 0), (what, k)
+        assert k["wf_shade_matsort"] == (pairs if sched.get("matsort") else 0), (what, k)
+    assert sum(k.values()) - k["wf_shade_reorder"] - k["wf_shade_matsort"] - k["wf_finish_requeue"] == got.launches, (what, k)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case,kw,tables", TABLE_CASES, ids=[c[0] for c in TABLE_CASES])
+def test_shading_past_the_staged_tables_and_the_packed_word(gpu_scenes, dev_scenes, oracle, case, kw, tables):
+    """Each table configuration on every schedule: the megakernel unsliced and sliced, the wavefront renderer's one launch unsliced and sliced
+    (both stage the tables), its per-bounce schedules split and fused (the dense SHADE kernel: memory only), and re-ordered with the material
+    sort, whose key reads the material with and without the packed word. Frame, unorm8 image and ray count bit for bit the oracle's (brute
+    force), and the launch counts prove each schedule ran. The scene's table state and the hits of its primary rays prove which shading path
+    the frame has to take."""
+    t = dev_scenes("tables", **kw).shading_tables()
+    assert (t["packed_mat"], t["lds_nm"], t["lds_mats"]) == tables
+    gs = gpu_scenes("tables", **kw)
+    sd = gs.desc
+    mats, rows = _table_hits(oracle, sd, t if t["packed_mat"] else None)
+    staged = (mats < 24) & (rows < 8) if rows is not None else np.zeros(mats.shape, bool)
+    if case == "staged":
+        assert staged.all() and t["rows"].shape[0] == 8
+    elif case == "one_past":
+        assert (mats == 24).any() and (rows == 8).any() and staged.any()
+    elif case == "many":
+        assert (mats >= 24).any() and (rows >= 8).any() and (~staged).mean() > 0.5
+    elif case == "packed_4096":
+        assert (mats == 4095).any() and (mats < 24).any() and staged.any()
+    else:
+        assert (mats == 4096).any() and (mats < 24).any()
+    cam = Camera.for_scene(sd, (TABLE_W, TABLE_H))
+    want = {kind: _oracle_frame(oracle, sd, TABLE_W, TABLE_H, kind, TABLE_DEPTH, TABLE_SPP, use_bvh=False) for _cls, kind in KINDS}
+    for what, cls, sched in TABLE_SCHEDULES:
+        what = f"{case}: {what}"
+        r = cls(gs, (TABLE_W, TABLE_H), TABLE_DEPTH, TABLE_SPP)
+        r.set_schedule(**sched)
+        got = r.render_frame(cam)
+        _assert_table_schedule_ran(got, cls, sched, what)
+        f, b, rays = want[cls.KIND]
+        _assert_frames_equal(got.rgba_f32, got.rgba_u8, got.rays, f, b, rays, what)
+        r.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case,kw,tables", [c for c in TABLE_CASES if c[1]["n_mats"] > 24], ids=[c[0] for c in TABLE_CASES if c[1]["n_mats"] > 24])
+def test_scatter_probe_reads_high_material_indices(gpu_scenes, oracle, case, kw, tables):
+    """rt_probe_scatter on materials 24, 4095 and 4096 where the scene has them (and its first and last): the probe and the oracle read the
+    same record at high indices, bit for bit."""
+    gs = gpu_scenes("tables", **kw)
+    sd = gs.desc
+    osc = oracle.OracleScene(sd)
+    rng = np.random.default_rng(24)
+    n = 4096
+    dirs, nrm = _unit(rng.normal(size=(n, 3))), _unit(rng.normal(size=(n, 3)))
+    uv = rng.uniform(-3, 3, (n, 2)).astype(np.float32)
+    seeds = rng.integers(0, 2 ** 32, n, dtype=np.uint64).astype(np.uint32)
+    for m in sorted({0, 24, 4095, 4096, len(sd.materials) - 1} & set(range(len(sd.materials)))):
+        g, e = gs.scatter(m, dirs, nrm, uv, seeds), osc.scatter(m, dirs, nrm, uv, seeds)
+        for a, b, part in zip(g, e, ("ok flag", "direction", "attenuation", "rng state")):
+            np.testing.assert_array_equal(a, b, err_msg=f"{case} material {m}: {part}")

@@ -2,8 +2,9 @@
 // Karras' binary radix tree, bottom-up refit, breadth-first collapse to the quantised BVH4 the traversal
 // kernels use. It replaces the host builder when scene (re)build time matters (the
 // reference rebuilds through Embree's rtcCommitScene, src/scene.cpp:101-107). The image does not depend on
-// the tree, so this builder is validated structurally (rt_scene_check_bvh on the downloaded tree) and by
-// the same render parity tests as the host builders.
+// the tree, so this builder is validated structurally (rt_scene_check_bvh on the downloaded tree), by the
+// same render parity tests as the host builders, and node for node against a model of the tree it must
+// build (tests/test_gpu_lbvh.py).
 //
 // Pipeline (all on one stream):
 //   k_prims    world-space triangle boxes + 63-bit Morton code of the box centre, key = code
@@ -137,15 +138,20 @@ __global__ void __launch_bounds__(256) k_refit(int n, const uint32_t* __restrict
 
 __device__ __forceinline__ float grid_step_dev(uint32_t biased_exp) { return __uint_as_float(biased_exp << 23); }
 
-// quantises the padded boxes of the nk children of one node (same rules as the host's quantise_node)
-__device__ void quantise_node_dev(BvhNode& n, int nk, const Box3* kb, float pad) {
+// quantises the padded boxes of the nk children of one node (same rules as the host's quantise_node). Returns false, like the host's,
+// on a non-finite padded box or when no grid step up to 2^121 fits; every word is written all the same (an axis that did not fit keeps
+// the empty pattern qlo 255, qhi 0), so a failed node holds nothing stale.
+__device__ bool quantise_node_dev(BvhNode& n, int nk, const Box3* kb, float pad) {
     float nlo[3];
     n.scale_x = n.scale_y = n.scale_z = 1.0f;
+    n.origin[0] = n.origin[1] = n.origin[2] = 0.0f;
+    for (int i = 0; i < 6; ++i) n.q[i] = (i & 1) ? 0u : 0xFFFFFFFFu;
     for (int a = 0; a < 3; ++a) {
         float lo = kb[0].lo[a] - pad, hi = kb[0].hi[a] + pad;
         for (int k = 1; k < nk; ++k) lo = fminf(lo, kb[k].lo[a] - pad), hi = fmaxf(hi, kb[k].hi[a] + pad);
         nlo[a] = lo;
         n.origin[a] = lo;
+        if (!isfinite(lo) || !isfinite(hi)) return false;
         const double ext = (double)hi - (double)lo;
         int e = ext > 0 ? (int)ceil(log2(ext / 255.0)) : -100;
         e = e < -100 ? -100 : (e > 100 ? 100 : e);
@@ -174,9 +180,10 @@ __device__ void quantise_node_dev(BvhNode& n, int nk, const Box3* kb, float pad)
                 else n.scale_z = s;
                 break;
             }
-            if (e > 120) break;
+            if (e > 120) return false;
         }
     }
+    return true;
 }
 
 // frontier entry: binary internal node -> BVH4 node slot
@@ -184,7 +191,8 @@ __global__ void __launch_bounds__(128) k_emit(uint32_t n_in, const int2* __restr
                                                unsigned int* __restrict__ node_counter, unsigned int* __restrict__ out_count,
                                                const int* __restrict__ left, const int* __restrict__ right,
                                                const uint32_t* __restrict__ sorted_tri, const Box3* __restrict__ tri_box,
-                                               const Box3* __restrict__ node_box, float pad, BvhNode* __restrict__ nodes) {
+                                               const Box3* __restrict__ node_box, float pad, BvhNode* __restrict__ nodes,
+                                               unsigned int* __restrict__ failed) {
     const uint32_t i = blockIdx.x * 128u + threadIdx.x;
     if (i >= n_in) return;
     const int b = frontier_in[i].x, slot = frontier_in[i].y;
@@ -198,7 +206,7 @@ __global__ void __launch_bounds__(128) k_emit(uint32_t n_in, const int2* __restr
     Box3 kb[4];
     for (int k = 0; k < nk; ++k) kb[k] = kids[k] >= 0 ? node_box[kids[k]] : tri_box[sorted_tri[~kids[k]]];
     BvhNode out;
-    quantise_node_dev(out, nk, kb, pad);
+    if (!quantise_node_dev(out, nk, kb, pad)) atomicOr(failed, 1u); // the host turns it into an error after the level
     for (int k = 0; k < 4; ++k) {
         if (k >= nk) { out.child[k] = kChildEmpty; continue; }
         if (kids[k] < 0) {
@@ -269,8 +277,8 @@ int build_lbvh_gpu(HostScene& hs, const std::vector<TriRec>& gtris, std::string&
     hipLaunchKernelGGL(k_permute, dim3(g256), dim3(256), 0, 0, n, d_sorted, d_gtris, d_tris);
     LB_CHK(hipGetLastError());
 
-    // breadth-first emission, one launch per BVH4 level; counters: [0] nodes allocated, [1] next frontier length
-    unsigned int h_counters[2] = {1u, 0u};
+    // breadth-first emission, one launch per BVH4 level; counters: [0] nodes allocated, [1] next frontier length, [2] quantisation failed
+    unsigned int h_counters[3] = {1u, 0u, 0u};
     int2 root = make_int2(0, 0);
     LB_CHK(hipMemcpy(d_front[0], &root, sizeof(root), hipMemcpyHostToDevice));
     uint32_t n_front = 1, level = 0;
@@ -280,9 +288,10 @@ int build_lbvh_gpu(HostScene& hs, const std::vector<TriRec>& gtris, std::string&
         h_counters[1] = 0;
         LB_CHK(hipMemcpy(d_counters, h_counters, sizeof(h_counters), hipMemcpyHostToDevice));
         hipLaunchKernelGGL(k_emit, dim3((n_front + 127u) / 128u), dim3(128), 0, 0, n_front, d_front[cur], d_front[cur ^ 1], d_counters,
-                           d_counters + 1, d_left, d_right, d_sorted, d_tri_box, d_node_box, hs.pad, d_nodes);
+                           d_counters + 1, d_left, d_right, d_sorted, d_tri_box, d_node_box, hs.pad, d_nodes, d_counters + 2);
         LB_CHK(hipGetLastError());
         LB_CHK(hipMemcpy(h_counters, d_counters, sizeof(h_counters), hipMemcpyDeviceToHost));
+        if (h_counters[2]) { err = "GPU LBVH: a node's child boxes could not be quantised (non-finite or beyond fp32)"; return RT_ERR_INVALID; }
         n_front = h_counters[1];
         cur ^= 1;
     }

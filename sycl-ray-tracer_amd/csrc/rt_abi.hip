@@ -356,5 +356,41 @@ int rt_dev_scene_tables(const rt_scene* s, uint32_t* packed_mat, uint32_t* lds_n
     return RT_OK;
 }
 
+// The scene's BVH as built, for the tests that hold the device-built tree against a model of it (tests/test_gpu_lbvh.py). Scalars:
+// n_nodes, n_tris (leaf-order records), n_wverts (floats), stack_need, built_by (RT_BVH_LBVH_GPU: built on the device; 99 =
+// RT_BVH_MEDIAN_INTERNAL: the balanced host fallback; else the host builder asked for); pad and bounds[6] (lo xyz, hi xyz) as the builder
+// used them. Arrays (each may be null, else takes the first `capacity` entries): nodes as raw 64-byte BvhNode records (the host copy: child
+// words are node indices), every leaf record's global_index, and the fp32 world-space vertices (9 per triangle, scene order).
+int rt_dev_scene_tree(const rt_scene* s, uint32_t* n_nodes, uint32_t* n_tris, uint32_t* n_wverts, uint32_t* stack_need, int32_t* built_by,
+                      float* pad, float* bounds, void* nodes, uint32_t* global_index, float* wverts, uint32_t capacity) {
+    if (!s || !n_nodes || !n_tris || !n_wverts || !stack_need || !built_by || !pad || !bounds) return fail(RT_ERR_INVALID, "null argument");
+    const HostScene& hs = s->hs;
+    *n_nodes = (uint32_t)hs.nodes.size(), *n_tris = (uint32_t)hs.tris.size(), *n_wverts = (uint32_t)hs.wverts.size();
+    *stack_need = hs.stack_need, *built_by = hs.built_by, *pad = hs.pad;
+    for (int a = 0; a < 3; ++a) bounds[a] = hs.bounds_lo[a], bounds[3 + a] = hs.bounds_hi[a];
+    if (nodes) std::memcpy(nodes, hs.nodes.data(), std::min<size_t>(capacity, hs.nodes.size()) * sizeof(BvhNode));
+    if (global_index)
+        for (size_t t = 0; t < std::min<size_t>(capacity, hs.tris.size()); ++t) global_index[t] = hs.tris[t].global_index;
+    if (wverts) std::memcpy(wverts, hs.wverts.data(), std::min<size_t>(capacity, hs.wverts.size()) * sizeof(float));
+    return RT_OK;
+}
+
+// Host only: the host quantiser (scene_build.cpp: quantise_node) on `count` nodes. nk[i] in 1..4 children; klo/khi: 4 x 3 floats per node,
+// the children's already padded boxes (entries past nk[i] are ignored); nodes_out: count 64-byte BvhNode records (origin, scales and
+// planes; child words kChildEmpty); ok[i] = 0 where quantise_node refused the node (a non-finite box or no grid step that fits).
+int rt_dev_quantise_node(uint32_t count, const int32_t* nk, const float* klo, const float* khi, void* nodes_out, uint8_t* ok) {
+    if (!nk || !klo || !khi || !nodes_out || !ok) return fail(RT_ERR_INVALID, "null argument");
+    BvhNode* out = static_cast<BvhNode*>(nodes_out);
+    for (uint32_t i = 0; i < count; ++i) {
+        if (nk[i] < 1 || nk[i] > 4) return fail(RT_ERR_INVALID, "nk must be 1..4");
+        BvhNode n{};
+        for (int k = 0; k < 4; ++k) n.child[k] = kChildEmpty;
+        ok[i] = quantise_node_dev_export(n, nk[i], reinterpret_cast<const float(*)[3]>(klo + 12 * (size_t)i),
+                                         reinterpret_cast<const float(*)[3]>(khi + 12 * (size_t)i)) ? 1 : 0;
+        out[i] = n;
+    }
+    return RT_OK;
+}
+
 } // extern "C"
 #endif

@@ -548,6 +548,10 @@ bool quantise_node(BvhNode& n, int nk, const float (*klo)[3], const float (*khi)
 
 } // namespace
 
+#ifdef RT_DEVELOPER_KNOBS
+bool quantise_node_dev_export(BvhNode& n, int nk, const float (*klo)[3], const float (*khi)[3]) { return quantise_node(n, nk, klo, khi); }
+#endif
+
 // Which binary nodes become BVH4 nodes: dynamic programme over the binary tree (after Ylitie, Karras, Laine 2017).
 // best[n][k] = least SAH cost of covering subtree n with at most k child slots of its BVH4 parent; a subtree that
 // takes one slot is a leaf or a BVH4 node of its own (area + the best way to hand its 4 slots to its two halves).
@@ -710,6 +714,7 @@ int build_host_scene(const rt_scene_desc* d, int bvh_kind, HostScene& hs, std::s
         return n;
     };
     if (T == 0) {
+        hs.built_by = bvh_kind;
         hs.nodes.assign(1, empty_node());
         hs.tris.assign(1, TriRec{}); // one dummy record so device pointers are never null
         hs.tris[0].global_index = kNoTri;
@@ -730,6 +735,11 @@ int build_host_scene(const rt_scene_desc* d, int bvh_kind, HostScene& hs, std::s
     // Moller-Trumbore t is ~1e-7 x scale, so a padded box can only cull triangles the exact test
     // would also miss ("culling is conservative").
     hs.pad = 2e-5f * std::max(ext, amax) + 1e-30f;
+    // Finite vertices can still span more than fp32 holds (x from -2e38 to 2e38): no builder can quantise such a scene, and every
+    // builder refuses it here alike, before one is chosen (the device quantiser would otherwise meet it only per node).
+    bool finite = std::isfinite(ext) && std::isfinite(hs.pad);
+    for (int a = 0; a < 3; ++a) finite = finite && std::isfinite(hs.bounds_lo[a] - hs.pad) && std::isfinite(hs.bounds_hi[a] + hs.pad);
+    if (!finite) { err = "scene extent overflows fp32 (the padded bounds are not finite)"; return RT_ERR_INVALID; }
 
     // Exact worst-case traversal stack need: at every level all siblings of the entered child may be waiting.
     std::function<uint32_t(int32_t)> need = [&](int32_t node) -> uint32_t {
@@ -750,6 +760,7 @@ int build_host_scene(const rt_scene_desc* d, int bvh_kind, HostScene& hs, std::s
         if (rc != RT_OK) return rc;
         hs.stack_need = need(0);
         if (hs.stack_need + 2 >= (uint32_t)kStackSize) return build_host_scene(d, RT_BVH_MEDIAN_INTERNAL, hs, err);
+        hs.built_by = RT_BVH_LBVH_GPU;
         // surface-area cost of the downloaded tree (the diagnostic rt_scene_info reports for the host builders too): every node's
         // children boxes decoded, inner child 1 step x area, leaf child (triangles) x area, relative to the root's area
         {
@@ -968,6 +979,7 @@ int build_host_scene(const rt_scene_desc* d, int bvh_kind, HostScene& hs, std::s
         err = "internal: BVH deeper than the traversal stack";
         return RT_ERR_INVALID;
     }
+    hs.built_by = bvh_kind == RT_BVH_LBVH_GPU ? RT_BVH_LBVH : bvh_kind; // (a GPU request for fewer than 8 triangles: the host LBVH)
     return RT_OK;
 }
 

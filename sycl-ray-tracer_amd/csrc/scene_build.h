@@ -22,6 +22,7 @@ struct HostScene {
     uint32_t n_split_triangles = 0;    // triangles the SAH builder's pre-splitting pass cut into several references
     uint32_t n_layers = 0;
     bool packed_mat = false;      // ShadeRec::instance = instance | material << 20 (rt_types.h)
+    int8_t built_by = -1;         // the builder that produced `nodes`: the requested kind, or RT_BVH_MEDIAN_INTERNAL after a fallback
     float sky[3] = {0.5f, 0.7f, 1.0f};
     float bounds_lo[3] = {0, 0, 0}, bounds_hi[3] = {0, 0, 0};
     float pad = 0.0f;             // absolute box padding used by the builder
@@ -36,6 +37,11 @@ int build_host_scene(const rt_scene_desc* desc, int bvh_kind, HostScene& out, st
 
 // lbvh_gpu.hip: BVH construction on the current HIP device; fills hs.nodes / hs.tris (downloaded copies).
 int build_lbvh_gpu(HostScene& hs, const std::vector<TriRec>& gtris, std::string& err);
+
+#ifdef RT_DEVELOPER_KNOBS
+// Developer library only: quantise_node (the host quantiser every host builder uses) on nk <= 4 already padded child boxes.
+bool quantise_node_dev_export(BvhNode& n, int nk, const float (*klo)[3], const float (*khi)[3]);
+#endif
 
 // Structural check used by rt_scene_check_bvh.
 int check_bvh(const HostScene& hs, std::string& err);

@@ -21,6 +21,7 @@ RT_TEX_COLOR, RT_TEX_IMAGE = 0, 1
 RT_RENDERER_MEGAKERNEL, RT_RENDERER_WAVEFRONT = 0, 1
 RT_SEED_DEFAULT, RT_SEED_WAVEFRONT, RT_SEED_MEGAKERNEL = 0, 1, 2
 RT_BVH_DEFAULT, RT_BVH_LBVH, RT_BVH_SAH, RT_BVH_LBVH_GPU = 0, 1, 2, 3
+RT_BVH_MEDIAN_INTERNAL = 99  # not a request: what rt_dev_scene_tree reports after a builder fell back to the balanced host tree
 RT_TEX_SIZE = 512
 RT_TEX_MAX_LAYERS = 128
 
@@ -251,6 +252,12 @@ DEV_PROTOTYPES = {
     # the scene's shading tables as built (csrc/rt_abi.hip; tests/test_gpu_parity.py, tests/test_host.py)
     "rt_dev_scene_tables": (C.c_int, [C.c_void_p, _P(C.c_uint32), _P(C.c_uint32), _P(C.c_uint32), _P(C.c_uint32), _P(C.c_float), C.c_uint32,
                                       _P(C.c_uint32)]),
+    # (scene, out n_nodes, out n_tris, out n_wverts, out stack_need, out built_by, out pad, out bounds[6], out nodes[64 B x capacity] | NULL,
+    #  out global_index[capacity] | NULL, out wverts[capacity] | NULL, capacity): the scene's BVH as built (csrc/rt_abi.hip; tests/test_gpu_lbvh.py)
+    "rt_dev_scene_tree": (C.c_int, [C.c_void_p, _P(C.c_uint32), _P(C.c_uint32), _P(C.c_uint32), _P(C.c_uint32), _P(C.c_int32), _P(C.c_float),
+                                    _P(C.c_float), C.c_void_p, _P(C.c_uint32), _P(C.c_float), C.c_uint32]),
+    # (count, nk[count], klo[count x 4 x 3], khi[count x 4 x 3], out nodes[64 B x count], out ok[count]): the host quantiser on padded boxes
+    "rt_dev_quantise_node": (C.c_int, [C.c_uint32, _P(C.c_int32), _P(C.c_float), _P(C.c_float), C.c_void_p, _P(C.c_uint8)]),
 }
 
 
@@ -264,3 +271,7 @@ def u32ptr(a):
 
 def u8ptr(a):
     return a.ctypes.data_as(_P(C.c_uint8))
+
+
+def i32ptr(a):
+    return a.ctypes.data_as(_P(C.c_int32))

@@ -92,6 +92,27 @@ class Scene:
         abi.check(self._lib.rt_dev_scene_tables(self.h, *args, abi.fptr(rows), n_rows.value, abi.u32ptr(words)), self._lib)
         return dict(packed_mat=packed.value, lds_nm=lds_nm.value, lds_mats=lds_mats.value, rows=rows, words=words)
 
+    def tree(self) -> dict:
+        """rt_dev_scene_tree, for a scene built by the DEVELOPER library: the BVH as built. `nodes` is the host copy of the node array as
+        (n_nodes, 16) uint32 words (64-byte BvhNode records, child words are node indices), `global_index` every leaf-order triangle's
+        scene index, `wverts` the fp32 world-space vertices the builder used as (n_triangles, 3, 3), `pad` and `bounds_lo/hi` its box
+        padding and scene bounds, `stack_need` the tree's worst-case traversal stack need and `built_by` the builder that produced it
+        (abi.RT_BVH_LBVH_GPU on the device, abi.RT_BVH_MEDIAN_INTERNAL after a fallback to the balanced host build)."""
+        if not hasattr(self._lib, "rt_dev_scene_tree"):
+            raise RuntimeError("tree() needs a scene of the developer library")
+        n_nodes, n_tris, n_wverts, stack_need = (C.c_uint32() for _ in range(4))
+        built_by, pad, bounds = C.c_int32(), C.c_float(), (C.c_float * 6)()
+        args = (C.byref(n_nodes), C.byref(n_tris), C.byref(n_wverts), C.byref(stack_need), C.byref(built_by), C.byref(pad), bounds)
+        abi.check(self._lib.rt_dev_scene_tree(self.h, *args, None, None, None, 0), self._lib)
+        cap = max(n_nodes.value, n_tris.value, n_wverts.value)
+        nodes = np.zeros((cap, 16), np.uint32)
+        gidx = np.zeros(cap, np.uint32)
+        wv = np.zeros(cap, np.float32)
+        abi.check(self._lib.rt_dev_scene_tree(self.h, *args, nodes.ctypes.data_as(C.c_void_p), abi.u32ptr(gidx), abi.fptr(wv), cap), self._lib)
+        b = np.frombuffer(bounds, np.float32).copy()
+        return dict(nodes=nodes[: n_nodes.value], global_index=gidx[: n_tris.value], wverts=wv[: n_wverts.value].reshape(-1, 3, 3),
+                    pad=np.float32(pad.value), bounds_lo=b[:3], bounds_hi=b[3:], stack_need=stack_need.value, built_by=built_by.value)
+
     def close(self):
         if self.h:
             self._lib.rt_scene_destroy(self.h)

@@ -328,6 +328,27 @@ int rt_render_frame_device(rt_renderer* r, const rt_camera* cam, void* d_rgba_f3
 int rt_render_frame_begin(rt_renderer* r, const rt_camera* cam, void* d_rgba_f32, void* d_rgba_u8, void* stream);
 int rt_render_frame_end(rt_renderer* r, rt_stats* stats);
 
+/* ---- Progressive rendering (no reference counterpart: the reference renders every frame from scratch, src/main.cpp:57-70).
+ * A pixel's samples are one sequential chain: one xorshift word and three fp32 sums, added in sample order. With progressive rendering
+ * on, every frame (rt_render_frame, _device, _begin + _end) also stores each pixel's final sums and RNG word, 16 bytes per pixel of the
+ * tile, and its output is unchanged. rt_render_frame_continue[_device] then adds `samples` samples to every pixel of the last frame, with
+ * that frame's camera, starting from the stored state, and writes sqrt(sum / total) as fp32 and unorm8 exactly as a frame does, total =
+ * the pixel's samples in all. The identity this guarantees: a frame of a samples followed by continuations of b1, b2, ... samples gives,
+ * bit for bit in both images and in the summed ray counts, the frame of a + b1 + b2 + ... samples — under every schedule a frame
+ * accepts, and for the strips of a multi-GPU split (rt_frame_gather after a host continuation gathers the accumulated image).
+ * rt_stats describes the call alone (its rays, launches, slices: a continuation of b samples is planned as a frame of b samples).
+ *   rt_renderer_set_progressive(r, 1) allocates the state, (r, 0) frees it; no frame may be in flight.
+ *   rt_render_frame_continue[_device] returns RT_ERR_INVALID when progressive rendering is off, when no frame has completed since it was
+ *   turned on or since the state was discarded, for samples == 0, and when the total would exceed 2^24 (past which (float)total is not
+ *   exact); RT_ERR_UNSUPPORTED under rt_schedule::hip_graph = 1. rt_renderer_set_tile, rt_renderer_set_schedule,
+ *   rt_renderer_set_russian_roulette and rt_renderer_set_progressive discard the state.
+ *   rt_renderer_accumulated_samples: the samples the stored state holds (0: nothing to continue). */
+int rt_renderer_set_progressive(rt_renderer* r, int enable);
+int rt_render_frame_continue(rt_renderer* r, uint32_t samples, float* rgba_f32, uint8_t* rgba_u8, rt_stats* stats);
+int rt_render_frame_continue_device(rt_renderer* r, uint32_t samples, void* d_rgba_f32, void* d_rgba_u8,
+                                    void* stream, rt_stats* stats);
+int rt_renderer_accumulated_samples(const rt_renderer* r, uint32_t* out);
+
 /* ---- Multi-GPU frame gather over xGMI (no reference counterpart: the reference renders on ONE device and hands its
  * single image to stbi_write_png, src/main.cpp:57-70, src/util.hpp:8-33). SURVEY §8(e): the frame is split into interleaved
  * strips (rt_renderer_set_tile), every GPU renders its strips into its own compact device buffer, and ONE collective brings

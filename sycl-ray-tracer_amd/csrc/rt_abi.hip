@@ -278,6 +278,7 @@ int rt_renderer_set_russian_roulette(rt_renderer* r, uint32_t start_bounce) {
     if (!r) return fail(RT_ERR_INVALID, "null renderer");
     if (r->rr_start != start_bounce) drop_graph(r); // the bounce flags are baked into the captured launches
     r->rr_start = start_bounce;
+    r->carry_samples = 0, r->carry_mode = 0; // (progressive rendering: the carried chains were rendered with the old paths' ends)
     return RT_OK;
 }
 
@@ -296,6 +297,7 @@ int rt_renderer_set_schedule(rt_renderer* r, const rt_schedule* s) {
     if (s->pixel_slices < -1 || s->pixel_slices > (int32_t)kMaxSlices) return fail(RT_ERR_INVALID, "pixel_slices: -1 (automatic), 0 or 1 (off), 2 .. 8");
     if (r->kind != RT_RENDERER_WAVEFRONT && (s->pixel_slices > 1 || s->pixel_slices < 0) == (r->sched.pixel_slices > 1 || r->sched.pixel_slices < 0)) { // the megakernel is one launch: only its pixel slices are a choice (their state buffer exists or not)
         r->sched = *s;
+        r->carry_samples = 0; // (progressive rendering: a new schedule discards the carried state)
         return RT_OK;
     }
     HIPCHK(hipSetDevice(r->scene->device));
@@ -320,6 +322,37 @@ int rt_render_frame_device(rt_renderer* r, const rt_camera* cam, void* d_rgba_f3
                            rt_stats* stats) {
     if (!r) return fail(RT_ERR_INVALID, "null renderer");
     return no_throw([&] { return render_impl(r, cam, (float*)d_rgba_f32, (uint8_t*)d_rgba_u8, stream ? (hipStream_t)stream : r->stream, stats); });
+}
+
+int rt_renderer_set_progressive(rt_renderer* r, int enable) {
+    if (!r) return fail(RT_ERR_INVALID, "null renderer");
+    if (r->frame_pending) return fail(RT_ERR_INVALID, "a frame is in flight (rt_render_frame_end first)");
+    HIPCHK(hipSetDevice(r->scene->device));
+    drop_graph(r); // (a captured frame stores the carried state or does not)
+    r->progressive = enable != 0;
+    const int rc = no_throw([&] { return alloc_carry(r); });
+    if (rc != RT_OK) r->progressive = false;
+    return rc;
+}
+
+int rt_render_frame_continue(rt_renderer* r, uint32_t samples, float* rgba_f32, uint8_t* rgba_u8, rt_stats* stats) {
+    if (!r) return fail(RT_ERR_INVALID, "null renderer");
+    int rc = no_throw([&] { return continue_impl(r, samples, rgba_f32 ? r->d_f32 : nullptr, rgba_u8 ? r->d_u8 : nullptr, r->stream, stats); });
+    if (rc != RT_OK) return rc;
+    if (rgba_f32 && r->n_local) HIPCHK(hipMemcpy(rgba_f32, r->d_f32, (size_t)r->n_local * 16, hipMemcpyDeviceToHost));
+    if (rgba_u8 && r->n_local) HIPCHK(hipMemcpy(rgba_u8, r->d_u8, (size_t)r->n_local * 4, hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+int rt_render_frame_continue_device(rt_renderer* r, uint32_t samples, void* d_rgba_f32, void* d_rgba_u8, void* stream, rt_stats* stats) {
+    if (!r) return fail(RT_ERR_INVALID, "null renderer");
+    return no_throw([&] { return continue_impl(r, samples, (float*)d_rgba_f32, (uint8_t*)d_rgba_u8, stream ? (hipStream_t)stream : r->stream, stats); });
+}
+
+int rt_renderer_accumulated_samples(const rt_renderer* r, uint32_t* out) {
+    if (!r || !out) return fail(RT_ERR_INVALID, "null argument");
+    *out = r->carry_samples;
+    return RT_OK;
 }
 
 int rt_render_frame_begin(rt_renderer* r, const rt_camera* cam, void* d_rgba_f32, void* d_rgba_u8, void* stream) {

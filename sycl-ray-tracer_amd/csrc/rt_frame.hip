@@ -41,7 +41,8 @@ void free_tile_buffers(rt_renderer* r) {
         if (p) (void)hipFree((void*)p);
         p = nullptr;
     };
-    fr(r->d_f32), fr(r->d_u8), fr(r->d_ray_counter), fr(r->d_stats), fr(r->d_slice_state);
+    fr(r->d_f32), fr(r->d_u8), fr(r->d_ray_counter), fr(r->d_stats), fr(r->d_slice_state), fr(r->d_carry);
+    r->carry_samples = 0; // (a new tile or schedule: the carried state is gone)
     for (auto& L : r->lanes) {
         fr(L.d_rng), fr(L.d_accum), fr(L.d_counts), fr(L.d_hits), fr(L.d_rq_entries), fr(L.d_rq_ctl), fr(L.d_extra), fr(L.d_cost), fr(L.d_tile_key), fr(L.d_tile_order);
         for (auto& q : L.q) fr(q.org_id), fr(q.a), fr(q.b), fr(q.c);
@@ -216,6 +217,7 @@ int alloc_tile_buffers_impl(rt_renderer* r) {
     HIPCHK(hipMemsetAsync(r->d_f32, 0, n_pad * 16, r->stream));
     HIPCHK(hipMemsetAsync(r->d_u8, 0, n_pad * 4, r->stream));
     HIPCHK(hipStreamSynchronize(r->stream));
+    if (r->progressive) HIPCHK(dalloc(&r->d_carry, n * 16)); // (no frame has filled it yet: carry_samples 0)
     if (r->kind == RT_RENDERER_MEGAKERNEL) {
         HIPCHK(dalloc((void**)&r->d_ray_counter, 8 * sizeof(unsigned long long))); // [0] ray count, [1] the frame's pixel cursor (low word)
         if (r->sched.pixel_slices != 0 && r->sched.pixel_slices != 1 && (uint64_t)n * 32u < (1ull << 31)) { // (the kernel addresses the state with 32-bit offsets)
@@ -451,7 +453,11 @@ int enqueue_wavefront(rt_renderer* r, float* d_f32, uint8_t* d_u8, hipStream_t s
         ext_grid[k] = (ext_waves + ext_wpb - 1u) / ext_wpb;
         if (int rc_ = fill_bytes(L.d_counts, 0, (L.h_counts.size() + (size_t)r->spp * D + (size_t)r->spp + 1) * 4, lane_stream(L), capturing)) return rc_;
         if (int rc_ = fill_bytes(L.d_extra, 0, L.h_extra.size() * 8, lane_stream(L), capturing)) return rc_;
-        hipLaunchKernelGGL(k_wf_init, dim3(grid[k]), dim3(256), 0, lane_stream(L), r->d_cam, L.tile, r->seed_mode, L.n_local, L.d_rng, L.d_accum);
+        if (r->carry_mode == 2) // a continuation: the chains go on from the carried state
+            hipLaunchKernelGGL(k_wf_init_carry, dim3(grid[k]), dim3(256), 0, lane_stream(L), L.n_local, (uint32_t)r->width, r->tile.strip_rows, K, k,
+                               (const u32x4*)r->d_carry, L.d_rng, L.d_accum);
+        else
+            hipLaunchKernelGGL(k_wf_init, dim3(grid[k]), dim3(256), 0, lane_stream(L), r->d_cam, L.tile, r->seed_mode, L.n_local, L.d_rng, L.d_accum);
         launches.add(RT_K_WF_INIT);
     }
     // the lanes' chains are enqueued round-robin, bounce by bounce, so their kernels interleave on the device
@@ -462,7 +468,7 @@ int enqueue_wavefront(rt_renderer* r, float* d_f32, uint8_t* d_u8, hipStream_t s
     for (uint32_t k = 0; k < K; ++k)
         if (r->lanes[k].n_local) chunk = std::min(chunk, wf_chunk(r, r->lanes[k].n_local));
     // cost ordering (one-launch schedule, one stream lane): sample 0 in a launch of its own, then all the others, most expensive blocks first
-    const bool lpt = K == 1 && r->lanes[0].n_tiles != 0 && chunk == r->spp && D0 == 0 && D > 0;
+    const bool lpt = K == 1 && r->lanes[0].n_tiles != 0 && wf_cost_order(r) && chunk == r->spp && D0 == 0 && D > 0;
     const bool shoot_frame = r->sched.fused_bounce && D0 > 0; // queues may hold holes: every launch counts its rays on the device
     for (uint32_t s = 0; s < r->spp;) {
         const uint32_t n_samples = lpt ? (s == 0 ? 1u : r->spp - 1u) : std::min(chunk, r->spp - s);
@@ -599,17 +605,20 @@ int enqueue_wavefront(rt_renderer* r, float* d_f32, uint8_t* d_u8, hipStream_t s
                     if (int rc_ = fill_bytes(L.d_rq_entries, 0xFF, (size_t)L.n_local * (n_samples - 1u) * 8, ls, capturing)) return rc_;
                     if (int rc_ = fill_bytes(L.d_rq_ctl, 0, 80 * 4, ls, capturing)) return rc_;
                 }
-#define RT_FINISH_LAUNCH(ST, RQ, SL)                                                                                                          \
-    hipLaunchKernelGGL((k_wf_finish<ST, RQ, false, SL>), dim3(fin_grid), dim3(kMegaBlock), 0, ls, S, r->d_cam, L.tile, L.q[buf[k]], counts + D0, \
+#define RT_FINISH_LAUNCH(ST, RQ, SL, CA)                                                                                                      \
+    hipLaunchKernelGGL((k_wf_finish<ST, RQ, false, SL, CA>), dim3(fin_grid), dim3(kMegaBlock), 0, ls, S, r->d_cam, L.tile, L.q[buf[k]], counts + D0, \
                        cursors + (size_t)s * D + D0, L.d_rng, L.d_accum, extra, D0, D, n_samples, r->rr_start,                                 \
                        ST ? r->d_stats : (unsigned long long*)nullptr, fq, chunk_slots, lpt && s == 0 ? L.d_cost : (uint8_t*)nullptr, QueueDev{}, (uint32_t*)nullptr, 0u,     \
                        shoot_frame ? 1u : 0u, r->d_frame, sl.n_slices)
-                if (sl.n_slices > 1u && r->d_stats) RT_FINISH_LAUNCH(true, false, true);
-                else if (sl.n_slices > 1u) RT_FINISH_LAUNCH(false, false, true);
-                else if (r->d_stats && req) RT_FINISH_LAUNCH(true, true, false);
-                else if (r->d_stats) RT_FINISH_LAUNCH(true, false, false);
-                else if (req) RT_FINISH_LAUNCH(false, true, false);
-                else RT_FINISH_LAUNCH(false, false, false);
+                const bool carry_in = r->carry_mode == 2;
+                if (sl.n_slices > 1u && r->d_stats && carry_in) RT_FINISH_LAUNCH(true, false, true, true);
+                else if (sl.n_slices > 1u && carry_in) RT_FINISH_LAUNCH(false, false, true, true);
+                else if (sl.n_slices > 1u && r->d_stats) RT_FINISH_LAUNCH(true, false, true, false);
+                else if (sl.n_slices > 1u) RT_FINISH_LAUNCH(false, false, true, false);
+                else if (r->d_stats && req) RT_FINISH_LAUNCH(true, true, false, false);
+                else if (r->d_stats) RT_FINISH_LAUNCH(true, false, false, false);
+                else if (req) RT_FINISH_LAUNCH(false, true, false, false);
+                else RT_FINISH_LAUNCH(false, false, false, false);
 #undef RT_FINISH_LAUNCH
                 if (r->profile_kernels) {
                     HIPCHK(hipEventRecord(e1, ls));
@@ -626,8 +635,12 @@ int enqueue_wavefront(rt_renderer* r, float* d_f32, uint8_t* d_u8, hipStream_t s
     for (uint32_t k = 0; k < K; ++k) {
         auto& L = r->lanes[k];
         if (L.n_local) {
-            hipLaunchKernelGGL(k_wf_resolve, dim3(grid[k]), dim3(256), 0, lane_stream(L), L.n_local, r->spp, (uint32_t)r->width,
-                               r->tile.strip_rows, K, k, L.d_accum, d_f32, d_u8);
+            if (r->carry_mode) // progressive: the pixels' state for the next continuation, and the mean over all their samples
+                hipLaunchKernelGGL(k_wf_resolve<true>, dim3(grid[k]), dim3(256), 0, lane_stream(L), L.n_local, r->carry_total, (uint32_t)r->width,
+                                   r->tile.strip_rows, K, k, L.d_accum, d_f32, d_u8, (const uint32_t*)L.d_rng, (u32x4*)r->d_carry);
+            else
+                hipLaunchKernelGGL(k_wf_resolve<false>, dim3(grid[k]), dim3(256), 0, lane_stream(L), L.n_local, r->spp, (uint32_t)r->width,
+                                   r->tile.strip_rows, K, k, L.d_accum, d_f32, d_u8, (const uint32_t*)nullptr, (u32x4*)nullptr);
             launches.add(RT_K_WF_RESOLVE);
         }
         L.n_hot = ne[k];
@@ -673,6 +686,16 @@ int enqueue_frame(rt_renderer* r, const rt_camera* cam, float* d_f32, uint8_t* d
             (void)hipFuncSetAttribute((const void*)k_megakernel<1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pad);
             (void)hipFuncSetAttribute((const void*)k_megakernel<2, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pad);
             (void)hipFuncSetAttribute((const void*)k_megakernel<2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pad);
+#define RT_MEGA_PAD_CA(CA)                                                                                                  \
+    (void)hipFuncSetAttribute((const void*)k_megakernel<0, false, CA>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pad); \
+    (void)hipFuncSetAttribute((const void*)k_megakernel<0, true, CA>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pad);  \
+    (void)hipFuncSetAttribute((const void*)k_megakernel<1, false, CA>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pad); \
+    (void)hipFuncSetAttribute((const void*)k_megakernel<1, true, CA>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pad);  \
+    (void)hipFuncSetAttribute((const void*)k_megakernel<2, false, CA>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pad); \
+    (void)hipFuncSetAttribute((const void*)k_megakernel<2, true, CA>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pad);
+            RT_MEGA_PAD_CA(1)
+            RT_MEGA_PAD_CA(2)
+#undef RT_MEGA_PAD_CA
         }
         hipEvent_t e0 = pool_event(r->ev_pool, 0), e1 = pool_event(r->ev_pool, 1);
         if (!e0 || !e1) return fail(RT_ERR_HIP, "hipEventCreate failed");
@@ -686,6 +709,7 @@ int enqueue_frame(rt_renderer* r, const rt_camera* cam, float* d_f32, uint8_t* d
         if (stats) stats->pixel_slices = sl.n_slices;
         // (h_frame is rewritten per frame: the previous frame of this renderer has been collected, frame_begin refuses a second one in flight)
         r->h_frame->cam = c, r->h_frame->sl = sl;
+        r->h_frame->carry = r->d_carry, r->h_frame->carry_total = r->carry_total;
         HIPCHK(hipMemcpyAsync(r->d_frame, r->h_frame, sizeof(MegaFrame), hipMemcpyHostToDevice, st));
         HIPCHK(hipEventRecord(e0, st));
         if (r->max_depth == 0) {
@@ -694,9 +718,16 @@ int enqueue_frame(rt_renderer* r, const rt_camera* cam, float* d_f32, uint8_t* d
             HIPCHK(hipMemsetAsync(r->d_stats, 0, 13 * sizeof(unsigned long long), st));
             HIPCHK(hipMemsetAsync(r->d_stats + 13, 0xff, 2 * sizeof(unsigned long long), st)); // the two atomicMin slots
             HIPCHK(hipMemsetAsync(r->d_stats + 15, 0, 9 * sizeof(unsigned long long), st));
-#define RT_MEGA_LAUNCH(ST, SL)                                                                                                                    \
-    hipLaunchKernelGGL((k_megakernel<ST, SL>), dim3(grid), dim3(kMegaBlock), pad, st, S, r->d_frame, c.width, c.height, r->tile, r->max_depth, r->spp, \
+#define RT_MEGA_LAUNCH_CA(ST, SL, CA)                                                                                                              \
+    hipLaunchKernelGGL((k_megakernel<ST, SL, CA>), dim3(grid), dim3(kMegaBlock), pad, st, S, r->d_frame, c.width, c.height, r->tile, r->max_depth, r->spp, \
                        r->seed_mode, r->rr_start, d_f32, d_u8, r->d_ray_counter, ST ? r->d_stats : (unsigned long long*)nullptr, sl.n_slices)
+// (progressive rendering: the instantiation that stores the pixels' state, or loads and stores it)
+#define RT_MEGA_LAUNCH(ST, SL)                                   \
+    do {                                                         \
+        if (r->carry_mode == 2) RT_MEGA_LAUNCH_CA(ST, SL, 2);    \
+        else if (r->carry_mode == 1) RT_MEGA_LAUNCH_CA(ST, SL, 1); \
+        else RT_MEGA_LAUNCH_CA(ST, SL, 0);                       \
+    } while (0)
             if (r->stats_level == 1) { // timing only
                 if (sl.n_slices > 1u) RT_MEGA_LAUNCH(1, true);
                 else RT_MEGA_LAUNCH(1, false);
@@ -706,6 +737,7 @@ int enqueue_frame(rt_renderer* r, const rt_camera* cam, float* d_f32, uint8_t* d
             if (sl.n_slices > 1u) RT_MEGA_LAUNCH(0, true);
             else RT_MEGA_LAUNCH(0, false);
 #undef RT_MEGA_LAUNCH
+#undef RT_MEGA_LAUNCH_CA
         }
         HIPCHK(hipGetLastError());
         HIPCHK(hipEventRecord(e1, st));
@@ -759,9 +791,67 @@ int enqueue_frame(rt_renderer* r, const rt_camera* cam, float* d_f32, uint8_t* d
     return RT_OK;
 }
 
+// The wavefront renderer's per-sample buffers (queue lengths, chunk cursors, extra-ray counters, the dynamic queue, the cost ordering's) are
+// sized for the frame's samples at allocation. A continuation of progressive rendering renders a different number of samples with the same
+// tile and schedule: the buffers that depend on it are re-sized here, before the frame is enqueued (for a frame of the renderer's own
+// sample count, sized as they are, this changes nothing). A failure leaves the renderer unusable, as a failed re-allocation does.
+int ensure_wf_sample_buffers_impl(rt_renderer* r, bool* changed) {
+    const uint32_t D = r->max_depth, spp = r->spp;
+    for (auto& L : r->lanes) {
+        const size_t nc = (size_t)spp * ((size_t)D + 1);
+        if (L.h_counts.size() != nc || L.h_extra.size() != (size_t)spp + 1) {
+            *changed = true;
+            (void)hipFree(L.d_counts), (void)hipFree(L.d_extra);
+            L.d_counts = nullptr, L.d_extra = nullptr;
+            HIPCHK(hipMalloc((void**)&L.d_counts, (nc + (size_t)spp * D + (size_t)spp + 1) * 4)); // as alloc_tile_buffers_impl
+            L.h_counts.resize(nc);
+            L.h_extra.resize((size_t)spp + 1);
+            HIPCHK(hipMalloc((void**)&L.d_extra, L.h_extra.size() * 8));
+        }
+        const uint32_t chunk = wf_chunk(r, L.n_local);
+        if (chunk > 1 && wf_uses_requeue(r) && (uint64_t)L.rq_capacity < (uint64_t)L.n_local * (chunk - 1u)) {
+            *changed = true;
+            (void)hipFree(L.d_rq_entries);
+            L.d_rq_entries = nullptr, L.rq_capacity = 0;
+            HIPCHK(hipMalloc((void**)&L.d_rq_entries, (size_t)L.n_local * (chunk - 1u) * 8));
+            L.rq_capacity = L.n_local * (chunk - 1u);
+            if (!L.d_rq_ctl) HIPCHK(hipMalloc((void**)&L.d_rq_ctl, 80 * 4));
+        }
+        if (!L.d_cost && wf_cost_order(r) && r->width % 8 == 0 && L.tile.local_rows % 8 == 0 && L.n_local) {
+            *changed = true;
+            HIPCHK(hipMalloc((void**)&L.d_cost, L.n_local));
+            HIPCHK(hipMalloc((void**)&L.d_tile_key, (size_t)(L.n_local / 64u) * 4));
+            HIPCHK(hipMalloc((void**)&L.d_tile_order, (size_t)(L.n_local / 64u) * 4));
+            L.n_tiles = L.n_local / 64u;
+        }
+    }
+    return RT_OK;
+}
+int ensure_wf_sample_buffers(rt_renderer* r) {
+    bool changed = false;
+    const int rc = ensure_wf_sample_buffers_impl(r, &changed);
+    if (changed) drop_graph(r); // (a captured frame holds the old buffers' addresses)
+    if (rc != RT_OK) {
+        const std::string msg = g_err;
+        free_tile_buffers(r);
+        r->unusable = true, r->n_local = 0, r->tile.local_rows = 0;
+        g_err = msg;
+    }
+    return rc;
+}
+
+int alloc_carry(rt_renderer* r) {
+    if (r->d_carry) (void)hipFree(r->d_carry);
+    r->d_carry = nullptr, r->carry_samples = 0;
+    if (!r->progressive || r->unusable) return RT_OK;
+    HIPCHK(hipMalloc(&r->d_carry, std::max<size_t>(r->n_local, 1) * 16));
+    return RT_OK;
+}
+
 // A frame is enqueued (frame_begin) and collected (frame_end) separately, so that a caller can keep a second frame
 // of ANOTHER renderer in flight meanwhile: its persistent waves move in as this frame's last pixels drain.
-int frame_begin(rt_renderer* r, const rt_camera* cam, float* d_f32, uint8_t* d_u8, hipStream_t st) {
+// (r->carry_mode: set by the caller, frame_begin or continue_impl)
+int frame_begin_impl(rt_renderer* r, const rt_camera* cam, float* d_f32, uint8_t* d_u8, hipStream_t st) {
     if (!r || !cam) return fail(RT_ERR_INVALID, "null renderer or camera");
     if (r->frame_pending) return fail(RT_ERR_INVALID, "the renderer's previous frame has not been collected (rt_render_frame_end)");
     if (r->unusable) return fail(RT_ERR_INVALID, "the renderer has no buffers: its last rt_renderer_set_tile / rt_renderer_set_schedule failed (call either again)");
@@ -769,6 +859,14 @@ int frame_begin(rt_renderer* r, const rt_camera* cam, float* d_f32, uint8_t* d_u
     if (!origin_in_contract_range(r->scene->hs, cam->center))
         return fail(RT_ERR_INVALID, "the camera lies more than 100 scene scales outside the scene's bounds: outside the range of the closest-hit contract (rt_intersect_batch)");
     HIPCHK(hipSetDevice(r->scene->device));
+    if (r->kind == RT_RENDERER_WAVEFRONT) {
+        const int rc0 = ensure_wf_sample_buffers(r);
+        if (rc0 != RT_OK) return rc0;
+    }
+    if (r->carry_mode) { // the carried state is about to be overwritten: nothing to continue unless this frame completes
+        r->carry_samples = 0;
+        if (r->carry_mode == 1) r->carry_cam = *cam;
+    }
     r->pending_stats = rt_stats{};
     r->pending_stats.hw_queues = r->hw_queues;
     r->pending_hot = 0;
@@ -788,6 +886,15 @@ int frame_begin(rt_renderer* r, const rt_camera* cam, float* d_f32, uint8_t* d_u
     r->pending_stream = st;
     r->frame_pending = true;
     return RT_OK;
+}
+
+int frame_begin(rt_renderer* r, const rt_camera* cam, float* d_f32, uint8_t* d_u8, hipStream_t st) {
+    if (!r) return fail(RT_ERR_INVALID, "null renderer or camera");
+    if (r->frame_pending) return fail(RT_ERR_INVALID, "the renderer's previous frame has not been collected (rt_render_frame_end)");
+    // progressive rendering: a frame stores its pixels' state, renders the renderer's own sample count and starts the count over
+    r->carry_mode = r->progressive && r->d_carry ? 1 : 0;
+    r->carry_total = r->spp;
+    return frame_begin_impl(r, cam, d_f32, d_u8, st);
 }
 
 int frame_end(rt_renderer* r, rt_stats* stats) {
@@ -884,12 +991,37 @@ int frame_end(rt_renderer* r, rt_stats* stats) {
                          (h[15] - h[13]) * 1e-5, (h[14] - h[13]) * 1e-5, (h[15] - h[14]) * 1e-5, 100.0 * (h[15] - h[14]) / (h[15] - h[13]));
     }
     if (stats) *stats = local;
+    if (r->carry_mode) r->carry_samples = r->carry_total;
     return RT_OK;
 }
 
 int render_impl(rt_renderer* r, const rt_camera* cam, float* d_f32, uint8_t* d_u8, hipStream_t st, rt_stats* stats) {
     const int rc = frame_begin(r, cam, d_f32, d_u8, st);
     return rc != RT_OK ? rc : frame_end(r, stats);
+}
+
+// Progressive rendering: `samples` more samples for every pixel of the last frame, from the state it left. The launch is a frame of `samples`
+// samples in every respect (slice plan, slice tags, per-sample buffers, statistics) but where a pixel's chain starts and ends: that is what makes
+// a frame of a samples and a continuation of b the frame of a + b, bit for bit.
+int continue_impl(rt_renderer* r, uint32_t samples, float* d_f32, uint8_t* d_u8, hipStream_t st, rt_stats* stats) {
+    if (!r) return fail(RT_ERR_INVALID, "null renderer");
+    if (r->frame_pending) return fail(RT_ERR_INVALID, "the renderer's previous frame has not been collected (rt_render_frame_end)");
+    if (!r->progressive) return fail(RT_ERR_INVALID, "progressive rendering is off (rt_renderer_set_progressive)");
+    if (r->kind == RT_RENDERER_WAVEFRONT && r->sched.hip_graph)
+        return fail(RT_ERR_UNSUPPORTED, "a continuation cannot run as a replayed hipGraph (rt_schedule::hip_graph = 1)");
+    if (r->carry_samples == 0)
+        return fail(RT_ERR_INVALID, "nothing to continue: no frame has completed since progressive rendering was turned on or its state was discarded");
+    if (samples == 0) return fail(RT_ERR_INVALID, "samples must be >= 1");
+    const uint64_t total = (uint64_t)r->carry_samples + samples;
+    if (total > (1ull << 24)) return fail(RT_ERR_INVALID, "more than 2^24 samples in all: their count would not be exact as a float");
+    if ((uint64_t)samples * ((uint64_t)r->max_depth + 1) > (1ull << 26)) return fail(RT_ERR_INVALID, "samples * max_depth too large");
+    const rt_camera cam = r->carry_cam;
+    const uint32_t spp = r->spp;
+    r->spp = samples, r->carry_mode = 2, r->carry_total = (uint32_t)total;
+    int rc = frame_begin_impl(r, &cam, d_f32, d_u8, st);
+    if (rc == RT_OK) rc = frame_end(r, stats);
+    r->spp = spp;
+    return rc;
 }
 
 } // namespace rtlib

@@ -214,6 +214,16 @@ struct rt_renderer {
     std::vector<hipEvent_t> ev_pool;
     // diagnostics: RT_MEGA_LDS_PAD=<bytes> of unused dynamic LDS per workgroup lowers the number of
     // resident workgroups per CU without touching the code; RT_MEGA_OCC=<waves per SIMD> sizes the persistent grid to match
+    // progressive rendering (rt_renderer_set_progressive): every pixel's chain state {sum r, sum g, sum b, RNG word}, 16 bytes per pixel of the
+    // tile in tile order, as the last frame or continuation left it. carry_samples: the samples it holds (0: none — no frame since the state was
+    // (re)allocated or discarded); carry_cam: the camera of the frame it belongs to. carry_mode / carry_total: what the frame being enqueued does
+    // with it (0 nothing, 1 store, 2 load and store; the samples the pixels hold at its end)
+    bool progressive = false;
+    void* d_carry = nullptr;
+    uint32_t carry_samples = 0;
+    rt_camera carry_cam{};
+    int carry_mode = 0;
+    uint32_t carry_total = 0;
     uint32_t hw_queues = 4; // GPU_MAX_HW_QUEUES as the host had set it when the renderer was created (4 = HIP's default): bounds the automatic stream lanes
     uint32_t mega_lds_pad = 0, mega_occ = kMegaWaves;
 };
@@ -230,4 +240,6 @@ int alloc_tile_buffers(rt_renderer* r);
 int frame_begin(rt_renderer* r, const rt_camera* cam, float* d_f32, uint8_t* d_u8, hipStream_t st);
 int frame_end(rt_renderer* r, rt_stats* stats);
 int render_impl(rt_renderer* r, const rt_camera* cam, float* d_f32, uint8_t* d_u8, hipStream_t st, rt_stats* stats);
+int alloc_carry(rt_renderer* r);
+int continue_impl(rt_renderer* r, uint32_t samples, float* d_f32, uint8_t* d_u8, hipStream_t st, rt_stats* stats);
 } // namespace rtlib

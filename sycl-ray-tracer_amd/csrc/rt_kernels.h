@@ -170,6 +170,23 @@ RT_DEV uint32_t frame_slice_bound(const MegaFrame* f, uint32_t j) { // bound[j],
                  : "s"(f), "s"(at));
     return v;
 }
+static_assert(offsetof(MegaFrame, carry) == 120 && offsetof(MegaFrame, carry_total) == 128, "frame_carry* below read MegaFrame by byte offset");
+RT_DEV u32x4* frame_carry(const MegaFrame* f) { // progressive rendering: the tile's carried state, {sum r, sum g, sum b, RNG word} per pixel
+    u32x2 p;
+    asm volatile("s_load_dwordx2 %0, %1, 0x78\n\t"
+                 "s_waitcnt lgkmcnt(0)"
+                 : "=&s"(p)
+                 : "s"(f));
+    return (u32x4*)(((unsigned long long)p.y << 32) | p.x);
+}
+RT_DEV uint32_t frame_carry_total(const MegaFrame* f) { // ... and the samples every pixel holds when this launch is done
+    uint32_t v;
+    asm volatile("s_load_dword %0, %1, 0x80\n\t"
+                 "s_waitcnt lgkmcnt(0)"
+                 : "=&s"(v)
+                 : "s"(f));
+    return v;
+}
 RT_DEV uint32_t frame_slice_wait_cap(const MegaFrame* f) {
     uint32_t v;
     asm volatile("s_load_dword %0, %1, 0x74\n\t"
@@ -205,7 +222,11 @@ RT_DEV lds_u32_word* slice_looks_word(const void __attribute__((address_space(3)
 // accumulators and two clock reads per round — the instantiation whose cycles per step and per shading round are the product's within a per
 // cent (the full one below holds ~20 more scalars through the loops and spills 32 dwords where the product spills 2: its rounds read 15 %
 // long); 2 FULL (RT_KERNEL_STATS=1): lanes per step kind, node visits in the LDS part of the tree, the frame's timeline as well.
-template <int STATS, bool SLICED>
+// CARRY (progressive rendering, rt_renderer_set_progressive): 0 the product; 1 a frame that also STORES every finished pixel's state {three sums,
+// RNG word} in frame_carry; 2 a continuation that LOADS that state where a pixel's chain starts (instead of pixel_seed and zero sums), stores it
+// again at the pixel's end and divides by frame_carry_total, the pixel's samples in all. `spp` and the slices stay those of this launch: a chain
+// of a + b samples is the same sequence of operations whether it runs in one launch or in two.
+template <int STATS, bool SLICED, int CARRY = 0>
 __global__ void __launch_bounds__(kMegaBlock, kMegaWaves) k_megakernel(SceneDev S, const MegaFrame* frame, int32_t width, int32_t height, TileDev tile,
                                                     uint32_t max_depth, uint32_t spp, uint32_t seed_mode, uint32_t rr_start, float* __restrict__ out_f32,
                                                     uint8_t* __restrict__ out_u8,
@@ -262,8 +283,14 @@ __global__ void __launch_bounds__(kMegaBlock, kMegaWaves) k_megakernel(SceneDev 
         if (x < width && ly < tile.local_rows && gy < height) {
             s = first;
             if (!SLICED || first == 0) {
-                rng = pixel_seed(x, gy, width, height, seed_mode);
-                *color_r = 0.0f, *color_g = 0.0f, *color_b = 0.0f;
+                if constexpr (CARRY == 2) { // the pixel goes on from where its previous launch left it
+                    const u32x4 c = frame_carry(frame)[pix];
+                    rng = c.w;
+                    *color_r = __uint_as_float(c.x), *color_g = __uint_as_float(c.y), *color_b = __uint_as_float(c.z);
+                } else {
+                    rng = pixel_seed(x, gy, width, height, seed_mode);
+                    *color_r = 0.0f, *color_g = 0.0f, *color_b = 0.0f;
+                }
                 depth = 0;
                 r = camera_ray(frame_camera(frame, width, height), x, gy, rng);
                 trav_begin(T, r.org, ray_dir(r), stack);
@@ -419,13 +446,18 @@ __global__ void __launch_bounds__(kMegaBlock, kMegaWaves) k_megakernel(SceneDev 
                         start = true;
                     } else { // pixel finished: mean, sqrt gamma, fp32 + unorm8 stores (src/render_megakernel.cpp:154-158)
                         live = false, pixel_finished = true;
-                        const float n = (float)spp;
+                        const float n = (float)(CARRY == 2 ? frame_carry_total(frame) : spp);
                         const f3 c = mk3(__builtin_sqrtf(*color_r / n), __builtin_sqrtf(*color_g / n), __builtin_sqrtf(*color_b / n));
                         const uint32_t o = pix;
                         if (out_f32) reinterpret_cast<float4*>(out_f32)[o] = make_float4(c.x, c.y, c.z, 1.0f);
                         if (out_u8)
                             reinterpret_cast<uint32_t*>(out_u8)[o] = (uint32_t)to_unorm8(c.x) | ((uint32_t)to_unorm8(c.y) << 8) |
                                                                      ((uint32_t)to_unorm8(c.z) << 16) | 0xff000000u;
+                        if constexpr (CARRY != 0) { // the pixel's state for the next continuation
+                            u32x4 w;
+                            w.x = __float_as_uint(*color_r), w.y = __float_as_uint(*color_g), w.z = __float_as_uint(*color_b), w.w = rng;
+                            frame_carry(frame)[o] = w;
+                        }
                     }
                 }
             }
@@ -482,6 +514,18 @@ __global__ void __launch_bounds__(256) k_wf_init(const CameraDev* __restrict__ c
     const int gy = tile_global_row(tile, ly);
     rng[i] = pixel_seed(x, gy, cam.width, cam.height, seed_mode);
     accum[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+}
+// ... a continuation (progressive rendering): the RNG words and sums the tile's last frame or continuation left in `carry` (tile order, one
+// {sum r, sum g, sum b, RNG word} per pixel), for the pixels of stream lane `lane_index` of `n_lanes` (the row mapping of k_wf_resolve)
+__global__ void __launch_bounds__(256) k_wf_init_carry(uint32_t n_local, uint32_t width, uint32_t strip_rows, uint32_t n_lanes, uint32_t lane_index,
+                                                        const u32x4* __restrict__ carry, uint32_t* __restrict__ rng, float4* __restrict__ accum) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n_local) return;
+    const uint32_t x = i % width, r = i / width;
+    const uint32_t row = ((r / strip_rows) * n_lanes + lane_index) * strip_rows + r % strip_rows;
+    const u32x4 c = carry[(size_t)row * width + x];
+    rng[i] = c.w;
+    accum[i] = make_float4(__uint_as_float(c.x), __uint_as_float(c.y), __uint_as_float(c.z), 0.0f);
 }
 
 // ---- K3: camera rays for every pixel of the tile into queue slot = local pixel index -----------------
@@ -840,7 +884,9 @@ RT_DEV void rq_store64(unsigned long long* p, unsigned long long v) { __hip_atom
 // leave the same bytes dirty in two L2s that do not know of each other (seen: a frame off in its last bits with eight slices). The
 // accumulator is written once, by the lane that finishes the pixel. The LDS for the sums is what the unsliced kernel spends on the cached
 // pixel coordinates (xg_lds): a sliced launch divides for them per sample.
-template <bool STATS, bool REQ, bool LIMIT = false, bool SLICED = false>
+// CARRY (SLICED only; a continuation of progressive rendering): a pixel's first slice starts from the sums k_wf_init_carry left in the accumulator,
+// not from zero. (The unsliced schedules add to the accumulator in memory and need no flag.)
+template <bool STATS, bool REQ, bool LIMIT = false, bool SLICED = false, bool CARRY = false>
 __global__ void __launch_bounds__(kMegaBlock, kMegaWaves) k_wf_finish(SceneDev S, const CameraDev* __restrict__ camp, TileDev tile, QueueDev qin,
                                                                     const uint32_t* __restrict__ count_in, uint32_t* __restrict__ cursor,
                                                                     uint32_t* __restrict__ rng_buf, float4* __restrict__ accum,
@@ -851,6 +897,7 @@ __global__ void __launch_bounds__(kMegaBlock, kMegaWaves) k_wf_finish(SceneDev S
                                                                     uint32_t qflags = 0, const MegaFrame* slices = nullptr, uint32_t n_slices = 1) {
     static_assert(!(REQ && LIMIT), "the dynamic queue and the per-bounce hand-over are different schedules");
     static_assert(!(SLICED && (REQ || LIMIT)), "pixel slices belong to the one-launch schedule");
+    static_assert(!CARRY || SLICED, "only the sliced schedule keeps a pixel's sums outside the accumulator");
     constexpr uint32_t kPend = 0x40000000u; // SLICED, in `depth`: the lane has taken a later slice of a pixel and waits for its state (as in k_megakernel)
     // qflags & 1 (every launch of a frame whose bounces are SHOOT launches): the input queue may hold HOLES (entries whose pixel id is
     // kNoRay: the unused tail of a workgroup's last output block, below) and is therefore longer than the number of rays in it, so every
@@ -1059,7 +1106,12 @@ __global__ void __launch_bounds__(kMegaBlock, kMegaWaves) k_wf_finish(SceneDev S
                                     rng = rng_buf[id]; // ScopedRng load (src/render_wavefront.cpp:15-32): held in a register until the lane lets the pixel go
                                     depth = first_depth;
                                     samples_left = n_samples, first_counted = !holes;
-                                    if (SLICED) *sum_r = 0.0f, *sum_g = 0.0f, *sum_b = 0.0f; // (k_wf_init left the accumulator at zero)
+                                    if (SLICED && CARRY) { // (k_wf_init_carry left the pixel's sums so far in the accumulator)
+                                        const float4 a = accum[id];
+                                        *sum_r = a.x, *sum_g = a.y, *sum_b = a.z;
+                                    } else if (SLICED) {
+                                        *sum_r = 0.0f, *sum_g = 0.0f, *sum_b = 0.0f; // (k_wf_init left the accumulator at zero)
+                                    }
                                     if (!REQ && n_samples > 1u && xg_packed) { // the pixel's coordinates for its later camera rays: two divisions ONCE per pixel
                                         const uint32_t w = (uint32_t)camp->width;
                                         *xg_word() = (id % w) | ((uint32_t)tile_global_row(tile, (int)(id / w)) << 16);
@@ -1281,9 +1333,13 @@ __global__ void __launch_bounds__(kMegaBlock, kMegaWaves) k_wf_finish(SceneDev S
 }
 
 // ---- K6 + K7: mean over samples, sqrt gamma, fp32 + unorm8 outputs ------------------------------------
+// `spp`: the samples the accumulator holds (a continuation: all of the pixel's samples so far). CARRY (progressive rendering): the pixel's
+// sums and final RNG word are also stored in `carry`, in tile order, for the next continuation
+template <bool CARRY = false>
 __global__ void __launch_bounds__(256) k_wf_resolve(uint32_t n_local, uint32_t spp, uint32_t width, uint32_t strip_rows,
                                                      uint32_t n_lanes, uint32_t lane_index, const float4* __restrict__ accum,
-                                                     float* __restrict__ out_f32, uint8_t* __restrict__ out_u8) {
+                                                     float* __restrict__ out_f32, uint8_t* __restrict__ out_u8,
+                                                     const uint32_t* __restrict__ rng, u32x4* __restrict__ carry) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= n_local) return;
     const float4 a = accum[i];
@@ -1297,6 +1353,11 @@ __global__ void __launch_bounds__(256) k_wf_resolve(uint32_t n_local, uint32_t s
     if (out_u8)
         reinterpret_cast<uint32_t*>(out_u8)[o] = (uint32_t)to_unorm8(c.x) | ((uint32_t)to_unorm8(c.y) << 8) |
                                                  ((uint32_t)to_unorm8(c.z) << 16) | 0xff000000u;
+    if (CARRY) {
+        u32x4 w;
+        w.x = __float_as_uint(a.x), w.y = __float_as_uint(a.y), w.z = __float_as_uint(a.z), w.w = rng[i];
+        carry[o] = w;
+    }
 }
 
 } // namespace rt

@@ -93,9 +93,14 @@ struct SliceCursor {
 // traversal loop, in a kernel that has none to spare (with the slices on top: 38 scalar registers spilled into vector lanes, 46 vector
 // registers into scratch, 122 -> 145 ms). frame_now() hides the pointer's origin from the compiler, or it would hoist the loads out of the
 // wave's loop again.
+// carry / carry_total: progressive rendering (rt_renderer_set_progressive): the tile's carried pixel state, one uint4 {sum r, sum g, sum b, RNG
+// word} per pixel, and the samples the pixels hold once this launch is done (what k_megakernel<.., CARRY = 2> divides by). Read only by the carry
+// instantiations.
 struct MegaFrame {
     CameraDev cam;
     SliceDev sl;
+    void* carry;
+    uint32_t carry_total;
 };
 
 // EXTEND (k_wf_extend)

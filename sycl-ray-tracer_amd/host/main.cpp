@@ -4,6 +4,8 @@
 //   -w,--wavefront         -m,--megakernel        neither => wavefront
 // Extensions (the reference hard-codes 1920x1080, one device, out.png):
 //   --width N --height N   --device N   --devices A,B,..   --out FILE   --bvh {sah,lbvh}   --rr N   --quiet
+//   --passes K             render -s samples, then continue the frame K - 1 times by -s samples (progressive rendering): the image of
+//                          K x -s samples, bit for bit; the statistics lines sum the passes' rays and times
 //   --schedule {default,per-sample,per-bounce,per-bounce-fused}   which of the wavefront renderer's schedules renders the frame
 //                          (rt_renderer_set_schedule; per-bounce = the reference's own: src/render_wavefront.cpp:396-417)
 // Prints the same lines as the reference (Loading scene, loader chatter, Sample n, the three statistics
@@ -31,6 +33,7 @@ static void usage(const char* argv0) {
                 "  --out FILE                  Output PNG (default out.png)\n"
                 "  --bvh sah|lbvh              BVH builder (default sah)\n"
                 "  --rr UINT                   Russian roulette from this bounce on (default 0 = off, as the reference)\n"
+                "  --passes UINT               progressive rendering: -s samples, then K - 1 continuations by -s samples (default 1)\n"
                 "  --schedule NAME             wavefront schedule: default (one launch per frame), per-sample, per-bounce (a launch pair per\n"
                 "                              bounce with compaction in between, the reference's), per-bounce-fused (one kernel per bounce)\n"
                 "  --quiet                     No loader chatter\n"
@@ -40,7 +43,7 @@ static void usage(const char* argv0) {
 }
 
 int main(int argc, const char* argv[]) {
-    uint32_t max_depth = 10, sample_count = 32, rr = 0;
+    uint32_t max_depth = 10, sample_count = 32, rr = 0, passes = 1;
     std::string scene_path = "./assets/sponza.glb", out_path = "out.png";
     bool use_wavefront = false, use_megakernel = false, quiet = false;
     int32_t width = 1920, height = 1080;
@@ -91,6 +94,10 @@ int main(int argc, const char* argv[]) {
         }
         else if (a == "--out") out_path = need(i);
         else if (a == "--rr") rr = to_u32("--rr", need(i));
+        else if (a == "--passes") {
+            passes = to_u32("--passes", need(i));
+            if (passes == 0) { std::fprintf(stderr, "--passes: expected at least 1\n"); return 105; }
+        }
         else if (a == "--quiet") quiet = true;
         else if (a == "--schedule") {
             const std::string v = need(i);
@@ -141,12 +148,14 @@ int main(int argc, const char* argv[]) {
             r->out_path = out_path;
             r->russian_roulette = rr;
             r->devices = devices;
+            r->passes = passes;
             renderer.reset(r);
         } else {
             auto* r = new raytracer::WavefrontRenderer({width, height}, image_buf.data(), max_depth, sample_count);
             r->out_path = out_path;
             r->russian_roulette = rr;
             r->devices = devices;
+            r->passes = passes;
             if (schedule_given) r->schedule = schedule, r->has_schedule = true;
             renderer.reset(r);
         }

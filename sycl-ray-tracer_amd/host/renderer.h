@@ -98,6 +98,9 @@ struct HipRendererBase : public IRenderer {
     // grouped ncclGather over xGMI and de-interleaves them there: the frame touches host memory once, for the PNG.
     // (The one-process-per-GPU form of the same gather is rtamd/dist.py + bench.py.)
     std::vector<int> devices;
+    // Extension: progressive rendering (rt_renderer_set_progressive). passes > 1 renders sample_count samples, then continues the frame
+    // passes - 1 times by sample_count samples (rt_render_frame_continue): the image of sample_count x passes samples, bit for bit.
+    uint32_t passes = 1;
     std::vector<rt_renderer*> tile_handles;
     rt_comm* comm = nullptr;
     rt_stats last{};
@@ -135,10 +138,20 @@ struct HipRendererBase : public IRenderer {
         for (uint32_t k = 0; k < G; ++k) {
             threads.emplace_back([&, k]() {
                 rt_renderer* h = tile_handles[k];
-                if (rt_renderer_set_russian_roulette(h, russian_roulette) != RT_OK ||
+                if (rt_renderer_set_russian_roulette(h, russian_roulette) != RT_OK || (passes > 1 && rt_renderer_set_progressive(h, 1) != RT_OK) ||
                     rt_render_frame_begin(h, &camera.c, nullptr, rt_renderer_tile_u8(h), nullptr) != RT_OK ||
-                    rt_render_frame_end(h, &st[k]) != RT_OK)
+                    rt_render_frame_end(h, &st[k]) != RT_OK) {
                     err[k] = rt_last_error(); // rt_last_error is per thread
+                    return;
+                }
+                for (uint32_t p = 1; p < passes; ++p) { // every rank continues its own strips, into its own tile buffer
+                    rt_stats more{};
+                    if (rt_render_frame_continue_device(h, sample_count, nullptr, rt_renderer_tile_u8(h), nullptr, &more) != RT_OK) {
+                        err[k] = rt_last_error();
+                        return;
+                    }
+                    add_stats(st[k], more);
+                }
             });
         }
         for (auto& t : threads) t.join();
@@ -155,10 +168,18 @@ struct HipRendererBase : public IRenderer {
         last.seconds = wall;
     }
 
+    // a continuation's statistics added to the frame's: what the stat lines report for all the passes together
+    static void add_stats(rt_stats& into, const rt_stats& more) {
+        into.rays += more.rays;
+        into.launches += more.launches;
+        into.seconds += more.seconds;
+        into.device_ms += more.device_ms;
+    }
+
     void render_frame(const Camera& camera, const Scene& scene) override {
         if (devices.size() > 1) {
             if (kind == RT_RENDERER_WAVEFRONT)
-                for (uint32_t s = 0; s < sample_count; ++s) std::printf("Sample %u\n", s);
+                for (uint32_t s = 0; s < sample_count * passes; ++s) std::printf("Sample %u\n", s);
             render_tiled(camera, scene);
             report_and_write(last.seconds); // tiles run concurrently: the frame time is the wall time of the slowest
             return;
@@ -171,9 +192,15 @@ struct HipRendererBase : public IRenderer {
             bound = &scene;
         }
         rt_check(rt_renderer_set_russian_roulette(handle, russian_roulette));
+        if (passes > 1) rt_check(rt_renderer_set_progressive(handle, 1));
         if (kind == RT_RENDERER_WAVEFRONT)
-            for (uint32_t s = 0; s < sample_count; ++s) std::printf("Sample %u\n", s); // src/render_wavefront.cpp:402
+            for (uint32_t s = 0; s < sample_count * passes; ++s) std::printf("Sample %u\n", s); // src/render_wavefront.cpp:402
         rt_check(rt_render_frame(handle, &camera.c, nullptr, image, &last));
+        for (uint32_t p = 1; p < passes; ++p) { // the image of the last pass holds all sample_count x passes samples
+            rt_stats more{};
+            rt_check(rt_render_frame_continue(handle, sample_count, nullptr, image, &more));
+            add_stats(last, more);
+        }
         report_and_write(last.device_ms * 1e-3);
     }
 

@@ -163,6 +163,10 @@ PROTOTYPES = {
     "rt_render_frame": (C.c_int, [C.c_void_p, _P(rt_camera), _P(C.c_float), _P(C.c_uint8), _P(rt_stats)]),
     "rt_render_frame_device": (C.c_int, [C.c_void_p, _P(rt_camera), C.c_void_p, C.c_void_p, C.c_void_p,
                                          _P(rt_stats)]),
+    "rt_renderer_set_progressive": (C.c_int, [C.c_void_p, C.c_int]),
+    "rt_render_frame_continue": (C.c_int, [C.c_void_p, C.c_uint32, _P(C.c_float), _P(C.c_uint8), _P(rt_stats)]),
+    "rt_render_frame_continue_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, _P(rt_stats)]),
+    "rt_renderer_accumulated_samples": (C.c_int, [C.c_void_p, _P(C.c_uint32)]),
     "rt_comm_create": (C.c_int, [C.c_int, _P(C.c_int), _P(C.c_void_p)]),
     "rt_comm_destroy": (None, [C.c_void_p]),
     "rt_comm_uses_rccl": (C.c_int, [C.c_void_p]),

@@ -235,6 +235,36 @@ class IRenderer:
         abi.check(self._lib.rt_render_frame_end(self.h, C.byref(st)), self._lib)
         return Frame.from_stats(None, None, st)
 
+    def set_progressive(self, enable: bool) -> None:
+        """rt_renderer_set_progressive: with it on, every frame also keeps each pixel's sums and RNG word (16 bytes per pixel), and
+        continue_frame() adds samples to the last frame: a frame of a samples continued by b is the frame of a + b, bit for bit."""
+        abi.check(self._lib.rt_renderer_set_progressive(self.h, int(bool(enable))), self._lib)
+
+    @property
+    def accumulated_samples(self) -> int:
+        """Samples every pixel of the last frame holds (0: nothing to continue)."""
+        n = C.c_uint32()
+        abi.check(self._lib.rt_renderer_accumulated_samples(self.h, C.byref(n)), self._lib)
+        return int(n.value)
+
+    def continue_frame(self, samples: int, want_f32: bool = True, want_u8: bool = True) -> Frame:
+        """rt_render_frame_continue: `samples` more samples for every pixel of the last frame, with its camera; the images are the mean
+        over all the pixel's samples, the Frame's statistics (rays, launches, slices) those of this call."""
+        rows, w = self.local_rows, self.img_size[0]
+        f = np.zeros((rows, w, 4), np.float32) if want_f32 else None
+        b = np.zeros((rows, w, 4), np.uint8) if want_u8 else None
+        st = abi.rt_stats()
+        abi.check(self._lib.rt_render_frame_continue(self.h, int(samples), abi.fptr(f) if want_f32 else None,
+                                                     abi.u8ptr(b) if want_u8 else None, C.byref(st)), self._lib)
+        return Frame.from_stats(f, b, st)
+
+    def continue_frame_device(self, samples: int, d_f32: int = 0, d_u8: int = 0, stream: int = 0) -> Frame:
+        """rt_render_frame_continue_device: as continue_frame, the outputs to DEVICE pointers; nothing is copied to host."""
+        st = abi.rt_stats()
+        abi.check(self._lib.rt_render_frame_continue_device(self.h, int(samples), C.c_void_p(d_f32 or None), C.c_void_p(d_u8 or None),
+                                                            C.c_void_p(stream or None), C.byref(st)), self._lib)
+        return Frame.from_stats(None, None, st)
+
     def close(self):
         if self.h:
             self._lib.rt_renderer_destroy(self.h)

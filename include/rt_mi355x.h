@@ -280,6 +280,7 @@ enum {
     RT_K_WF_RESOLVE = 10,
     RT_K_FILL_BLACK = 11,
     RT_K_WF_SHOOT = 12, /* k_wf_finish limited to one bounce: intersect + shade + compact, one launch per bounce (fused_bounce) */
+    RT_K_BLOCK_RESOLVE = 13, /* k_blocks_resolve: the megakernel's whole image of a block continuation (adaptive sampling) */
     RT_K_COUNT = 16
 };
 
@@ -348,6 +349,50 @@ int rt_render_frame_continue(rt_renderer* r, uint32_t samples, float* rgba_f32, 
 int rt_render_frame_continue_device(rt_renderer* r, uint32_t samples, void* d_rgba_f32, void* d_rgba_u8,
                                     void* stream, rt_stats* stats);
 int rt_renderer_accumulated_samples(const rt_renderer* r, uint32_t* out);
+
+/* ---- Adaptive sampling (no reference counterpart): continue a progressive frame only where it is still noisy.
+ * A BLOCK is an 8x8 pixel block of the renderer's tile: rt_renderer_block_grid gives blocks_x = ceil(width / 8) per row and blocks_y =
+ * ceil(local_rows / 8) rows; block b covers columns (b % blocks_x) * 8 ... + 7 and tile rows (b / blocks_x) * 8 ... + 7 (the tile's rows as
+ * rt_frame_gather lays them out, tile-local), as far as they lie in the image. Progressive rendering keeps, beside every pixel's chain state, a
+ * sample count per block: a frame sets every block to its spp, a continuation adds `samples` to every block, a block continuation to the blocks it
+ * lists. A pixel's chain is its own, so the identity of progressive rendering holds per pixel: every pixel whose block holds n samples is, bit
+ * for bit in both images, the pixel of a frame of n samples, and the rays of the calls sum to those of the frames of the blocks' totals.
+ * rt_renderer_accumulated_samples returns the SMALLEST block count (0: nothing to continue); rt_render_frame_continue stays valid after block
+ * continuations (every block gains `samples`).
+ *   rt_render_frame_continue_blocks[_device] renders `samples` more samples for the pixels of the n_blocks listed blocks (host memory, both
+ *   variants; any order, no index twice) and writes the tile's WHOLE current image: every other pixel gets sqrt(sum / its block's count) and its
+ *   unorm8, as a frame would. n_blocks == 0 traces nothing and writes the current image. RT_ERR_INVALID for an index out of range or listed
+ *   twice, samples == 0, a listed block whose count would exceed 2^24, and wherever rt_render_frame_continue refuses; RT_ERR_UNSUPPORTED under
+ *   hip_graph = 1, and on the wavefront renderer for every schedule but its one-launch default (finish_depth 0, samples_per_launch 0; with
+ *   max_depth 0 every schedule). rt_stats describes the call: its rays, launches and slices.
+ *   rt_renderer_block_samples: the blocks' counts, blocks_x * blocks_y of them in host memory (zeros when there is nothing to continue).
+ * Every call that renders a block first keeps a SNAPSHOT of it: its pixels' sums and its count as they were (16 bytes per pixel, 4 per block);
+ * a frame clears the snapshots. The policy compares a block with its snapshot (Dammertz et al., "A Hierarchical Automatic Stopping Condition for
+ * Monte Carlo Global Illumination", 2009: the two-image criterion, with "A" = the block as of its previous render). For a block B with count n and
+ * snapshot count n' (n' < n), for each pixel p of B that lies in the image:
+ *   I_p = sum_p / n, in linear RGB;
+ *   A_p = snapshot sum_p / n';
+ *   e_p = (|I_r - A_r| + |I_g - A_g| + |I_b - A_b|) / sqrt(eps + I_r + I_g + I_b), eps = 1e-4;
+ *   e_B = the mean of e_p over B's pixels that lie in the image.
+ * With b = n' (a doubling schedule) A holds exactly half of I's samples, the published setting. A block is ACTIVE when it has no snapshot yet
+ * (n' = 0: the first call after a frame), when n < min_samples, or when e_B >= threshold.
+ *   rt_renderer_adapt evaluates every block and writes the active ones, ascending, to blocks_out (room for blocks_x * blocks_y) and their number
+ *   to n_out; it renders nothing. rt_renderer_block_errors: the last evaluation's e_B per block (+inf where n' = 0; zeros before the first).
+ *   rt_render_frame_continue_adaptive[_device] evaluates, continues the active blocks by `samples` (as rt_render_frame_continue_blocks, whose
+ *   refusals it shares) and reports their number in n_blocks_out (may be null). It reads the list back to the host on the way: one small sync. */
+int rt_renderer_block_grid(const rt_renderer* r, uint32_t* blocks_x, uint32_t* blocks_y);
+int rt_render_frame_continue_blocks(rt_renderer* r, uint32_t samples, const uint32_t* blocks, uint32_t n_blocks,
+                                    float* rgba_f32, uint8_t* rgba_u8, rt_stats* stats);
+int rt_render_frame_continue_blocks_device(rt_renderer* r, uint32_t samples, const uint32_t* blocks, uint32_t n_blocks,
+                                           void* d_rgba_f32, void* d_rgba_u8, void* stream, rt_stats* stats);
+int rt_renderer_block_samples(const rt_renderer* r, uint32_t* out);
+int rt_renderer_adapt(rt_renderer* r, float threshold, uint32_t min_samples, uint32_t* blocks_out, uint32_t* n_out);
+int rt_render_frame_continue_adaptive(rt_renderer* r, uint32_t samples, float threshold, uint32_t min_samples,
+                                      float* rgba_f32, uint8_t* rgba_u8, rt_stats* stats, uint32_t* n_blocks_out);
+int rt_render_frame_continue_adaptive_device(rt_renderer* r, uint32_t samples, float threshold, uint32_t min_samples,
+                                             void* d_rgba_f32, void* d_rgba_u8, void* stream, rt_stats* stats,
+                                             uint32_t* n_blocks_out);
+int rt_renderer_block_errors(const rt_renderer* r, float* out);
 
 /* ---- Multi-GPU frame gather over xGMI (no reference counterpart: the reference renders on ONE device and hands its
  * single image to stbi_write_png, src/main.cpp:57-70, src/util.hpp:8-33). SURVEY §8(e): the frame is split into interleaved

@@ -355,6 +355,78 @@ int rt_renderer_accumulated_samples(const rt_renderer* r, uint32_t* out) {
     return RT_OK;
 }
 
+int rt_renderer_block_grid(const rt_renderer* r, uint32_t* blocks_x, uint32_t* blocks_y) {
+    if (!r || !blocks_x || !blocks_y) return fail(RT_ERR_INVALID, "null argument");
+    *blocks_x = ((uint32_t)r->width + 7u) / 8u, *blocks_y = ((uint32_t)r->tile.local_rows + 7u) / 8u;
+    return RT_OK;
+}
+
+int rt_renderer_block_samples(const rt_renderer* r, uint32_t* out) {
+    if (!r || !out) return fail(RT_ERR_INVALID, "null argument");
+    const size_t nb = (size_t)(((uint32_t)r->width + 7u) / 8u) * (((uint32_t)r->tile.local_rows + 7u) / 8u);
+    if (r->carry_samples == 0 || r->h_block_count.size() != nb) std::memset(out, 0, nb * 4); // nothing to continue
+    else std::memcpy(out, r->h_block_count.data(), nb * 4);
+    return RT_OK;
+}
+
+int rt_renderer_block_errors(const rt_renderer* r, float* out) {
+    if (!r || !out) return fail(RT_ERR_INVALID, "null argument");
+    return no_throw([&] { return block_errors(r, out); });
+}
+
+int rt_render_frame_continue_blocks(rt_renderer* r, uint32_t samples, const uint32_t* blocks, uint32_t n_blocks, float* rgba_f32, uint8_t* rgba_u8,
+                                    rt_stats* stats) {
+    if (!r) return fail(RT_ERR_INVALID, "null renderer");
+    int rc = no_throw([&] { return continue_blocks_impl(r, samples, blocks, n_blocks, rgba_f32 ? r->d_f32 : nullptr, rgba_u8 ? r->d_u8 : nullptr, r->stream, stats); });
+    if (rc != RT_OK) return rc;
+    if (rgba_f32 && r->n_local) HIPCHK(hipMemcpy(rgba_f32, r->d_f32, (size_t)r->n_local * 16, hipMemcpyDeviceToHost));
+    if (rgba_u8 && r->n_local) HIPCHK(hipMemcpy(rgba_u8, r->d_u8, (size_t)r->n_local * 4, hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+int rt_render_frame_continue_blocks_device(rt_renderer* r, uint32_t samples, const uint32_t* blocks, uint32_t n_blocks, void* d_rgba_f32, void* d_rgba_u8,
+                                           void* stream, rt_stats* stats) {
+    if (!r) return fail(RT_ERR_INVALID, "null renderer");
+    return no_throw([&] {
+        return continue_blocks_impl(r, samples, blocks, n_blocks, (float*)d_rgba_f32, (uint8_t*)d_rgba_u8, stream ? (hipStream_t)stream : r->stream, stats);
+    });
+}
+
+int rt_renderer_adapt(rt_renderer* r, float threshold, uint32_t min_samples, uint32_t* blocks_out, uint32_t* n_out) {
+    if (!r || !n_out) return fail(RT_ERR_INVALID, "null argument");
+    return no_throw([&]() -> int {
+        std::vector<uint32_t> blocks;
+        const int rc = adapt_impl(r, threshold, min_samples, blocks);
+        if (rc != RT_OK) return rc;
+        if (!blocks.empty() && !blocks_out) return fail(RT_ERR_INVALID, "null block list");
+        if (!blocks.empty()) std::memcpy(blocks_out, blocks.data(), blocks.size() * 4);
+        *n_out = (uint32_t)blocks.size();
+        return (int)RT_OK;
+    });
+}
+
+int rt_render_frame_continue_adaptive(rt_renderer* r, uint32_t samples, float threshold, uint32_t min_samples, float* rgba_f32, uint8_t* rgba_u8,
+                                      rt_stats* stats, uint32_t* n_blocks_out) {
+    if (!r) return fail(RT_ERR_INVALID, "null renderer");
+    int rc = no_throw([&] {
+        return continue_adaptive_impl(r, samples, threshold, min_samples, rgba_f32 ? r->d_f32 : nullptr, rgba_u8 ? r->d_u8 : nullptr, r->stream, stats,
+                                      n_blocks_out);
+    });
+    if (rc != RT_OK) return rc;
+    if (rgba_f32 && r->n_local) HIPCHK(hipMemcpy(rgba_f32, r->d_f32, (size_t)r->n_local * 16, hipMemcpyDeviceToHost));
+    if (rgba_u8 && r->n_local) HIPCHK(hipMemcpy(rgba_u8, r->d_u8, (size_t)r->n_local * 4, hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+int rt_render_frame_continue_adaptive_device(rt_renderer* r, uint32_t samples, float threshold, uint32_t min_samples, void* d_rgba_f32, void* d_rgba_u8,
+                                             void* stream, rt_stats* stats, uint32_t* n_blocks_out) {
+    if (!r) return fail(RT_ERR_INVALID, "null renderer");
+    return no_throw([&] {
+        return continue_adaptive_impl(r, samples, threshold, min_samples, (float*)d_rgba_f32, (uint8_t*)d_rgba_u8, stream ? (hipStream_t)stream : r->stream,
+                                      stats, n_blocks_out);
+    });
+}
+
 int rt_render_frame_begin(rt_renderer* r, const rt_camera* cam, void* d_rgba_f32, void* d_rgba_u8, void* stream) {
     if (!r) return fail(RT_ERR_INVALID, "null renderer");
     return no_throw([&] { return frame_begin(r, cam, (float*)d_rgba_f32, (uint8_t*)d_rgba_u8, stream ? (hipStream_t)stream : r->stream); });

@@ -224,6 +224,20 @@ struct rt_renderer {
     rt_camera carry_cam{};
     int carry_mode = 0;
     uint32_t carry_total = 0;
+    // adaptive sampling (rt_render_frame_continue_blocks, rt_renderer_adapt): the tile's 8x8 blocks, allocated with d_carry. d_blk holds, for
+    // N = max(blocks_x * blocks_y, 1): [0, N) every block's sample count, [N, 2N) its count at its snapshot (0: none), [2N, 3N) the last evaluation's
+    // active flags, [3N, 4N) its errors (fp32), [4N, 5N + 1) its compacted list {length, blocks...}, [5N + 1, 6N + 1) the list of the call being
+    // enqueued. d_snap: per pixel the carried state before the last call that rendered its block (16 B). h_blk: pinned, N + 1 words (the call's
+    // list on its way up, the evaluation's on its way down). h_block_count: the counts as the host knows them (valid while carry_samples != 0;
+    // carry_samples is then their minimum). carry_mode 3 (a block continuation): n_call_blocks blocks listed, lane_pixels[k] of their pixels in
+    // stream lane k (the wavefront renderer)
+    uint32_t blocks_x = 0, blocks_y = 0;
+    uint32_t* d_blk = nullptr;
+    void* d_snap = nullptr;
+    uint32_t* h_blk = nullptr;
+    std::vector<uint32_t> h_block_count;
+    uint32_t n_call_blocks = 0;
+    std::vector<uint32_t> lane_pixels;
     uint32_t hw_queues = 4; // GPU_MAX_HW_QUEUES as the host had set it when the renderer was created (4 = HIP's default): bounds the automatic stream lanes
     uint32_t mega_lds_pad = 0, mega_occ = kMegaWaves;
 };
@@ -242,4 +256,10 @@ int frame_end(rt_renderer* r, rt_stats* stats);
 int render_impl(rt_renderer* r, const rt_camera* cam, float* d_f32, uint8_t* d_u8, hipStream_t st, rt_stats* stats);
 int alloc_carry(rt_renderer* r);
 int continue_impl(rt_renderer* r, uint32_t samples, float* d_f32, uint8_t* d_u8, hipStream_t st, rt_stats* stats);
+int continue_blocks_impl(rt_renderer* r, uint32_t samples, const uint32_t* blocks, uint32_t n_blocks, float* d_f32, uint8_t* d_u8, hipStream_t st,
+                         rt_stats* stats);
+int adapt_impl(rt_renderer* r, float threshold, uint32_t min_samples, std::vector<uint32_t>& blocks);
+int continue_adaptive_impl(rt_renderer* r, uint32_t samples, float threshold, uint32_t min_samples, float* d_f32, uint8_t* d_u8, hipStream_t st,
+                           rt_stats* stats, uint32_t* n_blocks_out);
+int block_errors(const rt_renderer* r, float* out);
 } // namespace rtlib

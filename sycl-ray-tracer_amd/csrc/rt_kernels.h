@@ -187,6 +187,32 @@ RT_DEV uint32_t frame_carry_total(const MegaFrame* f) { // ... and the samples e
                  : "s"(f));
     return v;
 }
+static_assert(offsetof(MegaFrame, n_blocks) == 132 && offsetof(MegaFrame, blocks) == 136 && offsetof(MegaFrame, block_count) == 144,
+              "frame_blocks* below read MegaFrame by byte offset");
+RT_DEV uint32_t frame_n_blocks(const MegaFrame* f) { // a block continuation (adaptive sampling): the blocks in the launch's list
+    uint32_t v;
+    asm volatile("s_load_dword %0, %1, 0x84\n\t"
+                 "s_waitcnt lgkmcnt(0)"
+                 : "=&s"(v)
+                 : "s"(f));
+    return v;
+}
+RT_DEV const uint32_t* frame_blocks(const MegaFrame* f) { // ... the list (8x8 block indices of the tile, ascending)
+    u32x2 p;
+    asm volatile("s_load_dwordx2 %0, %1, 0x88\n\t"
+                 "s_waitcnt lgkmcnt(0)"
+                 : "=&s"(p)
+                 : "s"(f));
+    return (const uint32_t*)(((unsigned long long)p.y << 32) | p.x);
+}
+RT_DEV const uint32_t* frame_block_count(const MegaFrame* f) { // ... and the samples every block of the tile holds when this launch is done
+    u32x2 p;
+    asm volatile("s_load_dwordx2 %0, %1, 0x90\n\t"
+                 "s_waitcnt lgkmcnt(0)"
+                 : "=&s"(p)
+                 : "s"(f));
+    return (const uint32_t*)(((unsigned long long)p.y << 32) | p.x);
+}
 RT_DEV uint32_t frame_slice_wait_cap(const MegaFrame* f) {
     uint32_t v;
     asm volatile("s_load_dword %0, %1, 0x74\n\t"
@@ -225,7 +251,9 @@ RT_DEV lds_u32_word* slice_looks_word(const void __attribute__((address_space(3)
 // CARRY (progressive rendering, rt_renderer_set_progressive): 0 the product; 1 a frame that also STORES every finished pixel's state {three sums,
 // RNG word} in frame_carry; 2 a continuation that LOADS that state where a pixel's chain starts (instead of pixel_seed and zero sums), stores it
 // again at the pixel's end and divides by frame_carry_total, the pixel's samples in all. `spp` and the slices stay those of this launch: a chain
-// of a + b samples is the same sequence of operations whether it runs in one launch or in two.
+// of a + b samples is the same sequence of operations whether it runs in one launch or in two. 3: a BLOCK continuation (adaptive sampling): as 2,
+// but the cursor's slots are those of the 8x8 blocks in frame_blocks (slot p -> block frame_blocks[p >> 6]) and a pixel divides by its own block's
+// count in frame_block_count, loaded at the pixel's end.
 template <int STATS, bool SLICED, int CARRY = 0>
 __global__ void __launch_bounds__(kMegaBlock, kMegaWaves) k_megakernel(SceneDev S, const MegaFrame* frame, int32_t width, int32_t height, TileDev tile,
                                                     uint32_t max_depth, uint32_t spp, uint32_t seed_mode, uint32_t rr_start, float* __restrict__ out_f32,
@@ -239,7 +267,7 @@ __global__ void __launch_bounds__(kMegaBlock, kMegaWaves) k_megakernel(SceneDev 
     unsigned long long wall_begin = 0, wall_exhausted = 0;
     if (STATS >= 2) wall_begin = wall_clock64(); // 100 MHz, the same counter on every CU
     const uint32_t tiles_x = (uint32_t)(width + 7) >> 3, tiles_y = (uint32_t)(tile.local_rows + 7) >> 3;
-    const uint32_t n_slots = tiles_x * tiles_y * 64u; // pixel slots in 8x8-tile order (slots outside the image are skipped)
+    const uint32_t n_slots = (CARRY == 3 ? frame_n_blocks(frame) : tiles_x * tiles_y) * 64u; // pixel slots in 8x8-tile order (slots outside the image are skipped)
     const int lane = (int)(threadIdx.x & 63u);
     uint32_t* pixel_cursor = reinterpret_cast<uint32_t*>(ray_counter + 1);
     int x = 0, gy = 0;  // the lane's pixel: column, global row
@@ -275,7 +303,8 @@ __global__ void __launch_bounds__(kMegaBlock, kMegaWaves) k_megakernel(SceneDev 
     // (ONE frame-wide cursor. Round 1 cut the frame into a region per XCD, for L2 locality: +4 % then, -2 % ... -16 % once the kernel was bound
     // by instruction issue — all waves should advance over one front, or the frame's last pixels all lie in the slowest region. EXPERIMENTS.md)
     auto take_slot = [&](uint32_t p, uint32_t first) { // the slice of pixel slot p (8x8-tile order) that starts with sample `first` becomes this lane's; slots outside the image are skipped
-        const uint32_t t = p >> 6; // (slots in row order instead of 8x8 blocks: +-0 on both scenes)
+        uint32_t t = p >> 6; // (slots in row order instead of 8x8 blocks: +-0 on both scenes)
+        if constexpr (CARRY == 3) t = frame_blocks(frame)[t];
         x = (int)((t % tiles_x) * 8u + (p & 7u));
         const int ly = (int)((t / tiles_x) * 8u + ((p >> 3) & 7u));
         gy = tile_global_row(tile, ly);
@@ -283,7 +312,7 @@ __global__ void __launch_bounds__(kMegaBlock, kMegaWaves) k_megakernel(SceneDev 
         if (x < width && ly < tile.local_rows && gy < height) {
             s = first;
             if (!SLICED || first == 0) {
-                if constexpr (CARRY == 2) { // the pixel goes on from where its previous launch left it
+                if constexpr (CARRY >= 2) { // the pixel goes on from where its previous launch left it
                     const u32x4 c = frame_carry(frame)[pix];
                     rng = c.w;
                     *color_r = __uint_as_float(c.x), *color_g = __uint_as_float(c.y), *color_b = __uint_as_float(c.z);
@@ -446,7 +475,11 @@ __global__ void __launch_bounds__(kMegaBlock, kMegaWaves) k_megakernel(SceneDev 
                         start = true;
                     } else { // pixel finished: mean, sqrt gamma, fp32 + unorm8 stores (src/render_megakernel.cpp:154-158)
                         live = false, pixel_finished = true;
-                        const float n = (float)(CARRY == 2 ? frame_carry_total(frame) : spp);
+                        float n;
+                        if constexpr (CARRY == 3) // (a discarded branch captures nothing: the other instantiations compile as before)
+                            n = (float)frame_block_count(frame)[(pix / (uint32_t)width >> 3) * tiles_x + ((uint32_t)x >> 3)];
+                        else
+                            n = (float)(CARRY == 2 ? frame_carry_total(frame) : spp);
                         const f3 c = mk3(__builtin_sqrtf(*color_r / n), __builtin_sqrtf(*color_g / n), __builtin_sqrtf(*color_b / n));
                         const uint32_t o = pix;
                         if (out_f32) reinterpret_cast<float4*>(out_f32)[o] = make_float4(c.x, c.y, c.z, 1.0f);
@@ -886,7 +919,9 @@ RT_DEV void rq_store64(unsigned long long* p, unsigned long long v) { __hip_atom
 // pixel coordinates (xg_lds): a sliced launch divides for them per sample.
 // CARRY (SLICED only; a continuation of progressive rendering): a pixel's first slice starts from the sums k_wf_init_carry left in the accumulator,
 // not from zero. (The unsliced schedules add to the accumulator in memory and need no flag.)
-template <bool STATS, bool REQ, bool LIMIT = false, bool SLICED = false, bool CARRY = false>
+// BLOCKS (SLICED + CARRY; a block continuation of adaptive sampling): the queue holds only the pixels of the listed 8x8 blocks (k_wf_generate_blocks),
+// so a pixel id may lie past the queue's length: the slice state is addressed over the whole stream lane's pixels instead.
+template <bool STATS, bool REQ, bool LIMIT = false, bool SLICED = false, bool CARRY = false, bool BLOCKS = false>
 __global__ void __launch_bounds__(kMegaBlock, kMegaWaves) k_wf_finish(SceneDev S, const CameraDev* __restrict__ camp, TileDev tile, QueueDev qin,
                                                                     const uint32_t* __restrict__ count_in, uint32_t* __restrict__ cursor,
                                                                     uint32_t* __restrict__ rng_buf, float4* __restrict__ accum,
@@ -898,6 +933,7 @@ __global__ void __launch_bounds__(kMegaBlock, kMegaWaves) k_wf_finish(SceneDev S
     static_assert(!(REQ && LIMIT), "the dynamic queue and the per-bounce hand-over are different schedules");
     static_assert(!(SLICED && (REQ || LIMIT)), "pixel slices belong to the one-launch schedule");
     static_assert(!CARRY || SLICED, "only the sliced schedule keeps a pixel's sums outside the accumulator");
+    static_assert(!BLOCKS || CARRY, "a block continuation is a continuation");
     constexpr uint32_t kPend = 0x40000000u; // SLICED, in `depth`: the lane has taken a later slice of a pixel and waits for its state (as in k_megakernel)
     // qflags & 1 (every launch of a frame whose bounces are SHOOT launches): the input queue may hold HOLES (entries whose pixel id is
     // kNoRay: the unused tail of a workgroup's last output block, below) and is therefore longer than the number of rays in it, so every
@@ -990,7 +1026,8 @@ __global__ void __launch_bounds__(kMegaBlock, kMegaWaves) k_wf_finish(SceneDev S
     uint32_t chunk_end = chunk_pos + first_slots < n_total ? chunk_pos + first_slots : n_total;
     bool exhausted = chunk_pos >= n_total; // the sample-0 queue has no chunk left for this wave
     auto state_rsrc = [&](const SliceNow& sn) {
-        return __builtin_amdgcn_make_buffer_rsrc((void*)(((unsigned long long)sn.head.y << 32) | sn.head.x), 0, (int)(n * 32u), 0x00020000);
+        const uint32_t n_state = BLOCKS ? (uint32_t)tile.local_rows * (uint32_t)camp->width : n;
+        return __builtin_amdgcn_make_buffer_rsrc((void*)(((unsigned long long)sn.head.y << 32) | sn.head.x), 0, (int)(n_state * 32u), 0x00020000);
     };
     auto leave = [&]() { // SHOOT: the workgroup's last wave to exit marks the unused tail of the workgroup's output block
         if (!LIMIT) return;
@@ -1358,6 +1395,164 @@ __global__ void __launch_bounds__(256) k_wf_resolve(uint32_t n_local, uint32_t s
         w.x = __float_as_uint(a.x), w.y = __float_as_uint(a.y), w.z = __float_as_uint(a.z), w.w = rng[i];
         carry[o] = w;
     }
+}
+
+// ---- adaptive sampling: block continuations and the two-image error estimate ------------------------------------------------------
+// A block is an 8x8 pixel block of the tile: blocks_x = ceil(width / 8) per row, ceil(local_rows / 8) rows, tile-local row-major (block b covers
+// columns (b % blocks_x) * 8 ... + 7 and tile rows (b / blocks_x) * 8 ... + 7, as far as they lie in the tile). Per block the tile keeps its sample
+// count (`count`); per pixel a SNAPSHOT of the carried state before the last call that rendered its block (`snap`), and per block the count at that
+// time (`snap_count`, 0: no snapshot since the last frame).
+
+// One wave per block a call renders (list[i]; block i when `list` is null): the block's carried state becomes its snapshot, its count the snapshot's,
+// and its count grows by `samples`. The host has checked that no index appears twice: no two waves touch one block.
+__global__ void __launch_bounds__(256) k_blocks_begin(const uint32_t* __restrict__ list, uint32_t n_blocks, uint32_t blocks_x, uint32_t width,
+                                                       uint32_t local_rows, uint32_t samples, const u32x4* __restrict__ carry, u32x4* __restrict__ snap,
+                                                       uint32_t* __restrict__ count, uint32_t* __restrict__ snap_count) {
+    const uint32_t i = blockIdx.x * 4u + (threadIdx.x >> 6), w = threadIdx.x & 63u;
+    if (i >= n_blocks) return;
+    const uint32_t b = list ? list[i] : i;
+    const uint32_t x = (b % blocks_x) * 8u + (w & 7u), ly = (b / blocks_x) * 8u + (w >> 3);
+    if (x < width && ly < local_rows) snap[(size_t)ly * width + x] = carry[(size_t)ly * width + x];
+    if (w == 0) {
+        const uint32_t c = count[b];
+        snap_count[b] = c;
+        count[b] = c + samples;
+    }
+}
+
+// The whole image of the tile after a block continuation of the megakernel, from the carried sums: sqrt(sum / the pixel's block count), fp32 +
+// unorm8 — the operations of k_megakernel's pixel end. Enqueued BEFORE the megakernel, which then overwrites the pixels of the listed blocks.
+__global__ void __launch_bounds__(256) k_blocks_resolve(uint32_t n_local, uint32_t width, uint32_t blocks_x, const u32x4* __restrict__ carry,
+                                                         const uint32_t* __restrict__ count, float* __restrict__ out_f32, uint8_t* __restrict__ out_u8) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n_local) return;
+    const uint32_t x = i % width, ly = i / width;
+    const u32x4 a = carry[i];
+    const float n = (float)count[(ly >> 3) * blocks_x + (x >> 3)];
+    const f3 c = mk3(__builtin_sqrtf(__uint_as_float(a.x) / n), __builtin_sqrtf(__uint_as_float(a.y) / n), __builtin_sqrtf(__uint_as_float(a.z) / n));
+    if (out_f32) reinterpret_cast<float4*>(out_f32)[i] = make_float4(c.x, c.y, c.z, 1.0f);
+    if (out_u8)
+        reinterpret_cast<uint32_t*>(out_u8)[i] = (uint32_t)to_unorm8(c.x) | ((uint32_t)to_unorm8(c.y) << 8) |
+                                                 ((uint32_t)to_unorm8(c.z) << 16) | 0xff000000u;
+}
+
+// The wavefront renderer's camera rays of a block continuation: slot i of the list -> pixel i & 63 of block list[i >> 6] (the mapping of
+// k_wf_generate's tile_order), kept if it lies in the tile and in stream lane `lane_index`'s rows (strip k of the tile belongs to lane k % n_lanes),
+// and compacted into the queue: ballot + mbcnt in the wave, one atomic per wave on the queue's length (zero before the launch). Ragged right and
+// bottom blocks and lanes that own part of a block's rows simply keep fewer lanes. Which queue slot a pixel gets is the device's order: its chain,
+// sums and rays do not depend on it.
+__global__ void __launch_bounds__(256) k_wf_generate_blocks(const CameraDev* __restrict__ camp, TileDev tile, const uint32_t* __restrict__ list,
+                                                             uint32_t n_blocks, uint32_t tile_rows, uint32_t strip_rows, uint32_t n_lanes,
+                                                             uint32_t lane_index, uint32_t* __restrict__ rng, QueueDev q,
+                                                             uint32_t* __restrict__ count_out) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    const CameraDev cam = *camp;
+    const uint32_t width = (uint32_t)cam.width, blocks_x = (width + 7u) >> 3;
+    bool take = false;
+    uint32_t id = 0;
+    if (i < n_blocks * 64u) {
+        const uint32_t b = list[i >> 6], w = i & 63u;
+        const uint32_t x = (b % blocks_x) * 8u + (w & 7u), row = (b / blocks_x) * 8u + (w >> 3); // row of the renderer's tile
+        const uint32_t strip = row / strip_rows;
+        if (x < width && row < tile_rows && strip % n_lanes == lane_index) {
+            id = ((strip / n_lanes) * strip_rows + row % strip_rows) * width + x; // the pixel's index in the stream lane
+            take = true;
+        }
+    }
+    const unsigned long long m = __ballot(take);
+    if (m == 0ull) return; // (wave-uniform)
+    uint32_t base = 0;
+    if ((threadIdx.x & 63u) == 0u) base = atomicAdd(count_out, (uint32_t)__popcll(m));
+    base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
+    if (!take) return;
+    const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+    const int x = (int)(id % width), gy = tile_global_row(tile, (int)(id / width));
+    uint32_t st = rng[id];
+    const RayState r = gy < cam.height ? camera_ray(cam, x, gy, st) : RayState{};
+    rng[id] = st;
+    queue_store(q, base + rank, id, r);
+}
+
+// k_wf_resolve<true> of a block continuation: every pixel of the stream lane divides by its own block's count (the listed blocks' pixels hold their
+// new sums, every other pixel the carried ones k_wf_init_carry put in the accumulator), and its state goes back to `carry`
+__global__ void __launch_bounds__(256) k_wf_resolve_blocks(uint32_t n_local, uint32_t width, uint32_t strip_rows, uint32_t n_lanes, uint32_t lane_index,
+                                                            const uint32_t* __restrict__ count, const float4* __restrict__ accum,
+                                                            float* __restrict__ out_f32, uint8_t* __restrict__ out_u8,
+                                                            const uint32_t* __restrict__ rng, u32x4* __restrict__ carry) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n_local) return;
+    const float4 a = accum[i];
+    const uint32_t x = i % width, r = i / width;
+    const uint32_t row = ((r / strip_rows) * n_lanes + lane_index) * strip_rows + r % strip_rows;
+    const float n = (float)count[(row >> 3) * ((width + 7u) >> 3) + (x >> 3)];
+    const f3 c = mk3(__builtin_sqrtf(a.x / n), __builtin_sqrtf(a.y / n), __builtin_sqrtf(a.z / n));
+    const size_t o = (size_t)row * width + x;
+    if (out_f32) reinterpret_cast<float4*>(out_f32)[o] = make_float4(c.x, c.y, c.z, 1.0f);
+    if (out_u8)
+        reinterpret_cast<uint32_t*>(out_u8)[o] = (uint32_t)to_unorm8(c.x) | ((uint32_t)to_unorm8(c.y) << 8) |
+                                                 ((uint32_t)to_unorm8(c.z) << 16) | 0xff000000u;
+    u32x4 w;
+    w.x = __float_as_uint(a.x), w.y = __float_as_uint(a.y), w.z = __float_as_uint(a.z), w.w = rng[i];
+    carry[o] = w;
+}
+
+// The two-image error of every block (Dammertz et al.: include/rt_mi355x.h states the estimator), one wave per block, a lane per pixel. I = sum / n
+// from the carried state, A = snapshot sum / n' (the block before its last render); e_p = |I - A|_1 / sqrt(eps + I_r + I_g + I_b), e_B = the mean over
+// the block's pixels in the image (a fixed butterfly of shuffles: the same sum on every lane and in every run). No snapshot (n' = 0): +inf. A block
+// is ACTIVE when n' = 0, n < min_samples or e_B >= threshold.
+constexpr float kAdaptEps = 1e-4f;
+__global__ void __launch_bounds__(256) k_adapt_errors(uint32_t n_blocks, uint32_t blocks_x, uint32_t width, uint32_t local_rows,
+                                                       const u32x4* __restrict__ carry, const u32x4* __restrict__ snap,
+                                                       const uint32_t* __restrict__ count, const uint32_t* __restrict__ snap_count, float threshold,
+                                                       uint32_t min_samples, float* __restrict__ err, uint32_t* __restrict__ active) {
+    const uint32_t b = blockIdx.x * 4u + (threadIdx.x >> 6), w = threadIdx.x & 63u;
+    if (b >= n_blocks) return; // (wave-uniform)
+    const uint32_t n = count[b], n0 = snap_count[b];
+    const uint32_t x = (b % blocks_x) * 8u + (w & 7u), ly = (b / blocks_x) * 8u + (w >> 3);
+    const bool in = x < width && ly < local_rows;
+    float e = 0.0f;
+    if (in && n0 != 0u) {
+        const size_t o = (size_t)ly * width + x;
+        const u32x4 c = carry[o], a = snap[o];
+        const float fn = (float)n, fa = (float)n0;
+        const float ir = __uint_as_float(c.x) / fn, ig = __uint_as_float(c.y) / fn, ib = __uint_as_float(c.z) / fn;
+        const float ar = __uint_as_float(a.x) / fa, ag = __uint_as_float(a.y) / fa, ab = __uint_as_float(a.z) / fa;
+        e = (__builtin_fabsf(ir - ar) + __builtin_fabsf(ig - ag) + __builtin_fabsf(ib - ab)) / __builtin_sqrtf(kAdaptEps + ir + ig + ib);
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) e += __shfl_xor(e, off, 64);
+    const uint32_t n_in = (uint32_t)__popcll(__ballot(in)); // >= 1: every block of the grid has a pixel in the tile
+    if (w == 0) {
+        const float eb = n0 != 0u ? e / (float)n_in : __builtin_inff();
+        err[b] = eb;
+        active[b] = n0 == 0u || n < min_samples || eb >= threshold ? 1u : 0u;
+    }
+}
+
+// The active blocks as a list in ascending order, one workgroup: per 1024 blocks, ballot + mbcnt in each wave and the waves' counts through LDS.
+// out[0] = the list's length, out[1 ...] = the list.
+__global__ void __launch_bounds__(1024) k_adapt_compact(uint32_t n_blocks, const uint32_t* __restrict__ active, uint32_t* __restrict__ out) {
+    __shared__ uint32_t wave_n[16];
+    const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+    uint32_t base = 0;
+    for (uint32_t c = 0; c < n_blocks; c += 1024u) {
+        const uint32_t i = c + threadIdx.x;
+        const bool f = i < n_blocks && active[i] != 0u;
+        const unsigned long long m = __ballot(f);
+        if (lane == 0) wave_n[wv] = (uint32_t)__popcll(m);
+        __syncthreads();
+        uint32_t before = 0, total = 0;
+        for (uint32_t k = 0; k < 16u; ++k) {
+            const uint32_t v = wave_n[k];
+            before += k < wv ? v : 0u;
+            total += v;
+        }
+        const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+        if (f) out[1u + base + before + rank] = i;
+        base += total;
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) out[0] = base;
 }
 
 } // namespace rt

@@ -96,11 +96,17 @@ struct SliceCursor {
 // carry / carry_total: progressive rendering (rt_renderer_set_progressive): the tile's carried pixel state, one uint4 {sum r, sum g, sum b, RNG
 // word} per pixel, and the samples the pixels hold once this launch is done (what k_megakernel<.., CARRY = 2> divides by). Read only by the carry
 // instantiations.
+// n_blocks / blocks / block_count: a block continuation (adaptive sampling, rt_render_frame_continue_blocks): the launch's list of 8x8 blocks of the
+// tile (ascending block indices, tile-local row-major) and the tile's per-block sample counts, what k_megakernel<.., CARRY = 3> divides by. Read only
+// by that instantiation.
 struct MegaFrame {
     CameraDev cam;
     SliceDev sl;
     void* carry;
     uint32_t carry_total;
+    uint32_t n_blocks;
+    const uint32_t* blocks;
+    const uint32_t* block_count;
 };
 
 // EXTEND (k_wf_extend)

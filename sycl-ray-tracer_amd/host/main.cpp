@@ -6,6 +6,8 @@
 //   --width N --height N   --device N   --devices A,B,..   --out FILE   --bvh {sah,lbvh}   --rr N   --quiet
 //   --passes K             render -s samples, then continue the frame K - 1 times by -s samples (progressive rendering): the image of
 //                          K x -s samples, bit for bit; the statistics lines sum the passes' rays and times
+//   --adaptive T [--min-samples N]   with --passes: passes 2 .. K continue only the 8x8 blocks that are still noisy (adaptive sampling:
+//                          rt_render_frame_continue_adaptive, threshold T on the two-image error, blocks under N samples always continue)
 //   --schedule {default,per-sample,per-bounce,per-bounce-fused}   which of the wavefront renderer's schedules renders the frame
 //                          (rt_renderer_set_schedule; per-bounce = the reference's own: src/render_wavefront.cpp:396-417)
 // Prints the same lines as the reference (Loading scene, loader chatter, Sample n, the three statistics
@@ -34,6 +36,9 @@ static void usage(const char* argv0) {
                 "  --bvh sah|lbvh              BVH builder (default sah)\n"
                 "  --rr UINT                   Russian roulette from this bounce on (default 0 = off, as the reference)\n"
                 "  --passes UINT               progressive rendering: -s samples, then K - 1 continuations by -s samples (default 1)\n"
+                "  --adaptive FLOAT            adaptive sampling: passes 2 .. K continue only the 8x8 blocks whose two-image error is at\n"
+                "                              least this threshold (default: off, every pass continues every pixel)\n"
+                "  --min-samples UINT          with --adaptive: blocks with fewer samples always continue (default 0)\n"
                 "  --schedule NAME             wavefront schedule: default (one launch per frame), per-sample, per-bounce (a launch pair per\n"
                 "                              bounce with compaction in between, the reference's), per-bounce-fused (one kernel per bounce)\n"
                 "  --quiet                     No loader chatter\n"
@@ -43,7 +48,8 @@ static void usage(const char* argv0) {
 }
 
 int main(int argc, const char* argv[]) {
-    uint32_t max_depth = 10, sample_count = 32, rr = 0, passes = 1;
+    uint32_t max_depth = 10, sample_count = 32, rr = 0, passes = 1, min_samples = 0;
+    float adaptive = -1.0f; // < 0: off
     std::string scene_path = "./assets/sponza.glb", out_path = "out.png";
     bool use_wavefront = false, use_megakernel = false, quiet = false;
     int32_t width = 1920, height = 1080;
@@ -98,6 +104,13 @@ int main(int argc, const char* argv[]) {
             passes = to_u32("--passes", need(i));
             if (passes == 0) { std::fprintf(stderr, "--passes: expected at least 1\n"); return 105; }
         }
+        else if (a == "--adaptive") {
+            const std::string v = need(i);
+            char* end = nullptr;
+            adaptive = std::strtof(v.c_str(), &end);
+            if (v.empty() || *end || !(adaptive >= 0.0f)) { std::fprintf(stderr, "--adaptive: expected a threshold >= 0, got '%s'\n", v.c_str()); return 105; }
+        }
+        else if (a == "--min-samples") min_samples = to_u32("--min-samples", need(i));
         else if (a == "--quiet") quiet = true;
         else if (a == "--schedule") {
             const std::string v = need(i);
@@ -149,6 +162,7 @@ int main(int argc, const char* argv[]) {
             r->russian_roulette = rr;
             r->devices = devices;
             r->passes = passes;
+            r->adaptive = adaptive, r->min_samples = min_samples;
             renderer.reset(r);
         } else {
             auto* r = new raytracer::WavefrontRenderer({width, height}, image_buf.data(), max_depth, sample_count);
@@ -156,6 +170,7 @@ int main(int argc, const char* argv[]) {
             r->russian_roulette = rr;
             r->devices = devices;
             r->passes = passes;
+            r->adaptive = adaptive, r->min_samples = min_samples;
             if (schedule_given) r->schedule = schedule, r->has_schedule = true;
             renderer.reset(r);
         }

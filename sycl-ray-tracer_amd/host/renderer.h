@@ -101,6 +101,10 @@ struct HipRendererBase : public IRenderer {
     // Extension: progressive rendering (rt_renderer_set_progressive). passes > 1 renders sample_count samples, then continues the frame
     // passes - 1 times by sample_count samples (rt_render_frame_continue): the image of sample_count x passes samples, bit for bit.
     uint32_t passes = 1;
+    // Extension: adaptive sampling. adaptive >= 0: passes 2 .. K continue only the 8x8 blocks rt_renderer_adapt finds active (threshold
+    // `adaptive` on the two-image error, blocks under min_samples samples always) — rt_render_frame_continue_adaptive; every rank adapts its own
+    float adaptive = -1.0f;
+    uint32_t min_samples = 0;
     std::vector<rt_renderer*> tile_handles;
     rt_comm* comm = nullptr;
     rt_stats last{};
@@ -146,7 +150,10 @@ struct HipRendererBase : public IRenderer {
                 }
                 for (uint32_t p = 1; p < passes; ++p) { // every rank continues its own strips, into its own tile buffer
                     rt_stats more{};
-                    if (rt_render_frame_continue_device(h, sample_count, nullptr, rt_renderer_tile_u8(h), nullptr, &more) != RT_OK) {
+                    const int rc = adaptive >= 0.0f ? rt_render_frame_continue_adaptive_device(h, sample_count, adaptive, min_samples, nullptr,
+                                                                                                 rt_renderer_tile_u8(h), nullptr, &more, nullptr)
+                                                    : rt_render_frame_continue_device(h, sample_count, nullptr, rt_renderer_tile_u8(h), nullptr, &more);
+                    if (rc != RT_OK) {
                         err[k] = rt_last_error();
                         return;
                     }
@@ -198,7 +205,8 @@ struct HipRendererBase : public IRenderer {
         rt_check(rt_render_frame(handle, &camera.c, nullptr, image, &last));
         for (uint32_t p = 1; p < passes; ++p) { // the image of the last pass holds all sample_count x passes samples
             rt_stats more{};
-            rt_check(rt_render_frame_continue(handle, sample_count, nullptr, image, &more));
+            if (adaptive >= 0.0f) rt_check(rt_render_frame_continue_adaptive(handle, sample_count, adaptive, min_samples, nullptr, image, &more, nullptr));
+            else rt_check(rt_render_frame_continue(handle, sample_count, nullptr, image, &more));
             add_stats(last, more);
         }
         report_and_write(last.device_ms * 1e-3);

@@ -94,7 +94,8 @@ class rt_scene_info_t(C.Structure):
 RT_SCHED_ALL_BOUNCES = 0xFFFFFFFF
 # kernel families of rt_stats.launches_by_kernel (include/rt_mi355x.h)
 KERNELS = {"megakernel": 0, "wf_init": 1, "wf_generate": 2, "wf_extend": 3, "wf_shade": 4, "wf_shade_reorder": 5, "wf_shade_matsort": 6,
-           "wf_finish": 7, "wf_finish_requeue": 8, "wf_tile_order": 9, "wf_resolve": 10, "fill_black": 11, "wf_shoot": 12}
+           "wf_finish": 7, "wf_finish_requeue": 8, "wf_tile_order": 9, "wf_resolve": 10, "fill_black": 11, "wf_shoot": 12,
+           "block_resolve": 13}
 RT_K_COUNT = 16
 
 
@@ -167,6 +168,17 @@ PROTOTYPES = {
     "rt_render_frame_continue": (C.c_int, [C.c_void_p, C.c_uint32, _P(C.c_float), _P(C.c_uint8), _P(rt_stats)]),
     "rt_render_frame_continue_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, _P(rt_stats)]),
     "rt_renderer_accumulated_samples": (C.c_int, [C.c_void_p, _P(C.c_uint32)]),
+    "rt_renderer_block_grid": (C.c_int, [C.c_void_p, _P(C.c_uint32), _P(C.c_uint32)]),
+    "rt_render_frame_continue_blocks": (C.c_int, [C.c_void_p, C.c_uint32, _P(C.c_uint32), C.c_uint32, _P(C.c_float), _P(C.c_uint8), _P(rt_stats)]),
+    "rt_render_frame_continue_blocks_device": (C.c_int, [C.c_void_p, C.c_uint32, _P(C.c_uint32), C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                         _P(rt_stats)]),
+    "rt_renderer_block_samples": (C.c_int, [C.c_void_p, _P(C.c_uint32)]),
+    "rt_renderer_adapt": (C.c_int, [C.c_void_p, C.c_float, C.c_uint32, _P(C.c_uint32), _P(C.c_uint32)]),
+    "rt_render_frame_continue_adaptive": (C.c_int, [C.c_void_p, C.c_uint32, C.c_float, C.c_uint32, _P(C.c_float), _P(C.c_uint8), _P(rt_stats),
+                                                    _P(C.c_uint32)]),
+    "rt_render_frame_continue_adaptive_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_float, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                           _P(rt_stats), _P(C.c_uint32)]),
+    "rt_renderer_block_errors": (C.c_int, [C.c_void_p, _P(C.c_float)]),
     "rt_comm_create": (C.c_int, [C.c_int, _P(C.c_int), _P(C.c_void_p)]),
     "rt_comm_destroy": (None, [C.c_void_p]),
     "rt_comm_uses_rccl": (C.c_int, [C.c_void_p]),

@@ -265,6 +265,91 @@ class IRenderer:
                                                             C.c_void_p(stream or None), C.byref(st)), self._lib)
         return Frame.from_stats(None, None, st)
 
+    # ---- adaptive sampling (rt_mi355x.h): 8x8 blocks of the tile, tile-local row-major
+    def block_grid(self) -> tuple[int, int]:
+        """(blocks_x, blocks_y) = (ceil(W / 8), ceil(local_rows / 8))."""
+        bx, by = C.c_uint32(), C.c_uint32()
+        abi.check(self._lib.rt_renderer_block_grid(self.h, C.byref(bx), C.byref(by)), self._lib)
+        return int(bx.value), int(by.value)
+
+    def _n_blocks(self) -> int:
+        bx, by = self.block_grid()
+        return bx * by
+
+    def continue_blocks(self, samples: int, blocks, want_f32: bool = True, want_u8: bool = True) -> Frame:
+        """rt_render_frame_continue_blocks: `samples` more samples for the pixels of the listed blocks; the images are the tile's whole
+        current image (every pixel over its own block's count), the Frame's statistics those of this call."""
+        lst = np.ascontiguousarray(np.asarray(blocks, np.uint32).reshape(-1))
+        rows, w = self.local_rows, self.img_size[0]
+        f = np.zeros((rows, w, 4), np.float32) if want_f32 else None
+        b = np.zeros((rows, w, 4), np.uint8) if want_u8 else None
+        st = abi.rt_stats()
+        abi.check(self._lib.rt_render_frame_continue_blocks(self.h, int(samples), lst.ctypes.data_as(C.POINTER(C.c_uint32)), int(lst.size),
+                                                            abi.fptr(f) if want_f32 else None, abi.u8ptr(b) if want_u8 else None,
+                                                            C.byref(st)), self._lib)
+        return Frame.from_stats(f, b, st)
+
+    def continue_blocks_device(self, samples: int, blocks, d_f32: int = 0, d_u8: int = 0, stream: int = 0) -> Frame:
+        """rt_render_frame_continue_blocks_device: as continue_blocks, the outputs to DEVICE pointers (the list stays host memory)."""
+        lst = np.ascontiguousarray(np.asarray(blocks, np.uint32).reshape(-1))
+        st = abi.rt_stats()
+        abi.check(self._lib.rt_render_frame_continue_blocks_device(self.h, int(samples), lst.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                                   int(lst.size), C.c_void_p(d_f32 or None), C.c_void_p(d_u8 or None),
+                                                                   C.c_void_p(stream or None), C.byref(st)), self._lib)
+        return Frame.from_stats(None, None, st)
+
+    def adapt(self, threshold: float, min_samples: int = 0) -> np.ndarray:
+        """rt_renderer_adapt: the active blocks, ascending (renders nothing)."""
+        out = np.zeros(max(self._n_blocks(), 1), np.uint32)
+        n = C.c_uint32()
+        abi.check(self._lib.rt_renderer_adapt(self.h, float(threshold), int(min_samples), out.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                              C.byref(n)), self._lib)
+        return out[:n.value].copy()
+
+    def continue_adaptive(self, samples: int, threshold: float, min_samples: int = 0, want_f32: bool = True,
+                          want_u8: bool = True) -> tuple[Frame, np.ndarray]:
+        """rt_renderer_adapt + rt_render_frame_continue_blocks in one call (rt_render_frame_continue_adaptive): (Frame, the blocks it
+        continued)."""
+        blocks = self.adapt(threshold, min_samples)
+        return self.continue_blocks(samples, blocks, want_f32, want_u8), blocks
+
+    def continue_adaptive_c(self, samples: int, threshold: float, min_samples: int = 0, want_f32: bool = True,
+                            want_u8: bool = True) -> tuple[Frame, int]:
+        """rt_render_frame_continue_adaptive itself: (Frame, the number of blocks it continued)."""
+        rows, w = self.local_rows, self.img_size[0]
+        f = np.zeros((rows, w, 4), np.float32) if want_f32 else None
+        b = np.zeros((rows, w, 4), np.uint8) if want_u8 else None
+        st = abi.rt_stats()
+        n = C.c_uint32()
+        abi.check(self._lib.rt_render_frame_continue_adaptive(self.h, int(samples), float(threshold), int(min_samples),
+                                                              abi.fptr(f) if want_f32 else None, abi.u8ptr(b) if want_u8 else None,
+                                                              C.byref(st), C.byref(n)), self._lib)
+        return Frame.from_stats(f, b, st), int(n.value)
+
+    def continue_adaptive_device(self, samples: int, threshold: float, min_samples: int = 0, d_f32: int = 0, d_u8: int = 0,
+                                 stream: int = 0) -> tuple[Frame, int]:
+        """rt_render_frame_continue_adaptive_device: (Frame, the number of blocks it continued); outputs to DEVICE pointers."""
+        st = abi.rt_stats()
+        n = C.c_uint32()
+        abi.check(self._lib.rt_render_frame_continue_adaptive_device(self.h, int(samples), float(threshold), int(min_samples),
+                                                                     C.c_void_p(d_f32 or None), C.c_void_p(d_u8 or None),
+                                                                     C.c_void_p(stream or None), C.byref(st), C.byref(n)), self._lib)
+        return Frame.from_stats(None, None, st), int(n.value)
+
+    def block_samples(self) -> np.ndarray:
+        """Every block's sample count, (blocks_y, blocks_x) uint32 (zeros: nothing to continue)."""
+        bx, by = self.block_grid()
+        out = np.zeros(max(bx * by, 1), np.uint32)
+        abi.check(self._lib.rt_renderer_block_samples(self.h, out.ctypes.data_as(C.POINTER(C.c_uint32))), self._lib)
+        return out[:bx * by].reshape(by, bx)
+
+    def block_errors(self) -> np.ndarray:
+        """The last evaluation's e_B per block, (blocks_y, blocks_x) float32 (+inf: no snapshot)."""
+        bx, by = self.block_grid()
+        out = np.zeros(max(bx * by, 1), np.float32)
+        abi.check(self._lib.rt_renderer_block_errors(self.h, out.ctypes.data_as(C.POINTER(C.c_float))), self._lib)
+        return out[:bx * by].reshape(by, bx)
+
     def close(self):
         if self.h:
             self._lib.rt_renderer_destroy(self.h)

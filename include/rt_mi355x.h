@@ -121,6 +121,39 @@ enum { RT_BVH_DEFAULT = 0, RT_BVH_LBVH = 1, RT_BVH_SAH = 2, RT_BVH_LBVH_GPU = 3 
 int rt_scene_create(const rt_scene_desc* desc, int device, int bvh_kind, rt_scene** out);
 void rt_scene_destroy(rt_scene* scene);
 
+/* ---- Dynamic scenes (no reference counterpart here; Embree re-commits a scene whose instance matrices were changed through
+ * rtcSetGeometryTransform, src/scene.cpp:491, with a refit). */
+#define RT_SCENE_UPDATABLE 1u
+/* == rt_scene_create, plus flags. RT_SCENE_UPDATABLE keeps on the device what an update needs (object positions, indices, every triangle's
+ * instance, the world-space vertices, the exact box of every node and the nodes' height levels: counted in device_bytes). Unknown flag
+ * bits -> RT_ERR_INVALID. */
+int rt_scene_create_ex(const rt_scene_desc* desc, int device, int bvh_kind, uint32_t flags, rt_scene** out);
+
+typedef struct rt_scene_update_desc {
+    uint32_t n_instances;         /* 0 = transforms unchanged, else == the scene's n_instances            */
+    const rt_instance* instances; /* new transform + normal_mat; .material must equal the scene's        */
+    uint32_t n_vertices;          /* 0 = vertices unchanged, else == the scene's n_vertices               */
+    const float* positions;       /* 3 * n_vertices object-space positions, or NULL                       */
+    const float* normals;         /* 3 * n_vertices object-space normals, or NULL                         */
+} rt_scene_update_desc;
+/* device_ms: hipEvent time of the update's device work (0 for a host-only scene); launches: kernel launches; refit_nodes: nodes refitted */
+typedef struct rt_update_stats { double device_ms; uint32_t launches; uint32_t refit_nodes; } rt_update_stats;
+/* Moves instances and / or vertices of a scene created with RT_SCENE_UPDATABLE, keeping its BVH's topology and refitting its boxes.
+ * The contract: for an updatable scene made from desc D, rt_scene_update(S, U) makes S behave as rt_scene_create(D') would, bit for bit,
+ * D' being D with U applied (the instances' transform and normal_mat, the positions, the normals). Behave means every frame under every
+ * renderer, schedule, tile split and BVH kind (fp32, unorm8 and the ray count), every continuation of a frame rendered after the update,
+ * rt_intersect_batch, rt_scene_info().bounds_*, the box padding (2e-5 x the scale of the new world vertices) and the contract-range check
+ * on camera centres. Only the tree may differ from a fresh build: its topology is kept (child words, leaf codes, node order), so traversal
+ * cost changes; rt_scene_info().sah_cost reports the refit tree's cost, so that a caller can decide when to rebuild. A triangle the SAH
+ * builder pre-split sits in several leaves: after an update each of them bounds the whole triangle.
+ * Refused with RT_ERR_INVALID, the scene left unchanged: a scene created without the flag, counts other than 0 or the scene's, a changed
+ * material, NULL where a count is non-zero, world vertices that are non-finite or whose padded bounds overflow fp32 (rt_scene_create's
+ * test), and any renderer of the scene with a frame in flight (rt_render_frame_begin without _end).
+ * The call is synchronous: it returns when the device has finished. Every renderer of the scene discards its progressive state (the next
+ * frame starts a new chain; continuations are refused until then, rt_renderer_accumulated_samples is 0) and re-captures its hipGraph.
+ * A host-only scene (device < 0) is updated on the host with the same arithmetic. stats may be NULL. */
+int rt_scene_update(rt_scene* scene, const rt_scene_update_desc* u, rt_update_stats* stats);
+
 typedef struct rt_scene_info_t {
     uint32_t n_triangles;
     uint32_t n_nodes;

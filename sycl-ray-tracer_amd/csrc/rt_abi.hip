@@ -48,9 +48,12 @@ int rt_camera_init(rt_camera* out, int32_t width, int32_t height, const float ce
     return RT_OK;
 }
 
-int rt_scene_create(const rt_scene_desc* desc, int device, int bvh_kind, rt_scene** out) {
+int rt_scene_create(const rt_scene_desc* desc, int device, int bvh_kind, rt_scene** out) { return rt_scene_create_ex(desc, device, bvh_kind, 0u, out); }
+
+int rt_scene_create_ex(const rt_scene_desc* desc, int device, int bvh_kind, uint32_t flags, rt_scene** out) {
     if (!out) return fail(RT_ERR_INVALID, "null output pointer");
     *out = nullptr;
+    if (flags & ~RT_SCENE_UPDATABLE) return fail(RT_ERR_INVALID, "unknown scene flags");
     if (bvh_kind != RT_BVH_DEFAULT && bvh_kind != RT_BVH_LBVH && bvh_kind != RT_BVH_SAH && bvh_kind != RT_BVH_LBVH_GPU)
         return fail(RT_ERR_INVALID, "unknown bvh_kind");
     if (bvh_kind == RT_BVH_LBVH_GPU) { // the build itself runs on the device
@@ -95,7 +98,11 @@ int rt_scene_create(const rt_scene_desc* desc, int device, int bvh_kind, rt_scen
             rc = upload(packed, &s->dev.tris, s->device_bytes);
         }
         if (rc == RT_OK) rc = upload(s->hs.shade, &s->dev.shade, s->device_bytes);
-        if (rc == RT_OK) rc = upload(s->hs.inst, &s->dev.inst, s->device_bytes);
+        if (rc == RT_OK) { // (an updatable scene's table has room for a row per instance: the distinct matrices may grow)
+            std::vector<InstRec> rows(s->hs.inst);
+            if (flags & RT_SCENE_UPDATABLE) rows.resize(std::max<size_t>(rows.size(), desc->n_instances));
+            rc = upload(rows, &s->dev.inst, s->device_bytes);
+        }
         if (rc == RT_OK) rc = upload(s->hs.mats, &s->dev.mats, s->device_bytes);
         if (rc == RT_OK) rc = upload(s->hs.tex, &s->dev.tex, s->device_bytes);
         if (rc != RT_OK) {
@@ -116,6 +123,13 @@ int rt_scene_create(const rt_scene_desc* desc, int device, int bvh_kind, rt_scen
             s->dev.cell_scale[a] = ext > 0.0f && std::isfinite(ext) ? 4.0f / ext : 0.0f;
         }
     }
+    if (flags & RT_SCENE_UPDATABLE) {
+        rc = no_throw([&] { return init_scene_update(s, desc); });
+        if (rc != RT_OK) {
+            rt_scene_destroy(s);
+            return rc;
+        }
+    }
     *out = s;
     return RT_OK;
 }
@@ -126,11 +140,13 @@ void rt_scene_destroy(rt_scene* s) {
         (void)hipFree((void*)s->dev.nodes), (void)hipFree((void*)s->dev.tris), (void)hipFree((void*)s->dev.shade);
         (void)hipFree((void*)s->dev.inst), (void)hipFree((void*)s->dev.mats), (void)hipFree((void*)s->dev.tex);
     }
+    free_scene_update(s);
     delete s;
 }
 
 int rt_scene_info(const rt_scene* s, rt_scene_info_t* out) {
     if (!s || !out) return fail(RT_ERR_INVALID, "null argument");
+    if (const int rc = sync_host_copy(s)) return rc;
     out->n_triangles = (uint32_t)(s->hs.wverts.size() / 9);
     out->n_nodes = (uint32_t)s->hs.nodes.size();
     out->max_depth = s->hs.max_depth;
@@ -145,6 +161,7 @@ int rt_scene_info(const rt_scene* s, rt_scene_info_t* out) {
 
 int rt_scene_check_bvh(const rt_scene* s) {
     if (!s) return fail(RT_ERR_INVALID, "null scene");
+    if (const int rc0 = sync_host_copy(s)) return rc0;
     std::string err;
     int rc = check_bvh(s->hs, err);
     return rc == RT_OK ? RT_OK : fail(rc, err);
@@ -153,6 +170,7 @@ int rt_scene_check_bvh(const rt_scene* s) {
 int rt_scene_count_visits(const rt_scene* s, uint32_t n, const float* org, const float* dir, int mode, uint64_t* node_visits, uint64_t* tri_tests,
                           float* t, uint32_t* tri) {
     if (!s || (n && (!org || !dir))) return fail(RT_ERR_INVALID, "null argument");
+    if (const int rc0 = sync_host_copy(s)) return rc0;
     std::string err;
     const int rc = no_throw([&] { return count_visits(s->hs, n, org, dir, mode, node_visits, tri_tests, t, tri, err); });
     return rc == RT_OK ? RT_OK : fail(rc, err.empty() ? g_err : err);
@@ -174,6 +192,7 @@ int rt_renderer_create(int kind, rt_scene* scene, int32_t width, int32_t height,
     rt_renderer* r = new (std::nothrow) rt_renderer();
     if (!r) return fail(RT_ERR_OOM, "host allocation failed");
     r->kind = kind, r->scene = scene, r->width = width, r->height = height;
+    r->scene_gen = scene->generation;
     r->max_depth = max_depth, r->spp = sample_count;
     r->seed_mode = seed_mode != RT_SEED_DEFAULT ? seed_mode
                    : (kind == RT_RENDERER_MEGAKERNEL ? RT_SEED_MEGAKERNEL : RT_SEED_WAVEFRONT);
@@ -230,6 +249,7 @@ int rt_renderer_create(int kind, rt_scene* scene, int32_t width, int32_t height,
 
 void rt_renderer_destroy(rt_renderer* r) {
     if (!r) return;
+    if (r->scene && r->frame_pending && r->scene->frames_pending) r->scene->frames_pending--;
     if (r->scene && hipSetDevice(r->scene->device) == hipSuccess) {
         drain_streams(r, r->pending_stream);
         free_tile_buffers(r);
@@ -351,7 +371,7 @@ int rt_render_frame_continue_device(rt_renderer* r, uint32_t samples, void* d_rg
 
 int rt_renderer_accumulated_samples(const rt_renderer* r, uint32_t* out) {
     if (!r || !out) return fail(RT_ERR_INVALID, "null argument");
-    *out = r->carry_samples;
+    *out = carry_is_current(r) ? r->carry_samples : 0u; // (a scene update ends the chain)
     return RT_OK;
 }
 
@@ -364,7 +384,7 @@ int rt_renderer_block_grid(const rt_renderer* r, uint32_t* blocks_x, uint32_t* b
 int rt_renderer_block_samples(const rt_renderer* r, uint32_t* out) {
     if (!r || !out) return fail(RT_ERR_INVALID, "null argument");
     const size_t nb = (size_t)(((uint32_t)r->width + 7u) / 8u) * (((uint32_t)r->tile.local_rows + 7u) / 8u);
-    if (r->carry_samples == 0 || r->h_block_count.size() != nb) std::memset(out, 0, nb * 4); // nothing to continue
+    if (r->carry_samples == 0 || !carry_is_current(r) || r->h_block_count.size() != nb) std::memset(out, 0, nb * 4); // nothing to continue
     else std::memcpy(out, r->h_block_count.data(), nb * 4);
     return RT_OK;
 }
@@ -451,6 +471,7 @@ extern "C" {
 int rt_dev_scene_tables(const rt_scene* s, uint32_t* packed_mat, uint32_t* lds_nm, uint32_t* lds_mats, uint32_t* n_rows, float* rows,
                         uint32_t capacity, uint32_t* words) {
     if (!s || !packed_mat || !lds_nm || !lds_mats || !n_rows) return fail(RT_ERR_INVALID, "null argument");
+    if (const int rc = sync_host_copy(s)) return rc;
     *packed_mat = s->hs.packed_mat ? 1u : 0u;
     *lds_nm = s->dev.lds_nm, *lds_mats = s->dev.lds_mats;
     *n_rows = (uint32_t)s->hs.inst.size();
@@ -469,6 +490,7 @@ int rt_dev_scene_tables(const rt_scene* s, uint32_t* packed_mat, uint32_t* lds_n
 int rt_dev_scene_tree(const rt_scene* s, uint32_t* n_nodes, uint32_t* n_tris, uint32_t* n_wverts, uint32_t* stack_need, int32_t* built_by,
                       float* pad, float* bounds, void* nodes, uint32_t* global_index, float* wverts, uint32_t capacity) {
     if (!s || !n_nodes || !n_tris || !n_wverts || !stack_need || !built_by || !pad || !bounds) return fail(RT_ERR_INVALID, "null argument");
+    if (const int rc = sync_host_copy(s)) return rc;
     const HostScene& hs = s->hs;
     *n_nodes = (uint32_t)hs.nodes.size(), *n_tris = (uint32_t)hs.tris.size(), *n_wverts = (uint32_t)hs.wverts.size();
     *stack_need = hs.stack_need, *built_by = hs.built_by, *pad = hs.pad;
@@ -477,6 +499,13 @@ int rt_dev_scene_tree(const rt_scene* s, uint32_t* n_nodes, uint32_t* n_tris, ui
     if (global_index)
         for (size_t t = 0; t < std::min<size_t>(capacity, hs.tris.size()); ++t) global_index[t] = hs.tris[t].global_index;
     if (wverts) std::memcpy(wverts, hs.wverts.data(), std::min<size_t>(capacity, hs.wverts.size()) * sizeof(float));
+    return RT_OK;
+}
+
+// How many hipGraphs the renderer has captured (rt_schedule::hip_graph = 1): a scene update makes the next frame capture again.
+int rt_dev_renderer_graph_captures(const rt_renderer* r, uint32_t* out) {
+    if (!r || !out) return fail(RT_ERR_INVALID, "null argument");
+    *out = r->graph_captures;
     return RT_OK;
 }
 

@@ -829,6 +829,7 @@ int enqueue_frame(rt_renderer* r, const rt_camera* cam, float* d_f32, uint8_t* d
                     return fail(RT_ERR_HIP, std::string("hipGraphInstantiate: ") + hipGetErrorString(ie));
                 }
                 r->graph_f32 = d_f32, r->graph_u8 = d_u8, r->graph_stream = st;
+                r->graph_captures++;
             }
             HIPCHK(hipGraphLaunch(r->graph_exec, st));
             launches = r->graph_launches;
@@ -975,12 +976,14 @@ int frame_begin_impl(rt_renderer* r, const rt_camera* cam, float* d_f32, uint8_t
     HIPCHK(hipEventRecord(r->ev_end, st));
     r->pending_stream = st;
     r->frame_pending = true;
+    r->scene->frames_pending++;
     return RT_OK;
 }
 
 int frame_begin(rt_renderer* r, const rt_camera* cam, float* d_f32, uint8_t* d_u8, hipStream_t st) {
     if (!r) return fail(RT_ERR_INVALID, "null renderer or camera");
     if (r->frame_pending) return fail(RT_ERR_INVALID, "the renderer's previous frame has not been collected (rt_render_frame_end)");
+    sync_scene_generation(r);
     // progressive rendering: a frame stores its pixels' state, renders the renderer's own sample count and starts the count over
     r->carry_mode = r->progressive && r->d_carry ? 1 : 0;
     r->carry_total = r->spp;
@@ -995,6 +998,7 @@ int frame_end(rt_renderer* r, rt_stats* stats) {
     rt_stats local = r->pending_stats;
     const size_t n_hot = r->pending_hot;
     r->frame_pending = false;
+    if (r->scene->frames_pending) r->scene->frames_pending--;
     HIPCHK(hipStreamSynchronize(st));
     const auto t1 = std::chrono::high_resolution_clock::now();
     local.seconds = std::chrono::duration<double>(t1 - r->pending_t0).count();
@@ -1103,6 +1107,7 @@ int render_impl(rt_renderer* r, const rt_camera* cam, float* d_f32, uint8_t* d_u
 int continue_impl(rt_renderer* r, uint32_t samples, float* d_f32, uint8_t* d_u8, hipStream_t st, rt_stats* stats) {
     if (!r) return fail(RT_ERR_INVALID, "null renderer");
     if (r->frame_pending) return fail(RT_ERR_INVALID, "the renderer's previous frame has not been collected (rt_render_frame_end)");
+    sync_scene_generation(r); // (after a scene update there is nothing to continue)
     if (!r->progressive) return fail(RT_ERR_INVALID, "progressive rendering is off (rt_renderer_set_progressive)");
     if (r->kind == RT_RENDERER_WAVEFRONT && r->sched.hip_graph)
         return fail(RT_ERR_UNSUPPORTED, "a continuation cannot run as a replayed hipGraph (rt_schedule::hip_graph = 1)");
@@ -1134,6 +1139,7 @@ int continue_blocks_impl(rt_renderer* r, uint32_t samples, const uint32_t* block
                          rt_stats* stats) {
     if (!r) return fail(RT_ERR_INVALID, "null renderer");
     if (r->frame_pending) return fail(RT_ERR_INVALID, "the renderer's previous frame has not been collected (rt_render_frame_end)");
+    sync_scene_generation(r);
     if (!r->progressive) return fail(RT_ERR_INVALID, "progressive rendering is off (rt_renderer_set_progressive)");
     if (r->kind == RT_RENDERER_WAVEFRONT && r->sched.hip_graph)
         return fail(RT_ERR_UNSUPPORTED, "a continuation cannot run as a replayed hipGraph (rt_schedule::hip_graph = 1)");
@@ -1180,6 +1186,7 @@ int adapt_impl(rt_renderer* r, float threshold, uint32_t min_samples, std::vecto
     blocks.clear();
     if (!r) return fail(RT_ERR_INVALID, "null renderer");
     if (r->frame_pending) return fail(RT_ERR_INVALID, "the renderer's previous frame has not been collected (rt_render_frame_end)");
+    sync_scene_generation(r);
     if (!r->progressive) return fail(RT_ERR_INVALID, "progressive rendering is off (rt_renderer_set_progressive)");
     if (r->carry_samples == 0 || !r->d_blk)
         return fail(RT_ERR_INVALID, "nothing to evaluate: no frame has completed since progressive rendering was turned on or its state was discarded");

@@ -4,6 +4,7 @@
 //   rt_frame.hip   tile buffers, schedules, the launches of a frame (the only unit that includes the render kernels, rt_kernels.h)
 //   rt_comm.hip    the multi-GPU frame gather (RCCL) and its de-interleave kernel
 //   rt_probes.hip  rt_intersect_batch and the rt_probe_* entry points with their kernels (rt_probe_kernels.h)
+//   rt_update.hip  dynamic scenes: rt_scene_create_ex's updatable state, rt_scene_update and its refit kernels
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -91,11 +92,50 @@ int upload(const std::vector<T>& v, const T** out, uint64_t& bytes) {
 using namespace rt;
 using namespace rtlib;
 
+// What an updatable scene (RT_SCENE_UPDATABLE, rt_update.hip) keeps beside the built one. Host side: the instances as they are now, every
+// instance's triangle count and table row (the shading grouping is re-run per update), the node height levels; a host-only scene also
+// keeps its description's geometry here (a device scene keeps it on the device). Device side, allocated at creation and never moved:
+//   pos, pos_stage   object positions (3 per vertex) and the staging buffer an update uploads into (swapped on success; normals go there too)
+//   idx, tri_inst    3 vertex indices and the instance of every triangle, global order
+//   xf, xf_stage     16 floats per instance: the transforms, and their staging copy
+//   islot            every instance's shading word, uploaded per update where the table rows moved
+//   wv               world-space vertices, 9 floats per triangle (the transform's scratch output, the host copy's source)
+//   box              the exact box of every node, 6 floats (24 bytes) per node
+//   levels           the nodes by height (level_start on the host)
+//   red              the transform's reduction: 6 ordered 64-bit keys (bounds, first occurrence) + a non-finite flag
+struct SceneUpdate {
+    std::vector<rt_instance> instances;
+    std::vector<uint64_t> inst_use;
+    std::vector<uint32_t> inst_slot;
+    std::vector<uint32_t> level_nodes, level_start;
+    uint32_t n_vertices = 0;
+    std::vector<float> positions, normals; // host-only scenes
+    std::vector<uint32_t> indices, tri_instance;
+    float* d_pos = nullptr;
+    float* d_pos_stage = nullptr;
+    uint32_t* d_idx = nullptr;
+    uint32_t* d_tri_inst = nullptr;
+    float* d_xf = nullptr;
+    float* d_xf_stage = nullptr;
+    uint32_t* d_islot = nullptr;
+    float* d_wv = nullptr;
+    float* d_box = nullptr;
+    uint32_t* d_levels = nullptr;
+    unsigned long long* d_red = nullptr;
+    unsigned long long* h_red = nullptr; // pinned
+    hipStream_t stream = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    bool host_stale = false; // the host copy (hs.nodes, tris, wverts, shade, sah_cost) lags a device update
+};
+
 struct rt_scene {
     HostScene hs;
     int device = -1;
     SceneDev dev{};
     uint64_t device_bytes = 0;
+    SceneUpdate* upd = nullptr; // RT_SCENE_UPDATABLE only
+    uint64_t generation = 0;    // bumped by every rt_scene_update: renderers drop what belongs to an older one
+    uint32_t frames_pending = 0; // frames of its renderers between _begin and _end (an update is refused meanwhile)
 };
 
 // kernel launches of one frame, in all and per kernel family (rt_stats::launches_by_kernel)
@@ -240,6 +280,9 @@ struct rt_renderer {
     std::vector<uint32_t> lane_pixels;
     uint32_t hw_queues = 4; // GPU_MAX_HW_QUEUES as the host had set it when the renderer was created (4 = HIP's default): bounds the automatic stream lanes
     uint32_t mega_lds_pad = 0, mega_occ = kMegaWaves;
+    // the scene generation (rt_scene::generation) the captured graph and the carried progressive state belong to (sync_scene_generation)
+    uint64_t scene_gen = 0;
+    uint32_t graph_captures = 0; // hipGraphs instantiated (the developer build reports it: rt_dev_renderer_graph_captures)
 };
 
 namespace rtlib {
@@ -262,4 +305,19 @@ int adapt_impl(rt_renderer* r, float threshold, uint32_t min_samples, std::vecto
 int continue_adaptive_impl(rt_renderer* r, uint32_t samples, float threshold, uint32_t min_samples, float* d_f32, uint8_t* d_u8, hipStream_t st,
                            rt_stats* stats, uint32_t* n_blocks_out);
 int block_errors(const rt_renderer* r, float* out);
+// after rt_scene_update: the captured graph (it holds SceneDev by value) and the carried progressive state belong to the old scene
+inline void sync_scene_generation(rt_renderer* r) {
+    if (r->scene_gen == r->scene->generation) return;
+    drop_graph(r);
+    r->carry_samples = 0;
+    r->scene_gen = r->scene->generation;
+}
+inline bool carry_is_current(const rt_renderer* r) { return r->scene_gen == r->scene->generation; }
+
+// rt_update.hip
+void free_scene_update(rt_scene* s);
+int init_scene_update(rt_scene* s, const rt_scene_desc* d);
+uint32_t scene_inst_capacity(const rt_scene* s); // rows the device's instance table is allocated with
+// brings the host copy up to date after device updates (rt_scene_info, rt_scene_check_bvh, rt_scene_count_visits, rt_dev_scene_*)
+int sync_host_copy(const rt_scene* s);
 } // namespace rtlib

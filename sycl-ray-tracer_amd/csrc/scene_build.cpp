@@ -628,39 +628,11 @@ int build_host_scene(const rt_scene_desc* d, int bvh_kind, HostScene& hs, std::s
     // instance is its normal matrix — and a scene has far fewer DISTINCT matrices than instances (one instance per glTF node and primitive:
     // 166 and 5 on the atrium). The table holds every distinct bit pattern once, ordered by the number of triangles that use it, so that the
     // head of the table — what the shading kernels stage in LDS — covers the most hits. inst_slot[i]: instance i's row of the table.
-    std::vector<uint32_t> inst_slot(d->n_instances);
-    if (hs.packed_mat) {
+    std::vector<uint32_t> inst_slot;
+    {
         std::vector<uint64_t> use(d->n_instances, 0);
         for (uint32_t t = 0; t < d->n_triangles; ++t) use[d->tri_instance[t]]++;
-        std::map<std::array<uint32_t, 9>, uint32_t> seen; // bit pattern -> provisional row
-        std::vector<std::array<uint32_t, 9>> rows;
-        std::vector<uint64_t> row_use;
-        for (uint32_t i = 0; i < d->n_instances; ++i) {
-            std::array<uint32_t, 9> key;
-            std::memcpy(key.data(), d->instances[i].normal_mat, 36);
-            auto it = seen.find(key);
-            if (it == seen.end()) {
-                it = seen.emplace(key, (uint32_t)rows.size()).first;
-                rows.push_back(key), row_use.push_back(0);
-            }
-            inst_slot[i] = it->second;
-            row_use[it->second] += use[i];
-        }
-        std::vector<uint32_t> order(rows.size()), rank(rows.size());
-        for (uint32_t k = 0; k < order.size(); ++k) order[k] = k;
-        std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return row_use[a] > row_use[b]; });
-        for (uint32_t k = 0; k < order.size(); ++k) rank[order[k]] = k;
-        hs.inst.assign(rows.size(), InstRec{});
-        for (uint32_t k = 0; k < rows.size(); ++k) std::memcpy(hs.inst[rank[k]].normal_mat, rows[k].data(), 36);
-        for (uint32_t i = 0; i < d->n_instances; ++i) inst_slot[i] = rank[inst_slot[i]];
-    } else {
-        hs.inst.resize(d->n_instances);
-        for (uint32_t i = 0; i < d->n_instances; ++i) {
-            std::memcpy(hs.inst[i].normal_mat, d->instances[i].normal_mat, sizeof(float) * 9);
-            hs.inst[i].material = d->instances[i].material;
-            hs.inst[i].pad[0] = hs.inst[i].pad[1] = 0;
-            inst_slot[i] = i;
-        }
+        shading_rows(d->instances, d->n_instances, use, hs.packed_mat, hs.inst, inst_slot);
     }
     hs.mats.resize(d->n_materials);
     for (uint32_t i = 0; i < d->n_materials; ++i) {
@@ -726,20 +698,9 @@ int build_host_scene(const rt_scene_desc* d, int bvh_kind, HostScene& hs, std::s
         const int a = (int)(i % 3);
         hs.bounds_lo[a] = std::min(hs.bounds_lo[a], hs.wverts[i]), hs.bounds_hi[a] = std::max(hs.bounds_hi[a], hs.wverts[i]);
     }
-    float ext = 0.0f, amax = 0.0f;
-    for (int a = 0; a < 3; ++a) {
-        ext = std::max(ext, hs.bounds_hi[a] - hs.bounds_lo[a]);
-        amax = std::max(amax, std::max(std::fabs(hs.bounds_lo[a]), std::fabs(hs.bounds_hi[a])));
-    }
-    // Absolute padding of every box: 2e-5 x scene scale. Float rounding of the slab test and of the
-    // Moller-Trumbore t is ~1e-7 x scale, so a padded box can only cull triangles the exact test
-    // would also miss (see DESIGN.md, "culling is conservative").
-    hs.pad = 2e-5f * std::max(ext, amax) + 1e-30f;
-    // Finite vertices can still span more than fp32 holds (x from -2e38 to 2e38): no builder can quantise such a scene, and every
-    // builder refuses it here alike, before one is chosen (the device quantiser would otherwise meet it only per node).
-    bool finite = std::isfinite(ext) && std::isfinite(hs.pad);
-    for (int a = 0; a < 3; ++a) finite = finite && std::isfinite(hs.bounds_lo[a] - hs.pad) && std::isfinite(hs.bounds_hi[a] + hs.pad);
-    if (!finite) { err = "scene extent overflows fp32 (the padded bounds are not finite)"; return RT_ERR_INVALID; }
+    float ext = 0.0f;
+    for (int a = 0; a < 3; ++a) ext = std::max(ext, hs.bounds_hi[a] - hs.bounds_lo[a]);
+    if (!scene_padding(hs.bounds_lo, hs.bounds_hi, hs.pad, err)) return RT_ERR_INVALID;
 
     // Exact worst-case traversal stack need: at every level all siblings of the entered child may be waiting.
     std::function<uint32_t(int32_t)> need = [&](int32_t node) -> uint32_t {
@@ -981,6 +942,165 @@ int build_host_scene(const rt_scene_desc* d, int bvh_kind, HostScene& hs, std::s
     }
     hs.built_by = bvh_kind == RT_BVH_LBVH_GPU ? RT_BVH_LBVH : bvh_kind; // (a GPU request for fewer than 8 triangles: the host LBVH)
     return RT_OK;
+}
+
+// The device's instance table. Packed shading word (the rule, rt_types.h): the material index travels in the word, so what is left of an
+// instance is its normal matrix — and a scene has far fewer DISTINCT matrices than instances (one instance per glTF node and primitive:
+// 166 and 5 on the atrium). The table holds every distinct bit pattern once, ordered by the number of triangles that use it, so that the
+// head of the table — what the shading kernels stage in LDS — covers the most hits. slot[i]: instance i's row of the table.
+void shading_rows(const rt_instance* inst, uint32_t n, const std::vector<uint64_t>& use, bool packed, std::vector<InstRec>& out,
+                  std::vector<uint32_t>& slot) {
+    slot.assign(n, 0);
+    if (packed) {
+        std::map<std::array<uint32_t, 9>, uint32_t> seen; // bit pattern -> provisional row
+        std::vector<std::array<uint32_t, 9>> rows;
+        std::vector<uint64_t> row_use;
+        for (uint32_t i = 0; i < n; ++i) {
+            std::array<uint32_t, 9> key;
+            std::memcpy(key.data(), inst[i].normal_mat, 36);
+            auto it = seen.find(key);
+            if (it == seen.end()) {
+                it = seen.emplace(key, (uint32_t)rows.size()).first;
+                rows.push_back(key), row_use.push_back(0);
+            }
+            slot[i] = it->second;
+            row_use[it->second] += use[i];
+        }
+        std::vector<uint32_t> order(rows.size()), rank(rows.size());
+        for (uint32_t k = 0; k < order.size(); ++k) order[k] = k;
+        std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return row_use[a] > row_use[b]; });
+        for (uint32_t k = 0; k < order.size(); ++k) rank[order[k]] = k;
+        out.assign(rows.size(), InstRec{});
+        for (uint32_t k = 0; k < rows.size(); ++k) std::memcpy(out[rank[k]].normal_mat, rows[k].data(), 36);
+        for (uint32_t i = 0; i < n; ++i) slot[i] = rank[slot[i]];
+    } else {
+        out.assign(n, InstRec{});
+        for (uint32_t i = 0; i < n; ++i) {
+            std::memcpy(out[i].normal_mat, inst[i].normal_mat, sizeof(float) * 9);
+            out[i].material = inst[i].material;
+            slot[i] = i;
+        }
+    }
+}
+
+bool scene_padding(const float lo[3], const float hi[3], float& pad, std::string& err) {
+    float ext = 0.0f, amax = 0.0f;
+    for (int a = 0; a < 3; ++a) {
+        ext = std::max(ext, hi[a] - lo[a]);
+        amax = std::max(amax, std::max(std::fabs(lo[a]), std::fabs(hi[a])));
+    }
+    // Absolute padding of every box: 2e-5 x scene scale. Float rounding of the slab test and of the
+    // Moller-Trumbore t is ~1e-7 x scale, so a padded box can only cull triangles the exact test
+    // would also miss (see DESIGN.md, "culling is conservative").
+    pad = 2e-5f * std::max(ext, amax) + 1e-30f;
+    // Finite vertices can still span more than fp32 holds (x from -2e38 to 2e38): no builder can quantise such a scene, and every
+    // builder refuses it here alike, before one is chosen (the device quantiser would otherwise meet it only per node).
+    bool finite = std::isfinite(ext) && std::isfinite(pad);
+    for (int a = 0; a < 3; ++a) finite = finite && std::isfinite(lo[a] - pad) && std::isfinite(hi[a] + pad);
+    if (!finite) { err = "scene extent overflows fp32 (the padded bounds are not finite)"; return false; }
+    return true;
+}
+
+void node_levels(const std::vector<BvhNode>& nodes, std::vector<uint32_t>& level_nodes, std::vector<uint32_t>& level_start) {
+    const size_t n = nodes.size();
+    std::vector<uint32_t> height(n, 0), post;
+    std::vector<uint32_t> st{0};
+    post.reserve(n);
+    while (!st.empty()) { // pre-order from the root, reversed below: children before parents
+        const uint32_t i = st.back();
+        st.pop_back();
+        post.push_back(i);
+        for (int k = 0; k < 4; ++k)
+            if (nodes[i].child[k] >= 0) st.push_back((uint32_t)nodes[i].child[k]);
+    }
+    uint32_t top = 0;
+    for (size_t q = post.size(); q-- > 0;) {
+        const uint32_t i = post[q];
+        uint32_t h = 0;
+        for (int k = 0; k < 4; ++k)
+            if (nodes[i].child[k] >= 0) h = std::max(h, height[(size_t)nodes[i].child[k]] + 1);
+        height[i] = h, top = std::max(top, h);
+    }
+    level_start.assign((size_t)top + 2, 0);
+    for (uint32_t i : post) level_start[(size_t)height[i] + 1]++;
+    for (size_t h = 1; h < level_start.size(); ++h) level_start[h] += level_start[h - 1];
+    level_nodes.assign(post.size(), 0);
+    std::vector<uint32_t> at(level_start.begin(), level_start.end() - 1);
+    // ascending node index within a level (nodes the root cannot reach — none in a built tree — are left out)
+    std::vector<uint8_t> reached(n, 0);
+    for (uint32_t i : post) reached[i] = 1;
+    for (uint32_t i = 0; i < (uint32_t)n; ++i)
+        if (reached[i]) level_nodes[at[height[i]]++] = i;
+}
+
+bool refit_host(HostScene& hs, const std::vector<uint32_t>& level_nodes, std::vector<float>& box, std::string& err) {
+    const float inf = std::numeric_limits<float>::infinity();
+    // leaf records: the packed v0 / e1 / e2 of their triangle, and the whole triangle's box (a pre-split triangle's pieces mean nothing now)
+    hs.rec_lo.assign(3 * hs.tris.size(), 0.0f), hs.rec_hi.assign(3 * hs.tris.size(), 0.0f);
+    for (size_t r = 0; r < hs.tris.size(); ++r) {
+        TriRec& tr = hs.tris[r];
+        if (tr.global_index == kNoTri) continue;
+        const float* w = &hs.wverts[9 * (size_t)tr.global_index];
+        for (int a = 0; a < 3; ++a) {
+            tr.v0[a] = w[a];
+            tr.e1[a] = w[3 + a] - w[a];
+            tr.e2[a] = w[6 + a] - w[a];
+            hs.rec_lo[3 * r + a] = std::min(w[a], std::min(w[3 + a], w[6 + a]));
+            hs.rec_hi[3 * r + a] = std::max(w[a], std::max(w[3 + a], w[6 + a]));
+        }
+    }
+    box.assign(6 * hs.nodes.size(), 0.0f);
+    for (uint32_t i : level_nodes) {
+        BvhNode& n = hs.nodes[i];
+        float klo[4][3], khi[4][3];
+        int nk = 0;
+        for (int k = 0; k < 4 && n.child[k] != kChildEmpty; ++k, ++nk) {
+            float lo[3] = {inf, inf, inf}, hi[3] = {-inf, -inf, -inf};
+            if (n.child[k] >= 0) {
+                const float* b = &box[6 * (size_t)n.child[k]];
+                for (int a = 0; a < 3; ++a) lo[a] = b[a], hi[a] = b[3 + a];
+            } else {
+                const uint32_t code = (uint32_t)~n.child[k], first = code >> 2, count = (code & 3u) + 1u;
+                for (uint32_t r = first; r < first + count; ++r)
+                    for (int a = 0; a < 3; ++a)
+                        lo[a] = std::min(lo[a], hs.rec_lo[3 * (size_t)r + a]), hi[a] = std::max(hi[a], hs.rec_hi[3 * (size_t)r + a]);
+            }
+            float* b = &box[6 * (size_t)i];
+            for (int a = 0; a < 3; ++a) {
+                b[a] = k ? std::min(b[a], lo[a]) : lo[a], b[3 + a] = k ? std::max(b[3 + a], hi[a]) : hi[a];
+                klo[k][a] = lo[a] - hs.pad, khi[k][a] = hi[a] + hs.pad;
+            }
+        }
+        if (nk == 0) continue; // the empty scene's root
+        BvhNode q = n;
+        if (!quantise_node(q, nk, klo, khi)) { err = "a refit node's child boxes could not be quantised"; return false; }
+        std::memcpy(&n, &q, 48); // words 0..11; the child words stay
+    }
+    hs.sah_cost = refit_sah_cost(hs, box);
+    return true;
+}
+
+double refit_sah_cost(const HostScene& hs, const std::vector<float>& box) {
+    if (hs.nodes.empty() || box.size() < 6 * hs.nodes.size()) return 0.0;
+    const double root_area = std::max(1e-30, (double)half_area(&box[0], &box[3]));
+    double cost = 0.0;
+    for (size_t i = 0; i < hs.nodes.size(); ++i) {
+        const BvhNode& n = hs.nodes[i];
+        for (int k = 0; k < 4; ++k) {
+            if (n.child[k] == kChildEmpty) continue;
+            if (n.child[k] >= 0) {
+                cost += (double)half_area(&box[6 * (size_t)n.child[k]], &box[6 * (size_t)n.child[k] + 3]) / root_area;
+            } else {
+                const uint32_t code = (uint32_t)~n.child[k], first = code >> 2, count = (code & 3u) + 1u;
+                float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+                for (uint32_t r = first; r < first + count && 3 * (size_t)r + 2 < hs.rec_lo.size(); ++r)
+                    for (int a = 0; a < 3; ++a)
+                        lo[a] = std::min(lo[a], hs.rec_lo[3 * (size_t)r + a]), hi[a] = std::max(hi[a], hs.rec_hi[3 * (size_t)r + a]);
+                cost += (double)half_area(lo, hi) / root_area * (double)count;
+            }
+        }
+    }
+    return 1.0 + cost;
 }
 
 int check_bvh(const HostScene& hs, std::string& err) {

@@ -43,6 +43,25 @@ int build_lbvh_gpu(HostScene& hs, const std::vector<TriRec>& gtris, std::string&
 bool quantise_node_dev_export(BvhNode& n, int nk, const float (*klo)[3], const float (*khi)[3]);
 #endif
 
+// ---- dynamic scenes (rt_scene_update) ---------------------------------------------------------------------------------------------------
+// The device's instance table from the instances' normal matrices (the packed shading word's distinct-matrix grouping, rt_types.h): `use`
+// is the number of triangles of every instance; rows receives the table, slot[i] instance i's row.
+void shading_rows(const rt_instance* inst, uint32_t n, const std::vector<uint64_t>& use, bool packed, std::vector<InstRec>& rows,
+                  std::vector<uint32_t>& slot);
+// The scene's bounds and box padding from the fp32 world-space vertices as min / max reduced (lo, hi): pad = 2e-5 x scene scale. Returns
+// false (err set) when the padded bounds are not finite.
+bool scene_padding(const float lo[3], const float hi[3], float& pad, std::string& err);
+// Height levels of the node topology (height: distance to the deepest leaf below): level_nodes lists the nodes by height, level h being
+// level_nodes[level_start[h] .. level_start[h + 1]). A node's children all lie in lower levels.
+void node_levels(const std::vector<BvhNode>& nodes, std::vector<uint32_t>& level_nodes, std::vector<uint32_t>& level_start);
+// Refits hs.nodes in place over hs.wverts (node topology, child words and leaf records kept): rewrites every leaf record's v0 / e1 / e2 and
+// its rec_lo / rec_hi box (the whole triangle's), every node's exact child boxes (box: 6 floats per node, the union of its children) and its
+// quantised words 0..11 with hs.pad, level by level, and hs.sah_cost. Returns false if a node cannot be quantised.
+bool refit_host(HostScene& hs, const std::vector<uint32_t>& level_nodes, std::vector<float>& box, std::string& err);
+// Surface-area cost of a refit tree from the nodes' exact boxes (box, 6 floats per node): inner child 1 x area, leaf child its records x
+// area, relative to the root's area.
+double refit_sah_cost(const HostScene& hs, const std::vector<float>& box);
+
 // Structural check used by rt_scene_check_bvh.
 int check_bvh(const HostScene& hs, std::string& err);
 

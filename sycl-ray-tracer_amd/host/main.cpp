@@ -9,9 +9,12 @@
 //   --adaptive T [--min-samples N]   with --passes: passes 2 .. K continue only the 8x8 blocks that are still noisy (adaptive sampling:
 //                          rt_render_frame_continue_adaptive, threshold T on the two-image error, blocks under N samples always continue)
 //   --schedule {default,per-sample,per-bounce,per-bounce-fused}   which of the wavefront renderer's schedules renders the frame
+//   --frames N --spin DEG  render N frames, every instance turned by DEG more per frame about the vertical axis through the centre of the
+//                          scene's bounds (rt_scene_update between frames: the BVH is refit, not rebuilt); writes OUT_0000.png onwards
 //                          (rt_renderer_set_schedule; per-bounce = the reference's own: src/render_wavefront.cpp:396-417)
 // Prints the same lines as the reference (Loading scene, loader chatter, Sample n, the three statistics
 // lines benchmark.py scrapes, Writing image to disk) and writes the PNG.
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -41,6 +44,9 @@ static void usage(const char* argv0) {
                 "  --min-samples UINT          with --adaptive: blocks with fewer samples always continue (default 0)\n"
                 "  --schedule NAME             wavefront schedule: default (one launch per frame), per-sample, per-bounce (a launch pair per\n"
                 "                              bounce with compaction in between, the reference's), per-bounce-fused (one kernel per bounce)\n"
+                "  --frames UINT               render this many frames, written to OUT_0000.png onwards (default 1)\n"
+                "  --spin FLOAT                with --frames: turn every instance by this many degrees per frame about the vertical axis\n"
+                "                              through the centre of the scene (a BVH refit per frame; prints each update's device time)\n"
                 "  --quiet                     No loader chatter\n"
                 "\nThe camera must lie within 100 scene scales of the scene's bounds (scale = largest extent or coordinate): farther out the\n"
                 "conservative box culling of the closest-hit query no longer holds and the frame is refused with an error, not rendered wrong.\n",
@@ -48,8 +54,9 @@ static void usage(const char* argv0) {
 }
 
 int main(int argc, const char* argv[]) {
-    uint32_t max_depth = 10, sample_count = 32, rr = 0, passes = 1, min_samples = 0;
+    uint32_t max_depth = 10, sample_count = 32, rr = 0, passes = 1, min_samples = 0, frames = 1;
     float adaptive = -1.0f; // < 0: off
+    double spin = 0.0;      // degrees per frame (--frames)
     std::string scene_path = "./assets/sponza.glb", out_path = "out.png";
     bool use_wavefront = false, use_megakernel = false, quiet = false;
     int32_t width = 1920, height = 1080;
@@ -112,6 +119,16 @@ int main(int argc, const char* argv[]) {
         }
         else if (a == "--min-samples") min_samples = to_u32("--min-samples", need(i));
         else if (a == "--quiet") quiet = true;
+        else if (a == "--frames") {
+            frames = to_u32("--frames", need(i));
+            if (frames == 0) { std::fprintf(stderr, "--frames: expected at least 1\n"); return 105; }
+        }
+        else if (a == "--spin") {
+            const std::string v = need(i);
+            char* end = nullptr;
+            spin = std::strtod(v.c_str(), &end);
+            if (v.empty() || *end || !std::isfinite(spin)) { std::fprintf(stderr, "--spin: expected degrees, got '%s'\n", v.c_str()); return 105; }
+        }
         else if (a == "--schedule") {
             const std::string v = need(i);
             schedule_given = true;
@@ -153,7 +170,8 @@ int main(int argc, const char* argv[]) {
         } else
             std::printf("Running on device: HIP device %d of %d (gfx950 path)\n", device, n_dev); // src/app.hpp:51-54
         std::vector<uint8_t> image_buf((size_t)width * (size_t)height * 4);
-        raytracer::Scene scene(scene_path, device, bvh, !quiet);
+        if (frames > 1 && devices.size() > 1) throw std::runtime_error("--frames: one device only");
+        raytracer::Scene scene(scene_path, device, bvh, !quiet, frames > 1 ? RT_SCENE_UPDATABLE : 0u);
         raytracer::Camera camera({width, height}, scene.camera_position, scene.camera_direction, scene.camera_focal_length);
         std::unique_ptr<raytracer::IRenderer> renderer;
         if (use_megakernel) {
@@ -174,7 +192,18 @@ int main(int argc, const char* argv[]) {
             if (schedule_given) r->schedule = schedule, r->has_schedule = true;
             renderer.reset(r);
         }
-        renderer->render_frame(camera, scene);
+        if (frames == 1) renderer->render_frame(camera, scene);
+        const std::string stem = out_path.size() > 4 && out_path.compare(out_path.size() - 4, 4, ".png") == 0 ? out_path.substr(0, out_path.size() - 4) : out_path;
+        for (uint32_t f = 0; frames > 1 && f < frames; ++f) {
+            char name[32];
+            std::snprintf(name, sizeof(name), "_%04u.png", f);
+            static_cast<raytracer::HipRendererBase*>(renderer.get())->out_path = stem + name;
+            if (f > 0) {
+                const rt_update_stats us = scene.spin(spin * (double)f);
+                std::printf("Frame %u: update %.3f ms on the device (%u launches, %u nodes refit)\n", f, us.device_ms, us.launches, us.refit_nodes);
+            }
+            renderer->render_frame(camera, scene);
+        }
     } catch (const std::exception& e) {
         std::printf("Caught exception: %s\n", e.what());
         return 1;

@@ -11,6 +11,7 @@
 #pragma once
 #include <array>
 #include <chrono>
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -47,12 +48,56 @@ struct Scene {
     float camera_position[3], camera_direction[3], camera_focal_length;
 
     // Scene(app, filepath): src/scene.cpp:54-129. `device` replaces App's SYCL device.
-    Scene(const std::string& filepath, int device = 0, int bvh_kind = RT_BVH_DEFAULT, bool verbose = true)
+    // flags: RT_SCENE_UPDATABLE for a scene that spin() moves between frames
+    Scene(const std::string& filepath, int device = 0, int bvh_kind = RT_BVH_DEFAULT, bool verbose = true, uint32_t flags = 0)
         : data(rthost::load_glb(filepath, verbose)), device(device), bvh_kind(bvh_kind) {
         for (int k = 0; k < 3; ++k) camera_position[k] = data.camera_position[k], camera_direction[k] = data.camera_direction[k];
         camera_focal_length = data.camera_focal_length;
         const rt_scene_desc d = data.desc();
-        rt_check(rt_scene_create(&d, device, bvh_kind, &handle));
+        rt_check(rt_scene_create_ex(&d, device, bvh_kind, flags, &handle));
+        rt_scene_info_t info{};
+        rt_check(rt_scene_info(handle, &info));
+        for (int k = 0; k < 3; ++k) spin_centre[k] = 0.5f * (info.bounds_lo[k] + info.bounds_hi[k]);
+    }
+    float spin_centre[3] = {0, 0, 0}; // the centre of the scene's bounds as loaded
+
+    // Every instance turned by `deg` degrees (from its loaded pose) about the vertical axis through spin_centre: rt_scene_update of an
+    // updatable scene. normal_mat = transpose(inverse(mat3(transform))) as the loader makes it.
+    rt_update_stats spin(double deg) {
+        const double a = deg * 3.14159265358979323846 / 180.0;
+        const float c = (float)std::cos(a), s = (float)std::sin(a);
+        // R about y through the centre, column-major: x' = c x + s z, z' = -s x + c z (+ the translation that keeps the centre)
+        float r[16] = {c, 0, -s, 0, 0, 1, 0, 0, s, 0, c, 0, 0, 0, 0, 1};
+        r[12] = spin_centre[0] - (c * spin_centre[0] + s * spin_centre[2]);
+        r[14] = spin_centre[2] - (-s * spin_centre[0] + c * spin_centre[2]);
+        std::vector<rt_instance> inst(data.instances);
+        for (rt_instance& in : inst) {
+            float m[16];
+            for (int col = 0; col < 4; ++col)
+                for (int row = 0; row < 4; ++row) {
+                    float v = 0.0f;
+                    for (int k = 0; k < 4; ++k) v += r[k * 4 + row] * in.transform[col * 4 + k];
+                    m[col * 4 + row] = v;
+                }
+            std::memcpy(in.transform, m, sizeof(m));
+            // cofactors of the 3x3 part: inverse-transpose = cofactor matrix / det
+            auto e = [&](int col, int row) { return m[col * 4 + row]; };
+            float cof[3][3];
+            for (int i = 0; i < 3; ++i)
+                for (int j = 0; j < 3; ++j) {
+                    const int i1 = (i + 1) % 3, i2 = (i + 2) % 3, j1 = (j + 1) % 3, j2 = (j + 2) % 3;
+                    cof[i][j] = e(i1, j1) * e(i2, j2) - e(i1, j2) * e(i2, j1); // cofactor of column i, row j
+                }
+            const float det = e(0, 0) * cof[0][0] + e(0, 1) * cof[0][1] + e(0, 2) * cof[0][2];
+            for (int i = 0; i < 3; ++i)
+                for (int j = 0; j < 3; ++j) in.normal_mat[i * 3 + j] = cof[i][j] / det;
+        }
+        rt_scene_update_desc u{};
+        u.n_instances = (uint32_t)inst.size();
+        u.instances = inst.data();
+        rt_update_stats st{};
+        rt_check(rt_scene_update(handle, &u, &st));
+        return st;
     }
     Scene(const Scene&) = delete;
     Scene& operator=(const Scene&) = delete;

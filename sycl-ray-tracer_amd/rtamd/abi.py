@@ -22,6 +22,7 @@ RT_RENDERER_MEGAKERNEL, RT_RENDERER_WAVEFRONT = 0, 1
 RT_SEED_DEFAULT, RT_SEED_WAVEFRONT, RT_SEED_MEGAKERNEL = 0, 1, 2
 RT_BVH_DEFAULT, RT_BVH_LBVH, RT_BVH_SAH, RT_BVH_LBVH_GPU = 0, 1, 2, 3
 RT_BVH_MEDIAN_INTERNAL = 99  # not a request: what rt_dev_scene_tree reports after a builder fell back to the balanced host tree
+RT_SCENE_UPDATABLE = 1
 RT_TEX_SIZE = 512
 RT_TEX_MAX_LAYERS = 128
 
@@ -91,6 +92,24 @@ class rt_scene_info_t(C.Structure):
     ]
 
 
+class rt_scene_update_desc(C.Structure):
+    _fields_ = [
+        ("n_instances", C.c_uint32),
+        ("instances", C.POINTER(rt_instance)),
+        ("n_vertices", C.c_uint32),
+        ("positions", C.POINTER(C.c_float)),
+        ("normals", C.POINTER(C.c_float)),
+    ]
+
+
+class rt_update_stats(C.Structure):
+    _fields_ = [
+        ("device_ms", C.c_double),
+        ("launches", C.c_uint32),
+        ("refit_nodes", C.c_uint32),
+    ]
+
+
 RT_SCHED_ALL_BOUNCES = 0xFFFFFFFF
 # kernel families of rt_stats.launches_by_kernel (include/rt_mi355x.h)
 KERNELS = {"megakernel": 0, "wf_init": 1, "wf_generate": 2, "wf_extend": 3, "wf_shade": 4, "wf_shade_reorder": 5, "wf_shade_matsort": 6,
@@ -143,6 +162,8 @@ PROTOTYPES = {
     "rt_camera_init": (C.c_int, [_P(rt_camera), C.c_int32, C.c_int32, _P(C.c_float), _P(C.c_float), C.c_float]),
     "rt_scene_create": (C.c_int, [_P(rt_scene_desc), C.c_int, C.c_int, _P(C.c_void_p)]),
     "rt_scene_destroy": (None, [C.c_void_p]),
+    "rt_scene_create_ex": (C.c_int, [_P(rt_scene_desc), C.c_int, C.c_int, C.c_uint32, _P(C.c_void_p)]),
+    "rt_scene_update": (C.c_int, [C.c_void_p, _P(rt_scene_update_desc), _P(rt_update_stats)]),
     "rt_scene_info": (C.c_int, [C.c_void_p, _P(rt_scene_info_t)]),
     "rt_scene_check_bvh": (C.c_int, [C.c_void_p]),
     "rt_scene_count_visits": (C.c_int, [C.c_void_p, C.c_uint32, _P(C.c_float), _P(C.c_float), C.c_int, _P(C.c_uint64), _P(C.c_uint64),
@@ -272,6 +293,8 @@ DEV_PROTOTYPES = {
     #  out global_index[capacity] | NULL, out wverts[capacity] | NULL, capacity): the scene's BVH as built (csrc/rt_abi.hip; tests/test_gpu_lbvh.py)
     "rt_dev_scene_tree": (C.c_int, [C.c_void_p, _P(C.c_uint32), _P(C.c_uint32), _P(C.c_uint32), _P(C.c_uint32), _P(C.c_int32), _P(C.c_float),
                                     _P(C.c_float), C.c_void_p, _P(C.c_uint32), _P(C.c_float), C.c_uint32]),
+    # (renderer, out captures): hipGraphs the renderer has instantiated (csrc/rt_abi.hip; tests/test_gpu_scene_update.py)
+    "rt_dev_renderer_graph_captures": (C.c_int, [C.c_void_p, _P(C.c_uint32)]),
     # (count, nk[count], klo[count x 4 x 3], khi[count x 4 x 3], out nodes[64 B x count], out ok[count]): the host quantiser on padded boxes
     "rt_dev_quantise_node": (C.c_int, [C.c_uint32, _P(C.c_int32), _P(C.c_float), _P(C.c_float), C.c_void_p, _P(C.c_uint8)]),
 }

@@ -38,14 +38,47 @@ class Camera:
 class Scene:
     """Device-resident scene: == what raytracer::Scene hands the kernels (RTCScene + GeometryData)."""
 
-    def __init__(self, desc: SceneDesc, device: int = 0, bvh: int = abi.RT_BVH_DEFAULT, lib=None):
-        """`lib`: another build of the library (abi.load_developer_library()); renderers of this scene use the same one."""
+    def __init__(self, desc: SceneDesc, device: int = 0, bvh: int = abi.RT_BVH_DEFAULT, lib=None, updatable: bool = False):
+        """`lib`: another build of the library (abi.load_developer_library()); renderers of this scene use the same one.
+        `updatable`: rt_scene_create_ex with RT_SCENE_UPDATABLE, so that update() can move instances and vertices."""
         self.desc = desc
         self.device = device
         self._lib = lib or abi.load_library()
         self._c = desc.to_c()
         self.h = C.c_void_p()
-        abi.check(self._lib.rt_scene_create(C.byref(self._c), device, bvh, C.byref(self.h)), self._lib)
+        if updatable:
+            abi.check(self._lib.rt_scene_create_ex(C.byref(self._c), device, bvh, abi.RT_SCENE_UPDATABLE, C.byref(self.h)), self._lib)
+        else:
+            abi.check(self._lib.rt_scene_create(C.byref(self._c), device, bvh, C.byref(self.h)), self._lib)
+
+    def update(self, instances=None, positions=None, normals=None) -> abi.rt_update_stats:
+        """rt_scene_update: new instance matrices and / or object-space vertices, the BVH refit in place. `instances`: (transforms (I, 16),
+        normal_mats (I, 9)) or None; `positions` / `normals`: (V, 3) or None. Returns the update's statistics (device_ms, launches,
+        refit_nodes). self.desc is replaced by the description the scene now behaves as (SceneDesc.updated)."""
+        u = abi.rt_scene_update_desc()
+        keep = []
+        if instances is not None:
+            xf, nm = instances
+            n = int(np.asarray(xf).shape[0])
+            insts = (abi.rt_instance * max(n, 1))()
+            words = np.frombuffer(insts, np.float32).reshape(-1, 26)
+            words[:n, :16] = np.asarray(xf, np.float32).reshape(n, 16)
+            words[:n, 16:25] = np.asarray(nm, np.float32).reshape(n, 9)
+            words.view(np.uint32)[:n, 25] = np.asarray(self.desc.inst_material, np.uint32)[:n]
+            u.n_instances, u.instances = n, insts
+            keep.append(insts)
+        if positions is not None or normals is not None:
+            u.n_vertices = int(self.desc.positions.shape[0])
+            for name, a in (("positions", positions), ("normals", normals)):
+                if a is not None:
+                    a = np.ascontiguousarray(a, np.float32).reshape(-1, 3)
+                    u.n_vertices = a.shape[0]
+                    setattr(u, name, abi.fptr(a))
+                    keep.append(a)
+        st = abi.rt_update_stats()
+        abi.check(self._lib.rt_scene_update(self.h, C.byref(u), C.byref(st)), self._lib)
+        self.desc = self.desc.updated(instances, positions, normals)
+        return st
 
     def info(self) -> abi.rt_scene_info_t:
         out = abi.rt_scene_info_t()

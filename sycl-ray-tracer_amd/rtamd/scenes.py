@@ -201,6 +201,21 @@ class SceneDesc:
         self._keep = [insts, mats]
         return d
 
+    def updated(self, instances=None, positions=None, normals=None) -> "SceneDesc":
+        """D' of rt_scene_update: this description with new instance matrices (transforms (I, 16), normal_mats (I, 9)) and / or new
+        object-space positions / normals (V, 3); everything else shared. rt_scene_create of the result is what an updated scene behaves as."""
+        import copy
+        out = copy.copy(self)
+        if instances is not None:
+            out.transforms = np.ascontiguousarray(np.asarray(instances[0], f32).reshape(-1, 16))
+            out.normal_mats = np.ascontiguousarray(np.asarray(instances[1], f32).reshape(-1, 9))
+        if positions is not None:
+            out.positions = np.ascontiguousarray(np.asarray(positions, f32).reshape(-1, 3))
+        if normals is not None:
+            out.normals = np.ascontiguousarray(np.asarray(normals, f32).reshape(-1, 3))
+        out._keep = []
+        return out
+
     def world_triangles(self) -> np.ndarray:
         """(T,3,3) float64 world-space vertices (for analytic checks in tests)."""
         out = np.zeros((self.n_triangles, 3, 3))

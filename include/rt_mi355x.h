@@ -427,6 +427,63 @@ int rt_render_frame_continue_adaptive_device(rt_renderer* r, uint32_t samples, f
                                              uint32_t* n_blocks_out);
 int rt_renderer_block_errors(const rt_renderer* r, float* out);
 
+/* ---- Primary-hit G-buffer and the a-trous denoiser (no reference counterpart: the reference returns the raw Monte Carlo estimate).
+ *
+ * rt_scene_gbuffer: the guide images of a camera's first hits, one unjittered ray per pixel. H = cam->height rows, W = cam->width columns,
+ * row 0 first; each output is H*W*4 fp32. Per pixel (x, y), in R1 arithmetic:
+ *   pc = (pixel00 + (float)x * delta_u) + (float)y * delta_v (camera_ray's pixel centre, no jitter); d = pc - center (fp32, not half);
+ *   org = center. The hit is rt_intersect_batch's closest hit of (org, d): t, u, v and the triangle are its, bit for bit.
+ *   miss: albedo = (sky, 0), normal = (0, 0, 0, 0), position = (0, 0, 0, +inf)
+ *   hit:  w, tu, tv, the interpolated normal and the world-space shading normal with exactly the expressions of shading (rt_device.h:
+ *         shade_hit): normals and uvs of the triangle's shading record, its instance's normal matrix, both normalisations normalize3.
+ *         albedo = the attenuation the first bounce's scatter applies, alpha 0: diffuse and metallic the material's colour or texel
+ *         (unorm8_to_float), dielectric (1, 1, 1), RT_MAT_NONE (0, 0, 0); emission is not included.
+ *         normal = (shading normal, 0); position = (org.x + d.x * t, org.y + d.y * t, org.z + d.z * t, t).
+ * The G-buffer belongs to the scene, not to a renderer: every full-frame rendering of cam shares it, whatever the tile split (a multi-GPU
+ * frame: the root device's scene computes the G-buffer of the gathered frame). Refused: RT_ERR_INVALID for a NULL argument, width or
+ * height <= 0, or a camera centre outside the contract range (rt_render_frame*'s check); RT_ERR_NO_DEVICE for a host-only scene.
+ * The host variant synchronises. The _device variant enqueues on `stream` (NULL = the null stream) and returns; the scene records an event
+ * behind the launch, one event per stream used, and rt_scene_update waits for all of them before it writes: launches pending on any number of
+ * streams read the scene as it was, and the update stays synchronous. */
+int rt_scene_gbuffer(rt_scene* scene, const rt_camera* cam, float* albedo, float* normal, float* position);
+int rt_scene_gbuffer_device(rt_scene* scene, const rt_camera* cam, void* d_albedo, void* d_normal, void* d_position, void* stream);
+
+/* Edge-avoiding a-trous wavelet filter (Dammertz, Sewtz, Hanika, Lensch, HPG 2010) guided by rt_scene_gbuffer's planes.
+ * Inputs are H x W x 4 fp32: the frame as a renderer writes it (rgb = sqrt(mean), alpha 1) and the three guides. Outputs: out_f32 H*W*4
+ * floats, out_u8 H*W*4 bytes; either may be NULL, not both. out_f32 may alias rgba_f32 (in-place); no other aliasing is allowed.
+ * The filter, every operation one R1 fp32 op, left to right:
+ *   1. L_p = (F_r*F_r, F_g*F_g, F_b*F_b): filtering happens in linear radiance.
+ *   2. For i = 0 .. iterations-1, step s = 2^i, every pixel p = (x, y): taps q = (x + s*dx, y + s*dy), dy = -2..2 (outer), dx = -2..2
+ *      (inner); taps outside the image are skipped, and so is a tap that differs from p in being a hit (a hit: P.w finite).
+ *        E = ((dot(L_p-L_q)*kc_i + dot(N_p-N_q)*kn_i) + dot(P_p.xyz-P_q.xyz)*kx) + dot(A_p-A_q)*ka
+ *      dot = (x*x + y*y) + z*z; a term whose coefficient is 0 is left out (E starts at +0); k = RN(1/RN(sigma*sigma)), 0 for sigma = +inf;
+ *      kc_i = ldexp(kc, 2i) (the colour sigma halves per iteration), kn_i = ldexp(kn, -2i) (the normal distance over the step squared).
+ *        w = (h[dy+2]*h[dx+2]) * exp_m(-E), h = {1/16, 1/4, 3/8, 1/4, 1/16}; S += w*L_q per channel, Wsum += w, in tap order
+ *        L'_p = S / Wsum (Wsum >= 9/64: the centre tap has E = 0 and exp_m(-0) = 1). L' is the next iteration's L; the guides stay fixed.
+ *      exp_m: csrc/denoise_math.h (R1 operations only; within 4 ulp of exp on [-87, 0], exp_m(+-0) = 1, 0 below -87).
+ *   3. Output rgb = sqrt(L'), alpha 1; the unorm8 image is to_unorm8 of it, alpha 255, as a frame's.
+ *   4. iterations = 0: out_f32 is the frame bit for bit, out_u8 the frame's own unorm8 image.
+ * Refused with RT_ERR_INVALID, before any HIP call: NULL handles or pointers, device < 0, non-positive sizes, W * H >= 2^31, a shape so
+ * narrow and tall that the filter's grid of 64 x 4 tiles would exceed 2^32 threads, iterations > 10, a sigma that is NaN or below 1e-6 (so
+ * that every k_i stays finite: the centre tap's 0 * k must stay 0).
+ * A denoiser owns, for one W x H on one device, the ping-pong scratch and rt_denoise's device staging (116 bytes per pixel in all), all
+ * allocated by rt_denoiser_create: no call allocates on the device. rt_denoise synchronises; rt_denoise_device enqueues on `stream` (NULL = the null stream) and returns.
+ * Calls on one denoiser are serialised by the denoiser: each records an event that the next call's stream waits for. */
+typedef struct rt_denoise_params {
+    uint32_t iterations;   /* 0 .. 10; 0 = copy                                                      */
+    float sigma_color;     /* >= 1e-6, +inf = guide ignored; NaN / < 1e-6 -> RT_ERR_INVALID          */
+    float sigma_normal;
+    float sigma_position;  /* world units                                                            */
+    float sigma_albedo;
+} rt_denoise_params;       /* 20 bytes */
+typedef struct rt_denoiser rt_denoiser;
+int rt_denoiser_create(int device, int32_t width, int32_t height, rt_denoiser** out);
+void rt_denoiser_destroy(rt_denoiser* d);
+int rt_denoise(rt_denoiser* d, const rt_denoise_params* p, const float* rgba_f32, const float* albedo, const float* normal,
+               const float* position, float* out_f32, uint8_t* out_u8);
+int rt_denoise_device(rt_denoiser* d, const rt_denoise_params* p, const void* d_rgba_f32, const void* d_albedo, const void* d_normal,
+                      const void* d_position, void* d_out_f32, void* d_out_u8, void* stream);
+
 /* ---- Multi-GPU frame gather over xGMI (no reference counterpart: the reference renders on ONE device and hands its
  * single image to stbi_write_png, src/main.cpp:57-70, src/util.hpp:8-33). SURVEY §8(e): the frame is split into interleaved
  * strips (rt_renderer_set_tile), every GPU renders its strips into its own compact device buffer, and ONE collective brings

@@ -137,6 +137,7 @@ int rt_scene_create_ex(const rt_scene_desc* desc, int device, int bvh_kind, uint
 void rt_scene_destroy(rt_scene* s) {
     if (!s) return;
     if (s->device >= 0 && hipSetDevice(s->device) == hipSuccess) {
+        for (auto& se : s->ev_gbuffer) (void)hipEventSynchronize(se.second), (void)hipEventDestroy(se.second);
         (void)hipFree((void*)s->dev.nodes), (void)hipFree((void*)s->dev.tris), (void)hipFree((void*)s->dev.shade);
         (void)hipFree((void*)s->dev.inst), (void)hipFree((void*)s->dev.mats), (void)hipFree((void*)s->dev.tex);
     }

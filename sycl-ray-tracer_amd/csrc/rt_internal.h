@@ -5,6 +5,8 @@
 //   rt_comm.hip    the multi-GPU frame gather (RCCL) and its de-interleave kernel
 //   rt_probes.hip  rt_intersect_batch and the rt_probe_* entry points with their kernels (rt_probe_kernels.h)
 //   rt_update.hip  dynamic scenes: rt_scene_create_ex's updatable state, rt_scene_update and its refit kernels
+//   rt_gbuffer.hip the primary-hit G-buffer (rt_scene_gbuffer[_device]) and its kernel
+//   rt_denoise.hip the a-trous denoiser (rt_denoiser_*, rt_denoise[_device]) and its kernels
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -136,6 +138,9 @@ struct rt_scene {
     SceneUpdate* upd = nullptr; // RT_SCENE_UPDATABLE only
     uint64_t generation = 0;    // bumped by every rt_scene_update: renderers drop what belongs to an older one
     uint32_t frames_pending = 0; // frames of its renderers between _begin and _end (an update is refused meanwhile)
+    // one event per stream a G-buffer was enqueued on (rt_scene_gbuffer[_device]), recorded behind every launch there: rt_scene_update waits for
+    // all of them, so no launch on any stream still reads the scene when it is rewritten
+    std::vector<std::pair<hipStream_t, hipEvent_t>> ev_gbuffer;
 };
 
 // kernel launches of one frame, in all and per kernel family (rt_stats::launches_by_kernel)

@@ -22,6 +22,8 @@
 #include <thread>
 #include <vector>
 
+#include <hip/hip_runtime_api.h>
+
 #include "../../include/rt_mi355x.h"
 #include "png.h"
 #include "scene_loader.h"
@@ -150,6 +152,17 @@ struct HipRendererBase : public IRenderer {
     // `adaptive` on the two-image error, blocks under min_samples samples always) — rt_render_frame_continue_adaptive; every rank adapts its own
     float adaptive = -1.0f;
     uint32_t min_samples = 0;
+    // Extension: denoise > 0 runs the a-trous denoiser (rt_denoise_device, `denoise` iterations, the defaults of rtamd/renderer.py) on the frame
+    // after its last pass, guided by the G-buffer of the camera (rt_scene_gbuffer_device), and writes the denoised unorm8 image. A tiled frame is
+    // denoised on the root device after the gather (its fp32 plane gathered too), with the root's scene. Everything stays on that device.
+    uint32_t denoise = 0;
+    std::vector<float> frame_f32;
+    rt_denoiser* denoiser = nullptr;
+    float* d_gbuf = nullptr;      // the three guide planes, W*H*4 floats each (on den_device)
+    uint8_t* d_den_u8 = nullptr;  // the denoised unorm8 image
+    hipStream_t den_stream = nullptr;
+    hipEvent_t den_ev[3] = {nullptr, nullptr, nullptr};
+    int den_device = -1;
     std::vector<rt_renderer*> tile_handles;
     rt_comm* comm = nullptr;
     rt_stats last{};
@@ -160,6 +173,57 @@ struct HipRendererBase : public IRenderer {
         for (rt_renderer* h : tile_handles) rt_renderer_destroy(h);
         rt_comm_destroy(comm);
         rt_renderer_destroy(handle);
+        release_denoiser();
+    }
+
+    // the denoiser's defaults (rtamd/renderer.py: DENOISE_*): sigma_position is a fraction of the largest extent of the scene's bounds
+    static constexpr float kSigmaColor = 1.0f, kSigmaNormal = 0.25f, kPositionFraction = 0.05f, kSigmaAlbedo = 0.1f;
+
+    static void hip_check(hipError_t e, const char* what) {
+        if (e != hipSuccess) throw std::runtime_error(std::string(what) + ": " + hipGetErrorString(e));
+    }
+    void release_denoiser() {
+        if (den_device >= 0 && hipSetDevice(den_device) == hipSuccess) {
+            if (den_stream) (void)hipStreamSynchronize(den_stream), (void)hipStreamDestroy(den_stream);
+            for (hipEvent_t& e : den_ev)
+                if (e) (void)hipEventDestroy(e), e = nullptr;
+            (void)hipFree(d_gbuf), (void)hipFree(d_den_u8);
+        }
+        rt_denoiser_destroy(denoiser);
+        denoiser = nullptr, d_gbuf = nullptr, d_den_u8 = nullptr, den_stream = nullptr, den_device = -1;
+    }
+
+    // d_frame (the last pass's fp32 frame, W x H, on `dev`) -> `image`, denoised with the G-buffer of `sc` (the scene on `dev`); prints the device
+    // time of the G-buffer and of the filter (hipEvents on one stream). The frame is complete when this is called: every render call before it returns
+    // with its frame on the device.
+    void denoise_image(const Camera& camera, rt_scene* sc, int dev, const void* d_frame) {
+        const size_t n = (size_t)img_size[0] * (size_t)img_size[1];
+        if (den_device != dev) release_denoiser();
+        hip_check(hipSetDevice(dev), "hipSetDevice");
+        if (!denoiser) {
+            den_device = dev;
+            rt_check(rt_denoiser_create(dev, img_size[0], img_size[1], &denoiser));
+            hip_check(hipMalloc((void**)&d_gbuf, 3 * n * 16), "hipMalloc");
+            hip_check(hipMalloc((void**)&d_den_u8, n * 4), "hipMalloc");
+            hip_check(hipStreamCreateWithFlags(&den_stream, hipStreamNonBlocking), "hipStreamCreate");
+            for (hipEvent_t& e : den_ev) hip_check(hipEventCreate(&e), "hipEventCreate");
+        }
+        rt_scene_info_t info{};
+        rt_check(rt_scene_info(sc, &info));
+        float scale = 0.0f;
+        for (int a = 0; a < 3; ++a) scale = std::max(scale, info.bounds_hi[a] - info.bounds_lo[a]);
+        const rt_denoise_params p{denoise, kSigmaColor, kSigmaNormal, kPositionFraction * scale, kSigmaAlbedo};
+        hip_check(hipEventRecord(den_ev[0], den_stream), "hipEventRecord");
+        rt_check(rt_scene_gbuffer_device(sc, &camera.c, d_gbuf, d_gbuf + 4 * n, d_gbuf + 8 * n, den_stream));
+        hip_check(hipEventRecord(den_ev[1], den_stream), "hipEventRecord");
+        rt_check(rt_denoise_device(denoiser, &p, d_frame, d_gbuf, d_gbuf + 4 * n, d_gbuf + 8 * n, nullptr, d_den_u8, den_stream));
+        hip_check(hipEventRecord(den_ev[2], den_stream), "hipEventRecord");
+        hip_check(hipStreamSynchronize(den_stream), "hipStreamSynchronize");
+        float g_ms = 0.0f, f_ms = 0.0f;
+        hip_check(hipEventElapsedTime(&g_ms, den_ev[0], den_ev[1]), "hipEventElapsedTime");
+        hip_check(hipEventElapsedTime(&f_ms, den_ev[1], den_ev[2]), "hipEventElapsedTime");
+        hip_check(hipMemcpy(image, d_den_u8, n * 4, hipMemcpyDeviceToHost), "hipMemcpy");
+        std::printf("Denoise: %u iterations, G-buffer %.3f ms, filter %.3f ms on device %d\n", denoise, g_ms, f_ms, dev);
     }
 
     // one frame over devices.size() tiles: returns with `image` assembled and `last` = summed rays / wall time
@@ -188,16 +252,17 @@ struct HipRendererBase : public IRenderer {
             threads.emplace_back([&, k]() {
                 rt_renderer* h = tile_handles[k];
                 if (rt_renderer_set_russian_roulette(h, russian_roulette) != RT_OK || (passes > 1 && rt_renderer_set_progressive(h, 1) != RT_OK) ||
-                    rt_render_frame_begin(h, &camera.c, nullptr, rt_renderer_tile_u8(h), nullptr) != RT_OK ||
+                    rt_render_frame_begin(h, &camera.c, denoise ? rt_renderer_tile_f32(h) : nullptr, rt_renderer_tile_u8(h), nullptr) != RT_OK ||
                     rt_render_frame_end(h, &st[k]) != RT_OK) {
                     err[k] = rt_last_error(); // rt_last_error is per thread
                     return;
                 }
                 for (uint32_t p = 1; p < passes; ++p) { // every rank continues its own strips, into its own tile buffer
                     rt_stats more{};
-                    const int rc = adaptive >= 0.0f ? rt_render_frame_continue_adaptive_device(h, sample_count, adaptive, min_samples, nullptr,
+                    void* f32 = denoise ? rt_renderer_tile_f32(h) : nullptr;
+                    const int rc = adaptive >= 0.0f ? rt_render_frame_continue_adaptive_device(h, sample_count, adaptive, min_samples, f32,
                                                                                                  rt_renderer_tile_u8(h), nullptr, &more, nullptr)
-                                                    : rt_render_frame_continue_device(h, sample_count, nullptr, rt_renderer_tile_u8(h), nullptr, &more);
+                                                    : rt_render_frame_continue_device(h, sample_count, f32, rt_renderer_tile_u8(h), nullptr, &more);
                     if (rc != RT_OK) {
                         err[k] = rt_last_error();
                         return;
@@ -209,7 +274,7 @@ struct HipRendererBase : public IRenderer {
         for (auto& t : threads) t.join();
         for (uint32_t k = 0; k < G; ++k)
             if (!err[k].empty()) throw std::runtime_error("librt_mi355x (tile " + std::to_string(k) + "): " + err[k]);
-        rt_check(rt_frame_gather(comm, tile_handles.data(), nullptr, image, 0, 0)); // strips -> root GPU -> full frame -> host, once
+        rt_check(rt_frame_gather(comm, tile_handles.data(), nullptr, image, denoise ? 1 : 0, 0)); // strips -> root GPU -> full frame -> host, once
         const double wall = std::chrono::duration<double>(std::chrono::high_resolution_clock::now() - t0).count();
         last = rt_stats{};
         for (uint32_t k = 0; k < G; ++k) {
@@ -233,6 +298,7 @@ struct HipRendererBase : public IRenderer {
             if (kind == RT_RENDERER_WAVEFRONT)
                 for (uint32_t s = 0; s < sample_count * passes; ++s) std::printf("Sample %u\n", s);
             render_tiled(camera, scene);
+            if (denoise) denoise_image(camera, scene.on_device(devices[0]), devices[0], rt_comm_frame_f32(comm)); // the root's frame and scene
             report_and_write(last.seconds); // tiles run concurrently: the frame time is the wall time of the slowest
             return;
         }
@@ -247,13 +313,17 @@ struct HipRendererBase : public IRenderer {
         if (passes > 1) rt_check(rt_renderer_set_progressive(handle, 1));
         if (kind == RT_RENDERER_WAVEFRONT)
             for (uint32_t s = 0; s < sample_count * passes; ++s) std::printf("Sample %u\n", s); // src/render_wavefront.cpp:402
-        rt_check(rt_render_frame(handle, &camera.c, nullptr, image, &last));
+        // (a host fp32 pointer makes the renderer write its own device copy of the frame, rt_renderer_tile_f32, which the denoiser reads)
+        if (denoise) frame_f32.resize((size_t)img_size[0] * (size_t)img_size[1] * 4);
+        float* f32 = denoise ? frame_f32.data() : nullptr;
+        rt_check(rt_render_frame(handle, &camera.c, f32, image, &last));
         for (uint32_t p = 1; p < passes; ++p) { // the image of the last pass holds all sample_count x passes samples
             rt_stats more{};
-            if (adaptive >= 0.0f) rt_check(rt_render_frame_continue_adaptive(handle, sample_count, adaptive, min_samples, nullptr, image, &more, nullptr));
-            else rt_check(rt_render_frame_continue(handle, sample_count, nullptr, image, &more));
+            if (adaptive >= 0.0f) rt_check(rt_render_frame_continue_adaptive(handle, sample_count, adaptive, min_samples, f32, image, &more, nullptr));
+            else rt_check(rt_render_frame_continue(handle, sample_count, f32, image, &more));
             add_stats(last, more);
         }
+        if (denoise) denoise_image(camera, scene.handle, scene.device, rt_renderer_tile_f32(handle)); // the renderer's own copy of the frame
         report_and_write(last.device_ms * 1e-3);
     }
 

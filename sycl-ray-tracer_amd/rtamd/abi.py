@@ -152,6 +152,17 @@ class rt_stats(C.Structure):
     ]
 
 
+class rt_denoise_params(C.Structure):
+    _fields_ = [
+        ("iterations", C.c_uint32),
+        ("sigma_color", C.c_float),
+        ("sigma_normal", C.c_float),
+        ("sigma_position", C.c_float),
+        ("sigma_albedo", C.c_float),
+    ]
+
+
+assert C.sizeof(rt_denoise_params) == 20
 assert C.sizeof(rt_material) == 44
 assert C.sizeof(rt_instance) == 104
 assert C.sizeof(rt_camera) == 56
@@ -200,6 +211,14 @@ PROTOTYPES = {
     "rt_render_frame_continue_adaptive_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_float, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
                                                            _P(rt_stats), _P(C.c_uint32)]),
     "rt_renderer_block_errors": (C.c_int, [C.c_void_p, _P(C.c_float)]),
+    "rt_scene_gbuffer": (C.c_int, [C.c_void_p, _P(rt_camera), _P(C.c_float), _P(C.c_float), _P(C.c_float)]),
+    "rt_scene_gbuffer_device": (C.c_int, [C.c_void_p, _P(rt_camera), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_denoiser_create": (C.c_int, [C.c_int, C.c_int32, C.c_int32, _P(C.c_void_p)]),
+    "rt_denoiser_destroy": (None, [C.c_void_p]),
+    "rt_denoise": (C.c_int, [C.c_void_p, _P(rt_denoise_params), _P(C.c_float), _P(C.c_float), _P(C.c_float), _P(C.c_float),
+                             _P(C.c_float), _P(C.c_uint8)]),
+    "rt_denoise_device": (C.c_int, [C.c_void_p, _P(rt_denoise_params), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.c_void_p]),
     "rt_comm_create": (C.c_int, [C.c_int, _P(C.c_int), _P(C.c_void_p)]),
     "rt_comm_destroy": (None, [C.c_void_p]),
     "rt_comm_uses_rccl": (C.c_int, [C.c_void_p]),

@@ -98,6 +98,25 @@ class Scene:
                                                abi.fptr(v), abi.u32ptr(tri)), self._lib)
         return t, u, v, tri
 
+    def gbuffer(self, camera: Camera) -> dict:
+        """rt_scene_gbuffer: the guide images of the camera's primary hits, {"albedo", "normal", "position"}, each (H, W, 4) float32
+        (include/rt_mi355x.h states what a pixel holds)."""
+        w, h = int(camera.c.width), int(camera.c.height)
+        out = {k: np.zeros((max(h, 0), max(w, 0), 4), np.float32) for k in ("albedo", "normal", "position")}
+        abi.check(self._lib.rt_scene_gbuffer(self.h, C.byref(camera.c), abi.fptr(out["albedo"]), abi.fptr(out["normal"]),
+                                             abi.fptr(out["position"])), self._lib)
+        return out
+
+    def gbuffer_device(self, camera: Camera, d_albedo: int, d_normal: int, d_position: int, stream: int = 0) -> None:
+        """rt_scene_gbuffer_device: the three planes into DEVICE buffers of H*W*4 floats (e.g. torch .data_ptr()), enqueued on `stream`."""
+        abi.check(self._lib.rt_scene_gbuffer_device(self.h, C.byref(camera.c), C.c_void_p(d_albedo or None), C.c_void_p(d_normal or None),
+                                                    C.c_void_p(d_position or None), C.c_void_p(stream or None)), self._lib)
+
+    def scale(self) -> np.float32:
+        """The largest extent of the scene's bounds (rt_scene_info), fp32: what the denoiser's default sigma_position is a fraction of."""
+        i = self.info()
+        return np.float32(max(np.float32(i.bounds_hi[a]) - np.float32(i.bounds_lo[a]) for a in range(3)))
+
     def scatter(self, material: int, dirs, normals, uvs, seeds):
         dirs = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
         normals = np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
@@ -457,6 +476,70 @@ class TileComm:
     def close(self):
         if self.h:
             self._lib.rt_comm_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+# The denoiser's defaults (chosen by scripts/denoise_probe.py's sweep on the atrium and the Cornell box). sigma_position is
+# DENOISE_POSITION_FRACTION of the scene's scale (Scene.scale()); host/main.cpp's --denoise uses the same values.
+DENOISE_ITERATIONS = 5
+DENOISE_SIGMA_COLOR = 1.0
+DENOISE_SIGMA_NORMAL = 0.25
+DENOISE_POSITION_FRACTION = 0.05
+DENOISE_SIGMA_ALBEDO = 0.1
+
+
+def denoise_params(iterations: int = DENOISE_ITERATIONS, sigma_color: float = DENOISE_SIGMA_COLOR, sigma_normal: float = DENOISE_SIGMA_NORMAL,
+                   sigma_position: float | None = None, sigma_albedo: float = DENOISE_SIGMA_ALBEDO, scene_scale: float | None = None):
+    """rt_denoise_params; sigma_position None: DENOISE_POSITION_FRACTION * scene_scale, in fp32 (scene_scale is then required)."""
+    if sigma_position is None:
+        if scene_scale is None:
+            raise ValueError("give sigma_position or scene_scale (Scene.scale())")
+        sigma_position = np.float32(DENOISE_POSITION_FRACTION) * np.float32(scene_scale)
+    return abi.rt_denoise_params(int(iterations), float(sigma_color), float(sigma_normal), float(sigma_position), float(sigma_albedo))
+
+
+class Denoiser:
+    """rt_denoiser: the edge-avoiding a-trous filter for W x H frames on one device, guided by Scene.gbuffer's planes."""
+
+    def __init__(self, device: int, width: int, height: int, lib=None):
+        self._lib = lib or abi.load_library()
+        self.width, self.height = int(width), int(height)
+        self.h = C.c_void_p()
+        abi.check(self._lib.rt_denoiser_create(int(device), self.width, self.height, C.byref(self.h)), self._lib)
+
+    def denoise(self, frame_f32: np.ndarray, gbuf: dict, iterations: int = DENOISE_ITERATIONS, want_f32: bool = True, want_u8: bool = True,
+                out_f32: np.ndarray | None = None, **sigmas):
+        """rt_denoise of a (H, W, 4) float32 frame; returns (f32, u8), None for a plane not asked for. `sigmas`: sigma_color,
+        sigma_normal, sigma_position, sigma_albedo, scene_scale (denoise_params). out_f32: where the fp32 result goes (may be frame_f32)."""
+        p = denoise_params(iterations, **sigmas)
+        shape = (self.height, self.width, 4)
+        frame_f32 = np.ascontiguousarray(frame_f32, np.float32)
+        planes = [np.ascontiguousarray(gbuf[k], np.float32) for k in ("albedo", "normal", "position")]
+        for a in [frame_f32] + planes:
+            if a.shape != shape:
+                raise ValueError(f"expected {shape}, got {a.shape}")
+        f = (out_f32 if out_f32 is not None else np.zeros(shape, np.float32)) if want_f32 else None
+        b = np.zeros(shape, np.uint8) if want_u8 else None
+        abi.check(self._lib.rt_denoise(self.h, C.byref(p), abi.fptr(frame_f32), *(abi.fptr(a) for a in planes),
+                                       abi.fptr(f) if f is not None else None, abi.u8ptr(b) if b is not None else None), self._lib)
+        return f, b
+
+    def denoise_device(self, d_frame: int, d_albedo: int, d_normal: int, d_position: int, d_out_f32: int = 0, d_out_u8: int = 0,
+                       stream: int = 0, iterations: int = DENOISE_ITERATIONS, **sigmas) -> None:
+        """rt_denoise_device on DEVICE pointers (e.g. torch .data_ptr()), enqueued on `stream`."""
+        p = denoise_params(iterations, **sigmas)
+        v = [C.c_void_p(x or None) for x in (d_frame, d_albedo, d_normal, d_position, d_out_f32, d_out_u8, stream)]
+        abi.check(self._lib.rt_denoise_device(self.h, C.byref(p), *v), self._lib)
+
+    def close(self):
+        if self.h:
+            self._lib.rt_denoiser_destroy(self.h)
             self.h = C.c_void_p()
 
     def __del__(self):

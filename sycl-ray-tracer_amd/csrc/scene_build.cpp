@@ -722,28 +722,7 @@ int build_host_scene(const rt_scene_desc* d, int bvh_kind, HostScene& hs, std::s
         hs.stack_need = need(0);
         if (hs.stack_need + 2 >= (uint32_t)kStackSize) return build_host_scene(d, RT_BVH_MEDIAN_INTERNAL, hs, err);
         hs.built_by = RT_BVH_LBVH_GPU;
-        // surface-area cost of the downloaded tree (the diagnostic rt_scene_info reports for the host builders too): every node's
-        // children boxes decoded, inner child 1 step x area, leaf child (triangles) x area, relative to the root's area
-        {
-            double cost = 0.0, root_area = 0.0;
-            for (size_t i = 0; i < hs.nodes.size(); ++i) {
-                const BvhNode& n = hs.nodes[i];
-                float nlo[3] = {INFINITY, INFINITY, INFINITY}, nhi[3] = {-INFINITY, -INFINITY, -INFINITY};
-                for (int k = 0; k < 4; ++k) {
-                    if (n.child[k] == kChildEmpty) continue;
-                    float lo[3], hi[3];
-                    for (int a = 0; a < 3; ++a) {
-                        lo[a] = n.origin[a] + (float)((n.q[2 * a] >> (8 * k)) & 0xffu) * n.scale(a);
-                        hi[a] = n.origin[a] + (float)((n.q[2 * a + 1] >> (8 * k)) & 0xffu) * n.scale(a);
-                        nlo[a] = std::min(nlo[a], lo[a]), nhi[a] = std::max(nhi[a], hi[a]);
-                    }
-                    const double w = n.child[k] >= 0 ? 1.0 : (double)(((uint32_t)~n.child[k] & 3u) + 1u);
-                    cost += w * (double)half_area(lo, hi);
-                }
-                if (i == 0) root_area = (double)half_area(nlo, nhi);
-            }
-            hs.sah_cost = root_area > 0.0 ? 1.0 + cost / root_area : 0.0;
-        }
+        hs.sah_cost = decoded_sah_cost(hs);
         return RT_OK;
     }
 
@@ -1080,7 +1059,31 @@ bool refit_host(HostScene& hs, const std::vector<uint32_t>& level_nodes, std::ve
     return true;
 }
 
+// Surface-area cost of a device-built tree (the diagnostic rt_scene_info reports for the host builders too): every node's children boxes
+// decoded, inner child 1 step x area, leaf child (triangles) x area, relative to the root's area.
+double decoded_sah_cost(const HostScene& hs) {
+    double cost = 0.0, root_area = 0.0;
+    for (size_t i = 0; i < hs.nodes.size(); ++i) {
+        const BvhNode& n = hs.nodes[i];
+        float nlo[3] = {INFINITY, INFINITY, INFINITY}, nhi[3] = {-INFINITY, -INFINITY, -INFINITY};
+        for (int k = 0; k < 4; ++k) {
+            if (n.child[k] == kChildEmpty) continue;
+            float lo[3], hi[3];
+            for (int a = 0; a < 3; ++a) {
+                lo[a] = n.origin[a] + (float)((n.q[2 * a] >> (8 * k)) & 0xffu) * n.scale(a);
+                hi[a] = n.origin[a] + (float)((n.q[2 * a + 1] >> (8 * k)) & 0xffu) * n.scale(a);
+                nlo[a] = std::min(nlo[a], lo[a]), nhi[a] = std::max(nhi[a], hi[a]);
+            }
+            const double w = n.child[k] >= 0 ? 1.0 : (double)(((uint32_t)~n.child[k] & 3u) + 1u);
+            cost += w * (double)half_area(lo, hi);
+        }
+        if (i == 0) root_area = (double)half_area(nlo, nhi);
+    }
+    return root_area > 0.0 ? 1.0 + cost / root_area : 0.0;
+}
+
 double refit_sah_cost(const HostScene& hs, const std::vector<float>& box) {
+    if (hs.built_by == RT_BVH_LBVH_GPU) return decoded_sah_cost(hs); // the measure its build reported: the same tree, the same cost
     if (hs.nodes.empty() || box.size() < 6 * hs.nodes.size()) return 0.0;
     const double root_area = std::max(1e-30, (double)half_area(&box[0], &box[3]));
     double cost = 0.0;

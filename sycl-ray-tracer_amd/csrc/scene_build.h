@@ -59,8 +59,10 @@ void node_levels(const std::vector<BvhNode>& nodes, std::vector<uint32_t>& level
 // quantised words 0..11 with hs.pad, level by level, and hs.sah_cost. Returns false if a node cannot be quantised.
 bool refit_host(HostScene& hs, const std::vector<uint32_t>& level_nodes, std::vector<float>& box, std::string& err);
 // Surface-area cost of a refit tree from the nodes' exact boxes (box, 6 floats per node): inner child 1 x area, leaf child its records x
-// area, relative to the root's area.
+// area, relative to the root's area. A device-built tree (RT_BVH_LBVH_GPU) keeps the measure its build reported, decoded_sah_cost.
 double refit_sah_cost(const HostScene& hs, const std::vector<float>& box);
+// The same cost from the nodes' decoded (quantised, padded) child boxes: what a device build reports.
+double decoded_sah_cost(const HostScene& hs);
 
 // Structural check used by rt_scene_check_bvh.
 int check_bvh(const HostScene& hs, std::string& err);

@@ -7,7 +7,8 @@ import pytest
 
 from rtamd import abi, scenes
 from rtamd.renderer import Camera, MegakernelRenderer, Scene, TileComm, WavefrontRenderer, assemble_tiles
-from test_scene_update import chain_scene, model_node_words, rays, same_bits, spin_about_centre, update_sequence
+from test_scene_update import (_tables_equal, _tree_equal, chain_scene, model_node_words, rays, same_bits, spin_about_centre,
+                               update_sequence)
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
@@ -145,17 +146,6 @@ def test_updated_scene_matches_the_oracle(oracle, scene_cache):
         np.testing.assert_array_equal(fr.rgba_f32, f)
         np.testing.assert_array_equal(fr.rgba_u8, b)
     s.close()
-
-
-def _tree_equal(a, b):
-    for k in ("nodes", "global_index", "wverts", "pad", "bounds_lo", "bounds_hi", "stack_need", "built_by"):
-        assert same_bits(np.asarray(a[k]), np.asarray(b[k])), k
-
-
-def _tables_equal(a, b, lds=True):
-    for k in ("packed_mat",) + (("lds_nm", "lds_mats") if lds else ()):
-        assert a[k] == b[k], k
-    assert same_bits(a["rows"], b["rows"]) and same_bits(a["words"], b["words"])
 
 
 @pytest.mark.parametrize("bvh", [abi.RT_BVH_SAH, abi.RT_BVH_LBVH])

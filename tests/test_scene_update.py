@@ -91,6 +91,88 @@ def chain_scene(m: int = 63, dups: int = 40):
     return sb.build()
 
 
+ZERO_TRIS = 700  # three reduction workgroups of 256 triangles (k_upd_transform: one thread per triangle, waves of 64)
+ZERO_PLACES = {"wave": (10, 41), "waves": (10, 200), "workgroups": (10, 310)}  # the triangles of the two zeros (slots 3t + k)
+ZERO_CASES = [(bound, order, place) for bound in ("min", "max") for order in ("neg_first", "pos_first") for place in ZERO_PLACES] + \
+             [("min", "neg_only", "workgroups"), ("max", "neg_only", "workgroups")]
+ZERO_MIX = -0.0  # off-diagonals and translation of the scene's transform: x * 1 + (-0 * y) + (-0 * z) + (-0) is x, sign of a zero included
+
+
+def _zero_transform():
+    """Identity with -0 off-diagonals and translation: world = object, bit for bit, while every other coordinate is positive."""
+    m = np.full(16, ZERO_MIX, f32)
+    m[0] = m[5] = m[10] = m[15] = 1.0
+    m[3] = m[7] = m[11] = 0.0
+    return m
+
+
+def signed_zero_scene(lib, case, axis):
+    """ZERO_TRIS triangles whose world coordinates on `axis` are all >= 0 (case[0] "min") or all <= 0 ("max"), the bound attained at exactly
+    0 by two vertices at the slots ZERO_PLACES[case[2]] names: -0 then +0 ("neg_first"), +0 then -0 ("pos_first"), or -0 alone ("neg_only").
+    Every other coordinate is positive, so the transform keeps the zeros' signs. The host std::min / std::max keep the first of equal values:
+    the bound is the first zero's bits. Asserted here on a fresh host build's world vertices, else a test of it checks nothing."""
+    bound, order, place = case
+    rng = np.random.default_rng(17 + axis)
+    pos = rng.uniform(1.0, 2.0, (ZERO_TRIS, 3, 3)).astype(f32)
+    side = f32(1.0) if bound == "min" else f32(-1.0)
+    pos[:, :, axis] = side * rng.uniform(0.5, 1.5, (ZERO_TRIS, 3)).astype(f32)
+    first, second = ZERO_PLACES[place]
+    zeros = {"neg_first": (-0.0, 0.0), "pos_first": (0.0, -0.0), "neg_only": (-0.0, None)}[order]
+    slots = []
+    for t, k, z in ((first, 1, zeros[0]), (second, 2, zeros[1])):
+        if z is not None:
+            pos[t, k, axis] = z
+            slots.append((3 * t + k, z))
+    sb = scenes.SceneBuilder(f"zero_{bound}_{order}_{place}_{axis}")
+    mat = sb.add_material(scenes.Material(abi.RT_MAT_DIFFUSE, (0.6, 0.5, 0.4)))
+    p = pos.reshape(-1, 3)
+    nrm = np.tile(np.array([[0, 0, 1]], f32), (p.shape[0], 1))
+    sb.add_instance(sb.add_mesh(p, nrm, np.zeros((p.shape[0], 2), f32), np.arange(p.shape[0], dtype=np.uint32)), mat, _zero_transform())
+    sb.camera = scenes.CameraPose((1.5, 1.5, 6.0), (0, 0, -1), 1.2)
+    sd = sb.build()
+    s = Scene(sd, -1, abi.RT_BVH_SAH, lib=lib)
+    tree = s.tree()
+    s.close()
+    w = tree["wverts"].reshape(-1, 3)[:, axis]
+    assert same_bits(w, pos.reshape(-1, 3)[:, axis]), "the transform changed a coordinate"
+    at_zero = np.nonzero(w == 0.0)[0]
+    assert [int(v) for v in at_zero] == [v for v, _ in slots]
+    for v, z in slots:
+        assert np.signbit(w[v]) == np.signbit(z), (v, z)
+    want = f32(slots[0][1])
+    got = tree["bounds_lo" if bound == "min" else "bounds_hi"][axis]
+    assert got == 0.0 and np.signbit(got) == np.signbit(want), "the bound is not the first zero"
+    return sd
+
+
+def signed_zero_starts(sd, case, axis):
+    """(kind, start description, updates) that reach sd from a scene whose bound on `axis` is not zero, through every kind of update: the
+    transform alone, the positions alone, both, all three, and a normals-only call right after a positions call (the device then stages the
+    normals in the buffer the positions call swapped out). The reduction of the update, not the build, makes the zero bound."""
+    sign = 1.0 if case[0] == "min" else -1.0
+    shift = [0.0, 0.0, 0.0]
+    shift[axis] = sign
+    xf = np.array(sd.transforms, f32, copy=True)
+    moved = xf.copy()
+    moved[0] = scenes.mat4_mul(scenes.mat4_translate(shift), xf[0])
+    pos = sd.positions.copy()
+    pos[:, axis] += f32(0.25 * sign)
+    nrm = np.tile(np.array([[0, 1, 0]], f32), (sd.positions.shape[0], 1))
+    own = (sd.transforms, sd.normal_mats)
+    return [
+        ("transforms", sd.updated(instances=(moved, sd.normal_mats)), [dict(instances=own)]),
+        ("positions", sd.updated(positions=pos), [dict(positions=sd.positions)]),
+        ("transforms+positions", sd.updated(instances=(moved, sd.normal_mats), positions=pos), [dict(instances=own, positions=sd.positions)]),
+        ("transforms+positions+normals", sd.updated(instances=(moved, sd.normal_mats), positions=pos, normals=nrm),
+         [dict(instances=own, positions=sd.positions, normals=sd.normals)]),
+        ("positions, then normals", sd.updated(positions=pos, normals=nrm), [dict(positions=sd.positions), dict(normals=sd.normals)]),
+    ]
+
+
+def zero_case_id(case):
+    return "-".join(case)
+
+
 SCENES = [("cornell", {}), ("table", {}), ("atrium", {"detail": 1}), ("atrium", {"detail": 2}), ("voxel", {"detail": 1}),
           ("atrium_tilted", {"detail": 1})]
 
@@ -191,6 +273,17 @@ def same_bits(a, b):
     return a.shape == b.shape and a.tobytes() == b.tobytes()
 
 
+def _tree_equal(a, b):
+    for k in ("nodes", "global_index", "wverts", "pad", "bounds_lo", "bounds_hi", "stack_need", "built_by"):
+        assert same_bits(np.asarray(a[k]), np.asarray(b[k])), k
+
+
+def _tables_equal(a, b, lds=True):
+    for k in ("packed_mat",) + (("lds_nm", "lds_mats") if lds else ()):
+        assert a[k] == b[k], k
+    assert same_bits(a["rows"], b["rows"]) and same_bits(a["words"], b["words"])
+
+
 def check_against_fresh(devlib, s, bvh, built, org, d):
     """s (updated) against a fresh host scene of s.desc: structure, closest hits, world vertices / bounds / pad, node words, tables."""
     s.check_bvh()
@@ -284,6 +377,27 @@ def test_presplit_tree_bounds_whole_triangles(devlib, scene_cache):
     org, d = rays(sd)
     check_against_fresh(devlib, s, abi.RT_BVH_SAH, built, org, d)
     s.close()
+
+
+@pytest.mark.parametrize("case", ZERO_CASES, ids=[zero_case_id(c) for c in ZERO_CASES])
+def test_host_update_keeps_the_first_signed_zero_bound(devlib, case):
+    """Bounds attained at 0 by -0 and +0 (and by -0 alone): the host update, reached by every kind of update from non-zero bounds, gives the
+    bounds bits of a fresh build, which are the first zero's in scene order."""
+    axis = ZERO_CASES.index(case) % 3
+    sd = signed_zero_scene(devlib, case, axis)
+    fresh = Scene(sd, -1, abi.RT_BVH_SAH, lib=devlib)
+    ftree = fresh.tree()
+    fresh.close()
+    for kind, start, updates in signed_zero_starts(sd, case, axis):
+        s = Scene(start, -1, abi.RT_BVH_SAH, lib=devlib, updatable=True)
+        assert s.tree()["bounds_lo" if case[0] == "min" else "bounds_hi"][axis] != 0.0, kind
+        for u in updates:
+            s.update(**u)
+        tree = s.tree()
+        for k in ("wverts", "pad", "bounds_lo", "bounds_hi"):
+            assert same_bits(tree[k], ftree[k]), (kind, k)
+        s.check_bvh()
+        s.close()
 
 
 def _status(s, **u):

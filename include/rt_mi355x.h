@@ -195,6 +195,39 @@ int rt_scene_count_visits(const rt_scene* scene, uint32_t n, const float* org, c
 int rt_intersect_batch(rt_scene* scene, uint32_t n, const float* org, const float* dir, float* t,
                        float* u, float* v, uint32_t* tri);
 
+/* ---- Ray queries: closest hit and occlusion with a per-ray tmax (rtcIntersect1 / rtcOccluded1; the reference calls only the first).
+ * A hit COUNTS iff 1e-4 < t <= tmax[i], with rt_intersect_batch's fp32 Moller-Trumbore test and tie-break (lowest global index at equal t).
+ *   RT_QUERY_CLOSEST: the closest counting hit into t, u, v, tri — a miss (t = +inf, u = v = 0, tri = 0xFFFFFFFF) when none counts. With
+ *                     tmax == NULL (+inf for every ray) that is rt_intersect_batch's result bit for bit; with a tmax it is that result when
+ *                     its t <= tmax and a miss otherwise. Any of t, u, v, tri may be NULL: that output is not written.
+ *   RT_QUERY_ANY:     occluded[i] = 1 iff a counting hit exists (= rt_intersect_batch hits at t <= tmax), else 0. The traversal of a ray ends
+ *                     at its first counting hit.
+ * Rejected rays: an origin outside the contract range or not finite (rt_intersect_batch), or a NaN tmax. rt_trace_rays returns RT_ERR_INVALID
+ * naming the first of them and writes nothing; rt_trace_rays_device marks each instead — t = NaN, tri = RT_TRI_REJECTED (u, v unwritten),
+ * occluded = 2 — and traces the others.
+ * n == 0: RT_OK, nothing launched. RT_ERR_INVALID: NULL scene, org or dir, an unknown mode, CLOSEST with every output NULL, ANY with occluded
+ * NULL; RT_ERR_NO_DEVICE: a host-only scene (the arguments are checked first).
+ * rt_trace_rays takes host arrays, stages them through device buffers and synchronises. rt_trace_rays_device takes device arrays and enqueues
+ * on `stream` (NULL = the null stream): no allocation, no synchronisation, no host copy. As with rt_scene_gbuffer_device, the scene records
+ * an event behind the launch on each stream used and rt_scene_update waits for all of them. Query launches of one scene on different streams
+ * run one after the other (they share the scene's ray cursors: the later waits for the earlier on the device, never on the host). */
+enum { RT_QUERY_CLOSEST = 0, RT_QUERY_ANY = 1 };
+#define RT_TRI_REJECTED 0xFFFFFFFEu
+typedef struct rt_ray_query {
+    uint32_t n;
+    uint32_t mode;      /* RT_QUERY_*                                              */
+    const float* org;   /* 3n, xyz per ray, as rt_intersect_batch                  */
+    const float* dir;   /* 3n                                                      */
+    const float* tmax;  /* n, or NULL = +inf for every ray                         */
+    float* t;           /* CLOSEST: n each; NULL = not written                     */
+    float* u;
+    float* v;
+    uint32_t* tri;
+    uint8_t* occluded;  /* ANY: n bytes, 0 clear / 1 occluded / 2 rejected         */
+} rt_ray_query;
+int rt_trace_rays(rt_scene* scene, const rt_ray_query* q);
+int rt_trace_rays_device(rt_scene* scene, const rt_ray_query* q, void* stream);
+
 /* ---- Renderers: == IRenderer implementations (src/render.hpp:11-18) ------------------------ */
 enum {
     RT_RENDERER_MEGAKERNEL = 0, /* MegakernelRenderer (src/render_megakernel.hpp:13-19) */

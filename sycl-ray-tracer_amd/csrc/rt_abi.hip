@@ -105,6 +105,8 @@ int rt_scene_create_ex(const rt_scene_desc* desc, int device, int bvh_kind, uint
         }
         if (rc == RT_OK) rc = upload(s->hs.mats, &s->dev.mats, s->device_bytes);
         if (rc == RT_OK) rc = upload(s->hs.tex, &s->dev.tex, s->device_bytes);
+        if (rc == RT_OK && hipMalloc((void**)&s->d_query_cursor, kQueryCursorBytes) != hipSuccess) // rt_query.hip
+            rc = fail(RT_ERR_OOM, "device allocation failed (the ray-query cursors)");
         if (rc != RT_OK) {
             rt_scene_destroy(s);
             return rc;
@@ -140,6 +142,7 @@ void rt_scene_destroy(rt_scene* s) {
         for (auto& se : s->ev_gbuffer) (void)hipEventSynchronize(se.second), (void)hipEventDestroy(se.second);
         (void)hipFree((void*)s->dev.nodes), (void)hipFree((void*)s->dev.tris), (void)hipFree((void*)s->dev.shade);
         (void)hipFree((void*)s->dev.inst), (void)hipFree((void*)s->dev.mats), (void)hipFree((void*)s->dev.tex);
+        (void)hipFree((void*)s->d_query_cursor);
     }
     free_scene_update(s);
     delete s;

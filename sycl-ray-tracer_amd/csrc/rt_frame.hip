@@ -94,20 +94,19 @@ void drain_streams(rt_renderer* r, hipStream_t extra) {
 // and the box test could cull a hit the triangle test would report; the entry points refuse such origins instead of answering
 // silently wrong. NaN origins are refused too.
 constexpr float kContractRange = 100.0f;
-bool origin_in_contract_range(const HostScene& hs, const float o[3]) {
-    if (hs.wverts.empty()) return std::isfinite(o[0]) && std::isfinite(o[1]) && std::isfinite(o[2]); // nothing to cull
+ContractRange contract_range(const HostScene& hs) {
+    ContractRange r{};
+    std::memcpy(r.lo, hs.bounds_lo, 12), std::memcpy(r.hi, hs.bounds_hi, 12);
+    if (hs.wverts.empty()) return r.finite_only = 1u, r; // nothing to cull
     float scale = 0.0f;
     for (int a = 0; a < 3; ++a)
         scale = std::max(scale, std::max(hs.bounds_hi[a] - hs.bounds_lo[a], std::max(std::fabs(hs.bounds_lo[a]), std::fabs(hs.bounds_hi[a]))));
     // a degenerate scene (all geometry in the origin: scale 0) has nothing a box test could cull wrongly: every finite origin is in range
-    if (!(scale > 0.0f)) return std::isfinite(o[0]) && std::isfinite(o[1]) && std::isfinite(o[2]);
-    const float limit = kContractRange * scale;
-    for (int a = 0; a < 3; ++a) {
-        const float outside = std::max(std::max(hs.bounds_lo[a] - o[a], o[a] - hs.bounds_hi[a]), 0.0f);
-        if (!(outside <= limit)) return false;
-    }
-    return true;
+    if (!(scale > 0.0f)) return r.finite_only = 1u, r;
+    r.limit = kContractRange * scale;
+    return r;
 }
+bool origin_in_contract_range(const HostScene& hs, const float o[3]) { return in_contract_range(contract_range(hs), o[0], o[1], o[2]); }
 
 int32_t rows_of_tile(const TileDev& t, int32_t height) {
     int32_t rows = 0;

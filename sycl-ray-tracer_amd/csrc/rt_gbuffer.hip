@@ -71,17 +71,7 @@ int gbuffer_check(const rt_scene* s, const rt_camera* cam) {
 int gbuffer_enqueue(rt_scene* s, const rt_camera* cam, float4* alb, float4* nrm, float4* pos, hipStream_t st) {
     HIPCHK(hipSetDevice(s->device));
     hipEvent_t ev = nullptr;
-    for (const auto& se : s->ev_gbuffer)
-        if (se.first == st) ev = se.second;
-    if (!ev) {
-        HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-        try {
-            s->ev_gbuffer.emplace_back(st, ev);
-        } catch (const std::bad_alloc&) {
-            (void)hipEventDestroy(ev);
-            return fail(RT_ERR_OOM, "host allocation failed");
-        }
-    }
+    if (const int rc = scene_stream_event(s, st, &ev)) return rc;
     CameraDev c;
     std::memcpy(c.center, cam->center, 12), std::memcpy(c.pixel00, cam->pixel00, 12);
     std::memcpy(c.du, cam->delta_u, 12), std::memcpy(c.dv, cam->delta_v, 12);

@@ -7,6 +7,7 @@
 //   rt_update.hip  dynamic scenes: rt_scene_create_ex's updatable state, rt_scene_update and its refit kernels
 //   rt_gbuffer.hip the primary-hit G-buffer (rt_scene_gbuffer[_device]) and its kernel
 //   rt_denoise.hip the a-trous denoiser (rt_denoiser_*, rt_denoise[_device]) and its kernels
+//   rt_query.hip   ray queries with a per-ray tmax (rt_trace_rays[_device]) and their kernel
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -130,6 +131,8 @@ struct SceneUpdate {
     bool host_stale = false; // the host copy (hs.nodes, tris, wverts, shade, sah_cost) lags a device update
 };
 
+constexpr uint32_t kQueryCursorBytes = 32u * 128u; // rt_query.hip: a cursor per shard of the rays, each on a 128-byte line of its own
+
 struct rt_scene {
     HostScene hs;
     int device = -1;
@@ -138,10 +141,34 @@ struct rt_scene {
     SceneUpdate* upd = nullptr; // RT_SCENE_UPDATABLE only
     uint64_t generation = 0;    // bumped by every rt_scene_update: renderers drop what belongs to an older one
     uint32_t frames_pending = 0; // frames of its renderers between _begin and _end (an update is refused meanwhile)
-    // one event per stream a G-buffer was enqueued on (rt_scene_gbuffer[_device]), recorded behind every launch there: rt_scene_update waits for
-    // all of them, so no launch on any stream still reads the scene when it is rewritten
+    // one event per stream a G-buffer or a ray query was enqueued on (rt_scene_gbuffer[_device], rt_trace_rays[_device]), recorded behind
+    // every launch there: rt_scene_update waits for all of them, so no launch on any stream still reads the scene when it is rewritten
     std::vector<std::pair<hipStream_t, hipEvent_t>> ev_gbuffer;
+    // ray queries (rt_query.hip): the ray cursors their launches share (kQueryCursorBytes of device memory, device scenes only), the stream of the last
+    // query launch (a launch on another stream waits for it on the device: they share the cursor), the persistent grid per mode (0 = not sized)
+    unsigned long long* d_query_cursor = nullptr;
+    hipStream_t query_stream = nullptr;
+    bool query_launched = false;
+    uint32_t query_grid[2] = {0u, 0u};
 };
+
+namespace rtlib {
+// the scene's event for stream st (rt_scene::ev_gbuffer), created on the stream's first use
+inline int scene_stream_event(rt_scene* s, hipStream_t st, hipEvent_t* out) {
+    for (const auto& se : s->ev_gbuffer)
+        if (se.first == st) return *out = se.second, RT_OK;
+    hipEvent_t ev = nullptr;
+    HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    try {
+        s->ev_gbuffer.emplace_back(st, ev);
+    } catch (const std::bad_alloc&) {
+        (void)hipEventDestroy(ev);
+        return fail(RT_ERR_OOM, "host allocation failed");
+    }
+    *out = ev;
+    return RT_OK;
+}
+} // namespace rtlib
 
 // kernel launches of one frame, in all and per kernel family (rt_stats::launches_by_kernel)
 struct LaunchCount {
@@ -295,6 +322,7 @@ namespace rtlib {
 void drop_graph(rt_renderer* r);
 void free_tile_buffers(rt_renderer* r);
 void drain_streams(rt_renderer* r, hipStream_t extra);
+ContractRange contract_range(const HostScene& hs);
 bool origin_in_contract_range(const HostScene& hs, const float o[3]);
 uint32_t hw_queues_from_env();
 hipError_t lane_stream_of(int device, uint32_t k, hipStream_t* out, bool* owned);

@@ -40,6 +40,31 @@ constexpr int kStackSize = 64;      // traversal stack entries per ray; builders
 constexpr uint32_t kNoTri = 0xFFFFFFFFu;
 constexpr float kTNear = 0.0001f;   // RayData::to_embree tnear (src/camera.hpp:50)
 
+// ---- range of the closest-hit contract (include/rt_mi355x.h: rt_intersect_batch) ------------------
+// What the origin test needs of a scene (rt_frame.hip: contract_range): the bounds and the limit, kContractRange scene scales; finite_only
+// when nothing could be culled wrongly (no geometry, or all of it in the origin). One predicate for the host entry points and the query
+// kernel (rt_query.hip), written with std::max's operand order so that both evaluate the same fp32 operations with the same NaN outcome.
+#ifdef __HIPCC__
+#define RT_HD __host__ __device__ inline
+#else
+#define RT_HD inline
+#endif
+struct ContractRange {
+    float lo[3], hi[3];
+    float limit;
+    uint32_t finite_only;
+};
+RT_HD float contract_max(float a, float b) { return a < b ? b : a; } // std::max(a, b)
+RT_HD bool in_contract_range(const ContractRange& r, float ox, float oy, float oz) {
+    if (r.finite_only) return __builtin_isfinite(ox) && __builtin_isfinite(oy) && __builtin_isfinite(oz);
+    const float o[3] = {ox, oy, oz};
+    for (int a = 0; a < 3; ++a) {
+        const float outside = contract_max(contract_max(r.lo[a] - o[a], o[a] - r.hi[a]), 0.0f);
+        if (!(outside <= r.limit)) return false;
+    }
+    return true;
+}
+
 // ---- triangles, leaf order: 48 bytes = 3 x float4 -------------------------------------------------
 //   a = (v0.x, v0.y, v0.z, e1.x)  b = (e1.y, e1.z, e2.x, e2.y)  c = (e2.z, bits(global index), 0, 0)
 struct alignas(16) TriRec {

@@ -495,7 +495,7 @@ extern "C" int rt_scene_update(rt_scene* s, const rt_scene_update_desc* u, rt_up
     if (u->n_vertices && !u->positions && !u->normals) return fail(RT_ERR_INVALID, "n_vertices given with neither positions nor normals");
     for (uint32_t i = 0; i < u->n_instances; ++i)
         if (u->instances[i].material != up.instances[i].material) return fail(RT_ERR_INVALID, "an update cannot change an instance's material");
-    if (!s->ev_gbuffer.empty()) { // G-buffer launches still reading the scene (rt_scene_gbuffer_device, any stream) finish before anything is rewritten
+    if (!s->ev_gbuffer.empty()) { // G-buffer and ray-query launches still reading the scene (rt_scene_gbuffer_device, rt_trace_rays_device, any stream) finish before anything is rewritten
         HIPCHK(hipSetDevice(s->device));
         for (const auto& se : s->ev_gbuffer) HIPCHK(hipEventSynchronize(se.second));
     }

@@ -162,6 +162,26 @@ class rt_denoise_params(C.Structure):
     ]
 
 
+RT_QUERY_CLOSEST, RT_QUERY_ANY = 0, 1
+RT_TRI_REJECTED = 0xFFFFFFFE
+
+
+class rt_ray_query(C.Structure):
+    _fields_ = [
+        ("n", C.c_uint32),
+        ("mode", C.c_uint32),
+        ("org", C.c_void_p),
+        ("dir", C.c_void_p),
+        ("tmax", C.c_void_p),
+        ("t", C.c_void_p),
+        ("u", C.c_void_p),
+        ("v", C.c_void_p),
+        ("tri", C.c_void_p),
+        ("occluded", C.c_void_p),
+    ]
+
+
+assert C.sizeof(rt_ray_query) == 72
 assert C.sizeof(rt_denoise_params) == 20
 assert C.sizeof(rt_material) == 44
 assert C.sizeof(rt_instance) == 104
@@ -181,6 +201,8 @@ PROTOTYPES = {
                                          _P(C.c_float), _P(C.c_uint32)]),
     "rt_intersect_batch": (C.c_int, [C.c_void_p, C.c_uint32, _P(C.c_float), _P(C.c_float), _P(C.c_float),
                                      _P(C.c_float), _P(C.c_float), _P(C.c_uint32)]),
+    "rt_trace_rays": (C.c_int, [C.c_void_p, _P(rt_ray_query)]),
+    "rt_trace_rays_device": (C.c_int, [C.c_void_p, _P(rt_ray_query), C.c_void_p]),
     "rt_renderer_create": (C.c_int, [C.c_int, C.c_void_p, C.c_int32, C.c_int32, C.c_uint32, C.c_uint32,
                                      C.c_uint32, _P(C.c_void_p)]),
     "rt_renderer_destroy": (None, [C.c_void_p]),

@@ -98,6 +98,40 @@ class Scene:
                                                abi.fptr(v), abi.u32ptr(tri)), self._lib)
         return t, u, v, tri
 
+    def trace(self, org: np.ndarray, dirs: np.ndarray, tmax=None, any_hit: bool = False):
+        """rt_trace_rays on host arrays: org, dirs (n, 3); tmax (n,) or None (+inf). Closest hit: (t, u, v, tri), a miss where no hit has
+        1e-4 < t <= tmax. any_hit: the occlusion bytes (n,) uint8, 1 where such a hit exists (include/rt_mi355x.h: rt_ray_query)."""
+        org = np.ascontiguousarray(org, np.float32).reshape(-1, 3)
+        dirs = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
+        n = org.shape[0]
+        if dirs.shape[0] != n:
+            raise ValueError("org and dirs must hold the same number of rays")
+        q = abi.rt_ray_query(n=n, mode=abi.RT_QUERY_ANY if any_hit else abi.RT_QUERY_CLOSEST, org=org.ctypes.data, dir=dirs.ctypes.data)
+        if tmax is not None:
+            tmax = np.ascontiguousarray(tmax, np.float32).reshape(-1)
+            if tmax.shape[0] != n:
+                raise ValueError("tmax must hold one value per ray")
+            q.tmax = tmax.ctypes.data
+        if any_hit:
+            occ = np.zeros(n, np.uint8)
+            q.occluded = occ.ctypes.data
+            abi.check(self._lib.rt_trace_rays(self.h, C.byref(q)), self._lib)
+            return occ
+        t, u, v = (np.zeros(n, np.float32) for _ in range(3))
+        tri = np.zeros(n, np.uint32)
+        q.t, q.u, q.v, q.tri = t.ctypes.data, u.ctypes.data, v.ctypes.data, tri.ctypes.data
+        abi.check(self._lib.rt_trace_rays(self.h, C.byref(q)), self._lib)
+        return t, u, v, tri
+
+    def trace_device(self, n: int, d_org: int, d_dir: int, d_tmax: int = 0, d_t: int = 0, d_u: int = 0, d_v: int = 0, d_tri: int = 0,
+                     d_occluded: int = 0, any_hit: bool = False, stream: int = 0) -> None:
+        """rt_trace_rays_device on DEVICE pointers (e.g. torch .data_ptr()), enqueued on `stream`; 0 = NULL (no tmax / output not written).
+        Rejected rays are marked: t = NaN, tri = abi.RT_TRI_REJECTED, occluded = 2."""
+        q = abi.rt_ray_query(n=int(n), mode=abi.RT_QUERY_ANY if any_hit else abi.RT_QUERY_CLOSEST, org=d_org or None, dir=d_dir or None,
+                             tmax=d_tmax or None, t=d_t or None, u=d_u or None, v=d_v or None, tri=d_tri or None,
+                             occluded=d_occluded or None)
+        abi.check(self._lib.rt_trace_rays_device(self.h, C.byref(q), C.c_void_p(stream or None)), self._lib)
+
     def gbuffer(self, camera: Camera) -> dict:
         """rt_scene_gbuffer: the guide images of the camera's primary hits, {"albedo", "normal", "position"}, each (H, W, 4) float32
         (include/rt_mi355x.h states what a pixel holds)."""

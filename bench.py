@@ -19,18 +19,26 @@ Four renderers of the path are measured with the same K steps:
   wavefront_per_bounce_fused  the same with ONE kernel per bounce (intersect + shade + compact: the reference's shoot_rays, :222-312)
 The headline `value` is the fastest (`config.renderer`); `renderers` holds all four with their rooflines.
 
+A plain run does only what the headline needs: set-up, the W warm-up and K timed frames of each renderer, --dump-outputs, the JSON line.
+`--full` adds, after the timed regions, everything else the benchmark measures (marked [full] below): the per-bounce renderers' per-kernel
+durations, the two-frames-in-flight leg, workload_sensitivity, the rocprofv3 --pmc passes behind `traffic` / `binding`, and cpu_baseline.
+The --no-* options leave single legs out of a --full run.
+
 Prints ONE JSON line on rank 0 (contract in the task statement) with these extra objects:
   roofline     — of the headline renderer, as SURVEY §8(d) states it: algorithmic bytes per unit of work x units per second of the whole timed
                  region against the 8 TB/s HBM peak (tiny by construction for a traversal kernel), the dominant kernel's own per-launch
-                 figure under `per_launch`; `traffic` = FETCH_SIZE + WRITE_SIZE of that kernel; `binding` = the bounds that actually bind,
+                 figure under `per_launch` (of the per-bounce renderers [full]: one more frame with per-launch hipEvents after the timed region);
+                 [full] `traffic` = FETCH_SIZE + WRITE_SIZE of that kernel; `binding` = the bounds that actually bind,
                  MEASURED: VALU issue busy = 4 x (SQ_ACTIVE_INST_VALU - SQ_ACTIVE_INST_VALU2) / (SIMDs x kernel cycles) and the vector L1's
                  tag look-ups per cycle and CU — counters of the product build in this very run, no model (semantics pinned on known
                  instruction streams: profiles/r03_valu_calibration2.json). traffic and binding are measured at N = 1: after the timed
                  region one more frame per renderer is rendered in a child process under `rocprofv3 --pmc`, one pass per counter group.
-  cpu_baseline — the CPU oracle (a port, not the reference: the reference cannot be built here) timed on the
+  cpu_baseline — [full] the CPU oracle (a port of the reference's algorithm, not the reference's own build) timed on the
                  host cores on a bounded sample of the same workload (rank 0, N = 1 only)
-  workload_sensitivity — information only (N = 1): the megakernel with the same K frames on the atrium turned out of the coordinate axes and on the
+  workload_sensitivity — [full] information only (N = 1): the megakernel with the same K frames on the atrium turned out of the coordinate axes and on the
                  voxel terrain, each with node visits / triangle tests per ray: the bench scene is this traversal's best case.
+  two_frames_in_flight — [full] information only: the headline renderer's K frames again with the next frame enqueued before the current one
+                 is collected.
 For N > 1 the line also carries `per_rank_ms` (every rank's own time for the K frames), `gather_ms` (rank 0's mean time in the
 gather + de-interleave per frame) and `rccl_ranks` (an all-reduce of ones over the process group: what RCCL saw).
 
@@ -106,15 +114,18 @@ def parse_args(argv=None):
     ap.add_argument("--depth", type=int, default=10)
     ap.add_argument("--detail", type=int, default=4, help="atrium tessellation (4 = ~281k triangles)")
     ap.add_argument("--bvh", choices=["sah", "lbvh"], default="sah")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed regions also measure what the headline does not need: per-kernel durations of the per-bounce "
+                         "renderers, the two-frames-in-flight leg, workload_sensitivity, the rocprofv3 --pmc passes, the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--frames-in-flight", type=int, default=1,
                     help="frames enqueued at once, each in its own renderer and strip buffer (1 = the reference's one frame at a "
                          "time; 2 hides the end-of-frame drain of the per-pixel sample chains behind the next frame)")
-    ap.add_argument("--no-pipelined", action="store_true", help="skip the informational two-frames-in-flight measurement")
-    ap.add_argument("--pipelined-renderer", default="", help="the renderer of the two-frames-in-flight leg (default: the headline's)")
-    ap.add_argument("--cpu-spp", type=int, default=8, help="samples per pixel of the bounded CPU-oracle sample")
-    ap.add_argument("--no-live-pmc", action="store_true", help="do not run the rocprofv3 --pmc child passes after the timed region")
-    ap.add_argument("--no-sensitivity", action="store_true", help="skip the information-only workload_sensitivity leg (the megakernel on the rotated atrium and the voxel terrain)")
+    ap.add_argument("--no-pipelined", action="store_true", help="--full without the informational two-frames-in-flight measurement")
+    ap.add_argument("--pipelined-renderer", default="", help="the renderer of the two-frames-in-flight leg of --full (default: the headline's)")
+    ap.add_argument("--cpu-spp", type=int, default=8, help="samples per pixel of the bounded CPU-oracle sample (--full)")
+    ap.add_argument("--no-live-pmc", action="store_true", help="--full without the rocprofv3 --pmc child passes after the timed region")
+    ap.add_argument("--no-sensitivity", action="store_true", help="--full without the information-only workload_sensitivity leg (the megakernel on the rotated atrium and the voxel terrain)")
     ap.add_argument("--stats-child", default=None, help=argparse.SUPPRESS)  # comma-separated scenes: one 4-spp frame each under RT_KERNEL_STATS=1 (node visits / triangle tests per ray)
     ap.add_argument("--backend", choices=["nccl", "gloo"], default="nccl", help="gloo: CPU rehearsal of the multi-rank path (needs --rehearsal-tiles)")
     ap.add_argument("--rehearsal-tiles", default=None, help="directory with tile_<rank>.npy (rows x W x 4 float32): used INSTEAD of rendering")
@@ -122,13 +133,15 @@ def parse_args(argv=None):
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
                     help="rank 0 writes what every timed renderer returned for its last timed frame to DIR/<renderer>_<output>.npy "
                          "(float32 / float64, at most 64 MB in all: a fixed, seeded sample of pixels where the full frames do not fit)")
-    ap.add_argument("--dump-pmc", default=None, help="write the raw counter sums of the live --pmc passes here (JSON; profiles/r03_pmc_bench.json is one)")
+    ap.add_argument("--dump-pmc", default=None, help="write the raw counter sums of the live --pmc passes of --full here (JSON; profiles/r03_pmc_bench.json is one)")
     ap.add_argument("--pmc-child", default=None, help=argparse.SUPPRESS)  # comma-separated renderers: one untimed frame each, the process rocprofv3 wraps
     args = ap.parse_args(argv)
     if args.steps < 1:
         ap.error("--steps must be at least 1")
     if args.warmup < 0:
         ap.error("--warmup must not be negative")
+    if not args.full and (args.dump_pmc or args.pipelined_renderer):
+        ap.error("--dump-pmc and --pipelined-renderer belong to the legs of --full")
     return args
 
 
@@ -340,7 +353,7 @@ def main() -> int:
             if world == 1:  # the unorm8 image stays on the rank that rendered it: with one rank it is the whole frame's
                 outputs[name]["rgba_u8"] = last.local_u8[:rows].cpu().numpy()
         kernel_frames = args.steps
-        if rs and name.startswith("wavefront_per_bounce"):  # the per-kernel durations: one profiled frame outside the timed region
+        if args.full and rs and name.startswith("wavefront_per_bounce"):  # the per-kernel durations: one profiled frame outside the timed region
             rs[0].set_profiling(True)
             fr = rs[0].render_frame_device(cam, d_f32=fgs[0].local.data_ptr(), d_u8=fgs[0].local_u8.data_ptr())
             tot["kernel_ms"], tot["hot_ms"], tot["hot_launches"], kernel_frames = dict(fr.kernel_ms), fr.hot_kernel_ms, fr.hot_kernel_launches, 1
@@ -382,7 +395,7 @@ def main() -> int:
             dist.broadcast_object_list(box, src=0)
             lead = box[0]
         pipelined = None
-        if F0 == 1 and not args.no_pipelined:
+        if args.full and F0 == 1 and not args.no_pipelined:
             try:  # information only: never the reason a bench line is missing (with several ranks a failure here would have to be collective: let it raise)
                 pipelined = measure(args.pipelined_renderer or lead, 2)
             except Exception as e:
@@ -418,7 +431,8 @@ def main() -> int:
                                                    "current one is collected; not the headline: ms_per_step is then no longer one frame's latency"}
             if pipelined.get("error"):
                 out["two_frames_in_flight"]["error"] = pipelined["error"]
-        if world == 1 and not rehearsal and not args.no_sensitivity and "megakernel" in out["renderers"]:
+        full = args.full and world == 1 and not rehearsal  # the legs below run in one process on one GPU
+        if full and not args.no_sensitivity and "megakernel" in out["renderers"]:
             try:
                 out["workload_sensitivity"] = workload_sensitivity(args, out["renderers"]["megakernel"]["value"], abi, Scene, Camera, MegakernelRenderer)
                 mine = out["workload_sensitivity"]["scenes"].get("atrium", {})
@@ -428,9 +442,12 @@ def main() -> int:
                             mk["roofline"]["traversal"] = traversal_object({k: mine[k] for k in ATRIUM_VISITS}, mk["value"] * 1e6, "measured in this run (RT_KERNEL_STATS=1 child, 4 spp, megakernel)")
             except Exception as e:  # information only: never the reason a bench line is missing
                 out["workload_sensitivity"] = {"error": str(e)[:300]}
-        if world == 1 and not rehearsal:
+        if full:
             attach_pmc(out, args)
-        if world == 1 and not rehearsal and not args.no_cpu_baseline:
+        elif world == 1 and not rehearsal:
+            for d in results:
+                d["roofline"]["pmc_source"] = "not collected: bench.py --full runs the rocprofv3 --pmc passes behind traffic and binding"
+        if full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(sd, W, H, args.depth, args.cpu_spp, best["renderer"])
         if args.dump_frame:
             np.save(args.dump_frame, fgs[last_buffer[0]].frame.cpu().numpy())
@@ -533,20 +550,26 @@ def roofline_of(name, args, tot, rows, W, rays_all, elapsed, kernel_frames):
             "per_launch": {"achieved": round(per_launch, 3), "frac": round(per_launch / HBM_PEAK_GBS, 6), "launches": hot_launches,
                            "mean_launch_ms": round(mean_launch_s * 1e3, 5), "bytes_per_launch": round(bytes_per_launch, 1),
                            "note": "the dominant kernel alone: its algorithmic bytes per launch / its mean launch duration (hipEvents on the launch's own stream)"}}
+    # the per-bounce renderers' timed frames run without events: their launch durations come from the one profiled frame of --full
+    durations = args.full or not name.startswith("wavefront_per_bounce")
+    if not durations:
+        roof["per_launch"] = {"achieved": None, "frac": None, "launches": 0, "mean_launch_ms": None, "bytes_per_launch": None,
+                              "note": "not measured: bench.py --full renders one more frame with per-launch hipEvents after the timed region"}
     if name == "wavefront_per_bounce":
         # both kernels of the pipeline, each against its own algorithmic bytes; the launches of the stream lanes overlap, so the
         # per-kernel sums are device time of a lane, not wall time
         ext_s, shd_s = tot["kernel_ms"].get("wf_extend", 0.0) * 1e-3, tot["kernel_ms"].get("wf_shade", 0.0) * 1e-3
         n_pairs = max(tot["kernels"].get("wf_shade", 0) // max(args.steps, 1) * kernel_frames, 1)
         roof["pipeline"] = {
-            "k_wf_extend": {"bytes_per_ray": EXTEND_BYTES_PER_RAY, "sum_launch_ms_per_frame": round(ext_s * 1e3 / kernel_frames, 3),
+            "k_wf_extend": {"bytes_per_ray": EXTEND_BYTES_PER_RAY, "sum_launch_ms_per_frame": round(ext_s * 1e3 / kernel_frames, 3) if durations else None,
                             "achieved_gbs": round(EXTEND_BYTES_PER_RAY * rays / ext_s / 1e9, 3) if ext_s else None},
-            "k_wf_shade": {"bytes_per_ray": SHADE_BYTES_PER_RAY, "sum_launch_ms_per_frame": round(shd_s * 1e3 / kernel_frames, 3),
-                           "mean_launch_ms": round(shd_s * 1e3 / n_pairs, 5),
+            "k_wf_shade": {"bytes_per_ray": SHADE_BYTES_PER_RAY, "sum_launch_ms_per_frame": round(shd_s * 1e3 / kernel_frames, 3) if durations else None,
+                           "mean_launch_ms": round(shd_s * 1e3 / n_pairs, 5) if durations else None,
                            "achieved_gbs": round(SHADE_BYTES_PER_RAY * rays / shd_s / 1e9, 3) if shd_s else None,
                            "frac": round(SHADE_BYTES_PER_RAY * rays / shd_s / 1e9 / HBM_PEAK_GBS, 6) if shd_s else None},
             "stream_lanes": tot["lanes"], "launch_pairs_per_frame": n_pairs // kernel_frames,
-            "kernel_durations_from": "one frame with per-launch hipEvents rendered after the timed region (events on ~3,800 launches slow the timed frames by a third)",
+            "kernel_durations_from": "one frame with per-launch hipEvents rendered after the timed region (events on ~3,800 launches slow the timed frames by a third)"
+                                     if durations else "not measured: bench.py --full renders one frame with per-launch hipEvents after the timed region",
             "note": "the reference's shape: per sample and bounce one EXTEND + one SHADE launch, survivors compacted between bounces (wave ballot + mbcnt "
                     "prefix, one atomic per 256-thread block); interleaved sub-tiles on HIP streams overlap one lane's launch tails with the others' traversal"}
     elif name == "wavefront_per_bounce_fused":

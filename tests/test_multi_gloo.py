@@ -149,6 +149,30 @@ def test_bench_dump_outputs_stay_within_their_budget(tmp_path):
     assert bench.parse_args(["--steps", "7"]).steps == 7
 
 
+def test_bench_full_legs_are_opt_in():
+    """A plain run measures what the headline needs; `--full` adds the legs after the timed regions. Options that only feed those legs are
+    refused without it, and a plain run's per-bounce rooflines say that their launch durations were not measured instead of reporting zeros."""
+    sys.path.insert(0, str(REPO))
+    import bench
+    assert not bench.parse_args([]).full and bench.parse_args(["--full"]).full
+    for only_full in (["--dump-pmc", "pmc.json"], ["--pipelined-renderer", "megakernel"]):
+        with pytest.raises(SystemExit):
+            bench.parse_args(only_full)
+        assert bench.parse_args(["--full"] + only_full).full
+    steps, rays = 4, 4_000_000
+    for name in ("wavefront_per_bounce", "wavefront_per_bounce_fused"):
+        plain = {"rays": rays * steps, "hot_ms": 0.0, "hot_launches": 0, "kernel_ms": {}, "kernels": {"wf_shade": 640 * steps}, "lanes": 3}
+        roof = bench.roofline_of(name, bench.parse_args(["--steps", str(steps)]), plain, 1080, 1920, rays * steps, 0.5, steps)
+        assert roof["achieved"] > 0 and roof["per_launch"]["achieved"] is None and "--full" in roof["per_launch"]["note"]
+        full = dict(plain, hot_ms=50.0, hot_launches=640, kernel_ms={"wf_extend": 50.0, "wf_shade": 30.0}, kernels={"wf_shade": 640 * steps}, profiled_rays=rays)
+        roof_full = bench.roofline_of(name, bench.parse_args(["--steps", str(steps), "--full"]), full, 1080, 1920, rays * steps, 0.5, 1)
+        assert roof_full["achieved"] == roof["achieved"] and roof_full["per_launch"]["achieved"] > 0
+        if name == "wavefront_per_bounce":
+            assert roof["pipeline"]["k_wf_shade"]["mean_launch_ms"] is None and roof["pipeline"]["k_wf_extend"]["sum_launch_ms_per_frame"] is None
+            assert roof["pipeline"]["launch_pairs_per_frame"] == roof_full["pipeline"]["launch_pairs_per_frame"] == 640
+            assert roof_full["pipeline"]["k_wf_shade"]["mean_launch_ms"] > 0
+
+
 def test_bench_launcher_reports_a_failing_rank(tmp_path):
     """A rank that fails (here: its tile file is missing) must make `bench.py --gpus N` exit non-zero, not hang and not print a line."""
     np.save(tmp_path / "tile_0.npy", np.zeros((24, 16, 4), np.float32))  # tile_1.npy is missing

@@ -4,7 +4,15 @@
 
 namespace rtlib {
 thread_local std::string g_err;
+
+// a frame or continuation rendered into the renderer's own tile buffers: the host outputs asked for
+int copy_out(const rt_renderer* r, int rc, float* rgba_f32, uint8_t* rgba_u8) {
+    if (rc != RT_OK) return rc;
+    if (rgba_f32 && r->n_local) HIPCHK(hipMemcpy(rgba_f32, r->d_f32, (size_t)r->n_local * 16, hipMemcpyDeviceToHost));
+    if (rgba_u8 && r->n_local) HIPCHK(hipMemcpy(rgba_u8, r->d_u8, (size_t)r->n_local * 4, hipMemcpyDeviceToHost));
+    return RT_OK;
 }
+} // namespace rtlib
 
 extern "C" {
 
@@ -255,7 +263,7 @@ void rt_renderer_destroy(rt_renderer* r) {
     if (!r) return;
     if (r->scene && r->frame_pending && r->scene->frames_pending) r->scene->frames_pending--;
     if (r->scene && hipSetDevice(r->scene->device) == hipSuccess) {
-        drain_streams(r, r->pending_stream);
+        drain_streams(r, r->pending.stream);
         free_tile_buffers(r);
         if (r->d_cam) (void)hipFree(r->d_cam);
         if (r->h_cam) (void)hipHostFree(r->h_cam);
@@ -276,7 +284,7 @@ int rt_renderer_set_tile(rt_renderer* r, uint32_t rank, uint32_t world, uint32_t
     if (world == 0 || rank >= world || strip_rows == 0) return fail(RT_ERR_INVALID, "bad tile split");
     if (r->frame_pending) return fail(RT_ERR_INVALID, "a frame is in flight (rt_render_frame_end first)");
     HIPCHK(hipSetDevice(r->scene->device));
-    drain_streams(r, r->pending_stream); // the queues are about to be freed: nothing may be running on any of the renderer's streams
+    drain_streams(r, r->pending.stream); // the queues are about to be freed: nothing may be running on any of the renderer's streams
     const TileDev old = r->tile;
     r->tile.rank = rank, r->tile.world = world, r->tile.strip_rows = strip_rows;
     const int rc = no_throw([&] { return alloc_tile_buffers(r); });
@@ -302,7 +310,7 @@ int rt_renderer_set_russian_roulette(rt_renderer* r, uint32_t start_bounce) {
     if (!r) return fail(RT_ERR_INVALID, "null renderer");
     if (r->rr_start != start_bounce) drop_graph(r); // the bounce flags are baked into the captured launches
     r->rr_start = start_bounce;
-    r->carry_samples = 0, r->carry_mode = 0; // (progressive rendering: the carried chains were rendered with the old paths' ends)
+    r->carry_samples = 0; // (progressive rendering: the carried chains were rendered with the old paths' ends)
     return RT_OK;
 }
 
@@ -319,13 +327,13 @@ int rt_renderer_set_schedule(rt_renderer* r, const rt_schedule* s) {
         return fail(RT_ERR_INVALID, "schedule field out of range");
     if (r->frame_pending) return fail(RT_ERR_INVALID, "a frame is in flight (rt_render_frame_end first)");
     if (s->pixel_slices < -1 || s->pixel_slices > (int32_t)kMaxSlices) return fail(RT_ERR_INVALID, "pixel_slices: -1 (automatic), 0 or 1 (off), 2 .. 8");
-    if (r->kind != RT_RENDERER_WAVEFRONT && (s->pixel_slices > 1 || s->pixel_slices < 0) == (r->sched.pixel_slices > 1 || r->sched.pixel_slices < 0)) { // the megakernel is one launch: only its pixel slices are a choice (their state buffer exists or not)
+    if (r->kind != RT_RENDERER_WAVEFRONT && wants_slices(s->pixel_slices) == wants_slices(r->sched.pixel_slices)) { // the megakernel is one launch: only its pixel slices are a choice (their state buffer exists or not)
         r->sched = *s;
         r->carry_samples = 0; // (progressive rendering: a new schedule discards the carried state)
         return RT_OK;
     }
     HIPCHK(hipSetDevice(r->scene->device));
-    drain_streams(r, r->pending_stream); // the queues are re-allocated (stream lanes, second queue, hit records, dynamic queue)
+    drain_streams(r, r->pending.stream); // the queues are re-allocated (stream lanes, second queue, hit records, dynamic queue)
     const rt_schedule old = r->sched;
     r->sched = *s;
     const int rc = no_throw([&] { return alloc_tile_buffers(r); });
@@ -335,11 +343,7 @@ int rt_renderer_set_schedule(rt_renderer* r, const rt_schedule* s) {
 
 int rt_render_frame(rt_renderer* r, const rt_camera* cam, float* rgba_f32, uint8_t* rgba_u8, rt_stats* stats) {
     if (!r) return fail(RT_ERR_INVALID, "null renderer");
-    int rc = no_throw([&] { return render_impl(r, cam, rgba_f32 ? r->d_f32 : nullptr, rgba_u8 ? r->d_u8 : nullptr, r->stream, stats); });
-    if (rc != RT_OK) return rc;
-    if (rgba_f32 && r->n_local) HIPCHK(hipMemcpy(rgba_f32, r->d_f32, (size_t)r->n_local * 16, hipMemcpyDeviceToHost));
-    if (rgba_u8 && r->n_local) HIPCHK(hipMemcpy(rgba_u8, r->d_u8, (size_t)r->n_local * 4, hipMemcpyDeviceToHost));
-    return RT_OK;
+    return copy_out(r, no_throw([&] { return render_impl(r, cam, rgba_f32 ? r->d_f32 : nullptr, rgba_u8 ? r->d_u8 : nullptr, r->stream, stats); }), rgba_f32, rgba_u8);
 }
 
 int rt_render_frame_device(rt_renderer* r, const rt_camera* cam, void* d_rgba_f32, void* d_rgba_u8, void* stream,
@@ -361,11 +365,7 @@ int rt_renderer_set_progressive(rt_renderer* r, int enable) {
 
 int rt_render_frame_continue(rt_renderer* r, uint32_t samples, float* rgba_f32, uint8_t* rgba_u8, rt_stats* stats) {
     if (!r) return fail(RT_ERR_INVALID, "null renderer");
-    int rc = no_throw([&] { return continue_impl(r, samples, rgba_f32 ? r->d_f32 : nullptr, rgba_u8 ? r->d_u8 : nullptr, r->stream, stats); });
-    if (rc != RT_OK) return rc;
-    if (rgba_f32 && r->n_local) HIPCHK(hipMemcpy(rgba_f32, r->d_f32, (size_t)r->n_local * 16, hipMemcpyDeviceToHost));
-    if (rgba_u8 && r->n_local) HIPCHK(hipMemcpy(rgba_u8, r->d_u8, (size_t)r->n_local * 4, hipMemcpyDeviceToHost));
-    return RT_OK;
+    return copy_out(r, no_throw([&] { return continue_impl(r, samples, rgba_f32 ? r->d_f32 : nullptr, rgba_u8 ? r->d_u8 : nullptr, r->stream, stats); }), rgba_f32, rgba_u8);
 }
 
 int rt_render_frame_continue_device(rt_renderer* r, uint32_t samples, void* d_rgba_f32, void* d_rgba_u8, void* stream, rt_stats* stats) {
@@ -401,11 +401,7 @@ int rt_renderer_block_errors(const rt_renderer* r, float* out) {
 int rt_render_frame_continue_blocks(rt_renderer* r, uint32_t samples, const uint32_t* blocks, uint32_t n_blocks, float* rgba_f32, uint8_t* rgba_u8,
                                     rt_stats* stats) {
     if (!r) return fail(RT_ERR_INVALID, "null renderer");
-    int rc = no_throw([&] { return continue_blocks_impl(r, samples, blocks, n_blocks, rgba_f32 ? r->d_f32 : nullptr, rgba_u8 ? r->d_u8 : nullptr, r->stream, stats); });
-    if (rc != RT_OK) return rc;
-    if (rgba_f32 && r->n_local) HIPCHK(hipMemcpy(rgba_f32, r->d_f32, (size_t)r->n_local * 16, hipMemcpyDeviceToHost));
-    if (rgba_u8 && r->n_local) HIPCHK(hipMemcpy(rgba_u8, r->d_u8, (size_t)r->n_local * 4, hipMemcpyDeviceToHost));
-    return RT_OK;
+    return copy_out(r, no_throw([&] { return continue_blocks_impl(r, samples, blocks, n_blocks, rgba_f32 ? r->d_f32 : nullptr, rgba_u8 ? r->d_u8 : nullptr, r->stream, stats); }), rgba_f32, rgba_u8);
 }
 
 int rt_render_frame_continue_blocks_device(rt_renderer* r, uint32_t samples, const uint32_t* blocks, uint32_t n_blocks, void* d_rgba_f32, void* d_rgba_u8,
@@ -432,14 +428,10 @@ int rt_renderer_adapt(rt_renderer* r, float threshold, uint32_t min_samples, uin
 int rt_render_frame_continue_adaptive(rt_renderer* r, uint32_t samples, float threshold, uint32_t min_samples, float* rgba_f32, uint8_t* rgba_u8,
                                       rt_stats* stats, uint32_t* n_blocks_out) {
     if (!r) return fail(RT_ERR_INVALID, "null renderer");
-    int rc = no_throw([&] {
+    return copy_out(r, no_throw([&] {
         return continue_adaptive_impl(r, samples, threshold, min_samples, rgba_f32 ? r->d_f32 : nullptr, rgba_u8 ? r->d_u8 : nullptr, r->stream, stats,
                                       n_blocks_out);
-    });
-    if (rc != RT_OK) return rc;
-    if (rgba_f32 && r->n_local) HIPCHK(hipMemcpy(rgba_f32, r->d_f32, (size_t)r->n_local * 16, hipMemcpyDeviceToHost));
-    if (rgba_u8 && r->n_local) HIPCHK(hipMemcpy(rgba_u8, r->d_u8, (size_t)r->n_local * 4, hipMemcpyDeviceToHost));
-    return RT_OK;
+    }), rgba_f32, rgba_u8);
 }
 
 int rt_render_frame_continue_adaptive_device(rt_renderer* r, uint32_t samples, float threshold, uint32_t min_samples, void* d_rgba_f32, void* d_rgba_u8,

@@ -178,6 +178,52 @@ struct LaunchCount {
     void also(int kernel, uint32_t n = 1) { by[kernel] += n; } // a second family of a launch already counted
 };
 
+// What one call renders (frame_begin, continue_impl, continue_blocks_impl): its samples, and what it does with the carried progressive state.
+// CarryMode is k_megakernel's CARRY template argument.
+enum CarryMode : int {
+    kCarryNone = 0,      // a frame, progressive rendering off
+    kCarryStore = 1,     // a frame that stores its pixels' state
+    kCarryLoadStore = 2, // a continuation: every pixel goes on from its state
+    kCarryBlocks = 3,    // a block continuation (adaptive sampling): the listed 8x8 blocks' pixels go on from theirs
+};
+struct FrameRequest {
+    uint32_t spp = 0;
+    CarryMode carry = kCarryNone;
+    uint32_t carry_total = 0;         // the samples the pixels hold at its end
+    const uint32_t* blocks = nullptr; // kCarryBlocks: the listed blocks (pinned: rt_renderer::h_blk)
+    uint32_t n_blocks = 0;
+};
+
+// rt_schedule::pixel_slices asks for pixel slices: -1 (automatic) or 2 .. 8 (rt_frame.hip: slices_possible)
+inline bool wants_slices(int32_t pixel_slices) { return pixel_slices != 0 && pixel_slices != 1; }
+
+constexpr uint32_t kMaxLanes = 8; // stream lanes at most (rt_schedule::stream_lanes)
+
+// Every decision about what a frame launches, made once per frame from the renderer and the request (rt_frame.hip: plan_frame). The launches, the
+// statistics and frame_end read it.
+struct FramePlan {
+    FrameRequest req;
+    int hot = 0;                        // the dominant kernel family (rt_stats::hot_kernel_ms)
+    SliceDev sl{};                      // the pixel slices of the one launch (n_slices 1: unsliced); tag0 is the renderer's, set at the launch
+    uint32_t chunk = 0;                 // samples one launch renders per pixel
+    uint32_t grid = 0, n_tiles = 0;     // megakernel: persistent workgroups; 8x8 tiles of the launch (a block continuation: the listed blocks)
+    uint32_t lanes = 1, D0 = 0;         // wavefront: stream lanes; bounces rendered launch by launch before k_wf_finish takes over
+    bool requeue = false;               // k_wf_finish's dynamic queue between the samples of a launch
+    bool spread = false;                // the queue hands every wave pixels spread over the tile
+    bool lpt = false;                   // cost-ordered: sample 0 in a launch of its own, then the other samples, costliest 8x8 blocks first
+    bool shoot_frame = false;           // SHOOT launches: the queues hold holes, every launch counts its rays on the device
+    uint32_t lane_pixels[kMaxLanes] = {}; // the queue of every lane (a block continuation: the listed blocks' pixels in that lane)
+};
+
+// the frame between rt_render_frame_begin and rt_render_frame_end
+struct PendingFrame {
+    hipStream_t stream = nullptr;
+    rt_stats stats{};
+    size_t hot_events = 0;
+    std::chrono::high_resolution_clock::time_point t0{};
+    FramePlan plan;
+};
+
 struct rt_renderer {
     int kind = 0;
     rt_scene* scene = nullptr;
@@ -197,7 +243,6 @@ struct rt_renderer {
     MegaFrame* d_frame = nullptr;          // the frame's constants k_megakernel reads from device memory: camera + slices (copied per frame from h_frame, pinned)
     MegaFrame* h_frame = nullptr;
     int stats_level = 2;                   // RT_KERNEL_STATS: 2 = the full counters (=1), 1 = the megakernel's timing-only instantiation (=2)
-    uint32_t last_slices = 1;              // slices the wavefront renderer's last enqueued frame used (rt_stats.pixel_slices)
     uint32_t slice_tag = 0;                // tag0 of the last frame (grows by spp + 1 per frame: a tag is tag0 + the first sample of a slice)
     uint32_t rr_start = 0;                 // Russian roulette from this bounce on (0 = off, the reference's behaviour)
     unsigned long long* d_stats = nullptr; // RT_KERNEL_STATS=1: wave scheduling statistics (diagnostic)
@@ -276,40 +321,30 @@ struct rt_renderer {
     // frame_begin makes such a stream wait for before anything writes the tile again.
     hipEvent_t ev_tile_read = nullptr;
     bool tile_read_recorded = false;
-    // the frame between rt_render_frame_begin and rt_render_frame_end
     bool frame_pending = false;
-    hipStream_t pending_stream = nullptr;
-    rt_stats pending_stats{};
-    size_t pending_hot = 0;
-    std::chrono::high_resolution_clock::time_point pending_t0{};
+    PendingFrame pending;
     bool profile_kernels = false;
     std::vector<hipEvent_t> ev_pool;
     // diagnostics: RT_MEGA_LDS_PAD=<bytes> of unused dynamic LDS per workgroup lowers the number of
     // resident workgroups per CU without touching the code; RT_MEGA_OCC=<waves per SIMD> sizes the persistent grid to match
     // progressive rendering (rt_renderer_set_progressive): every pixel's chain state {sum r, sum g, sum b, RNG word}, 16 bytes per pixel of the
     // tile in tile order, as the last frame or continuation left it. carry_samples: the samples it holds (0: none — no frame since the state was
-    // (re)allocated or discarded); carry_cam: the camera of the frame it belongs to. carry_mode / carry_total: what the frame being enqueued does
-    // with it (0 nothing, 1 store, 2 load and store; the samples the pixels hold at its end)
+    // (re)allocated or discarded); carry_cam: the camera of the frame it belongs to. What a frame does with it is its request's (FrameRequest)
     bool progressive = false;
     void* d_carry = nullptr;
     uint32_t carry_samples = 0;
     rt_camera carry_cam{};
-    int carry_mode = 0;
-    uint32_t carry_total = 0;
     // adaptive sampling (rt_render_frame_continue_blocks, rt_renderer_adapt): the tile's 8x8 blocks, allocated with d_carry. d_blk holds, for
     // N = max(blocks_x * blocks_y, 1): [0, N) every block's sample count, [N, 2N) its count at its snapshot (0: none), [2N, 3N) the last evaluation's
     // active flags, [3N, 4N) its errors (fp32), [4N, 5N + 1) its compacted list {length, blocks...}, [5N + 1, 6N + 1) the list of the call being
     // enqueued. d_snap: per pixel the carried state before the last call that rendered its block (16 B). h_blk: pinned, N + 1 words (the call's
     // list on its way up, the evaluation's on its way down). h_block_count: the counts as the host knows them (valid while carry_samples != 0;
-    // carry_samples is then their minimum). carry_mode 3 (a block continuation): n_call_blocks blocks listed, lane_pixels[k] of their pixels in
-    // stream lane k (the wavefront renderer)
+    // carry_samples is then their minimum)
     uint32_t blocks_x = 0, blocks_y = 0;
     uint32_t* d_blk = nullptr;
     void* d_snap = nullptr;
     uint32_t* h_blk = nullptr;
     std::vector<uint32_t> h_block_count;
-    uint32_t n_call_blocks = 0;
-    std::vector<uint32_t> lane_pixels;
     uint32_t hw_queues = 4; // GPU_MAX_HW_QUEUES as the host had set it when the renderer was created (4 = HIP's default): bounds the automatic stream lanes
     uint32_t mega_lds_pad = 0, mega_occ = kMegaWaves;
     // the scene generation (rt_scene::generation) the captured graph and the carried progressive state belong to (sync_scene_generation)
@@ -327,9 +362,9 @@ bool origin_in_contract_range(const HostScene& hs, const float o[3]);
 uint32_t hw_queues_from_env();
 hipError_t lane_stream_of(int device, uint32_t k, hipStream_t* out, bool* owned);
 int alloc_tile_buffers(rt_renderer* r);
-int frame_begin(rt_renderer* r, const rt_camera* cam, float* d_f32, uint8_t* d_u8, hipStream_t st);
+int frame_begin(rt_renderer* r, const rt_camera* cam, float* d_f32, uint8_t* d_u8, hipStream_t st, const FrameRequest* req = nullptr);
 int frame_end(rt_renderer* r, rt_stats* stats);
-int render_impl(rt_renderer* r, const rt_camera* cam, float* d_f32, uint8_t* d_u8, hipStream_t st, rt_stats* stats);
+int render_impl(rt_renderer* r, const rt_camera* cam, float* d_f32, uint8_t* d_u8, hipStream_t st, rt_stats* stats, const FrameRequest* req = nullptr);
 int alloc_carry(rt_renderer* r);
 int continue_impl(rt_renderer* r, uint32_t samples, float* d_f32, uint8_t* d_u8, hipStream_t st, rt_stats* stats);
 int continue_blocks_impl(rt_renderer* r, uint32_t samples, const uint32_t* blocks, uint32_t n_blocks, float* d_f32, uint8_t* d_u8, hipStream_t st,

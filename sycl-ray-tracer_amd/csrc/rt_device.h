@@ -303,6 +303,7 @@ RT_DEV void top_tree_fill(const SceneDev& S, u32x4* w0, u32x4* w1, u32x4* w2, u3
 // these helpers pin the compare to an SGPR-pair result (ballot) and the select to the e64 form.
 typedef unsigned long long lmask;
 RT_DEV lmask lanes(bool c) { return __builtin_amdgcn_ballot_w64(c); } // v_cmp_*_e64 into an SGPR pair
+RT_DEV uint32_t lane_rank(lmask m) { return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u)); } // lanes of m below this one
 RT_DEV float sel(lmask m, float a, float b) { // m ? b : a
     float d;
     asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "s"(m));

@@ -78,6 +78,28 @@ RT_DEV unsigned long long wave_sum_u64(uint32_t v) {
     return (unsigned long long)wave_sum_u32(v & 0xFFFFu) + ((unsigned long long)wave_sum_u32(v >> 16) << 16);
 }
 
+// the eight shared counters of a wave's WaveStats, added to stats_out[0 ... 7] (by one lane)
+RT_DEV void wave_stats_flush(const WaveStats& ws, unsigned long long* stats_out) {
+    atomicAdd(stats_out + 0, (unsigned long long)ws.inner_steps), atomicAdd(stats_out + 1, (unsigned long long)ws.inner_lanes);
+    atomicAdd(stats_out + 2, (unsigned long long)ws.leaf_steps), atomicAdd(stats_out + 3, (unsigned long long)ws.leaf_lanes);
+    atomicAdd(stats_out + 4, (unsigned long long)ws.shade_rounds), atomicAdd(stats_out + 5, (unsigned long long)ws.shade_lanes);
+    atomicAdd(stats_out + 6, (unsigned long long)ws.live_lane_steps), atomicAdd(stats_out + 7, (unsigned long long)ws.top_lanes);
+}
+
+// A pixel's end: mean over n samples, sqrt gamma, fp32 + unorm8 stores at index o (src/render_megakernel.cpp:154-158; K6 + K7,
+// src/render_wavefront.cpp:377-390, src/util.hpp:16-23). The sums are passed by address (k_megakernel: its LDS planes) and each is read where it
+// is divided: read up front, the three LDS reads of k_megakernel's pixel end moved against the divisions and its registers were allocated anew.
+template <class F, class I> RT_DEV void pixel_end(const F* sum_r, const F* sum_g, const F* sum_b, float n, I o, float* __restrict__ out_f32, uint8_t* __restrict__ out_u8) {
+    const f3 c = mk3(__builtin_sqrtf(*sum_r / n), __builtin_sqrtf(*sum_g / n), __builtin_sqrtf(*sum_b / n));
+    if (out_f32) reinterpret_cast<float4*>(out_f32)[o] = make_float4(c.x, c.y, c.z, 1.0f);
+    if (out_u8)
+        reinterpret_cast<uint32_t*>(out_u8)[o] = (uint32_t)to_unorm8(c.x) | ((uint32_t)to_unorm8(c.y) << 8) | ((uint32_t)to_unorm8(c.z) << 16) | 0xff000000u;
+}
+// row r of stream lane `lane_index` (its strips are every n_lanes-th strip of the renderer's tile) -> tile row
+RT_DEV uint32_t stream_lane_row(uint32_t r, uint32_t strip_rows, uint32_t n_lanes, uint32_t lane_index) {
+    return ((r / strip_rows) * n_lanes + lane_index) * strip_rows + r % strip_rows;
+}
+
 // ---- K1: megakernel ---------------------------------------------------------------------------------
 // One lane per pixel; a 64-thread block is one wave covering an 8x8 pixel tile. The sample loop, the
 // depth loop and the BVH traversal of render_pixel are flattened into ONE wave-level state machine:
@@ -128,18 +150,36 @@ struct RefillPolicy { // wave-uniform, ONE scalar register (k_megakernel is at t
         }
     }
 };
-typedef uint32_t u32x8 __attribute__((ext_vector_type(8)));
-static_assert(offsetof(MegaFrame, sl) == 56 && offsetof(SliceDev, tag0) == 8 && offsetof(SliceDev, cuts) == 16 && offsetof(SliceDev, bound) == 24 && offsetof(SliceDev, wait_cap) == 60,
-              "frame_* below read MegaFrame by byte offset");
-RT_DEV CameraDev frame_camera(const MegaFrame* f, int32_t width, int32_t height) { // the twelve floats as three scalar loads, here and now
+// The frame's constants as scalar loads, here and now, at byte offsets the compiler takes from MegaFrame itself (offsetof, an immediate). Each
+// statement waits for its own loads. (no memory clobber: the frame's constants are written by nobody while the kernel runs, and a clobber would
+// pin every variable a lambda captures by reference to scratch memory)
+template <uint32_t OFF> RT_DEV uint32_t frame_u32(const MegaFrame* f) {
+    uint32_t v;
+    asm volatile("s_load_dword %0, %1, %2\n\t"
+                 "s_waitcnt lgkmcnt(0)"
+                 : "=&s"(v)
+                 : "s"(f), "i"(OFF));
+    return v;
+}
+template <uint32_t OFF> RT_DEV unsigned long long frame_u64(const MegaFrame* f) {
+    unsigned long long v;
+    asm volatile("s_load_dwordx2 %0, %1, %2\n\t"
+                 "s_waitcnt lgkmcnt(0)"
+                 : "=&s"(v)
+                 : "s"(f), "i"(OFF));
+    return v;
+}
+// The camera's twelve floats as three loads with one wait. (Its offsets stay literal: as "i" operands they moved the camera-ray code around the
+// statement and cost k_megakernel<1, false> 16 bytes of scratch.)
+RT_DEV CameraDev frame_camera(const MegaFrame* f, int32_t width, int32_t height) {
+    static_assert(offsetof(MegaFrame, cam) == 0 && offsetof(CameraDev, dv) + sizeof(CameraDev::dv) == 48, "the camera's twelve floats lead MegaFrame");
     u32x4 a, b, c;
     asm volatile("s_load_dwordx4 %0, %3, 0x0\n\t"
                  "s_load_dwordx4 %1, %3, 0x10\n\t"
                  "s_load_dwordx4 %2, %3, 0x20\n\t"
                  "s_waitcnt lgkmcnt(0)"
                  : "=&s"(a), "=&s"(b), "=&s"(c)
-                 : "s"(f)); // (no memory clobber: the frame's constants are written by nobody while the kernel runs, and a clobber would pin every
-                            // variable a lambda captures by reference to scratch memory)
+                 : "s"(f));
     CameraDev cam;
     cam.center[0] = __uint_as_float(a.x), cam.center[1] = __uint_as_float(a.y), cam.center[2] = __uint_as_float(a.z);
     cam.pixel00[0] = __uint_as_float(a.w), cam.pixel00[1] = __uint_as_float(b.x), cam.pixel00[2] = __uint_as_float(b.y);
@@ -152,74 +192,39 @@ struct SliceNow { // as loaded: {state pointer, tag0, shift}, cuts
     u32x4 head;
     u32x2 cuts;
 };
-RT_DEV SliceNow frame_slices(const MegaFrame* f) {
+RT_DEV SliceNow frame_slices(const MegaFrame* f) { // two loads with one wait
+    static_assert(offsetof(SliceDev, tag0) == offsetof(SliceDev, state) + 8 && offsetof(SliceDev, shift) == offsetof(SliceDev, state) + 12, "SliceNow::head");
     SliceNow n;
-    asm volatile("s_load_dwordx4 %0, %2, 0x38\n\t"
-                 "s_load_dwordx2 %1, %2, 0x48\n\t"
+    asm volatile("s_load_dwordx4 %0, %2, %3\n\t"
+                 "s_load_dwordx2 %1, %2, %4\n\t"
                  "s_waitcnt lgkmcnt(0)"
                  : "=&s"(n.head), "=&s"(n.cuts)
-                 : "s"(f));
+                 : "s"(f), "i"((uint32_t)offsetof(MegaFrame, sl.state)), "i"((uint32_t)offsetof(MegaFrame, sl.cuts)));
     return n;
 }
 RT_DEV uint32_t frame_slice_bound(const MegaFrame* f, uint32_t j) { // bound[j], j wave-uniform
     uint32_t v;
-    const uint32_t at = (uint32_t)__builtin_amdgcn_readfirstlane((int)(0x50u + 4u * j)); // (hipcc may keep a wave-uniform value in a vector register: "s" alone does not move it)
+    const uint32_t at = (uint32_t)__builtin_amdgcn_readfirstlane((int)((uint32_t)offsetof(MegaFrame, sl.bound) + 4u * j)); // (hipcc may keep a wave-uniform value in a vector register: "s" alone does not move it)
     asm volatile("s_load_dword %0, %1, %2\n\t"
                  "s_waitcnt lgkmcnt(0)"
                  : "=&s"(v)
                  : "s"(f), "s"(at));
     return v;
 }
-static_assert(offsetof(MegaFrame, carry) == 120 && offsetof(MegaFrame, carry_total) == 128, "frame_carry* below read MegaFrame by byte offset");
-RT_DEV u32x4* frame_carry(const MegaFrame* f) { // progressive rendering: the tile's carried state, {sum r, sum g, sum b, RNG word} per pixel
-    u32x2 p;
-    asm volatile("s_load_dwordx2 %0, %1, 0x78\n\t"
-                 "s_waitcnt lgkmcnt(0)"
-                 : "=&s"(p)
-                 : "s"(f));
-    return (u32x4*)(((unsigned long long)p.y << 32) | p.x);
-}
-RT_DEV uint32_t frame_carry_total(const MegaFrame* f) { // ... and the samples every pixel holds when this launch is done
-    uint32_t v;
-    asm volatile("s_load_dword %0, %1, 0x80\n\t"
-                 "s_waitcnt lgkmcnt(0)"
-                 : "=&s"(v)
-                 : "s"(f));
-    return v;
-}
-static_assert(offsetof(MegaFrame, n_blocks) == 132 && offsetof(MegaFrame, blocks) == 136 && offsetof(MegaFrame, block_count) == 144,
-              "frame_blocks* below read MegaFrame by byte offset");
-RT_DEV uint32_t frame_n_blocks(const MegaFrame* f) { // a block continuation (adaptive sampling): the blocks in the launch's list
-    uint32_t v;
-    asm volatile("s_load_dword %0, %1, 0x84\n\t"
-                 "s_waitcnt lgkmcnt(0)"
-                 : "=&s"(v)
-                 : "s"(f));
-    return v;
-}
-RT_DEV const uint32_t* frame_blocks(const MegaFrame* f) { // ... the list (8x8 block indices of the tile, ascending)
-    u32x2 p;
-    asm volatile("s_load_dwordx2 %0, %1, 0x88\n\t"
-                 "s_waitcnt lgkmcnt(0)"
-                 : "=&s"(p)
-                 : "s"(f));
-    return (const uint32_t*)(((unsigned long long)p.y << 32) | p.x);
-}
-RT_DEV const uint32_t* frame_block_count(const MegaFrame* f) { // ... and the samples every block of the tile holds when this launch is done
-    u32x2 p;
-    asm volatile("s_load_dwordx2 %0, %1, 0x90\n\t"
-                 "s_waitcnt lgkmcnt(0)"
-                 : "=&s"(p)
-                 : "s"(f));
-    return (const uint32_t*)(((unsigned long long)p.y << 32) | p.x);
-}
-RT_DEV uint32_t frame_slice_wait_cap(const MegaFrame* f) {
-    uint32_t v;
-    asm volatile("s_load_dword %0, %1, 0x74\n\t"
-                 "s_waitcnt lgkmcnt(0)"
-                 : "=&s"(v)
-                 : "s"(f));
-    return v;
+// progressive rendering: the tile's carried state, {sum r, sum g, sum b, RNG word} per pixel (carry_word), and the samples every pixel holds when this launch is done
+RT_DEV u32x4* frame_carry(const MegaFrame* f) { return (u32x4*)frame_u64<offsetof(MegaFrame, carry)>(f); }
+RT_DEV uint32_t frame_carry_total(const MegaFrame* f) { return frame_u32<offsetof(MegaFrame, carry_total)>(f); }
+// a block continuation (adaptive sampling): the blocks in the launch's list, the list (8x8 block indices of the tile, ascending) and the samples
+// every block of the tile holds when this launch is done
+RT_DEV uint32_t frame_n_blocks(const MegaFrame* f) { return frame_u32<offsetof(MegaFrame, n_blocks)>(f); }
+RT_DEV const uint32_t* frame_blocks(const MegaFrame* f) { return (const uint32_t*)frame_u64<offsetof(MegaFrame, blocks)>(f); }
+RT_DEV const uint32_t* frame_block_count(const MegaFrame* f) { return (const uint32_t*)frame_u64<offsetof(MegaFrame, block_count)>(f); }
+RT_DEV uint32_t frame_slice_wait_cap(const MegaFrame* f) { return frame_u32<offsetof(MegaFrame, sl.wait_cap)>(f); }
+// A pixel's state as it changes hands — between slices, and between a frame and its continuation: {sum r, sum g, sum b, RNG word}
+RT_DEV u32x4 carry_word(float r, float g, float b, uint32_t rng) {
+    u32x4 w;
+    w.x = __float_as_uint(r), w.y = __float_as_uint(g), w.z = __float_as_uint(b), w.w = rng;
+    return w;
 }
 // A wave of a SLICED launch that holds nothing but lanes waiting for their pixel's state (no ray traced in this round, no lane traversing): sleep ~3 us before
 // the next look — a look is two 16-byte loads per lane past every cache, and at a frame's end thousands of waves may be in this state while the
@@ -362,6 +367,7 @@ __global__ void __launch_bounds__(kMegaBlock, kMegaWaves) k_megakernel(SceneDev 
                     first_next = frame_slice_bound(frame, slice_j);
                 }
                 const uint32_t total_slots = SLICED ? n_slots * n_slices : n_slots;
+                // (lane_rank's own expression: through the helper hipcc lowered the claim test below differently and spilled more in k_megakernel<1, false>)
                 const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(idle_m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)idle_m, 0u));
                 const uint32_t q = base + rank;
                 if (!live && q < total_slots && rank < w) {
@@ -473,24 +479,15 @@ __global__ void __launch_bounds__(kMegaBlock, kMegaWaves) k_megakernel(SceneDev 
                         __builtin_amdgcn_raw_buffer_store_b128(w1, rsrc, (int)(at + 16u), 0, 16 /* sc1 */);
                     } else if (s < spp) {
                         start = true;
-                    } else { // pixel finished: mean, sqrt gamma, fp32 + unorm8 stores (src/render_megakernel.cpp:154-158)
+                    } else { // pixel finished
                         live = false, pixel_finished = true;
                         float n;
                         if constexpr (CARRY == 3) // (a discarded branch captures nothing: the other instantiations compile as before)
                             n = (float)frame_block_count(frame)[(pix / (uint32_t)width >> 3) * tiles_x + ((uint32_t)x >> 3)];
                         else
                             n = (float)(CARRY == 2 ? frame_carry_total(frame) : spp);
-                        const f3 c = mk3(__builtin_sqrtf(*color_r / n), __builtin_sqrtf(*color_g / n), __builtin_sqrtf(*color_b / n));
-                        const uint32_t o = pix;
-                        if (out_f32) reinterpret_cast<float4*>(out_f32)[o] = make_float4(c.x, c.y, c.z, 1.0f);
-                        if (out_u8)
-                            reinterpret_cast<uint32_t*>(out_u8)[o] = (uint32_t)to_unorm8(c.x) | ((uint32_t)to_unorm8(c.y) << 8) |
-                                                                     ((uint32_t)to_unorm8(c.z) << 16) | 0xff000000u;
-                        if constexpr (CARRY != 0) { // the pixel's state for the next continuation
-                            u32x4 w;
-                            w.x = __float_as_uint(*color_r), w.y = __float_as_uint(*color_g), w.z = __float_as_uint(*color_b), w.w = rng;
-                            frame_carry(frame)[o] = w;
-                        }
+                        pixel_end(color_r, color_g, color_b, n, pix, out_f32, out_u8);
+                        if constexpr (CARRY != 0) frame_carry(frame)[pix] = carry_word(*color_r, *color_g, *color_b, rng); // the pixel's state for the next continuation
                     }
                 }
             }
@@ -509,10 +506,7 @@ __global__ void __launch_bounds__(kMegaBlock, kMegaWaves) k_megakernel(SceneDev 
     }
     if (lane == 0 && wave_rays) atomicAdd(ray_counter, wave_rays);
     if (STATS && lane == 0) {
-        atomicAdd(stats_out + 0, (unsigned long long)ws.inner_steps), atomicAdd(stats_out + 1, (unsigned long long)ws.inner_lanes);
-        atomicAdd(stats_out + 2, (unsigned long long)ws.leaf_steps), atomicAdd(stats_out + 3, (unsigned long long)ws.leaf_lanes);
-        atomicAdd(stats_out + 4, (unsigned long long)ws.shade_rounds), atomicAdd(stats_out + 5, (unsigned long long)ws.shade_lanes);
-        atomicAdd(stats_out + 6, (unsigned long long)ws.live_lane_steps), atomicAdd(stats_out + 7, (unsigned long long)ws.top_lanes);
+        wave_stats_flush(ws, stats_out);
         // wave timeline (shader clock cycles): total residency, its maximum, time in traversal and in shading
         const unsigned long long dur = (unsigned long long)((long long)__builtin_readcyclecounter() - t_begin);
         atomicAdd(stats_out + 8, dur), atomicMax(stats_out + 9, dur), atomicAdd(stats_out + 10, 1ull);
@@ -554,8 +548,7 @@ __global__ void __launch_bounds__(256) k_wf_init_carry(uint32_t n_local, uint32_
                                                         const u32x4* __restrict__ carry, uint32_t* __restrict__ rng, float4* __restrict__ accum) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= n_local) return;
-    const uint32_t x = i % width, r = i / width;
-    const uint32_t row = ((r / strip_rows) * n_lanes + lane_index) * strip_rows + r % strip_rows;
+    const uint32_t x = i % width, row = stream_lane_row(i / width, strip_rows, n_lanes, lane_index);
     const u32x4 c = carry[(size_t)row * width + x];
     rng[i] = c.w;
     accum[i] = make_float4(__uint_as_float(c.x), __uint_as_float(c.y), __uint_as_float(c.z), 0.0f);
@@ -694,7 +687,7 @@ __global__ void __launch_bounds__(kExtendBlock, kExtendWaves) k_wf_extend(SceneD
                 if (!exhausted) {
                     const uint32_t avail = chunk_end - chunk_pos;
                     const uint32_t take = cnt < avail ? cnt : avail;
-                    const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(need_m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)need_m, 0u));
+                    const uint32_t rank = lane_rank(need_m);
                     if (need && rank < take) {
                         slot = chunk_pos + rank;
                         pend_o = qin.org_id[slot];
@@ -714,12 +707,7 @@ __global__ void __launch_bounds__(kExtendBlock, kExtendWaves) k_wf_extend(SceneD
         if (STATS) ws.live_lane_steps += (uint32_t)__popcll(__ballot(has));
         (void)trav_step_wave<STATS, true>(S, T, stack, top, sg, &ws);
     }
-    if (STATS && lane == 0) {
-        atomicAdd(stats_out + 0, (unsigned long long)ws.inner_steps), atomicAdd(stats_out + 1, (unsigned long long)ws.inner_lanes);
-        atomicAdd(stats_out + 2, (unsigned long long)ws.leaf_steps), atomicAdd(stats_out + 3, (unsigned long long)ws.leaf_lanes);
-        atomicAdd(stats_out + 4, (unsigned long long)ws.shade_rounds), atomicAdd(stats_out + 5, (unsigned long long)ws.shade_lanes);
-        atomicAdd(stats_out + 6, (unsigned long long)ws.live_lane_steps), atomicAdd(stats_out + 7, (unsigned long long)ws.top_lanes);
-    }
+    if (STATS && lane == 0) wave_stats_flush(ws, stats_out);
 }
 
 // SHADE (+K5): one thread per queue slot, dense. Reads the ray state and its hit record, runs the part of
@@ -845,7 +833,7 @@ __global__ void __launch_bounds__(256) k_wf_shade(SceneDev S, QueueDev qin, Queu
     }
     const unsigned long long mask = __ballot(survive);
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const uint32_t prefix = __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+    const uint32_t prefix = lane_rank(mask);
     if (lane == 0) wave_total[wave] = (uint32_t)__popcll(mask);
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -1114,7 +1102,7 @@ __global__ void __launch_bounds__(kMegaBlock, kMegaWaves) k_wf_finish(SceneDev S
                 if (chunk_pos != chunk_end) {
                     const uint32_t avail = chunk_end - chunk_pos;
                     const uint32_t take = cnt < avail ? cnt : avail;
-                    const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(idle_m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)idle_m, 0u));
+                    const uint32_t rank = lane_rank(idle_m);
                     uint32_t first_here = 0, first_next = 0; // SLICED: first samples of the slice the chunk starts in and of the next
                     if (SLICED) {
                         slice_j = SliceCursor::advance(slice_j, n_slices, chunk_pos, n);
@@ -1335,7 +1323,7 @@ __global__ void __launch_bounds__(kMegaBlock, kMegaWaves) k_wf_finish(SceneDev S
                 }
                 b0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)b0), c0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)c0);
                 b1 = (uint32_t)__builtin_amdgcn_readfirstlane((int)b1);
-                const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(hm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)hm, 0u));
+                const uint32_t rank = lane_rank(hm);
                 if (hand_on) {
                     queue_store(qout, rank < c0 ? b0 + rank : b1 + (rank - c0), id, r);
                     rng_buf[id] = rng; // ScopedRng store: the next bounce's launch reads the word back
@@ -1347,7 +1335,7 @@ __global__ void __launch_bounds__(kMegaBlock, kMegaWaves) k_wf_finish(SceneDev S
             const unsigned long long rq_m = __ballot(requeue);
             const uint32_t n_rq = (uint32_t)__popcll(rq_m);
             if (n_rq) {
-                const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(rq_m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)rq_m, 0u));
+                const uint32_t rank = lane_rank(rq_m);
                 if (requeue) stage[staged + rank] = (unsigned long long)(id | ((samples_left - 2u) << 24)) | ((unsigned long long)rng << 32);
                 staged += n_rq;
             }
@@ -1360,12 +1348,7 @@ __global__ void __launch_bounds__(kMegaBlock, kMegaWaves) k_wf_finish(SceneDev S
     }
     if (SLICED && lane == 0 && slot_lost && fq.error) __hip_atomic_store(fq.error, 5u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (lane == 0 && wave_rays) atomicAdd(extra_rays, wave_rays);
-    if (STATS && lane == 0) {
-        atomicAdd(stats_out + 0, (unsigned long long)ws.inner_steps), atomicAdd(stats_out + 1, (unsigned long long)ws.inner_lanes);
-        atomicAdd(stats_out + 2, (unsigned long long)ws.leaf_steps), atomicAdd(stats_out + 3, (unsigned long long)ws.leaf_lanes);
-        atomicAdd(stats_out + 4, (unsigned long long)ws.shade_rounds), atomicAdd(stats_out + 5, (unsigned long long)ws.shade_lanes);
-        atomicAdd(stats_out + 6, (unsigned long long)ws.live_lane_steps), atomicAdd(stats_out + 7, (unsigned long long)ws.top_lanes);
-    }
+    if (STATS && lane == 0) wave_stats_flush(ws, stats_out);
     leave();
 }
 
@@ -1380,21 +1363,10 @@ __global__ void __launch_bounds__(256) k_wf_resolve(uint32_t n_local, uint32_t s
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= n_local) return;
     const float4 a = accum[i];
-    const float n = (float)spp;
-    const f3 c = mk3(__builtin_sqrtf(a.x / n), __builtin_sqrtf(a.y / n), __builtin_sqrtf(a.z / n));
-    // row r of stream-lane `lane_index` (its strips are every n_lanes-th strip of the renderer's tile) -> tile row
-    const uint32_t x = i % width, r = i / width;
-    const uint32_t row = ((r / strip_rows) * n_lanes + lane_index) * strip_rows + r % strip_rows;
+    const uint32_t x = i % width, row = stream_lane_row(i / width, strip_rows, n_lanes, lane_index);
     const size_t o = (size_t)row * width + x;
-    if (out_f32) reinterpret_cast<float4*>(out_f32)[o] = make_float4(c.x, c.y, c.z, 1.0f);
-    if (out_u8)
-        reinterpret_cast<uint32_t*>(out_u8)[o] = (uint32_t)to_unorm8(c.x) | ((uint32_t)to_unorm8(c.y) << 8) |
-                                                 ((uint32_t)to_unorm8(c.z) << 16) | 0xff000000u;
-    if (CARRY) {
-        u32x4 w;
-        w.x = __float_as_uint(a.x), w.y = __float_as_uint(a.y), w.z = __float_as_uint(a.z), w.w = rng[i];
-        carry[o] = w;
-    }
+    pixel_end(&a.x, &a.y, &a.z, (float)spp, o, out_f32, out_u8);
+    if (CARRY) carry[o] = carry_word(a.x, a.y, a.z, rng[i]);
 }
 
 // ---- adaptive sampling: block continuations and the two-image error estimate ------------------------------------------------------
@@ -1428,12 +1400,8 @@ __global__ void __launch_bounds__(256) k_blocks_resolve(uint32_t n_local, uint32
     if (i >= n_local) return;
     const uint32_t x = i % width, ly = i / width;
     const u32x4 a = carry[i];
-    const float n = (float)count[(ly >> 3) * blocks_x + (x >> 3)];
-    const f3 c = mk3(__builtin_sqrtf(__uint_as_float(a.x) / n), __builtin_sqrtf(__uint_as_float(a.y) / n), __builtin_sqrtf(__uint_as_float(a.z) / n));
-    if (out_f32) reinterpret_cast<float4*>(out_f32)[i] = make_float4(c.x, c.y, c.z, 1.0f);
-    if (out_u8)
-        reinterpret_cast<uint32_t*>(out_u8)[i] = (uint32_t)to_unorm8(c.x) | ((uint32_t)to_unorm8(c.y) << 8) |
-                                                 ((uint32_t)to_unorm8(c.z) << 16) | 0xff000000u;
+    const float sr = __uint_as_float(a.x), sg = __uint_as_float(a.y), sb = __uint_as_float(a.z);
+    pixel_end(&sr, &sg, &sb, (float)count[(ly >> 3) * blocks_x + (x >> 3)], i, out_f32, out_u8);
 }
 
 // The wavefront renderer's camera rays of a block continuation: slot i of the list -> pixel i & 63 of block list[i >> 6] (the mapping of
@@ -1465,7 +1433,7 @@ __global__ void __launch_bounds__(256) k_wf_generate_blocks(const CameraDev* __r
     if ((threadIdx.x & 63u) == 0u) base = atomicAdd(count_out, (uint32_t)__popcll(m));
     base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
     if (!take) return;
-    const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+    const uint32_t rank = lane_rank(m);
     const int x = (int)(id % width), gy = tile_global_row(tile, (int)(id / width));
     uint32_t st = rng[id];
     const RayState r = gy < cam.height ? camera_ray(cam, x, gy, st) : RayState{};
@@ -1482,18 +1450,10 @@ __global__ void __launch_bounds__(256) k_wf_resolve_blocks(uint32_t n_local, uin
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= n_local) return;
     const float4 a = accum[i];
-    const uint32_t x = i % width, r = i / width;
-    const uint32_t row = ((r / strip_rows) * n_lanes + lane_index) * strip_rows + r % strip_rows;
-    const float n = (float)count[(row >> 3) * ((width + 7u) >> 3) + (x >> 3)];
-    const f3 c = mk3(__builtin_sqrtf(a.x / n), __builtin_sqrtf(a.y / n), __builtin_sqrtf(a.z / n));
+    const uint32_t x = i % width, row = stream_lane_row(i / width, strip_rows, n_lanes, lane_index);
     const size_t o = (size_t)row * width + x;
-    if (out_f32) reinterpret_cast<float4*>(out_f32)[o] = make_float4(c.x, c.y, c.z, 1.0f);
-    if (out_u8)
-        reinterpret_cast<uint32_t*>(out_u8)[o] = (uint32_t)to_unorm8(c.x) | ((uint32_t)to_unorm8(c.y) << 8) |
-                                                 ((uint32_t)to_unorm8(c.z) << 16) | 0xff000000u;
-    u32x4 w;
-    w.x = __float_as_uint(a.x), w.y = __float_as_uint(a.y), w.z = __float_as_uint(a.z), w.w = rng[i];
-    carry[o] = w;
+    pixel_end(&a.x, &a.y, &a.z, (float)count[(row >> 3) * ((width + 7u) >> 3) + (x >> 3)], o, out_f32, out_u8);
+    carry[o] = carry_word(a.x, a.y, a.z, rng[i]);
 }
 
 // The two-image error of every block (Dammertz et al.: include/rt_mi355x.h states the estimator), one wave per block, a lane per pixel. I = sum / n
@@ -1547,7 +1507,7 @@ __global__ void __launch_bounds__(1024) k_adapt_compact(uint32_t n_blocks, const
             before += k < wv ? v : 0u;
             total += v;
         }
-        const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+        const uint32_t rank = lane_rank(m);
         if (f) out[1u + base + before + rank] = i;
         base += total;
         __syncthreads();

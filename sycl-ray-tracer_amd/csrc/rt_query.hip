@@ -74,7 +74,7 @@ __global__ void __launch_bounds__(kQueryBlock, kQueryWaves) k_query(SceneDev S, 
             }
             if (cb == ce) break; // every shard exhausted
             const uint32_t take = ce - cb < cnt ? (uint32_t)(ce - cb) : cnt;
-            const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(idle >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)idle, 0u));
+            const uint32_t rank = lane_rank(idle);
             if (!busy && rank < take) {
                 const unsigned long long i = cb + rank;
                 const f3 o = mk3(q.org[3 * i], q.org[3 * i + 1], q.org[3 * i + 2]);

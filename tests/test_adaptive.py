@@ -1,7 +1,7 @@
 """CPU tests of adaptive sampling's host side (no GPU needed): the entry points are declared in the header, exported by both builds of the
 library and prototyped in rtamd/abi.py; null handles are refused without a HIP call; the CLI documents and checks --adaptive; the block
 grid's arithmetic; and the float64 model of the two-image error estimate (rt_mi355x.h) that tests/test_gpu_adaptive.py holds the library
-to, on hand-made arrays."""
+to, on hand-made arrays, with its vectorised form (the one tests/test_gpu_continuations_full_size.py uses at full frame size) equal to it."""
 import ctypes as C
 import re
 import subprocess
@@ -39,6 +39,28 @@ def block_errors_model(I, before, counts, eps=EPS):
             e = np.abs(Ib - A).sum(-1) / np.sqrt(eps + Ib.sum(-1))
             out[y, x] = e.mean()
     return out
+
+
+def block_index_map(rows, w):
+    """(rows, w) map of every pixel's block index, tile-local row-major."""
+    bx = (w + 7) // 8
+    return (np.arange(rows)[:, None] // 8) * bx + np.arange(w)[None, :] // 8
+
+
+def block_errors_vec(I, before, counts, has_snap, eps=EPS):
+    """block_errors_model without a whole image per block. I: (rows, W, 3) linear image of the current state; before: (rows, W, >= 3) every
+    pixel's image as of its block's last render, in sqrt space as returned; counts: (by, bx); has_snap: (by, bx) bool, whether the block has a
+    snapshot. Returns (by, bx) float64, +inf where a block has none."""
+    by, bx = counts.shape
+    rows, w = I.shape[:2]
+    A = before[..., :3].astype(np.float64) ** 2
+    I = I[..., :3].astype(np.float64)
+    e = np.abs(I - A).sum(-1) / np.sqrt(eps + I.sum(-1))
+    idx = block_index_map(rows, w).reshape(-1)
+    n_in = np.bincount(idx, minlength=by * bx)
+    out = np.bincount(idx, weights=e.reshape(-1), minlength=by * bx) / np.maximum(n_in, 1)
+    out[~np.asarray(has_snap, bool).reshape(-1)] = np.inf
+    return out.reshape(by, bx)
 
 
 def test_entry_points_are_declared_exported_and_prototyped(rtlib, devlib):
@@ -99,3 +121,50 @@ def test_estimator_model_on_hand_made_arrays():
     np.testing.assert_allclose(e[0, 1], 3 * 0.11 / np.sqrt(EPS + 0.75), rtol=1e-12)
     np.testing.assert_allclose(e[1, 0], (3 * 0.25 / np.sqrt(EPS + 0.75)) / 16, rtol=1e-12)  # 8 x 2 pixels in the image
     assert np.isinf(e[1, 1])
+
+
+def _per_pixel_snapshots(before):
+    """The per-pixel image of each block's snapshot and the snapshot flags, from block_errors_model's per-block images."""
+    by, bx, rows, w = before.shape[:4]
+    idx = block_index_map(rows, w)
+    img = before.reshape(by * bx, rows, w, -1)[idx, np.arange(rows)[:, None], np.arange(w)[None, :]]
+    has = np.array([[before[y, x].any() for x in range(bx)] for y in range(by)])
+    return img, has
+
+
+def test_vectorised_estimator_equals_the_model():
+    """block_errors_vec against block_errors_model: the hand-made arrays above, then random images with ragged right and bottom blocks,
+    blocks without a snapshot, snapshots equal to the image and all-black pixels (A = I = 0: e_p = 0, the eps keeps the root positive)."""
+    rows, w = 10, 12
+    I = np.full((rows, w, 3), 0.25)
+    before = np.zeros((2, 2, rows, w, 4))
+    before[0, 0, ..., :3], before[0, 0, ..., 3] = 0.5, 1.0
+    before[0, 1, ..., :3], before[0, 1, ..., 3] = np.sqrt(0.36), 1.0
+    before[1, 0, ..., :3], before[1, 0, ..., 3] = 0.5, 1.0
+    before[1, 0, 9, 3, :3] = 0.0
+    counts = np.full((2, 2), 8, np.uint32)
+    img, has = _per_pixel_snapshots(before)
+    vec, model = block_errors_vec(I, img, counts, has), block_errors_model(I, before, counts)
+    assert (np.isinf(vec) == np.isinf(model)).all() and vec[0, 0] == 0.0
+    np.testing.assert_allclose(vec[~np.isinf(vec)], model[~np.isinf(model)], rtol=1e-12, atol=0)  # (the two sum in different orders)
+    rng = np.random.default_rng(5)
+    for rows, w in ((8, 8), (9, 17), (21, 13), (24, 40), (1, 3), (31, 33)):
+        bx, by = block_grid(w, rows)
+        cur = rng.random((rows, w, 4)).astype(np.float32)
+        cur[rng.random((rows, w)) < 0.1, :3] = 0.0
+        I = cur[..., :3].astype(np.float64) ** 2
+        before = np.zeros((by, bx, rows, w, 4), np.float32)
+        counts = rng.integers(1, 100, (by, bx)).astype(np.uint32)
+        snap = rng.random((by, bx)) < 0.7
+        snap.reshape(-1)[0] = True
+        for y in range(by):
+            for x in range(bx):
+                if snap[y, x]:
+                    before[y, x] = cur if rng.random() < 0.2 else rng.random((rows, w, 4)).astype(np.float32)
+                    before[y, x, ..., 3] = 1.0
+        img, has = _per_pixel_snapshots(before)
+        assert (has == snap).all()
+        model = block_errors_model(I, before, counts)
+        vec = block_errors_vec(I, img, counts, snap)
+        assert (np.isinf(vec) == ~snap).all() and (np.isinf(model) == ~snap).all()
+        np.testing.assert_allclose(vec[snap], model[snap], rtol=1e-12, atol=0)

@@ -124,10 +124,16 @@ void rt_scene_destroy(rt_scene* scene);
 /* ---- Dynamic scenes (no reference counterpart here; Embree re-commits a scene whose instance matrices were changed through
  * rtcSetGeometryTransform, src/scene.cpp:491, with a refit). */
 #define RT_SCENE_UPDATABLE 1u
-/* == rt_scene_create, plus flags. RT_SCENE_UPDATABLE keeps on the device what an update needs (object positions, indices, every triangle's
+/* == rt_scene_create, plus flags (RT_SCENE_UPDATABLE, RT_SCENE_KEEP_PREVIOUS below). RT_SCENE_UPDATABLE keeps on the device what an update needs (object positions, indices, every triangle's
  * instance, the world-space vertices, the exact box of every node and the nodes' height levels: counted in device_bytes). Unknown flag
  * bits -> RT_ERR_INVALID. */
 int rt_scene_create_ex(const rt_scene_desc* desc, int device, int bvh_kind, uint32_t flags, rt_scene** out);
+/* RT_SCENE_KEEP_PREVIOUS (only together with RT_SCENE_UPDATABLE, else RT_ERR_INVALID): the scene keeps a second copy of its world-space vertices
+ * on the device, 9 floats per triangle (+36 bytes per triangle in device_bytes): the vertices as they were before the last accepted
+ * rt_scene_update. Before the first update previous == current; an update makes the current vertices the previous ones before it writes the new
+ * ones (whatever it changes: after an update of the normals alone previous == current); a refused update leaves both untouched. What reads them
+ * is rt_scene_gbuffer_motion. A scene without the flag behaves exactly as before, and its updates do no extra work. */
+#define RT_SCENE_KEEP_PREVIOUS 2u
 
 typedef struct rt_scene_update_desc {
     uint32_t n_instances;         /* 0 = transforms unchanged, else == the scene's n_instances            */
@@ -270,6 +276,14 @@ int rt_renderer_set_profiling(rt_renderer* r, int enable);
  * p = clamp(max component of its stored attenuation, 0.05, 1) (one extra RNG draw) and carries on with
  * attenuation / p; otherwise it ends with no contribution. Same rule in both renderers and in the oracle. */
 int rt_renderer_set_russian_roulette(rt_renderer* r, uint32_t start_bounce);
+
+/* Per-frame seed salt (no reference counterpart: the reference seeds a pixel from its coordinates alone, so every frame of an animation carries
+ * the same noise). A pixel's xorshift chain starts at pixel_seed(x, gy, W, H, seed_mode) + salt * 0x9E3779B9u (uint32, wrapping); salt 0, the
+ * default, is the reference's seed: the same frames bit for bit. It holds for the frames begun after the call, under both renderers and every
+ * schedule, slicing and tile split (seeds stay a function of GLOBAL pixel coordinates: tiles still union to the single-GPU frame). A continuation
+ * (rt_render_frame_continue*) goes on with the chain it was started with, whatever the salt is by then. RT_ERR_INVALID while a frame is in
+ * flight; a captured hipGraph is re-captured by the next frame when the salt changed. An animation passes its frame number. */
+int rt_renderer_set_frame_seed(rt_renderer* r, uint32_t salt);
 
 /* ---- Schedule of the wavefront renderer --------------------------------------------------------------------------------
  * The reference's WavefrontRenderer::render_frame (src/render_wavefront.cpp:396-431) has ONE schedule: per sample, one
@@ -481,6 +495,18 @@ int rt_renderer_block_errors(const rt_renderer* r, float* out);
 int rt_scene_gbuffer(rt_scene* scene, const rt_camera* cam, float* albedo, float* normal, float* position);
 int rt_scene_gbuffer_device(rt_scene* scene, const rt_camera* cam, void* d_albedo, void* d_normal, void* d_position, void* stream);
 
+/* The motion guide: rt_scene_gbuffer (the same three planes, bit for bit) plus a fourth H x W x 4 plane from the same traversal, where each
+ * visible surface point was before the scene's last update. For a hit on triangle T (rt_intersect_batch's index: a pre-split triangle reports its
+ * original) at (u, v), with T's PREVIOUS world-space vertices b0, b1, b2 (RT_SCENE_KEEP_PREVIOUS) and w = (1 - u) - v, per component
+ *   prev = (b0 * w + b1 * u) + b2 * v,  prev.w = 1;     a miss writes (0, 0, 0, 0).
+ * It covers instance motion and vertex animation alike, and a static scene under a moving camera (create the scene with both flags and never
+ * update it: prev_position == position up to the rounding of the two expressions). Refusals as rt_scene_gbuffer, plus RT_ERR_INVALID for a scene
+ * created without RT_SCENE_KEEP_PREVIOUS. The _device form records the scene's per-stream event as rt_scene_gbuffer_device does: an update
+ * waits for it. */
+int rt_scene_gbuffer_motion(rt_scene* scene, const rt_camera* cam, float* albedo, float* normal, float* position, float* prev_position);
+int rt_scene_gbuffer_motion_device(rt_scene* scene, const rt_camera* cam, void* d_albedo, void* d_normal, void* d_position,
+                                   void* d_prev_position, void* stream);
+
 /* Edge-avoiding a-trous wavelet filter (Dammertz, Sewtz, Hanika, Lensch, HPG 2010) guided by rt_scene_gbuffer's planes.
  * Inputs are H x W x 4 fp32: the frame as a renderer writes it (rgb = sqrt(mean), alpha 1) and the three guides. Outputs: out_f32 H*W*4
  * floats, out_u8 H*W*4 bytes; either may be NULL, not both. out_f32 may alias rgba_f32 (in-place); no other aliasing is allowed.
@@ -516,6 +542,59 @@ int rt_denoise(rt_denoiser* d, const rt_denoise_params* p, const float* rgba_f32
                const float* position, float* out_f32, uint8_t* out_u8);
 int rt_denoise_device(rt_denoiser* d, const rt_denoise_params* p, const void* d_rgba_f32, const void* d_albedo, const void* d_normal,
                       const void* d_position, void* d_out_f32, void* d_out_u8, void* stream);
+
+/* ---- Temporal accumulation by reprojection (no reference counterpart). Frames of an animation rendered with different seed salts
+ * (rt_renderer_set_frame_seed) are independent estimates; the accumulator carries a running mean of them from frame to frame, fetched for every
+ * pixel where its surface point was one frame ago (rt_scene_gbuffer_motion's prev_position, projected through the previous call's camera),
+ * tested against the G-buffer and blended with the new frame. Its output is a frame in the form rt_denoise takes: temporal first, a-trous second.
+ *
+ * An accumulator owns, for one W x H on one device, two sets (ping-pong: taps read neighbours) of three float4 planes — history colour (linear
+ * rgb, .w = the history length n, a float holding an integer), and the position and normal planes of the frame that history belongs to — and that
+ * frame's camera: 96 bytes per pixel, plus the host variant's staging (88 bytes per pixel), all allocated by rt_temporal_create: no call allocates.
+ * Per call, per pixel p = (x, y), with F, N, P, Q = rgba_f32, normal, position, prev_position at p and c', p00', du', dv' the camera of the
+ * previous call; every operation one R1 fp32 op, left to right as bracketed; dot(a, b) = (a.x*b.x + a.y*b.y) + a.z*b.z,
+ * cross(a, b) = (a.y*b.z - a.z*b.y, a.z*b.x - a.x*b.z, a.x*b.y - a.y*b.x), each product and difference one op:
+ *   1. L = (F_r*F_r, F_g*F_g, F_b*F_b): linear radiance, as rt_denoise's step 1.
+ *   2. p has NO HISTORY when there is no previous call since create / reset, when p is a miss (P.w not finite), or when step 3, 4 or 5 fails.
+ *      Then L' = L, n' = 1 for a hit and 0 for a miss, and the outputs at p are the input's own: out_f32 = (F_r, F_g, F_b, 1) and its to_unorm8
+ *      (not a square root of a square).
+ *   3. r = Q.xyz - c'; m = cross(du', dv'); e = p00' - c'; s = dot(e, m) / dot(r, m); fail unless s is finite and > 0. h = r*s - e;
+ *      sx = dot(h, du') / dot(du', du'), sy = dot(h, dv') / dot(dv', dv'); fail unless -1 < sx < (float)W and -1 < sy < (float)H (NaN fails, before
+ *      any conversion to an integer). The centre of pixel column x is sx = x. (du' and dv' are taken to be perpendicular, as rt_camera_init makes
+ *      them: for a sheared pixel grid sx, sy are not the grid's coordinates.)
+ *   4. x0 = floor(sx), fx = sx - x0, likewise y0, fy. Four taps t = (x0 + i, y0 + j) in the order (i, j) = (0,0), (1,0), (0,1), (1,1), with the
+ *      weight w_t = (i ? fx : 1 - fx) * (j ? fy : 1 - fy). A tap is VALID when it lies in the image, w_t > 0, its stored n_t >= 1 (it was a hit),
+ *      dot(d, d) * kx <= 1 for d = Ppos_t.xyz - Q.xyz (kx = RN(1 / RN(sigma_position^2)), rt_denoise's coefficient; for sigma = +inf kx = 0 and
+ *      the test is left out) and dot(N.xyz, Pnrm_t.xyz) >= cos_normal (cos_normal = -1: the test is left out). Wsum and S accumulate w_t and
+ *      w_t * Lhist_t over the valid taps in tap order; fail when Wsum < 1/64. Hc = S / Wsum; n_prev = the MINIMUM n_t of the valid taps (it stays
+ *      an exact integer and is conservative at disocclusion edges).
+ *   5. n' = min(n_prev + 1, max_history). n' == 1 (only with max_history = 1): no history (step 2). Otherwise a = 1 / n';
+ *      L' = Hc + (L - Hc) * a per channel.
+ *   6. The current set becomes colour (L', n'), position P, normal N, camera cam. Where p had history: out_f32 = (sqrt(L'), 1), out_u8 = its
+ *      to_unorm8 with alpha 255; everywhere history_len = n'.
+ * Limits: reflections and refractions are reprojected with the surface they appear on (history on mirrors and glass lags the motion of what they
+ * show); lighting that changes on a static surface lags by up to max_history frames.
+ * Refused with RT_ERR_INVALID, before any HIP call: NULL handles or required pointers, out_f32 and out_u8 both NULL, device < 0, non-positive
+ * sizes, W * H >= 2^31, a shape so narrow and tall that the grid of 64 x 4 tiles would exceed 2^32 threads, max_history outside 1 .. 4096, a
+ * sigma_position that is NaN or below 1e-6, cos_normal NaN or outside [-1, 1], a camera whose width or height is not the accumulator's.
+ * history_len (H*W floats) may be NULL. out_f32 may alias rgba_f32 (in place); no other aliasing is allowed.
+ * rt_temporal_accumulate takes host arrays and synchronises; rt_temporal_accumulate_device takes device arrays and enqueues one kernel on
+ * `stream` (NULL = the null stream). Calls on one accumulator are serialised by the accumulator: each records an event that the next call's
+ * stream waits for. rt_temporal_reset forgets the history: the next call passes its frame through. */
+typedef struct rt_temporal_params {
+    uint32_t max_history;  /* 1 .. 4096: the blend weight never drops below 1 / max_history; 1 = pass-through */
+    float sigma_position;  /* world units, >= 1e-6 or +inf (test off)                                         */
+    float cos_normal;      /* -1 .. 1; -1 = test off                                                           */
+} rt_temporal_params;      /* 12 bytes */
+typedef struct rt_temporal rt_temporal;
+int rt_temporal_create(int device, int32_t width, int32_t height, rt_temporal** out);
+void rt_temporal_destroy(rt_temporal* t);
+int rt_temporal_reset(rt_temporal* t);
+int rt_temporal_accumulate(rt_temporal* t, const rt_temporal_params* p, const rt_camera* cam, const float* rgba_f32, const float* normal,
+                           const float* position, const float* prev_position, float* out_f32, uint8_t* out_u8, float* history_len);
+int rt_temporal_accumulate_device(rt_temporal* t, const rt_temporal_params* p, const rt_camera* cam, const void* d_rgba_f32, const void* d_normal,
+                                  const void* d_position, const void* d_prev_position, void* d_out_f32, void* d_out_u8, void* d_history_len,
+                                  void* stream);
 
 /* ---- Multi-GPU frame gather over xGMI (no reference counterpart: the reference renders on ONE device and hands its
  * single image to stbi_write_png, src/main.cpp:57-70, src/util.hpp:8-33). SURVEY §8(e): the frame is split into interleaved

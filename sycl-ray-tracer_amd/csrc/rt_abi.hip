@@ -61,7 +61,8 @@ int rt_scene_create(const rt_scene_desc* desc, int device, int bvh_kind, rt_scen
 int rt_scene_create_ex(const rt_scene_desc* desc, int device, int bvh_kind, uint32_t flags, rt_scene** out) {
     if (!out) return fail(RT_ERR_INVALID, "null output pointer");
     *out = nullptr;
-    if (flags & ~RT_SCENE_UPDATABLE) return fail(RT_ERR_INVALID, "unknown scene flags");
+    if (flags & ~(RT_SCENE_UPDATABLE | RT_SCENE_KEEP_PREVIOUS)) return fail(RT_ERR_INVALID, "unknown scene flags");
+    if ((flags & RT_SCENE_KEEP_PREVIOUS) && !(flags & RT_SCENE_UPDATABLE)) return fail(RT_ERR_INVALID, "RT_SCENE_KEEP_PREVIOUS is a flag of updatable scenes: pass RT_SCENE_UPDATABLE with it");
     if (bvh_kind != RT_BVH_DEFAULT && bvh_kind != RT_BVH_LBVH && bvh_kind != RT_BVH_SAH && bvh_kind != RT_BVH_LBVH_GPU)
         return fail(RT_ERR_INVALID, "unknown bvh_kind");
     if (bvh_kind == RT_BVH_LBVH_GPU) { // the build itself runs on the device
@@ -134,7 +135,7 @@ int rt_scene_create_ex(const rt_scene_desc* desc, int device, int bvh_kind, uint
         }
     }
     if (flags & RT_SCENE_UPDATABLE) {
-        rc = no_throw([&] { return init_scene_update(s, desc); });
+        rc = no_throw([&] { return init_scene_update(s, desc, (flags & RT_SCENE_KEEP_PREVIOUS) != 0); });
         if (rc != RT_OK) {
             rt_scene_destroy(s);
             return rc;
@@ -311,6 +312,14 @@ int rt_renderer_set_russian_roulette(rt_renderer* r, uint32_t start_bounce) {
     if (r->rr_start != start_bounce) drop_graph(r); // the bounce flags are baked into the captured launches
     r->rr_start = start_bounce;
     r->carry_samples = 0; // (progressive rendering: the carried chains were rendered with the old paths' ends)
+    return RT_OK;
+}
+
+int rt_renderer_set_frame_seed(rt_renderer* r, uint32_t salt) {
+    if (!r) return fail(RT_ERR_INVALID, "null renderer");
+    if (r->frame_pending) return fail(RT_ERR_INVALID, "a frame is in flight (rt_render_frame_end first)");
+    if (r->frame_salt != salt) drop_graph(r); // k_wf_init's seed offset is baked into the captured launches
+    r->frame_salt = salt; // (a continuation goes on from the carried RNG words: the chain keeps the salt it was started with)
     return RT_OK;
 }
 

@@ -637,7 +637,7 @@ int enqueue_wavefront(rt_renderer* r, const FramePlan& p, float* d_f32, uint8_t*
             hipLaunchKernelGGL(k_wf_init_carry, dim3(grid[k]), dim3(256), 0, lane_stream(L), L.n_local, (uint32_t)r->width, r->tile.strip_rows, K, k,
                                (const u32x4*)r->d_carry, L.d_rng, L.d_accum);
         else
-            hipLaunchKernelGGL(k_wf_init, dim3(grid[k]), dim3(256), 0, lane_stream(L), r->d_cam, L.tile, r->seed_mode, L.n_local, L.d_rng, L.d_accum);
+            hipLaunchKernelGGL(k_wf_init, dim3(grid[k]), dim3(256), 0, lane_stream(L), r->d_cam, L.tile, r->seed_mode, frame_seed_add(r), L.n_local, L.d_rng, L.d_accum);
         launches.add(RT_K_WF_INIT);
     }
     // the lanes' chains are enqueued round-robin, bounce by bounce, so their kernels interleave on the device. D0 bounces are done launch by launch,
@@ -824,6 +824,7 @@ int enqueue_frame(rt_renderer* r, const FramePlan& p, const rt_camera* cam, floa
         r->h_frame->cam = c, r->h_frame->sl = sl;
         r->h_frame->carry = r->d_carry, r->h_frame->carry_total = p.req.carry_total;
         r->h_frame->n_blocks = blocks ? p.req.n_blocks : 0u;
+        r->h_frame->seed_add = frame_seed_add(r);
         r->h_frame->blocks = r->d_blk ? r->d_blk + 5 * blk_words(r) + 1 : nullptr, r->h_frame->block_count = r->d_blk;
         HIPCHK(hipMemcpyAsync(r->d_frame, r->h_frame, sizeof(MegaFrame), hipMemcpyHostToDevice, st));
         if (blocks && r->max_depth > 0 && (d_f32 || d_u8)) { // a block continuation: the whole image from the carried state, the listed blocks' pixels rewritten by the megakernel

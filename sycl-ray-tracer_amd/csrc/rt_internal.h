@@ -5,9 +5,11 @@
 //   rt_comm.hip    the multi-GPU frame gather (RCCL) and its de-interleave kernel
 //   rt_probes.hip  rt_intersect_batch and the rt_probe_* entry points with their kernels (rt_probe_kernels.h)
 //   rt_update.hip  dynamic scenes: rt_scene_create_ex's updatable state, rt_scene_update and its refit kernels
-//   rt_gbuffer.hip the primary-hit G-buffer (rt_scene_gbuffer[_device]) and its kernel
+//   rt_gbuffer.hip the primary-hit G-buffer (rt_scene_gbuffer[_device], rt_scene_gbuffer_motion[_device]) and k_gbuffer
+//   rt_gbuffer_motion.hip k_gbuffer_motion: the same pixel (rt_gbuffer_pixel.h) plus the motion guide
 //   rt_denoise.hip the a-trous denoiser (rt_denoiser_*, rt_denoise[_device]) and its kernels
 //   rt_query.hip   ray queries with a per-ray tmax (rt_trace_rays[_device]) and their kernel
+//   rt_temporal.hip the temporal accumulator (rt_temporal_*) and its kernel
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -103,6 +105,8 @@ using namespace rtlib;
 //   xf, xf_stage     16 floats per instance: the transforms, and their staging copy
 //   islot            every instance's shading word, uploaded per update where the table rows moved
 //   wv               world-space vertices, 9 floats per triangle (the transform's scratch output, the host copy's source)
+//   wv_prev          RT_SCENE_KEEP_PREVIOUS only: the world-space vertices as they were before the last accepted update (== wv before the first);
+//                    an update swaps the two pointers and writes the new vertices into what becomes wv (rt_scene_gbuffer_motion reads wv_prev)
 //   box              the exact box of every node, 6 floats (24 bytes) per node
 //   levels           the nodes by height (level_start on the host)
 //   red              the transform's reduction: 6 ordered 64-bit keys (bounds, first occurrence) + a non-finite flag
@@ -122,6 +126,8 @@ struct SceneUpdate {
     float* d_xf_stage = nullptr;
     uint32_t* d_islot = nullptr;
     float* d_wv = nullptr;
+    float* d_wv_prev = nullptr;
+    bool keep_previous = false;
     float* d_box = nullptr;
     uint32_t* d_levels = nullptr;
     unsigned long long* d_red = nullptr;
@@ -229,6 +235,7 @@ struct rt_renderer {
     rt_scene* scene = nullptr;
     int32_t width = 0, height = 0;
     uint32_t max_depth = 0, spp = 0, seed_mode = 0;
+    uint32_t frame_salt = 0; // rt_renderer_set_frame_seed: the frames begun from now on start their chains at pixel_seed + salt * 0x9E3779B9
     TileDev tile{0, 1, 8, 0};
     uint32_t n_local = 0; // pixels in this tile
     bool unusable = false; // the last (re-)allocation of the tile's buffers failed: no frame until one succeeds
@@ -380,11 +387,15 @@ inline void sync_scene_generation(rt_renderer* r) {
     r->carry_samples = 0;
     r->scene_gen = r->scene->generation;
 }
+inline uint32_t frame_seed_add(const rt_renderer* r) { return r->frame_salt * 0x9E3779B9u; }
 inline bool carry_is_current(const rt_renderer* r) { return r->scene_gen == r->scene->generation; }
 
+// rt_gbuffer_motion.hip
+void launch_gbuffer_motion(const SceneDev& S, const CameraDev& c, uint32_t n, float4* alb, float4* nrm, float4* pos, const float* prev_wv, float4* prev,
+                           hipStream_t st);
 // rt_update.hip
 void free_scene_update(rt_scene* s);
-int init_scene_update(rt_scene* s, const rt_scene_desc* d);
+int init_scene_update(rt_scene* s, const rt_scene_desc* d, bool keep_previous);
 uint32_t scene_inst_capacity(const rt_scene* s); // rows the device's instance table is allocated with
 // brings the host copy up to date after device updates (rt_scene_info, rt_scene_check_bvh, rt_scene_count_visits, rt_dev_scene_*)
 int sync_host_copy(const rt_scene* s);

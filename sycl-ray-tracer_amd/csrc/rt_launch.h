@@ -99,6 +99,7 @@ struct SliceCursor {
 // n_blocks / blocks / block_count: a block continuation (adaptive sampling, rt_render_frame_continue_blocks): the launch's list of 8x8 blocks of the
 // tile (ascending block indices, tile-local row-major) and the tile's per-block sample counts, what k_megakernel<.., CARRY = 3> divides by. Read only
 // by that instantiation.
+// seed_add: the frame's seed salt (rt_renderer_set_frame_seed), read where a pixel's chain starts from pixel_seed.
 struct MegaFrame {
     CameraDev cam;
     SliceDev sl;
@@ -107,6 +108,7 @@ struct MegaFrame {
     uint32_t n_blocks;
     const uint32_t* blocks;
     const uint32_t* block_count;
+    uint32_t seed_add; // rt_renderer_set_frame_seed: salt * 0x9E3779B9, added to every pixel_seed (0: the reference's seeds)
 };
 
 // EXTEND (k_wf_extend)

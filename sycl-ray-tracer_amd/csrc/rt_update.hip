@@ -44,9 +44,11 @@ inline float key_value(unsigned long long key) {
     return f;
 }
 
-constexpr uint32_t kRedWords = 8; // [0, 3) min keys, [3, 6) max keys, [6] non-finite flag
+constexpr uint32_t kRedWords = 8; // [0, 3) min keys, [3, 6) max keys, [6] non-finite flag, [7] the refit's failure flag
 
-// Phase 1: world-space vertices + bounds + non-finite flag. One thread per triangle.
+// Phase 1: world-space vertices + bounds + non-finite flag. One thread per triangle. WRITE = false: the bounds and the flag only, `wv` untouched
+// (a scene that keeps its previous vertices tests an update before it writes anything: a refusal must leave both copies as they were).
+template <bool WRITE = true>
 __global__ void __launch_bounds__(256) k_upd_transform(uint32_t n_tris, const float* __restrict__ pos, const uint32_t* __restrict__ idx,
                                                         const uint32_t* __restrict__ tri_inst, const float* __restrict__ xf,
                                                         float* __restrict__ wv, unsigned long long* __restrict__ red) {
@@ -60,7 +62,7 @@ __global__ void __launch_bounds__(256) k_upd_transform(uint32_t n_tris, const fl
             const float x = pos[3 * (size_t)vi], y = pos[3 * (size_t)vi + 1], z = pos[3 * (size_t)vi + 2];
             for (int a = 0; a < 3; ++a) {
                 const float p = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(m[a], x), __fmul_rn(m[4 + a], y)), __fmul_rn(m[8 + a], z)), m[12 + a]);
-                wv[9 * (size_t)t + 3 * k + a] = p;
+                if (WRITE) wv[9 * (size_t)t + 3 * k + a] = p;
                 bad |= isfinite(p) ? 0u : 1u;
                 const uint32_t v = 3u * t + (uint32_t)k;
                 kmin[a] = min(kmin[a], min_key(p, v));
@@ -283,7 +285,10 @@ int update_device(rt_scene* s, const std::vector<rt_instance>& inst, const rt_sc
         for (int a = 0; a < 3; ++a) up.h_red[a] = ~0ull, up.h_red[3 + a] = 0ull;
         up.h_red[6] = up.h_red[7] = 0ull;
         HIPCHK(hipMemcpyAsync(up.d_red, up.h_red, kRedWords * 8, hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(k_upd_transform, dim3(g256), dim3(256), 0, st, T, pos_new, up.d_idx, up.d_tri_inst, xf_new, up.d_wv, up.d_red);
+        if (up.keep_previous) // test first, write after (below): the current vertices are still needed as the previous ones
+            hipLaunchKernelGGL(k_upd_transform<false>, dim3(g256), dim3(256), 0, st, T, pos_new, (const uint32_t*)up.d_idx, (const uint32_t*)up.d_tri_inst, xf_new, up.d_wv, up.d_red);
+        else
+            hipLaunchKernelGGL(k_upd_transform<true>, dim3(g256), dim3(256), 0, st, T, pos_new, (const uint32_t*)up.d_idx, (const uint32_t*)up.d_tri_inst, xf_new, up.d_wv, up.d_red);
         ++launches;
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(up.h_red, up.d_red, kRedWords * 8, hipMemcpyDeviceToHost, st));
@@ -291,12 +296,20 @@ int update_device(rt_scene* s, const std::vector<rt_instance>& inst, const rt_sc
         for (int a = 0; a < 3; ++a) lo[a] = key_value(up.h_red[a]), hi[a] = key_value(up.h_red[3 + a]);
         std::string err;
         const bool ok = up.h_red[6] == 0 ? scene_padding(lo, hi, pad, err) : (err = "non-finite world-space vertex", false);
+        if (!ok && up.keep_previous) return fail(RT_ERR_INVALID, err); // refused: nothing was written
         if (!ok) { // refused: the scratch vertices go back to the scene's own, nothing else was written
-            hipLaunchKernelGGL(k_upd_transform, dim3(g256), dim3(256), 0, st, T, (const float*)up.d_pos, (const uint32_t*)up.d_idx,
+            hipLaunchKernelGGL(k_upd_transform<true>, dim3(g256), dim3(256), 0, st, T, (const float*)up.d_pos, (const uint32_t*)up.d_idx,
                                (const uint32_t*)up.d_tri_inst, (const float*)up.d_xf, up.d_wv, up.d_red);
             HIPCHK(hipGetLastError());
             HIPCHK(hipStreamSynchronize(st));
             return fail(RT_ERR_INVALID, err);
+        }
+        if (up.keep_previous) { // accepted: the current vertices become the previous ones (a pointer swap), the new ones are written over the older copy
+            std::swap(up.d_wv, up.d_wv_prev);
+            hipLaunchKernelGGL(k_upd_transform<true>, dim3(g256), dim3(256), 0, st, T, pos_new, (const uint32_t*)up.d_idx, (const uint32_t*)up.d_tri_inst, xf_new, up.d_wv,
+                               up.d_red); // (its reduction repeats the one read above: words 0 .. 6, nobody reads them again)
+            ++launches;
+            HIPCHK(hipGetLastError());
         }
     }
     // phase 2: the update is accepted
@@ -378,7 +391,7 @@ void free_scene_update(rt_scene* s) {
     if (!u) return;
     if (s->device >= 0 && hipSetDevice(s->device) == hipSuccess) {
         for (void* p : {(void*)u->d_pos, (void*)u->d_pos_stage, (void*)u->d_idx, (void*)u->d_tri_inst, (void*)u->d_xf, (void*)u->d_xf_stage,
-                        (void*)u->d_islot, (void*)u->d_wv, (void*)u->d_box, (void*)u->d_levels, (void*)u->d_red})
+                        (void*)u->d_islot, (void*)u->d_wv, (void*)u->d_wv_prev, (void*)u->d_box, (void*)u->d_levels, (void*)u->d_red})
             if (p) (void)hipFree(p);
         if (u->h_red) (void)hipHostFree(u->h_red);
         if (u->ev0) (void)hipEventDestroy(u->ev0);
@@ -389,9 +402,10 @@ void free_scene_update(rt_scene* s) {
     s->upd = nullptr;
 }
 
-int init_scene_update(rt_scene* s, const rt_scene_desc* d) {
+int init_scene_update(rt_scene* s, const rt_scene_desc* d, bool keep_previous) {
     s->upd = new SceneUpdate();
     SceneUpdate& u = *s->upd;
+    u.keep_previous = keep_previous;
     const uint32_t T = d->n_triangles, I = d->n_instances, V = d->n_vertices;
     u.n_vertices = V;
     u.instances.assign(d->instances, d->instances + I);
@@ -422,6 +436,7 @@ int init_scene_update(rt_scene* s, const rt_scene_desc* d) {
     HIPCHK(dev_alloc(&u.d_xf_stage, 16 * (size_t)I, b));
     HIPCHK(dev_alloc(&u.d_islot, I, b));
     HIPCHK(dev_alloc(&u.d_wv, 9 * (size_t)T, b));
+    if (keep_previous && T) HIPCHK(dev_alloc(&u.d_wv_prev, 9 * (size_t)T, b)); // + 36 bytes per triangle
     HIPCHK(dev_alloc(&u.d_box, 6 * n_nodes, b));
     HIPCHK(dev_alloc(&u.d_levels, u.level_nodes.size(), b));
     HIPCHK(dev_alloc(&u.d_red, kRedWords, b));
@@ -434,6 +449,7 @@ int init_scene_update(rt_scene* s, const rt_scene_desc* d) {
         HIPCHK(hipMemcpy(u.d_idx, d->indices, 12 * (size_t)T, hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(u.d_tri_inst, d->tri_instance, 4 * (size_t)T, hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(u.d_wv, s->hs.wverts.data(), 4 * s->hs.wverts.size(), hipMemcpyHostToDevice));
+        if (keep_previous) HIPCHK(hipMemcpy(u.d_wv_prev, s->hs.wverts.data(), 4 * s->hs.wverts.size(), hipMemcpyHostToDevice)); // before the first update previous == current
     }
     if (I) {
         std::vector<float> xf(16 * (size_t)I);

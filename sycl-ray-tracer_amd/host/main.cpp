@@ -11,6 +11,9 @@
 //   --schedule {default,per-sample,per-bounce,per-bounce-fused}   which of the wavefront renderer's schedules renders the frame
 //   --denoise ITER         every image written is denoised after its last pass (rt_scene_gbuffer + rt_denoise, ITER a-trous iterations,
 //                          the default sigmas of rtamd/renderer.py); a tiled frame is denoised on the root device after the gather
+//   --temporal N           with --frames: temporal accumulation. Frame f is rendered with seed salt f (rt_renderer_set_frame_seed), then
+//                          accumulated over the frames before it by reprojection (rt_scene_gbuffer_motion + rt_temporal_accumulate, history
+//                          capped at N frames), then denoised if --denoise is given, then written. One device only.
 //   --frames N --spin DEG  render N frames, every instance turned by DEG more per frame about the vertical axis through the centre of the
 //                          scene's bounds (rt_scene_update between frames: the BVH is refit, not rebuilt); writes OUT_0000.png onwards
 //                          (rt_renderer_set_schedule; per-bounce = the reference's own: src/render_wavefront.cpp:396-417)
@@ -52,6 +55,9 @@ static void usage(const char* argv0) {
                 "  --denoise UINT              denoise every image written with this many a-trous iterations (1 .. 10; default 0 = off),\n"
                 "                              guided by the scene's primary-hit G-buffer (a tiled frame: on the first device, after the\n"
                 "                              gather); prints the G-buffer's and the filter's device time\n"
+                "  --temporal UINT             with --frames > 1: accumulate every frame over the frames before it by reprojection, the history\n"
+                "                              capped at this many frames (1 .. 4096; default 0 = off); every frame gets its own noise (seed salt\n"
+                "                              = frame number); before --denoise; one device only; prints the stage's device times\n"
                 "  --quiet                     No loader chatter\n"
                 "\nThe camera must lie within 100 scene scales of the scene's bounds (scale = largest extent or coordinate): farther out the\n"
                 "conservative box culling of the closest-hit query no longer holds and the frame is refused with an error, not rendered wrong.\n",
@@ -59,7 +65,7 @@ static void usage(const char* argv0) {
 }
 
 int main(int argc, const char* argv[]) {
-    uint32_t max_depth = 10, sample_count = 32, rr = 0, passes = 1, min_samples = 0, frames = 1, denoise = 0;
+    uint32_t max_depth = 10, sample_count = 32, rr = 0, passes = 1, min_samples = 0, frames = 1, denoise = 0, temporal = 0;
     float adaptive = -1.0f; // < 0: off
     double spin = 0.0;      // degrees per frame (--frames)
     std::string scene_path = "./assets/sponza.glb", out_path = "out.png";
@@ -127,6 +133,10 @@ int main(int argc, const char* argv[]) {
             denoise = to_u32("--denoise", need(i));
             if (denoise > 10) { std::fprintf(stderr, "--denoise: expected 0 .. 10 iterations\n"); return 105; }
         }
+        else if (a == "--temporal") {
+            temporal = to_u32("--temporal", need(i));
+            if (temporal > 4096) { std::fprintf(stderr, "--temporal: expected a history of 1 .. 4096 frames (0 = off)\n"); return 105; }
+        }
         else if (a == "--quiet") quiet = true;
         else if (a == "--frames") {
             frames = to_u32("--frames", need(i));
@@ -164,6 +174,8 @@ int main(int argc, const char* argv[]) {
         }
     }
     if (!use_wavefront && !use_megakernel) use_wavefront = true; // src/main.cpp:26-28
+    if (temporal && frames < 2) { std::fprintf(stderr, "--temporal: needs --frames of at least 2\n"); return 105; }
+    if (temporal && devices.size() > 1) { std::fprintf(stderr, "--temporal: one device only (--devices with one entry)\n"); return 105; }
 
     std::printf("Loading scene: %s\n", scene_path.c_str());
     try {
@@ -180,7 +192,7 @@ int main(int argc, const char* argv[]) {
             std::printf("Running on device: HIP device %d of %d (gfx950 path)\n", device, n_dev); // src/app.hpp:51-54
         std::vector<uint8_t> image_buf((size_t)width * (size_t)height * 4);
         if (frames > 1 && devices.size() > 1) throw std::runtime_error("--frames: one device only");
-        raytracer::Scene scene(scene_path, device, bvh, !quiet, frames > 1 ? RT_SCENE_UPDATABLE : 0u);
+        raytracer::Scene scene(scene_path, device, bvh, !quiet, frames > 1 ? (temporal ? RT_SCENE_UPDATABLE | RT_SCENE_KEEP_PREVIOUS : RT_SCENE_UPDATABLE) : 0u);
         raytracer::Camera camera({width, height}, scene.camera_position, scene.camera_direction, scene.camera_focal_length);
         std::unique_ptr<raytracer::IRenderer> renderer;
         if (use_megakernel) {
@@ -191,6 +203,7 @@ int main(int argc, const char* argv[]) {
             r->passes = passes;
             r->adaptive = adaptive, r->min_samples = min_samples;
             r->denoise = denoise;
+            r->temporal = temporal;
             renderer.reset(r);
         } else {
             auto* r = new raytracer::WavefrontRenderer({width, height}, image_buf.data(), max_depth, sample_count);
@@ -200,6 +213,7 @@ int main(int argc, const char* argv[]) {
             r->passes = passes;
             r->adaptive = adaptive, r->min_samples = min_samples;
             r->denoise = denoise;
+            r->temporal = temporal;
             if (schedule_given) r->schedule = schedule, r->has_schedule = true;
             renderer.reset(r);
         }
@@ -209,6 +223,7 @@ int main(int argc, const char* argv[]) {
             char name[32];
             std::snprintf(name, sizeof(name), "_%04u.png", f);
             static_cast<raytracer::HipRendererBase*>(renderer.get())->out_path = stem + name;
+            static_cast<raytracer::HipRendererBase*>(renderer.get())->frame_salt = f; // (used with --temporal only)
             if (f > 0) {
                 const rt_update_stats us = scene.spin(spin * (double)f);
                 std::printf("Frame %u: update %.3f ms on the device (%u launches, %u nodes refit)\n", f, us.device_ms, us.launches, us.refit_nodes);

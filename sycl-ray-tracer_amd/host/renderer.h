@@ -163,6 +163,19 @@ struct HipRendererBase : public IRenderer {
     hipStream_t den_stream = nullptr;
     hipEvent_t den_ev[3] = {nullptr, nullptr, nullptr};
     int den_device = -1;
+    // Extension: temporal > 0 (one device, frames of an animation): every frame is rendered with its own seed salt (frame_salt,
+    // rt_renderer_set_frame_seed) and accumulated over the frames before it (rt_scene_gbuffer_motion_device + rt_temporal_accumulate_device,
+    // max_history = temporal, the defaults of rtamd/renderer.py) before it is denoised (if asked for) and written. The scene must keep its
+    // previous vertices (RT_SCENE_KEEP_PREVIOUS). temporal == 0: salt 0, nothing of this runs.
+    uint32_t temporal = 0;
+    uint32_t frame_salt = 0;
+    rt_temporal* accumulator = nullptr;
+    float* d_tmp_gbuf = nullptr;  // the four planes of the motion G-buffer, W*H*4 floats each
+    float* d_tmp_f32 = nullptr;   // the accumulated frame (what the denoiser reads)
+    uint8_t* d_tmp_u8 = nullptr;  // ... and its unorm8 image
+    hipStream_t tmp_stream = nullptr;
+    hipEvent_t tmp_ev[3] = {nullptr, nullptr, nullptr};
+    int tmp_device = -1;
     std::vector<rt_renderer*> tile_handles;
     rt_comm* comm = nullptr;
     rt_stats last{};
@@ -174,8 +187,11 @@ struct HipRendererBase : public IRenderer {
         rt_comm_destroy(comm);
         rt_renderer_destroy(handle);
         release_denoiser();
+        release_accumulator();
     }
 
+    // the accumulator's defaults (rtamd/renderer.py: TEMPORAL_*)
+    static constexpr float kTemporalPositionFraction = 0.05f, kTemporalCosNormal = 0.9f;
     // the denoiser's defaults (rtamd/renderer.py: DENOISE_*): sigma_position is a fraction of the largest extent of the scene's bounds
     static constexpr float kSigmaColor = 1.0f, kSigmaNormal = 0.25f, kPositionFraction = 0.05f, kSigmaAlbedo = 0.1f;
 
@@ -193,6 +209,55 @@ struct HipRendererBase : public IRenderer {
         denoiser = nullptr, d_gbuf = nullptr, d_den_u8 = nullptr, den_stream = nullptr, den_device = -1;
     }
 
+    void release_accumulator() {
+        if (tmp_device >= 0 && hipSetDevice(tmp_device) == hipSuccess) {
+            if (tmp_stream) (void)hipStreamSynchronize(tmp_stream), (void)hipStreamDestroy(tmp_stream);
+            for (hipEvent_t& e : tmp_ev)
+                if (e) (void)hipEventDestroy(e), e = nullptr;
+            (void)hipFree(d_tmp_gbuf), (void)hipFree(d_tmp_f32), (void)hipFree(d_tmp_u8);
+        }
+        rt_temporal_destroy(accumulator);
+        accumulator = nullptr, d_tmp_gbuf = nullptr, d_tmp_f32 = nullptr, d_tmp_u8 = nullptr, tmp_stream = nullptr, tmp_device = -1;
+    }
+
+    static float scene_scale(rt_scene* sc) { // the largest extent of the scene's bounds (rtamd/renderer.py: Scene.scale)
+        rt_scene_info_t info{};
+        rt_check(rt_scene_info(sc, &info));
+        float scale = 0.0f;
+        for (int a = 0; a < 3; ++a) scale = std::max(scale, info.bounds_hi[a] - info.bounds_lo[a]);
+        return scale;
+    }
+
+    // d_frame (this frame's fp32 image, W x H, on `dev`) accumulated over the frames before it; returns the accumulated fp32 frame (on the device)
+    // and leaves its unorm8 image in `image`. Prints the device time of the motion G-buffer and of the accumulation (hipEvents on one stream).
+    const float* accumulate_image(const Camera& camera, rt_scene* sc, int dev, const void* d_frame) {
+        const size_t n = (size_t)img_size[0] * (size_t)img_size[1];
+        hip_check(hipSetDevice(dev), "hipSetDevice");
+        if (!accumulator) {
+            tmp_device = dev;
+            rt_check(rt_temporal_create(dev, img_size[0], img_size[1], &accumulator));
+            hip_check(hipMalloc((void**)&d_tmp_gbuf, 4 * n * 16), "hipMalloc");
+            hip_check(hipMalloc((void**)&d_tmp_f32, n * 16), "hipMalloc");
+            hip_check(hipMalloc((void**)&d_tmp_u8, n * 4), "hipMalloc");
+            hip_check(hipStreamCreateWithFlags(&tmp_stream, hipStreamNonBlocking), "hipStreamCreate");
+            for (hipEvent_t& e : tmp_ev) hip_check(hipEventCreate(&e), "hipEventCreate");
+        }
+        const rt_temporal_params p{temporal, kTemporalPositionFraction * scene_scale(sc), kTemporalCosNormal};
+        float* g = d_tmp_gbuf;
+        hip_check(hipEventRecord(tmp_ev[0], tmp_stream), "hipEventRecord");
+        rt_check(rt_scene_gbuffer_motion_device(sc, &camera.c, g, g + 4 * n, g + 8 * n, g + 12 * n, tmp_stream));
+        hip_check(hipEventRecord(tmp_ev[1], tmp_stream), "hipEventRecord");
+        rt_check(rt_temporal_accumulate_device(accumulator, &p, &camera.c, d_frame, g + 4 * n, g + 8 * n, g + 12 * n, d_tmp_f32, d_tmp_u8, nullptr, tmp_stream));
+        hip_check(hipEventRecord(tmp_ev[2], tmp_stream), "hipEventRecord");
+        hip_check(hipStreamSynchronize(tmp_stream), "hipStreamSynchronize");
+        float g_ms = 0.0f, a_ms = 0.0f;
+        hip_check(hipEventElapsedTime(&g_ms, tmp_ev[0], tmp_ev[1]), "hipEventElapsedTime");
+        hip_check(hipEventElapsedTime(&a_ms, tmp_ev[1], tmp_ev[2]), "hipEventElapsedTime");
+        hip_check(hipMemcpy(image, d_tmp_u8, n * 4, hipMemcpyDeviceToHost), "hipMemcpy");
+        std::printf("Temporal: max history %u, motion G-buffer %.3f ms, accumulation %.3f ms on device %d\n", temporal, g_ms, a_ms, dev);
+        return d_tmp_f32;
+    }
+
     // d_frame (the last pass's fp32 frame, W x H, on `dev`) -> `image`, denoised with the G-buffer of `sc` (the scene on `dev`); prints the device
     // time of the G-buffer and of the filter (hipEvents on one stream). The frame is complete when this is called: every render call before it returns
     // with its frame on the device.
@@ -208,10 +273,7 @@ struct HipRendererBase : public IRenderer {
             hip_check(hipStreamCreateWithFlags(&den_stream, hipStreamNonBlocking), "hipStreamCreate");
             for (hipEvent_t& e : den_ev) hip_check(hipEventCreate(&e), "hipEventCreate");
         }
-        rt_scene_info_t info{};
-        rt_check(rt_scene_info(sc, &info));
-        float scale = 0.0f;
-        for (int a = 0; a < 3; ++a) scale = std::max(scale, info.bounds_hi[a] - info.bounds_lo[a]);
+        const float scale = scene_scale(sc);
         const rt_denoise_params p{denoise, kSigmaColor, kSigmaNormal, kPositionFraction * scale, kSigmaAlbedo};
         hip_check(hipEventRecord(den_ev[0], den_stream), "hipEventRecord");
         rt_check(rt_scene_gbuffer_device(sc, &camera.c, d_gbuf, d_gbuf + 4 * n, d_gbuf + 8 * n, den_stream));
@@ -310,12 +372,13 @@ struct HipRendererBase : public IRenderer {
             bound = &scene;
         }
         rt_check(rt_renderer_set_russian_roulette(handle, russian_roulette));
+        if (temporal) rt_check(rt_renderer_set_frame_seed(handle, frame_salt));
         if (passes > 1) rt_check(rt_renderer_set_progressive(handle, 1));
         if (kind == RT_RENDERER_WAVEFRONT)
             for (uint32_t s = 0; s < sample_count * passes; ++s) std::printf("Sample %u\n", s); // src/render_wavefront.cpp:402
         // (a host fp32 pointer makes the renderer write its own device copy of the frame, rt_renderer_tile_f32, which the denoiser reads)
-        if (denoise) frame_f32.resize((size_t)img_size[0] * (size_t)img_size[1] * 4);
-        float* f32 = denoise ? frame_f32.data() : nullptr;
+        if (denoise || temporal) frame_f32.resize((size_t)img_size[0] * (size_t)img_size[1] * 4);
+        float* f32 = denoise || temporal ? frame_f32.data() : nullptr;
         rt_check(rt_render_frame(handle, &camera.c, f32, image, &last));
         for (uint32_t p = 1; p < passes; ++p) { // the image of the last pass holds all sample_count x passes samples
             rt_stats more{};
@@ -323,7 +386,9 @@ struct HipRendererBase : public IRenderer {
             else rt_check(rt_render_frame_continue(handle, sample_count, f32, image, &more));
             add_stats(last, more);
         }
-        if (denoise) denoise_image(camera, scene.handle, scene.device, rt_renderer_tile_f32(handle)); // the renderer's own copy of the frame
+        const void* d_frame = rt_renderer_tile_f32(handle); // the renderer's own copy of the frame
+        if (temporal) d_frame = accumulate_image(camera, scene.handle, scene.device, d_frame);
+        if (denoise) denoise_image(camera, scene.handle, scene.device, d_frame);
         report_and_write(last.device_ms * 1e-3);
     }
 

@@ -23,6 +23,7 @@ RT_SEED_DEFAULT, RT_SEED_WAVEFRONT, RT_SEED_MEGAKERNEL = 0, 1, 2
 RT_BVH_DEFAULT, RT_BVH_LBVH, RT_BVH_SAH, RT_BVH_LBVH_GPU = 0, 1, 2, 3
 RT_BVH_MEDIAN_INTERNAL = 99  # not a request: what rt_dev_scene_tree reports after a builder fell back to the balanced host tree
 RT_SCENE_UPDATABLE = 1
+RT_SCENE_KEEP_PREVIOUS = 2
 RT_TEX_SIZE = 512
 RT_TEX_MAX_LAYERS = 128
 
@@ -162,6 +163,14 @@ class rt_denoise_params(C.Structure):
     ]
 
 
+class rt_temporal_params(C.Structure):
+    _fields_ = [
+        ("max_history", C.c_uint32),
+        ("sigma_position", C.c_float),
+        ("cos_normal", C.c_float),
+    ]
+
+
 RT_QUERY_CLOSEST, RT_QUERY_ANY = 0, 1
 RT_TRI_REJECTED = 0xFFFFFFFE
 
@@ -183,6 +192,7 @@ class rt_ray_query(C.Structure):
 
 assert C.sizeof(rt_ray_query) == 72
 assert C.sizeof(rt_denoise_params) == 20
+assert C.sizeof(rt_temporal_params) == 12
 assert C.sizeof(rt_material) == 44
 assert C.sizeof(rt_instance) == 104
 assert C.sizeof(rt_camera) == 56
@@ -211,6 +221,7 @@ PROTOTYPES = {
     "rt_renderer_global_row": (C.c_int32, [C.c_void_p, C.c_int32]),
     "rt_renderer_set_profiling": (C.c_int, [C.c_void_p, C.c_int]),
     "rt_renderer_set_russian_roulette": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "rt_renderer_set_frame_seed": (C.c_int, [C.c_void_p, C.c_uint32]),
     "rt_renderer_set_schedule": (C.c_int, [C.c_void_p, _P(rt_schedule)]),
     "rt_renderer_get_schedule": (C.c_int, [C.c_void_p, _P(rt_schedule)]),
     "rt_render_frame_begin": (C.c_int, [C.c_void_p, C.POINTER(rt_camera), C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -235,6 +246,15 @@ PROTOTYPES = {
     "rt_renderer_block_errors": (C.c_int, [C.c_void_p, _P(C.c_float)]),
     "rt_scene_gbuffer": (C.c_int, [C.c_void_p, _P(rt_camera), _P(C.c_float), _P(C.c_float), _P(C.c_float)]),
     "rt_scene_gbuffer_device": (C.c_int, [C.c_void_p, _P(rt_camera), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_scene_gbuffer_motion": (C.c_int, [C.c_void_p, _P(rt_camera), _P(C.c_float), _P(C.c_float), _P(C.c_float), _P(C.c_float)]),
+    "rt_scene_gbuffer_motion_device": (C.c_int, [C.c_void_p, _P(rt_camera), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_temporal_create": (C.c_int, [C.c_int, C.c_int32, C.c_int32, _P(C.c_void_p)]),
+    "rt_temporal_destroy": (None, [C.c_void_p]),
+    "rt_temporal_reset": (C.c_int, [C.c_void_p]),
+    "rt_temporal_accumulate": (C.c_int, [C.c_void_p, _P(rt_temporal_params), _P(rt_camera), _P(C.c_float), _P(C.c_float), _P(C.c_float),
+                                         _P(C.c_float), _P(C.c_float), _P(C.c_uint8), _P(C.c_float)]),
+    "rt_temporal_accumulate_device": (C.c_int, [C.c_void_p, _P(rt_temporal_params), _P(rt_camera), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rt_denoiser_create": (C.c_int, [C.c_int, C.c_int32, C.c_int32, _P(C.c_void_p)]),
     "rt_denoiser_destroy": (None, [C.c_void_p]),
     "rt_denoise": (C.c_int, [C.c_void_p, _P(rt_denoise_params), _P(C.c_float), _P(C.c_float), _P(C.c_float), _P(C.c_float),

@@ -38,16 +38,19 @@ class Camera:
 class Scene:
     """Device-resident scene: == what raytracer::Scene hands the kernels (RTCScene + GeometryData)."""
 
-    def __init__(self, desc: SceneDesc, device: int = 0, bvh: int = abi.RT_BVH_DEFAULT, lib=None, updatable: bool = False):
+    def __init__(self, desc: SceneDesc, device: int = 0, bvh: int = abi.RT_BVH_DEFAULT, lib=None, updatable: bool = False,
+                 keep_previous: bool = False):
         """`lib`: another build of the library (abi.load_developer_library()); renderers of this scene use the same one.
-        `updatable`: rt_scene_create_ex with RT_SCENE_UPDATABLE, so that update() can move instances and vertices."""
+        `updatable`: rt_scene_create_ex with RT_SCENE_UPDATABLE, so that update() can move instances and vertices. `keep_previous`: RT_SCENE_KEEP_PREVIOUS on
+        top (needs `updatable`): the scene keeps its vertices of before the last update, what gbuffer_motion() reads."""
         self.desc = desc
         self.device = device
         self._lib = lib or abi.load_library()
         self._c = desc.to_c()
         self.h = C.c_void_p()
-        if updatable:
-            abi.check(self._lib.rt_scene_create_ex(C.byref(self._c), device, bvh, abi.RT_SCENE_UPDATABLE, C.byref(self.h)), self._lib)
+        if updatable or keep_previous:
+            flags = (abi.RT_SCENE_UPDATABLE if updatable else 0) | (abi.RT_SCENE_KEEP_PREVIOUS if keep_previous else 0)
+            abi.check(self._lib.rt_scene_create_ex(C.byref(self._c), device, bvh, flags, C.byref(self.h)), self._lib)
         else:
             abi.check(self._lib.rt_scene_create(C.byref(self._c), device, bvh, C.byref(self.h)), self._lib)
 
@@ -145,6 +148,20 @@ class Scene:
         """rt_scene_gbuffer_device: the three planes into DEVICE buffers of H*W*4 floats (e.g. torch .data_ptr()), enqueued on `stream`."""
         abi.check(self._lib.rt_scene_gbuffer_device(self.h, C.byref(camera.c), C.c_void_p(d_albedo or None), C.c_void_p(d_normal or None),
                                                     C.c_void_p(d_position or None), C.c_void_p(stream or None)), self._lib)
+
+    def gbuffer_motion(self, camera: Camera) -> dict:
+        """rt_scene_gbuffer_motion: gbuffer()'s three planes plus "prev_position", where every visible surface point was before the scene's
+        last update (w = 1; zeros on a miss). The scene must have been created with keep_previous."""
+        w, h = int(camera.c.width), int(camera.c.height)
+        out = {k: np.zeros((max(h, 0), max(w, 0), 4), np.float32) for k in ("albedo", "normal", "position", "prev_position")}
+        abi.check(self._lib.rt_scene_gbuffer_motion(self.h, C.byref(camera.c), abi.fptr(out["albedo"]), abi.fptr(out["normal"]),
+                                                    abi.fptr(out["position"]), abi.fptr(out["prev_position"])), self._lib)
+        return out
+
+    def gbuffer_motion_device(self, camera: Camera, d_albedo: int, d_normal: int, d_position: int, d_prev_position: int, stream: int = 0) -> None:
+        """rt_scene_gbuffer_motion_device: the four planes into DEVICE buffers of H*W*4 floats, enqueued on `stream`."""
+        v = [C.c_void_p(x or None) for x in (d_albedo, d_normal, d_position, d_prev_position, stream)]
+        abi.check(self._lib.rt_scene_gbuffer_motion_device(self.h, C.byref(camera.c), *v), self._lib)
 
     def scale(self) -> np.float32:
         """The largest extent of the scene's bounds (rt_scene_info), fp32: what the denoiser's default sigma_position is a fraction of."""
@@ -267,6 +284,11 @@ class IRenderer:
     def set_russian_roulette(self, start_bounce: int) -> None:
         """Extension (a to-do upstream: PLAN.md:23-27): paths are thinned from bounce `start_bounce` on; 0 = off (default)."""
         abi.check(self._lib.rt_renderer_set_russian_roulette(self.h, int(start_bounce)), self._lib)
+
+    def set_frame_seed(self, salt: int) -> None:
+        """rt_renderer_set_frame_seed: the frames begun from now on start every pixel's chain at pixel_seed + salt * 0x9E3779B9 (0: the
+        reference's seeds). An animation passes its frame number, so that its frames' noise is independent."""
+        abi.check(self._lib.rt_renderer_set_frame_seed(self.h, int(salt) & 0xFFFFFFFF), self._lib)
 
     def set_schedule(self, finish_depth: int = 0, samples_per_launch: int = 0, stream_lanes: int = 0, requeue: int = -1,
                      reorder: bool = False, matsort: bool = False, cost_order: int = -1, hip_graph: bool = False,
@@ -574,6 +596,75 @@ class Denoiser:
     def close(self):
         if self.h:
             self._lib.rt_denoiser_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+# The temporal accumulator's defaults. sigma_position is TEMPORAL_POSITION_FRACTION of the scene's scale (Scene.scale()), as the
+# denoiser's; host/main.cpp's --temporal uses the same values.
+TEMPORAL_MAX_HISTORY = 32
+TEMPORAL_POSITION_FRACTION = 0.05
+TEMPORAL_COS_NORMAL = 0.9
+
+
+def temporal_params(max_history: int = TEMPORAL_MAX_HISTORY, sigma_position: float | None = None, cos_normal: float = TEMPORAL_COS_NORMAL,
+                    scene_scale: float | None = None):
+    """rt_temporal_params; sigma_position None: TEMPORAL_POSITION_FRACTION * scene_scale, in fp32 (scene_scale is then required)."""
+    if sigma_position is None:
+        if scene_scale is None:
+            raise ValueError("sigma_position or scene_scale is required")
+        sigma_position = np.float32(TEMPORAL_POSITION_FRACTION) * np.float32(scene_scale)
+    return abi.rt_temporal_params(int(max_history), float(sigma_position), float(cos_normal))
+
+
+class TemporalAccumulator:
+    """rt_temporal: temporal accumulation by reprojection for W x H frames on one device, guided by Scene.gbuffer_motion's planes."""
+
+    def __init__(self, device: int, width: int, height: int, lib=None):
+        self._lib = lib or abi.load_library()
+        self.width, self.height = int(width), int(height)
+        self.h = C.c_void_p()
+        abi.check(self._lib.rt_temporal_create(int(device), self.width, self.height, C.byref(self.h)), self._lib)
+
+    def accumulate(self, frame_f32: np.ndarray, gbuf: dict, camera: Camera, want_f32: bool = True, want_u8: bool = True,
+                   out_f32: np.ndarray | None = None, **params):
+        """rt_temporal_accumulate of a (H, W, 4) float32 frame rendered with `camera`, with the planes of Scene.gbuffer_motion(camera); returns
+        (f32, u8, history_len (H, W) float32), None for an image not asked for. `params`: max_history, sigma_position, cos_normal, scene_scale
+        (temporal_params). out_f32: where the fp32 result goes (may be frame_f32)."""
+        p = temporal_params(**params)
+        shape = (self.height, self.width, 4)
+        frame_f32 = np.ascontiguousarray(frame_f32, np.float32)
+        planes = [np.ascontiguousarray(gbuf[k], np.float32) for k in ("normal", "position", "prev_position")]
+        for a in [frame_f32] + planes:
+            if a.shape != shape:
+                raise ValueError(f"expected {shape}, got {a.shape}")
+        f = (out_f32 if out_f32 is not None else np.zeros(shape, np.float32)) if want_f32 else None
+        b = np.zeros(shape, np.uint8) if want_u8 else None
+        n = np.zeros(shape[:2], np.float32)
+        abi.check(self._lib.rt_temporal_accumulate(self.h, C.byref(p), C.byref(camera.c), abi.fptr(frame_f32), *(abi.fptr(a) for a in planes),
+                                                   abi.fptr(f) if f is not None else None, abi.u8ptr(b) if b is not None else None,
+                                                   abi.fptr(n)), self._lib)
+        return f, b, n
+
+    def accumulate_device(self, camera: Camera, d_frame: int, d_normal: int, d_position: int, d_prev_position: int, d_out_f32: int = 0,
+                          d_out_u8: int = 0, d_history_len: int = 0, stream: int = 0, **params) -> None:
+        """rt_temporal_accumulate_device on DEVICE pointers (e.g. torch .data_ptr()), enqueued on `stream`."""
+        p = temporal_params(**params)
+        v = [C.c_void_p(x or None) for x in (d_frame, d_normal, d_position, d_prev_position, d_out_f32, d_out_u8, d_history_len, stream)]
+        abi.check(self._lib.rt_temporal_accumulate_device(self.h, C.byref(p), C.byref(camera.c), *v), self._lib)
+
+    def reset(self) -> None:
+        """rt_temporal_reset: forget the history; the next call passes its frame through."""
+        abi.check(self._lib.rt_temporal_reset(self.h), self._lib)
+
+    def close(self):
+        if self.h:
+            self._lib.rt_temporal_destroy(self.h)
             self.h = C.c_void_p()
 
     def __del__(self):

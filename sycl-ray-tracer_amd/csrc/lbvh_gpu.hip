@@ -153,11 +153,11 @@ __global__ void __launch_bounds__(128) k_emit(uint32_t n_in, const int2* __restr
     Box3 kb[4];
     for (int k = 0; k < nk; ++k) kb[k] = kids[k] >= 0 ? node_box[kids[k]] : tri_box[sorted_tri[~kids[k]]];
     BvhNode out;
-    if (!quantise_node_dev(out, nk, kb, pad)) atomicOr(failed, 1u); // the host turns it into an error after the level
+    if (!quantise_node(out, nk, kb, pad)) atomicOr(failed, 1u); // the host turns it into an error after the level
     for (int k = 0; k < 4; ++k) {
         if (k >= nk) { out.child[k] = kChildEmpty; continue; }
         if (kids[k] < 0) {
-            out.child[k] = ~(int32_t)(((uint32_t)~kids[k] << 2) | 0u); // leaf: one triangle at its Morton position
+            out.child[k] = leaf_child((uint32_t)~kids[k], 1u); // leaf: one triangle at its Morton position
         } else {
             const unsigned int idx = atomicAdd(node_counter, 1u);
             out.child[k] = (int32_t)idx;

@@ -1,5 +1,6 @@
 // rt_abi.hip — the C entry points of include/rt_mi355x.h for scenes, renderers and frames: argument checks and object life time. What a frame
 // launches is rt_frame.hip; the gather rt_comm.hip; the probes rt_probes.hip.
+#include "bvh_quantise.h"
 #include "rt_internal.h"
 
 namespace rtlib {
@@ -128,11 +129,7 @@ int rt_scene_create_ex(const rt_scene_desc* desc, int device, int bvh_kind, uint
         const bool stage = s->hs.packed_mat && s->hs.n_layers <= 65536u; // (the staged material keeps its layer in 16 bits)
         s->dev.lds_nm = stage ? (uint32_t)std::min<size_t>(s->hs.inst.size(), kLdsNm) : 0u;
         s->dev.lds_mats = stage ? (uint32_t)std::min<size_t>(s->hs.mats.size(), kLdsMats) : 0u;
-        for (int a = 0; a < 3; ++a) {
-            const float ext = s->hs.bounds_hi[a] - s->hs.bounds_lo[a];
-            s->dev.cell_lo[a] = s->hs.bounds_lo[a];
-            s->dev.cell_scale[a] = ext > 0.0f && std::isfinite(ext) ? 4.0f / ext : 0.0f;
-        }
+        scene_cells(s->hs, s->dev);
     }
     if (flags & RT_SCENE_UPDATABLE) {
         rc = no_throw([&] { return init_scene_update(s, desc, (flags & RT_SCENE_KEEP_PREVIOUS) != 0); });
@@ -514,19 +511,19 @@ int rt_dev_renderer_graph_captures(const rt_renderer* r, uint32_t* out) {
     return RT_OK;
 }
 
-// Host only: the host quantiser (scene_build.cpp: quantise_node) on `count` nodes. nk[i] in 1..4 children; klo/khi: 4 x 3 floats per node,
-// the children's already padded boxes (entries past nk[i] are ignored); nodes_out: count 64-byte BvhNode records (origin, scales and
-// planes; child words kChildEmpty); ok[i] = 0 where quantise_node refused the node (a non-finite box or no grid step that fits).
+// Host only: the quantiser (bvh_quantise.h: quantise_node) as the host runs it, on `count` nodes. nk[i] in 1..4 children; klo/khi: 4 x 3
+// floats per node, the children's already padded boxes (entries past nk[i] are ignored; pad = 0 here, and x - 0 and x + 0 keep every x the
+// quantiser stores, -0 included); nodes_out: count 64-byte BvhNode records (origin, scales and planes; child words kChildEmpty); ok[i] = 0
+// where quantise_node refused the node (a non-finite box or no grid step that fits).
 int rt_dev_quantise_node(uint32_t count, const int32_t* nk, const float* klo, const float* khi, void* nodes_out, uint8_t* ok) {
     if (!nk || !klo || !khi || !nodes_out || !ok) return fail(RT_ERR_INVALID, "null argument");
     BvhNode* out = static_cast<BvhNode*>(nodes_out);
     for (uint32_t i = 0; i < count; ++i) {
         if (nk[i] < 1 || nk[i] > 4) return fail(RT_ERR_INVALID, "nk must be 1..4");
-        BvhNode n{};
-        for (int k = 0; k < 4; ++k) n.child[k] = kChildEmpty;
-        ok[i] = quantise_node_dev_export(n, nk[i], reinterpret_cast<const float(*)[3]>(klo + 12 * (size_t)i),
-                                         reinterpret_cast<const float(*)[3]>(khi + 12 * (size_t)i)) ? 1 : 0;
-        out[i] = n;
+        Box3 kb[4];
+        for (int k = 0; k < 4; ++k) std::memcpy(kb[k].lo, klo + 12 * (size_t)i + 3 * k, 12), std::memcpy(kb[k].hi, khi + 12 * (size_t)i + 3 * k, 12);
+        out[i] = empty_node();
+        ok[i] = quantise_node(out[i], nk[i], kb, 0.0f) ? 1 : 0;
     }
     return RT_OK;
 }

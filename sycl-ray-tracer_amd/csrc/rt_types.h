@@ -1,5 +1,5 @@
 // rt_types.h — data layouts of the device-resident scene and of the kernel parameter block.
-// Shared by the host builder (scene_build.cpp) and the HIP kernels (rt_kernels.h, rt_device.h).
+// Shared by the host builder (scene_build.cpp, scene_check.cpp) and the HIP kernels (rt_kernels.h, rt_device.h).
 #pragma once
 #include <cstdint>
 
@@ -19,17 +19,55 @@ namespace rt {
 //  node visit on a VALU-bound kernel — profiles/r02_valu_calibration.json — and the two spare words were there.)
 // child >= 0: index of an inner node.  child < 0: leaf, ~child = (first << 2) | (count - 1), with
 // `first` indexing the leaf-ordered triangle array and 1 <= count <= 4.  child == kChildEmpty: absent.
+#ifdef __HIPCC__
+#define RT_HD __host__ __device__ inline
+#else
+#define RT_HD inline
+#endif
 struct alignas(64) BvhNode {
     float origin[3];
     float scale_x;
     uint32_t q[6]; // qlo_x, qhi_x, qlo_y, qhi_y, qlo_z, qhi_z
     float scale_y, scale_z;
     int32_t child[4];
-    float scale(int a) const { const float s = a == 0 ? scale_x : (a == 1 ? scale_y : scale_z); return s < 0.0f ? -s : s; }
-    void set_scale(int a, float s) { (a == 0 ? scale_x : (a == 1 ? scale_y : scale_z)) = s; }
+    RT_HD float scale(int a) const { const float s = a == 0 ? scale_x : (a == 1 ? scale_y : scale_z); return s < 0.0f ? -s : s; }
+    RT_HD void set_scale(int a, float s) { (a == 0 ? scale_x : (a == 1 ? scale_y : scale_z)) = s; }
 };
 static_assert(sizeof(BvhNode) == 64, "BvhNode must be 64 bytes");
 constexpr int32_t kChildEmpty = (int32_t)0x80000000;
+struct Box3 {
+    float lo[3], hi[3];
+};
+
+// The tree's encoding rules, each written once. Words 0..11 of a node without children: the unit grid at the origin, every plane pair
+// inverted (qlo = 255, qhi = 0), a miss for every ray inside the contract's range (rt_device.h: trav_inner).
+RT_HD void clear_planes(BvhNode& n) {
+    n.scale_x = n.scale_y = n.scale_z = 1.0f;
+    n.origin[0] = n.origin[1] = n.origin[2] = 0.0f;
+    for (int i = 0; i < 6; ++i) n.q[i] = (i & 1) ? 0u : 0xFFFFFFFFu;
+}
+RT_HD BvhNode empty_node() {
+    BvhNode n;
+    clear_planes(n);
+    for (int k = 0; k < 4; ++k) n.child[k] = kChildEmpty;
+    return n;
+}
+// a leaf child word <-> its records [first, first + count) of the leaf-ordered triangle array
+struct LeafRange {
+    uint32_t first, count;
+};
+RT_HD LeafRange leaf_range(int32_t child) {
+    const uint32_t code = (uint32_t)~child;
+    return {code >> 2, (code & 3u) + 1u};
+}
+RT_HD int32_t leaf_child(uint32_t first, uint32_t count) { return ~(int32_t)((first << 2) | (count - 1)); }
+// the box the kernels test for child k: its quantised planes decoded (side 0: the low plane of axis a, 1: the high one)
+RT_HD float child_plane(const BvhNode& n, int k, int a, int side) { return n.origin[a] + (float)((n.q[2 * a + side] >> (8 * k)) & 0xffu) * n.scale(a); }
+RT_HD Box3 child_box(const BvhNode& n, int k) {
+    Box3 b;
+    for (int a = 0; a < 3; ++a) b.lo[a] = child_plane(n, k, a, 0), b.hi[a] = child_plane(n, k, a, 1);
+    return b;
+}
 
 // In the DEVICE copy of the node array a child word >= 0 is the child node's BYTE offset (index * 64), so that the inner step
 // addresses the node with no arithmetic of its own — a 32-bit offset on the scalar base for global memory (the index form cost a
@@ -44,11 +82,6 @@ constexpr float kTNear = 0.0001f;   // RayData::to_embree tnear (src/camera.hpp:
 // What the origin test needs of a scene (rt_frame.hip: contract_range): the bounds and the limit, kContractRange scene scales; finite_only
 // when nothing could be culled wrongly (no geometry, or all of it in the origin). One predicate for the host entry points and the query
 // kernel (rt_query.hip), written with std::max's operand order so that both evaluate the same fp32 operations with the same NaN outcome.
-#ifdef __HIPCC__
-#define RT_HD __host__ __device__ inline
-#else
-#define RT_HD inline
-#endif
 struct ContractRange {
     float lo[3], hi[3];
     float limit;

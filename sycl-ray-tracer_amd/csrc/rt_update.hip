@@ -3,7 +3,7 @@
 //
 // An update keeps the BVH's topology (child words, leaf codes, node order) and recomputes everything geometric in place, in two phases:
 //   1. k_upd_transform: every triangle's world-space vertices, with the host builder's expression ((m0*x + m4*y) + m8*z) + m12
-//      (scene_build.cpp, -ffp-contract=off), into the scratch array `wv`; in the same pass the scene's bounds as ordered keys that also
+//      (scene_build.cpp: world_vertices, -ffp-contract=off), into the scratch array `wv`; in the same pass the scene's bounds as ordered keys that also
 //      carry the first occurrence (the host's std::min / std::max keep the first of equal values: the sign of a zero bound depends on it)
 //      and a non-finite flag. The host reads back 7 words and applies rt_scene_create's test. A refusal restores `wv` and stops here:
 //      nothing else of the scene has been written.
@@ -127,9 +127,9 @@ __global__ void __launch_bounds__(128) k_upd_refit(uint32_t n, const uint32_t* _
         if (c >= 0) {
             kb[k] = box[(uint32_t)c / 64u]; // (the device's child words are byte offsets)
         } else {
-            const uint32_t code = (uint32_t)~c, first = code >> 2, count = (code & 3u) + 1u;
+            const LeafRange leaf = leaf_range(c);
             for (int a = 0; a < 3; ++a) kb[k].lo[a] = INFINITY, kb[k].hi[a] = -INFINITY;
-            for (uint32_t r = first; r < first + count; ++r) {
+            for (uint32_t r = leaf.first; r < leaf.first + leaf.count; ++r) {
                 const uint32_t g = *reinterpret_cast<const uint32_t*>(tris + (size_t)r * kTriBytes + 36);
                 const float* w = wv + 9 * (size_t)g;
                 for (int a = 0; a < 3; ++a) {
@@ -145,7 +145,7 @@ __global__ void __launch_bounds__(128) k_upd_refit(uint32_t n, const uint32_t* _
         for (int a = 0; a < 3; ++a) u.lo[a] = fminf(u.lo[a], kb[k].lo[a]), u.hi[a] = fmaxf(u.hi[a], kb[k].hi[a]);
     box[ni] = u;
     BvhNode q;
-    if (!quantise_node_dev(q, nk, kb, pad)) atomicOr(failed, 1ull);
+    if (!quantise_node(q, nk, kb, pad)) atomicOr(failed, 1ull);
     for (int k = 0; k < 4; ++k) q.child[k] = nd.child[k];
     nodes[ni] = q;
 }
@@ -185,14 +185,6 @@ uint32_t shading_word(const rt_scene* s, uint32_t inst) {
     return s->hs.packed_mat ? (u.inst_slot[inst] | (u.instances[inst].material << kPackedInstBits)) : inst;
 }
 
-void set_cells(rt_scene* s) { // as rt_scene_create sets them
-    for (int a = 0; a < 3; ++a) {
-        const float ext = s->hs.bounds_hi[a] - s->hs.bounds_lo[a];
-        s->dev.cell_lo[a] = s->hs.bounds_lo[a];
-        s->dev.cell_scale[a] = ext > 0.0f && std::isfinite(ext) ? 4.0f / ext : 0.0f;
-    }
-}
-
 // the new instance table; returns whether any instance's row moved
 bool regroup(rt_scene* s, const std::vector<rt_instance>& inst, std::vector<InstRec>& rows, std::vector<uint32_t>& slot) {
     shading_rows(inst.data(), (uint32_t)inst.size(), s->upd->inst_use, s->hs.packed_mat, rows, slot);
@@ -205,29 +197,11 @@ int update_host(rt_scene* s, const std::vector<rt_instance>& inst, const rt_scen
     HostScene& hs = s->hs;
     const uint32_t T = (uint32_t)up.tri_instance.size();
     const float* pos = (u->n_vertices && u->positions) ? u->positions : up.positions.data();
-    std::vector<float> wv(9 * (size_t)T);
-    for (uint32_t t = 0; t < T; ++t) {
-        const float* m = inst[up.tri_instance[t]].transform;
-        for (int k = 0; k < 3; ++k) {
-            const uint32_t vi = up.indices[3 * (size_t)t + k];
-            const float x = pos[3 * (size_t)vi], y = pos[3 * (size_t)vi + 1], z = pos[3 * (size_t)vi + 2];
-            wv[9 * (size_t)t + 3 * k + 0] = ((m[0] * x + m[4] * y) + m[8] * z) + m[12];
-            wv[9 * (size_t)t + 3 * k + 1] = ((m[1] * x + m[5] * y) + m[9] * z) + m[13];
-            wv[9 * (size_t)t + 3 * k + 2] = ((m[2] * x + m[6] * y) + m[10] * z) + m[14];
-        }
-    }
+    std::vector<float> wv;
+    world_vertices(T, up.indices.data(), up.tri_instance.data(), inst.data(), pos, wv);
     float lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0}, pad = hs.pad;
-    if (T) {
-        for (size_t i = 0; i < wv.size(); ++i)
-            if (!std::isfinite(wv[i])) return fail(RT_ERR_INVALID, "non-finite world-space vertex");
-        for (int a = 0; a < 3; ++a) lo[a] = INFINITY, hi[a] = -INFINITY;
-        for (size_t i = 0; i < wv.size(); ++i) {
-            const int a = (int)(i % 3);
-            lo[a] = std::min(lo[a], wv[i]), hi[a] = std::max(hi[a], wv[i]);
-        }
-        std::string err;
-        if (!scene_padding(lo, hi, pad, err)) return fail(RT_ERR_INVALID, err);
-    }
+    std::string err;
+    if (T && !world_bounds(wv, lo, hi, pad, err)) return fail(RT_ERR_INVALID, err);
     // accepted: from here on the scene changes
     HostScene next = hs; // (a quantisation failure below leaves the scene as it was)
     if (T) {
@@ -235,7 +209,6 @@ int update_host(rt_scene* s, const std::vector<rt_instance>& inst, const rt_scen
         std::memcpy(next.bounds_lo, lo, 12), std::memcpy(next.bounds_hi, hi, 12);
         next.pad = pad;
         std::vector<float> box;
-        std::string err;
         if (!refit_host(next, up.level_nodes, box, err)) return fail(RT_ERR_INVALID, err);
     }
     std::vector<InstRec> rows;
@@ -373,7 +346,7 @@ int update_device(rt_scene* s, const std::vector<rt_instance>& inst, const rt_sc
     if (T) {
         std::memcpy(hs.bounds_lo, lo, 12), std::memcpy(hs.bounds_hi, hi, 12);
         hs.pad = pad;
-        set_cells(s);
+        scene_cells(hs, s->dev);
     }
     up.host_stale = true;
     if (stats) stats->device_ms = (double)ms, stats->launches = launches, stats->refit_nodes = refit_nodes;
@@ -485,13 +458,7 @@ int sync_host_copy(const rt_scene* cs) {
         hs.nodes.swap(nodes);
         hs.wverts.swap(wv);
         hs.shade.swap(shade);
-        hs.rec_lo.assign(3 * hs.tris.size(), 0.0f), hs.rec_hi.assign(3 * hs.tris.size(), 0.0f);
-        for (size_t r = 0; r < hs.tris.size(); ++r) {
-            if (hs.tris[r].global_index == kNoTri) continue;
-            const float* w = &hs.wverts[9 * (size_t)hs.tris[r].global_index];
-            for (int a = 0; a < 3; ++a)
-                hs.rec_lo[3 * r + a] = std::min(w[a], std::min(w[3 + a], w[6 + a])), hs.rec_hi[3 * r + a] = std::max(w[a], std::max(w[3 + a], w[6 + a]));
-        }
+        record_boxes(hs);
         if (!hs.wverts.empty()) hs.sah_cost = refit_sah_cost(hs, box);
         up.host_stale = false;
         return (int)RT_OK;

@@ -7,7 +7,9 @@
 //
 // Compiled with -ffp-contract=off: the world-space vertices and edges computed here are part of
 // the arithmetic contract shared with the CPU oracle (instance transform row order, e1 = v1 - v0).
+// The diagnostics of a built scene (costs, check_bvh, count_visits) are in scene_check.cpp.
 #include "scene_build.h"
+#include "bvh_quantise.h"
 #include "rt_knobs.h"
 
 #include <algorithm>
@@ -20,7 +22,6 @@
 #include <map>
 #include <memory>
 #include <deque>
-#include <functional>
 #include <queue>
 
 namespace rt {
@@ -213,10 +214,23 @@ void presplit(Builder& b, double budget, float floor_extent) {
     for (size_t t = 0; t < T; ++t) b.n_split += was_split[t];
 }
 
-inline float half_area(const float* lo, const float* hi) {
-    float dx = hi[0] - lo[0], dy = hi[1] - lo[1], dz = hi[2] - lo[2];
-    if (!(dx >= 0 && dy >= 0 && dz >= 0)) return 0.0f;
-    return dx * dy + dy * dz + dz * dx;
+// ---- what the two top-down builders share: the to-do stack of index ranges ---------------------------------------------------------------------
+struct Work {
+    int32_t node;
+    uint32_t first, count, depth;
+};
+std::vector<Work> start_tree(Builder& b) { // the root over every reference
+    b.nodes.assign(1, GNode{});
+    return {{0, 0, (uint32_t)b.order.size(), 0}};
+}
+// makes nd an inner node over w's range cut at `split`: two fresh nodes, their ranges on the stack
+void open_children(Builder& b, GNode& nd, const Work& w, uint32_t split, std::vector<Work>& todo) {
+    nd.left = (int32_t)b.nodes.size();
+    nd.right = nd.left + 1;
+    b.nodes.push_back(GNode{});
+    b.nodes.push_back(GNode{});
+    todo.push_back({nd.left, w.first, split, w.depth + 1});
+    todo.push_back({nd.right, w.first + split, w.count - split, w.depth + 1});
 }
 
 // ---- LBVH: 63-bit Morton order + top-down split at the highest differing bit -----------------------
@@ -248,14 +262,7 @@ void build_lbvh(Builder& b) {
     std::sort(keys.begin(), keys.end());
     for (uint32_t i = 0; i < n; ++i) b.order[i] = keys[i].second;
 
-    struct Work {
-        int32_t node;
-        uint32_t first, count, depth;
-    };
-    std::vector<Work> todo;
-    b.nodes.clear();
-    b.nodes.push_back(GNode{});
-    todo.push_back({0, 0, n, 0});
+    std::vector<Work> todo = start_tree(b);
     while (!todo.empty()) {
         Work w = todo.back();
         todo.pop_back();
@@ -280,32 +287,16 @@ void build_lbvh(Builder& b) {
                 split = l;
                 if (split == 0 || split == w.count) split = w.count / 2;
             }
-            nd.left = (int32_t)b.nodes.size();
-            nd.right = nd.left + 1;
-            b.nodes.push_back(GNode{});
-            b.nodes.push_back(GNode{});
-            todo.push_back({nd.left, w.first, split, w.depth + 1});
-            todo.push_back({nd.right, w.first + split, w.count - split, w.depth + 1});
+            open_children(b, nd, w, split, todo);
         }
         b.nodes[w.node] = nd;
     }
 }
 
 // ---- binned SAH, top-down -------------------------------------------------------------------------
-void build_sah(Builder& b, uint32_t max_sah_depth) {
-    const uint32_t n = (uint32_t)b.order.size();
+void build_sah(Builder& b, uint32_t max_sah_depth, float trav_cost) {
     constexpr int NB = 32;
-    // cost of one traversal step relative to one triangle test, for the leaf-vs-split decision of small ranges
-    float trav_cost = 1.0f;
-    if (const char* e = dev_knob("RT_SAH_TRAV_COST")) trav_cost = (float)std::atof(e);
-    struct Work {
-        int32_t node;
-        uint32_t first, count, depth;
-    };
-    std::vector<Work> todo;
-    b.nodes.clear();
-    b.nodes.push_back(GNode{});
-    todo.push_back({0, 0, n, 0});
+    std::vector<Work> todo = start_tree(b);
     std::vector<uint32_t> tmp;
     while (!todo.empty()) {
         Work w = todo.back();
@@ -378,14 +369,7 @@ void build_sah(Builder& b, uint32_t max_sah_depth) {
                                  b.order.begin() + w.first + w.count);
             }
         }
-        if (!make_leaf) {
-            nd.left = (int32_t)b.nodes.size();
-            nd.right = nd.left + 1;
-            b.nodes.push_back(GNode{});
-            b.nodes.push_back(GNode{});
-            todo.push_back({nd.left, w.first, split, w.depth + 1});
-            todo.push_back({nd.right, w.first + split, w.count - split, w.depth + 1});
-        }
+        if (!make_leaf) open_children(b, nd, w, split, todo);
         b.nodes[w.node] = nd;
     }
 }
@@ -495,69 +479,18 @@ void optimise_by_reinsertion(Builder& b, int passes, double fraction) {
     }
 }
 
-inline float grid_step(uint32_t biased_exp) { // 2^(e-127) as a float, exactly as the kernel decodes it
-    uint32_t bits = biased_exp << 23;
-    float f;
-    std::memcpy(&f, &bits, 4);
-    return f;
-}
-
-// Quantises the (already padded) child boxes of one BVH4 node. Returns false only on non-finite input.
-bool quantise_node(BvhNode& n, int nk, const float (*klo)[3], const float (*khi)[3]) {
-    float nlo[3], nhi[3];
-    for (int a = 0; a < 3; ++a) {
-        nlo[a] = klo[0][a], nhi[a] = khi[0][a];
-        for (int k = 1; k < nk; ++k) nlo[a] = std::min(nlo[a], klo[k][a]), nhi[a] = std::max(nhi[a], khi[k][a]);
-        if (!std::isfinite(nlo[a]) || !std::isfinite(nhi[a])) return false;
-        n.origin[a] = nlo[a];
-    }
-    uint32_t q[6] = {0, 0, 0, 0, 0, 0};
-    for (int a = 0; a < 3; ++a) {
-        const double ext = (double)nhi[a] - (double)nlo[a];
-        int e = ext > 0 ? (int)std::ceil(std::log2(ext / 255.0)) : -100;
-        e = std::max(-100, std::min(100, e));
-        for (;; ++e) { // raise the grid step until every plane fits in 8 bits
-            const float s = grid_step((uint32_t)(e + 127));
-            uint32_t lo_b = 0, hi_b = 0;
-            bool ok = true;
-            for (int k = 0; k < 4 && ok; ++k) {
-                uint32_t ql = 255, qh = 0; // absent child: inverted box = a miss for every ray inside the contract's range (rt_device.h, trav_inner)
-                if (k < nk) {
-                    double fl = std::floor(((double)klo[k][a] - (double)nlo[a]) / (double)s);
-                    double fh = std::ceil(((double)khi[k][a] - (double)nlo[a]) / (double)s);
-                    long il = (long)std::max(0.0, std::min(255.0, fl)), ih = (long)std::max(0.0, std::min(256.0, fh));
-                    // verify with the kernel's own float decode; nudge outwards if rounding bit us
-                    while (il > 0 && n.origin[a] + (float)il * s > klo[k][a]) --il;
-                    while (ih <= 255 && n.origin[a] + (float)ih * s < khi[k][a]) ++ih;
-                    if (ih > 255 || n.origin[a] + (float)il * s > klo[k][a]) { ok = false; break; }
-                    ql = (uint32_t)il, qh = (uint32_t)ih;
-                }
-                lo_b |= ql << (8 * k), hi_b |= qh << (8 * k);
-            }
-            if (ok) {
-                q[2 * a] = lo_b, q[2 * a + 1] = hi_b;
-                n.set_scale(a, s);
-                break;
-            }
-            if (e > 120) return false;
-        }
-    }
-    for (int i = 0; i < 6; ++i) n.q[i] = q[i];
-    return true;
-}
-
-} // namespace
-
-#ifdef RT_DEVELOPER_KNOBS
-bool quantise_node_dev_export(BvhNode& n, int nk, const float (*klo)[3], const float (*khi)[3]) { return quantise_node(n, nk, klo, khi); }
-#endif
-
+// ---- collapse to four children -----------------------------------------------------------------------------------------------------------------
 // Which binary nodes become BVH4 nodes: dynamic programme over the binary tree (after Ylitie, Karras, Laine 2017).
 // best[n][k] = least SAH cost of covering subtree n with at most k child slots of its BVH4 parent; a subtree that
 // takes one slot is a leaf or a BVH4 node of its own (area + the best way to hand its 4 slots to its two halves).
 // cut[n][4] = slots a BVH4 node n gives to its LEFT half. best[0][1] / area(root) is the 4-wide tree's surface-area cost.
-static void collapse_dp(const Builder& b, std::vector<std::array<float, 5>>& best, std::vector<std::array<uint8_t, 5>>& cut) {
-    best.assign(b.nodes.size(), {}), cut.assign(b.nodes.size(), {});
+struct Collapse {
+    std::vector<std::array<float, 5>> best;
+    std::vector<std::array<uint8_t, 5>> cut;
+};
+
+void collapse_dp(const Builder& b, Collapse& c) {
+    c.best.assign(b.nodes.size(), {}), c.cut.assign(b.nodes.size(), {});
     std::vector<int32_t> post, st{0};
     while (!st.empty()) { // pre-order, reversed = children before parents
         const int32_t i = st.back();
@@ -570,7 +503,7 @@ static void collapse_dp(const Builder& b, std::vector<std::array<float, 5>>& bes
         const GNode& g = b.nodes[i];
         const float ar = half_area(g.lo, g.hi);
         if (g.left < 0) {
-            for (int k = 1; k <= 4; ++k) best[i][k] = ar * (float)g.count;
+            for (int k = 1; k <= 4; ++k) c.best[i][k] = ar * (float)g.count;
             continue;
         }
         float dist[5];
@@ -578,271 +511,167 @@ static void collapse_dp(const Builder& b, std::vector<std::array<float, 5>>& bes
         for (int k = 2; k <= 4; ++k) {
             dist[k] = std::numeric_limits<float>::infinity(), dl[k] = 1;
             for (int l = 1; l < k; ++l) {
-                const float c = best[g.left][l] + best[g.right][k - l];
-                if (c < dist[k]) dist[k] = c, dl[k] = (uint8_t)l;
+                const float cost = c.best[g.left][l] + c.best[g.right][k - l];
+                if (cost < dist[k]) dist[k] = cost, dl[k] = (uint8_t)l;
             }
         }
-        best[i][1] = ar + dist[4];
-        for (int k = 2; k <= 4; ++k) best[i][k] = std::min(dist[k], best[i][k - 1]);
-        cut[i][4] = dl[4]; // what the node does with its OWN four slots when it is a BVH4 node (best[i][1])
+        c.best[i][1] = ar + dist[4];
+        for (int k = 2; k <= 4; ++k) c.best[i][k] = std::min(dist[k], c.best[i][k - 1]);
+        c.cut[i][4] = dl[4]; // what the node does with its OWN four slots when it is a BVH4 node (best[i][1])
     }
 }
 
-int build_host_scene(const rt_scene_desc* d, int bvh_kind, HostScene& hs, std::string& err) {
-    if (!d) { err = "null scene description"; return RT_ERR_INVALID; }
-    if (d->n_triangles && (!d->positions || !d->normals || !d->uvs || !d->indices || !d->tri_instance)) {
-        err = "null geometry array"; return RT_ERR_INVALID;
+// the children subtree n contributes to a BVH4 node that grants it up to k slots: the recorded decisions, expanded
+void gather(const Builder& b, const Collapse& c, int32_t n, int k, int32_t* kids, int& nk) {
+    const GNode& g = b.nodes[n];
+    if (k <= 1 || g.left < 0) { kids[nk++] = n; return; }
+    // as a PARENT's subtree with k slots: either distribute them or fall back to k-1
+    float dist = std::numeric_limits<float>::infinity();
+    int dl = 1;
+    for (int l = 1; l < k; ++l) {
+        const float cost = c.best[g.left][l] + c.best[g.right][k - l];
+        if (cost < dist) dist = cost, dl = l;
     }
-    if ((d->n_instances && !d->instances) || (d->n_materials && !d->materials)) {
-        err = "null instance/material array"; return RT_ERR_INVALID;
-    }
-    if (d->n_layers > RT_TEX_MAX_LAYERS) { err = "more than 128 texture layers"; return RT_ERR_INVALID; }
-    if (d->n_layers && !d->textures) { err = "null texture array"; return RT_ERR_INVALID; }
-    if (d->n_triangles >= (1u << 28)) { err = "too many triangles (limit 2^28)"; return RT_ERR_INVALID; }
-    if (bvh_kind != RT_BVH_DEFAULT && bvh_kind != RT_BVH_LBVH && bvh_kind != RT_BVH_SAH && bvh_kind != RT_BVH_MEDIAN_INTERNAL &&
-        bvh_kind != RT_BVH_LBVH_GPU) {
-        err = "unknown bvh_kind"; return RT_ERR_INVALID;
-    }
-    for (uint32_t i = 0; i < d->n_instances; ++i) {
-        if (d->instances[i].material >= d->n_materials) { err = "instance material out of range"; return RT_ERR_INVALID; }
-    }
-    for (uint32_t i = 0; i < d->n_materials; ++i) {
-        const rt_material& m = d->materials[i];
-        if (m.type > RT_MAT_DIELECTRIC || m.tex_kind > RT_TEX_IMAGE) { err = "bad material type"; return RT_ERR_INVALID; }
-        if (m.tex_kind == RT_TEX_IMAGE && m.type != RT_MAT_DIELECTRIC && m.type != RT_MAT_NONE &&
-            m.tex_layer >= d->n_layers) { err = "material texture layer out of range"; return RT_ERR_INVALID; }
-    }
-    const uint32_t T = d->n_triangles;
-    for (uint32_t t = 0; t < T; ++t) {
-        if (d->tri_instance[t] >= d->n_instances) { err = "tri_instance out of range"; return RT_ERR_INVALID; }
-        for (int k = 0; k < 3; ++k)
-            if (d->indices[3 * t + k] >= d->n_vertices) { err = "vertex index out of range"; return RT_ERR_INVALID; }
-    }
+    if (dist < c.best[n][k - 1]) gather(b, c, g.left, dl, kids, nk), gather(b, c, g.right, k - dl, kids, nk);
+    else gather(b, c, n, k - 1, kids, nk);
+}
 
-    hs = HostScene{};
-    hs.sky[0] = d->sky[0], hs.sky[1] = d->sky[1], hs.sky[2] = d->sky[2];
-    hs.n_layers = d->n_layers;
-    if (d->n_layers) hs.tex.assign(d->textures, d->textures + (size_t)d->n_layers * 512u * 512u * 4u);
-    hs.packed_mat = d->n_instances <= (1u << kPackedInstBits) && d->n_materials <= (1u << (32u - kPackedInstBits));
-    // The device's instance table. Packed shading word (the rule, rt_types.h): the material index travels in the word, so what is left of an
-    // instance is its normal matrix — and a scene has far fewer DISTINCT matrices than instances (one instance per glTF node and primitive:
-    // 166 and 5 on the atrium). The table holds every distinct bit pattern once, ordered by the number of triangles that use it, so that the
-    // head of the table — what the shading kernels stage in LDS — covers the most hits. inst_slot[i]: instance i's row of the table.
-    std::vector<uint32_t> inst_slot;
-    {
-        std::vector<uint64_t> use(d->n_instances, 0);
-        for (uint32_t t = 0; t < d->n_triangles; ++t) use[d->tri_instance[t]]++;
-        shading_rows(d->instances, d->n_instances, use, hs.packed_mat, hs.inst, inst_slot);
+// the up to four children of the BVH4 node made of binary node n; greedy (RT_BVH_COLLAPSE=greedy): open the inner child with the largest surface area
+int wide_children(const Builder& b, const Collapse& c, bool use_dp, int32_t n, int32_t* kids) {
+    const GNode& g = b.nodes[n];
+    int nk = 0;
+    if (use_dp) {
+        const int li = c.cut[n][4];
+        gather(b, c, g.left, li, kids, nk), gather(b, c, g.right, 4 - li, kids, nk);
+        return nk;
     }
-    hs.mats.resize(d->n_materials);
-    for (uint32_t i = 0; i < d->n_materials; ++i) {
-        const rt_material& m = d->materials[i];
-        MatRec& r = hs.mats[i];
-        r.type = m.type, r.tex_kind = m.tex_kind, r.tex_layer = m.tex_layer;
-        std::memcpy(r.color, m.color, 12), std::memcpy(r.emissive, m.emissive, 12);
-        r.roughness = m.roughness, r.ior = m.ior, r.pad = 0;
-    }
-
-    // flatten: world = ((m0*x + m4*y) + m8*z) + m12 per row of the column-major instance matrix
-    hs.wverts.resize(9 * (size_t)T);
-    hs.shade.resize(T);
-    std::vector<TriRec> gtris(T);
-    for (uint32_t t = 0; t < T; ++t) {
-        const uint32_t ii = d->tri_instance[t];
-        const float* m = d->instances[ii].transform;
-        float p[3][3];
-        for (int k = 0; k < 3; ++k) {
-            const uint32_t vi = d->indices[3 * t + k];
-            const float x = d->positions[3 * vi], y = d->positions[3 * vi + 1], z = d->positions[3 * vi + 2];
-            p[k][0] = ((m[0] * x + m[4] * y) + m[8] * z) + m[12];
-            p[k][1] = ((m[1] * x + m[5] * y) + m[9] * z) + m[13];
-            p[k][2] = ((m[2] * x + m[6] * y) + m[10] * z) + m[14];
-            for (int a = 0; a < 3; ++a) hs.wverts[9 * (size_t)t + 3 * k + a] = p[k][a];
+    kids[nk++] = g.left, kids[nk++] = g.right;
+    while (nk < 4) {
+        int best = -1;
+        float best_area = -1.0f;
+        for (int k = 0; k < nk; ++k) {
+            const GNode& ch = b.nodes[kids[k]];
+            const float ar = ch.left >= 0 ? half_area(ch.lo, ch.hi) : -1.0f;
+            if (ar > best_area) best_area = ar, best = k;
         }
-        TriRec& tr = gtris[t];
-        for (int a = 0; a < 3; ++a) {
-            tr.v0[a] = p[0][a];
-            tr.e1[a] = p[1][a] - p[0][a];
-            tr.e2[a] = p[2][a] - p[0][a];
-        }
-        tr.global_index = t, tr.pad[0] = tr.pad[1] = 0;
-        ShadeRec& s = hs.shade[t];
-        const uint32_t i0 = d->indices[3 * t], i1 = d->indices[3 * t + 1], i2 = d->indices[3 * t + 2];
-        std::memcpy(s.n0, d->normals + 3 * i0, 12), std::memcpy(s.n1, d->normals + 3 * i1, 12);
-        std::memcpy(s.n2, d->normals + 3 * i2, 12);
-        std::memcpy(s.uv0, d->uvs + 2 * i0, 8), std::memcpy(s.uv1, d->uvs + 2 * i1, 8);
-        std::memcpy(s.uv2, d->uvs + 2 * i2, 8);
-        s.instance = hs.packed_mat ? (inst_slot[ii] | (d->instances[ii].material << kPackedInstBits)) : ii;
+        if (best < 0) break;
+        const GNode& ch = b.nodes[kids[best]];
+        kids[best] = ch.left;
+        kids[nk++] = ch.right;
     }
-    for (size_t i = 0; i < hs.wverts.size(); ++i) {
-        if (!std::isfinite(hs.wverts[i])) { err = "non-finite world-space vertex"; return RT_ERR_INVALID; }
-    }
+    return nk;
+}
 
-    auto empty_node = []() {
-        BvhNode n{};
-        n.scale_x = n.scale_y = n.scale_z = 1.0f;
-        for (int i = 0; i < 6; ++i) n.q[i] = (i & 1) ? 0u : 0xFFFFFFFFu; // qlo = 255, qhi = 0
-        for (int k = 0; k < 4; ++k) n.child[k] = kChildEmpty;
-        return n;
-    };
-    if (T == 0) {
-        hs.built_by = bvh_kind;
-        hs.nodes.assign(1, empty_node());
-        hs.tris.assign(1, TriRec{}); // one dummy record so device pointers are never null
-        hs.tris[0].global_index = kNoTri;
-        return RT_OK;
-    }
+// ---- the binary tree of one builder kind -------------------------------------------------------------------------------------------------------
+// The builders' knobs (developer build), read once per scene.
+struct BuildOptions {
+    // pre-splitting of large triangles (SAH builder only): at most 30 % more references, only boxes FATTER (geometric mean of the three
+    // extents) than 1/64 of the scene's largest extent — the finely tessellated bench scene has none and neither have axis-aligned walls
+    // (their trees are unchanged); large triangles that cross space diagonally do. RT_BVH_SPLIT_BUDGET=0 switches it off,
+    // RT_BVH_SPLIT_FLOOR=<fraction of the scene extent> moves the floor.
+    double budget = 0.3, floor_frac = 1.0 / 64.0;
+    // one pass over the larger half of the inner nodes: -2.6 % SAH cost, 17.9 -> 17.5 node visits per ray on the
+    // atrium (+0.7 % rays/s) for 0.18 s of extra build time; further passes change nothing. RT_BVH_REINSERT=0: off
+    int passes = 1;
+    double fraction = 0.5;
+    float trav_cost = 1.0f; // cost of one traversal step relative to one triangle test, for the leaf-vs-split decision of small ranges
+    bool use_dp = true;     // RT_BVH_COLLAPSE=greedy restores the open-the-largest-child rule
 
-    for (int a = 0; a < 3; ++a) hs.bounds_lo[a] = INFINITY, hs.bounds_hi[a] = -INFINITY;
-    for (size_t i = 0; i < hs.wverts.size(); ++i) {
-        const int a = (int)(i % 3);
-        hs.bounds_lo[a] = std::min(hs.bounds_lo[a], hs.wverts[i]), hs.bounds_hi[a] = std::max(hs.bounds_hi[a], hs.wverts[i]);
-    }
-    float ext = 0.0f;
-    for (int a = 0; a < 3; ++a) ext = std::max(ext, hs.bounds_hi[a] - hs.bounds_lo[a]);
-    if (!scene_padding(hs.bounds_lo, hs.bounds_hi, hs.pad, err)) return RT_ERR_INVALID;
-
-    // Exact worst-case traversal stack need: at every level all siblings of the entered child may be waiting.
-    std::function<uint32_t(int32_t)> need = [&](int32_t node) -> uint32_t {
-        const BvhNode& n = hs.nodes[node];
-        uint32_t nk = 0, worst = 0;
-        for (int k = 0; k < 4; ++k) nk += n.child[k] != kChildEmpty;
-        for (int k = 0; k < 4; ++k)
-            if (n.child[k] != kChildEmpty) worst = std::max(worst, (nk - 1) + (n.child[k] >= 0 ? need(n.child[k]) : 0u));
-        return worst;
-    };
-
-    if (bvh_kind == RT_BVH_LBVH_GPU && T >= 8) { // whole build on the device (lbvh_gpu.hip); tiny scenes use the host
-        int rc = build_lbvh_gpu(hs, gtris, err);
-        if (rc == RT_ERR_UNSUPPORTED) { // degenerate Morton order (deeper than the emission loop allows): balanced host fallback
-            err.clear();
-            return build_host_scene(d, RT_BVH_MEDIAN_INTERNAL, hs, err);
-        }
-        if (rc != RT_OK) return rc;
-        hs.stack_need = need(0);
-        if (hs.stack_need + 2 >= (uint32_t)kStackSize) return build_host_scene(d, RT_BVH_MEDIAN_INTERNAL, hs, err);
-        hs.built_by = RT_BVH_LBVH_GPU;
-        hs.sah_cost = decoded_sah_cost(hs);
-        return RT_OK;
-    }
-
-    std::unique_ptr<Builder> bp(new Builder(hs.wverts));
-    if (bvh_kind == RT_BVH_LBVH || bvh_kind == RT_BVH_LBVH_GPU) build_lbvh(*bp);
-    else {
-        // pre-splitting of large triangles (SAH builder only): at most 30 % more references, only boxes FATTER (geometric mean of the three
-        // extents) than 1/64 of the scene's largest extent — the finely tessellated bench scene has none and neither have axis-aligned walls
-        // (their trees are unchanged); large triangles that cross space diagonally do. Where it did split, the tree without splits is
-        // built too and the one with the lower surface-area cost is kept (a 116-triangle Cornell box gets worse, a tilted hall 15 % better).
-        // RT_BVH_SPLIT_BUDGET=0 switches it off, RT_BVH_SPLIT_FLOOR=<fraction of the scene extent> moves the floor.
-        double budget = 0.3, floor_frac = 1.0 / 64.0;
+    BuildOptions() {
         if (const char* e = dev_knob("RT_BVH_SPLIT_BUDGET")) budget = std::max(0.0, std::min(4.0, std::atof(e)));
         if (const char* e = dev_knob("RT_BVH_SPLIT_FLOOR")) floor_frac = std::max(1e-4, std::min(1.0, std::atof(e)));
-        // one pass over the larger half of the inner nodes: -2.6 % SAH cost, 17.9 -> 17.5 node visits per ray on the
-        // atrium (+0.7 % rays/s) for 0.18 s of extra build time; further passes change nothing. RT_BVH_REINSERT=0: off
-        int passes = 1;
-        double fraction = 0.5;
         if (const char* e = dev_knob("RT_BVH_REINSERT")) passes = std::atoi(e);
         if (const char* e = dev_knob("RT_BVH_REINSERT_FRACTION")) fraction = std::atof(e);
-        auto run = [&](Builder& bb, bool split) {
-            if (split && bvh_kind != RT_BVH_MEDIAN_INTERNAL && budget > 0.0) presplit(bb, budget, (float)(floor_frac * (double)ext));
-            build_sah(bb, bvh_kind == RT_BVH_MEDIAN_INTERNAL ? 0u : 48u);
-            if (bvh_kind != RT_BVH_MEDIAN_INTERNAL && passes > 0) optimise_by_reinsertion(bb, passes, std::min(1.0, std::max(0.0, fraction)));
-        };
-        auto wide_cost = [](const Builder& bb) { // surface-area cost of the 4-wide tree the collapse below will make of this binary tree
-            std::vector<std::array<float, 5>> bst;
-            std::vector<std::array<uint8_t, 5>> ct;
-            collapse_dp(bb, bst, ct);
-            return (double)bst[0][1] / std::max(1e-30, (double)half_area(bb.nodes[0].lo, bb.nodes[0].hi));
-        };
-        run(*bp, true);
-        if (bp->n_split > 0) {
-            std::unique_ptr<Builder> plain(new Builder(hs.wverts));
-            run(*plain, false);
-            if (bp->nodes[0].left < 0 || plain->nodes[0].left < 0 || wide_cost(*plain) <= wide_cost(*bp)) bp = std::move(plain);
-        }
+        if (const char* e = dev_knob("RT_SAH_TRAV_COST")) trav_cost = (float)std::atof(e);
+        if (const char* e = dev_knob("RT_BVH_COLLAPSE")) use_dp = std::string(e) != "greedy";
     }
-    Builder& b = *bp;
-    const GNode& g0 = b.nodes[0];
+};
 
-    // Collapse the binary tree into a 4-wide one and emit it top first (the order is described below): the nodes the traversal kernels
-    // stage in LDS are contiguous at the head of the array.
-    hs.tris.clear();
-    hs.tris.reserve(b.order.size());
-    hs.nodes.clear();
-    auto leaf_code = [&](const GNode& g, uint32_t depth) -> int32_t {
-        uint32_t first = (uint32_t)hs.tris.size();
-        uint32_t count = 0;
-        for (uint32_t k = 0; k < g.count; ++k) { // the triangles of the leaf's references, each once; its record keeps the box of its pieces HERE
-            const uint32_t ref = b.order[g.first + k], tri = b.ref_tri[ref];
-            uint32_t at = count;
-            for (uint32_t j = 0; j < count; ++j)
-                if (hs.tris[first + j].global_index == tri) at = j;
-            if (at == count) {
-                hs.tris.push_back(gtris[tri]);
-                for (int a = 0; a < 3; ++a) hs.rec_lo.push_back(b.tlo[3 * ref + a]), hs.rec_hi.push_back(b.thi[3 * ref + a]);
-                ++count;
-            } else {
-                for (int a = 0; a < 3; ++a) {
-                    float& lo = hs.rec_lo[3 * (size_t)(first + at) + a];
-                    float& hi = hs.rec_hi[3 * (size_t)(first + at) + a];
-                    lo = std::min(lo, b.tlo[3 * ref + a]), hi = std::max(hi, b.thi[3 * ref + a]);
-                }
+// Where pre-splitting did split, the tree without splits is built too and the one with the lower surface-area cost of its 4-wide collapse
+// is kept (a 116-triangle Cornell box gets worse, a tilted hall 15 % better).
+std::unique_ptr<Builder> build_binary(int kind, const HostScene& hs, const BuildOptions& o) {
+    std::unique_ptr<Builder> bp(new Builder(hs.wverts));
+    if (kind == RT_BVH_LBVH || kind == RT_BVH_LBVH_GPU) { // (a GPU request for fewer than 8 triangles: the host LBVH)
+        build_lbvh(*bp);
+        return bp;
+    }
+    const bool balanced = kind == RT_BVH_MEDIAN_INTERNAL;
+    float ext = 0.0f;
+    for (int a = 0; a < 3; ++a) ext = std::max(ext, hs.bounds_hi[a] - hs.bounds_lo[a]);
+    auto run = [&](Builder& b, bool split) {
+        if (split && !balanced && o.budget > 0.0) presplit(b, o.budget, (float)(o.floor_frac * (double)ext));
+        build_sah(b, balanced ? 0u : 48u, o.trav_cost);
+        if (!balanced && o.passes > 0) optimise_by_reinsertion(b, o.passes, std::min(1.0, std::max(0.0, o.fraction)));
+    };
+    auto wide_cost = [](const Builder& b) {
+        Collapse c;
+        collapse_dp(b, c);
+        return (double)c.best[0][1] / std::max(1e-30, (double)half_area(b.nodes[0].lo, b.nodes[0].hi));
+    };
+    run(*bp, true);
+    if (bp->n_split > 0) {
+        std::unique_ptr<Builder> plain(new Builder(hs.wverts));
+        run(*plain, false);
+        if (bp->nodes[0].left < 0 || plain->nodes[0].left < 0 || wide_cost(*plain) <= wide_cost(*bp)) bp = std::move(plain);
+    }
+    return bp;
+}
+
+// ---- emission: the 4-wide tree into hs.nodes / hs.tris -----------------------------------------------------------------------------------------
+// the leaf records of binary leaf g: the triangles of its references, each once; a record keeps the box of its pieces HERE
+int32_t emit_leaf(const Builder& b, const std::vector<TriRec>& gtris, const GNode& g, uint32_t depth, HostScene& hs) {
+    const uint32_t first = (uint32_t)hs.tris.size();
+    uint32_t count = 0;
+    for (uint32_t k = 0; k < g.count; ++k) {
+        const uint32_t ref = b.order[g.first + k], tri = b.ref_tri[ref];
+        uint32_t at = count;
+        for (uint32_t j = 0; j < count; ++j)
+            if (hs.tris[first + j].global_index == tri) at = j;
+        if (at == count) {
+            hs.tris.push_back(gtris[tri]);
+            for (int a = 0; a < 3; ++a) hs.rec_lo.push_back(b.tlo[3 * ref + a]), hs.rec_hi.push_back(b.thi[3 * ref + a]);
+            ++count;
+        } else {
+            for (int a = 0; a < 3; ++a) {
+                float& lo = hs.rec_lo[3 * (size_t)(first + at) + a];
+                float& hi = hs.rec_hi[3 * (size_t)(first + at) + a];
+                lo = std::min(lo, b.tlo[3 * ref + a]), hi = std::max(hi, b.thi[3 * ref + a]);
             }
         }
-        hs.max_leaf_tris = std::max(hs.max_leaf_tris, count);
-        hs.max_depth = std::max(hs.max_depth, depth);
-        return ~(int32_t)((first << 2) | (count - 1));
-    };
-    hs.rec_lo.clear(), hs.rec_hi.clear();
+    }
+    hs.max_leaf_tris = std::max(hs.max_leaf_tris, count);
+    hs.max_depth = std::max(hs.max_depth, depth);
+    return leaf_child(first, count);
+}
+
+// Collapses the binary tree into a 4-wide one and emits it top first. Emission order: largest surface area first until the LDS-staged top
+// of the tree is complete (the first kTopNodes nodes of the array are the children of the nodes a ray is most likely to visit; level order
+// staged 2 % fewer expected visits), depth-first below it, so that the nodes and the triangles of one subtree are contiguous in memory
+// (fewer distinct cache lines per ray than a pure breadth-first layout). Returns false with err set; `single` tells a root that is one leaf.
+bool emit_tree(const Builder& b, const std::vector<TriRec>& gtris, const BuildOptions& o, HostScene& hs, bool& single, std::string& err) {
+    const GNode& g0 = b.nodes[0];
+    hs.tris.reserve(b.order.size());
     hs.n_split_triangles = b.n_split;
+    hs.nodes.push_back(empty_node());
+    single = g0.left < 0;
+    if (single) { // give the root one leaf child
+        if (g0.count > (uint32_t)kMaxLeafTris) { err = "internal: oversized root leaf"; return false; }
+        Box3 kb;
+        std::memcpy(kb.lo, g0.lo, 12), std::memcpy(kb.hi, g0.hi, 12);
+        if (!quantise_node(hs.nodes[0], 1, &kb, hs.pad)) { err = "internal: quantisation failed"; return false; }
+        hs.nodes[0].child[0] = emit_leaf(b, gtris, g0, 1, hs);
+        hs.sah_cost = (double)g0.count;
+        return true;
+    }
     const double root_area = std::max(1e-30, (double)half_area(g0.lo, g0.hi));
     double cost = 0.0;
+    Collapse c;
+    if (o.use_dp) collapse_dp(b, c);
     struct Item { int32_t gnode; int32_t slot; uint32_t depth; };
-    std::deque<Item> q;
-    hs.nodes.push_back(empty_node());
-    if (g0.left < 0) { // a single leaf: give the root one leaf child
-        if (g0.count > (uint32_t)kMaxLeafTris) { err = "internal: oversized root leaf"; return RT_ERR_INVALID; }
-        BvhNode root = empty_node();
-        float klo[1][3], khi[1][3];
-        for (int a = 0; a < 3; ++a) klo[0][a] = g0.lo[a] - hs.pad, khi[0][a] = g0.hi[a] + hs.pad;
-        if (!quantise_node(root, 1, klo, khi)) { err = "internal: quantisation failed"; return RT_ERR_INVALID; }
-        root.child[0] = leaf_code(g0, 1);
-        hs.nodes[0] = root;
-        hs.sah_cost = (double)g0.count;
-        return RT_OK;
-    }
-    // Emission order: largest surface area first until the LDS-staged top of the tree is complete (the first kTopNodes nodes of the
-    // array are the children of the nodes a ray is most likely to visit; level order staged 2 % fewer expected visits), depth-first
-    // below it, so that the nodes and the triangles of one subtree are contiguous in memory (fewer distinct cache lines per ray than
-    // a pure breadth-first layout).
-    // Which binary nodes become BVH4 nodes: dynamic programme over the binary tree (after Ylitie, Karras, Laine 2017).
-    // best[n][k] = least SAH cost of covering subtree n with at most k child slots of its BVH4 parent; a subtree that
-    // takes one slot is a leaf or a BVH4 node of its own (area + the best way to hand its 4 slots to its two halves).
-    // cut[n][4] = slots a BVH4 node n gives to its LEFT half. RT_BVH_COLLAPSE=greedy restores the open-the-largest-child rule.
-    bool use_dp = true;
-    if (const char* e = dev_knob("RT_BVH_COLLAPSE")) use_dp = std::string(e) != "greedy";
-    std::vector<std::array<float, 5>> best;
-    std::vector<std::array<uint8_t, 5>> cut;
-    if (use_dp) collapse_dp(b, best, cut);
-    // children of BVH4 node: expand the recorded decisions (subtree n may use up to k slots)
-    std::function<void(int32_t, int, int32_t*, int&)> gather = [&](int32_t n, int k, int32_t* kids, int& nk) {
-        const GNode& g = b.nodes[n];
-        if (k <= 1 || g.left < 0) { kids[nk++] = n; return; }
-        // as a PARENT's subtree with k slots: either distribute them or fall back to k-1
-        float dist = std::numeric_limits<float>::infinity();
-        int dl = 1;
-        for (int l = 1; l < k; ++l) {
-            const float c = best[g.left][l] + best[g.right][k - l];
-            if (c < dist) dist = c, dl = l;
-        }
-        if (dist < best[n][k - 1]) gather(g.left, dl, kids, nk), gather(g.right, k - dl, kids, nk);
-        else gather(n, k - 1, kids, nk);
-    };
-    constexpr size_t kBfsNodes = kTopNodes; // the nodes the traversal kernels stage in LDS
-    q.push_back({0, 0, 0});
+    std::deque<Item> q{{0, 0, 0}};
     while (!q.empty()) {
         Item it;
-        if (hs.nodes.size() < kBfsNodes) {
+        if (hs.nodes.size() < (size_t)kTopNodes) { // the nodes the traversal kernels stage in LDS
             size_t pick = 0; // the pending node a ray is most likely to visit: the one with the largest surface area
             float best_area = -1.0f;
             for (size_t i = 0; i < q.size(); ++i) {
@@ -854,42 +683,20 @@ int build_host_scene(const rt_scene_desc* d, int bvh_kind, HostScene& hs, std::s
         } else { it = q.back(); q.pop_back(); }
         const GNode& g = b.nodes[it.gnode];
         cost += (double)half_area(g.lo, g.hi) / root_area;
-        int32_t kids[4] = {g.left, g.right, -1, -1};
-        int nk = 2;
-        if (use_dp) {
-            nk = 0;
-            const int li = cut[it.gnode][4];
-            gather(g.left, li, kids, nk), gather(g.right, 4 - li, kids, nk);
-        } else {
-            while (nk < 4) { // greedy: open the inner child with the largest surface area
-                int best = -1;
-                float best_area = -1.0f;
-                for (int k = 0; k < nk; ++k) {
-                    const GNode& c = b.nodes[kids[k]];
-                    if (c.left >= 0) {
-                        float ar = half_area(c.lo, c.hi);
-                        if (ar > best_area) best_area = ar, best = k;
-                    }
-                }
-                if (best < 0) break;
-                const GNode& c = b.nodes[kids[best]];
-                kids[best] = c.left;
-                kids[nk++] = c.right;
-            }
-        }
+        int32_t kids[4];
+        const int nk = wide_children(b, c, o.use_dp, it.gnode, kids);
         BvhNode out = empty_node();
         Item pending[4];
         int n_pending = 0;
-        float klo[4][3], khi[4][3];
-        for (int k = 0; k < nk; ++k)
-            for (int a = 0; a < 3; ++a) klo[k][a] = b.nodes[kids[k]].lo[a] - hs.pad, khi[k][a] = b.nodes[kids[k]].hi[a] + hs.pad;
-        if (!quantise_node(out, nk, klo, khi)) { err = "internal: quantisation failed"; return RT_ERR_INVALID; }
+        Box3 kb[4];
+        for (int k = 0; k < nk; ++k) std::memcpy(kb[k].lo, b.nodes[kids[k]].lo, 12), std::memcpy(kb[k].hi, b.nodes[kids[k]].hi, 12);
+        if (!quantise_node(out, nk, kb, hs.pad)) { err = "internal: quantisation failed"; return false; }
         for (int k = 0; k < nk; ++k) {
-            const GNode& c = b.nodes[kids[k]];
-            if (c.left < 0) {
-                if (c.count == 0 || c.count > (uint32_t)kMaxLeafTris) { err = "internal: bad leaf size"; return RT_ERR_INVALID; }
-                out.child[k] = leaf_code(c, it.depth + 1);
-                cost += (double)half_area(c.lo, c.hi) / root_area * (double)c.count;
+            const GNode& ch = b.nodes[kids[k]];
+            if (ch.left < 0) {
+                if (ch.count == 0 || ch.count > (uint32_t)kMaxLeafTris) { err = "internal: bad leaf size"; return false; }
+                out.child[k] = emit_leaf(b, gtris, ch, it.depth + 1, hs);
+                cost += (double)half_area(ch.lo, ch.hi) / root_area * (double)ch.count;
             } else {
                 out.child[k] = (int32_t)hs.nodes.size();
                 hs.nodes.push_back(empty_node());
@@ -897,7 +704,7 @@ int build_host_scene(const rt_scene_desc* d, int bvh_kind, HostScene& hs, std::s
             }
         }
         // top phase: children in order at the back; depth-first phase: reversed, so child 0 is next
-        if (hs.nodes.size() < kBfsNodes) for (int k = 0; k < n_pending; ++k) q.push_back(pending[k]);
+        if (hs.nodes.size() < (size_t)kTopNodes) for (int k = 0; k < n_pending; ++k) q.push_back(pending[k]);
         else for (int k = n_pending - 1; k >= 0; --k) q.push_back(pending[k]);
         hs.nodes[it.slot] = out;
     }
@@ -907,20 +714,180 @@ int build_host_scene(const rt_scene_desc* d, int bvh_kind, HostScene& hs, std::s
             size_t by[5] = {0, 0, 0, 0, 0};
             for (const BvhNode& n : hs.nodes)
                 for (int k = 0; k < 4; ++k)
-                    if (n.child[k] < 0 && n.child[k] != kChildEmpty) by[(((uint32_t)~n.child[k]) & 3u) + 1u]++;
-            std::fprintf(stderr, "[rt bvh] %zu nodes, leaves with 1 / 2 / 3 / 4 triangles: %zu / %zu / %zu / %zu, %zu records for %u triangles (%u split)\n", hs.nodes.size(),
-                         by[1], by[2], by[3], by[4], hs.tris.size(), T, hs.n_split_triangles);
+                    if (n.child[k] < 0 && n.child[k] != kChildEmpty) by[leaf_range(n.child[k]).count]++;
+            std::fprintf(stderr, "[rt bvh] %zu nodes, leaves with 1 / 2 / 3 / 4 triangles: %zu / %zu / %zu / %zu, %zu records for %zu triangles (%u split)\n", hs.nodes.size(),
+                         by[1], by[2], by[3], by[4], hs.tris.size(), gtris.size(), hs.n_split_triangles);
         }
     }
-    if (hs.tris.size() < T || hs.tris.size() > b.order.size()) { err = "internal: leaf record count mismatch after build"; return RT_ERR_INVALID; }
-    hs.stack_need = need(0);
-    if (hs.stack_need + 2 >= (uint32_t)kStackSize) {
-        if (bvh_kind != RT_BVH_MEDIAN_INTERNAL) return build_host_scene(d, RT_BVH_MEDIAN_INTERNAL, hs, err); // balanced fallback
-        err = "internal: BVH deeper than the traversal stack";
-        return RT_ERR_INVALID;
+    if (hs.tris.size() < gtris.size() || hs.tris.size() > b.order.size()) { err = "internal: leaf record count mismatch after build"; return false; }
+    return true;
+}
+
+// Exact worst-case traversal stack need: at every level all siblings of the entered child may be waiting.
+uint32_t stack_need(const std::vector<BvhNode>& nodes, int32_t node) {
+    const BvhNode& n = nodes[node];
+    uint32_t nk = 0, worst = 0;
+    for (int k = 0; k < 4; ++k) nk += n.child[k] != kChildEmpty;
+    for (int k = 0; k < 4; ++k)
+        if (n.child[k] != kChildEmpty) worst = std::max(worst, (nk - 1) + (n.child[k] >= 0 ? stack_need(nodes, n.child[k]) : 0u));
+    return worst;
+}
+
+// One attempt at the tree, from clean tree fields: RT_OK, an error, or kTooDeep where the tree would overflow the traversal stack (or the
+// device builder's emission loop) and the balanced builder has to take over.
+constexpr int kTooDeep = -1000;
+int build_tree(int kind, const std::vector<TriRec>& gtris, const BuildOptions& o, HostScene& hs, std::string& err) {
+    hs.nodes.clear(), hs.tris.clear(), hs.rec_lo.clear(), hs.rec_hi.clear();
+    hs.max_depth = hs.max_leaf_tris = hs.n_split_triangles = hs.stack_need = 0;
+    hs.sah_cost = 0.0;
+    const bool on_device = kind == RT_BVH_LBVH_GPU && gtris.size() >= 8; // whole build on the device (lbvh_gpu.hip); tiny scenes use the host
+    if (on_device) {
+        const int rc = build_lbvh_gpu(hs, gtris, err);
+        if (rc == RT_ERR_UNSUPPORTED) return kTooDeep; // degenerate Morton order (deeper than the emission loop allows)
+        if (rc != RT_OK) return rc;
+    } else {
+        bool single = false;
+        if (!emit_tree(*build_binary(kind, hs, o), gtris, o, hs, single, err)) return RT_ERR_INVALID;
+        if (single) return RT_OK; // (built_by and stack_need stay unset for a root that is one leaf)
     }
-    hs.built_by = bvh_kind == RT_BVH_LBVH_GPU ? RT_BVH_LBVH : bvh_kind; // (a GPU request for fewer than 8 triangles: the host LBVH)
+    hs.stack_need = stack_need(hs.nodes, 0);
+    if (hs.stack_need + 2 >= (uint32_t)kStackSize) return kTooDeep;
+    hs.built_by = (int8_t)(kind == RT_BVH_LBVH_GPU && !on_device ? RT_BVH_LBVH : kind);
+    if (on_device) hs.sah_cost = decoded_sah_cost(hs);
     return RT_OK;
+}
+
+// ---- the stages before the tree ----------------------------------------------------------------------------------------------------------------
+int validate_desc(const rt_scene_desc* d, int bvh_kind, std::string& err) {
+    auto bad = [&](const char* m) { err = m; return (int)RT_ERR_INVALID; };
+    if (!d) return bad("null scene description");
+    if (d->n_triangles && (!d->positions || !d->normals || !d->uvs || !d->indices || !d->tri_instance)) return bad("null geometry array");
+    if ((d->n_instances && !d->instances) || (d->n_materials && !d->materials)) return bad("null instance/material array");
+    if (d->n_layers > RT_TEX_MAX_LAYERS) return bad("more than 128 texture layers");
+    if (d->n_layers && !d->textures) return bad("null texture array");
+    if (d->n_triangles >= (1u << 28)) return bad("too many triangles (limit 2^28)");
+    if (bvh_kind != RT_BVH_DEFAULT && bvh_kind != RT_BVH_LBVH && bvh_kind != RT_BVH_SAH && bvh_kind != RT_BVH_MEDIAN_INTERNAL &&
+        bvh_kind != RT_BVH_LBVH_GPU)
+        return bad("unknown bvh_kind");
+    for (uint32_t i = 0; i < d->n_instances; ++i)
+        if (d->instances[i].material >= d->n_materials) return bad("instance material out of range");
+    for (uint32_t i = 0; i < d->n_materials; ++i) {
+        const rt_material& m = d->materials[i];
+        if (m.type > RT_MAT_DIELECTRIC || m.tex_kind > RT_TEX_IMAGE) return bad("bad material type");
+        if (m.tex_kind == RT_TEX_IMAGE && m.type != RT_MAT_DIELECTRIC && m.type != RT_MAT_NONE && m.tex_layer >= d->n_layers)
+            return bad("material texture layer out of range");
+    }
+    for (uint32_t t = 0; t < d->n_triangles; ++t) {
+        if (d->tri_instance[t] >= d->n_instances) return bad("tri_instance out of range");
+        for (int k = 0; k < 3; ++k)
+            if (d->indices[3 * t + k] >= d->n_vertices) return bad("vertex index out of range");
+    }
+    return RT_OK;
+}
+
+// sky, textures, the device's instance table (shading_rows; inst_slot[i]: instance i's row) and the materials
+void fill_tables(const rt_scene_desc& d, HostScene& hs, std::vector<uint32_t>& inst_slot) {
+    hs.sky[0] = d.sky[0], hs.sky[1] = d.sky[1], hs.sky[2] = d.sky[2];
+    hs.n_layers = d.n_layers;
+    if (d.n_layers) hs.tex.assign(d.textures, d.textures + (size_t)d.n_layers * 512u * 512u * 4u);
+    hs.packed_mat = d.n_instances <= (1u << kPackedInstBits) && d.n_materials <= (1u << (32u - kPackedInstBits));
+    std::vector<uint64_t> use(d.n_instances, 0);
+    for (uint32_t t = 0; t < d.n_triangles; ++t) use[d.tri_instance[t]]++;
+    shading_rows(d.instances, d.n_instances, use, hs.packed_mat, hs.inst, inst_slot);
+    hs.mats.resize(d.n_materials);
+    for (uint32_t i = 0; i < d.n_materials; ++i) {
+        const rt_material& m = d.materials[i];
+        MatRec& r = hs.mats[i];
+        r.type = m.type, r.tex_kind = m.tex_kind, r.tex_layer = m.tex_layer;
+        std::memcpy(r.color, m.color, 12), std::memcpy(r.emissive, m.emissive, 12);
+        r.roughness = m.roughness, r.ior = m.ior, r.pad = 0;
+    }
+}
+
+// world vertices, the triangle records in global order (e1 = v1 - v0, e2 = v2 - v0: part of the contract too) and the shading records
+void flatten(const rt_scene_desc& d, const std::vector<uint32_t>& inst_slot, HostScene& hs, std::vector<TriRec>& gtris) {
+    const uint32_t T = d.n_triangles;
+    world_vertices(T, d.indices, d.tri_instance, d.instances, d.positions, hs.wverts);
+    hs.shade.resize(T);
+    gtris.assign(T, TriRec{});
+    for (uint32_t t = 0; t < T; ++t) {
+        const float* p = &hs.wverts[9 * (size_t)t];
+        TriRec& tr = gtris[t];
+        for (int a = 0; a < 3; ++a) {
+            tr.v0[a] = p[a];
+            tr.e1[a] = p[3 + a] - p[a];
+            tr.e2[a] = p[6 + a] - p[a];
+        }
+        tr.global_index = t;
+        ShadeRec& s = hs.shade[t];
+        const uint32_t ii = d.tri_instance[t], i0 = d.indices[3 * t], i1 = d.indices[3 * t + 1], i2 = d.indices[3 * t + 2];
+        std::memcpy(s.n0, d.normals + 3 * i0, 12), std::memcpy(s.n1, d.normals + 3 * i1, 12);
+        std::memcpy(s.n2, d.normals + 3 * i2, 12);
+        std::memcpy(s.uv0, d.uvs + 2 * i0, 8), std::memcpy(s.uv1, d.uvs + 2 * i1, 8);
+        std::memcpy(s.uv2, d.uvs + 2 * i2, 8);
+        s.instance = hs.packed_mat ? (inst_slot[ii] | (d.instances[ii].material << kPackedInstBits)) : ii;
+    }
+}
+
+} // namespace
+
+int build_host_scene(const rt_scene_desc* d, int bvh_kind, HostScene& hs, std::string& err) {
+    if (const int rc = validate_desc(d, bvh_kind, err)) return rc;
+    hs = HostScene{};
+    std::vector<uint32_t> inst_slot;
+    fill_tables(*d, hs, inst_slot);
+    std::vector<TriRec> gtris;
+    flatten(*d, inst_slot, hs, gtris);
+    if (gtris.empty()) {
+        hs.built_by = (int8_t)bvh_kind;
+        hs.nodes.assign(1, empty_node());
+        hs.tris.assign(1, TriRec{}); // one dummy record so device pointers are never null
+        hs.tris[0].global_index = kNoTri;
+        return RT_OK;
+    }
+    if (!world_bounds(hs.wverts, hs.bounds_lo, hs.bounds_hi, hs.pad, err)) return RT_ERR_INVALID;
+    const BuildOptions options;
+    for (int kind = bvh_kind;; kind = RT_BVH_MEDIAN_INTERNAL) { // the requested builder, then the balanced fallback
+        const int rc = build_tree(kind, gtris, options, hs, err);
+        if (rc != kTooDeep) return rc;
+        if (kind == RT_BVH_MEDIAN_INTERNAL) { err = "internal: BVH deeper than the traversal stack"; return RT_ERR_INVALID; }
+        err.clear();
+    }
+}
+
+void world_vertices(uint32_t n_tris, const uint32_t* indices, const uint32_t* tri_instance, const rt_instance* inst, const float* positions,
+                    std::vector<float>& wv) {
+    wv.resize(9 * (size_t)n_tris);
+    for (uint32_t t = 0; t < n_tris; ++t) {
+        const float* m = inst[tri_instance[t]].transform;
+        for (int k = 0; k < 3; ++k) {
+            const uint32_t vi = indices[3 * (size_t)t + k];
+            const float x = positions[3 * (size_t)vi], y = positions[3 * (size_t)vi + 1], z = positions[3 * (size_t)vi + 2];
+            float* p = &wv[9 * (size_t)t + 3 * k];
+            p[0] = ((m[0] * x + m[4] * y) + m[8] * z) + m[12];
+            p[1] = ((m[1] * x + m[5] * y) + m[9] * z) + m[13];
+            p[2] = ((m[2] * x + m[6] * y) + m[10] * z) + m[14];
+        }
+    }
+}
+
+bool world_bounds(const std::vector<float>& wv, float lo[3], float hi[3], float& pad, std::string& err) {
+    for (float v : wv)
+        if (!std::isfinite(v)) { err = "non-finite world-space vertex"; return false; }
+    for (int a = 0; a < 3; ++a) lo[a] = INFINITY, hi[a] = -INFINITY;
+    for (size_t i = 0; i < wv.size(); ++i) {
+        const int a = (int)(i % 3);
+        lo[a] = std::min(lo[a], wv[i]), hi[a] = std::max(hi[a], wv[i]);
+    }
+    return scene_padding(lo, hi, pad, err);
+}
+
+void scene_cells(const HostScene& hs, SceneDev& dev) {
+    for (int a = 0; a < 3; ++a) {
+        const float ext = hs.bounds_hi[a] - hs.bounds_lo[a];
+        dev.cell_lo[a] = hs.bounds_lo[a];
+        dev.cell_scale[a] = ext > 0.0f && std::isfinite(ext) ? 4.0f / ext : 0.0f;
+    }
 }
 
 // The device's instance table. Packed shading word (the rule, rt_types.h): the material index travels in the word, so what is left of an
@@ -1012,309 +979,58 @@ void node_levels(const std::vector<BvhNode>& nodes, std::vector<uint32_t>& level
         if (reached[i]) level_nodes[at[height[i]]++] = i;
 }
 
-bool refit_host(HostScene& hs, const std::vector<uint32_t>& level_nodes, std::vector<float>& box, std::string& err) {
-    const float inf = std::numeric_limits<float>::infinity();
-    // leaf records: the packed v0 / e1 / e2 of their triangle, and the whole triangle's box (a pre-split triangle's pieces mean nothing now)
+void record_boxes(HostScene& hs) {
     hs.rec_lo.assign(3 * hs.tris.size(), 0.0f), hs.rec_hi.assign(3 * hs.tris.size(), 0.0f);
     for (size_t r = 0; r < hs.tris.size(); ++r) {
-        TriRec& tr = hs.tris[r];
+        if (hs.tris[r].global_index == kNoTri) continue;
+        const float* w = &hs.wverts[9 * (size_t)hs.tris[r].global_index];
+        for (int a = 0; a < 3; ++a)
+            hs.rec_lo[3 * r + a] = std::min(w[a], std::min(w[3 + a], w[6 + a])), hs.rec_hi[3 * r + a] = std::max(w[a], std::max(w[3 + a], w[6 + a]));
+    }
+}
+
+Box3 leaf_bounds(const HostScene& hs, int32_t child) {
+    const bool split = hs.rec_lo.size() == 3 * hs.tris.size() && hs.rec_hi.size() == 3 * hs.tris.size() && hs.n_split_triangles > 0;
+    const LeafRange leaf = leaf_range(child);
+    Box3 b{{INFINITY, INFINITY, INFINITY}, {-INFINITY, -INFINITY, -INFINITY}};
+    for (uint32_t r = leaf.first; r < leaf.first + leaf.count; ++r) {
+        if (split) {
+            for (int a = 0; a < 3; ++a) b.lo[a] = std::min(b.lo[a], hs.rec_lo[3 * (size_t)r + a]), b.hi[a] = std::max(b.hi[a], hs.rec_hi[3 * (size_t)r + a]);
+        } else {
+            const float* w = &hs.wverts[9 * (size_t)hs.tris[r].global_index];
+            for (int v = 0; v < 3; ++v)
+                for (int a = 0; a < 3; ++a) b.lo[a] = std::min(b.lo[a], w[3 * v + a]), b.hi[a] = std::max(b.hi[a], w[3 * v + a]);
+        }
+    }
+    return b;
+}
+
+bool refit_host(HostScene& hs, const std::vector<uint32_t>& level_nodes, std::vector<float>& box, std::string& err) {
+    // leaf records: the packed v0 / e1 / e2 of their triangle, and the whole triangle's box (a pre-split triangle's pieces mean nothing now)
+    record_boxes(hs);
+    for (TriRec& tr : hs.tris) {
         if (tr.global_index == kNoTri) continue;
         const float* w = &hs.wverts[9 * (size_t)tr.global_index];
-        for (int a = 0; a < 3; ++a) {
-            tr.v0[a] = w[a];
-            tr.e1[a] = w[3 + a] - w[a];
-            tr.e2[a] = w[6 + a] - w[a];
-            hs.rec_lo[3 * r + a] = std::min(w[a], std::min(w[3 + a], w[6 + a]));
-            hs.rec_hi[3 * r + a] = std::max(w[a], std::max(w[3 + a], w[6 + a]));
-        }
+        for (int a = 0; a < 3; ++a) tr.v0[a] = w[a], tr.e1[a] = w[3 + a] - w[a], tr.e2[a] = w[6 + a] - w[a];
     }
     box.assign(6 * hs.nodes.size(), 0.0f);
     for (uint32_t i : level_nodes) {
         BvhNode& n = hs.nodes[i];
-        float klo[4][3], khi[4][3];
+        Box3 kb[4];
         int nk = 0;
         for (int k = 0; k < 4 && n.child[k] != kChildEmpty; ++k, ++nk) {
-            float lo[3] = {inf, inf, inf}, hi[3] = {-inf, -inf, -inf};
-            if (n.child[k] >= 0) {
-                const float* b = &box[6 * (size_t)n.child[k]];
-                for (int a = 0; a < 3; ++a) lo[a] = b[a], hi[a] = b[3 + a];
-            } else {
-                const uint32_t code = (uint32_t)~n.child[k], first = code >> 2, count = (code & 3u) + 1u;
-                for (uint32_t r = first; r < first + count; ++r)
-                    for (int a = 0; a < 3; ++a)
-                        lo[a] = std::min(lo[a], hs.rec_lo[3 * (size_t)r + a]), hi[a] = std::max(hi[a], hs.rec_hi[3 * (size_t)r + a]);
-            }
+            if (n.child[k] >= 0) std::memcpy(&kb[k], &box[6 * (size_t)n.child[k]], sizeof(Box3));
+            else kb[k] = leaf_bounds(hs, n.child[k]);
             float* b = &box[6 * (size_t)i];
-            for (int a = 0; a < 3; ++a) {
-                b[a] = k ? std::min(b[a], lo[a]) : lo[a], b[3 + a] = k ? std::max(b[3 + a], hi[a]) : hi[a];
-                klo[k][a] = lo[a] - hs.pad, khi[k][a] = hi[a] + hs.pad;
-            }
+            for (int a = 0; a < 3; ++a) b[a] = k ? std::min(b[a], kb[k].lo[a]) : kb[k].lo[a], b[3 + a] = k ? std::max(b[3 + a], kb[k].hi[a]) : kb[k].hi[a];
         }
         if (nk == 0) continue; // the empty scene's root
         BvhNode q = n;
-        if (!quantise_node(q, nk, klo, khi)) { err = "a refit node's child boxes could not be quantised"; return false; }
+        if (!quantise_node(q, nk, kb, hs.pad)) { err = "a refit node's child boxes could not be quantised"; return false; }
         std::memcpy(&n, &q, 48); // words 0..11; the child words stay
     }
     hs.sah_cost = refit_sah_cost(hs, box);
     return true;
 }
 
-// Surface-area cost of a device-built tree (the diagnostic rt_scene_info reports for the host builders too): every node's children boxes
-// decoded, inner child 1 step x area, leaf child (triangles) x area, relative to the root's area.
-double decoded_sah_cost(const HostScene& hs) {
-    double cost = 0.0, root_area = 0.0;
-    for (size_t i = 0; i < hs.nodes.size(); ++i) {
-        const BvhNode& n = hs.nodes[i];
-        float nlo[3] = {INFINITY, INFINITY, INFINITY}, nhi[3] = {-INFINITY, -INFINITY, -INFINITY};
-        for (int k = 0; k < 4; ++k) {
-            if (n.child[k] == kChildEmpty) continue;
-            float lo[3], hi[3];
-            for (int a = 0; a < 3; ++a) {
-                lo[a] = n.origin[a] + (float)((n.q[2 * a] >> (8 * k)) & 0xffu) * n.scale(a);
-                hi[a] = n.origin[a] + (float)((n.q[2 * a + 1] >> (8 * k)) & 0xffu) * n.scale(a);
-                nlo[a] = std::min(nlo[a], lo[a]), nhi[a] = std::max(nhi[a], hi[a]);
-            }
-            const double w = n.child[k] >= 0 ? 1.0 : (double)(((uint32_t)~n.child[k] & 3u) + 1u);
-            cost += w * (double)half_area(lo, hi);
-        }
-        if (i == 0) root_area = (double)half_area(nlo, nhi);
-    }
-    return root_area > 0.0 ? 1.0 + cost / root_area : 0.0;
-}
-
-double refit_sah_cost(const HostScene& hs, const std::vector<float>& box) {
-    if (hs.built_by == RT_BVH_LBVH_GPU) return decoded_sah_cost(hs); // the measure its build reported: the same tree, the same cost
-    if (hs.nodes.empty() || box.size() < 6 * hs.nodes.size()) return 0.0;
-    const double root_area = std::max(1e-30, (double)half_area(&box[0], &box[3]));
-    double cost = 0.0;
-    for (size_t i = 0; i < hs.nodes.size(); ++i) {
-        const BvhNode& n = hs.nodes[i];
-        for (int k = 0; k < 4; ++k) {
-            if (n.child[k] == kChildEmpty) continue;
-            if (n.child[k] >= 0) {
-                cost += (double)half_area(&box[6 * (size_t)n.child[k]], &box[6 * (size_t)n.child[k] + 3]) / root_area;
-            } else {
-                const uint32_t code = (uint32_t)~n.child[k], first = code >> 2, count = (code & 3u) + 1u;
-                float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-                for (uint32_t r = first; r < first + count && 3 * (size_t)r + 2 < hs.rec_lo.size(); ++r)
-                    for (int a = 0; a < 3; ++a)
-                        lo[a] = std::min(lo[a], hs.rec_lo[3 * (size_t)r + a]), hi[a] = std::max(hi[a], hs.rec_hi[3 * (size_t)r + a]);
-                cost += (double)half_area(lo, hi) / root_area * (double)count;
-            }
-        }
-    }
-    return 1.0 + cost;
-}
-
-int check_bvh(const HostScene& hs, std::string& err) {
-    const size_t T = hs.wverts.size() / 9;
-    if (hs.nodes.empty()) { err = "no root node"; return RT_ERR_INVALID; }
-    std::vector<uint32_t> seen(T, 0);
-    // pre-split trees (scene_build.cpp: presplit): a triangle may sit in several leaves, each with the box of its pieces there
-    const bool split = hs.rec_lo.size() == 3 * hs.tris.size() && hs.rec_hi.size() == 3 * hs.tris.size() && hs.n_split_triangles > 0;
-    std::vector<std::vector<uint32_t>> pieces(split ? T : 0);
-    size_t visited = 0;
-    bool ok = true;
-    const float inf = std::numeric_limits<float>::infinity();
-    // returns the exact bounds of everything below `child`; checks them against every decoded box above
-    struct B { float lo[3], hi[3]; };
-    auto fail = [&](const std::string& m) { if (ok) err = m; ok = false; };
-    std::function<B(int32_t, uint32_t)> walk = [&](int32_t child, uint32_t depth) -> B {
-        B r;
-        for (int a = 0; a < 3; ++a) r.lo[a] = inf, r.hi[a] = -inf;
-        if (!ok) return r;
-        if (depth >= (uint32_t)kStackSize) { fail("tree deeper than traversal stack"); return r; }
-        if (child >= 0) {
-            if ((size_t)child >= hs.nodes.size()) { fail("child index out of range"); return r; }
-            if (++visited > hs.nodes.size()) { fail("cycle in node graph"); return r; }
-            const BvhNode& n = hs.nodes[child];
-            for (int k = 0; k < 4; ++k) {
-                if (n.child[k] == kChildEmpty) continue;
-                B c = walk(n.child[k], depth + 1);
-                if (!ok) return r;
-                for (int a = 0; a < 3; ++a) {
-                    const float s = n.scale(a);
-                    const float dlo = n.origin[a] + (float)((n.q[2 * a] >> (8 * k)) & 0xffu) * s;
-                    const float dhi = n.origin[a] + (float)((n.q[2 * a + 1] >> (8 * k)) & 0xffu) * s;
-                    // the decoded box must contain the subtree with at least half the builder's pad to spare
-                    if (!(dlo <= c.lo[a] - 0.5f * hs.pad) || !(dhi >= c.hi[a] + 0.5f * hs.pad)) {
-                        fail("decoded child box does not contain its subtree (node " + std::to_string(child) + ")");
-                        return r;
-                    }
-                    r.lo[a] = std::min(r.lo[a], c.lo[a]), r.hi[a] = std::max(r.hi[a], c.hi[a]);
-                }
-            }
-        } else {
-            uint32_t code = (uint32_t)~child;
-            uint32_t first = code >> 2, count = (code & 3u) + 1u;
-            if ((size_t)first + count > hs.tris.size()) { fail("leaf range out of bounds"); return r; }
-            for (uint32_t k = 0; k < count; ++k) {
-                const TriRec& tr = hs.tris[first + k];
-                if (tr.global_index >= T) { fail("leaf triangle has bad global index"); return r; }
-                for (uint32_t j = 0; j < k; ++j)
-                    if (hs.tris[first + j].global_index == tr.global_index) { fail("triangle twice in one leaf"); return r; }
-                if (seen[tr.global_index]++ && !split) { fail("triangle appears in two leaves"); return r; }
-                const float* w = &hs.wverts[9 * (size_t)tr.global_index];
-                if (tr.v0[0] != w[0] || tr.v0[1] != w[1] || tr.v0[2] != w[2]) { fail("leaf triangle data mismatch"); return r; }
-                if (split) { // the box of the triangle's pieces in THIS leaf (the whole triangle where it was not split)
-                    const float* plo = &hs.rec_lo[3 * (size_t)(first + k)];
-                    const float* phi = &hs.rec_hi[3 * (size_t)(first + k)];
-                    for (int a = 0; a < 3; ++a) r.lo[a] = std::min(r.lo[a], plo[a]), r.hi[a] = std::max(r.hi[a], phi[a]);
-                    pieces[tr.global_index].push_back(first + k);
-                } else {
-                    for (int v = 0; v < 3; ++v)
-                        for (int a = 0; a < 3; ++a) r.lo[a] = std::min(r.lo[a], w[3 * v + a]), r.hi[a] = std::max(r.hi[a], w[3 * v + a]);
-                }
-            }
-        }
-        return r;
-    };
-    (void)walk(0, 0);
-    if (!ok) return RT_ERR_INVALID;
-    for (size_t t = 0; t < T; ++t)
-        if (!seen[t]) { err = "triangle " + std::to_string(t) + " is in no leaf"; return RT_ERR_INVALID; }
-    if (split) { // the pieces of a split triangle must cover it: every point of a barycentric grid lies in the box of one of its records
-        for (size_t t = 0; t < T; ++t) {
-            if (pieces[t].size() < 2) continue;
-            const float* w = &hs.wverts[9 * t];
-            for (int i = 0; i <= 8; ++i)
-                for (int j = 0; i + j <= 8; ++j) {
-                    const double u = i / 8.0, v = j / 8.0, ww = 1.0 - u - v;
-                    double p[3];
-                    for (int a = 0; a < 3; ++a) p[a] = ww * w[a] + u * w[3 + a] + v * w[6 + a];
-                    bool in = false;
-                    for (uint32_t rec : pieces[t]) {
-                        bool inside = true;
-                        for (int a = 0; a < 3; ++a) {
-                            const double tol = 1e-6 * (std::fabs(p[a]) + 1.0);
-                            inside = inside && p[a] >= (double)hs.rec_lo[3 * (size_t)rec + a] - tol && p[a] <= (double)hs.rec_hi[3 * (size_t)rec + a] + tol;
-                        }
-                        in = in || inside;
-                    }
-                    if (!in) { err = "the pieces of split triangle " + std::to_string(t) + " do not cover it"; return RT_ERR_INVALID; }
-                }
-        }
-    }
-    return RT_OK;
-}
-
-} // namespace rt
-
-// ---- diagnostic: node visits of a closest-hit walk on the host (rt_scene_count_visits) --------------------------------------------------------
-// The walk the traversal kernels make — children entered nearest first, the others stacked, everything beyond the closest hit so far culled —
-// with a choice of the child boxes it tests:
-//   mode 0  the decoded quantised boxes, as the kernels test them
-//   mode 1  the exact bounds of each child's subtree, padded as the builder pads them: what an unquantised (fp32) node would hold
-//   mode 2  the exact padded bounds re-quantised on the node's grid with 2 more bits per plane (step / 4)
-// so that the share of the visits that is the price of 8-bit planes can be read off. Counts only: no result of a
-// render depends on it.
-namespace rt {
-int count_visits(const HostScene& hs, uint32_t n, const float* org, const float* dir, int mode, uint64_t* node_visits, uint64_t* tri_tests, float* t_out,
-                 uint32_t* tri_out, std::string& err) {
-    if (mode < 0 || mode > 2) { err = "mode: 0 quantised, 1 exact, 2 quantised with two more bits"; return RT_ERR_INVALID; }
-    if (hs.nodes.empty()) { err = "no tree"; return RT_ERR_INVALID; }
-    const float inf = std::numeric_limits<float>::infinity();
-    const bool split = hs.rec_lo.size() == 3 * hs.tris.size() && hs.rec_hi.size() == 3 * hs.tris.size() && hs.n_split_triangles > 0;
-    struct B { float lo[3], hi[3]; };
-    std::vector<B> box(hs.nodes.size() * 4); // the box tested for child k of node i
-    std::function<B(int32_t)> walk = [&](int32_t child) -> B {
-        B r;
-        for (int a = 0; a < 3; ++a) r.lo[a] = inf, r.hi[a] = -inf;
-        if (child >= 0) {
-            const BvhNode& nd = hs.nodes[(size_t)child];
-            for (int k = 0; k < 4; ++k) {
-                if (nd.child[k] == kChildEmpty) continue;
-                const B c = walk(nd.child[k]);
-                B& out = box[(size_t)child * 4 + k];
-                for (int a = 0; a < 3; ++a) {
-                    r.lo[a] = std::min(r.lo[a], c.lo[a]), r.hi[a] = std::max(r.hi[a], c.hi[a]);
-                    const float s = nd.scale(a);
-                    if (mode == 0) {
-                        out.lo[a] = nd.origin[a] + (float)((nd.q[2 * a] >> (8 * k)) & 0xffu) * s;
-                        out.hi[a] = nd.origin[a] + (float)((nd.q[2 * a + 1] >> (8 * k)) & 0xffu) * s;
-                    } else if (mode == 1) {
-                        out.lo[a] = c.lo[a] - hs.pad, out.hi[a] = c.hi[a] + hs.pad;
-                    } else {
-                        const float q = s * 0.25f;
-                        out.lo[a] = nd.origin[a] + std::floor((c.lo[a] - hs.pad - nd.origin[a]) / q) * q;
-                        out.hi[a] = nd.origin[a] + std::ceil((c.hi[a] + hs.pad - nd.origin[a]) / q) * q;
-                    }
-                }
-            }
-        } else {
-            const uint32_t code = (uint32_t)~child, first = code >> 2, count = (code & 3u) + 1u;
-            for (uint32_t k = 0; k < count; ++k) {
-                if (split) {
-                    for (int a = 0; a < 3; ++a)
-                        r.lo[a] = std::min(r.lo[a], hs.rec_lo[3 * (size_t)(first + k) + a]), r.hi[a] = std::max(r.hi[a], hs.rec_hi[3 * (size_t)(first + k) + a]);
-                } else {
-                    const float* w = &hs.wverts[9 * (size_t)hs.tris[first + k].global_index];
-                    for (int v = 0; v < 3; ++v)
-                        for (int a = 0; a < 3; ++a) r.lo[a] = std::min(r.lo[a], w[3 * v + a]), r.hi[a] = std::max(r.hi[a], w[3 * v + a]);
-                }
-            }
-        }
-        return r;
-    };
-    (void)walk(0);
-    uint64_t visits = 0, tests = 0;
-    for (uint32_t i = 0; i < n; ++i) {
-        const float o[3] = {org[3 * i], org[3 * i + 1], org[3 * i + 2]}, d[3] = {dir[3 * i], dir[3 * i + 1], dir[3 * i + 2]};
-        float inv[3];
-        for (int a = 0; a < 3; ++a) inv[a] = 1.0f / (std::fabs(d[a]) < 1e-30f ? std::copysign(1e-30f, d[a]) : d[a]);
-        float best = inf;
-        uint32_t best_tri = kNoTri;
-        int32_t stack[kStackSize * 4];
-        int sp = 0;
-        int32_t cur = 0;
-        for (;;) {
-            if (cur >= 0) {
-                visits++;
-                const BvhNode& nd = hs.nodes[(size_t)cur];
-                float key[4];
-                int32_t ch[4];
-                int m = 0;
-                for (int k = 0; k < 4; ++k) {
-                    if (nd.child[k] == kChildEmpty) continue;
-                    const B& b = box[(size_t)cur * 4 + k];
-                    float tn = 0.0f, tf = best;
-                    for (int a = 0; a < 3; ++a) {
-                        const float t0 = (b.lo[a] - o[a]) * inv[a], t1 = (b.hi[a] - o[a]) * inv[a];
-                        tn = std::max(tn, std::min(t0, t1)), tf = std::min(tf, std::max(t0, t1));
-                    }
-                    if (tn <= tf) key[m] = tn, ch[m] = nd.child[k], m++;
-                }
-                for (int a = 1; a < m; ++a) // nearest first
-                    for (int b = a; b > 0 && key[b] < key[b - 1]; --b) std::swap(key[b], key[b - 1]), std::swap(ch[b], ch[b - 1]);
-                for (int a = m - 1; a >= 1; --a) stack[sp++] = ch[a];
-                if (m) { cur = ch[0]; continue; }
-            } else {
-                const uint32_t code = (uint32_t)~cur, first = code >> 2, count = (code & 3u) + 1u;
-                for (uint32_t k = 0; k < count; ++k) {
-                    tests++;
-                    const TriRec& tr = hs.tris[first + k];
-                    // Moller-Trumbore on (v0, e1, e2), in double: only the count matters here
-                    const double e1[3] = {tr.e1[0], tr.e1[1], tr.e1[2]}, e2[3] = {tr.e2[0], tr.e2[1], tr.e2[2]};
-                    const double p[3] = {d[1] * e2[2] - d[2] * e2[1], d[2] * e2[0] - d[0] * e2[2], d[0] * e2[1] - d[1] * e2[0]};
-                    const double det = e1[0] * p[0] + e1[1] * p[1] + e1[2] * p[2];
-                    if (det == 0.0) continue;
-                    const double tv[3] = {o[0] - tr.v0[0], o[1] - tr.v0[1], o[2] - tr.v0[2]};
-                    const double u = (tv[0] * p[0] + tv[1] * p[1] + tv[2] * p[2]) / det;
-                    const double q[3] = {tv[1] * e1[2] - tv[2] * e1[1], tv[2] * e1[0] - tv[0] * e1[2], tv[0] * e1[1] - tv[1] * e1[0]};
-                    const double v = (d[0] * q[0] + d[1] * q[1] + d[2] * q[2]) / det;
-                    if (u < 0.0 || v < 0.0 || u + v > 1.0) continue;
-                    const double t = (e2[0] * q[0] + e2[1] * q[1] + e2[2] * q[2]) / det;
-                    if (t > (double)kTNear && (t < best || (t == best && tr.global_index < best_tri))) best = (float)t, best_tri = tr.global_index;
-                }
-            }
-            if (sp == 0) break;
-            cur = stack[--sp];
-        }
-        if (t_out) t_out[i] = best;
-        if (tri_out) tri_out[i] = best_tri;
-    }
-    if (node_visits) *node_visits = visits;
-    if (tri_tests) *tri_tests = tests;
-    return RT_OK;
-}
 } // namespace rt

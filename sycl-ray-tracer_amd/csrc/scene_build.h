@@ -38,10 +38,26 @@ int build_host_scene(const rt_scene_desc* desc, int bvh_kind, HostScene& out, st
 // lbvh_gpu.hip: BVH construction on the current HIP device; fills hs.nodes / hs.tris (downloaded copies).
 int build_lbvh_gpu(HostScene& hs, const std::vector<TriRec>& gtris, std::string& err);
 
-#ifdef RT_DEVELOPER_KNOBS
-// Developer library only: quantise_node (the host quantiser every host builder uses) on nk <= 4 already padded child boxes.
-bool quantise_node_dev_export(BvhNode& n, int nk, const float (*klo)[3], const float (*khi)[3]);
-#endif
+// ---- the scene-geometry rules, each written once ------------------------------------------------------------------------------------------
+// World-space vertices of a triangle list under a transform table, 9 floats per triangle: world = ((m0*x + m4*y) + m8*z) + m12 per row of
+// the column-major instance matrix. The expression is part of the arithmetic contract with the CPU oracle and stands here only.
+void world_vertices(uint32_t n_tris, const uint32_t* indices, const uint32_t* tri_instance, const rt_instance* inst, const float* positions,
+                    std::vector<float>& wv);
+// Refuses non-finite vertices, reduces the rest to the scene's bounds (std::min / std::max: the first of equal values stays, the sign of a
+// zero bound depends on it) and derives the box padding (scene_padding). Returns false with err set.
+bool world_bounds(const std::vector<float>& wv, float lo[3], float hi[3], float& pad, std::string& err);
+// The ray re-ordering cells of a device scene (SceneDev::cell_lo / cell_scale) from the scene's bounds.
+void scene_cells(const HostScene& hs, SceneDev& dev);
+// rec_lo / rec_hi of every leaf record as the whole triangle's box (what a refit leaves of a pre-split triangle's pieces).
+void record_boxes(HostScene& hs);
+// Exact bounds of a leaf child: the union of its records' boxes — the box of the triangle's pieces in that leaf where the tree is pre-split,
+// else the whole triangle's, from hs.wverts.
+Box3 leaf_bounds(const HostScene& hs, int32_t child);
+inline float half_area(const float* lo, const float* hi) {
+    float dx = hi[0] - lo[0], dy = hi[1] - lo[1], dz = hi[2] - lo[2];
+    if (!(dx >= 0 && dy >= 0 && dz >= 0)) return 0.0f;
+    return dx * dy + dy * dz + dz * dx;
+}
 
 // ---- dynamic scenes (rt_scene_update) ---------------------------------------------------------------------------------------------------
 // The device's instance table from the instances' normal matrices (the packed shading word's distinct-matrix grouping, rt_types.h): `use`
@@ -58,12 +74,13 @@ void node_levels(const std::vector<BvhNode>& nodes, std::vector<uint32_t>& level
 // its rec_lo / rec_hi box (the whole triangle's), every node's exact child boxes (box: 6 floats per node, the union of its children) and its
 // quantised words 0..11 with hs.pad, level by level, and hs.sah_cost. Returns false if a node cannot be quantised.
 bool refit_host(HostScene& hs, const std::vector<uint32_t>& level_nodes, std::vector<float>& box, std::string& err);
-// Surface-area cost of a refit tree from the nodes' exact boxes (box, 6 floats per node): inner child 1 x area, leaf child its records x
+// (scene_check.cpp) Surface-area cost of a refit tree from the nodes' exact boxes (box, 6 floats per node): inner child 1 x area, leaf child its records x
 // area, relative to the root's area. A device-built tree (RT_BVH_LBVH_GPU) keeps the measure its build reported, decoded_sah_cost.
 double refit_sah_cost(const HostScene& hs, const std::vector<float>& box);
 // The same cost from the nodes' decoded (quantised, padded) child boxes: what a device build reports.
 double decoded_sah_cost(const HostScene& hs);
 
+// ---- diagnostics (scene_check.cpp) ----------------------------------------------------------------------------------------------------------
 // Structural check used by rt_scene_check_bvh.
 int check_bvh(const HostScene& hs, std::string& err);
 

@@ -1,0 +1,235 @@
+// scene_check.cpp — host diagnostics of a built scene: the two surface-area costs rt_scene_info reports, the structural check behind
+// rt_scene_check_bvh and the node-visit count behind rt_scene_count_visits. Nothing here decides anything about a tree or a render.
+#include "scene_build.h"
+
+#include <algorithm>
+#include <cmath>
+#include <limits>
+
+namespace rt {
+namespace {
+
+void grow(Box3& r, const Box3& c) {
+    for (int a = 0; a < 3; ++a) r.lo[a] = std::min(r.lo[a], c.lo[a]), r.hi[a] = std::max(r.hi[a], c.hi[a]);
+}
+
+// Depth-first walk below `child`: r receives the exact bounds of everything below it, visit(node, k, box) the exact subtree box of every
+// child k of every inner node on the way (children before their parents). enter(child, depth) runs before a child is read; either
+// callback stops the walk by returning false, and so does the walk itself.
+template <class Enter, class Visit>
+bool exact_boxes(const HostScene& hs, int32_t child, uint32_t depth, Box3& r, Enter&& enter, Visit&& visit) {
+    const float inf = std::numeric_limits<float>::infinity();
+    r = Box3{{inf, inf, inf}, {-inf, -inf, -inf}};
+    if (!enter(child, depth)) return false;
+    if (child < 0) {
+        r = leaf_bounds(hs, child);
+        return true;
+    }
+    const BvhNode& n = hs.nodes[(size_t)child];
+    for (int k = 0; k < 4; ++k) {
+        if (n.child[k] == kChildEmpty) continue;
+        Box3 c;
+        if (!exact_boxes(hs, n.child[k], depth + 1, c, enter, visit) || !visit(child, k, c)) return false;
+        grow(r, c);
+    }
+    return true;
+}
+
+} // namespace
+
+// Surface-area cost of a device-built tree (the diagnostic rt_scene_info reports for the host builders too): every node's children boxes
+// decoded, inner child 1 step x area, leaf child (triangles) x area, relative to the root's area.
+double decoded_sah_cost(const HostScene& hs) {
+    double cost = 0.0, root_area = 0.0;
+    for (size_t i = 0; i < hs.nodes.size(); ++i) {
+        const BvhNode& n = hs.nodes[i];
+        Box3 nb{{INFINITY, INFINITY, INFINITY}, {-INFINITY, -INFINITY, -INFINITY}};
+        for (int k = 0; k < 4; ++k) {
+            if (n.child[k] == kChildEmpty) continue;
+            const Box3 b = child_box(n, k);
+            grow(nb, b);
+            const double w = n.child[k] >= 0 ? 1.0 : (double)leaf_range(n.child[k]).count;
+            cost += w * (double)half_area(b.lo, b.hi);
+        }
+        if (i == 0) root_area = (double)half_area(nb.lo, nb.hi);
+    }
+    return root_area > 0.0 ? 1.0 + cost / root_area : 0.0;
+}
+
+double refit_sah_cost(const HostScene& hs, const std::vector<float>& box) {
+    if (hs.built_by == RT_BVH_LBVH_GPU) return decoded_sah_cost(hs); // the measure its build reported: the same tree, the same cost
+    if (hs.nodes.empty() || box.size() < 6 * hs.nodes.size()) return 0.0;
+    const double root_area = std::max(1e-30, (double)half_area(&box[0], &box[3]));
+    double cost = 0.0;
+    for (const BvhNode& n : hs.nodes)
+        for (int k = 0; k < 4; ++k) {
+            if (n.child[k] == kChildEmpty) continue;
+            if (n.child[k] >= 0) {
+                cost += (double)half_area(&box[6 * (size_t)n.child[k]], &box[6 * (size_t)n.child[k] + 3]) / root_area;
+            } else {
+                const Box3 b = leaf_bounds(hs, n.child[k]);
+                cost += (double)half_area(b.lo, b.hi) / root_area * (double)leaf_range(n.child[k]).count;
+            }
+        }
+    return 1.0 + cost;
+}
+
+int check_bvh(const HostScene& hs, std::string& err) {
+    const size_t T = hs.wverts.size() / 9;
+    if (hs.nodes.empty()) { err = "no root node"; return RT_ERR_INVALID; }
+    std::vector<uint32_t> seen(T, 0);
+    // pre-split trees (scene_build.cpp: presplit): a triangle may sit in several leaves, each with the box of its pieces there
+    const bool split = hs.rec_lo.size() == 3 * hs.tris.size() && hs.rec_hi.size() == 3 * hs.tris.size() && hs.n_split_triangles > 0;
+    std::vector<std::vector<uint32_t>> pieces(split ? T : 0);
+    size_t visited = 0;
+    auto fail = [&](const std::string& m) { err = m; return false; };
+    auto enter = [&](int32_t child, uint32_t depth) { // everything the walk is about to read
+        if (depth >= (uint32_t)kStackSize) return fail("tree deeper than traversal stack");
+        if (child >= 0) {
+            if ((size_t)child >= hs.nodes.size()) return fail("child index out of range");
+            if (++visited > hs.nodes.size()) return fail("cycle in node graph");
+            return true;
+        }
+        const LeafRange leaf = leaf_range(child);
+        if ((size_t)leaf.first + leaf.count > hs.tris.size()) return fail("leaf range out of bounds");
+        for (uint32_t k = 0; k < leaf.count; ++k) {
+            const TriRec& tr = hs.tris[leaf.first + k];
+            if (tr.global_index >= T) return fail("leaf triangle has bad global index");
+            for (uint32_t j = 0; j < k; ++j)
+                if (hs.tris[leaf.first + j].global_index == tr.global_index) return fail("triangle twice in one leaf");
+            if (seen[tr.global_index]++ && !split) return fail("triangle appears in two leaves");
+            const float* w = &hs.wverts[9 * (size_t)tr.global_index];
+            if (tr.v0[0] != w[0] || tr.v0[1] != w[1] || tr.v0[2] != w[2]) return fail("leaf triangle data mismatch");
+            if (split) pieces[tr.global_index].push_back(leaf.first + k);
+        }
+        return true;
+    };
+    auto contained = [&](int32_t node, int k, const Box3& c) { // the decoded box must contain the subtree with at least half the builder's pad to spare
+        const Box3 d = child_box(hs.nodes[(size_t)node], k);
+        for (int a = 0; a < 3; ++a)
+            if (!(d.lo[a] <= c.lo[a] - 0.5f * hs.pad) || !(d.hi[a] >= c.hi[a] + 0.5f * hs.pad))
+                return fail("decoded child box does not contain its subtree (node " + std::to_string(node) + ")");
+        return true;
+    };
+    Box3 all;
+    if (!exact_boxes(hs, 0, 0, all, enter, contained)) return RT_ERR_INVALID;
+    for (size_t t = 0; t < T; ++t)
+        if (!seen[t]) { err = "triangle " + std::to_string(t) + " is in no leaf"; return RT_ERR_INVALID; }
+    if (split) { // the pieces of a split triangle must cover it: every point of a barycentric grid lies in the box of one of its records
+        for (size_t t = 0; t < T; ++t) {
+            if (pieces[t].size() < 2) continue;
+            const float* w = &hs.wverts[9 * t];
+            for (int i = 0; i <= 8; ++i)
+                for (int j = 0; i + j <= 8; ++j) {
+                    const double u = i / 8.0, v = j / 8.0, ww = 1.0 - u - v;
+                    double p[3];
+                    for (int a = 0; a < 3; ++a) p[a] = ww * w[a] + u * w[3 + a] + v * w[6 + a];
+                    bool in = false;
+                    for (uint32_t rec : pieces[t]) {
+                        bool inside = true;
+                        for (int a = 0; a < 3; ++a) {
+                            const double tol = 1e-6 * (std::fabs(p[a]) + 1.0);
+                            inside = inside && p[a] >= (double)hs.rec_lo[3 * (size_t)rec + a] - tol && p[a] <= (double)hs.rec_hi[3 * (size_t)rec + a] + tol;
+                        }
+                        in = in || inside;
+                    }
+                    if (!in) { err = "the pieces of split triangle " + std::to_string(t) + " do not cover it"; return RT_ERR_INVALID; }
+                }
+        }
+    }
+    return RT_OK;
+}
+
+// ---- node visits of a closest-hit walk on the host (rt_scene_count_visits) --------------------------------------------------------------------
+// The walk the traversal kernels make — children entered nearest first, the others stacked, everything beyond the closest hit so far culled —
+// with a choice of the child boxes it tests:
+//   mode 0  the decoded quantised boxes, as the kernels test them
+//   mode 1  the exact bounds of each child's subtree, padded as the builder pads them: what an unquantised (fp32) node would hold
+//   mode 2  the exact padded bounds re-quantised on the node's grid with 2 more bits per plane (step / 4)
+// so that the share of the visits that is the price of 8-bit planes can be read off. Counts only: no result of a
+// render depends on it.
+int count_visits(const HostScene& hs, uint32_t n, const float* org, const float* dir, int mode, uint64_t* node_visits, uint64_t* tri_tests, float* t_out,
+                 uint32_t* tri_out, std::string& err) {
+    if (mode < 0 || mode > 2) { err = "mode: 0 quantised, 1 exact, 2 quantised with two more bits"; return RT_ERR_INVALID; }
+    if (hs.nodes.empty()) { err = "no tree"; return RT_ERR_INVALID; }
+    const float inf = std::numeric_limits<float>::infinity();
+    std::vector<Box3> box(hs.nodes.size() * 4); // the box tested for child k of node i
+    auto tested = [&](int32_t node, int k, const Box3& c) {
+        const BvhNode& nd = hs.nodes[(size_t)node];
+        Box3& out = box[(size_t)node * 4 + k];
+        if (mode == 0) out = child_box(nd, k);
+        else for (int a = 0; a < 3; ++a) {
+            if (mode == 1) {
+                out.lo[a] = c.lo[a] - hs.pad, out.hi[a] = c.hi[a] + hs.pad;
+            } else {
+                const float q = nd.scale(a) * 0.25f;
+                out.lo[a] = nd.origin[a] + std::floor((c.lo[a] - hs.pad - nd.origin[a]) / q) * q;
+                out.hi[a] = nd.origin[a] + std::ceil((c.hi[a] + hs.pad - nd.origin[a]) / q) * q;
+            }
+        }
+        return true;
+    };
+    Box3 all;
+    (void)exact_boxes(hs, 0, 0, all, [](int32_t, uint32_t) { return true; }, tested);
+    uint64_t visits = 0, tests = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        const float o[3] = {org[3 * i], org[3 * i + 1], org[3 * i + 2]}, d[3] = {dir[3 * i], dir[3 * i + 1], dir[3 * i + 2]};
+        float inv[3];
+        for (int a = 0; a < 3; ++a) inv[a] = 1.0f / (std::fabs(d[a]) < 1e-30f ? std::copysign(1e-30f, d[a]) : d[a]);
+        float best = inf;
+        uint32_t best_tri = kNoTri;
+        int32_t stack[kStackSize * 4];
+        int sp = 0;
+        int32_t cur = 0;
+        for (;;) {
+            if (cur >= 0) {
+                visits++;
+                const BvhNode& nd = hs.nodes[(size_t)cur];
+                float key[4];
+                int32_t ch[4];
+                int m = 0;
+                for (int k = 0; k < 4; ++k) {
+                    if (nd.child[k] == kChildEmpty) continue;
+                    const Box3& b = box[(size_t)cur * 4 + k];
+                    float tn = 0.0f, tf = best;
+                    for (int a = 0; a < 3; ++a) {
+                        const float t0 = (b.lo[a] - o[a]) * inv[a], t1 = (b.hi[a] - o[a]) * inv[a];
+                        tn = std::max(tn, std::min(t0, t1)), tf = std::min(tf, std::max(t0, t1));
+                    }
+                    if (tn <= tf) key[m] = tn, ch[m] = nd.child[k], m++;
+                }
+                for (int a = 1; a < m; ++a) // nearest first
+                    for (int b = a; b > 0 && key[b] < key[b - 1]; --b) std::swap(key[b], key[b - 1]), std::swap(ch[b], ch[b - 1]);
+                for (int a = m - 1; a >= 1; --a) stack[sp++] = ch[a];
+                if (m) { cur = ch[0]; continue; }
+            } else {
+                const LeafRange leaf = leaf_range(cur);
+                for (uint32_t k = 0; k < leaf.count; ++k) {
+                    tests++;
+                    const TriRec& tr = hs.tris[leaf.first + k];
+                    // Moller-Trumbore on (v0, e1, e2), in double: only the count matters here
+                    const double e1[3] = {tr.e1[0], tr.e1[1], tr.e1[2]}, e2[3] = {tr.e2[0], tr.e2[1], tr.e2[2]};
+                    const double p[3] = {d[1] * e2[2] - d[2] * e2[1], d[2] * e2[0] - d[0] * e2[2], d[0] * e2[1] - d[1] * e2[0]};
+                    const double det = e1[0] * p[0] + e1[1] * p[1] + e1[2] * p[2];
+                    if (det == 0.0) continue;
+                    const double tv[3] = {o[0] - tr.v0[0], o[1] - tr.v0[1], o[2] - tr.v0[2]};
+                    const double u = (tv[0] * p[0] + tv[1] * p[1] + tv[2] * p[2]) / det;
+                    const double q[3] = {tv[1] * e1[2] - tv[2] * e1[1], tv[2] * e1[0] - tv[0] * e1[2], tv[0] * e1[1] - tv[1] * e1[0]};
+                    const double v = (d[0] * q[0] + d[1] * q[1] + d[2] * q[2]) / det;
+                    if (u < 0.0 || v < 0.0 || u + v > 1.0) continue;
+                    const double t = (e2[0] * q[0] + e2[1] * q[1] + e2[2] * q[2]) / det;
+                    if (t > (double)kTNear && (t < best || (t == best && tr.global_index < best_tri))) best = (float)t, best_tri = tr.global_index;
+                }
+            }
+            if (sp == 0) break;
+            cur = stack[--sp];
+        }
+        if (t_out) t_out[i] = best;
+        if (tri_out) tri_out[i] = best_tri;
+    }
+    if (node_visits) *node_visits = visits;
+    if (tri_tests) *tri_tests = tests;
+    return RT_OK;
+}
+
+} // namespace rt

@@ -251,7 +251,7 @@ def model_node_words(lib, tree):
 
 
 def _mt_double(o, d, w):
-    """Moller-Trumbore in double as rt_scene_count_visits runs it (scene_build.cpp: count_visits): t, or inf on a miss."""
+    """Moller-Trumbore in double as rt_scene_count_visits runs it (scene_check.cpp: count_visits): t, or inf on a miss."""
     o, d = o.astype(np.float64), d.astype(np.float64)
     v0 = w[0]
     e1, e2 = (f32(w[1] - w[0])).astype(np.float64), (f32(w[2] - w[0])).astype(np.float64)

@@ -26,7 +26,7 @@ INF = float("inf")
 
 # ---- the motion guide --------------------------------------------------------------------------------------------------------------------
 def world_vertices_f32(sd) -> np.ndarray:
-    """(T, 3, 3) float32: every triangle's world-space vertices as the library computes them (scene_build.cpp, rt_update.hip:
+    """(T, 3, 3) float32: every triangle's world-space vertices as the library computes them (scene_build.cpp: world_vertices, rt_update.hip:
     ((m0*x + m4*y) + m8*z) + m12 with the instance's column-major matrix)."""
     idx = np.asarray(sd.indices, np.int64).reshape(-1, 3)
     m = np.asarray(sd.transforms, f32).reshape(-1, 16)[np.asarray(sd.tri_instance, np.int64)]  # (T, 16)

@@ -543,6 +543,70 @@ int rt_denoise(rt_denoiser* d, const rt_denoise_params* p, const float* rgba_f32
 int rt_denoise_device(rt_denoiser* d, const rt_denoise_params* p, const void* d_rgba_f32, const void* d_albedo, const void* d_normal,
                       const void* d_position, void* d_out_f32, void* d_out_u8, void* stream);
 
+/* ---- Variance-guided denoising (after SVGF: Schied, Kaplanyan, Wyman, Patney, Chaitanya, Burgess, Liu, Dachsbacher, Lefohn, Salvi, HPG 2017;
+ * no reference counterpart). rt_denoise's colour term has one global sigma_color; here the tolerance of every pixel is its own noise level: the
+ * standard deviation of its luminance, estimated by rt_denoise_variance and carried through the filter by rt_denoise_guided. The chain is
+ * rt_temporal_accumulate_moments (below) -> rt_denoise_variance -> rt_denoise_guided, or the last two alone for a still image.
+ * Out of scope: feeding the first filtered iteration back into the history, and albedo demodulation.
+ *
+ * rt_denoiser_create_ex == rt_denoiser_create plus flags (rt_denoiser_create passes 0: the same allocation). RT_DENOISER_VARIANCE adds the host
+ * variants' staging of the two calls below (an input and an output variance plane, the moments and the history lengths: 20 bytes per pixel,
+ * 136 in all); the variance between iterations needs no plane, it rides in .w of the colour scratch. An unknown flag: RT_ERR_INVALID.
+ *
+ * Common to both calls: planes as rt_denoise's (H x W x 4 fp32 frame and guides, row 0 first); a hit is P.w finite; every operation one R1
+ * fp32 op, left to right as bracketed; dot = (x*x + y*y) + z*z; exp_m and k = coefficient(sigma) = RN(1/RN(sigma*sigma)), 0 for +inf, are
+ * rt_denoise's; lum(L) = (L_r*0.2126f + L_g*0.7152f) + L_b*0.0722f; L_q = (F_r*F_r, F_g*F_g, F_b*F_b) of the frame at q, as rt_denoise's step 1.
+ *
+ * rt_denoise_variance: out_variance (H*W floats) = the variance of every pixel's luminance. moments (H*W*2 floats, rt_temporal_accumulate_moments')
+ * and history_len (H*W floats) may both be NULL (a still image; one without the other is RT_ERR_INVALID). The frame is the one the moments belong
+ * to: the accumulated frame where there is temporal accumulation.
+ *   Where moments are given and history_len >= (float)min_history: (m1, m2) = moments at p.
+ *   Elsewhere, over the 7 x 7 window q = (x + dx, y + dy), dy = -3..3 (outer), dx = -3..3 (inner): taps outside the image are skipped, and so is
+ *   a tap that differs from p in being a hit;
+ *     E = (dot(N_p-N_q)*kn + dot(P_p.xyz-P_q.xyz)*kx) + dot(A_p-A_q)*ka   (a term whose coefficient is 0 is left out, E starts at +0; kn is not
+ *     scaled: there is no step); w = exp_m(-E); l_q = lum(L_q); s1 += w*l_q, s2 += w*(l_q*l_q), ws += w, in tap order;
+ *     m1 = s1 / ws, m2 = s2 / ws   (ws >= 1: the centre tap).
+ *   var = fmax(m2 - m1*m1, 0), fmax as IEEE 754's maxNum: fmax(NaN, 0) = 0.
+ *
+ * rt_denoise_guided: rt_denoise with its colour term replaced; variance is H*W floats (rt_denoise_variance's), out_variance (H*W floats, may be
+ * NULL) the variance of the filtered luminance. It is rt_denoise's steps 1 .. 4 with, in step 2, per iteration i (var = the input variance for
+ * i = 0, then var' of the iteration before):
+ *   a. g_p = sum over dy = -1..1 (outer), dx = -1..1 (inner) of (k3[dy+1]*k3[dx+1]) * var_q, k3 = {1/4, 1/2, 1/4}, q = (x + dx, y + dy) clamped
+ *      into the image (not scaled by the step), g starting at +0; kl_p = 1 / (sigma_luminance * sqrt(g_p) + 1e-8f).
+ *   b. E = ((fabs(l_p - l_q)*kl_p + dot(N_p-N_q)*kn_i) + dot(P_p.xyz-P_q.xyz)*kx) + dot(A_p-A_q)*ka, l = lum of this iteration's L. For
+ *      sigma_luminance = +inf the term and step a are left out: the images are then rt_denoise's with sigma_color = +inf, bit for bit.
+ *   c. beside S += w*L_q and Wsum += w: V += (w*w)*var_q, in tap order. L' = S / Wsum, var' = V / (Wsum*Wsum).
+ *   iterations = 0: rt_denoise's step 4, and out_variance = variance.
+ * Non-finite radiance (a frame may hold one: F = 1e20 gives L = +inf). There l = +inf and l*l = +inf, so moments or a window holding it have
+ * m2 - m1*m1 = inf - inf = NaN and var = fmax(NaN, 0) = 0: rt_denoise_variance never returns NaN for a frame without NaN, and returns +inf only
+ * where m2 overflows while m1*m1 does not. In the filter a variance of +inf gives sqrt(g) = +inf and kl = 0; a tap between a finite and an infinite
+ * luminance has fabs(..) * kl = inf * 0 or E = +inf or NaN, exp_m of which is 0: its weight is 0, and 0 * inf = NaN enters S. So (sigma_luminance
+ * finite) L' is NaN at every pixel with a non-finite L_q among its 25 taps, as in rt_denoise, and the region grows by 2 * step pixels per
+ * iteration. The pixel that holds the non-finite value has inf - inf = NaN at its own centre tap too: all its weights are 0, Wsum = 0, and
+ * there, and only there, var' = 0 / 0 = NaN as well (elsewhere V sums w*w*var_q with w = 0 and a finite var_q: it stays finite). The filter
+ * does not clamp: remove fireflies before it, or accept the hole.
+ * Refusals: rt_denoise's (for rt_denoise_variance out_variance is the required output), plus RT_ERR_INVALID for a denoiser created without
+ * RT_DENOISER_VARIANCE. out_f32 may alias rgba_f32; no other aliasing is allowed (out_variance must not be variance). Both calls are serialised
+ * with every other call on the denoiser; the host variants synchronise, the _device variants enqueue on `stream`. */
+#define RT_DENOISER_VARIANCE 1u
+typedef struct rt_denoise_var_params {
+    uint32_t iterations;    /* 0 .. 10; 0 = copy (rt_denoise_variance ignores it, but checks it)       */
+    float sigma_luminance;  /* in standard deviations; >= 1e-6, +inf = term off; NaN / < 1e-6 -> RT_ERR_INVALID */
+    float sigma_normal;
+    float sigma_position;   /* world units                                                             */
+    float sigma_albedo;
+    uint32_t min_history;   /* rt_denoise_variance: the moments are used where history_len >= this      */
+} rt_denoise_var_params;    /* 24 bytes */
+int rt_denoiser_create_ex(int device, int32_t width, int32_t height, uint32_t flags, rt_denoiser** out);
+int rt_denoise_variance(rt_denoiser* d, const rt_denoise_var_params* p, const float* rgba_f32, const float* albedo, const float* normal,
+                        const float* position, const float* moments, const float* history_len, float* out_variance);
+int rt_denoise_variance_device(rt_denoiser* d, const rt_denoise_var_params* p, const void* d_rgba_f32, const void* d_albedo, const void* d_normal,
+                               const void* d_position, const void* d_moments, const void* d_history_len, void* d_out_variance, void* stream);
+int rt_denoise_guided(rt_denoiser* d, const rt_denoise_var_params* p, const float* rgba_f32, const float* albedo, const float* normal,
+                      const float* position, const float* variance, float* out_f32, uint8_t* out_u8, float* out_variance);
+int rt_denoise_guided_device(rt_denoiser* d, const rt_denoise_var_params* p, const void* d_rgba_f32, const void* d_albedo, const void* d_normal,
+                             const void* d_position, const void* d_variance, void* d_out_f32, void* d_out_u8, void* d_out_variance, void* stream);
+
 /* ---- Temporal accumulation by reprojection (no reference counterpart). Frames of an animation rendered with different seed salts
  * (rt_renderer_set_frame_seed) are independent estimates; the accumulator carries a running mean of them from frame to frame, fetched for every
  * pixel where its surface point was one frame ago (rt_scene_gbuffer_motion's prev_position, projected through the previous call's camera),
@@ -595,6 +659,26 @@ int rt_temporal_accumulate(rt_temporal* t, const rt_temporal_params* p, const rt
 int rt_temporal_accumulate_device(rt_temporal* t, const rt_temporal_params* p, const rt_camera* cam, const void* d_rgba_f32, const void* d_normal,
                                   const void* d_position, const void* d_prev_position, void* d_out_f32, void* d_out_u8, void* d_history_len,
                                   void* stream);
+
+/* Temporal luminance moments, for rt_denoise_variance. rt_temporal_create_ex == rt_temporal_create plus flags (rt_temporal_create passes 0: the
+ * same allocation). With RT_TEMPORAL_MOMENTS the accumulator also owns two (ping-pong) planes of float2 moments, 8 bytes per pixel each, and the
+ * host variant's staging of them (8 more). An unknown flag: RT_ERR_INVALID.
+ * rt_temporal_accumulate_moments[_device] is rt_temporal_accumulate[_device] with one more output, moments (H*W*2 floats, required): its colour
+ * outputs and history_len are rt_temporal_accumulate's bit for bit. Added to that contract's steps, with lum(L) = (L_r*0.2126f + L_g*0.7152f) +
+ * L_b*0.0722f of step 1's L:
+ *   l = lum(L), M = (l, l*l). No history (step 2): M' = M. With history: Sm accumulates w_t * Mhist_t per component over step 4's valid taps, in
+ *   their order and with their weights; Hm = Sm / Wsum; M' = Hm + (M - Hm) * a per component, a of step 5. The current set keeps M'; moments = M'.
+ * M' is the running mean of l and of l*l over the frames the colour is the mean of. A non-finite L makes them +inf or NaN: see rt_denoise_variance.
+ * RT_ERR_INVALID on an accumulator created without the flag. A plain rt_temporal_accumulate[_device] on an accumulator WITH the flag is allowed
+ * and keeps the moments consistent: it computes and stores M' as above (the same kernel) and only does not return it. */
+#define RT_TEMPORAL_MOMENTS 1u
+int rt_temporal_create_ex(int device, int32_t width, int32_t height, uint32_t flags, rt_temporal** out);
+int rt_temporal_accumulate_moments(rt_temporal* t, const rt_temporal_params* p, const rt_camera* cam, const float* rgba_f32, const float* normal,
+                                   const float* position, const float* prev_position, float* out_f32, uint8_t* out_u8, float* history_len,
+                                   float* moments);
+int rt_temporal_accumulate_moments_device(rt_temporal* t, const rt_temporal_params* p, const rt_camera* cam, const void* d_rgba_f32,
+                                          const void* d_normal, const void* d_position, const void* d_prev_position, void* d_out_f32, void* d_out_u8,
+                                          void* d_history_len, void* d_moments, void* stream);
 
 /* ---- Multi-GPU frame gather over xGMI (no reference counterpart: the reference renders on ONE device and hands its
  * single image to stbi_write_png, src/main.cpp:57-70, src/util.hpp:8-33). SURVEY §8(e): the frame is split into interleaved

@@ -1,4 +1,4 @@
-// rt_denoise.hip — the edge-avoiding a-trous denoiser (Dammertz, Sewtz, Hanika, Lensch, HPG 2010): rt_denoiser_create / _destroy,
+// rt_denoise.hip — the edge-avoiding a-trous denoiser (Dammertz, Sewtz, Hanika, Lensch, HPG 2010): rt_denoiser_create[_ex] / _destroy,
 // rt_denoise[_device] and their kernels. The filter's arithmetic is the contract stated at rt_denoise in include/rt_mi355x.h; the
 // numpy model that pins it bit for bit is tests/test_denoise.py: denoise_model.
 //
@@ -6,37 +6,9 @@
 // iteration i). The first launch squares the frame as it loads it (linear radiance), the last writes sqrt and the unorm8 image; between
 // them linear colour ping-pongs through the denoiser's two float4 scratch planes. A workgroup is 64 x 4 pixels, a wave one row of 64
 // consecutive pixels: every tap's 16-byte loads of colour and guides are one contiguous 1 KB row segment per wave.
-#include "rt_internal.h"
-#include "rt_device.h"
-#include "denoise_math.h"
-
-struct rt_denoiser {
-    int device = -1;
-    int32_t width = 0, height = 0;
-    float4* d_scratch[2] = {nullptr, nullptr}; // linear colour between iterations
-    hipStream_t stream = nullptr;              // rt_denoise (the host variant) runs here
-    hipEvent_t ev_last = nullptr;              // recorded behind every call: the next call's stream waits for it
-    bool recorded = false;
-    // rt_denoise's device copies of its host arguments (four input planes, the fp32 and unorm8 outputs), allocated with the scratch at creation:
-    // no call allocates
-    float4* d_host_in = nullptr;
-    float4* d_host_f32 = nullptr;
-    uint8_t* d_host_u8 = nullptr;
-};
+#include "rt_denoiser.h"
 
 namespace {
-
-constexpr uint32_t kMaxIterations = 10;
-constexpr float kMinSigma = 1e-6f;
-
-// the weights of the B3-spline kernel, per axis: 1/16, 1/4, 3/8, 1/4, 1/16 (all exact; their products too)
-__constant__ float kTapH[5] = {0.0625f, 0.25f, 0.375f, 0.25f, 0.0625f};
-
-RT_DEV float dot_diff(float4 a, float4 b) { // R2's dot of a.xyz - b.xyz with itself
-    const float x = a.x - b.x, y = a.y - b.y, z = a.z - b.z;
-    return (x * x + y * y) + z * z;
-}
-RT_DEV float4 squared(float4 f) { return make_float4(f.x * f.x, f.y * f.y, f.z * f.z, 1.0f); }
 
 // one a-trous iteration with step `step`; kc / kn / kx / ka: this iteration's coefficients (0 = that term left out, its guide not read)
 // SQUARE: `in` is the frame (rgb = sqrt(mean)), squared as it is loaded; LAST: writes out_f32 (may be null) and out_u8 (may be null)
@@ -96,13 +68,6 @@ __global__ void __launch_bounds__(256) k_denoise_copy(const float4* __restrict__
     if (out_u8) out_u8[i] = make_uchar4(to_unorm8(f.x), to_unorm8(f.y), to_unorm8(f.z), 255);
 }
 
-// RN(1 / RN(sigma * sigma)); 0 for sigma = +inf (the guide ignored)
-float coefficient(float sigma) {
-    if (std::isinf(sigma)) return 0.0f;
-    const float s2 = sigma * sigma;
-    return 1.0f / s2;
-}
-
 int check_params(const rt_denoise_params* p) {
     if (!p) return fail(RT_ERR_INVALID, "null parameters");
     if (p->iterations > kMaxIterations) return fail(RT_ERR_INVALID, "iterations must be 0 .. 10");
@@ -158,9 +123,14 @@ int enqueue(rt_denoiser* d, const rt_denoise_params* p, const float4* frame, con
 extern "C" {
 
 int rt_denoiser_create(int device, int32_t width, int32_t height, rt_denoiser** out) {
+    return rt_denoiser_create_ex(device, width, height, 0u, out);
+}
+
+int rt_denoiser_create_ex(int device, int32_t width, int32_t height, uint32_t flags, rt_denoiser** out) {
     if (!out) return fail(RT_ERR_INVALID, "null output pointer");
     *out = nullptr;
     if (device < 0) return fail(RT_ERR_INVALID, "device index out of range");
+    if (flags & ~RT_DENOISER_VARIANCE) return fail(RT_ERR_INVALID, "unknown denoiser flag");
     if (width <= 0 || height <= 0) return fail(RT_ERR_INVALID, "width and height must be positive");
     if ((uint64_t)width * (uint64_t)height > 0x7fffffffull) return fail(RT_ERR_INVALID, "image too large (W x H must stay below 2^31)");
     // k_atrous's 1-D grid of 64 x 4 tiles: its threads, padding included, must stay below 2^32 (only very narrow images reach that)
@@ -170,11 +140,14 @@ int rt_denoiser_create(int device, int32_t width, int32_t height, rt_denoiser** 
     if (rc != RT_OK) return rc;
     return no_throw([&]() -> int {
         rt_denoiser* d = new rt_denoiser;
-        d->device = device, d->width = width, d->height = height;
+        d->device = device, d->width = width, d->height = height, d->flags = flags;
         const size_t n = (size_t)width * (size_t)height, bytes = n * 16u;
         if (hipMalloc((void**)&d->d_scratch[0], bytes) != hipSuccess || hipMalloc((void**)&d->d_scratch[1], bytes) != hipSuccess ||
             hipMalloc((void**)&d->d_host_in, 4 * bytes) != hipSuccess || hipMalloc((void**)&d->d_host_f32, bytes) != hipSuccess ||
-            hipMalloc((void**)&d->d_host_u8, n * 4u) != hipSuccess) {
+            hipMalloc((void**)&d->d_host_u8, n * 4u) != hipSuccess ||
+            ((flags & RT_DENOISER_VARIANCE) &&
+             (hipMalloc((void**)&d->d_host_var_in, n * 4u) != hipSuccess || hipMalloc((void**)&d->d_host_var_out, n * 4u) != hipSuccess ||
+              hipMalloc((void**)&d->d_host_mom, n * 8u) != hipSuccess || hipMalloc((void**)&d->d_host_len, n * 4u) != hipSuccess))) {
             rt_denoiser_destroy(d);
             return fail(RT_ERR_OOM, "hipMalloc of the denoiser's scratch and staging failed");
         }
@@ -194,6 +167,7 @@ void rt_denoiser_destroy(rt_denoiser* d) {
         if (d->recorded) (void)hipEventSynchronize(d->ev_last);
         (void)hipFree(d->d_scratch[0]), (void)hipFree(d->d_scratch[1]);
         (void)hipFree(d->d_host_in), (void)hipFree(d->d_host_f32), (void)hipFree(d->d_host_u8);
+        (void)hipFree(d->d_host_var_in), (void)hipFree(d->d_host_var_out), (void)hipFree(d->d_host_mom), (void)hipFree(d->d_host_len);
         if (d->ev_last) (void)hipEventDestroy(d->ev_last);
         if (d->stream) (void)hipStreamDestroy(d->stream);
     }

@@ -11,6 +11,9 @@
 //   --schedule {default,per-sample,per-bounce,per-bounce-fused}   which of the wavefront renderer's schedules renders the frame
 //   --denoise ITER         every image written is denoised after its last pass (rt_scene_gbuffer + rt_denoise, ITER a-trous iterations,
 //                          the default sigmas of rtamd/renderer.py); a tiled frame is denoised on the root device after the gather
+//   --guided SIGMA_L       with --denoise: the variance-guided filter in rt_denoise's place (rt_denoise_variance + rt_denoise_guided,
+//                          sigma_luminance = SIGMA_L standard deviations; 4 is rtamd/renderer.py's default). With --temporal the variance comes
+//                          from the accumulated luminance moments where the history is at least 4 frames, else from a 7 x 7 window
 //   --temporal N           with --frames: temporal accumulation. Frame f is rendered with seed salt f (rt_renderer_set_frame_seed), then
 //                          accumulated over the frames before it by reprojection (rt_scene_gbuffer_motion + rt_temporal_accumulate, history
 //                          capped at N frames), then denoised if --denoise is given, then written. One device only.
@@ -55,6 +58,9 @@ static void usage(const char* argv0) {
                 "  --denoise UINT              denoise every image written with this many a-trous iterations (1 .. 10; default 0 = off),\n"
                 "                              guided by the scene's primary-hit G-buffer (a tiled frame: on the first device, after the\n"
                 "                              gather); prints the G-buffer's and the filter's device time\n"
+                "  --guided FLOAT              with --denoise: filter with the variance-guided a-trous (the colour tolerance of every pixel is this\n"
+                "                              many standard deviations of its luminance; 4 is the default of the Python interface); with\n"
+                "                              --temporal the variance comes from the accumulated moments; adds the variance stage's device time\n"
                 "  --temporal UINT             with --frames > 1: accumulate every frame over the frames before it by reprojection, the history\n"
                 "                              capped at this many frames (1 .. 4096; default 0 = off); every frame gets its own noise (seed salt\n"
                 "                              = frame number); before --denoise; one device only; prints the stage's device times\n"
@@ -67,6 +73,7 @@ static void usage(const char* argv0) {
 int main(int argc, const char* argv[]) {
     uint32_t max_depth = 10, sample_count = 32, rr = 0, passes = 1, min_samples = 0, frames = 1, denoise = 0, temporal = 0;
     float adaptive = -1.0f; // < 0: off
+    float guided = 0.0f;    // 0: off
     double spin = 0.0;      // degrees per frame (--frames)
     std::string scene_path = "./assets/sponza.glb", out_path = "out.png";
     bool use_wavefront = false, use_megakernel = false, quiet = false;
@@ -133,6 +140,12 @@ int main(int argc, const char* argv[]) {
             denoise = to_u32("--denoise", need(i));
             if (denoise > 10) { std::fprintf(stderr, "--denoise: expected 0 .. 10 iterations\n"); return 105; }
         }
+        else if (a == "--guided") {
+            const std::string v = need(i);
+            char* end = nullptr;
+            guided = std::strtof(v.c_str(), &end);
+            if (v.empty() || *end || !(guided >= 1e-6f)) { std::fprintf(stderr, "--guided: expected a sigma of at least 1e-6 (inf = luminance ignored), got '%s'\n", v.c_str()); return 105; }
+        }
         else if (a == "--temporal") {
             temporal = to_u32("--temporal", need(i));
             if (temporal > 4096) { std::fprintf(stderr, "--temporal: expected a history of 1 .. 4096 frames (0 = off)\n"); return 105; }
@@ -174,6 +187,7 @@ int main(int argc, const char* argv[]) {
         }
     }
     if (!use_wavefront && !use_megakernel) use_wavefront = true; // src/main.cpp:26-28
+    if (guided > 0.0f && !denoise) { std::fprintf(stderr, "--guided: goes with --denoise of at least 1 iteration\n"); return 105; }
     if (temporal && frames < 2) { std::fprintf(stderr, "--temporal: needs --frames of at least 2\n"); return 105; }
     if (temporal && devices.size() > 1) { std::fprintf(stderr, "--temporal: one device only (--devices with one entry)\n"); return 105; }
 
@@ -203,6 +217,7 @@ int main(int argc, const char* argv[]) {
             r->passes = passes;
             r->adaptive = adaptive, r->min_samples = min_samples;
             r->denoise = denoise;
+            r->guided = guided;
             r->temporal = temporal;
             renderer.reset(r);
         } else {
@@ -213,6 +228,7 @@ int main(int argc, const char* argv[]) {
             r->passes = passes;
             r->adaptive = adaptive, r->min_samples = min_samples;
             r->denoise = denoise;
+            r->guided = guided;
             r->temporal = temporal;
             if (schedule_given) r->schedule = schedule, r->has_schedule = true;
             renderer.reset(r);

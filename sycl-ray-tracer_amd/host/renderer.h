@@ -161,8 +161,15 @@ struct HipRendererBase : public IRenderer {
     float* d_gbuf = nullptr;      // the three guide planes, W*H*4 floats each (on den_device)
     uint8_t* d_den_u8 = nullptr;  // the denoised unorm8 image
     hipStream_t den_stream = nullptr;
-    hipEvent_t den_ev[3] = {nullptr, nullptr, nullptr};
+    hipEvent_t den_ev[4] = {nullptr, nullptr, nullptr, nullptr};
     int den_device = -1;
+    // Extension: guided > 0 (with denoise > 0) replaces rt_denoise by the variance-guided filter with sigma_luminance = guided
+    // (rt_denoise_variance_device + rt_denoise_guided_device, the other defaults of rtamd/renderer.py). With temporal > 0 the accumulator carries the
+    // luminance moments (RT_TEMPORAL_MOMENTS) and the variance comes from them where the history is long enough; without it the estimate is spatial.
+    float guided = 0.0f;
+    float* d_var = nullptr;       // the variance plane between the estimate and the filter, W*H floats (on den_device)
+    float* d_tmp_mom = nullptr;   // the accumulated moments, W*H*2 floats, and
+    float* d_tmp_len = nullptr;   // the history lengths, W*H floats (on tmp_device): what the variance estimate reads
     // Extension: temporal > 0 (one device, frames of an animation): every frame is rendered with its own seed salt (frame_salt,
     // rt_renderer_set_frame_seed) and accumulated over the frames before it (rt_scene_gbuffer_motion_device + rt_temporal_accumulate_device,
     // max_history = temporal, the defaults of rtamd/renderer.py) before it is denoised (if asked for) and written. The scene must keep its
@@ -194,6 +201,7 @@ struct HipRendererBase : public IRenderer {
     static constexpr float kTemporalPositionFraction = 0.05f, kTemporalCosNormal = 0.9f;
     // the denoiser's defaults (rtamd/renderer.py: DENOISE_*): sigma_position is a fraction of the largest extent of the scene's bounds
     static constexpr float kSigmaColor = 1.0f, kSigmaNormal = 0.25f, kPositionFraction = 0.05f, kSigmaAlbedo = 0.1f;
+    static constexpr uint32_t kMinHistory = 4; // DENOISE_MIN_HISTORY
 
     static void hip_check(hipError_t e, const char* what) {
         if (e != hipSuccess) throw std::runtime_error(std::string(what) + ": " + hipGetErrorString(e));
@@ -203,10 +211,10 @@ struct HipRendererBase : public IRenderer {
             if (den_stream) (void)hipStreamSynchronize(den_stream), (void)hipStreamDestroy(den_stream);
             for (hipEvent_t& e : den_ev)
                 if (e) (void)hipEventDestroy(e), e = nullptr;
-            (void)hipFree(d_gbuf), (void)hipFree(d_den_u8);
+            (void)hipFree(d_gbuf), (void)hipFree(d_den_u8), (void)hipFree(d_var);
         }
         rt_denoiser_destroy(denoiser);
-        denoiser = nullptr, d_gbuf = nullptr, d_den_u8 = nullptr, den_stream = nullptr, den_device = -1;
+        denoiser = nullptr, d_gbuf = nullptr, d_den_u8 = nullptr, d_var = nullptr, den_stream = nullptr, den_device = -1;
     }
 
     void release_accumulator() {
@@ -214,10 +222,11 @@ struct HipRendererBase : public IRenderer {
             if (tmp_stream) (void)hipStreamSynchronize(tmp_stream), (void)hipStreamDestroy(tmp_stream);
             for (hipEvent_t& e : tmp_ev)
                 if (e) (void)hipEventDestroy(e), e = nullptr;
-            (void)hipFree(d_tmp_gbuf), (void)hipFree(d_tmp_f32), (void)hipFree(d_tmp_u8);
+            (void)hipFree(d_tmp_gbuf), (void)hipFree(d_tmp_f32), (void)hipFree(d_tmp_u8), (void)hipFree(d_tmp_mom), (void)hipFree(d_tmp_len);
         }
         rt_temporal_destroy(accumulator);
-        accumulator = nullptr, d_tmp_gbuf = nullptr, d_tmp_f32 = nullptr, d_tmp_u8 = nullptr, tmp_stream = nullptr, tmp_device = -1;
+        accumulator = nullptr, d_tmp_gbuf = nullptr, d_tmp_f32 = nullptr, d_tmp_u8 = nullptr, d_tmp_mom = nullptr, d_tmp_len = nullptr;
+        tmp_stream = nullptr, tmp_device = -1;
     }
 
     static float scene_scale(rt_scene* sc) { // the largest extent of the scene's bounds (rtamd/renderer.py: Scene.scale)
@@ -235,7 +244,12 @@ struct HipRendererBase : public IRenderer {
         hip_check(hipSetDevice(dev), "hipSetDevice");
         if (!accumulator) {
             tmp_device = dev;
-            rt_check(rt_temporal_create(dev, img_size[0], img_size[1], &accumulator));
+            const bool moments = denoise && guided > 0.0f;
+            rt_check(rt_temporal_create_ex(dev, img_size[0], img_size[1], moments ? RT_TEMPORAL_MOMENTS : 0u, &accumulator));
+            if (moments) {
+                hip_check(hipMalloc((void**)&d_tmp_mom, n * 8), "hipMalloc");
+                hip_check(hipMalloc((void**)&d_tmp_len, n * 4), "hipMalloc");
+            }
             hip_check(hipMalloc((void**)&d_tmp_gbuf, 4 * n * 16), "hipMalloc");
             hip_check(hipMalloc((void**)&d_tmp_f32, n * 16), "hipMalloc");
             hip_check(hipMalloc((void**)&d_tmp_u8, n * 4), "hipMalloc");
@@ -247,7 +261,11 @@ struct HipRendererBase : public IRenderer {
         hip_check(hipEventRecord(tmp_ev[0], tmp_stream), "hipEventRecord");
         rt_check(rt_scene_gbuffer_motion_device(sc, &camera.c, g, g + 4 * n, g + 8 * n, g + 12 * n, tmp_stream));
         hip_check(hipEventRecord(tmp_ev[1], tmp_stream), "hipEventRecord");
-        rt_check(rt_temporal_accumulate_device(accumulator, &p, &camera.c, d_frame, g + 4 * n, g + 8 * n, g + 12 * n, d_tmp_f32, d_tmp_u8, nullptr, tmp_stream));
+        if (d_tmp_mom)
+            rt_check(rt_temporal_accumulate_moments_device(accumulator, &p, &camera.c, d_frame, g + 4 * n, g + 8 * n, g + 12 * n, d_tmp_f32, d_tmp_u8,
+                                                           d_tmp_len, d_tmp_mom, tmp_stream));
+        else
+            rt_check(rt_temporal_accumulate_device(accumulator, &p, &camera.c, d_frame, g + 4 * n, g + 8 * n, g + 12 * n, d_tmp_f32, d_tmp_u8, nullptr, tmp_stream));
         hip_check(hipEventRecord(tmp_ev[2], tmp_stream), "hipEventRecord");
         hip_check(hipStreamSynchronize(tmp_stream), "hipStreamSynchronize");
         float g_ms = 0.0f, a_ms = 0.0f;
@@ -267,7 +285,8 @@ struct HipRendererBase : public IRenderer {
         hip_check(hipSetDevice(dev), "hipSetDevice");
         if (!denoiser) {
             den_device = dev;
-            rt_check(rt_denoiser_create(dev, img_size[0], img_size[1], &denoiser));
+            rt_check(rt_denoiser_create_ex(dev, img_size[0], img_size[1], guided > 0.0f ? RT_DENOISER_VARIANCE : 0u, &denoiser));
+            if (guided > 0.0f) hip_check(hipMalloc((void**)&d_var, n * 4), "hipMalloc");
             hip_check(hipMalloc((void**)&d_gbuf, 3 * n * 16), "hipMalloc");
             hip_check(hipMalloc((void**)&d_den_u8, n * 4), "hipMalloc");
             hip_check(hipStreamCreateWithFlags(&den_stream, hipStreamNonBlocking), "hipStreamCreate");
@@ -278,14 +297,26 @@ struct HipRendererBase : public IRenderer {
         hip_check(hipEventRecord(den_ev[0], den_stream), "hipEventRecord");
         rt_check(rt_scene_gbuffer_device(sc, &camera.c, d_gbuf, d_gbuf + 4 * n, d_gbuf + 8 * n, den_stream));
         hip_check(hipEventRecord(den_ev[1], den_stream), "hipEventRecord");
-        rt_check(rt_denoise_device(denoiser, &p, d_frame, d_gbuf, d_gbuf + 4 * n, d_gbuf + 8 * n, nullptr, d_den_u8, den_stream));
+        if (guided > 0.0f) {
+            // (the moments belong to d_frame: both are this frame's rt_temporal_accumulate_moments_device outputs, complete when it returned)
+            const rt_denoise_var_params vp{denoise, guided, kSigmaNormal, kPositionFraction * scale, kSigmaAlbedo, kMinHistory};
+            rt_check(rt_denoise_variance_device(denoiser, &vp, d_frame, d_gbuf, d_gbuf + 4 * n, d_gbuf + 8 * n, temporal ? d_tmp_mom : nullptr,
+                                                temporal ? d_tmp_len : nullptr, d_var, den_stream));
+            hip_check(hipEventRecord(den_ev[3], den_stream), "hipEventRecord");
+            rt_check(rt_denoise_guided_device(denoiser, &vp, d_frame, d_gbuf, d_gbuf + 4 * n, d_gbuf + 8 * n, d_var, nullptr, d_den_u8, nullptr, den_stream));
+        } else
+            rt_check(rt_denoise_device(denoiser, &p, d_frame, d_gbuf, d_gbuf + 4 * n, d_gbuf + 8 * n, nullptr, d_den_u8, den_stream));
         hip_check(hipEventRecord(den_ev[2], den_stream), "hipEventRecord");
         hip_check(hipStreamSynchronize(den_stream), "hipStreamSynchronize");
-        float g_ms = 0.0f, f_ms = 0.0f;
+        float g_ms = 0.0f, f_ms = 0.0f, v_ms = 0.0f;
         hip_check(hipEventElapsedTime(&g_ms, den_ev[0], den_ev[1]), "hipEventElapsedTime");
-        hip_check(hipEventElapsedTime(&f_ms, den_ev[1], den_ev[2]), "hipEventElapsedTime");
+        hip_check(hipEventElapsedTime(&f_ms, guided > 0.0f ? den_ev[3] : den_ev[1], den_ev[2]), "hipEventElapsedTime");
+        if (guided > 0.0f) hip_check(hipEventElapsedTime(&v_ms, den_ev[1], den_ev[3]), "hipEventElapsedTime");
         hip_check(hipMemcpy(image, d_den_u8, n * 4, hipMemcpyDeviceToHost), "hipMemcpy");
-        std::printf("Denoise: %u iterations, G-buffer %.3f ms, filter %.3f ms on device %d\n", denoise, g_ms, f_ms, dev);
+        if (guided > 0.0f)
+            std::printf("Denoise: %u iterations, G-buffer %.3f ms, variance %.3f ms, filter %.3f ms on device %d\n", denoise, g_ms, v_ms, f_ms, dev);
+        else
+            std::printf("Denoise: %u iterations, G-buffer %.3f ms, filter %.3f ms on device %d\n", denoise, g_ms, f_ms, dev);
     }
 
     // one frame over devices.size() tiles: returns with `image` assembled and `last` = summed rays / wall time

@@ -171,6 +171,19 @@ class rt_temporal_params(C.Structure):
     ]
 
 
+class rt_denoise_var_params(C.Structure):
+    _fields_ = [
+        ("iterations", C.c_uint32),
+        ("sigma_luminance", C.c_float),
+        ("sigma_normal", C.c_float),
+        ("sigma_position", C.c_float),
+        ("sigma_albedo", C.c_float),
+        ("min_history", C.c_uint32),
+    ]
+
+
+RT_DENOISER_VARIANCE = 1
+RT_TEMPORAL_MOMENTS = 1
 RT_QUERY_CLOSEST, RT_QUERY_ANY = 0, 1
 RT_TRI_REJECTED = 0xFFFFFFFE
 
@@ -193,6 +206,7 @@ class rt_ray_query(C.Structure):
 assert C.sizeof(rt_ray_query) == 72
 assert C.sizeof(rt_denoise_params) == 20
 assert C.sizeof(rt_temporal_params) == 12
+assert C.sizeof(rt_denoise_var_params) == 24
 assert C.sizeof(rt_material) == 44
 assert C.sizeof(rt_instance) == 104
 assert C.sizeof(rt_camera) == 56
@@ -255,12 +269,26 @@ PROTOTYPES = {
                                          _P(C.c_float), _P(C.c_float), _P(C.c_uint8), _P(C.c_float)]),
     "rt_temporal_accumulate_device": (C.c_int, [C.c_void_p, _P(rt_temporal_params), _P(rt_camera), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_temporal_create_ex": (C.c_int, [C.c_int, C.c_int32, C.c_int32, C.c_uint32, _P(C.c_void_p)]),
+    "rt_temporal_accumulate_moments": (C.c_int, [C.c_void_p, _P(rt_temporal_params), _P(rt_camera), _P(C.c_float), _P(C.c_float), _P(C.c_float),
+                                                 _P(C.c_float), _P(C.c_float), _P(C.c_uint8), _P(C.c_float), _P(C.c_float)]),
+    "rt_temporal_accumulate_moments_device": (C.c_int, [C.c_void_p, _P(rt_temporal_params), _P(rt_camera), C.c_void_p, C.c_void_p, C.c_void_p,
+                                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rt_denoiser_create": (C.c_int, [C.c_int, C.c_int32, C.c_int32, _P(C.c_void_p)]),
     "rt_denoiser_destroy": (None, [C.c_void_p]),
     "rt_denoise": (C.c_int, [C.c_void_p, _P(rt_denoise_params), _P(C.c_float), _P(C.c_float), _P(C.c_float), _P(C.c_float),
                              _P(C.c_float), _P(C.c_uint8)]),
     "rt_denoise_device": (C.c_int, [C.c_void_p, _P(rt_denoise_params), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p]),
+    "rt_denoiser_create_ex": (C.c_int, [C.c_int, C.c_int32, C.c_int32, C.c_uint32, _P(C.c_void_p)]),
+    "rt_denoise_variance": (C.c_int, [C.c_void_p, _P(rt_denoise_var_params), _P(C.c_float), _P(C.c_float), _P(C.c_float), _P(C.c_float),
+                                      _P(C.c_float), _P(C.c_float), _P(C.c_float)]),
+    "rt_denoise_variance_device": (C.c_int, [C.c_void_p, _P(rt_denoise_var_params), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_denoise_guided": (C.c_int, [C.c_void_p, _P(rt_denoise_var_params), _P(C.c_float), _P(C.c_float), _P(C.c_float), _P(C.c_float),
+                                    _P(C.c_float), _P(C.c_float), _P(C.c_uint8), _P(C.c_float)]),
+    "rt_denoise_guided_device": (C.c_int, [C.c_void_p, _P(rt_denoise_var_params), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rt_comm_create": (C.c_int, [C.c_int, _P(C.c_int), _P(C.c_void_p)]),
     "rt_comm_destroy": (None, [C.c_void_p]),
     "rt_comm_uses_rccl": (C.c_int, [C.c_void_p]),

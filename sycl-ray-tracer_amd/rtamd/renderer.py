@@ -548,6 +548,10 @@ DENOISE_SIGMA_COLOR = 1.0
 DENOISE_SIGMA_NORMAL = 0.25
 DENOISE_POSITION_FRACTION = 0.05
 DENOISE_SIGMA_ALBEDO = 0.1
+# The variance-guided filter's: the luminance tolerance in standard deviations, and the history length from which the temporal
+# moments are trusted; one setting for every scene. host/main.cpp's --guided uses the same min_history.
+DENOISE_SIGMA_LUMINANCE = 4.0
+DENOISE_MIN_HISTORY = 4
 
 
 def denoise_params(iterations: int = DENOISE_ITERATIONS, sigma_color: float = DENOISE_SIGMA_COLOR, sigma_normal: float = DENOISE_SIGMA_NORMAL,
@@ -560,14 +564,30 @@ def denoise_params(iterations: int = DENOISE_ITERATIONS, sigma_color: float = DE
     return abi.rt_denoise_params(int(iterations), float(sigma_color), float(sigma_normal), float(sigma_position), float(sigma_albedo))
 
 
-class Denoiser:
-    """rt_denoiser: the edge-avoiding a-trous filter for W x H frames on one device, guided by Scene.gbuffer's planes."""
+def denoise_var_params(iterations: int = DENOISE_ITERATIONS, sigma_luminance: float = DENOISE_SIGMA_LUMINANCE,
+                       sigma_normal: float = DENOISE_SIGMA_NORMAL, sigma_position: float | None = None, sigma_albedo: float = DENOISE_SIGMA_ALBEDO,
+                       min_history: int = DENOISE_MIN_HISTORY, scene_scale: float | None = None):
+    """rt_denoise_var_params; sigma_position None: DENOISE_POSITION_FRACTION * scene_scale, in fp32 (scene_scale is then required)."""
+    if sigma_position is None:
+        if scene_scale is None:
+            raise ValueError("give sigma_position or scene_scale (Scene.scale())")
+        sigma_position = np.float32(DENOISE_POSITION_FRACTION) * np.float32(scene_scale)
+    return abi.rt_denoise_var_params(int(iterations), float(sigma_luminance), float(sigma_normal), float(sigma_position), float(sigma_albedo),
+                                     int(min_history))
 
-    def __init__(self, device: int, width: int, height: int, lib=None):
+
+class Denoiser:
+    """rt_denoiser: the edge-avoiding a-trous filter for W x H frames on one device, guided by Scene.gbuffer's planes. variance=True
+    (RT_DENOISER_VARIANCE): also the variance estimate and the variance-guided filter."""
+
+    def __init__(self, device: int, width: int, height: int, lib=None, variance: bool = False):
         self._lib = lib or abi.load_library()
         self.width, self.height = int(width), int(height)
         self.h = C.c_void_p()
-        abi.check(self._lib.rt_denoiser_create(int(device), self.width, self.height, C.byref(self.h)), self._lib)
+        if variance:
+            abi.check(self._lib.rt_denoiser_create_ex(int(device), self.width, self.height, abi.RT_DENOISER_VARIANCE, C.byref(self.h)), self._lib)
+        else:
+            abi.check(self._lib.rt_denoiser_create(int(device), self.width, self.height, C.byref(self.h)), self._lib)
 
     def denoise(self, frame_f32: np.ndarray, gbuf: dict, iterations: int = DENOISE_ITERATIONS, want_f32: bool = True, want_u8: bool = True,
                 out_f32: np.ndarray | None = None, **sigmas):
@@ -592,6 +612,68 @@ class Denoiser:
         p = denoise_params(iterations, **sigmas)
         v = [C.c_void_p(x or None) for x in (d_frame, d_albedo, d_normal, d_position, d_out_f32, d_out_u8, stream)]
         abi.check(self._lib.rt_denoise_device(self.h, C.byref(p), *v), self._lib)
+
+    def _planes(self, frame_f32, gbuf):
+        shape = (self.height, self.width, 4)
+        frame_f32 = np.ascontiguousarray(frame_f32, np.float32)
+        planes = [np.ascontiguousarray(gbuf[k], np.float32) for k in ("albedo", "normal", "position")]
+        for a in [frame_f32] + planes:
+            if a.shape != shape:
+                raise ValueError(f"expected {shape}, got {a.shape}")
+        return frame_f32, planes
+
+    def estimate_variance(self, frame_f32: np.ndarray, gbuf: dict, moments: np.ndarray | None = None, history_len: np.ndarray | None = None,
+                          **params) -> np.ndarray:
+        """rt_denoise_variance: the (H, W) float32 variance of the frame's luminance; moments (H, W, 2) and history_len (H, W) as
+        TemporalAccumulator.accumulate(moments=True) returns them, or neither (a still image). `params`: denoise_var_params'."""
+        p = denoise_var_params(**params)
+        frame_f32, planes = self._planes(frame_f32, gbuf)
+        m = n = None
+        if moments is not None:
+            m = np.ascontiguousarray(moments, np.float32)
+            if m.shape != (self.height, self.width, 2):
+                raise ValueError(f"expected moments of shape {(self.height, self.width, 2)}, got {m.shape}")
+        if history_len is not None:
+            n = np.ascontiguousarray(history_len, np.float32)
+            if n.shape != (self.height, self.width):
+                raise ValueError(f"expected history_len of shape {(self.height, self.width)}, got {n.shape}")
+        var = np.zeros((self.height, self.width), np.float32)
+        abi.check(self._lib.rt_denoise_variance(self.h, C.byref(p), abi.fptr(frame_f32), *(abi.fptr(a) for a in planes),
+                                                abi.fptr(m) if m is not None else None, abi.fptr(n) if n is not None else None,
+                                                abi.fptr(var)), self._lib)
+        return var
+
+    def estimate_variance_device(self, d_frame: int, d_albedo: int, d_normal: int, d_position: int, d_moments: int, d_history_len: int,
+                                 d_out_variance: int, stream: int = 0, **params) -> None:
+        """rt_denoise_variance_device on DEVICE pointers, enqueued on `stream`."""
+        p = denoise_var_params(**params)
+        v = [C.c_void_p(x or None) for x in (d_frame, d_albedo, d_normal, d_position, d_moments, d_history_len, d_out_variance, stream)]
+        abi.check(self._lib.rt_denoise_variance_device(self.h, C.byref(p), *v), self._lib)
+
+    def denoise_guided(self, frame_f32: np.ndarray, gbuf: dict, variance: np.ndarray, iterations: int = DENOISE_ITERATIONS, want_f32: bool = True,
+                       want_u8: bool = True, want_variance: bool = True, out_f32: np.ndarray | None = None, **params):
+        """rt_denoise_guided of a (H, W, 4) float32 frame with its (H, W) variance; returns (f32, u8, variance of the result), None for what
+        was not asked for. `params`: denoise_var_params'. out_f32: where the fp32 result goes (may be frame_f32)."""
+        p = denoise_var_params(iterations, **params)
+        frame_f32, planes = self._planes(frame_f32, gbuf)
+        variance = np.ascontiguousarray(variance, np.float32)
+        if variance.shape != (self.height, self.width):
+            raise ValueError(f"expected variance of shape {(self.height, self.width)}, got {variance.shape}")
+        shape = (self.height, self.width, 4)
+        f = (out_f32 if out_f32 is not None else np.zeros(shape, np.float32)) if want_f32 else None
+        b = np.zeros(shape, np.uint8) if want_u8 else None
+        ov = np.zeros(shape[:2], np.float32) if want_variance else None
+        abi.check(self._lib.rt_denoise_guided(self.h, C.byref(p), abi.fptr(frame_f32), *(abi.fptr(a) for a in planes), abi.fptr(variance),
+                                              abi.fptr(f) if f is not None else None, abi.u8ptr(b) if b is not None else None,
+                                              abi.fptr(ov) if ov is not None else None), self._lib)
+        return f, b, ov
+
+    def denoise_guided_device(self, d_frame: int, d_albedo: int, d_normal: int, d_position: int, d_variance: int, d_out_f32: int = 0,
+                              d_out_u8: int = 0, d_out_variance: int = 0, stream: int = 0, iterations: int = DENOISE_ITERATIONS, **params) -> None:
+        """rt_denoise_guided_device on DEVICE pointers, enqueued on `stream`."""
+        p = denoise_var_params(iterations, **params)
+        v = [C.c_void_p(x or None) for x in (d_frame, d_albedo, d_normal, d_position, d_variance, d_out_f32, d_out_u8, d_out_variance, stream)]
+        abi.check(self._lib.rt_denoise_guided_device(self.h, C.byref(p), *v), self._lib)
 
     def close(self):
         if self.h:
@@ -623,19 +705,26 @@ def temporal_params(max_history: int = TEMPORAL_MAX_HISTORY, sigma_position: flo
 
 
 class TemporalAccumulator:
-    """rt_temporal: temporal accumulation by reprojection for W x H frames on one device, guided by Scene.gbuffer_motion's planes."""
+    """rt_temporal: temporal accumulation by reprojection for W x H frames on one device, guided by Scene.gbuffer_motion's planes. moments=True
+    (RT_TEMPORAL_MOMENTS): the accumulator also carries the luminance moments that Denoiser.estimate_variance takes."""
 
-    def __init__(self, device: int, width: int, height: int, lib=None):
+    def __init__(self, device: int, width: int, height: int, lib=None, moments: bool = False):
         self._lib = lib or abi.load_library()
         self.width, self.height = int(width), int(height)
+        self.moments = bool(moments)
         self.h = C.c_void_p()
-        abi.check(self._lib.rt_temporal_create(int(device), self.width, self.height, C.byref(self.h)), self._lib)
+        if moments:
+            abi.check(self._lib.rt_temporal_create_ex(int(device), self.width, self.height, abi.RT_TEMPORAL_MOMENTS, C.byref(self.h)), self._lib)
+        else:
+            abi.check(self._lib.rt_temporal_create(int(device), self.width, self.height, C.byref(self.h)), self._lib)
 
     def accumulate(self, frame_f32: np.ndarray, gbuf: dict, camera: Camera, want_f32: bool = True, want_u8: bool = True,
-                   out_f32: np.ndarray | None = None, **params):
+                   out_f32: np.ndarray | None = None, moments: bool | None = None, **params):
         """rt_temporal_accumulate of a (H, W, 4) float32 frame rendered with `camera`, with the planes of Scene.gbuffer_motion(camera); returns
         (f32, u8, history_len (H, W) float32), None for an image not asked for. `params`: max_history, sigma_position, cos_normal, scene_scale
-        (temporal_params). out_f32: where the fp32 result goes (may be frame_f32)."""
+        (temporal_params). out_f32: where the fp32 result goes (may be frame_f32). On an accumulator created with moments=True the call is
+        rt_temporal_accumulate_moments and the result a dict with the keys "f32", "u8", "history_len" and "moments" ((H, W, 2) float32);
+        moments=False there makes the plain call (the accumulator keeps its moments up to date all the same)."""
         p = temporal_params(**params)
         shape = (self.height, self.width, 4)
         frame_f32 = np.ascontiguousarray(frame_f32, np.float32)
@@ -646,6 +735,12 @@ class TemporalAccumulator:
         f = (out_f32 if out_f32 is not None else np.zeros(shape, np.float32)) if want_f32 else None
         b = np.zeros(shape, np.uint8) if want_u8 else None
         n = np.zeros(shape[:2], np.float32)
+        if self.moments if moments is None else moments:
+            m = np.zeros(shape[:2] + (2,), np.float32)
+            abi.check(self._lib.rt_temporal_accumulate_moments(self.h, C.byref(p), C.byref(camera.c), abi.fptr(frame_f32),
+                                                               *(abi.fptr(a) for a in planes), abi.fptr(f) if f is not None else None,
+                                                               abi.u8ptr(b) if b is not None else None, abi.fptr(n), abi.fptr(m)), self._lib)
+            return {"f32": f, "u8": b, "history_len": n, "moments": m}
         abi.check(self._lib.rt_temporal_accumulate(self.h, C.byref(p), C.byref(camera.c), abi.fptr(frame_f32), *(abi.fptr(a) for a in planes),
                                                    abi.fptr(f) if f is not None else None, abi.u8ptr(b) if b is not None else None,
                                                    abi.fptr(n)), self._lib)
@@ -657,6 +752,13 @@ class TemporalAccumulator:
         p = temporal_params(**params)
         v = [C.c_void_p(x or None) for x in (d_frame, d_normal, d_position, d_prev_position, d_out_f32, d_out_u8, d_history_len, stream)]
         abi.check(self._lib.rt_temporal_accumulate_device(self.h, C.byref(p), C.byref(camera.c), *v), self._lib)
+
+    def accumulate_moments_device(self, camera: Camera, d_frame: int, d_normal: int, d_position: int, d_prev_position: int, d_moments: int,
+                                  d_out_f32: int = 0, d_out_u8: int = 0, d_history_len: int = 0, stream: int = 0, **params) -> None:
+        """rt_temporal_accumulate_moments_device on DEVICE pointers, enqueued on `stream`."""
+        p = temporal_params(**params)
+        v = [C.c_void_p(x or None) for x in (d_frame, d_normal, d_position, d_prev_position, d_out_f32, d_out_u8, d_history_len, d_moments, stream)]
+        abi.check(self._lib.rt_temporal_accumulate_moments_device(self.h, C.byref(p), C.byref(camera.c), *v), self._lib)
 
     def reset(self) -> None:
         """rt_temporal_reset: forget the history; the next call passes its frame through."""

@@ -234,6 +234,49 @@ typedef struct rt_ray_query {
 int rt_trace_rays(rt_scene* scene, const rt_ray_query* q);
 int rt_trace_rays_device(rt_scene* scene, const rt_ray_query* q, void* stream);
 
+/* ---- Path queries: radiance along caller-supplied rays (light probes, irradiance volumes, baking, reflection captures, radiance caches).
+ * Entry i runs `samples` paths of at most `max_depth` rays from (org[i], dir[i]) with the renderers' own bounce (materials, textures, sky,
+ * Russian roulette) on the xorshift32 state rng[i], each path continuing the state the one before left:
+ *   a = rng[i]; color = (0, 0, 0)
+ *   for s in 0 .. samples-1:
+ *       ray: org = org[i], dir = half(dir[i]), attenuation = half(1, 1, 1), radiance = half(0, 0, 0)   (the camera ray without the camera
+ *       res = (0, 0, 0)                                                                                  and without its two draws)
+ *       for b in 0 .. max_depth-1:                                                   (render_pixel, src/render_megakernel.cpp:34-55)
+ *           rays++; closest hit; done = the bounce's shading (draws from a)
+ *           if (!done && rr_start && b+1 >= rr_start && b+1 < max_depth && !roulette(a)) break        (res stays 0)
+ *           if (done) { res = result; break }
+ *       color = color + res                                                          (per channel, one fp32 add; the sum starts at +0)
+ *   radiance[i] = color / (float)samples;  rng_out[i] = a;  rays[i] = rays
+ * Nothing is clamped and no square root is taken: the caller owns the estimator. A frame of the renderers is exactly a chain of path queries:
+ * per pixel, seed the state as the renderer does, and per sample draw the camera ray's two jitter values from it, trace samples = 1 with the
+ * state, add the radiance (the wavefront renderer clamps every sample to [0, 1] first); sqrt(sum / spp) is the frame bit for bit.
+ * Rejected rays: an origin outside the contract range or not finite, as for rt_trace_rays. rt_trace_paths returns RT_ERR_INVALID naming the
+ * first of them and writes nothing; rt_trace_paths_device marks each — radiance = three NaNs, rays = 0xFFFFFFFF, rng_out[i] = rng[i] — and
+ * traces the others.
+ * n == 0: RT_OK, nothing launched. RT_ERR_INVALID: NULL scene or query, NULL org, dir, rng or radiance, max_depth == 0, samples == 0;
+ * RT_ERR_NO_DEVICE: a host-only scene (the arguments are checked first). Aliasing: rng_out == rng is allowed, nothing else.
+ * rt_trace_paths takes host arrays, stages them through device buffers and synchronises. rt_trace_paths_device takes device arrays and enqueues
+ * on `stream` (NULL = the null stream): no allocation, no synchronisation, no host copy. It records the scene's per-stream event, so
+ * rt_scene_update waits for it, and it shares the scene's ray cursors with the ray queries: path- and ray-query launches of one scene on
+ * different streams run one after the other (the later waits for the earlier on the device).
+ * Limits: no per-ray tmin or tmax on the first segment; no per-ray depth; no camera model (the caller generates the rays); directions pass
+ * through half precision, as every ray of the renderers does; the paths of one entry repeat the same first segment (a caller who wants
+ * jitter issues samples = 1 calls); multi-GPU is the caller's split of the ray list across scene replicas. */
+typedef struct rt_path_query {
+    uint32_t n;
+    uint32_t max_depth;     /* >= 1: rays per path at most, as rt_renderer_create's            */
+    uint32_t samples;       /* >= 1: paths per ray                                             */
+    uint32_t rr_start;      /* rt_renderer_set_russian_roulette's start_bounce; 0 = off        */
+    const float* org;       /* 3n, fp32                                                        */
+    const float* dir;       /* 3n, fp32; stored as three halves, as the renderers' rays are    */
+    const uint32_t* rng;    /* n: every ray's xorshift32 state before its first path           */
+    uint32_t* rng_out;      /* n: the state after its last path; may be NULL, may be == rng    */
+    float* radiance;        /* 3n: linear radiance                                             */
+    uint32_t* rays;         /* n or NULL: rays traced for this entry (the frame's ray count)   */
+} rt_path_query;
+int rt_trace_paths(rt_scene* scene, const rt_path_query* q);
+int rt_trace_paths_device(rt_scene* scene, const rt_path_query* q, void* stream);
+
 /* ---- Renderers: == IRenderer implementations (src/render.hpp:11-18) ------------------------ */
 enum {
     RT_RENDERER_MEGAKERNEL = 0, /* MegakernelRenderer (src/render_megakernel.hpp:13-19) */

@@ -10,6 +10,7 @@
 //   rt_denoise.hip the a-trous denoiser (rt_denoiser_*, rt_denoise[_device]) and its kernels
 //   rt_query.hip   ray queries with a per-ray tmax (rt_trace_rays[_device]) and their kernel
 //   rt_temporal.hip the temporal accumulator (rt_temporal_*) and its kernel
+//   rt_path_query.hip path queries, radiance along caller-supplied rays (rt_trace_paths[_device]) and their kernel
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -156,6 +157,7 @@ struct rt_scene {
     hipStream_t query_stream = nullptr;
     bool query_launched = false;
     uint32_t query_grid[2] = {0u, 0u};
+    uint32_t path_grid = 0u; // path queries (rt_path_query.hip): their kernel's persistent grid (0 = not sized); they share the ray queries' cursors and stream chain
 };
 
 namespace rtlib {

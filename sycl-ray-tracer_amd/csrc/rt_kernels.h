@@ -11,6 +11,7 @@
 #pragma once
 #include <cstddef>
 
+#include "rt_bounce.h"
 #include "rt_device.h"
 #include "rt_launch.h"
 
@@ -31,40 +32,6 @@ RT_DEV uint32_t queue_load(const QueueDev& q, uint32_t slot, RayState& r) {
     r.att[0] = (uint16_t)(a.y >> 16), r.att[1] = (uint16_t)b.x, r.att[2] = (uint16_t)(b.x >> 16);
     r.rad[0] = (uint16_t)b.y, r.rad[1] = (uint16_t)(b.y >> 16), r.rad[2] = c;
     return __float_as_uint(o.w);
-}
-
-RT_DEV f3 ray_dir(const RayState& r) { return mk3(h2f(r.dir[0]), h2f(r.dir[1]), h2f(r.dir[2])); }
-
-// the part of one bounce after the closest-hit query: unpack halves -> shade_hit -> repack (the body of
-// render_pixel's loop, src/render_megakernel.cpp:34-55, and of shoot_rays, src/render_wavefront.cpp:245-291)
-// FROM_TRAV (the kernels whose lanes keep a ray across shading rounds): origin and direction are READ from the traversal state — T.o
-// and T.d are r.org and h2f(r.dir) exactly, trav_begin put them there — so that r.org / r.dir are written here and consumed by the
-// trav_begin (or the queue store) that follows, live only inside the round: six lane registers less through the traversal loop.
-// (with `tab`: the kernel's staged shading tables; without: the memory path only)
-// `sink`: see shade_hit
-template <bool FROM_TRAV = false, class Sink = NoSink>
-RT_DEV bool shade_bounce(const SceneDev& S, uint32_t& rng, RayState& r, const Hit& h, f3& result, const Trav* T = nullptr, const ShadeTables* tab = nullptr,
-                         long long* ck = nullptr, const Sink& sink = Sink{}) {
-    f3 org = FROM_TRAV ? T->o : r.org;
-    f3 dir = FROM_TRAV ? T->d : ray_dir(r);
-    f3 att = mk3(h2f(r.att[0]), h2f(r.att[1]), h2f(r.att[2]));
-    f3 rad = mk3(h2f(r.rad[0]), h2f(r.rad[1]), h2f(r.rad[2]));
-    const bool done = FROM_TRAV ? shade_hit<true>(S, *tab, rng, h, org, dir, att, rad, result, ck, sink) : shade_hit<false>(S, ShadeTables{}, rng, h, org, dir, att, rad, result, nullptr, sink);
-    r.org = org;
-    r.dir[0] = f2h(dir.x), r.dir[1] = f2h(dir.y), r.dir[2] = f2h(dir.z);
-    r.att[0] = f2h(att.x), r.att[1] = f2h(att.y), r.att[2] = f2h(att.z);
-    r.rad[0] = f2h(rad.x), r.rad[1] = f2h(rad.y), r.rad[2] = f2h(rad.z);
-    return done;
-}
-
-// Russian roulette on a continuing path (extension, see rt_renderer_set_russian_roulette); false = path ends
-RT_DEV bool roulette(uint32_t& rng, RayState& r) {
-    const float qx = h2f(r.att[0]), qy = h2f(r.att[1]), qz = h2f(r.att[2]);
-    const float p = __builtin_fminf(__builtin_fmaxf(__builtin_fmaxf(qx, __builtin_fmaxf(qy, qz)), 0.05f), 1.0f);
-    const float u = rng_next(rng);
-    if (!(u < p)) return false;
-    r.att[0] = f2h(qx / p), r.att[1] = f2h(qy / p), r.att[2] = f2h(qz / p);
-    return true;
 }
 
 RT_DEV uint32_t wave_sum_u32(uint32_t v) {

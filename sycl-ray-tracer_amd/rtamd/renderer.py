@@ -135,6 +135,38 @@ class Scene:
                              occluded=d_occluded or None)
         abi.check(self._lib.rt_trace_rays_device(self.h, C.byref(q), C.c_void_p(stream or None)), self._lib)
 
+    def trace_paths(self, org: np.ndarray, dirs: np.ndarray, rng: np.ndarray, max_depth: int, samples: int = 1, rr_start: int = 0) -> dict:
+        """rt_trace_paths on host arrays: org, dirs (n, 3) float32 and rng (n,) uint32, every ray's xorshift32 state. `samples` paths of at
+        most `max_depth` rays per entry, each continuing the state the one before left. Returns {"radiance": (n, 3) float32, the mean of
+        the paths' linear radiance, "rng": (n,) uint32, the states after the last path, "rays": (n,) uint32, the rays traced}
+        (include/rt_mi355x.h: rt_path_query)."""
+        org, dirs, rng = np.asarray(org), np.asarray(dirs), np.asarray(rng)
+        if org.ndim != 2 or org.shape[1] != 3 or dirs.shape != org.shape:
+            raise ValueError("org and dirs must both be (n, 3)")
+        n = org.shape[0]
+        if rng.shape != (n,):
+            raise ValueError("rng must hold one state per ray, shape (n,)")
+        if rng.dtype.kind not in "ui":
+            raise ValueError("rng must be an integer array (xorshift32 states)")
+        org = np.ascontiguousarray(org, np.float32)
+        dirs = np.ascontiguousarray(dirs, np.float32)
+        rng = np.ascontiguousarray(rng, np.uint32)
+        out = {"radiance": np.zeros((n, 3), np.float32), "rng": np.zeros(n, np.uint32), "rays": np.zeros(n, np.uint32)}
+        q = abi.rt_path_query(n=n, max_depth=int(max_depth), samples=int(samples), rr_start=int(rr_start), org=org.ctypes.data,
+                              dir=dirs.ctypes.data, rng=rng.ctypes.data, rng_out=out["rng"].ctypes.data,
+                              radiance=out["radiance"].ctypes.data, rays=out["rays"].ctypes.data)
+        abi.check(self._lib.rt_trace_paths(self.h, C.byref(q)), self._lib)
+        return out
+
+    def trace_paths_device(self, n: int, d_org: int, d_dir: int, d_rng: int, d_radiance: int, max_depth: int, samples: int = 1,
+                           rr_start: int = 0, d_rng_out: int = 0, d_rays: int = 0, stream: int = 0) -> None:
+        """rt_trace_paths_device on DEVICE pointers (e.g. torch .data_ptr()), enqueued on `stream`; 0 = NULL (d_rng_out, d_rays: not
+        written; d_rng_out may equal d_rng). Rejected rays are marked: radiance = NaN, rays = 0xFFFFFFFF, rng_out = rng."""
+        q = abi.rt_path_query(n=int(n), max_depth=int(max_depth), samples=int(samples), rr_start=int(rr_start), org=d_org or None,
+                              dir=d_dir or None, rng=d_rng or None, rng_out=d_rng_out or None, radiance=d_radiance or None,
+                              rays=d_rays or None)
+        abi.check(self._lib.rt_trace_paths_device(self.h, C.byref(q), C.c_void_p(stream or None)), self._lib)
+
     def gbuffer(self, camera: Camera) -> dict:
         """rt_scene_gbuffer: the guide images of the camera's primary hits, {"albedo", "normal", "position"}, each (H, W, 4) float32
         (include/rt_mi355x.h states what a pixel holds)."""

@@ -260,8 +260,9 @@ int rt_trace_rays_device(rt_scene* scene, const rt_ray_query* q, void* stream);
  * rt_scene_update waits for it, and it shares the scene's ray cursors with the ray queries: path- and ray-query launches of one scene on
  * different streams run one after the other (the later waits for the earlier on the device).
  * Limits: no per-ray tmin or tmax on the first segment; no per-ray depth; no camera model (the caller generates the rays); directions pass
- * through half precision, as every ray of the renderers does; the paths of one entry repeat the same first segment (a caller who wants
- * jitter issues samples = 1 calls); multi-GPU is the caller's split of the ray list across scene replicas. */
+ * through half precision, as every ray of the renderers does; a direction that half stores as (0, 0, 0) (every |component| <= 2^-25) or with an
+ * infinite component (|component| >= 65520) hits nothing: each of the entry's paths is the sky after one ray, and no draw is taken; the
+ * paths of one entry repeat the same first segment (a caller who wants jitter issues samples = 1 calls); multi-GPU is the caller's split of the ray list across scene replicas. */
 typedef struct rt_path_query {
     uint32_t n;
     uint32_t max_depth;     /* >= 1: rays per path at most, as rt_renderer_create's            */

@@ -47,6 +47,8 @@ def lib() -> C.CDLL:
         _lib.orc_render.argtypes = [C.c_void_p, _P(abi.rt_camera), C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int,
                                     C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _P(C.c_float), _P(C.c_uint8),
                                     _P(C.c_uint64)]
+        _lib.orc_trace_paths.argtypes = [C.c_void_p, C.c_uint32, _P(C.c_float), _P(C.c_float), _P(C.c_uint32), C.c_uint32, C.c_uint32,
+                                         C.c_uint32, C.c_int, C.c_int, _P(C.c_float), _P(C.c_uint32), _P(C.c_uint32)]
         _lib.orc_hardware_threads.restype = C.c_int
     return _lib
 
@@ -127,6 +129,25 @@ class OracleScene:
                               strip_rows, rr_start, abi.fptr(f), abi.u8ptr(b), C.byref(rays))
         assert rc == 0
         return f, b, rays.value
+
+    def trace_paths(self, org, dirs, rng, max_depth: int, samples: int = 1, rr_start: int = 0, use_bvh: bool = True, nthreads: int = 0):
+        """The path query of include/rt_mi355x.h (rt_path_query) on the CPU: `samples` paths of at most `max_depth` rays per entry along
+        (org[i], dirs[i]) on the xorshift32 state rng[i]. Returns {"radiance": (n, 3) float32, "rng": (n,) uint32, "rays": (n,) uint32},
+        the keys of Scene.trace_paths. No origin is rejected: the contract range is the product's limit, not the operation's."""
+        org = np.ascontiguousarray(org, np.float32).reshape(-1, 3)
+        dirs = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
+        rng = np.ascontiguousarray(rng, np.uint32).reshape(-1)
+        n = org.shape[0]
+        if dirs.shape[0] != n or rng.shape[0] != n:
+            raise ValueError("org, dirs and rng must hold one entry per ray")
+        out = {"radiance": np.zeros((n, 3), np.float32), "rng": np.zeros(n, np.uint32), "rays": np.zeros(n, np.uint32)}
+        if nthreads <= 0:
+            nthreads = hardware_threads()
+        rc = lib().orc_trace_paths(self.h, n, abi.fptr(org), abi.fptr(dirs), abi.u32ptr(rng), int(max_depth), int(samples), int(rr_start),
+                                   int(use_bvh), nthreads, abi.fptr(out["radiance"]), abi.u32ptr(out["rng"]), abi.u32ptr(out["rays"]))
+        if rc != 0:
+            raise ValueError("oracle: max_depth and samples must be at least 1")
+        return out
 
 
 def hardware_threads() -> int:

@@ -599,10 +599,9 @@ inline bool roulette(Rng& rng, V3& att) {
     return true;
 }
 
-// render_pixel: src/render_megakernel.cpp:20-63
-inline V3 render_pixel(const Scene& sc, bool use_bvh, const rt_camera& cam, Rng& rng, int x, int y,
-                       uint32_t max_depth, uint32_t rr_start, uint64_t& ray_count) {
-    Ray rd = get_ray(cam, x, y, rng);
+// render_pixel's bounce loop, src/render_megakernel.cpp:34-55, from a first segment: a pixel's camera ray (render_pixel) or a caller's ray
+// (orc_trace_paths)
+inline V3 trace_path(const Scene& sc, bool use_bvh, Rng& rng, Ray rd, uint32_t max_depth, uint32_t rr_start, uint64_t& ray_count) {
     for (uint32_t i = 0; i < max_depth; ++i) {
         ray_count++;
         V3 att = load3(rd.att);
@@ -619,6 +618,12 @@ inline V3 render_pixel(const Scene& sc, bool use_bvh, const rt_camera& cam, Rng&
         if (done) return res;
     }
     return mk(0.0f, 0.0f, 0.0f);
+}
+
+// render_pixel: src/render_megakernel.cpp:20-63
+inline V3 render_pixel(const Scene& sc, bool use_bvh, const rt_camera& cam, Rng& rng, int x, int y,
+                       uint32_t max_depth, uint32_t rr_start, uint64_t& ray_count) {
+    return trace_path(sc, use_bvh, rng, get_ray(cam, x, y, rng), max_depth, rr_start, ray_count);
 }
 
 inline uint8_t to_unorm8(float c) { // unorm8 image write (saturate, round to nearest even) then
@@ -878,6 +883,53 @@ int orc_render(const orc_scene* s, const rt_camera* cam, int kind, uint32_t seed
     }
     for (auto& t : th) t.join();
     if (rays_out) *rays_out = total.load();
+    return 0;
+}
+
+// Path queries (include/rt_mi355x.h: rt_path_query): `samples` paths per entry along the caller's ray, on the entry's running state.
+// A path is render_pixel with get_ray's Ray built from (org[i], dir[i]) instead of the camera, hence without get_ray's two draws.
+// Entries are independent; threads take them in blocks of 64 as orc_render's take rows.
+int orc_trace_paths(const orc_scene* s, uint32_t n, const float* org, const float* dir, const uint32_t* rng_in,
+                    uint32_t max_depth, uint32_t samples, uint32_t rr_start, int use_bvh, int nthreads, float* radiance,
+                    uint32_t* rng_out, uint32_t* rays_out) {
+    if (!s || max_depth == 0 || samples == 0) return -1;
+    if (n == 0) return 0;
+    if (!org || !dir || !rng_in || !radiance) return -1;
+    const Scene& sc = s->sc;
+    const bool bvh = use_bvh != 0;
+    if (nthreads <= 0) nthreads = (int)std::thread::hardware_concurrency();
+    if (nthreads <= 0) nthreads = 1;
+    constexpr size_t kBlock = 64;
+    const size_t n_blocks = ((size_t)n + kBlock - 1) / kBlock;
+    nthreads = (int)std::min<size_t>((size_t)nthreads, n_blocks);
+    std::atomic<size_t> next_block{0};
+    auto worker = [&]() {
+        for (;;) {
+            const size_t b = next_block.fetch_add(1);
+            if (b >= n_blocks) break;
+            const size_t end = std::min<size_t>((b + 1) * kBlock, n);
+            for (size_t i = b * kBlock; i < end; ++i) {
+                Rng rng{rng_in[i]};
+                uint64_t rays = 0;
+                V3 color = mk(0, 0, 0);
+                for (uint32_t p = 0; p < samples; ++p) {
+                    Ray rd; // get_ray's RayData without the camera
+                    rd.org = mk(org[3 * i], org[3 * i + 1], org[3 * i + 2]);
+                    store3(rd.dir, mk(dir[3 * i], dir[3 * i + 1], dir[3 * i + 2]));
+                    store3(rd.att, mk(1.0f, 1.0f, 1.0f));
+                    store3(rd.rad, mk(0.0f, 0.0f, 0.0f));
+                    color = color + trace_path(sc, bvh, rng, rd, max_depth, rr_start, rays);
+                }
+                color = color / (float)samples;
+                radiance[3 * i] = color.x, radiance[3 * i + 1] = color.y, radiance[3 * i + 2] = color.z;
+                if (rng_out) rng_out[i] = rng.a;
+                if (rays_out) rays_out[i] = (uint32_t)rays;
+            }
+        }
+    };
+    std::vector<std::thread> th;
+    for (int t = 0; t < nthreads; ++t) th.emplace_back(worker);
+    for (auto& t : th) t.join();
     return 0;
 }
 

@@ -182,6 +182,7 @@ int path_enqueue(rt_scene* s, const rt_path_query* q, hipStream_t st) {
         HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, s->device));
         HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_path_query, (int)kPathBlock, 0));
         s->path_grid = (uint32_t)std::max(1, cus * std::max(1, per_cu));
+        if (const char* e = dev_knob("RT_PATH_GRID")) s->path_grid = (uint32_t)std::max(1, std::atoi(e)); // tests: a grid far below the ray list's, so every wave refills mid-flight
     }
     hipEvent_t ev = nullptr;
     if (const int rc = scene_stream_event(s, st, &ev)) return rc;

@@ -50,6 +50,123 @@ def pixel_seed_model(x, y, w, h, megakernel, salt=0):
     return ((base + np.uint64(salt) * np.uint64(0x9E3779B9)) & np.uint64(0xFFFFFFFF)).astype(np.uint32)
 
 
+def scene_bounds(sd):
+    """(lo, hi, scale) of the world triangles: the bounds and max(largest extent, largest |coordinate|), the scene scale of the contract range"""
+    v = sd.world_triangles().reshape(-1, 3)
+    lo, hi = v.min(0), v.max(0)
+    return lo, hi, float(max((hi - lo).max(), np.abs(lo).max(), np.abs(hi).max()))
+
+
+def _directed_cases():
+    """Directions a camera fan never holds, unnormalised fp32: the six axes and the twelve two-axis diagonals with exact +0 and -0 in the
+    other components, components that are half subnormals, and components on half rounding ties (1 + 2^-11 lies between 1 and 1 + 2^-10
+    and goes to the even 1, 1 + 3 * 2^-11 between 1 + 2^-10 and 1 + 2^-9 and goes to the even 1 + 2^-9: truncation gives 1 and 1 + 2^-10,
+    round-half-up 1 + 2^-10 and 1 + 2^-9; 2^-25 and 3 * 2^-25 are the same pair among the subnormals)."""
+    d = []
+    for a in range(3):
+        for sgn in (1.0, -1.0):
+            for zero in (0.0, -0.0):
+                v = [zero] * 3
+                v[a] = sgn
+                d.append(v)
+    for a, b in ((0, 1), (0, 2), (1, 2)):
+        for sa in (1.0, -1.0):
+            for sb in (1.0, -1.0):
+                v = [0.0 if sa > 0 else -0.0] * 3
+                v[a], v[b] = sa, sb
+                d.append(v)
+    d += [[3e-6, 1.0, 0.5], [-1.0, -3e-6, 2e-7], [0.25, 3e-6, -3e-6], [3e-6, 3e-6, -5e-6], [6.0e-5, -1.0, 6.1e-5]]
+    t1, t3 = 1.0 + 2.0 ** -11, 1.0 + 3.0 * 2.0 ** -11
+    d += [[t1, t3, -t1], [-t3, t1, t3], [t1 * 0.125, -t3 * 0.125, 0.125], [t3 * 32.0, t1 * 32.0, -32.0], [t1, 0.0, t3], [-t1, -t3, -0.0],
+          [2.0 ** -25, 1.0, -3.0 * 2.0 ** -25], [3.0 * 2.0 ** -25, -2.0 ** -25, -1.0]]
+    return np.array(d, f32)
+
+
+def probe_mix(sd, n, seed):
+    """The rays of light probes and bakers rather than of a camera: (org (n, 3) float32, dirs (n, 3) float32, rng (n,) uint32), shuffled, so
+    that every prefix is a mix too. Directions are NOT rounded to half: that is the kernel's job and the oracle's (R3).
+      n // 2  origins uniform inside the scene's bounds, directions uniform on the sphere times a length log-uniform in [1e-2, 1e2]
+      n // 4  origins on triangle surfaces (random world triangles, random barycentrics), directions alternately into the front and the
+              back hemisphere of the face, same lengths: half of them start inside whatever closed mesh the face belongs to
+      n // 8  origins outside the bounds, up to 90 scene scales out on one, two or three axes (inside the 100 of the contract range), half
+              aimed at the bounds' centre and half away from it
+      rest    _directed_cases(), repeated, from origins inside the bounds
+    States: random non-zero words; entries 0 to 3 hold 0, 1, 0x80000000 and 0xFFFFFFFF."""
+    g = np.random.default_rng(seed)
+    lo, hi, scale = scene_bounds(sd)
+    centre = 0.5 * (lo + hi)
+
+    def sphere(k):
+        v = g.normal(size=(k, 3))
+        return v / np.linalg.norm(v, axis=1, keepdims=True)
+
+    def lengths(k):
+        return 10.0 ** g.uniform(-2.0, 2.0, size=(k, 1))
+
+    n_in, n_surf, n_out = n // 2, n // 4, n // 8
+    n_dir = n - n_in - n_surf - n_out
+    org, dirs = [], []
+    org.append(g.uniform(lo, hi, size=(n_in, 3)))
+    dirs.append(sphere(n_in) * lengths(n_in))
+    tris = sd.world_triangles()[g.integers(0, sd.n_triangles, n_surf)]
+    u, v = g.uniform(size=n_surf), g.uniform(size=n_surf)
+    fold = u + v > 1.0
+    u, v = np.where(fold, 1.0 - u, u)[:, None], np.where(fold, 1.0 - v, v)[:, None]
+    e1, e2 = tris[:, 1] - tris[:, 0], tris[:, 2] - tris[:, 0]
+    org.append(tris[:, 0] + u * e1 + v * e2)
+    d = sphere(n_surf)
+    side = np.where(np.arange(n_surf) % 2 == 0, 1.0, -1.0)  # the hemisphere the direction has to point into
+    flip = np.sign(np.einsum("ij,ij->i", d, np.cross(e1, e2))) * side < 0
+    dirs.append(np.where(flip[:, None], -d, d) * lengths(n_surf))
+    o = g.uniform(lo, hi, size=(n_out, 3))
+    axes = g.integers(1, 8, n_out)  # which axes leave the bounds: at least one
+    out = g.uniform(0.0, 90.0, size=(n_out, 3)) * scale
+    below = g.integers(0, 2, size=(n_out, 3)) == 1
+    far = np.where(below, lo - out, hi + out)
+    o = np.where((axes[:, None] >> np.arange(3)) & 1 == 1, far, o)
+    org.append(o)
+    to = centre - o
+    to /= np.linalg.norm(to, axis=1, keepdims=True)
+    dirs.append(np.where((np.arange(n_out) % 2 == 0)[:, None], to, -to) * lengths(n_out))
+    cases = _directed_cases()
+    org.append(g.uniform(lo, hi, size=(n_dir, 3)))
+    dirs.append(cases[np.arange(n_dir) % len(cases)])
+    perm = g.permutation(n)
+    org = np.concatenate(org).astype(f32)[perm]
+    dirs = np.concatenate([np.asarray(x, f32) for x in dirs])[perm]
+    state = g.integers(1, 2 ** 32, n, dtype=np.uint64).astype(np.uint32)
+    state[:4] = np.array([0, 1, 0x80000000, 0xFFFFFFFF], np.uint32)[:min(n, 4)]
+    return np.ascontiguousarray(org), np.ascontiguousarray(dirs), state
+
+
+PROBE_N, PROBE_SEED = 4096 + 33, 17  # 65 chunks of 64 rays: one partial; 129 or 130 rays per shard
+_PROBES = {}
+
+
+def probe_case(name):
+    """(description, the oracle's scene, probe_mix(PROBE_N, PROBE_SEED)) of "cornell", "atrium" (coarse) or "tables", built once per process"""
+    if name not in _PROBES:
+        from oracle import oracle as O
+        sd = scenes.table_scene() if name == "tables" else scenes.get_scene(name, **({"coarse": True} if name == "atrium" else {}))
+        _PROBES[name] = (sd, O.OracleScene(sd), probe_mix(sd, PROBE_N, PROBE_SEED))
+    return _PROBES[name]
+
+
+_EXPECTED = {}
+
+
+def probe_expected(name, max_depth, samples, rr_start):
+    """The oracle's path query on the scene's probe mix, computed once per process and shared (read only) by the tests that compare with it"""
+    key = (name, max_depth, samples, rr_start)
+    if key not in _EXPECTED:
+        _, osc, (org, dirs, state) = probe_case(name)
+        out = osc.trace_paths(org, dirs, state, max_depth, samples=samples, rr_start=rr_start)
+        for a in out.values():
+            a.setflags(write=False)
+        _EXPECTED[key] = out
+    return _EXPECTED[key]
+
+
 # ---- the surface --------------------------------------------------------------------------------------------------------------------------
 def test_entry_points_are_declared_exported_and_prototyped(rtlib, devlib):
     header = (REPO / "include" / "rt_mi355x.h").read_text()

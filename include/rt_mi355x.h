@@ -278,6 +278,53 @@ typedef struct rt_path_query {
 int rt_trace_paths(rt_scene* scene, const rt_path_query* q);
 int rt_trace_paths_device(rt_scene* scene, const rt_path_query* q, void* stream);
 
+/* ---- Gather queries: diffuse-lobe radiance at caller-supplied points (lightmap texels, mesh vertices, the faces of ambient-cube probes).
+ * Entry i runs `samples` paths from pos[i], each with a direction of its own: the diffuse bounce's scattered direction about normal[i]
+ * (MaterialDiffuse::scatter, src/material.hpp:72-86, without its near_zero clause: there is no incoming direction), drawn from the entry's
+ * xorshift32 state. From that ray on a path is rt_trace_paths' path, same loop, same roulette rule, on the same running state:
+ *   a = rng[i]; color = (0, 0, 0)
+ *   for s in 0 .. samples-1:
+ *       u = random_unit_vector(a)        (three draws x, y, z, each -1 + 2 * next(a); v * (1 / sqrt(dot(v, v))), R1 / R2 of DESIGN.md §3)
+ *       d = normal[i] + u                (one fp32 add per component)
+ *       ray: org = pos[i], dir = half(d), attenuation = half(1, 1, 1), radiance = half(0, 0, 0)
+ *       res = the path of rt_trace_paths from that ray (rays++ per closest-hit query, draws from a)
+ *       color = color + res              (per channel, one fp32 add; the sum starts at +0)
+ *   radiance[i] = color / (float)samples;  rng_out[i] = a;  rays[i] = rays
+ * The state goes in and comes out, so a gather is bit for bit a chain of path queries: per sample draw u from the state, call rt_trace_paths
+ * with (pos[i], normal[i] + u), samples = 1 and the state, add the radiance. The result is what a white Lambertian surface at pos[i] with
+ * shading normal normal[i] would scatter, in the renderers' own arithmetic: albedo x result is what the renderers show for that surface's
+ * first diffuse bounce. Six entries with the axis normals at one point are an ambient cube.
+ * Rejected entries: a pos outside the contract range or not finite (as rt_trace_paths' origin), or a normal component that is not finite.
+ * rt_gather_paths returns RT_ERR_INVALID naming the first of them and writes nothing; rt_gather_paths_device marks each — radiance = three NaNs,
+ * rays = 0xFFFFFFFF, rng_out[i] = rng[i], no draw taken — and traces the others.
+ * n == 0: RT_OK, nothing launched. RT_ERR_INVALID: NULL scene or query, NULL pos, normal, rng or radiance, max_depth == 0, samples == 0;
+ * RT_ERR_NO_DEVICE: a host-only scene (the arguments are checked first). Aliasing: rng_out == rng is allowed, nothing else.
+ * rt_gather_paths takes host arrays, stages them through device buffers and synchronises. rt_gather_paths_device takes device arrays and
+ * enqueues on `stream` (NULL = the null stream): no allocation, no synchronisation, no host copy. It records the scene's per-stream event, so
+ * rt_scene_update waits for it, and it shares the scene's ray cursors with the ray and path queries: query launches of one scene on different
+ * streams run one after the other (the later waits for the earlier on the device).
+ * A direction that half stores as (0, 0, 0) or with an infinite component (a finite normal of 1e5, say) hits nothing: that path is the sky
+ * after one ray, and its three direction draws are still taken.
+ * Limits: the lobe is the renderers' lobe. random_unit_vector is a normalised sample of the cube [-1, 1]^3, not a uniform sample of the sphere,
+ * so pi x result is the irradiance only as far as the reference's own diffuse bounce is cosine-weighted: a kept quirk, not a bug. The normal
+ * is used as given, not normalised: its length shapes the lobe. An entry is sequential work on one lane: fewer than about (resident lanes)
+ * entries under-fill the device, so a caller with few points and many samples passes each point several times with different states and
+ * averages. There is no per-entry samples, tmin or tmax. */
+typedef struct rt_gather_query {
+    uint32_t n;
+    uint32_t max_depth;     /* >= 1, as rt_path_query's                                  */
+    uint32_t samples;       /* >= 1: paths per entry, each with a direction of its own   */
+    uint32_t rr_start;      /* as rt_path_query's; 0 = off                               */
+    const float* pos;       /* 3n: where the paths start                                 */
+    const float* normal;    /* 3n: the lobe's axis, used as given (not normalised)       */
+    const uint32_t* rng;    /* n                                                         */
+    uint32_t* rng_out;      /* n or NULL; may be == rng                                  */
+    float* radiance;        /* 3n: mean radiance over the entry's paths                  */
+    uint32_t* rays;         /* n or NULL                                                 */
+} rt_gather_query;
+int rt_gather_paths(rt_scene* scene, const rt_gather_query* q);                       /* host arrays  */
+int rt_gather_paths_device(rt_scene* scene, const rt_gather_query* q, void* stream);  /* device arrays */
+
 /* ---- Renderers: == IRenderer implementations (src/render.hpp:11-18) ------------------------ */
 enum {
     RT_RENDERER_MEGAKERNEL = 0, /* MegakernelRenderer (src/render_megakernel.hpp:13-19) */

@@ -11,6 +11,7 @@
 //   rt_query.hip   ray queries with a per-ray tmax (rt_trace_rays[_device]) and their kernel
 //   rt_temporal.hip the temporal accumulator (rt_temporal_*) and its kernel
 //   rt_path_query.hip path queries, radiance along caller-supplied rays (rt_trace_paths[_device]) and their kernel
+//   rt_path_gather.hip gather queries, diffuse-lobe radiance at caller-supplied points (rt_gather_paths[_device]) and their kernel
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -158,6 +159,7 @@ struct rt_scene {
     bool query_launched = false;
     uint32_t query_grid[2] = {0u, 0u};
     uint32_t path_grid = 0u; // path queries (rt_path_query.hip): their kernel's persistent grid (0 = not sized); they share the ray queries' cursors and stream chain
+    uint32_t gather_grid = 0u; // gather queries (rt_path_gather.hip): likewise, for k_path_gather
 };
 
 namespace rtlib {

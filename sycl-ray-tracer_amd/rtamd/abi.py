@@ -218,8 +218,24 @@ class rt_path_query(C.Structure):
     ]
 
 
+class rt_gather_query(C.Structure):
+    _fields_ = [
+        ("n", C.c_uint32),
+        ("max_depth", C.c_uint32),
+        ("samples", C.c_uint32),
+        ("rr_start", C.c_uint32),
+        ("pos", C.c_void_p),
+        ("normal", C.c_void_p),
+        ("rng", C.c_void_p),
+        ("rng_out", C.c_void_p),
+        ("radiance", C.c_void_p),
+        ("rays", C.c_void_p),
+    ]
+
+
 assert C.sizeof(rt_ray_query) == 72
 assert C.sizeof(rt_path_query) == 64
+assert C.sizeof(rt_gather_query) == 64
 assert C.sizeof(rt_denoise_params) == 20
 assert C.sizeof(rt_temporal_params) == 12
 assert C.sizeof(rt_denoise_var_params) == 24
@@ -245,6 +261,8 @@ PROTOTYPES = {
     "rt_trace_rays_device": (C.c_int, [C.c_void_p, _P(rt_ray_query), C.c_void_p]),
     "rt_trace_paths": (C.c_int, [C.c_void_p, _P(rt_path_query)]),
     "rt_trace_paths_device": (C.c_int, [C.c_void_p, _P(rt_path_query), C.c_void_p]),
+    "rt_gather_paths": (C.c_int, [C.c_void_p, _P(rt_gather_query)]),
+    "rt_gather_paths_device": (C.c_int, [C.c_void_p, _P(rt_gather_query), C.c_void_p]),
     "rt_renderer_create": (C.c_int, [C.c_int, C.c_void_p, C.c_int32, C.c_int32, C.c_uint32, C.c_uint32,
                                      C.c_uint32, _P(C.c_void_p)]),
     "rt_renderer_destroy": (None, [C.c_void_p]),

@@ -1,0 +1,58 @@
+"""A small vertex baker over gather queries (include/rt_mi355x.h: rt_gather_paths): the diffuse-lobe radiance at every triangle corner of a
+scene. Pure Python over Scene.gather_paths; `albedo x result` is what the renderers show for a diffuse surface's first bounce there."""
+from __future__ import annotations
+
+import numpy as np
+
+from .renderer import Scene
+from .scenes import SceneDesc
+
+f32 = np.float32
+
+
+def vertex_points(sd: SceneDesc):
+    """The world-space corners of every triangle: (pos (T, 3, 3) float32, normal (T, 3, 3) float32), [triangle, corner, xyz].
+    Positions with the scene builder's expression ((m0*x + m4*y) + m8*z) + m12 in fp32 (csrc/scene_build.cpp); normals are the vertex
+    normals through the instance's normal matrix (column-major 3x3, the shading's expression), normalised, in fp32."""
+    idx = np.asarray(sd.indices, np.int64).reshape(-1, 3)
+    inst = np.asarray(sd.tri_instance, np.int64)
+    m = np.asarray(sd.transforms, f32).reshape(-1, 16)[inst][:, None, :]    # (T, 1, 16)
+    nm = np.asarray(sd.normal_mats, f32).reshape(-1, 9)[inst][:, None, :]   # (T, 1, 9)
+    p = np.asarray(sd.positions, f32)[idx]                                  # (T, 3, 3)
+    n = np.asarray(sd.normals, f32)[idx]
+    x, y, z = p[..., 0], p[..., 1], p[..., 2]
+    pos = np.stack([((m[..., r] * x + m[..., 4 + r] * y) + m[..., 8 + r] * z) + m[..., 12 + r] for r in range(3)], -1)
+    x, y, z = n[..., 0], n[..., 1], n[..., 2]
+    g = np.stack([(nm[..., r] * x + nm[..., 3 + r] * y) + nm[..., 6 + r] * z for r in range(3)], -1)
+    inv = f32(1.0) / np.sqrt((g[..., 0] * g[..., 0] + g[..., 1] * g[..., 1]) + g[..., 2] * g[..., 2])
+    nrm = g * inv[..., None]
+    assert pos.dtype == f32 and nrm.dtype == f32
+    return np.ascontiguousarray(pos), np.ascontiguousarray(nrm)
+
+
+def corner_seeds(n_corners: int, repeats: int, seed: int) -> np.ndarray:
+    """One xorshift32 state per (corner, repeat), (n_corners, repeats) uint32: a Weyl sequence from `seed`, never 0 (the state xorshift
+    cannot leave)."""
+    k = np.arange(n_corners * repeats, dtype=np.uint64) + np.uint64(1)
+    s = ((np.uint64(seed & 0xFFFFFFFF) + k * np.uint64(0x9E3779B9)) & np.uint64(0xFFFFFFFF)).astype(np.uint32)
+    s[s == 0] = np.uint32(0x9E3779B9)
+    return s.reshape(n_corners, repeats)
+
+
+def bake_vertices(scene: Scene, sd: SceneDesc, samples: int, max_depth: int, seed: int, repeats: int = 1) -> np.ndarray:
+    """The gathered radiance at every triangle corner, (T, 3, 3) float32 [triangle, corner, rgb]: one gather_paths call over 3T x repeats
+    entries (corner-major, the repeats of a corner side by side, each with a state of its own from corner_seeds), the repeats averaged in
+    fp32 in order. An entry is one lane's sequential work, so `repeats` is how a small mesh fills the device: samples x repeats paths per
+    corner in all."""
+    if repeats < 1:
+        raise ValueError("repeats must be at least 1")
+    pos, nrm = vertex_points(sd)
+    c = pos.shape[0] * 3
+    states = corner_seeds(c, repeats, seed)
+    out = scene.gather_paths(np.repeat(pos.reshape(c, 3), repeats, axis=0), np.repeat(nrm.reshape(c, 3), repeats, axis=0), states.reshape(-1),
+                             max_depth, samples=samples)
+    rad = out["radiance"].reshape(c, repeats, 3)
+    total = np.zeros((c, 3), f32)
+    for k in range(repeats):
+        total = total + rad[:, k]
+    return (total / f32(repeats)).reshape(-1, 3, 3)

@@ -167,6 +167,38 @@ class Scene:
                               rays=d_rays or None)
         abi.check(self._lib.rt_trace_paths_device(self.h, C.byref(q), C.c_void_p(stream or None)), self._lib)
 
+    def gather_paths(self, pos: np.ndarray, normals: np.ndarray, rng: np.ndarray, max_depth: int, samples: int = 1, rr_start: int = 0) -> dict:
+        """rt_gather_paths on host arrays: pos, normals (n, 3) float32 and rng (n,) uint32, every entry's xorshift32 state. `samples` paths
+        of at most `max_depth` rays per entry, each from pos[i] along the diffuse bounce's own direction normals[i] + random_unit_vector
+        drawn from the running state. Returns {"radiance": (n, 3) float32, the mean of the paths' linear radiance, "rng": (n,) uint32, the
+        states after the last path, "rays": (n,) uint32, the rays traced} (include/rt_mi355x.h: rt_gather_query)."""
+        pos, normals, rng = np.asarray(pos), np.asarray(normals), np.asarray(rng)
+        if pos.ndim != 2 or pos.shape[1] != 3 or normals.shape != pos.shape:
+            raise ValueError("pos and normals must both be (n, 3)")
+        n = pos.shape[0]
+        if rng.shape != (n,):
+            raise ValueError("rng must hold one state per entry, shape (n,)")
+        if rng.dtype.kind not in "ui":
+            raise ValueError("rng must be an integer array (xorshift32 states)")
+        pos = np.ascontiguousarray(pos, np.float32)
+        normals = np.ascontiguousarray(normals, np.float32)
+        rng = np.ascontiguousarray(rng, np.uint32)
+        out = {"radiance": np.zeros((n, 3), np.float32), "rng": np.zeros(n, np.uint32), "rays": np.zeros(n, np.uint32)}
+        q = abi.rt_gather_query(n=n, max_depth=int(max_depth), samples=int(samples), rr_start=int(rr_start), pos=pos.ctypes.data,
+                                normal=normals.ctypes.data, rng=rng.ctypes.data, rng_out=out["rng"].ctypes.data,
+                                radiance=out["radiance"].ctypes.data, rays=out["rays"].ctypes.data)
+        abi.check(self._lib.rt_gather_paths(self.h, C.byref(q)), self._lib)
+        return out
+
+    def gather_paths_device(self, n: int, d_pos: int, d_normal: int, d_rng: int, d_radiance: int, max_depth: int, samples: int = 1,
+                            rr_start: int = 0, d_rng_out: int = 0, d_rays: int = 0, stream: int = 0) -> None:
+        """rt_gather_paths_device on DEVICE pointers (e.g. torch .data_ptr()), enqueued on `stream`; 0 = NULL (d_rng_out, d_rays: not
+        written; d_rng_out may equal d_rng). Rejected entries are marked: radiance = NaN, rays = 0xFFFFFFFF, rng_out = rng."""
+        q = abi.rt_gather_query(n=int(n), max_depth=int(max_depth), samples=int(samples), rr_start=int(rr_start), pos=d_pos or None,
+                                normal=d_normal or None, rng=d_rng or None, rng_out=d_rng_out or None, radiance=d_radiance or None,
+                                rays=d_rays or None)
+        abi.check(self._lib.rt_gather_paths_device(self.h, C.byref(q), C.c_void_p(stream or None)), self._lib)
+
     def gbuffer(self, camera: Camera) -> dict:
         """rt_scene_gbuffer: the guide images of the camera's primary hits, {"albedo", "normal", "position"}, each (H, W, 4) float32
         (include/rt_mi355x.h states what a pixel holds)."""

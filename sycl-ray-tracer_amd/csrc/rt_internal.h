@@ -12,6 +12,8 @@
 //   rt_temporal.hip the temporal accumulator (rt_temporal_*) and its kernel
 //   rt_path_query.hip path queries, radiance along caller-supplied rays (rt_trace_paths[_device]) and their kernel
 //   rt_path_gather.hip gather queries, diffuse-lobe radiance at caller-supplied points (rt_gather_paths[_device]) and their kernel
+//   rt_query_launch.h what those three units share on the host: grid sizing, the launch on the shared cursors, the path / gather checks and staging
+//   rt_path_rounds.h  the kernel body the last two share (path_rounds<E>)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -139,7 +141,16 @@ struct SceneUpdate {
     bool host_stale = false; // the host copy (hs.nodes, tris, wverts, shade, sah_cost) lags a device update
 };
 
-constexpr uint32_t kQueryCursorBytes = 32u * 128u; // rt_query.hip: a cursor per shard of the rays, each on a 128-byte line of its own
+// The cursors of the three query kinds (rt_query.hip, rt_path_query.hip, rt_path_gather.hip). A launch's entries are cut into kQueryHeads
+// contiguous shards, each with a cursor of its own on a 128-byte line; a wave claims kQueryChunk entries per atomic. It starts at shard
+// blockIdx % kQueryHeads — workgroups are dealt round-robin to the 8 XCDs, so each shard is drawn on by one XCD — and moves on to the next
+// shard when its own is exhausted. The first version had ONE cursor and claimed as many rays as the wave had idle lanes: ~6,000 waves drawing
+// on one atomic word, and CLOSEST took 1.9 ms for 4 M primary rays of the atrium against k_intersect_batch's 0.49.
+constexpr uint32_t kQueryCursorBytes = 32u * 128u;
+constexpr uint32_t kQueryChunk = 64, kQueryHeads = 32, kQueryHeadStride = 16; // (stride in 8-byte words)
+static_assert(kQueryHeads * kQueryHeadStride * 8u == kQueryCursorBytes, "the scene's cursor block holds one 128-byte line per shard");
+// the query kernels, each with a persistent grid of its own (rt_scene::query_grid)
+enum QueryKind : int { kQueryKindClosest = 0, kQueryKindAny = 1, kQueryKindPath = 2, kQueryKindGather = 3, kQueryKinds = 4 };
 
 struct rt_scene {
     HostScene hs;
@@ -152,14 +163,13 @@ struct rt_scene {
     // one event per stream a G-buffer or a ray query was enqueued on (rt_scene_gbuffer[_device], rt_trace_rays[_device]), recorded behind
     // every launch there: rt_scene_update waits for all of them, so no launch on any stream still reads the scene when it is rewritten
     std::vector<std::pair<hipStream_t, hipEvent_t>> ev_gbuffer;
-    // ray queries (rt_query.hip): the ray cursors their launches share (kQueryCursorBytes of device memory, device scenes only), the stream of the last
-    // query launch (a launch on another stream waits for it on the device: they share the cursor), the persistent grid per mode (0 = not sized)
+    // ray, path and gather queries (rt_query_launch.h): the cursors their launches share (kQueryCursorBytes of device memory, device scenes only), the
+    // stream of the last query launch (a launch on another stream waits for it on the device: they share the cursors), every query kernel's
+    // persistent grid (0 = not sized)
     unsigned long long* d_query_cursor = nullptr;
     hipStream_t query_stream = nullptr;
     bool query_launched = false;
-    uint32_t query_grid[2] = {0u, 0u};
-    uint32_t path_grid = 0u; // path queries (rt_path_query.hip): their kernel's persistent grid (0 = not sized); they share the ray queries' cursors and stream chain
-    uint32_t gather_grid = 0u; // gather queries (rt_path_gather.hip): likewise, for k_path_gather
+    uint32_t query_grid[kQueryKinds] = {};
 };
 
 namespace rtlib {

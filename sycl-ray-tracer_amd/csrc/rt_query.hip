@@ -1,7 +1,7 @@
 // rt_query.hip — ray queries with a per-ray tmax: rt_trace_rays[_device] (closest hit, occlusion) and their kernel k_query<ANY>.
 // (A unit of its own, as rt_gbuffer.hip is: a second traversal kernel beside k_intersect_batch in rt_probes.hip changes that kernel's
 // listing. tests/test_ray_query.py runs the ISA hazard scan of tests/test_isa_hazards.py on this unit's listing.)
-#include "rt_internal.h"
+#include "rt_query_launch.h"
 #include "rt_device.h"
 
 namespace rt {
@@ -9,13 +9,7 @@ namespace rt {
 constexpr uint32_t kQueryBlock = 512; // threads per workgroup: 8 independent waves share one LDS copy of the top of the BVH (as k_megakernel)
 constexpr uint32_t kQueryWaves = 6;   // waves per SIMD the kernel is compiled for (k_megakernel's budget: 80 VGPRs)
 constexpr uint32_t kQueryRefill = 16; // idle lanes of a wave that end its traversal phase: they write their results and take new rays
-constexpr uint32_t kQueryChunk = 64;  // rays a wave claims per atomic
-// The rays are cut into kQueryHeads contiguous shards, each with a cursor of its own on a 128-byte line (rt_internal.h: kQueryCursorBytes). A
-// wave starts at shard blockIdx % kQueryHeads — workgroups are dealt round-robin to the 8 XCDs, so each shard is drawn on by one XCD — and moves
-// on to the next shard when its own is exhausted. The first version had ONE cursor and claimed as many rays as the wave had idle lanes: ~6,000
-// waves drawing on one atomic word, and CLOSEST took 1.9 ms for 4 M primary rays of the atrium against k_intersect_batch's 0.49.
-constexpr uint32_t kQueryHeads = 32, kQueryHeadStride = 16; // (in 8-byte words)
-static_assert(kQueryHeads * kQueryHeadStride * 8u == kQueryCursorBytes, "the scene's cursor block holds one 128-byte line per shard");
+// (the shards, their cursors and the claim size — kQueryHeads, kQueryHeadStride, kQueryChunk — are rt_internal.h's, shared with the path and gather queries)
 
 // what a launch reads and writes (include/rt_mi355x.h: rt_ray_query; NULL outputs are not written)
 struct QueryDev {
@@ -131,39 +125,16 @@ int query_check(const rt_scene* s, const rt_ray_query* q) {
     return RT_OK;
 }
 
-// the cursor reset, the launch and the event rt_scene_update waits for (PRE: query_check passed, n > 0, pointers on the scene's device)
+// fills the launch struct and hands it to the shared launch (PRE: query_check passed, n > 0, pointers on the scene's device)
 int query_enqueue(rt_scene* s, const rt_ray_query* q, hipStream_t st) {
-    HIPCHK(hipSetDevice(s->device));
     const bool any = q->mode == RT_QUERY_ANY;
-    if (!s->query_grid[any]) { // persistent: as many workgroups as are resident at once
-        int cus = 0, per_cu = 0;
-        HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, s->device));
-        if (any) HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_query<true>, (int)kQueryBlock, 0));
-        else HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_query<false>, (int)kQueryBlock, 0));
-        s->query_grid[any] = (uint32_t)std::max(1, cus * std::max(1, per_cu));
-    }
-    hipEvent_t ev = nullptr;
-    if (const int rc = scene_stream_event(s, st, &ev)) return rc;
-    if (s->query_launched && s->query_stream != st) { // the cursor is the scene's: the last query launch, on another stream, ends first
-        hipEvent_t prev = nullptr;
-        if (const int rc = scene_stream_event(s, s->query_stream, &prev)) return rc;
-        HIPCHK(hipStreamWaitEvent(st, prev, 0));
-    }
-    QueryDev d;
+    QueryDev d{};
     d.org = q->org, d.dir = q->dir, d.tmax = q->tmax;
     d.t = any ? nullptr : q->t, d.u = any ? nullptr : q->u, d.v = any ? nullptr : q->v, d.tri = any ? nullptr : q->tri;
     d.occluded = any ? q->occluded : nullptr;
-    d.cursor = s->d_query_cursor;
     d.n = q->n;
-    d.range = contract_range(s->hs);
-    const uint32_t grid = (uint32_t)std::min<uint64_t>(s->query_grid[any], ((uint64_t)q->n + kQueryBlock - 1u) / kQueryBlock);
-    HIPCHK(hipMemsetAsync(s->d_query_cursor, 0, kQueryCursorBytes, st));
-    if (any) hipLaunchKernelGGL(k_query<true>, dim3(grid), dim3(kQueryBlock), 0, st, s->dev, d);
-    else hipLaunchKernelGGL(k_query<false>, dim3(grid), dim3(kQueryBlock), 0, st, s->dev, d);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(ev, st));
-    s->query_stream = st, s->query_launched = true;
-    return RT_OK;
+    if (any) return query_launch(s, kQueryKindAny, k_query<true>, kQueryBlock, d, q->n, st);
+    return query_launch(s, kQueryKindClosest, k_query<false>, kQueryBlock, d, q->n, st);
 }
 
 } // namespace

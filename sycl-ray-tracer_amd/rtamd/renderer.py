@@ -135,28 +135,32 @@ class Scene:
                              occluded=d_occluded or None)
         abi.check(self._lib.rt_trace_rays_device(self.h, C.byref(q), C.c_void_p(stream or None)), self._lib)
 
+    def _paths(self, call, query, names, fields, what, in0, in1, rng, max_depth, samples, rr_start) -> dict:
+        """trace_paths and gather_paths: two (n, 3) float32 inputs (`names` in the messages, `fields` of `query`) and one xorshift32 state
+        per ray or entry (`what`), through the host-array entry point `call`."""
+        in0, in1, rng = np.asarray(in0), np.asarray(in1), np.asarray(rng)
+        if in0.ndim != 2 or in0.shape[1] != 3 or in1.shape != in0.shape:
+            raise ValueError(f"{names[0]} and {names[1]} must both be (n, 3)")
+        n = in0.shape[0]
+        if rng.shape != (n,):
+            raise ValueError(f"rng must hold one state per {what}, shape (n,)")
+        if rng.dtype.kind not in "ui":
+            raise ValueError("rng must be an integer array (xorshift32 states)")
+        in0, in1, rng = np.ascontiguousarray(in0, np.float32), np.ascontiguousarray(in1, np.float32), np.ascontiguousarray(rng, np.uint32)
+        out = {"radiance": np.zeros((n, 3), np.float32), "rng": np.zeros(n, np.uint32), "rays": np.zeros(n, np.uint32)}
+        q = query(n=n, max_depth=int(max_depth), samples=int(samples), rr_start=int(rr_start), rng=rng.ctypes.data,
+                  rng_out=out["rng"].ctypes.data, radiance=out["radiance"].ctypes.data, rays=out["rays"].ctypes.data,
+                  **{fields[0]: in0.ctypes.data, fields[1]: in1.ctypes.data})
+        abi.check(call(self.h, C.byref(q)), self._lib)
+        return out
+
     def trace_paths(self, org: np.ndarray, dirs: np.ndarray, rng: np.ndarray, max_depth: int, samples: int = 1, rr_start: int = 0) -> dict:
         """rt_trace_paths on host arrays: org, dirs (n, 3) float32 and rng (n,) uint32, every ray's xorshift32 state. `samples` paths of at
         most `max_depth` rays per entry, each continuing the state the one before left. Returns {"radiance": (n, 3) float32, the mean of
         the paths' linear radiance, "rng": (n,) uint32, the states after the last path, "rays": (n,) uint32, the rays traced}
         (include/rt_mi355x.h: rt_path_query)."""
-        org, dirs, rng = np.asarray(org), np.asarray(dirs), np.asarray(rng)
-        if org.ndim != 2 or org.shape[1] != 3 or dirs.shape != org.shape:
-            raise ValueError("org and dirs must both be (n, 3)")
-        n = org.shape[0]
-        if rng.shape != (n,):
-            raise ValueError("rng must hold one state per ray, shape (n,)")
-        if rng.dtype.kind not in "ui":
-            raise ValueError("rng must be an integer array (xorshift32 states)")
-        org = np.ascontiguousarray(org, np.float32)
-        dirs = np.ascontiguousarray(dirs, np.float32)
-        rng = np.ascontiguousarray(rng, np.uint32)
-        out = {"radiance": np.zeros((n, 3), np.float32), "rng": np.zeros(n, np.uint32), "rays": np.zeros(n, np.uint32)}
-        q = abi.rt_path_query(n=n, max_depth=int(max_depth), samples=int(samples), rr_start=int(rr_start), org=org.ctypes.data,
-                              dir=dirs.ctypes.data, rng=rng.ctypes.data, rng_out=out["rng"].ctypes.data,
-                              radiance=out["radiance"].ctypes.data, rays=out["rays"].ctypes.data)
-        abi.check(self._lib.rt_trace_paths(self.h, C.byref(q)), self._lib)
-        return out
+        return self._paths(self._lib.rt_trace_paths, abi.rt_path_query, ("org", "dirs"), ("org", "dir"), "ray", org, dirs, rng,
+                           max_depth, samples, rr_start)
 
     def trace_paths_device(self, n: int, d_org: int, d_dir: int, d_rng: int, d_radiance: int, max_depth: int, samples: int = 1,
                            rr_start: int = 0, d_rng_out: int = 0, d_rays: int = 0, stream: int = 0) -> None:
@@ -172,23 +176,8 @@ class Scene:
         of at most `max_depth` rays per entry, each from pos[i] along the diffuse bounce's own direction normals[i] + random_unit_vector
         drawn from the running state. Returns {"radiance": (n, 3) float32, the mean of the paths' linear radiance, "rng": (n,) uint32, the
         states after the last path, "rays": (n,) uint32, the rays traced} (include/rt_mi355x.h: rt_gather_query)."""
-        pos, normals, rng = np.asarray(pos), np.asarray(normals), np.asarray(rng)
-        if pos.ndim != 2 or pos.shape[1] != 3 or normals.shape != pos.shape:
-            raise ValueError("pos and normals must both be (n, 3)")
-        n = pos.shape[0]
-        if rng.shape != (n,):
-            raise ValueError("rng must hold one state per entry, shape (n,)")
-        if rng.dtype.kind not in "ui":
-            raise ValueError("rng must be an integer array (xorshift32 states)")
-        pos = np.ascontiguousarray(pos, np.float32)
-        normals = np.ascontiguousarray(normals, np.float32)
-        rng = np.ascontiguousarray(rng, np.uint32)
-        out = {"radiance": np.zeros((n, 3), np.float32), "rng": np.zeros(n, np.uint32), "rays": np.zeros(n, np.uint32)}
-        q = abi.rt_gather_query(n=n, max_depth=int(max_depth), samples=int(samples), rr_start=int(rr_start), pos=pos.ctypes.data,
-                                normal=normals.ctypes.data, rng=rng.ctypes.data, rng_out=out["rng"].ctypes.data,
-                                radiance=out["radiance"].ctypes.data, rays=out["rays"].ctypes.data)
-        abi.check(self._lib.rt_gather_paths(self.h, C.byref(q)), self._lib)
-        return out
+        return self._paths(self._lib.rt_gather_paths, abi.rt_gather_query, ("pos", "normals"), ("pos", "normal"), "entry", pos,
+                           normals, rng, max_depth, samples, rr_start)
 
     def gather_paths_device(self, n: int, d_pos: int, d_normal: int, d_rng: int, d_radiance: int, max_depth: int, samples: int = 1,
                             rr_start: int = 0, d_rng_out: int = 0, d_rays: int = 0, stream: int = 0) -> None:

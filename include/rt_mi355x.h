@@ -325,6 +325,57 @@ typedef struct rt_gather_query {
 int rt_gather_paths(rt_scene* scene, const rt_gather_query* q);                       /* host arrays  */
 int rt_gather_paths_device(rt_scene* scene, const rt_gather_query* q, void* stream);  /* device arrays */
 
+/* ---- Lightmap baking: the atlas-side half of a bake around one gather query, on one stream. A lightmap is a W x H atlas over one scene with
+ * one lightmap UV per triangle corner: lm_uv holds 6 floats per triangle in the scene's global triangle order, corner 0, 1, 2 as (u, v),
+ * copied at creation. Texel i = y * W + x; (u, v) = (0, 0) is the corner of texel (0, 0); nothing wraps. Every operation below is one R1 fp32
+ * operation of DESIGN.md §3, left to right as bracketed, never contracted.
+ *   1. Coverage. Corner k in texel space: P_k = (u_k * (float)W, v_k * (float)H); the texel's centre c = ((float)x + 0.5f, (float)y + 0.5f).
+ *      E(A, B, q) = (B.x - A.x) * (q.y - A.y) - (B.y - A.y) * (q.x - A.x). The value of the directed edge P_i -> P_j at q is E(P_i, P_j, q) if
+ *      P_i comes first in the order (x, then y; P_i.x < P_j.x, or equal and P_i.y <= P_j.y), else -E(P_j, P_i, q): two triangles that share
+ *      an edge with bit-identical corners see exact negatives, so no centre between them is lost and none needs a tolerance.
+ *      area = edge(P_0 -> P_1) at P_2; e0, e1, e2 = the edges P_1 -> P_2, P_2 -> P_0, P_0 -> P_1 at c. Triangle t covers the texel iff its six
+ *      texel-space coordinates are finite, area != 0, and e0, e1, e2 are all >= 0 (area > 0) or all <= 0 (area < 0); a NaN value covers
+ *      nothing (UVs of 1e30 overflow to that). The texel's owner is the LOWEST covering triangle index; 0xFFFFFFFF: none.
+ *   2. Guides, for the owner: bx = e1 / area, by = e2 / area, w = (1.0f - bx) - by, no clamp. pos = (b[k] * w + b[3 + k] * bx) + b[6 + k] * by
+ *      over the triangle's nine world-space vertex floats b (rt_scene_gbuffer_motion's expression). normal = rt_scene_gbuffer's: the vertex
+ *      normals as normalize((w * n0 + bx * n1) + by * n2), through the instance's normal matrix, normalised again. An empty texel has pos =
+ *      three quiet NaNs (0x7FC00000) and normal = 0.
+ *   3. Entries. Texel i and repeat k make entry e = i * repeats + k with texel i's pos and normal and the state
+ *      (seed + (e + 1) * 0x9E3779B9) mod 2^32, 0 replaced by 0x9E3779B9.
+ *   4. One rt_gather_paths_device over the W * H * repeats entries (samples, max_depth, rr_start as given). Empty texels are rejected there by
+ *      their position: a claim, no ray.
+ *   5. Resolve. A texel is SAMPLED iff it has an owner and none of its entries was rejected (vertex normals of zero make a NaN normal, which is).
+ *      Sampled: total = +0, total = total + radiance[i * repeats + k] for k in order, rgb = total / (float)repeats, alpha 1. Else (0, 0, 0, 0).
+ *   6. `dilate` passes, ping-pong: a texel with alpha 0 in the pass's input looks at dy = -1 .. 1 (outer), dx = -1 .. 1 (inner), the centre
+ *      and taps outside the atlas skipped; over the taps with alpha > 0, S += rgb in tap order from +0, n counted; n > 0: rgb = S / (float)n,
+ *      alpha 0.5. Every other texel is copied. So alpha 1 = sampled, 0.5 = filled by dilation, 0 = still empty.
+ *   7. Stats: covered = texels with an owner, sampled as in 5, filled = texels with alpha 0.5 at the end, rays = the sum of the gather's ray
+ *      counts over the entries not rejected. d_stats holds the same 24 bytes.
+ * Nothing here multiplies by an albedo or adds emission: albedo x lightmap is the caller's, as for the gather.
+ * rt_lightmap_texels[_device] return steps 1 and 2: tri (W*H uint32), pos and normal (3*W*H floats each); any may be NULL, not all three.
+ * rt_lightmap_bake[_device] run steps 1 to 7 into out_rgba (W*H*4 floats; the device pointer 16-byte aligned); stats / d_stats may be NULL.
+ * The lightmap owns every device buffer it needs, allocated by rt_lightmap_create: no later call allocates on the device. Per triangle: the
+ * UV copy, 24 bytes, and for a scene without RT_SCENE_UPDATABLE a copy of its world-space vertices, 36 bytes (an updatable scene's own are
+ * read in place, so a bake after rt_scene_update sees the moved geometry). Per texel: the owner plane (4) and two float4 planes (32), and per
+ * entry, max_repeats of them per texel, pos, normal, state, radiance and ray count (12 + 12 + 4 + 12 + 4): 36 + 44 * max_repeats bytes.
+ * The host forms synchronise; the device forms enqueue on `stream` (NULL = the null stream) and return. Calls on one lightmap are serialised
+ * by the lightmap: each records an event that the next call's stream waits for. Every call records the scene's per-stream event behind its
+ * last kernel that reads the scene's geometry, so rt_scene_update waits for it. A lightmap is destroyed before its scene, as a renderer is.
+ * Refused with RT_ERR_INVALID, before any HIP call: NULL handles or required pointers, W or H outside 1 .. 8192, max_repeats == 0,
+ * W * H * max_repeats >= 2^31, samples == 0, max_depth == 0, repeats == 0, repeats > max_repeats, dilate > 16. After these,
+ * rt_lightmap_create returns RT_ERR_NO_DEVICE for a host-only scene.
+ * Limits: a texel is its centre (no conservative rasterisation, no supersampling inside a texel); there is no chart packer and no reading of
+ * a second UV set from a file; one device. */
+typedef struct rt_lightmap rt_lightmap;
+typedef struct rt_lightmap_params { uint32_t samples, max_depth, rr_start, repeats, seed, dilate; } rt_lightmap_params; /* 24 bytes */
+typedef struct rt_lightmap_stats  { uint32_t covered, sampled, filled, reserved; uint64_t rays; } rt_lightmap_stats;    /* 24 bytes */
+int  rt_lightmap_create(rt_scene* scene, int32_t width, int32_t height, uint32_t max_repeats, const float* lm_uv, rt_lightmap** out);
+void rt_lightmap_destroy(rt_lightmap* lm);
+int  rt_lightmap_texels(rt_lightmap* lm, uint32_t* tri, float* pos, float* normal);                       /* host arrays, synchronises */
+int  rt_lightmap_texels_device(rt_lightmap* lm, void* d_tri, void* d_pos, void* d_normal, void* stream);  /* device arrays, enqueues    */
+int  rt_lightmap_bake(rt_lightmap* lm, const rt_lightmap_params* p, float* out_rgba, rt_lightmap_stats* stats);
+int  rt_lightmap_bake_device(rt_lightmap* lm, const rt_lightmap_params* p, void* d_out_rgba, void* d_stats, void* stream);
+
 /* ---- Renderers: == IRenderer implementations (src/render.hpp:11-18) ------------------------ */
 enum {
     RT_RENDERER_MEGAKERNEL = 0, /* MegakernelRenderer (src/render_megakernel.hpp:13-19) */

@@ -14,6 +14,7 @@
 //   rt_path_gather.hip gather queries, diffuse-lobe radiance at caller-supplied points (rt_gather_paths[_device]) and their kernel
 //   rt_query_launch.h what those three units share on the host: grid sizing, the launch on the shared cursors, the path / gather checks and staging
 //   rt_path_rounds.h  the kernel body the last two share (path_rounds<E>)
+//   rt_lightmap.hip lightmap baking around one gather query (rt_lightmap_*): UV coverage, texel guides, resolve and dilation kernels
 #pragma once
 #include <hip/hip_runtime.h>
 

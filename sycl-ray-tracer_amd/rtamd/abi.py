@@ -233,7 +233,33 @@ class rt_gather_query(C.Structure):
     ]
 
 
+class rt_lightmap_params(C.Structure):
+    _fields_ = [
+        ("samples", C.c_uint32),
+        ("max_depth", C.c_uint32),
+        ("rr_start", C.c_uint32),
+        ("repeats", C.c_uint32),
+        ("seed", C.c_uint32),
+        ("dilate", C.c_uint32),
+    ]
+
+
+class rt_lightmap_stats(C.Structure):
+    _fields_ = [
+        ("covered", C.c_uint32),
+        ("sampled", C.c_uint32),
+        ("filled", C.c_uint32),
+        ("reserved", C.c_uint32),
+        ("rays", C.c_uint64),
+    ]
+
+
+RT_LIGHTMAP_MAX_SIZE = 8192
+RT_LIGHTMAP_MAX_DILATE = 16
+
 assert C.sizeof(rt_ray_query) == 72
+assert C.sizeof(rt_lightmap_params) == 24
+assert C.sizeof(rt_lightmap_stats) == 24
 assert C.sizeof(rt_path_query) == 64
 assert C.sizeof(rt_gather_query) == 64
 assert C.sizeof(rt_denoise_params) == 20
@@ -263,6 +289,12 @@ PROTOTYPES = {
     "rt_trace_paths_device": (C.c_int, [C.c_void_p, _P(rt_path_query), C.c_void_p]),
     "rt_gather_paths": (C.c_int, [C.c_void_p, _P(rt_gather_query)]),
     "rt_gather_paths_device": (C.c_int, [C.c_void_p, _P(rt_gather_query), C.c_void_p]),
+    "rt_lightmap_create": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_uint32, _P(C.c_float), _P(C.c_void_p)]),
+    "rt_lightmap_destroy": (None, [C.c_void_p]),
+    "rt_lightmap_texels": (C.c_int, [C.c_void_p, _P(C.c_uint32), _P(C.c_float), _P(C.c_float)]),
+    "rt_lightmap_texels_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_lightmap_bake": (C.c_int, [C.c_void_p, _P(rt_lightmap_params), _P(C.c_float), _P(rt_lightmap_stats)]),
+    "rt_lightmap_bake_device": (C.c_int, [C.c_void_p, _P(rt_lightmap_params), C.c_void_p, C.c_void_p, C.c_void_p]),
     "rt_renderer_create": (C.c_int, [C.c_int, C.c_void_p, C.c_int32, C.c_int32, C.c_uint32, C.c_uint32,
                                      C.c_uint32, _P(C.c_void_p)]),
     "rt_renderer_destroy": (None, [C.c_void_p]),

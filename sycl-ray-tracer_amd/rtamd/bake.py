@@ -56,3 +56,30 @@ def bake_vertices(scene: Scene, sd: SceneDesc, samples: int, max_depth: int, see
     for k in range(repeats):
         total = total + rad[:, k]
     return (total / f32(repeats)).reshape(-1, 3, 3)
+
+
+def triangle_grid_uvs(n_triangles: int, width: int, height: int, gutter: int = 1) -> np.ndarray:
+    """A trivial lightmap unwrap for a width x height atlas (renderer.Lightmap), (n_triangles, 3, 2) float32: the atlas is cut into square
+    cells of s x s texels, s the largest side at which every triangle gets a cell of its own (row-major, triangle t in cell t), and triangle t
+    is the right triangle on its cell's low corner, inset by `gutter` texels on every side: corners (g, g), (s - g, g), (g, s - g) from the
+    cell's origin, in texels, divided by the atlas size in fp32. Raises ValueError where s - 2 * gutter would be under 2 texels: such a
+    triangle could miss every texel centre. It ignores the triangles' shapes: a way to bake and test scenes without lightmap UVs, not a
+    chart packer."""
+    n, w, h, g = int(n_triangles), int(width), int(height), int(gutter)
+    if n < 0 or w < 1 or h < 1 or g < 0:
+        raise ValueError("n_triangles and gutter must not be negative, width and height at least 1")
+    if n == 0:
+        return np.zeros((0, 3, 2), f32)
+    s = min(w, h)
+    while s >= 1 and (w // s) * (h // s) < n:
+        s -= 1
+    if s - 2 * g < 2:
+        raise ValueError(f"{n} triangles in a {w} x {h} atlas get cells of {max(s, 0)} texels: under 2 inside a gutter of {g}")
+    cols = w // s
+    t = np.arange(n)
+    ox, oy = (t % cols) * s, (t // cols) * s
+    px = np.stack([ox + g, ox + s - g, ox + g], 1).astype(f32)
+    py = np.stack([oy + g, oy + g, oy + s - g], 1).astype(f32)
+    uv = np.stack([px / f32(w), py / f32(h)], 2)
+    assert uv.dtype == f32
+    return np.ascontiguousarray(uv)

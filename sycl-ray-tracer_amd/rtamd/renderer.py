@@ -594,6 +594,66 @@ class TileComm:
             pass
 
 
+class Lightmap:
+    """rt_lightmap: a width x height lightmap atlas over `scene` (include/rt_mi355x.h: rt_lightmap_bake). lm_uv: (T, 3, 2) or (T, 6)
+    float32, every triangle's three lightmap UVs in the scene's triangle order (rtamd.bake.triangle_grid_uvs makes a trivial unwrap).
+    max_repeats: the most entries per texel a bake may ask for. Close it before its scene."""
+
+    def __init__(self, scene: Scene, lm_uv: np.ndarray, width: int, height: int, max_repeats: int = 1):
+        lm_uv = np.asarray(lm_uv)
+        t = scene.desc.n_triangles
+        if lm_uv.shape not in ((t, 3, 2), (t, 6)):
+            raise ValueError(f"lm_uv must hold three (u, v) per triangle, shape ({t}, 3, 2) or ({t}, 6), got {lm_uv.shape}")
+        if lm_uv.dtype.kind != "f":
+            raise ValueError("lm_uv must be a floating-point array")
+        self._uv = np.ascontiguousarray(lm_uv, np.float32)
+        self._lib = scene._lib
+        self.scene = scene
+        self.width, self.height, self.max_repeats = int(width), int(height), int(max_repeats)
+        self.h = C.c_void_p()
+        abi.check(self._lib.rt_lightmap_create(scene.h, self.width, self.height, self.max_repeats, abi.fptr(self._uv), C.byref(self.h)), self._lib)
+
+    def texels(self) -> dict:
+        """rt_lightmap_texels: {"tri": (H, W) uint32, the owning triangle or 0xFFFFFFFF, "pos": (H, W, 3) float32, the texel centre's point on
+        it (NaN where empty), "normal": (H, W, 3) float32, its shading normal there (0 where empty)}."""
+        out = {"tri": np.zeros((self.height, self.width), np.uint32), "pos": np.zeros((self.height, self.width, 3), np.float32),
+               "normal": np.zeros((self.height, self.width, 3), np.float32)}
+        abi.check(self._lib.rt_lightmap_texels(self.h, abi.u32ptr(out["tri"]), abi.fptr(out["pos"]), abi.fptr(out["normal"])), self._lib)
+        return out
+
+    def texels_device(self, d_tri: int = 0, d_pos: int = 0, d_normal: int = 0, stream: int = 0) -> None:
+        """rt_lightmap_texels_device on DEVICE pointers (e.g. torch .data_ptr()), enqueued on `stream`; 0 = NULL (not written)."""
+        v = [C.c_void_p(x or None) for x in (d_tri, d_pos, d_normal, stream)]
+        abi.check(self._lib.rt_lightmap_texels_device(self.h, *v), self._lib)
+
+    def bake(self, samples: int, max_depth: int, seed: int, repeats: int = 1, rr_start: int = 0, dilate: int = 0) -> dict:
+        """rt_lightmap_bake: {"rgba": (H, W, 4) float32, the gathered radiance with alpha 1 where sampled, 0.5 where filled by dilation, 0
+        where empty, "stats": {"covered", "sampled", "filled", "rays"}}. samples x repeats paths per texel; `dilate` gutter passes."""
+        p = abi.rt_lightmap_params(int(samples), int(max_depth), int(rr_start), int(repeats), int(seed) & 0xFFFFFFFF, int(dilate))
+        rgba = np.zeros((self.height, self.width, 4), np.float32)
+        st = abi.rt_lightmap_stats()
+        abi.check(self._lib.rt_lightmap_bake(self.h, C.byref(p), abi.fptr(rgba), C.byref(st)), self._lib)
+        return {"rgba": rgba, "stats": {"covered": st.covered, "sampled": st.sampled, "filled": st.filled, "rays": st.rays}}
+
+    def bake_device(self, d_rgba: int, samples: int, max_depth: int, seed: int, repeats: int = 1, rr_start: int = 0, dilate: int = 0,
+                    d_stats: int = 0, stream: int = 0) -> None:
+        """rt_lightmap_bake_device on DEVICE pointers, enqueued on `stream`: d_rgba H*W*4 floats, d_stats 24 bytes (rt_lightmap_stats) or 0."""
+        p = abi.rt_lightmap_params(int(samples), int(max_depth), int(rr_start), int(repeats), int(seed) & 0xFFFFFFFF, int(dilate))
+        abi.check(self._lib.rt_lightmap_bake_device(self.h, C.byref(p), C.c_void_p(d_rgba or None), C.c_void_p(d_stats or None),
+                                                    C.c_void_p(stream or None)), self._lib)
+
+    def close(self):
+        if self.h:
+            self._lib.rt_lightmap_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 # The denoiser's defaults (DESIGN.md §13: chosen by scripts/denoise_probe.py's sweep on the atrium and the Cornell box). sigma_position is
 # DENOISE_POSITION_FRACTION of the scene's scale (Scene.scale()); host/main.cpp's --denoise uses the same values.
 DENOISE_ITERATIONS = 5

@@ -1,23 +1,12 @@
 // rt_denoiser.h — the denoiser's state and the small pieces its two units share: rt_denoise.hip (the a-trous filter with one global colour
-// sigma) and rt_variance.hip (the variance estimate and the variance-guided filter, for a denoiser created with RT_DENOISER_VARIANCE).
+// sigma) and rt_variance.hip (the variance estimate and the variance-guided filter, for a denoiser created with RT_DENOISER_VARIANCE). The
+// stream protocol, the staging and the launch shape are every image op's (rt_image_op.h); the a-trous pixel and its iterations are rt_atrous_pixel.h.
 #pragma once
-#include "rt_internal.h"
-#include "rt_device.h"
+#include "rt_image_op.h"
 #include "denoise_math.h"
 
-struct rt_denoiser {
-    int device = -1;
-    int32_t width = 0, height = 0;
-    uint32_t flags = 0;                        // RT_DENOISER_*
+struct rt_denoiser : ImageOp {
     float4* d_scratch[2] = {nullptr, nullptr}; // linear colour between iterations (rt_denoise_guided: .w = the colour's variance)
-    hipStream_t stream = nullptr;              // the host variants run here
-    hipEvent_t ev_last = nullptr;              // recorded behind every call: the next call's stream waits for it
-    bool recorded = false;
-    // the host variants' device copies of their arguments (four input planes, the fp32 and unorm8 outputs), allocated with the scratch at
-    // creation: no call allocates
-    float4* d_host_in = nullptr;
-    float4* d_host_f32 = nullptr;
-    uint8_t* d_host_u8 = nullptr;
     // RT_DENOISER_VARIANCE: the variance plane a host call reads, the one it writes, and rt_denoise_variance's moments and history lengths
     float* d_host_var_in = nullptr;
     float* d_host_var_out = nullptr;
@@ -29,7 +18,6 @@ struct rt_denoiser {
 namespace {
 
 constexpr uint32_t kMaxIterations = 10;
-constexpr float kMinSigma = 1e-6f;
 
 // the weights of the B3-spline kernel, per axis: 1/16, 1/4, 3/8, 1/4, 1/16 (all exact; their products too)
 __constant__ float kTapH[5] = {0.0625f, 0.25f, 0.375f, 0.25f, 0.0625f};
@@ -39,12 +27,5 @@ RT_DEV float dot_diff(float4 a, float4 b) { // R2's dot of a.xyz - b.xyz with it
     return (x * x + y * y) + z * z;
 }
 RT_DEV float4 squared(float4 f) { return make_float4(f.x * f.x, f.y * f.y, f.z * f.z, 1.0f); }
-
-// RN(1 / RN(sigma * sigma)); 0 for sigma = +inf (the guide ignored)
-inline float coefficient(float sigma) {
-    if (std::isinf(sigma)) return 0.0f;
-    const float s2 = sigma * sigma;
-    return 1.0f / s2;
-}
 
 } // namespace

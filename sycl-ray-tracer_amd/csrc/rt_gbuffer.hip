@@ -38,15 +38,29 @@ int gbuffer_enqueue(rt_scene* s, const rt_camera* cam, float4* alb, float4* nrm,
     HIPCHK(hipSetDevice(s->device));
     hipEvent_t ev = nullptr;
     if (const int rc = scene_stream_event(s, st, &ev)) return rc;
-    CameraDev c;
-    std::memcpy(c.center, cam->center, 12), std::memcpy(c.pixel00, cam->pixel00, 12);
-    std::memcpy(c.du, cam->delta_u, 12), std::memcpy(c.dv, cam->delta_v, 12);
-    c.width = cam->width, c.height = cam->height;
+    const CameraDev c = to_dev(*cam);
     const uint32_t n = (uint32_t)cam->width * (uint32_t)cam->height;
     if (prev) launch_gbuffer_motion(s->dev, c, n, alb, nrm, pos, s->upd->d_wv_prev, prev, st); // (rt_gbuffer_motion.hip)
     else hipLaunchKernelGGL(k_gbuffer, dim3((n + 255u) / 256u), dim3(256), 0, st, s->dev, c, alb, nrm, pos);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(ev, st));
+    return RT_OK;
+}
+
+// the host variants: the planes on the device, then copied out; `out` has three planes, or four with the motion guide (PRE: the checks passed)
+int gbuffer_to_host(rt_scene* s, const rt_camera* cam, std::initializer_list<float*> out) {
+    HIPCHK(hipSetDevice(s->device));
+    const size_t n = (size_t)cam->width * (size_t)cam->height;
+    DevBuf b;
+    HIPCHK(b.alloc(out.size() * n * 16u));
+    float4* d = b.as<float4>();
+    if (const int rc = gbuffer_enqueue(s, cam, d, d + n, d + 2 * n, out.size() == 4 ? d + 3 * n : nullptr, 0)) return rc;
+    HIPCHK(hipStreamSynchronize(0));
+    const float4* src = d;
+    for (float* plane : out) {
+        HIPCHK(hipMemcpy(plane, src, n * 16u, hipMemcpyDeviceToHost));
+        src += n;
+    }
     return RT_OK;
 }
 
@@ -57,18 +71,7 @@ extern "C" {
 int rt_scene_gbuffer(rt_scene* s, const rt_camera* cam, float* albedo, float* normal, float* position) {
     if (!albedo || !normal || !position) return fail(RT_ERR_INVALID, "null argument");
     if (const int rc = gbuffer_check(s, cam)) return rc;
-    HIPCHK(hipSetDevice(s->device));
-    const size_t bytes = (size_t)cam->width * (size_t)cam->height * 16u;
-    DevBuf b;
-    HIPCHK(b.alloc(3 * bytes));
-    float4* d = b.as<float4>();
-    const size_t n = bytes / 16u;
-    if (const int rc = gbuffer_enqueue(s, cam, d, d + n, d + 2 * n, nullptr, 0)) return rc;
-    HIPCHK(hipStreamSynchronize(0));
-    HIPCHK(hipMemcpy(albedo, d, bytes, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(normal, d + n, bytes, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(position, d + 2 * n, bytes, hipMemcpyDeviceToHost));
-    return RT_OK;
+    return gbuffer_to_host(s, cam, {albedo, normal, position});
 }
 
 int rt_scene_gbuffer_device(rt_scene* s, const rt_camera* cam, void* d_albedo, void* d_normal, void* d_position, void* stream) {
@@ -81,19 +84,7 @@ int rt_scene_gbuffer_motion(rt_scene* s, const rt_camera* cam, float* albedo, fl
     if (!albedo || !normal || !position || !prev_position) return fail(RT_ERR_INVALID, "null argument");
     if (const int rc = gbuffer_check(s, cam)) return rc;
     if (const int rc = motion_check(s)) return rc;
-    HIPCHK(hipSetDevice(s->device));
-    const size_t bytes = (size_t)cam->width * (size_t)cam->height * 16u;
-    DevBuf b;
-    HIPCHK(b.alloc(4 * bytes));
-    float4* d = b.as<float4>();
-    const size_t n = bytes / 16u;
-    if (const int rc = gbuffer_enqueue(s, cam, d, d + n, d + 2 * n, d + 3 * n, 0)) return rc;
-    HIPCHK(hipStreamSynchronize(0));
-    HIPCHK(hipMemcpy(albedo, d, bytes, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(normal, d + n, bytes, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(position, d + 2 * n, bytes, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(prev_position, d + 3 * n, bytes, hipMemcpyDeviceToHost));
-    return RT_OK;
+    return gbuffer_to_host(s, cam, {albedo, normal, position, prev_position});
 }
 
 int rt_scene_gbuffer_motion_device(rt_scene* s, const rt_camera* cam, void* d_albedo, void* d_normal, void* d_position, void* d_prev_position,

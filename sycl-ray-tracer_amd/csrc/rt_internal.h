@@ -8,8 +8,13 @@
 //   rt_gbuffer.hip the primary-hit G-buffer (rt_scene_gbuffer[_device], rt_scene_gbuffer_motion[_device]) and k_gbuffer
 //   rt_gbuffer_motion.hip k_gbuffer_motion: the same pixel (rt_gbuffer_pixel.h) plus the motion guide
 //   rt_denoise.hip the a-trous denoiser (rt_denoiser_*, rt_denoise[_device]) and its kernels
+//   rt_variance.hip the variance estimate and the variance-guided filter (rt_denoise_variance[_device], rt_denoise_guided[_device]) and their kernels
 //   rt_query.hip   ray queries with a per-ray tmax (rt_trace_rays[_device]) and their kernel
 //   rt_temporal.hip the temporal accumulator (rt_temporal_*) and its kernel
+//   rt_temporal_moments.hip k_temporal_moments: the same pixel (rt_temporal_pixel_body.h) plus the luminance moments (rt_temporal_accumulate_moments[_device])
+//   rt_image_op.h  what those four units share: the object's stream, event and staging planes, the bracket of a call, the 64 x 4 launch shape
+//   rt_atrous_pixel.h the a-trous pixel of rt_denoise.hip's and rt_variance.hip's kernels (atrous_pixel<GUIDED, SQUARE, LAST>) and the loop over its iterations
+//   rt_denoiser.h, rt_temporal_pixel.h the two objects' own state; the second also holds the one host path of a temporal call (temporal_call)
 //   rt_path_query.hip path queries, radiance along caller-supplied rays (rt_trace_paths[_device]) and their kernel
 //   rt_path_gather.hip gather queries, diffuse-lobe radiance at caller-supplied points (rt_gather_paths[_device]) and their kernel
 //   rt_query_launch.h what those three units share on the host: grid sizing, the launch on the shared cursors, the path / gather checks and staging
@@ -383,6 +388,7 @@ ContractRange contract_range(const HostScene& hs);
 bool origin_in_contract_range(const HostScene& hs, const float o[3]);
 uint32_t hw_queues_from_env();
 hipError_t lane_stream_of(int device, uint32_t k, hipStream_t* out, bool* owned);
+CameraDev to_dev(const rt_camera& c); // the camera as the kernels take it
 int alloc_tile_buffers(rt_renderer* r);
 int frame_begin(rt_renderer* r, const rt_camera* cam, float* d_f32, uint8_t* d_u8, hipStream_t st, const FrameRequest* req = nullptr);
 int frame_end(rt_renderer* r, rt_stats* stats);

@@ -6,7 +6,8 @@
 // and normal planes of the frame that history belongs to): a call reads the previous set through its four bilinear taps and writes the
 // current one, then the two change roles. A workgroup is 64 x 4 pixels, a wave one row of 64 consecutive pixels: every plane load and store
 // of a wave is one contiguous 1 KB row segment, and the taps of a wave land on neighbouring pixels of the previous set for any coherent
-// motion. No atomics, no grid synchronisation: the kernel boundary is the only hand-off.
+// motion. No atomics, no grid synchronisation: the kernel boundary is the only hand-off. The host path of a call is
+// rt_temporal_pixel.h: temporal_call, shared with rt_temporal_moments.hip; creation, the bracket and the host staging are rt_image_op.h's.
 #include "rt_temporal_pixel.h"
 
 namespace {
@@ -28,20 +29,12 @@ int enqueue(rt_temporal* t, const rt_temporal_params* p, const rt_camera* cam, c
             const float4* prv, float4* out_f32, uchar4* out_u8, float* hist_len, hipStream_t st) {
     // an accumulator that has moments keeps them up to date through plain calls too: the same colour, from the kernel that also blends the moments
     if (t->flags & RT_TEMPORAL_MOMENTS) return enqueue_temporal_moments(t, p, cam, frame, nrm, pos, prv, out_f32, out_u8, hist_len, nullptr, st);
-    HIPCHK(hipSetDevice(t->device));
-    if (t->recorded) HIPCHK(hipStreamWaitEvent(st, t->ev_last, 0)); // the previous call (any stream) is done with both sets
-    const TemporalArgs a = temporal_args(t, p);
-    float4* const* prev = t->d_hist[t->cur ^ 1];
-    float4* const* next = t->d_hist[t->cur];
-    // W * H < 2^31 and the grid's threads < 2^32 (rt_temporal_create): every index fits in 32 bits
-    const dim3 grid((((uint32_t)a.W + 63u) / 64u) * (((uint32_t)a.H + 3u) / 4u)), block(64, 4);
-    hipLaunchKernelGGL(k_temporal, grid, block, 0, st, a, frame, nrm, pos, prv, (const float4*)prev[0], (const float4*)prev[1], (const float4*)prev[2],
-                       next[0], next[1], next[2], out_f32, out_u8, hist_len);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(t->ev_last, st));
-    t->recorded = true;
-    t->cur ^= 1, t->has_prev = true, t->prev_cam = *cam;
-    return RT_OK;
+    return temporal_call(t, p, cam, st, [&](const TemporalArgs& a, int prev, int next) {
+        float4* const* h = t->d_hist[prev];
+        float4* const* o = t->d_hist[next];
+        hipLaunchKernelGGL(k_temporal, tile_grid(a.W, a.H), tile_block(), 0, st, a, frame, nrm, pos, prv, (const float4*)h[0], (const float4*)h[1],
+                           (const float4*)h[2], o[0], o[1], o[2], out_f32, out_u8, hist_len);
+    });
 }
 
 } // namespace
@@ -55,35 +48,23 @@ int rt_temporal_create(int device, int32_t width, int32_t height, rt_temporal** 
 int rt_temporal_create_ex(int device, int32_t width, int32_t height, uint32_t flags, rt_temporal** out) {
     if (!out) return fail(RT_ERR_INVALID, "null output pointer");
     *out = nullptr;
-    if (device < 0) return fail(RT_ERR_INVALID, "device index out of range");
-    if (flags & ~RT_TEMPORAL_MOMENTS) return fail(RT_ERR_INVALID, "unknown accumulator flag");
-    if (width <= 0 || height <= 0) return fail(RT_ERR_INVALID, "width and height must be positive");
-    if ((uint64_t)width * (uint64_t)height > 0x7fffffffull) return fail(RT_ERR_INVALID, "image too large (W x H must stay below 2^31)");
-    // k_temporal's 1-D grid of 64 x 4 tiles: its threads, padding included, must stay below 2^32 (only very narrow images reach that)
-    if (((uint64_t)width + 63u) / 64u * (((uint64_t)height + 3u) / 4u) * 256u > 0xffffffffull)
-        return fail(RT_ERR_INVALID, "image shape too narrow and tall for the kernel's launch grid");
-    const int rc = device_ok(device);
-    if (rc != RT_OK) return rc;
+    if (const int rc = image_op_check(device, width, height, flags, RT_TEMPORAL_MOMENTS, "unknown accumulator flag", "kernel")) return rc;
     return no_throw([&]() -> int {
         rt_temporal* t = new rt_temporal;
-        t->device = device, t->width = width, t->height = height, t->flags = flags;
-        const size_t n = (size_t)width * (size_t)height, bytes = n * 16u;
-        bool ok = true;
+        const char* oom = "hipMalloc of the accumulator's history and staging failed";
+        int rc = image_op_open(t, device, width, height, flags, oom);
+        const size_t n = t->pixels();
+        bool ok = rc == RT_OK;
         for (int s = 0; s < 2; ++s)
-            for (int k = 0; k < 3; ++k) ok = ok && hipMalloc((void**)&t->d_hist[s][k], bytes) == hipSuccess;
-        ok = ok && hipMalloc((void**)&t->d_host_in, 4 * bytes) == hipSuccess && hipMalloc((void**)&t->d_host_f32, bytes) == hipSuccess &&
-             hipMalloc((void**)&t->d_host_u8, n * 4u) == hipSuccess && hipMalloc((void**)&t->d_host_len, n * 4u) == hipSuccess;
+            for (int k = 0; k < 3; ++k) ok = ok && hipMalloc((void**)&t->d_hist[s][k], n * 16u) == hipSuccess;
+        ok = ok && hipMalloc((void**)&t->d_host_len, n * 4u) == hipSuccess;
         if (flags & RT_TEMPORAL_MOMENTS)
             ok = ok && hipMalloc((void**)&t->d_mom[0], n * 8u) == hipSuccess && hipMalloc((void**)&t->d_mom[1], n * 8u) == hipSuccess &&
                  hipMalloc((void**)&t->d_host_mom, n * 8u) == hipSuccess;
-        if (!ok) {
+        if (rc == RT_OK && !ok) rc = fail(RT_ERR_OOM, oom);
+        if (rc != RT_OK) {
             rt_temporal_destroy(t);
-            return fail(RT_ERR_OOM, "hipMalloc of the accumulator's history and staging failed");
-        }
-        if (hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking) != hipSuccess ||
-            hipEventCreateWithFlags(&t->ev_last, hipEventDisableTiming) != hipSuccess) {
-            rt_temporal_destroy(t);
-            return fail(RT_ERR_HIP, "hipStreamCreate / hipEventCreate failed");
+            return rc;
         }
         *out = t;
         return (int)RT_OK;
@@ -92,14 +73,10 @@ int rt_temporal_create_ex(int device, int32_t width, int32_t height, uint32_t fl
 
 void rt_temporal_destroy(rt_temporal* t) {
     if (!t) return;
-    if (t->device >= 0 && hipSetDevice(t->device) == hipSuccess) {
-        if (t->recorded) (void)hipEventSynchronize(t->ev_last);
+    if (image_op_close(t)) {
         for (int s = 0; s < 2; ++s)
             for (int k = 0; k < 3; ++k) (void)hipFree(t->d_hist[s][k]);
-        (void)hipFree(t->d_host_in), (void)hipFree(t->d_host_f32), (void)hipFree(t->d_host_u8), (void)hipFree(t->d_host_len);
-        (void)hipFree(t->d_mom[0]), (void)hipFree(t->d_mom[1]), (void)hipFree(t->d_host_mom);
-        if (t->ev_last) (void)hipEventDestroy(t->ev_last);
-        if (t->stream) (void)hipStreamDestroy(t->stream);
+        (void)hipFree(t->d_host_len), (void)hipFree(t->d_mom[0]), (void)hipFree(t->d_mom[1]), (void)hipFree(t->d_host_mom);
     }
     delete t;
 }
@@ -113,23 +90,15 @@ int rt_temporal_reset(rt_temporal* t) {
 int rt_temporal_accumulate(rt_temporal* t, const rt_temporal_params* p, const rt_camera* cam, const float* rgba_f32, const float* normal,
                            const float* position, const float* prev_position, float* out_f32, uint8_t* out_u8, float* history_len) {
     if (const int rc = check_call(t, p, cam, rgba_f32, normal, position, prev_position, out_f32, out_u8)) return rc;
-    HIPCHK(hipSetDevice(t->device));
-    const size_t n = (size_t)t->width * (size_t)t->height, bytes = n * 16u;
-    float4* in = t->d_host_in;
     hipStream_t st = t->stream;
-    if (t->recorded) HIPCHK(hipStreamWaitEvent(st, t->ev_last, 0)); // a _device call on another stream may still run
-    HIPCHK(hipMemcpyAsync(in, rgba_f32, bytes, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(in + n, normal, bytes, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(in + 2 * n, position, bytes, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(in + 3 * n, prev_position, bytes, hipMemcpyHostToDevice, st));
+    if (const int rc = stage_in(t, st, {rgba_f32, normal, position, prev_position})) return rc;
+    const size_t n = t->pixels();
+    const float4* in = t->d_host_in;
     if (const int rc = enqueue(t, p, cam, in, in + n, in + 2 * n, in + 3 * n, out_f32 ? t->d_host_f32 : nullptr,
                                out_u8 ? (uchar4*)t->d_host_u8 : nullptr, history_len ? t->d_host_len : nullptr, st))
         return rc;
-    if (out_f32) HIPCHK(hipMemcpyAsync(out_f32, t->d_host_f32, bytes, hipMemcpyDeviceToHost, st));
-    if (out_u8) HIPCHK(hipMemcpyAsync(out_u8, t->d_host_u8, n * 4u, hipMemcpyDeviceToHost, st));
     if (history_len) HIPCHK(hipMemcpyAsync(history_len, t->d_host_len, n * 4u, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    return RT_OK;
+    return stage_out(t, st, out_f32, out_u8);
 }
 
 int rt_temporal_accumulate_device(rt_temporal* t, const rt_temporal_params* p, const rt_camera* cam, const void* d_rgba_f32, const void* d_normal,

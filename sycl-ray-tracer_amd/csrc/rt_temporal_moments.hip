@@ -1,4 +1,4 @@
-// rt_temporal_moments.hip — k_temporal_moments, the temporal kernel that also blends the luminance moments (RT_TEMPORAL_MOMENTS), its launch and
+// rt_temporal_moments.hip — k_temporal_moments, the temporal kernel that also blends the luminance moments (RT_TEMPORAL_MOMENTS), its launch (through temporal_call, as k_temporal's) and
 // rt_temporal_accumulate_moments[_device]. A unit of its own for the reason rt_temporal_pixel.h gives. The contract is stated at
 // rt_temporal_accumulate_moments in include/rt_mi355x.h; the numpy model that pins it bit for bit is tests/test_svgf.py: moments_model.
 #include "rt_temporal_pixel.h"
@@ -29,20 +29,12 @@ namespace rtlib {
 int enqueue_temporal_moments(rt_temporal* t, const rt_temporal_params* p, const rt_camera* cam, const float4* frame, const float4* nrm,
                              const float4* pos, const float4* prv, float4* out_f32, uchar4* out_u8, float* hist_len, float2* moments,
                              hipStream_t st) {
-    HIPCHK(hipSetDevice(t->device));
-    if (t->recorded) HIPCHK(hipStreamWaitEvent(st, t->ev_last, 0)); // the previous call (any stream) is done with both sets
-    const TemporalArgs a = temporal_args(t, p);
-    float4* const* prev = t->d_hist[t->cur ^ 1];
-    float4* const* next = t->d_hist[t->cur];
-    const dim3 grid((((uint32_t)a.W + 63u) / 64u) * (((uint32_t)a.H + 3u) / 4u)), block(64, 4);
-    hipLaunchKernelGGL(k_temporal_moments, grid, block, 0, st, a, frame, nrm, pos, prv, (const float4*)prev[0], (const float4*)prev[1],
-                       (const float4*)prev[2], next[0], next[1], next[2], out_f32, out_u8, hist_len, (const float2*)t->d_mom[t->cur ^ 1],
-                       t->d_mom[t->cur], moments);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(t->ev_last, st));
-    t->recorded = true;
-    t->cur ^= 1, t->has_prev = true, t->prev_cam = *cam;
-    return RT_OK;
+    return temporal_call(t, p, cam, st, [&](const TemporalArgs& a, int prev, int next) {
+        float4* const* h = t->d_hist[prev];
+        float4* const* o = t->d_hist[next];
+        hipLaunchKernelGGL(k_temporal_moments, tile_grid(a.W, a.H), tile_block(), 0, st, a, frame, nrm, pos, prv, (const float4*)h[0], (const float4*)h[1],
+                           (const float4*)h[2], o[0], o[1], o[2], out_f32, out_u8, hist_len, (const float2*)t->d_mom[prev], t->d_mom[next], moments);
+    });
 }
 
 } // namespace rtlib
@@ -54,24 +46,16 @@ int rt_temporal_accumulate_moments(rt_temporal* t, const rt_temporal_params* p, 
                                    float* moments) {
     if (const int rc = check_call(t, p, cam, rgba_f32, normal, position, prev_position, out_f32, out_u8)) return rc;
     if (const int rc = check_moments_call(t, moments)) return rc;
-    HIPCHK(hipSetDevice(t->device));
-    const size_t n = (size_t)t->width * (size_t)t->height, bytes = n * 16u;
-    float4* in = t->d_host_in;
     hipStream_t st = t->stream;
-    if (t->recorded) HIPCHK(hipStreamWaitEvent(st, t->ev_last, 0)); // a _device call on another stream may still run
-    HIPCHK(hipMemcpyAsync(in, rgba_f32, bytes, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(in + n, normal, bytes, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(in + 2 * n, position, bytes, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(in + 3 * n, prev_position, bytes, hipMemcpyHostToDevice, st));
+    if (const int rc = stage_in(t, st, {rgba_f32, normal, position, prev_position})) return rc;
+    const size_t n = t->pixels();
+    const float4* in = t->d_host_in;
     if (const int rc = enqueue_temporal_moments(t, p, cam, in, in + n, in + 2 * n, in + 3 * n, out_f32 ? t->d_host_f32 : nullptr,
                                                 out_u8 ? (uchar4*)t->d_host_u8 : nullptr, history_len ? t->d_host_len : nullptr, t->d_host_mom, st))
         return rc;
-    if (out_f32) HIPCHK(hipMemcpyAsync(out_f32, t->d_host_f32, bytes, hipMemcpyDeviceToHost, st));
-    if (out_u8) HIPCHK(hipMemcpyAsync(out_u8, t->d_host_u8, n * 4u, hipMemcpyDeviceToHost, st));
     if (history_len) HIPCHK(hipMemcpyAsync(history_len, t->d_host_len, n * 4u, hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(moments, t->d_host_mom, n * 8u, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    return RT_OK;
+    return stage_out(t, st, out_f32, out_u8);
 }
 
 int rt_temporal_accumulate_moments_device(rt_temporal* t, const rt_temporal_params* p, const rt_camera* cam, const void* d_rgba_f32,

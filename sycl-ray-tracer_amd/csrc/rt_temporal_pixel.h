@@ -1,28 +1,18 @@
 // rt_temporal_pixel.h — the accumulator's state, the kernels' arguments and the checks of a call: shared by k_temporal's unit (rt_temporal.hip)
 // and k_temporal_moments' (rt_temporal_moments.hip). What a thread of either does is rt_temporal_pixel_body.h. The two kernels live in units of
 // their own, as the G-buffer's two do (rt_gbuffer_pixel.h): k_temporal keeps its instructions, and an accumulator created without
-// RT_TEMPORAL_MOMENTS never runs the other.
+// RT_TEMPORAL_MOMENTS never runs the other. The stream protocol, the staging and the launch shape are every image op's (rt_image_op.h); the one
+// host path of a call, whichever kernel it launches, is temporal_call below.
 #pragma once
-#include "rt_internal.h"
-#include "rt_device.h"
+#include "rt_image_op.h"
 
-struct rt_temporal {
-    int device = -1;
-    int32_t width = 0, height = 0;
-    uint32_t flags = 0;    // RT_TEMPORAL_*
+struct rt_temporal : ImageOp {
     float4* d_hist[2][3] = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}}; // per set: colour (.w = history length), position, normal
     float2* d_mom[2] = {nullptr, nullptr}; // RT_TEMPORAL_MOMENTS, per set: the luminance moments (mean of l, mean of l*l)
     int cur = 0;           // the set the NEXT call writes
     bool has_prev = false; // the other set holds a frame's history (false after create / reset)
     rt_camera prev_cam{};  // ... and this was that frame's camera
-    hipStream_t stream = nullptr; // rt_temporal_accumulate (the host variant) runs here
-    hipEvent_t ev_last = nullptr; // recorded behind every call: the next call's stream waits for it
-    bool recorded = false;
-    // rt_temporal_accumulate's device copies of its host arguments (four input planes, the fp32 and unorm8 outputs, the history lengths, the
-    // moments where the accumulator has them), allocated with the sets at creation: no call allocates
-    float4* d_host_in = nullptr;
-    float4* d_host_f32 = nullptr;
-    uint8_t* d_host_u8 = nullptr;
+    // the host variants' device copies of the history lengths and, where the accumulator has them, the moments (beside ImageOp's)
     float* d_host_len = nullptr;
     float2* d_host_mom = nullptr;
 };
@@ -52,14 +42,6 @@ struct TemporalArgs {
 RT_DEV float dot3f(float ax, float ay, float az, float bx, float by, float bz) { return (ax * bx + ay * by) + az * bz; }
 
 constexpr uint32_t kMaxHistoryLimit = 4096;
-constexpr float kMinSigma = 1e-6f;
-
-// RN(1 / RN(sigma * sigma)); 0 for sigma = +inf (the test left out): the denoiser's coefficient()
-inline float coefficient(float sigma) {
-    if (std::isinf(sigma)) return 0.0f;
-    const float s2 = sigma * sigma;
-    return 1.0f / s2;
-}
 
 inline int check_params(const rt_temporal_params* p) {
     if (!p) return fail(RT_ERR_INVALID, "null parameters");
@@ -92,6 +74,18 @@ inline TemporalArgs temporal_args(const rt_temporal* t, const rt_temporal_params
     a.kx = coefficient(p->sigma_position), a.cos_normal = p->cos_normal, a.max_history = (float)p->max_history;
     a.W = t->width, a.H = t->height, a.has_prev = t->has_prev ? 1u : 0u;
     return a;
+}
+
+// One call on `t`, enqueued on st: the bracket, the kernel's arguments, the two sets' roles and their change. launch(a, prev, next) enqueues the
+// unit's kernel under tile_grid / tile_block: it reads set prev (t->d_hist[prev], t->d_mom[prev]) and writes set next.
+// PRE: the arguments were checked; all pointers are device pointers on t->device
+template <typename Launch>
+int temporal_call(rt_temporal* t, const rt_temporal_params* p, const rt_camera* cam, hipStream_t st, Launch launch) {
+    if (const int rc = begin_call(t, st)) return rc; // the previous call (any stream) is done with both sets
+    launch(temporal_args(t, p), t->cur ^ 1, t->cur);
+    if (const int rc = end_call(t, st)) return rc;
+    t->cur ^= 1, t->has_prev = true, t->prev_cam = *cam;
+    return RT_OK;
 }
 
 } // namespace

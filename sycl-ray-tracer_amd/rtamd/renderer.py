@@ -667,26 +667,44 @@ DENOISE_SIGMA_LUMINANCE = 4.0
 DENOISE_MIN_HISTORY = 4
 
 
+def _float_planes(shape, *arrays):
+    """The arrays as contiguous float32, each of `shape`."""
+    out = [np.ascontiguousarray(a, np.float32) for a in arrays]
+    for a in out:
+        if a.shape != shape:
+            raise ValueError(f"expected {shape}, got {a.shape}")
+    return out
+
+
+def _outputs(shape, want_f32, want_u8, out_f32):
+    """(f32, u8) a host call writes: fresh (or out_f32) where asked for, else None; and their pointers (None: not asked for)."""
+    f = (out_f32 if out_f32 is not None else np.zeros(shape, np.float32)) if want_f32 else None
+    b = np.zeros(shape, np.uint8) if want_u8 else None
+    return f, b, (abi.fptr(f) if f is not None else None, abi.u8ptr(b) if b is not None else None)
+
+
+def _sigma_position(sigma_position, fraction, scene_scale, missing):
+    """sigma_position, or `fraction` of the scene's scale in fp32 where it is None (`missing`: the caller's words where both are)."""
+    if sigma_position is not None:
+        return float(sigma_position)
+    if scene_scale is None:
+        raise ValueError(missing)
+    return float(np.float32(fraction) * np.float32(scene_scale))
+
+
 def denoise_params(iterations: int = DENOISE_ITERATIONS, sigma_color: float = DENOISE_SIGMA_COLOR, sigma_normal: float = DENOISE_SIGMA_NORMAL,
                    sigma_position: float | None = None, sigma_albedo: float = DENOISE_SIGMA_ALBEDO, scene_scale: float | None = None):
     """rt_denoise_params; sigma_position None: DENOISE_POSITION_FRACTION * scene_scale, in fp32 (scene_scale is then required)."""
-    if sigma_position is None:
-        if scene_scale is None:
-            raise ValueError("give sigma_position or scene_scale (Scene.scale())")
-        sigma_position = np.float32(DENOISE_POSITION_FRACTION) * np.float32(scene_scale)
-    return abi.rt_denoise_params(int(iterations), float(sigma_color), float(sigma_normal), float(sigma_position), float(sigma_albedo))
+    sp = _sigma_position(sigma_position, DENOISE_POSITION_FRACTION, scene_scale, "give sigma_position or scene_scale (Scene.scale())")
+    return abi.rt_denoise_params(int(iterations), float(sigma_color), float(sigma_normal), sp, float(sigma_albedo))
 
 
 def denoise_var_params(iterations: int = DENOISE_ITERATIONS, sigma_luminance: float = DENOISE_SIGMA_LUMINANCE,
                        sigma_normal: float = DENOISE_SIGMA_NORMAL, sigma_position: float | None = None, sigma_albedo: float = DENOISE_SIGMA_ALBEDO,
                        min_history: int = DENOISE_MIN_HISTORY, scene_scale: float | None = None):
     """rt_denoise_var_params; sigma_position None: DENOISE_POSITION_FRACTION * scene_scale, in fp32 (scene_scale is then required)."""
-    if sigma_position is None:
-        if scene_scale is None:
-            raise ValueError("give sigma_position or scene_scale (Scene.scale())")
-        sigma_position = np.float32(DENOISE_POSITION_FRACTION) * np.float32(scene_scale)
-    return abi.rt_denoise_var_params(int(iterations), float(sigma_luminance), float(sigma_normal), float(sigma_position), float(sigma_albedo),
-                                     int(min_history))
+    sp = _sigma_position(sigma_position, DENOISE_POSITION_FRACTION, scene_scale, "give sigma_position or scene_scale (Scene.scale())")
+    return abi.rt_denoise_var_params(int(iterations), float(sigma_luminance), float(sigma_normal), sp, float(sigma_albedo), int(min_history))
 
 
 class Denoiser:
@@ -707,16 +725,9 @@ class Denoiser:
         """rt_denoise of a (H, W, 4) float32 frame; returns (f32, u8), None for a plane not asked for. `sigmas`: sigma_color,
         sigma_normal, sigma_position, sigma_albedo, scene_scale (denoise_params). out_f32: where the fp32 result goes (may be frame_f32)."""
         p = denoise_params(iterations, **sigmas)
-        shape = (self.height, self.width, 4)
-        frame_f32 = np.ascontiguousarray(frame_f32, np.float32)
-        planes = [np.ascontiguousarray(gbuf[k], np.float32) for k in ("albedo", "normal", "position")]
-        for a in [frame_f32] + planes:
-            if a.shape != shape:
-                raise ValueError(f"expected {shape}, got {a.shape}")
-        f = (out_f32 if out_f32 is not None else np.zeros(shape, np.float32)) if want_f32 else None
-        b = np.zeros(shape, np.uint8) if want_u8 else None
-        abi.check(self._lib.rt_denoise(self.h, C.byref(p), abi.fptr(frame_f32), *(abi.fptr(a) for a in planes),
-                                       abi.fptr(f) if f is not None else None, abi.u8ptr(b) if b is not None else None), self._lib)
+        planes = self._planes(frame_f32, gbuf)
+        f, b, out = _outputs(planes[0].shape, want_f32, want_u8, out_f32)
+        abi.check(self._lib.rt_denoise(self.h, C.byref(p), *(abi.fptr(a) for a in planes), *out), self._lib)
         return f, b
 
     def denoise_device(self, d_frame: int, d_albedo: int, d_normal: int, d_position: int, d_out_f32: int = 0, d_out_u8: int = 0,
@@ -727,20 +738,15 @@ class Denoiser:
         abi.check(self._lib.rt_denoise_device(self.h, C.byref(p), *v), self._lib)
 
     def _planes(self, frame_f32, gbuf):
-        shape = (self.height, self.width, 4)
-        frame_f32 = np.ascontiguousarray(frame_f32, np.float32)
-        planes = [np.ascontiguousarray(gbuf[k], np.float32) for k in ("albedo", "normal", "position")]
-        for a in [frame_f32] + planes:
-            if a.shape != shape:
-                raise ValueError(f"expected {shape}, got {a.shape}")
-        return frame_f32, planes
+        """the four input planes of a host call, checked: the frame, albedo, normal, position"""
+        return _float_planes((self.height, self.width, 4), frame_f32, gbuf["albedo"], gbuf["normal"], gbuf["position"])
 
     def estimate_variance(self, frame_f32: np.ndarray, gbuf: dict, moments: np.ndarray | None = None, history_len: np.ndarray | None = None,
                           **params) -> np.ndarray:
         """rt_denoise_variance: the (H, W) float32 variance of the frame's luminance; moments (H, W, 2) and history_len (H, W) as
         TemporalAccumulator.accumulate(moments=True) returns them, or neither (a still image). `params`: denoise_var_params'."""
         p = denoise_var_params(**params)
-        frame_f32, planes = self._planes(frame_f32, gbuf)
+        planes = self._planes(frame_f32, gbuf)
         m = n = None
         if moments is not None:
             m = np.ascontiguousarray(moments, np.float32)
@@ -751,7 +757,7 @@ class Denoiser:
             if n.shape != (self.height, self.width):
                 raise ValueError(f"expected history_len of shape {(self.height, self.width)}, got {n.shape}")
         var = np.zeros((self.height, self.width), np.float32)
-        abi.check(self._lib.rt_denoise_variance(self.h, C.byref(p), abi.fptr(frame_f32), *(abi.fptr(a) for a in planes),
+        abi.check(self._lib.rt_denoise_variance(self.h, C.byref(p), *(abi.fptr(a) for a in planes),
                                                 abi.fptr(m) if m is not None else None, abi.fptr(n) if n is not None else None,
                                                 abi.fptr(var)), self._lib)
         return var
@@ -768,16 +774,13 @@ class Denoiser:
         """rt_denoise_guided of a (H, W, 4) float32 frame with its (H, W) variance; returns (f32, u8, variance of the result), None for what
         was not asked for. `params`: denoise_var_params'. out_f32: where the fp32 result goes (may be frame_f32)."""
         p = denoise_var_params(iterations, **params)
-        frame_f32, planes = self._planes(frame_f32, gbuf)
+        planes = self._planes(frame_f32, gbuf)
         variance = np.ascontiguousarray(variance, np.float32)
         if variance.shape != (self.height, self.width):
             raise ValueError(f"expected variance of shape {(self.height, self.width)}, got {variance.shape}")
-        shape = (self.height, self.width, 4)
-        f = (out_f32 if out_f32 is not None else np.zeros(shape, np.float32)) if want_f32 else None
-        b = np.zeros(shape, np.uint8) if want_u8 else None
-        ov = np.zeros(shape[:2], np.float32) if want_variance else None
-        abi.check(self._lib.rt_denoise_guided(self.h, C.byref(p), abi.fptr(frame_f32), *(abi.fptr(a) for a in planes), abi.fptr(variance),
-                                              abi.fptr(f) if f is not None else None, abi.u8ptr(b) if b is not None else None,
+        f, b, out = _outputs(planes[0].shape, want_f32, want_u8, out_f32)
+        ov = np.zeros(variance.shape, np.float32) if want_variance else None
+        abi.check(self._lib.rt_denoise_guided(self.h, C.byref(p), *(abi.fptr(a) for a in planes), abi.fptr(variance), *out,
                                               abi.fptr(ov) if ov is not None else None), self._lib)
         return f, b, ov
 
@@ -810,11 +813,8 @@ TEMPORAL_COS_NORMAL = 0.9
 def temporal_params(max_history: int = TEMPORAL_MAX_HISTORY, sigma_position: float | None = None, cos_normal: float = TEMPORAL_COS_NORMAL,
                     scene_scale: float | None = None):
     """rt_temporal_params; sigma_position None: TEMPORAL_POSITION_FRACTION * scene_scale, in fp32 (scene_scale is then required)."""
-    if sigma_position is None:
-        if scene_scale is None:
-            raise ValueError("sigma_position or scene_scale is required")
-        sigma_position = np.float32(TEMPORAL_POSITION_FRACTION) * np.float32(scene_scale)
-    return abi.rt_temporal_params(int(max_history), float(sigma_position), float(cos_normal))
+    sp = _sigma_position(sigma_position, TEMPORAL_POSITION_FRACTION, scene_scale, "sigma_position or scene_scale is required")
+    return abi.rt_temporal_params(int(max_history), sp, float(cos_normal))
 
 
 class TemporalAccumulator:
@@ -840,23 +840,15 @@ class TemporalAccumulator:
         moments=False there makes the plain call (the accumulator keeps its moments up to date all the same)."""
         p = temporal_params(**params)
         shape = (self.height, self.width, 4)
-        frame_f32 = np.ascontiguousarray(frame_f32, np.float32)
-        planes = [np.ascontiguousarray(gbuf[k], np.float32) for k in ("normal", "position", "prev_position")]
-        for a in [frame_f32] + planes:
-            if a.shape != shape:
-                raise ValueError(f"expected {shape}, got {a.shape}")
-        f = (out_f32 if out_f32 is not None else np.zeros(shape, np.float32)) if want_f32 else None
-        b = np.zeros(shape, np.uint8) if want_u8 else None
+        planes = _float_planes(shape, frame_f32, gbuf["normal"], gbuf["position"], gbuf["prev_position"])
+        f, b, out = _outputs(shape, want_f32, want_u8, out_f32)
         n = np.zeros(shape[:2], np.float32)
+        args = (self.h, C.byref(p), C.byref(camera.c), *(abi.fptr(a) for a in planes), *out, abi.fptr(n))
         if self.moments if moments is None else moments:
             m = np.zeros(shape[:2] + (2,), np.float32)
-            abi.check(self._lib.rt_temporal_accumulate_moments(self.h, C.byref(p), C.byref(camera.c), abi.fptr(frame_f32),
-                                                               *(abi.fptr(a) for a in planes), abi.fptr(f) if f is not None else None,
-                                                               abi.u8ptr(b) if b is not None else None, abi.fptr(n), abi.fptr(m)), self._lib)
+            abi.check(self._lib.rt_temporal_accumulate_moments(*args, abi.fptr(m)), self._lib)
             return {"f32": f, "u8": b, "history_len": n, "moments": m}
-        abi.check(self._lib.rt_temporal_accumulate(self.h, C.byref(p), C.byref(camera.c), abi.fptr(frame_f32), *(abi.fptr(a) for a in planes),
-                                                   abi.fptr(f) if f is not None else None, abi.u8ptr(b) if b is not None else None,
-                                                   abi.fptr(n)), self._lib)
+        abi.check(self._lib.rt_temporal_accumulate(*args), self._lib)
         return f, b, n
 
     def accumulate_device(self, camera: Camera, d_frame: int, d_normal: int, d_position: int, d_prev_position: int, d_out_f32: int = 0,

@@ -263,6 +263,37 @@ def test_guided_in_place_single_outputs_and_device_streams(rtlib):
     den.close()
 
 
+def test_three_entry_points_on_two_streams_and_the_host_share_one_bracket(rtlib):
+    """One denoiser, no host synchronisation between the calls: the estimate on stream A, the guided filter at 2 iterations on stream B reading
+    that variance, then the host rt_denoise at 1 iteration. Each call's stream waits for the event behind the call before it (the estimate's
+    output before the filter reads it, the scratch and staging planes before the next call writes them). 65 x 5: a full tile column and a
+    one-pixel one, a full tile row and a one-row one."""
+    import torch
+    h, w = 5, 65
+    frame, g, _ = _synthetic(h, w, 41)
+    sig = dict(zip(GNAMES, GSIG[0]))
+    den = Denoiser(0, w, h, variance=True)
+    df, da, dn, dp = (torch.from_numpy(np.ascontiguousarray(x)).to("cuda:0") for x in (frame, g["albedo"], g["normal"], g["position"]))
+    dvar = torch.zeros((h, w), dtype=torch.float32, device="cuda:0")
+    dof = torch.zeros((h, w, 4), dtype=torch.float32, device="cuda:0")
+    du8 = torch.zeros((h, w, 4), dtype=torch.uint8, device="cuda:0")
+    dov = torch.zeros((h, w), dtype=torch.float32, device="cuda:0")
+    sa, sb = torch.cuda.Stream(device=0), torch.cuda.Stream(device=0)
+    torch.cuda.synchronize()
+    den.estimate_variance_device(df.data_ptr(), da.data_ptr(), dn.data_ptr(), dp.data_ptr(), 0, 0, dvar.data_ptr(), stream=sa.cuda_stream, **SIG)
+    den.denoise_guided_device(df.data_ptr(), da.data_ptr(), dn.data_ptr(), dp.data_ptr(), dvar.data_ptr(), dof.data_ptr(), du8.data_ptr(),
+                              dov.data_ptr(), stream=sb.cuda_stream, iterations=2, **sig)
+    hf, hb = den.denoise(frame, g, iterations=1, sigma_color=0.7, sigma_normal=0.3, sigma_position=0.4, sigma_albedo=0.2)
+    torch.cuda.synchronize()
+    mv = variance_model(frame, g, SIG["sigma_normal"], SIG["sigma_position"], SIG["sigma_albedo"])
+    assert same_bits(dvar.cpu().numpy(), mv)
+    mf, mb, mov = guided_model(frame, g, mv, 2, *GSIG[0])
+    assert same_bits(dof.cpu().numpy(), mf) and same_bits(du8.cpu().numpy(), mb) and same_bits(dov.cpu().numpy(), mov)
+    df1, db1 = _m._dn.denoise_model(frame, g, 1, 0.7, 0.3, 0.4, 0.2)
+    assert same_bits(hf, df1) and same_bits(hb, db1)
+    den.close()
+
+
 def test_guided_at_the_contracts_edges(rtlib):
     """Zero variance everywhere; one 1e20 firefly (include/rt_mi355x.h, "Non-finite radiance"); a hit / miss checkerboard."""
     h, w = 40, 70

@@ -13,6 +13,7 @@ from rtamd.renderer import TemporalAccumulator, temporal_params
 from test_gpu_temporal import same_bits
 from test_temporal import (PLANE_SIZES, PLANE_STEPS, ROOM_PARAMS, _edge, frame_of, plane_camera, plane_gbuffer, plane_step_by_hand,
                            plane_step_inputs, room_sequence, temporal_model)
+from test_svgf import moments_model
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
@@ -168,6 +169,42 @@ def test_calls_on_two_streams_and_the_host_are_serialised(rtlib):
         mo, mb, mn, state = temporal_model(state, frame, g, cam, **p)
         assert same_bits(n, mn) and same_bits(o, mo) and same_bits(b, mb), (i + 2, "host call")
         assert (mn >= 2).mean() > 0.5  # (the three calls did depend on each other)
+    acc.close()
+
+
+def test_plain_moments_and_host_calls_on_one_accumulator_share_one_bracket(rtlib):
+    """One accumulator with moments, three room frames, no host synchronisation between the calls: rt_temporal_accumulate_device on stream A,
+    rt_temporal_accumulate_moments_device on stream B, then the host rt_temporal_accumulate_moments. Each call's stream waits for the event
+    behind the call before it, so the three equal the models' sequential answers. 65 x 5: one tile and one pixel more in x and in y."""
+    import torch
+    W, H = 65, 5
+    p = ROOM_PARAMS
+    seq = list(room_sequence(W, H))[:3]
+    keys = ("normal", "position", "prev_position")
+    t_in = [[torch.from_numpy(np.ascontiguousarray(a)).to("cuda:0") for a in (frame, *(g[k] for k in keys))] for _, _, _, frame, g, _ in seq[:2]]
+    t_out = [[torch.zeros((H, W, 4), dtype=torch.float32, device="cuda:0"), torch.zeros((H, W, 4), dtype=torch.uint8, device="cuda:0"),
+              torch.zeros((H, W), dtype=torch.float32, device="cuda:0")] for _ in range(2)]
+    d_mom = torch.zeros((H, W, 2), dtype=torch.float32, device="cuda:0")
+    sa, sb = torch.cuda.Stream(device=0), torch.cuda.Stream(device=0)
+    acc = TemporalAccumulator(0, W, H, moments=True)
+    torch.cuda.synchronize()
+    acc.accumulate_device(cam_of(seq[0][2]), *(t.data_ptr() for t in t_in[0]), *(t.data_ptr() for t in t_out[0]), stream=sa.cuda_stream, **p)
+    acc.accumulate_moments_device(cam_of(seq[1][2]), *(t.data_ptr() for t in t_in[1]), d_mom.data_ptr(), *(t.data_ptr() for t in t_out[1]),
+                                  stream=sb.cuda_stream, **p)
+    r = acc.accumulate(seq[2][3], seq[2][4], cam_of(seq[2][2]), moments=True, **p)
+    torch.cuda.synchronize()
+    state = plain = None
+    for k, (_, _, cam, frame, g, _) in enumerate(seq):
+        mo, mb, mn, mm, state = moments_model(state, frame, g, cam, **p)
+        po, pb, pn, plain = temporal_model(plain, frame, g, cam, **p)
+        assert same_bits(mo, po) and same_bits(mb, pb) and same_bits(mn, pn), k  # (the moments ride along: the colour is temporal_model's)
+        if k < 2:
+            do, db, dn = (t.cpu().numpy() for t in t_out[k])
+            assert same_bits(dn, mn) and same_bits(do, mo) and same_bits(db, mb), (k, "device call")
+        if k == 1:
+            assert same_bits(d_mom.cpu().numpy(), mm), "the moments call's moments, blended with those the plain call before it kept"
+    assert same_bits(r["history_len"], mn) and same_bits(r["f32"], mo) and same_bits(r["u8"], mb) and same_bits(r["moments"], mm)
+    assert mn.max() == 3 and (mn >= 2).mean() > 0.5  # (the three calls did depend on each other)
     acc.close()
 
 

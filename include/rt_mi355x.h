@@ -177,12 +177,15 @@ int rt_scene_info(const rt_scene* scene, rt_scene_info_t* out);
 
 /* Host-side structural check of the built BVH: every triangle in exactly one leaf, every child
  * box inside its parent's, every triangle inside its leaf box. Returns RT_OK or RT_ERR_INVALID
- * (message names the first violation). Needs no GPU. */
+ * (message names the first violation); every entry of the origin-skip table proven again (the triangle in the subtree it names, the
+ * subtree flat on the triangle's plane within what the entry's thresholds allow). Needs no GPU. */
 int rt_scene_check_bvh(const rt_scene* scene);
 /* Diagnostic, host only (works on a scene built with device < 0): closest-hit walks of the tree for n rays as the traversal kernels make them
  * (children nearest first, culled by the closest hit so far), counting node visits and triangle tests, with a choice of the child boxes
  * tested: mode 0 the decoded 8-bit quantised boxes (what the kernels test), 1 the exact padded bounds of each child's subtree (what fp32
- * boxes would hold), 2 the exact bounds re-quantised with two more bits per plane. t / tri (may be NULL) receive the closest hits. The
+ * boxes would hold), 2 the exact bounds re-quantised with two more bits per plane, 4 (bit 2 on top of box mode 0; 3 is refused) as 0 with the origin skip of the render kernels: tri
+ * (required) holds ON ENTRY the triangle each ray starts on, 0xFFFFFFFF for none, and a ray that leaves its triangle's plane steeply enough
+ * does not descend into the coplanar subtree around it (profiles/origin_skip_host.txt). t / tri (may be NULL) receive the closest hits. The
  * difference between the modes is what the quantisation costs in visits on a given scene and ray set (profiles/r05_quantisation.txt). */
 int rt_scene_count_visits(const rt_scene* scene, uint32_t n, const float* org, const float* dir, int mode,
                           uint64_t* node_visits, uint64_t* tri_tests, float* t, uint32_t* tri);

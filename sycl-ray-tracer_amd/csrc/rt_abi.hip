@@ -88,6 +88,16 @@ int rt_scene_create_ex(const rt_scene_desc* desc, int device, int bvh_kind, uint
         delete s;
         return fail(rc, err);
     }
+    // the origin skip (rt_types.h: SkipRec): static host-built trees only — vertices that move break coplanarity, and a device-built tree has no host pass
+    rc = no_throw([&] {
+        if ((flags & RT_SCENE_UPDATABLE) || s->hs.built_by == RT_BVH_LBVH_GPU) clear_skip_table(s->hs);
+        else build_skip_table(s->hs);
+        return (int)RT_OK;
+    });
+    if (rc != RT_OK) {
+        delete s;
+        return rc;
+    }
     s->device = device;
     if (device >= 0) {
         rc = device_ok(device);
@@ -108,6 +118,7 @@ int rt_scene_create_ex(const rt_scene_desc* desc, int device, int bvh_kind, uint
             rc = upload(packed, &s->dev.tris, s->device_bytes);
         }
         if (rc == RT_OK) rc = upload(s->hs.shade, &s->dev.shade, s->device_bytes);
+        if (rc == RT_OK) rc = upload(s->hs.skip, &s->dev.skip, s->device_bytes);
         if (rc == RT_OK) { // (an updatable scene's table has room for a row per instance: the distinct matrices may grow)
             std::vector<InstRec> rows(s->hs.inst);
             if (flags & RT_SCENE_UPDATABLE) rows.resize(std::max<size_t>(rows.size(), desc->n_instances));
@@ -148,7 +159,7 @@ void rt_scene_destroy(rt_scene* s) {
         for (auto& se : s->ev_gbuffer) (void)hipEventSynchronize(se.second), (void)hipEventDestroy(se.second);
         (void)hipFree((void*)s->dev.nodes), (void)hipFree((void*)s->dev.tris), (void)hipFree((void*)s->dev.shade);
         (void)hipFree((void*)s->dev.inst), (void)hipFree((void*)s->dev.mats), (void)hipFree((void*)s->dev.tex);
-        (void)hipFree((void*)s->d_query_cursor);
+        (void)hipFree((void*)s->d_query_cursor), (void)hipFree((void*)s->dev.skip);
     }
     free_scene_update(s);
     delete s;
@@ -501,6 +512,20 @@ int rt_dev_scene_tree(const rt_scene* s, uint32_t* n_nodes, uint32_t* n_tris, ui
     if (global_index)
         for (size_t t = 0; t < std::min<size_t>(capacity, hs.tris.size()); ++t) global_index[t] = hs.tris[t].global_index;
     if (wverts) std::memcpy(wverts, hs.wverts.data(), std::min<size_t>(capacity, hs.wverts.size()) * sizeof(float));
+    return RT_OK;
+}
+
+// The origin-skip table of the scene's HOST copy (rt_types.h: SkipRec, 8 words per triangle): write = 0 copies the first `capacity` entries
+// out, write = 1 overwrites them from `entries` — what rt_scene_check_bvh then examines (the device's copy is not touched).
+int rt_dev_scene_skip_table(rt_scene* s, uint32_t* n_entries, uint32_t* entries, uint32_t capacity, int write) {
+    if (!s || !n_entries) return fail(RT_ERR_INVALID, "null argument");
+    if (const int rc = sync_host_copy(s)) return rc;
+    *n_entries = (uint32_t)s->hs.skip.size();
+    const size_t n = std::min<size_t>(capacity, s->hs.skip.size());
+    if (entries && n) {
+        if (write) std::memcpy(s->hs.skip.data(), entries, n * sizeof(SkipRec));
+        else std::memcpy(entries, s->hs.skip.data(), n * sizeof(SkipRec));
+    }
     return RT_OK;
 }
 

@@ -30,6 +30,22 @@ RT_DEV bool shade_bounce(const SceneDev& S, uint32_t& rng, RayState& r, const Hi
     return done;
 }
 
+// The origin skip of the ray trav_begin has just started (rt_types.h: SkipRec, origin_skip_word): `tri` is the triangle the ray starts on, kNoTri
+// for a camera ray or a ray out of a queue. The test runs on T.o and T.d, the origin and the direction (out of its half storage) that are
+// traversed; the word goes to the lane's LDS slot above its stack, where trav_inner<true> reads it. One 32-byte entry per bounce ray, loaded
+// by every lane (a lane without a triangle reads entry 0 and keeps kSkipNone): no exec-mask region of its own.
+RT_DEV void origin_skip_none(const TravStack& stack) { *lds_at(skip_word_addr(stack)) = (int32_t)kSkipNone; }
+RT_DEV void origin_skip(const SceneDev& S, uint32_t tri, const Trav& T, const TravStack& stack) {
+    const u32x4* ep = reinterpret_cast<const u32x4*>(S.skip + (tri == kNoTri ? 0u : tri));
+    const u32x4 a = ep[0], b = ep[1];
+    SkipRec e;
+    e.ref = a.x, e.n[0] = __uint_as_float(a.y), e.n[1] = __uint_as_float(a.z), e.n[2] = __uint_as_float(a.w);
+    e.p[0] = __uint_as_float(b.x), e.p[1] = __uint_as_float(b.y), e.p[2] = __uint_as_float(b.z), e.a = b.w;
+    const float o[3] = {T.o.x, T.o.y, T.o.z}, d[3] = {T.d.x, T.d.y, T.d.z};
+    const uint32_t w = origin_skip_word(e, o, d);
+    *lds_at(skip_word_addr(stack)) = (int32_t)(tri == kNoTri ? kSkipNone : w);
+}
+
 // Russian roulette on a continuing path (extension, see rt_renderer_set_russian_roulette); false = path ends
 RT_DEV bool roulette(uint32_t& rng, RayState& r) {
     const float qx = h2f(r.att[0]), qy = h2f(r.att[1]), qz = h2f(r.att[2]);

@@ -253,6 +253,7 @@ struct TravStack {
 };
 RT_DEV uint32_t stack_base(const TravStack& st) { return st.base + st.pitch; } // the first entry above the sentinel
 RT_DEV lds_i32* lds_at(uint32_t addr) { return (lds_i32*)(size_t)addr; }
+RT_DEV uint32_t skip_word_addr(const TravStack& st) { return st.base + (uint32_t)kLdsStack * st.pitch; } // RT_TRAVERSAL_LDS_SKIP: one word per lane above the stacks
 // true when the lane's next `pushes` pushes and a pop all stay inside the LDS part of its stack
 RT_DEV bool stack_shallow(const TravStack& st, const Trav& T, uint32_t pushes) { return T.sp <= st.base + ((uint32_t)kLdsStack - pushes) * st.pitch; }
 RT_DEV void trav_pop_lds(Trav& T, const TravStack& st) { // caller: stack_shallow
@@ -343,8 +344,14 @@ struct WaveStats {
 // The near/far plane words are picked once per axis from the ray's direction sign, so no per-child
 // min/max pairing is needed.
 RT_DEV TravSigns trav_signs(const Trav& T) { return TravSigns{lanes(T.ix < 0.0f), lanes(T.iy < 0.0f), lanes(T.iz < 0.0f)}; }
+// SKIP (k_megakernel, k_wf_finish: the origin skip, rt_types.h: SkipRec): a child whose word equals the lane's skip word — kept in the
+// LDS word above its stack, written where the ray is started (rt_bounce.h: origin_skip) — counts as missed: one compare per child into an
+// SGPR pair, and-ed on the scalar unit into the hit mask. The child words are then needed at the keys, not only at the sort.
+template <bool SKIP = false>
 RT_DEV void trav_inner(const SceneDev& S, Trav& T, const TravStack& stack, const TopTree& top, const TravSigns& sg) {
     const float inf = __builtin_huge_valf();
+    uint32_t skip = kSkipNone;
+    if (SKIP) skip = (uint32_t)*lds_at(skip_word_addr(stack));
     float k0, k1, k2, k3;
     u32x4 w0, w1, w2, chw;
     if (T.cur < top.count * 64) { // top of the tree: LDS, 16 bytes per node and plane
@@ -384,18 +391,19 @@ RT_DEV void trav_inner(const SceneDev& S, Trav& T, const TravStack& stack, const
     // of origin * inv - o * inv on all three axes at once (entry == exit), and out there the padded boxes are no longer conservative
     // for any child, absent or not — so the child words are not tested here (an explicit kChildEmpty test per slot was measured at
     // 12 issue cycles of ~500 per step).
-#define RT_CHILD(K, CVT)                                                                                  \
+#define RT_CHILD(K, CVT, CW)                                                                              \
     {                                                                                                    \
         const float tn = __builtin_fmaxf(__builtin_fmaxf(__builtin_fmaf(CVT(qnx), ax, bx), __builtin_fmaf(CVT(qny), ay, by)), \
                                          __builtin_fmaxf(__builtin_fmaf(CVT(qnz), az, bz), 0.0f));       \
         const float tf = __builtin_fminf(__builtin_fminf(__builtin_fmaf(CVT(qfx), ax, bx), __builtin_fmaf(CVT(qfy), ay, by)), \
                                          __builtin_fminf(__builtin_fmaf(CVT(qfz), az, bz), T.best.t));   \
-        K = sel(lanes(tn <= tf), inf, tn);                                                               \
+        K = sel(SKIP ? (lanes(tn <= tf) & lanes(CW != skip)) : lanes(tn <= tf), inf, tn);                \
     }
-    RT_CHILD(k0, ub0)
-    RT_CHILD(k1, ub1)
-    RT_CHILD(k2, ub2)
-    RT_CHILD(k3, ub3)
+    if (SKIP) asm volatile("s_waitcnt vmcnt(0)" : "+v"(chw));
+    RT_CHILD(k0, ub0, chw.x)
+    RT_CHILD(k1, ub1, chw.y)
+    RT_CHILD(k2, ub2, chw.z)
+    RT_CHILD(k3, ub3, chw.w)
 #undef RT_CHILD
     // sorting network on (entry distance, child); misses carry +inf and sink to the end. One comparator = one compare into an
     // SGPR pair + four e64 selects on it (18 cycles).
@@ -406,7 +414,7 @@ RT_DEV void trav_inner(const SceneDev& S, Trav& T, const TravStack& stack, const
         const int32_t ca = sel(sw, CA, CB), cb = sel(sw, CB, CA);                   \
         KA = ka, KB = kb, CA = ca, CB = cb;                                         \
     }
-    asm volatile("s_waitcnt vmcnt(0)" : "+v"(chw));
+    if (!SKIP) asm volatile("s_waitcnt vmcnt(0)" : "+v"(chw));
     int32_t c0 = (int32_t)chw.x, c1 = (int32_t)chw.y, c2 = (int32_t)chw.z, c3 = (int32_t)chw.w;
     RT_CE(k0, c0, k1, c1)
     RT_CE(k2, c2, k3, c3)
@@ -466,7 +474,7 @@ RT_DEV void trav_leaf(const SceneDev& S, Trav& T, const TravStack& stack) {
 }
 
 // One wave-uniform step. Returns the number of lanes still traversing BEFORE the step (0 = all done).
-template <bool STATS = false, bool LEAF_BATCH = false>
+template <bool STATS = false, bool LEAF_BATCH = false, bool SKIP = false>
 RT_DEV uint32_t trav_step_wave(const SceneDev& S, Trav& T, const TravStack& stack, const TopTree& top, const TravSigns& sg, WaveStats* ws = nullptr) {
     const bool inner = T.cur >= 0;
     const bool leaf = T.cur < 0 && T.cur != kTravDone;
@@ -474,8 +482,8 @@ RT_DEV uint32_t trav_step_wave(const SceneDev& S, Trav& T, const TravStack& stac
     // the vote, weighted 3 : 4 — a leaf step as soon as the leaf lanes exceed 3/4 of the inner lanes: a lane parked at a leaf is idle for as
     // many iterations as the vote goes against it (plain majority: -1.2 %; EXPERIMENTS.md)
     if (ni * 3u >= nl * 4u && !(LEAF_BATCH && nl >= 64u)) {
-        if (STATS && ni) ws->inner_steps++, ws->inner_lanes += ni, ws->top_lanes += (uint32_t)__popcll(__ballot(inner && T.cur < kTopNodes * 64));
-        if (inner) trav_inner(S, T, stack, top, sg);
+        if (STATS && ni) ws->inner_steps++, ws->inner_lanes += ni, ws->top_lanes += (uint32_t)__popcll(__ballot(inner && T.cur < (SKIP ? top.count : kTopNodes) * 64));
+        if (inner) trav_inner<SKIP>(S, T, stack, top, sg);
     } else {
         if (STATS) ws->leaf_steps++, ws->leaf_lanes += (uint32_t)__popcll(__ballot(leaf));
         if (leaf) trav_leaf<LEAF_BATCH>(S, T, stack);
@@ -765,12 +773,19 @@ RT_DEV bool shade_hit(const SceneDev& S, const ShadeTables& tab, uint32_t& rng, 
 RT_DEV uint8_t to_unorm8(float c) { return (uint8_t)__builtin_rintf(clamp01(c) * 255.0f); }
 
 // LDS of a traversal kernel with BLOCK threads: the staged top of the BVH + the per-lane stacks
-#define RT_TRAVERSAL_LDS(BLOCK)                                                                        \
-    __shared__ u32x4 top_all[4 * kTopNodes]; /* the four planes back to back: trav_inner's fetch addresses them from ONE base */ \
-    u32x4 *const top_w0 = top_all, *const top_w1 = top_all + kTopNodes, *const top_w2 = top_all + 2 * kTopNodes, *const top_ch = top_all + 3 * kTopNodes; \
-    __shared__ int32_t lds_stack[kLdsStack * (BLOCK)];                                                 \
+#define RT_TRAVERSAL_LDS(BLOCK) RT_TRAVERSAL_LDS_(BLOCK, kTopNodes, 0)
+// ... of the two kernels with the origin skip: a skip word per lane above the stacks (skip_word_addr), its 4 x BLOCK bytes taken from the staged top
+// (kMegaBlock = 512: 32 nodes; 341 -> 309 measured flat, EXPERIMENTS.md). The word starts as kSkipNone. ON = false (a compile-time constant:
+// SHOOT) is RT_TRAVERSAL_LDS.
+#define RT_TRAVERSAL_LDS_SKIP(BLOCK, ON)                                                               \
+    RT_TRAVERSAL_LDS_(BLOCK, (ON) ? kTopNodes - (int)(BLOCK) / 16 : kTopNodes, (ON) ? 1 : 0)           \
+    if (ON) lds_stack[kLdsStack * (BLOCK) + threadIdx.x] = (int32_t)kSkipNone;
+#define RT_TRAVERSAL_LDS_(BLOCK, NTOP, EXTRA)                                                          \
+    __shared__ u32x4 top_all[4 * (NTOP)]; /* the four planes back to back: trav_inner's fetch addresses them from ONE base */ \
+    u32x4 *const top_w0 = top_all, *const top_w1 = top_all + (NTOP), *const top_w2 = top_all + 2 * (NTOP), *const top_ch = top_all + 3 * (NTOP); \
+    __shared__ int32_t lds_stack[(kLdsStack + (EXTRA)) * (BLOCK)];                                     \
     int32_t spill[kStackSize - kLdsStack];                                                             \
-    const int32_t top_count = (int32_t)S.n_nodes < kTopNodes ? (int32_t)S.n_nodes : kTopNodes;         \
+    const int32_t top_count = (int32_t)S.n_nodes < (NTOP) ? (int32_t)S.n_nodes : (NTOP);               \
     top_tree_fill(S, top_w0, top_w1, top_w2, top_ch, top_count);                                       \
     __syncthreads();                                                                                   \
     const TopTree top{(lds_u32x4*)top_w0, (lds_u32x4*)top_w1, (lds_u32x4*)top_w2, (lds_u32x4*)top_ch, top_count}; \

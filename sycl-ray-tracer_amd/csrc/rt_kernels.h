@@ -278,7 +278,7 @@ __global__ void __launch_bounds__(kMegaBlock, kMegaWaves) k_megakernel(SceneDev 
     Trav T;
     if (SLICED) *slice_looks_word(color_r, (lds_f32*)color_lds) = 0u; // per wave: rounds in which it held nothing but waiting lanes (slice_wait_count)
     RT_SHADE_LDS
-    RT_TRAVERSAL_LDS(kMegaBlock)
+    RT_TRAVERSAL_LDS_SKIP(kMegaBlock, true)
     T.cur = kTravDone;
     // A lane is `live` when it owns a pixel slice with samples left; `depth` then holds the bounces of its current path so far — or, in a
     // SLICED launch, kPend: the lane has taken a later slice of a pixel (`s` = the sample it starts with) and waits for the state the slice before ends with. It LOOKS for that
@@ -319,6 +319,7 @@ __global__ void __launch_bounds__(kMegaBlock, kMegaWaves) k_megakernel(SceneDev 
                     r = camera_ray(cam, x, gy, rng);
                 }
                 trav_begin(T, r.org, ray_dir(r), stack);
+                origin_skip_none(stack);
             } else {
                 depth = kPend; // the state the slice starts from comes from the lane that renders the slice before it (below)
             }
@@ -393,11 +394,11 @@ __global__ void __launch_bounds__(kMegaBlock, kMegaWaves) k_megakernel(SceneDev 
             if (STATS >= 2) ws.live_lane_steps += n_live;
             if (STATS == 1) ws.inner_steps += (uint32_t)kMegaUnroll; // (timing only: steps of either kind, counted per loop iteration)
             refill.stepped();
-            (void)trav_step_wave<(STATS >= 2), true>(S, T, stack, top, sg, &ws);
+            (void)trav_step_wave<(STATS >= 2), true, true>(S, T, stack, top, sg, &ws);
 #pragma unroll
             for (int k = 1; k < kMegaUnroll; ++k) { // the exit tests are checked every kMegaUnroll steps
                 if (STATS >= 2) ws.live_lane_steps += n_live;
-                (void)trav_step_wave<(STATS >= 2), true>(S, T, stack, top, sg, &ws);
+                (void)trav_step_wave<(STATS >= 2), true, true>(S, T, stack, top, sg, &ws);
             }
         }
         if (STATS) {
@@ -412,6 +413,7 @@ __global__ void __launch_bounds__(kMegaBlock, kMegaWaves) k_megakernel(SceneDev 
         if (STATS >= 2) ck[7] = (long long)__builtin_readcyclecounter();
 #endif
         bool pixel_finished = false;
+        bool bounced = false; // this lane's path goes on from the triangle it hit (the origin skip)
         {
             const unsigned long long traced = __ballot(live && T.cur == kTravDone && depth < kPend); // every lane of the round but those that wait for a state has traced a ray
             wave_rays += (unsigned long long)__popcll(traced);
@@ -480,6 +482,8 @@ __global__ void __launch_bounds__(kMegaBlock, kMegaWaves) k_megakernel(SceneDev 
                         pixel_end(color_r, color_g, color_b, n, pix, out_f32, out_u8);
                         if constexpr (CARRY != 0) frame_carry(frame)[pix] = carry_word(*color_r, *color_g, *color_b, rng); // the pixel's state for the next continuation
                     }
+                } else {
+                    bounced = true;
                 }
             }
             if (start) {
@@ -488,7 +492,11 @@ __global__ void __launch_bounds__(kMegaBlock, kMegaWaves) k_megakernel(SceneDev 
                 asm volatile("" : "+v"(cx), "+v"(cy)); // (or hipcc converts the pixel's coordinates to float where the lane takes the pixel and keeps them in scratch memory until here)
                 r = camera_ray(frame_camera(frame, width, height), cx, cy, rng);
             }
-            if (live && depth < kPend) trav_begin(T, r.org, ray_dir(r), stack);
+            if (live && depth < kPend) {
+                const uint32_t from = bounced ? T.best.tri : kNoTri;
+                trav_begin(T, r.org, ray_dir(r), stack);
+                origin_skip(S, from, T, stack);
+            }
             RT_STAMP_AFTER((STATS >= 2 ? ck : nullptr), 5, T.ox); // sky lanes, half conversions, path ends, camera rays, trav_begin
         }
         refill.round(pixel_finished);
@@ -938,7 +946,10 @@ __global__ void __launch_bounds__(kMegaBlock, kMegaWaves) k_wf_finish(SceneDev S
     const uint32_t wave_id = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
     const uint32_t n_waves = gridDim.x * kWavesPerBlock;
     RT_SHADE_LDS
-    RT_TRAVERSAL_LDS(kMegaBlock)
+    // (the origin skip, rt_bounce.h: not in SHOOT — its rays come out of a queue that does not say which triangle they start on, and the compare
+    // per child was -0.4 % there for nothing)
+    constexpr bool kSkip = !LIMIT;
+    RT_TRAVERSAL_LDS_SKIP(kMegaBlock, kSkip)
     __shared__ unsigned long long rq_stage_mem[REQ ? kWavesPerBlock * kRqStage : 1u];
     typedef __attribute__((address_space(3))) unsigned long long lds_u64_t;
     lds_u64_t* stage = (lds_u64_t*)rq_stage_mem + (threadIdx.x >> 6) * kRqStage; // REQ: this wave's staged entries
@@ -1044,6 +1055,7 @@ __global__ void __launch_bounds__(kMegaBlock, kMegaWaves) k_wf_finish(SceneDev S
             r = camera_ray(cam, x, tile_global_row(tile, ly), rng);
             depth = 0, first_counted = false;
             trav_begin(T, r.org, ray_dir(r), stack);
+            if constexpr (kSkip) origin_skip_none(stack);
             live = true, waiting = false;
         }
         if (!(REQ ? drained : exhausted)) {
@@ -1133,6 +1145,7 @@ __global__ void __launch_bounds__(kMegaBlock, kMegaWaves) k_wf_finish(SceneDev S
                                         *xg_word() = (id % w) | ((uint32_t)tile_global_row(tile, (int)(id / w)) << 16);
                                     }
                                     trav_begin(T, r.org, ray_dir(r), stack);
+                                    if constexpr (kSkip) origin_skip_none(stack); // (a ray out of a queue: the triangle it starts on is not on record)
                                     live = true;
                                 }
                             }
@@ -1174,9 +1187,9 @@ __global__ void __launch_bounds__(kMegaBlock, kMegaWaves) k_wf_finish(SceneDev S
             if ((uint32_t)__popcll(__ballot(done_trav)) * 100u >= shade_at) break;
             if (STATS) ws.live_lane_steps += n_live * kMegaUnroll;
             refill.stepped();
-            (void)trav_step_wave<STATS, true>(S, T, stack, top, sg, &ws);
+            (void)trav_step_wave<STATS, true, kSkip>(S, T, stack, top, sg, &ws);
 #pragma unroll
-            for (int k = 1; k < kMegaUnroll; ++k) (void)trav_step_wave<STATS, true>(S, T, stack, top, sg, &ws);
+            for (int k = 1; k < kMegaUnroll; ++k) (void)trav_step_wave<STATS, true, kSkip>(S, T, stack, top, sg, &ws);
         }
         if (STATS) ws.shade_rounds++, ws.shade_lanes += (uint32_t)__popcll(__ballot(live && T.cur == kTravDone));
         __builtin_amdgcn_s_setprio(0);
@@ -1208,12 +1221,14 @@ __global__ void __launch_bounds__(kMegaBlock, kMegaWaves) k_wf_finish(SceneDev S
                 r = camera_ray(cam, x, gy, rng);
                 depth = 0;
                 trav_begin(T, r.org, ray_dir(r), stack);
+                if constexpr (kSkip) origin_skip_none(stack);
             }
         } else if (live && T.cur == kTravDone) { // SHADE: the body of shoot_rays after rtcIntersect1 (src/render_wavefront.cpp:245-291)
             f3 res;
             const bool done = shade_bounce<true>(S, rng, r, T.best, res, &T, &tab);
             depth++;
             bool ends = done;
+            bool bounced = !done; // the path goes on from the triangle it hit (the origin skip), unless it ends below
             if (SLICED && done) { // the same additions in the same order, on the sums this lane holds in LDS
                 *sum_r = *sum_r + clamp01(res.x), *sum_g = *sum_g + clamp01(res.y), *sum_b = *sum_b + clamp01(res.z);
             } else if (done) {
@@ -1264,7 +1279,7 @@ __global__ void __launch_bounds__(kMegaBlock, kMegaWaves) k_wf_finish(SceneDev S
                 }
                 r = camera_ray(cam, x, gy, rng);
                 depth = 0, first_counted = false;
-                ends = false;
+                ends = false, bounced = false;
             }
             // SLICED: only the lane that finishes the pixel writes its words in memory — a lane that hands it on stores nothing there, or several
             // lanes, on different XCDs, would write the same word with plain stores (the next slice's lane carries the RNG word on)
@@ -1277,7 +1292,9 @@ __global__ void __launch_bounds__(kMegaBlock, kMegaWaves) k_wf_finish(SceneDev S
             } else if (LIMIT && depth - first_depth >= bounce_limit) {
                 hand_on = true, live = false, slot_finished = true; // the survivor goes to the next bounce's queue (below)
             } else {
+                const uint32_t from = bounced ? T.best.tri : kNoTri;
                 trav_begin(T, r.org, ray_dir(r), stack);
+                if constexpr (kSkip) origin_skip(S, from, T, stack);
             }
         }
         if (LIMIT) { // compaction of the survivors into the next queue: src/render_wavefront.cpp:282-311 (there: per 16-item work-group through LDS)

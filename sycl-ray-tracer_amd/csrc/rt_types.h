@@ -153,6 +153,45 @@ struct alignas(16) MatRec {
 };
 static_assert(sizeof(MatRec) == 48, "MatRec must be 48 bytes");
 
+// ---- the surface a ray starts on, GLOBAL order: 32 bytes ("the origin skip") ------------------------------------------
+// A bounce ray starts on the triangle it hit, inside the padded boxes of that triangle's leaf and of every ancestor that holds nothing
+// but triangles of the same plane: it would walk down to them first and test triangles that can only give t ~ 0 < kTNear. `ref` is
+// the child word — as the DEVICE's parent node stores it: a node's byte offset, or a leaf code — of the highest such ancestor the
+// builder has PROVEN flat (scene_check.cpp: skip_bounds), kSkipNone where there is none; the render kernels count the child with that
+// word as missed for a ray whose start passes the test below.
+//   n     the triangle's unit normal, computed in double and rounded to fp32 (either orientation)
+//   p     the triangle's first vertex
+//   a     two halves, rounded up: a0 (low) and a2 (high) of the test
+//             |n . d|  >  a0 + kSkipDist * |n . (o - p)| + a2 * |o - p|_1      and      |n . d|  >  kSkipTilt * |d|_1
+//         evaluated in fp32 on the origin o and the direction d the traversal uses (rt_bounce.h: origin_skip)
+constexpr uint32_t kSkipNone = 1u; // no child word: a node offset is a multiple of 64, a leaf code is negative
+constexpr float kSkipDist = 40400.0f;        // (4 / kTNear) x 1.01
+constexpr float kSkipTilt = 1.0f / 256.0f;
+struct alignas(16) SkipRec {
+    uint32_t ref;
+    float n[3];
+    float p[3];
+    uint32_t a;
+};
+static_assert(sizeof(SkipRec) == 32, "SkipRec must be 32 bytes");
+// The test, written once for the kernels and for the host walk (scene_check.cpp: count_visits mode 4): the word a ray from o along d must not
+// descend into. Every operation is a single fp32 one as written (a NaN anywhere fails both compares: kSkipNone).
+RT_HD float skip_half(uint32_t bits16) {
+    const uint16_t b = (uint16_t)bits16;
+    _Float16 h;
+    __builtin_memcpy(&h, &b, 2);
+    return (float)h;
+}
+RT_HD uint32_t origin_skip_word(const SkipRec& e, const float o[3], const float d[3]) {
+    const float wx = o[0] - e.p[0], wy = o[1] - e.p[1], wz = o[2] - e.p[2];
+    const float s = __builtin_fmaf(e.n[2], wz, __builtin_fmaf(e.n[1], wy, e.n[0] * wx));
+    const float nd = __builtin_fabsf(__builtin_fmaf(e.n[2], d[2], __builtin_fmaf(e.n[1], d[1], e.n[0] * d[0])));
+    const float l = (__builtin_fabsf(wx) + __builtin_fabsf(wy)) + __builtin_fabsf(wz);
+    const float ld = (__builtin_fabsf(d[0]) + __builtin_fabsf(d[1])) + __builtin_fabsf(d[2]);
+    const float thr = __builtin_fmaf(skip_half(e.a >> 16), l, __builtin_fmaf(kSkipDist, __builtin_fabsf(s), skip_half(e.a & 0xffffu)));
+    return (nd > thr && nd > kSkipTilt * ld) ? e.ref : kSkipNone;
+}
+
 // device pointers of one scene replica
 struct SceneDev {
     const BvhNode* nodes;
@@ -167,6 +206,7 @@ struct SceneDev {
     float cell_lo[3], cell_scale[3]; // ray re-ordering (f-3): cell = (origin - cell_lo) * cell_scale, 0..4 per axis over the scene's bounds
     uint32_t packed_mat;             // 1: ShadeRec::instance carries the material index in bits 20..31
     uint32_t lds_nm, lds_mats;       // normal matrices / materials the shading kernels stage in LDS (0: shading word not packed)
+    const SkipRec* skip;             // per triangle, global order (k_megakernel and k_wf_finish only)
 };
 
 // == Camera POD (src/camera.hpp:65-72)

@@ -1033,4 +1033,65 @@ bool refit_host(HostScene& hs, const std::vector<uint32_t>& level_nodes, std::ve
     return true;
 }
 
+// ---- the origin skip (rt_types.h: SkipRec) -------------------------------------------------------------------------------------------------------
+void clear_skip_table(HostScene& hs) {
+    SkipRec none{};
+    none.ref = kSkipNone;
+    hs.skip.assign(hs.wverts.size() / 9, none);
+}
+
+// Per triangle: its plane (unit normal in double, rounded to fp32; first vertex), then up from its leaf while skip_bounds proves the whole
+// subtree flat on that plane — a subtree that fails makes every larger one fail, so the last one proven is the highest. A pre-split
+// triangle starts from the first leaf that holds a piece of it (any subtree proven flat may be skipped, the triangle's own or not).
+void build_skip_table(HostScene& hs) {
+    clear_skip_table(hs);
+    const size_t T = hs.skip.size();
+    if (T == 0 || hs.nodes.empty()) return;
+    std::vector<int32_t> parent(hs.nodes.size(), -1);    // node -> the node that names it
+    std::vector<int32_t> rec_node(hs.tris.size(), -1);   // leaf record -> the node whose leaf child holds it
+    std::vector<uint8_t> rec_slot(hs.tris.size(), 0);
+    for (size_t i = 0; i < hs.nodes.size(); ++i)
+        for (int k = 0; k < 4; ++k) {
+            const int32_t c = hs.nodes[i].child[k];
+            if (c == kChildEmpty) continue;
+            if (c >= 0) {
+                if ((size_t)c < hs.nodes.size()) parent[(size_t)c] = (int32_t)i;
+                continue;
+            }
+            const LeafRange leaf = leaf_range(c);
+            for (uint32_t r = leaf.first; r < leaf.first + leaf.count && r < hs.tris.size(); ++r) rec_node[r] = (int32_t)i, rec_slot[r] = (uint8_t)k;
+        }
+    std::vector<int32_t> first_rec(T, -1);
+    for (size_t r = hs.tris.size(); r-- > 0;)
+        if (hs.tris[r].global_index < T && rec_node[r] >= 0) first_rec[hs.tris[r].global_index] = (int32_t)r;
+    for (size_t t = 0; t < T; ++t) {
+        if (first_rec[t] < 0) continue;
+        const float* w = &hs.wverts[9 * t];
+        double e1[3], e2[3];
+        for (int a = 0; a < 3; ++a) e1[a] = (double)w[3 + a] - (double)w[a], e2[a] = (double)w[6 + a] - (double)w[a];
+        const double c[3] = {e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2], e1[0] * e2[1] - e1[1] * e2[0]};
+        const double len = std::sqrt(c[0] * c[0] + c[1] * c[1] + c[2] * c[2]);
+        if (!(len > 0.0) || !std::isfinite(len)) continue;
+        SkipRec e{};
+        for (int a = 0; a < 3; ++a) e.n[a] = (float)(c[a] / len), e.p[a] = w[a];
+        int32_t at = rec_node[(size_t)first_rec[t]];
+        int32_t child = hs.nodes[(size_t)at].child[rec_slot[(size_t)first_rec[t]]]; // the leaf, then its ancestors
+        double a0 = 0.0, a2 = 0.0, b0, b2;
+        bool any = false;
+        while (skip_bounds(hs, e.n, e.p, child, b0, b2) && b0 < 1.0) {
+            any = true, a0 = b0, a2 = b2;
+            e.ref = device_child_word(child);
+            if (at <= 0) break; // the root has no word
+            child = at, at = parent[(size_t)at];
+            if (at < 0) break;
+        }
+        if (!any) continue;
+        const uint16_t h0 = half_up(a0), h2 = half_up(a2);
+        if (h0 == 0x7C00 || h2 == 0x7C00) continue;
+        e.a = (uint32_t)h0 | ((uint32_t)h2 << 16);
+        hs.skip[t] = e;
+    }
+}
+
+
 } // namespace rt

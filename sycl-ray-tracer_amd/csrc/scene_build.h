@@ -18,6 +18,7 @@ struct HostScene {
     std::vector<MatRec> mats;
     std::vector<uint8_t> tex;
     std::vector<float> wverts;    // 9 floats per triangle, global order (diagnostics / checks)
+    std::vector<SkipRec> skip;    // global order: the subtree a ray that starts on the triangle need not enter (rt_types.h); all kSkipNone unless build_skip_table ran
     std::vector<float> rec_lo, rec_hi; // host SAH builder: per leaf record, the box of the triangle's pieces in that leaf (check_bvh)
     uint32_t n_split_triangles = 0;    // triangles the SAH builder's pre-splitting pass cut into several references
     uint32_t n_layers = 0;
@@ -80,11 +81,27 @@ double refit_sah_cost(const HostScene& hs, const std::vector<float>& box);
 // The same cost from the nodes' decoded (quantised, padded) child boxes: what a device build reports.
 double decoded_sah_cost(const HostScene& hs);
 
+// ---- the origin skip (rt_types.h: SkipRec) ------------------------------------------------------------------------------------
+// A child word as the device's nodes store it (rt_abi.hip: rt_scene_create_ex): what SkipRec::ref is compared with.
+inline uint32_t device_child_word(int32_t child) { return child >= 0 ? (uint32_t)child * 64u : (uint32_t)child; }
+constexpr uint32_t kSkipMaxRecords = 128; // the largest subtree (leaf records) an entry may name: proving one flat costs a pass over it per triangle
+// (scene_check.cpp) The proof behind one entry, in double: every leaf record below `child` — the triangle (v0, v0 + e1, v0 + e2) the kernels
+// test — lies within `dev` of the plane through p with normal n, is no sliver (|e1||e2| / |e1 x e2| <= 256), has an area and a normal within
+// 2^-10 of +-n. Returns false where that fails or the subtree holds more than kSkipMaxRecords records; else a0 and a2 of the test in rt_types.h.
+bool skip_bounds(const HostScene& hs, const float n[3], const float p[3], int32_t child, double& a0, double& a2);
+uint16_t half_up(double x);      // the smallest half >= x (x >= 0); 0x7C00 where there is none
+float half_value(uint16_t bits);
+// Fills hs.skip with kSkipNone; build_skip_table then names, per triangle, the highest ancestor skip_bounds accepts (host-built static trees only:
+// rt_abi.hip leaves the table cleared for updatable scenes — vertices that move break coplanarity — and device-built trees).
+void clear_skip_table(HostScene& hs);
+void build_skip_table(HostScene& hs);
+
 // ---- diagnostics (scene_check.cpp) ----------------------------------------------------------------------------------------------------------
 // Structural check used by rt_scene_check_bvh.
 int check_bvh(const HostScene& hs, std::string& err);
 
-// Diagnostic used by rt_scene_count_visits: closest-hit walks on the host with quantised (0), exact (1) or finer quantised (2) child boxes.
+// Diagnostic used by rt_scene_count_visits: closest-hit walks on the host with quantised (0), exact (1) or finer quantised (2) child boxes; 4: as 0 with the
+// origin skip of hs.skip, tri_out holding on entry the triangle every ray starts on (kNoTri: none).
 int count_visits(const HostScene& hs, uint32_t n, const float* org, const float* dir, int mode, uint64_t* node_visits, uint64_t* tri_tests, float* t_out,
                  uint32_t* tri_out, std::string& err);
 

@@ -4,6 +4,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstring>
 #include <limits>
 
 namespace rt {
@@ -74,6 +75,115 @@ double refit_sah_cost(const HostScene& hs, const std::vector<float>& box) {
     return 1.0 + cost;
 }
 
+// ---- the origin skip: the proof behind one table entry (rt_types.h: SkipRec) ------------------------------------------------------
+uint16_t half_up(double x) {
+    if (!(x >= 0.0)) return 0x7C00;
+    if (x > 65504.0) return 0x7C00;
+    const _Float16 h = (_Float16)x; // round to nearest even
+    uint16_t b;
+    std::memcpy(&b, &h, 2);
+    if ((double)h < x) b++; // positive and finite: the next half up (65504 was the largest x)
+    return b;
+}
+float half_value(uint16_t bits) {
+    _Float16 h;
+    std::memcpy(&h, &bits, 2);
+    return (float)h;
+}
+
+namespace {
+// the leaf records below `child`, at most kSkipMaxRecords of them (false: more)
+bool records_below(const HostScene& hs, int32_t child, uint32_t depth, std::vector<uint32_t>& out) {
+    if (child == kChildEmpty) return true;
+    if (child < 0) {
+        const LeafRange leaf = leaf_range(child);
+        if ((size_t)leaf.first + leaf.count > hs.tris.size()) return false;
+        for (uint32_t k = 0; k < leaf.count; ++k) out.push_back(leaf.first + k);
+        return out.size() <= kSkipMaxRecords;
+    }
+    if ((size_t)child >= hs.nodes.size() || depth >= (uint32_t)kStackSize) return false;
+    for (int k = 0; k < 4; ++k)
+        if (!records_below(hs, hs.nodes[(size_t)child].child[k], depth + 1, out)) return false;
+    return true;
+}
+} // namespace
+
+bool skip_bounds(const HostScene& hs, const float nf[3], const float pf[3], int32_t child, double& a0, double& a2) {
+    std::vector<uint32_t> recs;
+    if (!records_below(hs, child, 0, recs) || recs.empty()) return false;
+    const double n[3] = {nf[0], nf[1], nf[2]}, p[3] = {pf[0], pf[1], pf[2]};
+    const double nn = std::sqrt(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]);
+    if (!(std::fabs(nn - 1.0) <= 1e-6)) return false;
+    double dev = 0.0, reach = 0.0, kappa = 1.0;
+    for (uint32_t r : recs) {
+        const TriRec& tr = hs.tris[r];
+        const double e1[3] = {tr.e1[0], tr.e1[1], tr.e1[2]}, e2[3] = {tr.e2[0], tr.e2[1], tr.e2[2]};
+        const double c[3] = {e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2], e1[0] * e2[1] - e1[1] * e2[0]};
+        const double area2 = std::sqrt(c[0] * c[0] + c[1] * c[1] + c[2] * c[2]);
+        const double l1 = std::sqrt(e1[0] * e1[0] + e1[1] * e1[1] + e1[2] * e1[2]), l2 = std::sqrt(e2[0] * e2[0] + e2[1] * e2[1] + e2[2] * e2[2]);
+        if (!(area2 >= 1e-24) || !std::isfinite(area2)) return false;
+        kappa = std::max(kappa, l1 * l2 / area2);
+        double plus = 0.0, minus = 0.0; // |n' - n|^2, |n' + n|^2
+        for (int a = 0; a < 3; ++a) plus += (c[a] / area2 - n[a]) * (c[a] / area2 - n[a]), minus += (c[a] / area2 + n[a]) * (c[a] / area2 + n[a]);
+        if (!(std::sqrt(std::min(plus, minus)) <= 0.9 / 1024.0)) return false;
+        for (int v = 0; v < 3; ++v) { // the triangle the kernels test: v0, v0 + e1, v0 + e2
+            double s = 0.0, d2 = 0.0;
+            for (int a = 0; a < 3; ++a) {
+                const double x = (double)tr.v0[a] + (v == 1 ? e1[a] : (v == 2 ? e2[a] : 0.0)) - p[a];
+                s += n[a] * x, d2 += x * x;
+            }
+            dev = std::max(dev, std::fabs(s)), reach = std::max(reach, std::sqrt(d2));
+        }
+    }
+    if (!(kappa <= 256.0) || !std::isfinite(dev) || !std::isfinite(reach)) return false;
+    // t of any point of the subtree <= kTNear / 4 (flatness, the origin's measured distance and that measurement's rounding: 4.1 u |o - p|_1),
+    // Moller-Trumbore's error on it <= kTNear / 2 (16 u kappa (|o - p| + reach) / (0.75 |n . d|)); 1 % for the kernel's own fp32 evaluation
+    const double u = std::ldexp(1.0, -24), tn = (double)kTNear;
+    a0 = std::max(1.01 * (4.0 * dev + 2.0 * 16.0 * u * kappa * reach / 0.75) / tn, std::ldexp(1.0, -20));
+    a2 = 1.01 * (4.0 * 4.1 * u + 2.0 * 16.0 * u * kappa / 0.75) / tn;
+    return true;
+}
+
+namespace {
+// rt_scene_check_bvh's part for the table: every entry that names a subtree is proven again from the tree as it is
+bool check_skip_table(const HostScene& hs, std::string& err) {
+    const size_t T = hs.wverts.size() / 9;
+    if (hs.skip.empty()) return true; // (a scene description without triangles)
+    if (hs.skip.size() != T) { err = "origin-skip table: one entry per triangle expected"; return false; }
+    std::vector<uint8_t> is_word; // by node index: the node is some node's child (every reachable node but the root)
+    is_word.assign(hs.nodes.size(), 0);
+    for (const BvhNode& n : hs.nodes)
+        for (int k = 0; k < 4; ++k)
+            if (n.child[k] >= 0 && (size_t)n.child[k] < hs.nodes.size()) is_word[(size_t)n.child[k]] = 1;
+    for (size_t t = 0; t < T; ++t) {
+        const SkipRec& e = hs.skip[t];
+        if (e.ref == kSkipNone) continue;
+        const std::string at = "origin-skip entry of triangle " + std::to_string(t);
+        int32_t child;
+        if ((int32_t)e.ref < 0) {
+            child = (int32_t)e.ref;
+        } else {
+            if (e.ref % 64u || e.ref / 64u >= hs.nodes.size() || !is_word[e.ref / 64u]) { err = at + ": not a child word"; return false; }
+            child = (int32_t)(e.ref / 64u);
+        }
+        std::vector<uint32_t> recs;
+        if (!records_below(hs, child, 0, recs)) { err = at + ": names no subtree of at most " + std::to_string(kSkipMaxRecords) + " records"; return false; }
+        bool member = false;
+        for (uint32_t r : recs) member = member || hs.tris[r].global_index == t;
+        if (!member) { err = at + ": the triangle is not in the subtree"; return false; }
+        const float* w = &hs.wverts[9 * t];
+        if (e.p[0] != w[0] || e.p[1] != w[1] || e.p[2] != w[2]) { err = at + ": p is not the triangle's first vertex"; return false; }
+        double a0, a2;
+        if (!skip_bounds(hs, e.n, e.p, child, a0, a2)) { err = at + ": the subtree is not coplanar with the triangle"; return false; }
+        if (!((double)half_value((uint16_t)(e.a & 0xffffu)) >= a0) || !((double)half_value((uint16_t)(e.a >> 16)) >= a2) || !(a0 < 1.0)) {
+            err = at + ": thresholds below what the subtree's flatness proves";
+            return false;
+        }
+    }
+    return true;
+}
+} // namespace
+
 int check_bvh(const HostScene& hs, std::string& err) {
     const size_t T = hs.wverts.size() / 9;
     if (hs.nodes.empty()) { err = "no root node"; return RT_ERR_INVALID; }
@@ -137,6 +247,7 @@ int check_bvh(const HostScene& hs, std::string& err) {
                 }
         }
     }
+    if (!check_skip_table(hs, err)) return RT_ERR_INVALID;
     return RT_OK;
 }
 
@@ -146,11 +257,23 @@ int check_bvh(const HostScene& hs, std::string& err) {
 //   mode 0  the decoded quantised boxes, as the kernels test them
 //   mode 1  the exact bounds of each child's subtree, padded as the builder pads them: what an unquantised (fp32) node would hold
 //   mode 2  the exact padded bounds re-quantised on the node's grid with 2 more bits per plane (step / 4)
+//   mode 4  mode 0 with the origin skip as the render kernels apply it (rt_bounce.h: origin_skip, the same fp32 expressions): tri_out holds ON
+//           ENTRY the triangle every ray starts on (kNoTri: none), and the child whose word is that triangle's SkipRec::ref counts as missed
+//           for a ray that passes the entry's test
+//           (4, not 3: the modes 0..2 choose the BOXES, this one adds a cull to mode 0's boxes — bit 2 on top of box mode 0 — and 3 stays refused, as
+//           callers and tests/test_host.py know it)
 // so that the share of the visits that is the price of 8-bit planes can be read off. Counts only: no result of a
 // render depends on it.
 int count_visits(const HostScene& hs, uint32_t n, const float* org, const float* dir, int mode, uint64_t* node_visits, uint64_t* tri_tests, float* t_out,
                  uint32_t* tri_out, std::string& err) {
-    if (mode < 0 || mode > 2) { err = "mode: 0 quantised, 1 exact, 2 quantised with two more bits"; return RT_ERR_INVALID; }
+    if (mode != 4 && (mode < 0 || mode > 2)) { err = "mode: 0 quantised, 1 exact, 2 quantised with two more bits, 4 quantised with the origin skip"; return RT_ERR_INVALID; }
+    const bool skipping = mode == 4;
+    if (skipping) {
+        mode = 0;
+        if (!tri_out) { err = "mode 4: tri holds the triangle every ray starts on"; return RT_ERR_INVALID; }
+        for (uint32_t i = 0; i < n; ++i)
+            if (tri_out[i] != kNoTri && tri_out[i] >= hs.skip.size()) { err = "mode 4: start triangle out of range"; return RT_ERR_INVALID; }
+    }
     if (hs.nodes.empty()) { err = "no tree"; return RT_ERR_INVALID; }
     const float inf = std::numeric_limits<float>::infinity();
     std::vector<Box3> box(hs.nodes.size() * 4); // the box tested for child k of node i
@@ -178,6 +301,8 @@ int count_visits(const HostScene& hs, uint32_t n, const float* org, const float*
         for (int a = 0; a < 3; ++a) inv[a] = 1.0f / (std::fabs(d[a]) < 1e-30f ? std::copysign(1e-30f, d[a]) : d[a]);
         float best = inf;
         uint32_t best_tri = kNoTri;
+        uint32_t skip = kSkipNone;
+        if (skipping && tri_out[i] != kNoTri) skip = origin_skip_word(hs.skip[tri_out[i]], o, d);
         int32_t stack[kStackSize * 4];
         int sp = 0;
         int32_t cur = 0;
@@ -189,7 +314,7 @@ int count_visits(const HostScene& hs, uint32_t n, const float* org, const float*
                 int32_t ch[4];
                 int m = 0;
                 for (int k = 0; k < 4; ++k) {
-                    if (nd.child[k] == kChildEmpty) continue;
+                    if (nd.child[k] == kChildEmpty || device_child_word(nd.child[k]) == skip) continue;
                     const Box3& b = box[(size_t)cur * 4 + k];
                     float tn = 0.0f, tf = best;
                     for (int a = 0; a < 3; ++a) {

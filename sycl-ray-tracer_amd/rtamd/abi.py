@@ -450,6 +450,9 @@ DEV_PROTOTYPES = {
     #  out global_index[capacity] | NULL, out wverts[capacity] | NULL, capacity): the scene's BVH as built (csrc/rt_abi.hip; tests/test_gpu_lbvh.py)
     "rt_dev_scene_tree": (C.c_int, [C.c_void_p, _P(C.c_uint32), _P(C.c_uint32), _P(C.c_uint32), _P(C.c_uint32), _P(C.c_int32), _P(C.c_float),
                                     _P(C.c_float), C.c_void_p, _P(C.c_uint32), _P(C.c_float), C.c_uint32]),
+    # (scene, out n_entries, entries[8 words x capacity] | NULL, capacity, write): the host copy's origin-skip table, read (write = 0) or
+    # overwritten (write = 1) for the checker's tests (csrc/rt_abi.hip; tests/test_origin_skip.py)
+    "rt_dev_scene_skip_table": (C.c_int, [C.c_void_p, _P(C.c_uint32), _P(C.c_uint32), C.c_uint32, C.c_int]),
     # (renderer, out captures): hipGraphs the renderer has instantiated (csrc/rt_abi.hip; tests/test_gpu_scene_update.py)
     "rt_dev_renderer_graph_captures": (C.c_int, [C.c_void_p, _P(C.c_uint32)]),
     # (count, nk[count], klo[count x 4 x 3], khi[count x 4 x 3], out nodes[64 B x count], out ok[count]): the host quantiser on padded boxes

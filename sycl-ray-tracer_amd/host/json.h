@@ -110,6 +110,9 @@ class JsonParser {
         char* end = nullptr;
         double v = std::strtod(s_.c_str() + p_, &end);
         if (end == s_.c_str() + p_) fail("bad value");
+        // "-0" without fraction or exponent is an INTEGER in the reference's JSON library (nlohmann: int64 0), so it reads as +0.0 there;
+        // "-0.0" and "-0e0" are floats and keep their sign. Every other integer spelling converts to the double strtod gives.
+        if (v == 0.0 && std::string(s_.c_str() + p_, (size_t)(end - (s_.c_str() + p_))).find_first_of(".eE") == std::string::npos) v = 0.0;
         p_ = (size_t)(end - s_.c_str());
         Json j;
         j.kind = Json::Number;

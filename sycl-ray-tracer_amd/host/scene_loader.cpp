@@ -95,22 +95,34 @@ Glb read_glb(const std::string& path) {
     std::vector<uint8_t> b((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
     auto u32 = [&](size_t o) { return (uint32_t)b[o] | ((uint32_t)b[o + 1] << 8) | ((uint32_t)b[o + 2] << 16) | ((uint32_t)b[o + 3] << 24); };
     if (b.size() < 20 || u32(0) != 0x46546C67u || u32(4) != 2u) throw std::runtime_error("Failed to load .glTF : not a GLB v2 file");
-    const size_t total = std::min<size_t>(u32(8), b.size());
+    // what the reference's parser refuses is refused here too (tinygltf's LoadBinaryFromMemory): a length field past the end of the file,
+    // and a BIN chunk whose length is no multiple of 4
+    if (u32(8) > b.size()) throw std::runtime_error("Failed to load .glTF : GLB length runs past the end of the file");
+    const size_t total = u32(8);
     Glb g;
     size_t off = 12;
     bool have_json = false;
     while (off + 8 <= total) {
         const uint32_t len = u32(off), type = u32(off + 4);
-        if (off + 8 + (size_t)len > b.size()) throw std::runtime_error("Failed to load .glTF : truncated chunk");
+        if (off + 8 + (size_t)len > total) throw std::runtime_error("Failed to load .glTF : truncated chunk");
         if (type == 0x4E4F534Au) {
             g.js = JsonParser(std::string((const char*)b.data() + off + 8, len)).parse();
             have_json = true;
         } else if (type == 0x004E4942u) {
+            if (len % 4) throw std::runtime_error("Failed to load .glTF : BIN chunk length is not a multiple of 4");
             g.bin.assign(b.begin() + (long)off + 8, b.begin() + (long)off + 8 + len);
         }
         off += 8 + (size_t)len;
     }
     if (!have_json) throw std::runtime_error("Failed to load .glTF : no JSON chunk");
+    if (!g.js.is_object()) throw std::runtime_error("glTF: the JSON root is not an object");
+    // buffers[0] is the first byteLength bytes of the BIN chunk (tinygltf's ParseBuffer): a longer buffer is refused, and padding after
+    // it is no part of the data an accessor may reach
+    if (g.js.has("buffers") && g.js.at("buffers").size() > 0 && g.js.at("buffers").at(0).has("byteLength")) {
+        const Json& len = g.js.at("buffers").at(0).at("byteLength");
+        if (!len.is_number() || !(len.num >= 0.0 && len.num <= (double)g.bin.size())) throw std::runtime_error("glTF: buffer is longer than the BIN chunk");
+        g.bin.resize((size_t)len.num);
+    }
     return g;
 }
 
@@ -135,20 +147,25 @@ struct View {
     const uint8_t* base;
     size_t stride, count;
     int comp, ncomp;
+    bool normalized;
 };
-View accessor(const Glb& g, int index) {
+View accessor(const Glb& g, int index, bool packed = false) {
     const Json& acc = g.js.at("accessors").at((size_t)index);
+    // the reference reads the accessor's bufferView and nothing else (src/scene.cpp:280-287): sparse substitution is not done there, and an
+    // accessor without a view indexes bufferViews[-1]
+    if (acc.has("sparse") || !acc.has("bufferView")) throw std::runtime_error("glTF: sparse accessors are not supported");
     const Json& bv = g.js.at("bufferViews").at((size_t)acc.int_or("bufferView", 0));
     View v;
     v.comp = acc.int_or("componentType", 0);
     v.ncomp = type_count(acc.at("type").str);
+    v.normalized = acc.has("normalized") && acc.at("normalized").kind == Json::Bool && acc.at("normalized").b;
     // every number is validated against the BIN chunk's size BEFORE it is cast, and the range check is written without
     // sums or products that could wrap around in size_t (count = 2^61 with stride 8 used to pass)
     const size_t size = g.bin.size();
     v.count = acc.size_or("count", 0, size);
     const size_t off_bv = bv.size_or("byteOffset", 0, size), off_acc = acc.size_or("byteOffset", 0, size);
     const size_t elem = comp_size(v.comp) * (size_t)v.ncomp;
-    const size_t bs = bv.size_or("byteStride", 0, size);
+    const size_t bs = packed ? 0 : bv.size_or("byteStride", 0, size);
     v.stride = bs ? bs : elem;
     if (off_bv > size - off_acc) throw std::runtime_error("glTF: accessor out of bounds");
     const size_t start = off_bv + off_acc;
@@ -158,7 +175,7 @@ View accessor(const Glb& g, int index) {
     return v;
 }
 void read_floats(const View& v, int ncomp, std::vector<float>& out) {
-    if (v.comp != 5126 || v.ncomp != ncomp) throw std::runtime_error("glTF: POSITION/NORMAL/TEXCOORD_0 must be float");
+    if (v.comp != 5126 || v.ncomp != ncomp || v.normalized) throw std::runtime_error("glTF: POSITION/NORMAL/TEXCOORD_0 must be float");
     for (size_t i = 0; i < v.count; ++i) {
         float tmp[4];
         std::memcpy(tmp, v.base + i * v.stride, sizeof(float) * (size_t)ncomp);
@@ -248,7 +265,7 @@ LoadedScene load_glb(const std::string& path, bool verbose) {
             m.type = RT_MAT_DIELECTRIC, m.tex_kind = RT_TEX_COLOR;
             m.color[0] = m.color[1] = m.color[2] = 0.8f;
             m.roughness = 0.0f;
-            m.ior = (float)ext.at("KHR_materials_ior").number_or("ior", 1.5);
+            m.ior = (float)ext.at("KHR_materials_ior").number_or("ior", 0.0); // a missing number reads as 0 upstream (a null Value's GetNumberAsDouble, :214)
             if (verbose) std::printf("Dielectric: ior=%g\n", m.ior);
         } else {
             m.type = metallic > (double)0.01f ? RT_MAT_METALLIC : RT_MAT_DIFFUSE; // double vs float-literal compare, as src/scene.cpp:219
@@ -288,7 +305,7 @@ LoadedScene load_glb(const std::string& path, bool verbose) {
             const View vp = accessor(g, at.int_or("POSITION", 0)), vn = accessor(g, at.int_or("NORMAL", 0)), vt = accessor(g, at.int_or("TEXCOORD_0", 0));
             if (vn.count != vp.count || vt.count != vp.count) throw std::runtime_error("glTF: attribute counts differ");
             read_floats(vp, 3, sc.positions), read_floats(vn, 3, sc.normals), read_floats(vt, 2, sc.uvs);
-            const View vi = accessor(g, p.int_or("indices", 0));
+            const View vi = accessor(g, p.int_or("indices", 0), true); // read packed whatever the view's byteStride says (src/scene.cpp:374-395)
             if (vi.ncomp != 1 || vi.count % 3) throw std::runtime_error("glTF: indices must be a SCALAR triangle list");
             pr.indices.resize(vi.count);
             for (size_t k = 0; k < vi.count; ++k) {
@@ -352,11 +369,14 @@ LoadedScene load_glb(const std::string& path, bool verbose) {
         if (depth > 256) throw std::runtime_error("glTF: node hierarchy too deep (cycle?)");
         const Json& n = nodes.at(ni);
         float t[3] = {0, 0, 0}, q[4] = {0, 0, 0, 1}, s[3] = {1, 1, 1};
-        if (n.has("translation") && n.at("translation").size() == 3) for (int k = 0; k < 3; ++k) t[k] = (float)n.at("translation").at((size_t)k).num;
-        if (n.has("rotation") && n.at("rotation").size() == 4) for (int k = 0; k < 4; ++k) q[k] = (float)n.at("rotation").at((size_t)k).num;
-        if (n.has("scale") && n.at("scale").size() == 3) for (int k = 0; k < 3; ++k) s[k] = (float)n.at("scale").at((size_t)k).num;
+        // tinygltf's ParseNode reads T / R / S only where `matrix` is absent or no array of numbers: a node that has both is its matrix alone
+        bool has_matrix = n.has("matrix") && n.at("matrix").is_array();
+        for (size_t k = 0; has_matrix && k < n.at("matrix").size(); ++k) has_matrix = n.at("matrix").at(k).is_number();
+        if (!has_matrix && n.has("translation") && n.at("translation").size() == 3) for (int k = 0; k < 3; ++k) t[k] = (float)n.at("translation").at((size_t)k).num;
+        if (!has_matrix && n.has("rotation") && n.at("rotation").size() == 4) for (int k = 0; k < 4; ++k) q[k] = (float)n.at("rotation").at((size_t)k).num;
+        if (!has_matrix && n.has("scale") && n.at("scale").size() == 3) for (int k = 0; k < 3; ++k) s[k] = (float)n.at("scale").at((size_t)k).num;
         M4 mm = identity();
-        if (n.has("matrix") && n.at("matrix").size() == 16)
+        if (has_matrix && n.at("matrix").size() == 16)
             for (int k = 0; k < 16; ++k) mm.m[k] = (float)n.at("matrix").at((size_t)k).num;
         recs[ni].local = mul(mul(mul(translate(t), from_quat(q)), scale(s)), mm); // ((T * R) * S) * matrix, the identity included (:18-21)
         recs[ni].parent = parent, recs[ni].loaded = true;
@@ -414,8 +434,9 @@ LoadedScene load_glb(const std::string& path, bool verbose) {
         for (int k = 0; k < 3; ++k) d[k] = v[k] + ((uv[k] * qw) + uuv[k]) * 2.0f;
         const float inv = 1.0f / std::sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);
         for (int k = 0; k < 3; ++k) sc.camera_direction[k] = d[k] * inv, sc.camera_position[k] = g.m[12 + k];
-        const double yfov = js.at("cameras").at((size_t)cn.int_or("camera", 0)).at("perspective").number_or("yfov", 0.8);
-        sc.camera_focal_length = (float)(1.0 / std::tan(yfov / 2.0));
+        // float yfov = (double); focal = 1.0f / glm::tan(yfov / 2.0f), the C library's float tangent (:123-127)
+        const float yfov = (float)js.at("cameras").at((size_t)cn.int_or("camera", 0)).at("perspective").number_or("yfov", 0.8);
+        sc.camera_focal_length = 1.0f / std::tan(yfov / 2.0f);
         sc.has_camera = true;
     } else if (sc.name == "triangle") {
         const float p[3] = {-3.9f, 0.244f, 0.218f}, d[3] = {1.0f, 0.0f, 0.0f};

@@ -297,30 +297,59 @@ _COMP = {5120: np.int8, 5121: np.uint8, 5122: np.int16, 5123: np.uint16, 5125: n
 _NCOMP = {"SCALAR": 1, "VEC2": 2, "VEC3": 3, "VEC4": 4, "MAT4": 16}
 
 
+def _not_json(name):
+    raise ValueError(f"JSON parse error: {name} is not JSON")
+
+
 def read_glb(path) -> tuple[dict, bytes]:
+    """The JSON document and buffer 0 of a GLB. What the reference's parser (tinygltf) refuses is refused here too: a bad magic, a length
+    field past the end of the file, text that is not JSON (NaN and Infinity included), a root that is no object, a BIN chunk whose length is
+    no multiple of 4, and a buffer longer than the BIN chunk. Buffer 0 is the first byteLength bytes of the chunk, as there."""
     b = Path(path).read_bytes()
+    if len(b) < 20:
+        raise ValueError(f"{path}: not a GLB v2 file")
     magic, version, length = struct.unpack_from("<III", b, 0)
     if magic != 0x46546C67 or version != 2:
         raise ValueError(f"{path}: not a GLB v2 file")
+    if length > len(b):
+        raise ValueError(f"{path}: GLB length runs past the end of the file")
     off, js, bin_chunk = 12, None, b""
-    while off < length:
+    while off + 8 <= length:
         clen, ctype = struct.unpack_from("<II", b, off)
+        if off + 8 + clen > length:
+            raise ValueError(f"{path}: truncated chunk")
         data = b[off + 8: off + 8 + clen]
         if ctype == 0x4E4F534A:
-            js = json.loads(data)
+            js = json.loads(data, parse_constant=_not_json)
         elif ctype == 0x004E4942:
+            if clen % 4:
+                raise ValueError(f"{path}: BIN chunk length is not a multiple of 4")
             bin_chunk = data
         off += 8 + clen
+    if not isinstance(js, dict):
+        raise ValueError(f"{path}: the JSON root is not an object")
+    if js.get("buffers") and "byteLength" in js["buffers"][0]:
+        if not 0 <= js["buffers"][0]["byteLength"] <= len(bin_chunk):
+            raise ValueError(f"{path}: buffer is longer than the BIN chunk")
+        bin_chunk = bin_chunk[: int(js["buffers"][0]["byteLength"])]
     return js, bin_chunk
 
 
-def _accessor(js, blob, i) -> np.ndarray:
+def _accessor(js, blob, i, floats: int | None = None, packed: bool = False) -> np.ndarray:
+    """The elements of accessor i by the reference's pointer-and-stride rule (src/scene.cpp:280-353): data at accessor.byteOffset +
+    view.byteOffset, the view's byteStride where it has one. floats = 2 / 3: the accessor must be a plain float VEC2 / VEC3, which is what the
+    reference reads whatever the accessor says; packed: the view's byteStride is not looked at (the index list, :374-395). Sparse accessors,
+    which the reference reads as if they were not sparse, are refused."""
     acc = js["accessors"][i]
+    if "sparse" in acc or "bufferView" not in acc:
+        raise ValueError("glTF: sparse accessors are not supported")
     view = js["bufferViews"][acc["bufferView"]]
     dt = np.dtype(_COMP[acc["componentType"]])
     nc = _NCOMP[acc["type"]]
+    if floats is not None and (dt != np.float32 or nc != floats or acc.get("normalized") is True):
+        raise ValueError("glTF: POSITION/NORMAL/TEXCOORD_0 must be float")
     start = view.get("byteOffset", 0) + acc.get("byteOffset", 0)
-    stride = view.get("byteStride", 0) or dt.itemsize * nc
+    stride = (0 if packed else view.get("byteStride", 0)) or dt.itemsize * nc
     out = np.zeros((acc["count"], nc), dt)
     for k in range(acc["count"]):
         out[k] = np.frombuffer(blob, dt, nc, start + k * stride)
@@ -332,6 +361,13 @@ DEFAULT_CAMERAS = {
     "triangle": CameraPose((-3.9, 0.244, 0.218), (1.0, 0.0, 0.0), 1.0),
     "cube": CameraPose((0.0, 0.0, 0.0), (0.0, 0.0, -1.0), 1.0),
 }
+
+
+def _tanf(x) -> np.float32:
+    """the C library's float tangent, which glm::tan(float) is (numpy's own float32 tangent may round differently)"""
+    fn = C.CDLL(None).tanf
+    fn.restype, fn.argtypes = C.c_float, [C.c_float]
+    return f32(fn(float(x)))
 
 
 def camera_direction_of(g: np.ndarray):
@@ -391,8 +427,8 @@ def load_glb(path, name: str | None = None) -> SceneDesc:
         if "baseColorTexture" in pbr:
             tex_layer = js["textures"][pbr["baseColorTexture"]["index"]]["source"]
         if "KHR_materials_ior" in ext and "KHR_materials_transmission" in ext:
-            m = Material(abi.RT_MAT_DIELECTRIC, ior=ext["KHR_materials_ior"].get("ior", 1.5))
-        elif f32(metallic) > f32(0.01):
+            m = Material(abi.RT_MAT_DIELECTRIC, ior=ext["KHR_materials_ior"].get("ior", 0.0))  # a missing number reads as 0 upstream (:214)
+        elif float(metallic) > float(f32(0.01)):  # the double factor against the float literal 0.01f, compared in double (:219)
             m = Material(abi.RT_MAT_METALLIC, tuple(base[:3]), tex_layer, emissive, rough)
         else:
             m = Material(abi.RT_MAT_DIFFUSE, tuple(base[:3]), tex_layer, emissive)
@@ -404,10 +440,10 @@ def load_glb(path, name: str | None = None) -> SceneDesc:
         prims = []
         for p in gm["primitives"]:
             a = p["attributes"]
-            pos = _accessor(js, blob, a["POSITION"]).astype(f32)
-            nrm = _accessor(js, blob, a["NORMAL"]).astype(f32)
-            uv = _accessor(js, blob, a["TEXCOORD_0"]).astype(f32)
-            idx = _accessor(js, blob, p["indices"]).astype(np.uint32).reshape(-1, 3)
+            pos = _accessor(js, blob, a["POSITION"], floats=3)
+            nrm = _accessor(js, blob, a["NORMAL"], floats=3)
+            uv = _accessor(js, blob, a["TEXCOORD_0"], floats=2)
+            idx = _accessor(js, blob, p["indices"], packed=True).astype(np.uint32).reshape(-1, 3)
             prims.append((sb.add_mesh(pos, nrm, uv, idx), material_for(p.get("material", -1))))
         meshes.append(prims)
 
@@ -416,13 +452,18 @@ def load_glb(path, name: str | None = None) -> SceneDesc:
     extras = scene.get("extras", {})
     if isinstance(extras.get("sky_color"), list) and len(extras["sky_color"]) == 3:
         sb.sky = np.array(extras["sky_color"], f32)
-    if isinstance(extras.get("sky_strength"), (int, float)):
+    if isinstance(extras.get("sky_strength"), (int, float)) and not isinstance(extras["sky_strength"], bool):
         sb.sky = (sb.sky * f32(extras["sky_strength"])).astype(f32)
 
     def local(n) -> np.ndarray:
         """Node::local_matrix (src/scene.cpp:18-21): ((T * R) * S) * matrix, the identity `matrix` of a TRS node included"""
-        m = trs(n.get("translation", (0, 0, 0)), n.get("rotation", (0, 0, 0, 1)), n.get("scale", (1, 1, 1)))
-        return mat4_mul(m, np.array(n["matrix"], f32) if "matrix" in n else mat4_identity())
+        number = lambda v: isinstance(v, (int, float)) and not isinstance(v, bool)
+        # tinygltf's ParseNode reads T / R / S only where `matrix` is absent or no array of numbers: a node that has both is its matrix alone;
+        # load_node takes each field only at its proper size (:458-469)
+        has_matrix = isinstance(n.get("matrix"), list) and all(number(v) for v in n["matrix"])
+        field = lambda k, size, default: n[k] if not has_matrix and isinstance(n.get(k), list) and len(n[k]) == size and all(number(v) for v in n[k]) else default
+        m = trs(field("translation", 3, (0, 0, 0)), field("rotation", 4, (0, 0, 0, 1)), field("scale", 3, (1, 1, 1)))
+        return mat4_mul(m, np.array(n["matrix"], f32) if has_matrix and len(n["matrix"]) == 16 else mat4_identity())
 
     order = []  # instances are attached in NODE INDEX order (src/scene.cpp:101-106)
     cam = None
@@ -457,8 +498,8 @@ def load_glb(path, name: str | None = None) -> SceneDesc:
 
     if cam is not None:
         n, g = nodes[cam], global_of(cam)
-        yfov = js["cameras"][n["camera"]]["perspective"]["yfov"]
-        sb.camera = CameraPose(tuple(float(v) for v in g[12:15]), camera_direction_of(g), float(f32(1.0 / math.tan(yfov / 2.0))))
+        yfov = f32(js["cameras"][n["camera"]]["perspective"]["yfov"])  # float yfov = (double); 1.0f / glm::tan(yfov / 2.0f) (:123-127)
+        sb.camera = CameraPose(tuple(float(v) for v in g[12:15]), camera_direction_of(g), float(f32(f32(1.0) / _tanf(f32(yfov / f32(2.0))))))
     elif name in DEFAULT_CAMERAS:
         sb.camera = DEFAULT_CAMERAS[name]
     return sb.build()

@@ -123,13 +123,8 @@ def test_loader_error_paths(hostlib, tmp_path):
 
 
 def _craft_glb(path, js, bin_chunk=b""):
-    import json
-    import struct
-    j = json.dumps(js).encode() if not isinstance(js, bytes) else js
-    j += b" " * (-len(j) % 4)
-    b = bin_chunk + b"\0" * (-len(bin_chunk) % 4)
-    body = struct.pack("<II", len(j), 0x4E4F534A) + j + (struct.pack("<II", len(b), 0x004E4942) + b if b else b"")
-    path.write_bytes(struct.pack("<4sII", b"glTF", 2, 12 + len(body)) + body)
+    from test_ref_gltf import glb_bytes  # the container writer lives with the crafted files of tests/test_ref_gltf.py
+    path.write_bytes(glb_bytes(js, bin_chunk))
 
 
 def test_loader_rejects_numbers_that_would_wrap_the_bounds_checks(hostlib, tmp_path):

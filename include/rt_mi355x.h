@@ -879,6 +879,14 @@ int rt_probe_scatter(rt_scene* scene, uint32_t material, uint32_t n, const float
  * mismatches[0], mismatches[1] = inputs on which they differ. The arithmetic contract requires both to be 0. ~1 s. */
 int rt_probe_rounding(int device, uint64_t* mismatches);
 
+/* The origin skip's per-ray test on n rays: ray i (org, dir: 3n floats) is tested against entry i of `entries` (8 words each, the
+ * layout of a scene's skip table: child word, normal, first vertex, two half thresholds). word_device receives the word the render kernels would
+ * keep for the ray — the entry's child word, or the no-match word 1 — computed by a kernel that reads the entry as they do; word_host the
+ * same function compiled for the host, as the host walk (rt_scene_count_visits mode 4) applies it. Either output may be NULL. device < 0: the host
+ * form alone, no device call (word_device must be NULL). The two must agree on every input, NaN, infinities and subnormals included. */
+int rt_probe_origin_skip(int device, uint32_t n, const uint32_t* entries, const float* org, const float* dir,
+                         uint32_t* word_device, uint32_t* word_host);
+
 const char* rt_last_error(void);
 int rt_abi_version(void);
 /* Number of HIP devices visible, or a negative rt_status. */

@@ -1,6 +1,6 @@
 // rt_bounce.h — one bounce of a path after its closest-hit query, as the render kernels (rt_kernels.h) and the path queries (rt_path_query.hip)
 // run it: the ray's direction out of its half storage, shade_bounce and the Russian roulette. (Apart from rt_kernels.h, which defines the
-// renderers' kernels and belongs to rt_frame.hip alone.)
+// renderers' kernels and belongs to rt_frame.hip alone. rt_probe_kernels.h reads it for skip_entry, the origin skip's entry load.)
 #pragma once
 #include "rt_device.h"
 
@@ -35,12 +35,17 @@ RT_DEV bool shade_bounce(const SceneDev& S, uint32_t& rng, RayState& r, const Hi
 // traversed; the word goes to the lane's LDS slot above its stack, where trav_inner<true> reads it. One 32-byte entry per bounce ray, loaded
 // by every lane (a lane without a triangle reads entry 0 and keeps kSkipNone): no exec-mask region of its own.
 RT_DEV void origin_skip_none(const TravStack& stack) { *lds_at(skip_word_addr(stack)) = (int32_t)kSkipNone; }
-RT_DEV void origin_skip(const SceneDev& S, uint32_t tri, const Trav& T, const TravStack& stack) {
-    const u32x4* ep = reinterpret_cast<const u32x4*>(S.skip + (tri == kNoTri ? 0u : tri));
+// one entry out of memory: two 16-byte loads and their words (origin_skip below and k_probe_origin_skip, rt_probe_kernels.h, read it this way)
+RT_DEV SkipRec skip_entry(const SkipRec* at) {
+    const u32x4* ep = reinterpret_cast<const u32x4*>(at);
     const u32x4 a = ep[0], b = ep[1];
     SkipRec e;
     e.ref = a.x, e.n[0] = __uint_as_float(a.y), e.n[1] = __uint_as_float(a.z), e.n[2] = __uint_as_float(a.w);
     e.p[0] = __uint_as_float(b.x), e.p[1] = __uint_as_float(b.y), e.p[2] = __uint_as_float(b.z), e.a = b.w;
+    return e;
+}
+RT_DEV void origin_skip(const SceneDev& S, uint32_t tri, const Trav& T, const TravStack& stack) {
+    const SkipRec e = skip_entry(S.skip + (tri == kNoTri ? 0u : tri));
     const float o[3] = {T.o.x, T.o.y, T.o.z}, d[3] = {T.d.x, T.d.y, T.d.z};
     const uint32_t w = origin_skip_word(e, o, d);
     *lds_at(skip_word_addr(stack)) = (int32_t)(tri == kNoTri ? kSkipNone : w);

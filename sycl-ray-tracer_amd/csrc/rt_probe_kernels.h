@@ -1,7 +1,7 @@
 // rt_probe_kernels.h — the kernels behind rt_intersect_batch and the rt_probe_* entry points (rt_probes.hip is the one translation unit that
 // includes this header).
 #pragma once
-#include "rt_device.h"
+#include "rt_bounce.h"
 
 namespace rt {
 
@@ -67,5 +67,15 @@ __global__ void __launch_bounds__(256) k_probe_scatter(SceneDev S, uint32_t mate
     seed_out[i] = st;
 }
 
+// The origin skip's per-ray test (rt_bounce.h: origin_skip; rt_types.h: origin_skip_word) on entries and rays the caller supplies: ray i reads
+// entry i as the render kernels read theirs (skip_entry) and stores the word they would put above the lane's stack.
+__global__ void __launch_bounds__(256) k_probe_origin_skip(uint32_t n, const SkipRec* __restrict__ entries, const float* __restrict__ org,
+                                                            const float* __restrict__ dir, uint32_t* __restrict__ word) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const SkipRec e = skip_entry(entries + i);
+    const float o[3] = {org[3 * i], org[3 * i + 1], org[3 * i + 2]}, d[3] = {dir[3 * i], dir[3 * i + 1], dir[3 * i + 2]};
+    word[i] = origin_skip_word(e, o, d);
+}
 
 } // namespace rt

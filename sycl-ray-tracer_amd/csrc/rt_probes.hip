@@ -116,4 +116,36 @@ int rt_probe_scatter(rt_scene* s, uint32_t material, uint32_t n, const float* di
     return RT_OK;
 }
 
+int rt_probe_origin_skip(int device, uint32_t n, const uint32_t* entries, const float* org, const float* dir, uint32_t* word_device,
+                         uint32_t* word_host) {
+    if (!entries || !org || !dir || n == 0) return fail(RT_ERR_INVALID, "bad arguments");
+    if (word_host)
+        for (uint32_t i = 0; i < n; ++i) {
+            SkipRec e;
+            std::memcpy(&e, entries + 8 * (size_t)i, sizeof e);
+            word_host[i] = origin_skip_word(e, org + 3 * (size_t)i, dir + 3 * (size_t)i);
+        }
+    if (device < 0) { // the host form alone: no device call
+        if (word_device) return fail(RT_ERR_INVALID, "device < 0 runs the host form only: word_device must be NULL");
+        return RT_OK;
+    }
+    if (!word_device) return RT_OK;
+    int rc = device_ok(device);
+    if (rc != RT_OK) return rc;
+    DevBuf b_ent, b_org, b_dir, b_word;
+    HIPCHK(b_ent.alloc((size_t)n * sizeof(SkipRec)));
+    HIPCHK(b_org.alloc((size_t)n * 12));
+    HIPCHK(b_dir.alloc((size_t)n * 12));
+    HIPCHK(b_word.alloc((size_t)n * 4));
+    HIPCHK(hipMemcpy(b_ent.p, entries, (size_t)n * sizeof(SkipRec), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(b_org.p, org, (size_t)n * 12, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(b_dir.p, dir, (size_t)n * 12, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_probe_origin_skip, dim3((n + 255u) / 256u), dim3(256), 0, 0, n, b_ent.as<SkipRec>(), b_org.as<float>(), b_dir.as<float>(),
+                       b_word.as<uint32_t>());
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(word_device, b_word.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
 } // extern "C"

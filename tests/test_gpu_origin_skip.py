@@ -3,7 +3,12 @@ descend into the flat subtree a bounce ray starts on. The cull must be exact, so
 holds the fp32 frame, the unorm8 image and the ray count against the brute-force CPU oracle, bit for bit: scenes where the skip takes
 much (two-triangle walls), where it must let a ray through to a surface a hair away (gaps around kTNear), where |n . d| straddles the
 threshold (a grazing camera), where rays start on a face and go INWARD (glass), where nothing is coplanar (a column), with forced pixel
-slices, and on the scenes whose table holds only the no-match word (updatable, before and after an update; built on the device)."""
+slices, and on the scenes whose table holds only the no-match word (updatable, before and after an update; built on the device); where
+the first term of the test refuses half the rays of a wave and most entries name a node fetched from memory (a shallow bowl and dome),
+where the distance term decides (a turned room far from the origin), with node counts in and just past the band the two skip kernels stage
+no longer (floors of 28 x 28 and 32 x 32 cells). And because a frame cannot show WHICH word a ray got — the tilt test and the near bound
+protect the same rays — rt_probe_origin_skip compares the device's word with the host's on the rays of every case, on rays crafted onto both
+compares and on entries no scene holds. The scenes live in tests/test_origin_skip.py, which checks without a GPU that they are worth rendering."""
 import ctypes as C
 import re
 
@@ -12,84 +17,12 @@ import pytest
 
 from rtamd import abi, scenes
 from rtamd.renderer import Camera, MegakernelRenderer, Scene, WavefrontRenderer
-from rtamd.scenes import CameraPose, Material, SceneBuilder, mesh_box, mesh_cylinder, mesh_quad, trs
+from rtamd.scenes import trs
+from test_origin_skip import CASES, build_case, crafted_rays, planes_scene, probe, room_scene, synthetic_cases
 
 pytestmark = pytest.mark.gpu
 W, H, SPP, DEPTH = 64, 48, 8, 6
 SKIP_NONE = 1
-
-
-def _room(sb, light=True):
-    """a box room of two-triangle walls (each wall's leaf is the whole wall), open to the camera at +z"""
-    white = sb.add_material(Material(abi.RT_MAT_DIFFUSE, (0.73, 0.73, 0.73)))
-    red = sb.add_material(Material(abi.RT_MAT_DIFFUSE, (0.65, 0.05, 0.05)))
-    metal = sb.add_material(Material(abi.RT_MAT_METALLIC, (0.9, 0.85, 0.7), roughness=0.1))
-    q = lambda *a, **k: sb.add_mesh(*mesh_quad(*a, **k))
-    sb.add_instance(q((-1, -1, 1), (1, -1, 1), (1, -1, -1), (-1, -1, -1)), white)
-    sb.add_instance(q((-1, 1, -1), (1, 1, -1), (1, 1, 1), (-1, 1, 1)), white)
-    sb.add_instance(q((-1, -1, -1), (1, -1, -1), (1, 1, -1), (-1, 1, -1)), metal)
-    sb.add_instance(q((-1, -1, 1), (-1, -1, -1), (-1, 1, -1), (-1, 1, 1)), red)
-    sb.add_instance(q((1, -1, -1), (1, -1, 1), (1, 1, 1), (1, 1, -1)), white)
-    if light:
-        lamp = sb.add_material(Material(abi.RT_MAT_DIFFUSE, (0.78, 0.78, 0.78), emissive=(15.0, 15.0, 15.0)))
-        sb.add_instance(q((-0.25, 0.995, -0.25), (0.25, 0.995, -0.25), (0.25, 0.995, 0.25), (-0.25, 0.995, 0.25)), lamp)
-    sb.camera = CameraPose((0.0, 0.0, 3.4), (0.0, 0.0, -1.0), 2.0)
-    return white
-
-
-def room_scene():
-    sb = SceneBuilder("room")
-    _room(sb)
-    return sb.build()
-
-
-def planes_scene(gap):
-    """a floor tessellated 6 x 6 and a second sheet `gap` above its middle: a ray that leaves the floor must still find the sheet"""
-    sb = SceneBuilder(f"planes_{gap}")
-    white = _room(sb)
-    blue = sb.add_material(Material(abi.RT_MAT_DIFFUSE, (0.1, 0.2, 0.8)))
-    sb.add_instance(sb.add_mesh(*mesh_quad((-0.9, -0.9, 0.9), (0.9, -0.9, 0.9), (0.9, -0.9, -0.9), (-0.9, -0.9, -0.9), nx=6, ny=6)), white)
-    y = -0.9 + gap
-    sb.add_instance(sb.add_mesh(*mesh_quad((-0.5, y, 0.5), (0.5, y, 0.5), (0.5, y, -0.5), (-0.5, y, -0.5), nx=3, ny=3)), blue)
-    sb.camera = CameraPose((0.0, 0.6, 3.0), (0.0, -0.45, -1.0), 2.0)
-    return sb.build()
-
-
-def grazing_scene():
-    """the camera looks along a tessellated floor at under 1 degree: mirror-like bounces leave it with |n . d| around the entries' thresholds"""
-    sb = SceneBuilder("grazing")
-    gloss = sb.add_material(Material(abi.RT_MAT_METALLIC, (0.9, 0.9, 0.9), roughness=0.02))
-    white = sb.add_material(Material(abi.RT_MAT_DIFFUSE, (0.7, 0.7, 0.7)))
-    sb.add_instance(sb.add_mesh(*mesh_quad((-4, 0, 4), (4, 0, 4), (4, 0, -4), (-4, 0, -4), nx=8, ny=8)), gloss)
-    sb.add_instance(sb.add_mesh(*mesh_quad((-4, 0, -4), (4, 0, -4), (4, 3, -4), (-4, 3, -4), nx=2, ny=2)), white)
-    sb.camera = CameraPose((0.0, 0.03, 3.9), (0.0, -0.008, -1.0), 1.2)  # atan(0.008) = 0.46 degrees
-    return sb.build()
-
-
-def slab_scene():
-    sb = SceneBuilder("slab")
-    _room(sb)
-    glass = sb.add_material(Material(abi.RT_MAT_DIELECTRIC, ior=1.5))
-    sb.add_instance(sb.add_mesh(*mesh_box()), glass, trs((0.0, -0.2, 0.0), s=(0.6, 0.5, 0.08)))
-    return sb.build()
-
-
-def column_scene():
-    sb = SceneBuilder("column")
-    white = _room(sb)
-    sb.add_instance(sb.add_mesh(*mesh_cylinder(24, 6, radius=0.35, height=1.9)), white, trs((0.0, -0.98, 0.0)))
-    return sb.build()
-
-
-CASES = {
-    "room": room_scene,
-    "planes_5e-5": lambda: planes_scene(5e-5),
-    "planes_2e-4": lambda: planes_scene(2e-4),
-    "planes_1e-3": lambda: planes_scene(1e-3),
-    "grazing": grazing_scene,
-    "slab": slab_scene,
-    "column": column_scene,
-}
 
 
 def _oracle_frames(oracle, sd):
@@ -181,26 +114,126 @@ def test_a_device_built_tree_skips_nothing_and_renders_the_same(rtlib, devlib, o
         scene.close()
 
 
-def test_the_device_takes_the_skip(rtlib, monkeypatch, capfd):
+def test_the_device_takes_the_skip(rtlib, devlib, monkeypatch, capfd):
     """A frame that matches the oracle says nothing about whether the skip is taken. The instrumented instantiations (RT_KERNEL_STATS=1)
     count node visits and triangle tests per ray: the same scene built static (with its table) and updatable (no-match words only) traces
-    the same rays, and the static one must visit fewer nodes and test fewer triangles."""
-    sd = planes_scene(1e-3)
-    cam = Camera.for_scene(sd, (W, H))
+    the same rays, and the static one must visit fewer nodes and test fewer triangles — on the sheets a hair apart, on the bowl from above
+    (bowl_down: 70 % of the first bounces skip a node that is fetched from memory) and, in triangle tests, on the bowl from its low camera
+    (the first term refuses a fifth of the rays) and in the far room (the distance term refuses one in eleven). Node visits there:
+      far_300  12 triangles under 2 nodes, every entry names a LEAF: there is no node visit to save, the visits must be the same;
+      bowl     the renderers' own bounces leave the bowl at |n . d| = 0.2 .. 0.6, under the node entries' a0 = 0.79: they skip leaves only
+               (on the host walk of that camera's mirror bounces 6 node visits of 51,100 are saved), which the report's two decimals
+               cannot show — the visits must not be more."""
     monkeypatch.setenv("RT_KERNEL_STATS", "1")
-    for cls in (MegakernelRenderer, WavefrontRenderer):
-        seen = {}
-        for updatable in (False, True):
-            scene = Scene(sd, device=0, updatable=updatable)
-            try:
-                r = cls(scene, (W, H), DEPTH, SPP)
-                fr = r.render_frame(cam)
-                r.close()
-            finally:
-                scene.close()
-            m = re.findall(r"per ray: ([0-9.]+) inner \(.*?\), ([0-9.]+) tri", capfd.readouterr().err)
-            assert m, "no [rt stats] report"
-            seen[updatable] = (fr.rays, float(m[-1][0]), float(m[-1][1]))
-        print(cls.__name__, "rays, node visits, triangle tests per ray: with the table", seen[False], "without", seen[True])
-        assert seen[False][0] == seen[True][0]
-        assert seen[False][1] < seen[True][1] and seen[False][2] < seen[True][2]
+    for name in ("planes_1e-3", "bowl_down", "bowl", "far_300"):
+        sd = CASES[name]()
+        cam = Camera.for_scene(sd, (W, H))
+        words = _skip_words(devlib, sd)
+        leaves_only = bool(np.all((words == SKIP_NONE) | ((words & 0x80000000) != 0)))
+        assert leaves_only == (name == "far_300")
+        for cls in (MegakernelRenderer, WavefrontRenderer):
+            seen = {}
+            for updatable in (False, True):
+                scene = Scene(sd, device=0, updatable=updatable)
+                try:
+                    r = cls(scene, (W, H), DEPTH, SPP)
+                    fr = r.render_frame(cam)
+                    r.close()
+                finally:
+                    scene.close()
+                m = re.findall(r"per ray: ([0-9.]+) inner \(.*?\), ([0-9.]+) tri", capfd.readouterr().err)
+                assert m, "no [rt stats] report"
+                seen[updatable] = (fr.rays, float(m[-1][0]), float(m[-1][1]))
+            with capfd.disabled():
+                print(name, cls.__name__, "rays, node visits, triangle tests per ray: with the table", seen[False], "without", seen[True])
+            assert seen[False][0] == seen[True][0]
+            assert seen[False][2] < seen[True][2]
+            if leaves_only:
+                assert seen[False][1] == seen[True][1]
+            elif name == "bowl":
+                assert seen[False][1] <= seen[True][1]
+            else:
+                assert seen[False][1] < seen[True][1]
+
+
+@pytest.fixture(scope="module")
+def far_300(oracle):
+    sd = CASES["far_300"]()
+    return sd, _oracle_frames(oracle, sd)
+
+
+def test_the_far_room_in_forced_slices(rtlib, far_300):
+    """lanes that change rays inside a launch, where the distance term decides"""
+    sd, want = far_300
+    scene = Scene(sd, device=0)
+    try:
+        _hold(scene, sd, want, slices=4)
+    finally:
+        scene.close()
+
+
+def test_the_far_room_continued(rtlib, far_300):
+    """a progressive frame of 4 samples continued by 4 is the oracle's frame of 8, rays summed over the two calls"""
+    sd, want = far_300
+    cam = Camera.for_scene(sd, (W, H))
+    scene = Scene(sd, device=0)
+    try:
+        for cls, kind in ((WavefrontRenderer, abi.RT_RENDERER_WAVEFRONT), (MegakernelRenderer, abi.RT_RENDERER_MEGAKERNEL)):
+            r = cls(scene, (W, H), DEPTH, SPP // 2)
+            r.set_progressive(True)
+            first = r.render_frame(cam)
+            fr = r.continue_frame(SPP - SPP // 2)
+            total = r.accumulated_samples
+            r.close()
+            f, b, rays = want[kind]
+            assert total == SPP and first.rays + fr.rays == rays, f"{cls.__name__}: {first.rays} + {fr.rays} rays, the oracle {rays}"
+            bad = int((fr.rgba_f32 != f).any(-1).sum())
+            assert bad == 0, f"{cls.__name__}: {bad} pixels differ from the oracle"
+            assert np.array_equal(fr.rgba_f32, f) and np.array_equal(fr.rgba_u8, b)
+    finally:
+        scene.close()
+
+
+# ---- the device's word is the host's word (rt_probe_origin_skip: the render kernels' entry read and origin_skip_word, against the host's) -----
+@pytest.fixture(scope="module")
+def cases(devlib):
+    """every case built host only by the developer library, with its table and the bounce rays of a 64 x 48 camera chain on the host walk"""
+    cache = {}
+
+    def get(name):
+        if name not in cache:
+            cache[name] = build_case(devlib, name)
+        return cache[name]
+
+    return get
+
+
+@pytest.mark.parametrize("name", list(CASES))
+def test_the_devices_word_is_the_hosts_on_the_rays_of_a_case(rtlib, cases, name):
+    c = cases(name)
+    dev, host = probe(rtlib, c["words"][c["start"]], c["org"], c["dirs"], device=0)
+    print(f"{name}: {host.size} rays, {int((host != SKIP_NONE).sum())} skip, {int((dev != host).sum())} differ")
+    assert 0.2 < np.mean(host != SKIP_NONE) < 0.8
+    np.testing.assert_array_equal(dev, host)
+
+
+@pytest.mark.parametrize("name", list(CASES))
+def test_the_devices_word_is_the_hosts_on_rays_crafted_onto_the_compares(rtlib, cases, name):
+    """|n . d| within 4 ulp of the threshold, and of |d|_1 / 256: the float64 model is no judge here, only the host's word is, bit for bit
+    (tests/test_origin_skip.py holds that both compares come out both ways on these rays)"""
+    e, o, d, second = crafted_rays(cases(name))
+    dev, host = probe(rtlib, e, o, d, device=0)
+    print(f"{name}: {host.size} rays, {int((host != SKIP_NONE).sum())} skip, {int((dev != host).sum())} differ")
+    np.testing.assert_array_equal(dev, host)
+
+
+def test_the_devices_word_is_the_hosts_on_entries_no_scene_holds(rtlib):
+    """half-subnormal thresholds (flushed to zero they would let a ray skip), the largest half and half infinity, NaN and infinities in every
+    component of o, d, n and p, -0.0, subnormal directions, |d|_1 past the fp32 range: the word exact arithmetic gives, from both"""
+    e, o, d, want = synthetic_cases()
+    dev, host = probe(rtlib, e, o, d, device=0)
+    np.testing.assert_array_equal(host, want)
+    np.testing.assert_array_equal(dev, host)
+    only_dev = np.full(want.size, 7, np.uint32)  # either output may be NULL
+    abi.check(rtlib.rt_probe_origin_skip(0, want.size, abi.u32ptr(e), abi.fptr(o), abi.fptr(d), abi.u32ptr(only_dev), None))
+    np.testing.assert_array_equal(only_dev, want)

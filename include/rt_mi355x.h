@@ -368,7 +368,50 @@ int rt_gather_paths_device(rt_scene* scene, const rt_gather_query* q, void* stre
  * W * H * max_repeats >= 2^31, samples == 0, max_depth == 0, repeats == 0, repeats > max_repeats, dilate > 16. After these,
  * rt_lightmap_create returns RT_ERR_NO_DEVICE for a host-only scene.
  * Limits: a texel is its centre (no conservative rasterisation, no supersampling inside a texel); there is no chart packer and no reading of
- * a second UV set from a file; one device. */
+ * a second UV set from a file; one device. A filtered lightmap (below) is biased: it trades variance for blur across shadow edges narrower
+ * than a texel's noise.
+ *
+ * Lightmap filtering, for a lightmap created by rt_lightmap_create_ex with RT_LIGHTMAP_FILTER (rt_lightmap_create is rt_lightmap_create_ex
+ * with flags 0: the same allocation, the same behaviour; an unknown flag is RT_ERR_INVALID). The `repeats` entries of a texel are independent
+ * estimates, so their spread is an unbiased variance of the texel's mean, and the texel's world position and shading normal (step 2) are the
+ * edge-stopping guides of an a-trous filter in texel space: texels that are neighbours in the world filter together whichever chart they lie
+ * on, texels that are neighbours only in the atlas do not. lum, dot, exp_m, coefficient, h[5], k3[3] and the 1e-8f are rt_denoise_guided's;
+ * every operation is one R1 fp32 operation, left to right as bracketed, never contracted.
+ * rt_lightmap_bake_filtered[_device] are rt_lightmap_bake's steps 1 to 7 with two steps between 5 and 6:
+ *   5a. Variance. A sampled texel with entries r_k (k = 0 .. R-1, R = repeats): l_k = lum(r_k); m = (the sum of l_k in order from +0) / (float)R;
+ *       s = the sum of (l_k - m) * (l_k - m) in order from +0; var = s / ((float)R * (float)(R - 1)): the variance of the texel's mean luminance.
+ *       R = 1: var = 0. Not sampled: var = 0.
+ *   5b. Filter. The mask M is "sampled". For i = 0 .. iterations-1 with step s = 2^i, at every texel p = (x, y) in M:
+ *       a. g_p = G / K. G sums (k3[dy+1] * k3[dx+1]) * var_q and K the same kernel weights, both from +0 over dy = -1 .. 1 (outer), dx = -1 .. 1
+ *          (inner), over the taps q = (x + dx, y + dy) that lie inside the atlas and in M: nothing is clamped, nothing is scaled by the step,
+ *          and the centre is always in, so K >= 1/4. kl_p = 1 / (sigma_luminance * sqrt(g_p) + 1e-8f).
+ *       b. The taps are q = (x + s*dx, y + s*dy), dy = -2 .. 2 (outer), dx = -2 .. 2 (inner); a tap outside the atlas or not in M is skipped.
+ *          E = (fabs(l_p - l_q) * kl_p + dot(N_p - N_q) * kn_i) + dot(P_p - P_q) * kx, l = lum(L), kn_i = ldexp(kn, -2i), kn and kx the
+ *          coefficients of sigma_normal and sigma_position; a term whose coefficient is 0 is left out, and E starts at +0. With
+ *          sigma_luminance = +inf step a and the luminance term are left out. w = (h[dy+2] * h[dx+2]) * exp_m(-E).
+ *       c. In tap order: S += w * L_q, Wsum += w, V += (w * w) * var_q; then L' = S / Wsum, var' = V / (Wsum * Wsum). L and var are linear
+ *          radiance throughout: no square and no square root anywhere.
+ *       A texel outside M stays (0, 0, 0) with var 0 and contributes to nothing. After the last iteration alpha is 1 on M and 0 elsewhere, and
+ *       the dilation (step 6) runs on the filtered plane. out_variance (W*H floats; may be NULL) is var' on M and 0 elsewhere, filled texels
+ *       included.
+ *   With iterations == 0, or with the filter parameters NULL, out_rgba and the stats are rt_lightmap_bake's bit for bit and out_variance is 5a's.
+ * rt_lightmap_filter[_device] are step 5b alone on the caller's planes: rgba W*H*4 floats, variance W*H floats (NULL only with sigma_luminance
+ * = +inf: the variance is then 0 throughout). M is "rgba's alpha == 1.0f, the texel has an owner, and its six guide floats are finite". The
+ * guides are the lightmap's own: the call runs steps 1 and 2 first, so a call after rt_scene_update sees the moved geometry, and it records
+ * the scene's per-stream event as rt_lightmap_texels_device does. A texel outside M comes out (0, 0, 0, 0) with variance 0; there is no
+ * dilation; iterations == 0 copies (alpha 1 on M, zeros elsewhere). out_rgba may alias rgba; nothing else may alias. out_variance may be NULL.
+ * The 3 x 3 variance prefilter of step a has no guides: where two charts touch in the atlas it mixes the variances of both sides into g_p,
+ * which scales the luminance term there and moves no radiance across (a gutter of one texel between charts keeps it apart).
+ * Non-finite radiance or variance does what the arithmetic gives, as in rt_denoise_guided: the filter does not clamp (a NaN or negative
+ * variance under a texel's 3 x 3 window makes kl_p NaN, every weight of that texel 0 and the texel NaN; an infinite radiance spreads as NaN).
+ * RT_LIGHTMAP_FILTER adds 56 bytes per texel to the lightmap's buffers, allocated at creation like the others: two float4 guide planes,
+ * position with the mask in .w and normal (32: a tap is two aligned 16-byte loads beside its colour, whose .w carries the variance between
+ * iterations), and the host forms' staging, an rgba plane (16) and a variance plane in and out (4 + 4).
+ * Refused with RT_ERR_INVALID, before any HIP call and before the handle is looked at: iterations > 10; a sigma that is NaN or below 1e-6;
+ * rt_lightmap_bake_filtered with iterations > 0, a finite sigma_luminance and repeats < 2 (one entry has no noise estimate);
+ * rt_lightmap_filter with variance NULL and a finite sigma_luminance. Then: a lightmap created without RT_LIGHTMAP_FILTER.
+ * The four calls are serialised by the lightmap's event as the others are; the host forms run on the lightmap's stream and synchronise, the
+ * device forms (device pointers, 16-byte aligned planes) enqueue on `stream` and return. */
 typedef struct rt_lightmap rt_lightmap;
 typedef struct rt_lightmap_params { uint32_t samples, max_depth, rr_start, repeats, seed, dilate; } rt_lightmap_params; /* 24 bytes */
 typedef struct rt_lightmap_stats  { uint32_t covered, sampled, filled, reserved; uint64_t rays; } rt_lightmap_stats;    /* 24 bytes */
@@ -378,6 +421,23 @@ int  rt_lightmap_texels(rt_lightmap* lm, uint32_t* tri, float* pos, float* norma
 int  rt_lightmap_texels_device(rt_lightmap* lm, void* d_tri, void* d_pos, void* d_normal, void* stream);  /* device arrays, enqueues    */
 int  rt_lightmap_bake(rt_lightmap* lm, const rt_lightmap_params* p, float* out_rgba, rt_lightmap_stats* stats);
 int  rt_lightmap_bake_device(rt_lightmap* lm, const rt_lightmap_params* p, void* d_out_rgba, void* d_stats, void* stream);
+#define RT_LIGHTMAP_FILTER 1u
+typedef struct rt_lightmap_filter_params {
+    uint32_t iterations;    /* 0 .. 10; 0 = no filter                                              */
+    float sigma_luminance;  /* in standard deviations; >= 1e-6, +inf = term off                    */
+    float sigma_normal;     /* >= 1e-6, +inf = off                                                 */
+    float sigma_position;   /* world units; >= 1e-6, +inf = off                                    */
+} rt_lightmap_filter_params; /* 16 bytes */
+int  rt_lightmap_create_ex(rt_scene* scene, int32_t width, int32_t height, uint32_t max_repeats, const float* lm_uv, uint32_t flags,
+                           rt_lightmap** out);
+int  rt_lightmap_bake_filtered(rt_lightmap* lm, const rt_lightmap_params* p, const rt_lightmap_filter_params* f, float* out_rgba,
+                               float* out_variance, rt_lightmap_stats* stats);
+int  rt_lightmap_bake_filtered_device(rt_lightmap* lm, const rt_lightmap_params* p, const rt_lightmap_filter_params* f, void* d_out_rgba,
+                                      void* d_out_variance, void* d_stats, void* stream);
+int  rt_lightmap_filter(rt_lightmap* lm, const rt_lightmap_filter_params* f, const float* rgba, const float* variance, float* out_rgba,
+                        float* out_variance);
+int  rt_lightmap_filter_device(rt_lightmap* lm, const rt_lightmap_filter_params* f, const void* d_rgba, const void* d_variance,
+                               void* d_out_rgba, void* d_out_variance, void* stream);
 
 /* ---- Renderers: == IRenderer implementations (src/render.hpp:11-18) ------------------------ */
 enum {

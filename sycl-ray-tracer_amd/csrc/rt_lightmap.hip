@@ -1,11 +1,18 @@
-// rt_lightmap.hip — lightmap baking: rt_lightmap_create / _destroy, rt_lightmap_texels[_device], rt_lightmap_bake[_device] and their kernels.
+// rt_lightmap.hip — lightmap baking: rt_lightmap_create[_ex] / _destroy, rt_lightmap_texels[_device], rt_lightmap_bake[_device], and for a
+// lightmap created with RT_LIGHTMAP_FILTER rt_lightmap_bake_filtered[_device] and rt_lightmap_filter[_device], and their kernels.
 // The atlas-side half of a lightmap bake around one gather query (rt_path_gather.hip, called through its public entry point): which triangle
 // owns a texel (k_lm_owner), where the texel lies on it and with which shading normal, and the states of its entries (k_lm_texels), the mean
 // of the entries' radiances (k_lm_resolve) and the filling of the gutters (k_lm_dilate). The arithmetic is the contract stated at
 // rt_lightmap_bake in include/rt_mi355x.h; the numpy model that pins it bit for bit is tests/test_lightmap.py. No traversal, no LDS, no
 // float atomics in this unit: the owner plane is an integer minimum, the statistics are ballots and integer sums.
+// The filter (the contract's steps 5a and 5b, the model tests/test_lightmap_filter.py): k_lm_resolve_var is k_lm_resolve with the variance of
+// the texel's mean in .w and the two guide planes, k_lm_atrous one a-trous iteration in texel space, one launch per iteration, the kernel
+// boundary the only hand-off, in rt_image_op.h's 64 x 4 tile shape. Its tap loop is this unit's own: the mask is a plane (.w of the position
+// guide), the variance prefilter is renormalised over the mask, the values are linear and there is no albedo. The helpers it is made of
+// (exp_m, dot_diff, luminance, kTapH, kPreK, coefficient) are rt_atrous_pixel.h's and its includes', read from there.
 #include "rt_internal.h"
 #include "rt_device.h"
+#include "rt_atrous_pixel.h"
 
 struct rt_lightmap {
     rt_scene* scene = nullptr;
@@ -23,6 +30,13 @@ struct rt_lightmap {
     float* d_rad = nullptr;          // 3 floats per entry
     uint32_t* d_rays = nullptr;      // per entry
     float4* d_plane[2] = {nullptr, nullptr};
+    uint32_t flags = 0;              // RT_LIGHTMAP_*
+    // RT_LIGHTMAP_FILTER: the guide planes (position with the mask in .w, normal) and the host forms' staging
+    float4* d_gpos = nullptr;
+    float4* d_gnrm = nullptr;
+    float4* d_host_rgba = nullptr;
+    float* d_host_var_in = nullptr;
+    float* d_host_var_out = nullptr;
     rt_lightmap_stats* d_stats = nullptr;
     hipStream_t stream = nullptr;    // the host forms run here
     hipEvent_t ev_last = nullptr;    // recorded behind every call: the next call's stream waits for it
@@ -240,11 +254,173 @@ __global__ void __launch_bounds__(kLmStatBlock) k_lm_dilate(const float4* __rest
     if (COUNT && threadIdx.x == 0 && n_filled) atomicAdd(&stats->filled, n_filled);
 }
 
+// ---- the filter (RT_LIGHTMAP_FILTER) ---------------------------------------------------------------------------------------------------------
+// k_lm_resolve with step 5a: the same dealing of texels and the same statistics; .w of the output is the variance of the texel's mean
+// luminance (0 where not sampled, and for one repeat), not alpha: the mask goes to .w of the position guide, 1 where sampled. The guides are
+// the texel's first entry's.
+__global__ void __launch_bounds__(kLmStatBlock) k_lm_resolve_var(const uint32_t* __restrict__ owner, const float* __restrict__ rad,
+                                                                  const uint32_t* __restrict__ rays, const float* __restrict__ pos,
+                                                                  const float* __restrict__ nrm, uint32_t n, uint32_t repeats,
+                                                                  float4* __restrict__ out, float4* __restrict__ gpos, float4* __restrict__ gnrm,
+                                                                  rt_lightmap_stats* __restrict__ stats) {
+    uint32_t n_cov = 0, n_smp = 0;
+    unsigned long long traced = 0;
+    for (uint32_t j = 0; j < kLmLaneTexels; ++j) {
+        const uint32_t i = blockIdx.x * kLmWaveTexels + j * kLmStatBlock + threadIdx.x; // below 2^26 + kLmWaveTexels
+        bool covered = false, sampled = false;
+        if (i < n) {
+            covered = owner[i] != kNoTri;
+            bool rejected = false;
+            for (uint32_t k = 0; k < repeats; ++k) {
+                const uint32_t r = rays[i * repeats + k];
+                if (r == 0xFFFFFFFFu) rejected = true;
+                else traced += r;
+            }
+            sampled = covered && !rejected;
+            float4 o = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            if (sampled) {
+                const float d = (float)repeats;
+                float tx = 0.0f, ty = 0.0f, tz = 0.0f, tl = 0.0f;
+                for (uint32_t k = 0; k < repeats; ++k) {
+                    const float* r = rad + 3 * (size_t)(i * repeats + k);
+                    tx = tx + r[0], ty = ty + r[1], tz = tz + r[2];
+                    tl = tl + luminance(make_float4(r[0], r[1], r[2], 0.0f));
+                }
+                float var = 0.0f;
+                if (repeats > 1) {
+                    const float m = tl / d;
+                    float s = 0.0f;
+                    for (uint32_t k = 0; k < repeats; ++k) {
+                        const float* r = rad + 3 * (size_t)(i * repeats + k);
+                        const float dl = luminance(make_float4(r[0], r[1], r[2], 0.0f)) - m;
+                        s = s + dl * dl;
+                    }
+                    var = s / (d * (float)(repeats - 1u));
+                }
+                o = make_float4(tx / d, ty / d, tz / d, var);
+            }
+            out[i] = o;
+            const float* p = pos + 3 * (size_t)(i * repeats);
+            const float* q = nrm + 3 * (size_t)(i * repeats);
+            gpos[i] = make_float4(p[0], p[1], p[2], sampled ? 1.0f : 0.0f);
+            gnrm[i] = make_float4(q[0], q[1], q[2], 0.0f);
+        }
+        n_cov += lm_count(covered), n_smp += lm_count(sampled);
+    }
+    for (int off = 32; off > 0; off >>= 1) traced += __shfl_xor(traced, off, 64);
+    if (threadIdx.x == 0) {
+        if (n_cov) atomicAdd(&stats->covered, n_cov);
+        if (n_smp) atomicAdd(&stats->sampled, n_smp);
+        if (traced) atomicAdd((unsigned long long*)&stats->rays, traced);
+    }
+}
+
+// rt_lightmap_filter's planes from the caller's: one thread per texel. In M (alpha 1, an owner, six finite guide floats): rgb with the variance
+// in .w (0 without a variance plane); else zeros. The guides are k_lm_texels' for one repeat. `out` may be `rgba`: a thread reads its texel first.
+__global__ void __launch_bounds__(kLmBlock) k_lm_filter_in(const float4* rgba, const float* __restrict__ var, const uint32_t* __restrict__ owner,
+                                                            const float* __restrict__ pos, const float* __restrict__ nrm, uint32_t n, float4* out,
+                                                            float4* __restrict__ gpos, float4* __restrict__ gnrm) {
+    const uint32_t i = blockIdx.x * kLmBlock + threadIdx.x;
+    if (i >= n) return;
+    const float4 c = rgba[i];
+    const float* p = pos + 3 * (size_t)i;
+    const float* q = nrm + 3 * (size_t)i;
+    const bool in = c.w == 1.0f && owner[i] != kNoTri && __builtin_isfinite(p[0]) && __builtin_isfinite(p[1]) && __builtin_isfinite(p[2]) &&
+                    __builtin_isfinite(q[0]) && __builtin_isfinite(q[1]) && __builtin_isfinite(q[2]);
+    out[i] = in ? make_float4(c.x, c.y, c.z, var ? var[i] : 0.0f) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    gpos[i] = make_float4(p[0], p[1], p[2], in ? 1.0f : 0.0f);
+    gnrm[i] = make_float4(q[0], q[1], q[2], 0.0f);
+}
+
+// What leaves the filter: alpha in .w again (1 on M, where the plane's .w is the variance; outside M the plane is zeros) and the variance plane
+// (may be null). The whole filter for iterations = 0, and the last lines of k_lm_atrous<true>.
+RT_DEV void lm_filter_out(uint32_t p, float4 c, bool in, float4* __restrict__ out, float* __restrict__ out_var) {
+    out[p] = make_float4(c.x, c.y, c.z, in ? 1.0f : 0.0f);
+    if (out_var) out_var[p] = c.w;
+}
+__global__ void __launch_bounds__(kLmBlock) k_lm_filter_copy(const float4* __restrict__ in, const float4* __restrict__ gpos, uint32_t n,
+                                                              float4* __restrict__ out, float* __restrict__ out_var) {
+    const uint32_t i = blockIdx.x * kLmBlock + threadIdx.x;
+    if (i < n) lm_filter_out(i, in[i], gpos[i].w != 0.0f, out, out_var);
+}
+
+// One iteration of step 5b with step `step` at the thread's texel (tile_pixel: a wave is one row of 64 consecutive texels). in: rgb with the
+// variance in .w, zeros outside M; gpos: position, .w the mask; gnrm: normal, not read where kn is 0. use_l: the luminance term is on (sigma_l
+// finite), scaled by the 3 x 3 prefilter of the variance at p over the taps in M. LAST: alpha instead of the variance in out.w, the variance to
+// out_var (may be null). A texel outside M writes zeros and leaves, so a wave whose row holds none ends at its first branch: the exit of an
+// empty tile needs no ballot of its own. EARLY = false (the developer build's RT_LM_FILTER_NO_EARLY_EXIT, for the probe's comparison): such
+// a texel walks its taps like the others and writes its zeros at the end.
+template <bool LAST, bool EARLY = true>
+__global__ void __launch_bounds__(256) k_lm_atrous(const float4* __restrict__ in, const float4* __restrict__ gpos, const float4* __restrict__ gnrm,
+                                                    int32_t W, int32_t H, int32_t step, int32_t use_l, float sigma_l, float kn, float kx,
+                                                    float4* __restrict__ out, float* __restrict__ out_var) {
+    int32_t x, y;
+    if (!tile_pixel(W, H, &x, &y)) return;
+    const int32_t p = y * W + x;
+    const float4 Pp = gpos[p];
+    if (EARLY && Pp.w == 0.0f) {
+        out[p] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        if (LAST && out_var) out_var[p] = 0.0f;
+        return;
+    }
+    const float4 Lp = in[p];
+    const float4 Np = kn != 0.0f ? gnrm[p] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    const float lp = luminance(Lp);
+    float kl = 0.0f;
+    if (use_l) {
+        float g = 0.0f, ks = 0.0f;
+#pragma unroll
+        for (int dy = -1; dy <= 1; ++dy) {
+            const int32_t qy = y + dy;
+            if (qy < 0 || qy >= H) continue;
+#pragma unroll
+            for (int dx = -1; dx <= 1; ++dx) {
+                const int32_t qx = x + dx;
+                if (qx < 0 || qx >= W) continue;
+                const int32_t q = qy * W + qx;
+                if (gpos[q].w == 0.0f) continue;
+                const float k = kPreK[dy + 1] * kPreK[dx + 1];
+                g = g + k * in[q].w;
+                ks = ks + k;
+            }
+        }
+        kl = 1.0f / (sigma_l * __builtin_sqrtf(g / ks) + kLumEps);
+    }
+    float sx = 0.0f, sy = 0.0f, sz = 0.0f, sv = 0.0f, wsum = 0.0f;
+#pragma unroll
+    for (int dy = -2; dy <= 2; ++dy) {
+        const int32_t qy = y + step * dy;
+        if (qy < 0 || qy >= H) continue;
+#pragma unroll
+        for (int dx = -2; dx <= 2; ++dx) {
+            const int32_t qx = x + step * dx;
+            if (qx < 0 || qx >= W) continue;
+            const int32_t q = qy * W + qx;
+            const float4 Pq = gpos[q];
+            if (Pq.w == 0.0f) continue;
+            const float4 Lq = in[q];
+            float E = 0.0f;
+            if (use_l) E = E + __builtin_fabsf(lp - luminance(Lq)) * kl;
+            if (kn != 0.0f) E = E + dot_diff(Np, gnrm[q]) * kn;
+            if (kx != 0.0f) E = E + dot_diff(Pp, Pq) * kx;
+            const float w = (kTapH[dy + 2] * kTapH[dx + 2]) * exp_m(-E);
+            sx = sx + w * Lq.x, sy = sy + w * Lq.y, sz = sz + w * Lq.z;
+            wsum = wsum + w;
+            sv = sv + (w * w) * Lq.w;
+        }
+    }
+    float4 c = make_float4(sx / wsum, sy / wsum, sz / wsum, sv / (wsum * wsum));
+    if (!EARLY && Pp.w == 0.0f) c = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (LAST) lm_filter_out((uint32_t)p, c, Pp.w != 0.0f, out, out_var);
+    else out[p] = c;
+}
+
 } // namespace rt
 
 namespace {
 
-static_assert(sizeof(rt_lightmap_stats) == 24 && sizeof(rt_lightmap_params) == 24, "include/rt_mi355x.h states both sizes");
+static_assert(sizeof(rt_lightmap_stats) == 24 && sizeof(rt_lightmap_params) == 24 && sizeof(rt_lightmap_filter_params) == 16,
+              "include/rt_mi355x.h states the sizes");
 
 constexpr int32_t kMaxAtlas = 8192;
 constexpr uint32_t kMaxDilate = 16;
@@ -364,14 +540,136 @@ int bake_check(const rt_lightmap* lm, const rt_lightmap_params* p, const void* o
     return RT_OK;
 }
 
+// ---- the filter's calls (RT_LIGHTMAP_FILTER) -------------------------------------------------------------------------------------------------
+// (the entry points judge the parameters first: they need no lightmap)
+int check_filter_params(const rt_lightmap_filter_params* f) {
+    if (f->iterations > kMaxIterations) return fail(RT_ERR_INVALID, "iterations must be 0 .. 10");
+    const float s[3] = {f->sigma_luminance, f->sigma_normal, f->sigma_position};
+    for (float v : s)
+        if (!(v >= kMinSigma)) return fail(RT_ERR_INVALID, "every sigma must be at least 1e-6 (+inf ignores its guide); NaN is refused");
+    return RT_OK;
+}
+
+int check_filter_flag(const rt_lightmap* lm) {
+    if (!(lm->flags & RT_LIGHTMAP_FILTER)) return fail(RT_ERR_INVALID, "the lightmap was created without RT_LIGHTMAP_FILTER (rt_lightmap_create_ex)");
+    return RT_OK;
+}
+
+// f null: no filter (rt_lightmap_bake_filtered's identity)
+int bake_filtered_check(const rt_lightmap* lm, const rt_lightmap_params* p, const rt_lightmap_filter_params* f, const void* out) {
+    if (const int rc = check_params(p)) return rc;
+    if (f) {
+        if (const int rc = check_filter_params(f)) return rc;
+        if (f->iterations > 0 && !std::isinf(f->sigma_luminance) && p->repeats < 2)
+            return fail(RT_ERR_INVALID, "a finite sigma_luminance needs repeats >= 2: one entry per texel has no noise estimate");
+    }
+    if (!lm || !out) return fail(RT_ERR_INVALID, "null argument");
+    if (const int rc = check_filter_flag(lm)) return rc;
+    if (p->repeats > lm->max_repeats) return fail(RT_ERR_INVALID, "repeats exceeds the max_repeats the lightmap was created with");
+    return RT_OK;
+}
+
+int filter_check(const rt_lightmap* lm, const rt_lightmap_filter_params* f, const void* rgba, const void* var, const void* out) {
+    if (!f) return fail(RT_ERR_INVALID, "null parameters");
+    if (const int rc = check_filter_params(f)) return rc;
+    if (!var && !std::isinf(f->sigma_luminance)) return fail(RT_ERR_INVALID, "variance may be null only with sigma_luminance = +inf");
+    if (!lm || !rgba || !out) return fail(RT_ERR_INVALID, "null argument");
+    return check_filter_flag(lm);
+}
+
+// the plane the filter's result lies in where it stays in the lightmap: the last launch reads d_plane[(iters - 1) & 1], or d_plane[0] without one
+uint32_t filtered_plane(const rt_lightmap_filter_params* f) { return f && f->iterations ? (f->iterations & 1u) : 1u; }
+
+// Step 5b on st: the iterations from d_plane[0] (rgb, variance) and the guide planes, ping-pong through the two planes, the last into dst with
+// alpha and into out_var (may be null). dst is none of the lightmap's planes, or d_plane[filtered_plane(f)]. PRE: the call's bracket is open
+int enqueue_filter(rt_lightmap* lm, const rt_lightmap_filter_params* f, float4* dst, float* out_var, hipStream_t st) {
+    const int32_t W = lm->width, H = lm->height;
+    const uint32_t n = (uint32_t)W * (uint32_t)H, iters = f ? f->iterations : 0u;
+    if (iters == 0) {
+        hipLaunchKernelGGL(k_lm_filter_copy, dim3((n + kLmBlock - 1u) / kLmBlock), dim3(kLmBlock), 0, st, (const float4*)lm->d_plane[0],
+                           (const float4*)lm->d_gpos, n, dst, out_var);
+        HIPCHK(hipGetLastError());
+        return RT_OK;
+    }
+    const int32_t use_l = std::isinf(f->sigma_luminance) ? 0 : 1;
+    const float kn = coefficient(f->sigma_normal), kx = coefficient(f->sigma_position);
+    auto last_kernel = k_lm_atrous<true>;
+    auto other_kernel = k_lm_atrous<false>;
+#ifdef RT_DEVELOPER_KNOBS
+    if (dev_knob("RT_LM_FILTER_NO_EARLY_EXIT")) last_kernel = k_lm_atrous<true, false>, other_kernel = k_lm_atrous<false, false>;
+#endif
+    for (uint32_t i = 0; i < iters; ++i) {
+        const bool last = i + 1 == iters;
+        hipLaunchKernelGGL(last ? last_kernel : other_kernel, tile_grid(W, H), tile_block(), 0, st, (const float4*)lm->d_plane[i & 1u],
+                           (const float4*)lm->d_gpos, (const float4*)lm->d_gnrm, W, H, 1 << i, use_l, f->sigma_luminance,
+                           std::ldexp(kn, -2 * (int)i), kx, last ? dst : lm->d_plane[(i + 1u) & 1u], last ? out_var : (float*)nullptr);
+        HIPCHK(hipGetLastError());
+    }
+    return RT_OK;
+}
+
+// rt_lightmap_bake_filtered[_device]: bake_enqueue with the resolve that keeps the variance and the guides, and the filter in front of the
+// dilation. out / result as bake_enqueue's; out_var: a device plane or null. PRE: the arguments were checked
+int bake_filtered_enqueue(rt_lightmap* lm, const rt_lightmap_params* p, const rt_lightmap_filter_params* f, float4* out, float* out_var,
+                          rt_lightmap_stats* stats, hipStream_t st, float4** result) {
+    if (const int rc = begin_call(lm, st)) return rc;
+    const int32_t W = lm->width, H = lm->height;
+    const uint32_t n = (uint32_t)W * (uint32_t)H, R = p->repeats;
+    if (const int rc = enqueue_texels(lm, R, p->seed, nullptr, lm->d_pos, lm->d_nrm, lm->d_state, st)) return rc;
+    rt_gather_query q{};
+    q.n = n * R, q.max_depth = p->max_depth, q.samples = p->samples, q.rr_start = p->rr_start;
+    q.pos = lm->d_pos, q.normal = lm->d_nrm, q.rng = lm->d_state, q.rng_out = nullptr, q.radiance = lm->d_rad, q.rays = lm->d_rays;
+    if (const int rc = rt_gather_paths_device(lm->scene, &q, st)) return rc; // records the scene's event for st behind k_lm_texels too
+    HIPCHK(hipSetDevice(lm->device));
+    rt_lightmap_stats* d_stats = stats ? stats : lm->d_stats;
+    HIPCHK(hipMemsetAsync(d_stats, 0, sizeof(rt_lightmap_stats), st));
+    const uint32_t fp = filtered_plane(f);
+    float4* last = out ? out : lm->d_plane[(fp + p->dilate) & 1u];
+    const dim3 grid((n + kLmWaveTexels - 1u) / kLmWaveTexels), block(kLmStatBlock);
+    hipLaunchKernelGGL(k_lm_resolve_var, grid, block, 0, st, (const uint32_t*)lm->d_owner, (const float*)lm->d_rad, (const uint32_t*)lm->d_rays,
+                       (const float*)lm->d_pos, (const float*)lm->d_nrm, n, R, lm->d_plane[0], lm->d_gpos, lm->d_gnrm, d_stats);
+    HIPCHK(hipGetLastError());
+    if (const int rc = enqueue_filter(lm, f, p->dilate ? lm->d_plane[fp] : last, out_var, st)) return rc;
+    for (uint32_t j = 0; j < p->dilate; ++j) {
+        const float4* src = lm->d_plane[(fp + j) & 1u];
+        if (j + 1 == p->dilate) hipLaunchKernelGGL(k_lm_dilate<true>, grid, block, 0, st, src, W, H, last, d_stats);
+        else hipLaunchKernelGGL(k_lm_dilate<false>, grid, block, 0, st, src, W, H, lm->d_plane[(fp + j + 1u) & 1u], d_stats);
+        HIPCHK(hipGetLastError());
+    }
+    if (result) *result = last;
+    return end_call(lm, st);
+}
+
+// rt_lightmap_filter[_device]: the lightmap's guides as they are now, the caller's planes cut to the mask, the filter. All pointers are device
+// pointers; var and out_var may be null. PRE: the arguments were checked
+int filter_enqueue(rt_lightmap* lm, const rt_lightmap_filter_params* f, const float4* rgba, const float* var, float4* out, float* out_var,
+                   hipStream_t st) {
+    if (const int rc = begin_call(lm, st)) return rc;
+    hipEvent_t ev = nullptr;
+    if (const int rc = scene_stream_event(lm->scene, st, &ev)) return rc;
+    if (const int rc = enqueue_texels(lm, 1u, 0u, nullptr, lm->d_pos, lm->d_nrm, nullptr, st)) return rc;
+    HIPCHK(hipEventRecord(ev, st));
+    const uint32_t n = (uint32_t)lm->width * (uint32_t)lm->height;
+    hipLaunchKernelGGL(k_lm_filter_in, dim3((n + kLmBlock - 1u) / kLmBlock), dim3(kLmBlock), 0, st, rgba, var, (const uint32_t*)lm->d_owner,
+                       (const float*)lm->d_pos, (const float*)lm->d_nrm, n, lm->d_plane[0], lm->d_gpos, lm->d_gnrm);
+    HIPCHK(hipGetLastError());
+    if (const int rc = enqueue_filter(lm, f, out, out_var, st)) return rc;
+    return end_call(lm, st);
+}
+
 } // namespace
 
 extern "C" {
 
 int rt_lightmap_create(rt_scene* s, int32_t width, int32_t height, uint32_t max_repeats, const float* lm_uv, rt_lightmap** out) {
+    return rt_lightmap_create_ex(s, width, height, max_repeats, lm_uv, 0u, out);
+}
+
+int rt_lightmap_create_ex(rt_scene* s, int32_t width, int32_t height, uint32_t max_repeats, const float* lm_uv, uint32_t flags, rt_lightmap** out) {
     if (!out) return fail(RT_ERR_INVALID, "null output pointer");
     *out = nullptr;
     if (!s) return fail(RT_ERR_INVALID, "null scene");
+    if (flags & ~RT_LIGHTMAP_FILTER) return fail(RT_ERR_INVALID, "unknown lightmap flag");
     if (width < 1 || width > kMaxAtlas || height < 1 || height > kMaxAtlas) return fail(RT_ERR_INVALID, "width and height must be 1 .. 8192");
     if (max_repeats == 0) return fail(RT_ERR_INVALID, "max_repeats must be at least 1");
     if ((uint64_t)width * (uint64_t)height * max_repeats > 0x7fffffffull)
@@ -383,16 +681,19 @@ int rt_lightmap_create(rt_scene* s, int32_t width, int32_t height, uint32_t max_
     return no_throw([&]() -> int {
         rt_lightmap* lm = new rt_lightmap;
         lm->scene = s, lm->device = s->device, lm->width = width, lm->height = height, lm->max_repeats = max_repeats, lm->n_tris = T;
-        lm->bands = lm_bands(lm_uv, T, width, height);
+        lm->bands = lm_bands(lm_uv, T, width, height), lm->flags = flags;
         const size_t n = (size_t)width * (size_t)height, e = n * max_repeats;
-        const bool copy_wv = !s->upd;
+        const bool copy_wv = !s->upd, filter = (flags & RT_LIGHTMAP_FILTER) != 0;
         if (hipMalloc((void**)&lm->d_uv, std::max<size_t>(T, 1) * 24u) != hipSuccess ||
             (copy_wv && hipMalloc((void**)&lm->d_wv, std::max<size_t>(T, 1) * 36u) != hipSuccess) ||
             hipMalloc((void**)&lm->d_owner, n * 4u) != hipSuccess || hipMalloc((void**)&lm->d_pos, e * 12u) != hipSuccess ||
             hipMalloc((void**)&lm->d_nrm, e * 12u) != hipSuccess || hipMalloc((void**)&lm->d_state, e * 4u) != hipSuccess ||
             hipMalloc((void**)&lm->d_rad, e * 12u) != hipSuccess || hipMalloc((void**)&lm->d_rays, e * 4u) != hipSuccess ||
             hipMalloc((void**)&lm->d_plane[0], n * 16u) != hipSuccess || hipMalloc((void**)&lm->d_plane[1], n * 16u) != hipSuccess ||
-            hipMalloc((void**)&lm->d_stats, sizeof(rt_lightmap_stats)) != hipSuccess) {
+            hipMalloc((void**)&lm->d_stats, sizeof(rt_lightmap_stats)) != hipSuccess ||
+            (filter && (hipMalloc((void**)&lm->d_gpos, n * 16u) != hipSuccess || hipMalloc((void**)&lm->d_gnrm, n * 16u) != hipSuccess ||
+                        hipMalloc((void**)&lm->d_host_rgba, n * 16u) != hipSuccess || hipMalloc((void**)&lm->d_host_var_in, n * 4u) != hipSuccess ||
+                        hipMalloc((void**)&lm->d_host_var_out, n * 4u) != hipSuccess))) {
             rt_lightmap_destroy(lm);
             return fail(RT_ERR_OOM, "hipMalloc of the lightmap's buffers failed");
         }
@@ -416,7 +717,8 @@ void rt_lightmap_destroy(rt_lightmap* lm) {
     if (lm->device >= 0 && hipSetDevice(lm->device) == hipSuccess) {
         if (lm->recorded) (void)hipEventSynchronize(lm->ev_last);
         for (void* p : {(void*)lm->d_uv, (void*)lm->d_wv, (void*)lm->d_owner, (void*)lm->d_pos, (void*)lm->d_nrm, (void*)lm->d_state, (void*)lm->d_rad,
-                        (void*)lm->d_rays, (void*)lm->d_plane[0], (void*)lm->d_plane[1], (void*)lm->d_stats})
+                        (void*)lm->d_rays, (void*)lm->d_plane[0], (void*)lm->d_plane[1], (void*)lm->d_stats, (void*)lm->d_gpos, (void*)lm->d_gnrm,
+                        (void*)lm->d_host_rgba, (void*)lm->d_host_var_in, (void*)lm->d_host_var_out})
             (void)hipFree(p);
         if (lm->ev_last) (void)hipEventDestroy(lm->ev_last);
         if (lm->stream) (void)hipStreamDestroy(lm->stream);
@@ -457,6 +759,49 @@ int rt_lightmap_bake(rt_lightmap* lm, const rt_lightmap_params* p, float* out_rg
 int rt_lightmap_bake_device(rt_lightmap* lm, const rt_lightmap_params* p, void* d_out_rgba, void* d_stats, void* stream) {
     if (const int rc = bake_check(lm, p, d_out_rgba)) return rc;
     return bake_enqueue(lm, p, (float4*)d_out_rgba, (rt_lightmap_stats*)d_stats, (hipStream_t)stream, nullptr);
+}
+
+int rt_lightmap_bake_filtered(rt_lightmap* lm, const rt_lightmap_params* p, const rt_lightmap_filter_params* f, float* out_rgba, float* out_variance,
+                              rt_lightmap_stats* stats) {
+    if (const int rc = bake_filtered_check(lm, p, f, out_rgba)) return rc;
+    hipStream_t st = lm->stream;
+    float4* result = nullptr;
+    if (const int rc = bake_filtered_enqueue(lm, p, f, nullptr, out_variance ? lm->d_host_var_out : nullptr, nullptr, st, &result)) return rc;
+    const size_t n = (size_t)lm->width * (size_t)lm->height;
+    HIPCHK(hipMemcpyAsync(out_rgba, result, n * 16u, hipMemcpyDeviceToHost, st));
+    if (out_variance) HIPCHK(hipMemcpyAsync(out_variance, lm->d_host_var_out, n * 4u, hipMemcpyDeviceToHost, st));
+    if (stats) HIPCHK(hipMemcpyAsync(stats, lm->d_stats, sizeof(rt_lightmap_stats), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return RT_OK;
+}
+
+int rt_lightmap_bake_filtered_device(rt_lightmap* lm, const rt_lightmap_params* p, const rt_lightmap_filter_params* f, void* d_out_rgba,
+                                     void* d_out_variance, void* d_stats, void* stream) {
+    if (const int rc = bake_filtered_check(lm, p, f, d_out_rgba)) return rc;
+    return bake_filtered_enqueue(lm, p, f, (float4*)d_out_rgba, (float*)d_out_variance, (rt_lightmap_stats*)d_stats, (hipStream_t)stream, nullptr);
+}
+
+int rt_lightmap_filter(rt_lightmap* lm, const rt_lightmap_filter_params* f, const float* rgba, const float* variance, float* out_rgba,
+                       float* out_variance) {
+    if (const int rc = filter_check(lm, f, rgba, variance, out_rgba)) return rc;
+    hipStream_t st = lm->stream;
+    if (const int rc = begin_call(lm, st)) return rc; // a _device call may still read the staging planes
+    const size_t n = (size_t)lm->width * (size_t)lm->height;
+    HIPCHK(hipMemcpyAsync(lm->d_host_rgba, rgba, n * 16u, hipMemcpyHostToDevice, st));
+    if (variance) HIPCHK(hipMemcpyAsync(lm->d_host_var_in, variance, n * 4u, hipMemcpyHostToDevice, st));
+    if (const int rc = filter_enqueue(lm, f, lm->d_host_rgba, variance ? lm->d_host_var_in : nullptr, lm->d_host_rgba,
+                                      out_variance ? lm->d_host_var_out : nullptr, st))
+        return rc;
+    HIPCHK(hipMemcpyAsync(out_rgba, lm->d_host_rgba, n * 16u, hipMemcpyDeviceToHost, st));
+    if (out_variance) HIPCHK(hipMemcpyAsync(out_variance, lm->d_host_var_out, n * 4u, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return RT_OK;
+}
+
+int rt_lightmap_filter_device(rt_lightmap* lm, const rt_lightmap_filter_params* f, const void* d_rgba, const void* d_variance, void* d_out_rgba,
+                              void* d_out_variance, void* stream) {
+    if (const int rc = filter_check(lm, f, d_rgba, d_variance, d_out_rgba)) return rc;
+    return filter_enqueue(lm, f, (const float4*)d_rgba, (const float*)d_variance, (float4*)d_out_rgba, (float*)d_out_variance, (hipStream_t)stream);
 }
 
 } // extern "C"

@@ -254,12 +254,23 @@ class rt_lightmap_stats(C.Structure):
     ]
 
 
+class rt_lightmap_filter_params(C.Structure):
+    _fields_ = [
+        ("iterations", C.c_uint32),
+        ("sigma_luminance", C.c_float),
+        ("sigma_normal", C.c_float),
+        ("sigma_position", C.c_float),
+    ]
+
+
+RT_LIGHTMAP_FILTER = 1
 RT_LIGHTMAP_MAX_SIZE = 8192
 RT_LIGHTMAP_MAX_DILATE = 16
 
 assert C.sizeof(rt_ray_query) == 72
 assert C.sizeof(rt_lightmap_params) == 24
 assert C.sizeof(rt_lightmap_stats) == 24
+assert C.sizeof(rt_lightmap_filter_params) == 16
 assert C.sizeof(rt_path_query) == 64
 assert C.sizeof(rt_gather_query) == 64
 assert C.sizeof(rt_denoise_params) == 20
@@ -295,6 +306,14 @@ PROTOTYPES = {
     "rt_lightmap_texels_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rt_lightmap_bake": (C.c_int, [C.c_void_p, _P(rt_lightmap_params), _P(C.c_float), _P(rt_lightmap_stats)]),
     "rt_lightmap_bake_device": (C.c_int, [C.c_void_p, _P(rt_lightmap_params), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_lightmap_create_ex": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_uint32, _P(C.c_float), C.c_uint32, _P(C.c_void_p)]),
+    "rt_lightmap_bake_filtered": (C.c_int, [C.c_void_p, _P(rt_lightmap_params), _P(rt_lightmap_filter_params), _P(C.c_float), _P(C.c_float),
+                                            _P(rt_lightmap_stats)]),
+    "rt_lightmap_bake_filtered_device": (C.c_int, [C.c_void_p, _P(rt_lightmap_params), _P(rt_lightmap_filter_params), C.c_void_p, C.c_void_p,
+                                                   C.c_void_p, C.c_void_p]),
+    "rt_lightmap_filter": (C.c_int, [C.c_void_p, _P(rt_lightmap_filter_params), _P(C.c_float), _P(C.c_float), _P(C.c_float), _P(C.c_float)]),
+    "rt_lightmap_filter_device": (C.c_int, [C.c_void_p, _P(rt_lightmap_filter_params), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_void_p]),
     "rt_renderer_create": (C.c_int, [C.c_int, C.c_void_p, C.c_int32, C.c_int32, C.c_uint32, C.c_uint32,
                                      C.c_uint32, _P(C.c_void_p)]),
     "rt_renderer_destroy": (None, [C.c_void_p]),

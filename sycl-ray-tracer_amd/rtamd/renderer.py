@@ -594,12 +594,31 @@ class TileComm:
             pass
 
 
+# The lightmap filter's defaults (the image filter's, kept after scripts/lightmap_filter_probe.py's sweep). sigma_position is
+# LIGHTMAP_POSITION_FRACTION of the scene's scale (Scene.scale()).
+LIGHTMAP_FILTER_ITERATIONS = 5
+LIGHTMAP_SIGMA_LUMINANCE = 4.0
+LIGHTMAP_SIGMA_NORMAL = 0.25
+LIGHTMAP_POSITION_FRACTION = 0.05
+
+
+def lightmap_filter_params(iterations: int = LIGHTMAP_FILTER_ITERATIONS, sigma_luminance: float = LIGHTMAP_SIGMA_LUMINANCE,
+                           sigma_normal: float = LIGHTMAP_SIGMA_NORMAL, sigma_position: float | None = None, scene_scale: float | None = None):
+    """rt_lightmap_filter_params; sigma_position None: LIGHTMAP_POSITION_FRACTION * scene_scale, in fp32 (scene_scale is then required)."""
+    if sigma_position is None:
+        if scene_scale is None:
+            raise ValueError("give sigma_position or scene_scale (Scene.scale())")
+        sigma_position = float(np.float32(LIGHTMAP_POSITION_FRACTION) * np.float32(scene_scale))
+    return abi.rt_lightmap_filter_params(int(iterations), float(sigma_luminance), float(sigma_normal), float(sigma_position))
+
+
 class Lightmap:
     """rt_lightmap: a width x height lightmap atlas over `scene` (include/rt_mi355x.h: rt_lightmap_bake). lm_uv: (T, 3, 2) or (T, 6)
     float32, every triangle's three lightmap UVs in the scene's triangle order (rtamd.bake.triangle_grid_uvs makes a trivial unwrap).
-    max_repeats: the most entries per texel a bake may ask for. Close it before its scene."""
+    max_repeats: the most entries per texel a bake may ask for. filter=True (RT_LIGHTMAP_FILTER): also bake_filtered and filter. Close it
+    before its scene."""
 
-    def __init__(self, scene: Scene, lm_uv: np.ndarray, width: int, height: int, max_repeats: int = 1):
+    def __init__(self, scene: Scene, lm_uv: np.ndarray, width: int, height: int, max_repeats: int = 1, filter: bool = False):
         lm_uv = np.asarray(lm_uv)
         t = scene.desc.n_triangles
         if lm_uv.shape not in ((t, 3, 2), (t, 6)):
@@ -611,7 +630,12 @@ class Lightmap:
         self.scene = scene
         self.width, self.height, self.max_repeats = int(width), int(height), int(max_repeats)
         self.h = C.c_void_p()
-        abi.check(self._lib.rt_lightmap_create(scene.h, self.width, self.height, self.max_repeats, abi.fptr(self._uv), C.byref(self.h)), self._lib)
+        if filter:
+            abi.check(self._lib.rt_lightmap_create_ex(scene.h, self.width, self.height, self.max_repeats, abi.fptr(self._uv),
+                                                      abi.RT_LIGHTMAP_FILTER, C.byref(self.h)), self._lib)
+        else:
+            abi.check(self._lib.rt_lightmap_create(scene.h, self.width, self.height, self.max_repeats, abi.fptr(self._uv), C.byref(self.h)),
+                      self._lib)
 
     def texels(self) -> dict:
         """rt_lightmap_texels: {"tri": (H, W) uint32, the owning triangle or 0xFFFFFFFF, "pos": (H, W, 3) float32, the texel centre's point on
@@ -641,6 +665,61 @@ class Lightmap:
         p = abi.rt_lightmap_params(int(samples), int(max_depth), int(rr_start), int(repeats), int(seed) & 0xFFFFFFFF, int(dilate))
         abi.check(self._lib.rt_lightmap_bake_device(self.h, C.byref(p), C.c_void_p(d_rgba or None), C.c_void_p(d_stats or None),
                                                     C.c_void_p(stream or None)), self._lib)
+
+    def _filter_params(self, params: dict):
+        """lightmap_filter_params(**params), sigma_position a fraction of the lightmap's scene where neither it nor scene_scale is given"""
+        if params.get("sigma_position") is None and params.get("scene_scale") is None:
+            params = dict(params, scene_scale=self.scene.scale())
+        return lightmap_filter_params(**params)
+
+    def bake_filtered(self, samples: int, max_depth: int, seed: int, repeats: int = 2, rr_start: int = 0, dilate: int = 0,
+                      want_variance: bool = True, **params) -> dict:
+        """rt_lightmap_bake_filtered: bake()'s dictionary with the plane filtered in front of the dilation, and "variance": (H, W) float32,
+        the variance of each sampled texel's mean luminance after the filter (None if not wanted). `params`: lightmap_filter_params'."""
+        f = self._filter_params(params)
+        p = abi.rt_lightmap_params(int(samples), int(max_depth), int(rr_start), int(repeats), int(seed) & 0xFFFFFFFF, int(dilate))
+        rgba = np.zeros((self.height, self.width, 4), np.float32)
+        var = np.zeros((self.height, self.width), np.float32) if want_variance else None
+        st = abi.rt_lightmap_stats()
+        abi.check(self._lib.rt_lightmap_bake_filtered(self.h, C.byref(p), C.byref(f), abi.fptr(rgba), abi.fptr(var) if want_variance else None,
+                                                      C.byref(st)), self._lib)
+        return {"rgba": rgba, "variance": var, "stats": {"covered": st.covered, "sampled": st.sampled, "filled": st.filled, "rays": st.rays}}
+
+    def bake_filtered_device(self, d_rgba: int, samples: int, max_depth: int, seed: int, repeats: int = 2, rr_start: int = 0, dilate: int = 0,
+                             d_variance: int = 0, d_stats: int = 0, stream: int = 0, **params) -> None:
+        """rt_lightmap_bake_filtered_device on DEVICE pointers, enqueued on `stream`: d_rgba H*W*4 floats, d_variance H*W floats or 0, d_stats
+        24 bytes or 0."""
+        f = self._filter_params(params)
+        p = abi.rt_lightmap_params(int(samples), int(max_depth), int(rr_start), int(repeats), int(seed) & 0xFFFFFFFF, int(dilate))
+        v = [C.c_void_p(x or None) for x in (d_rgba, d_variance, d_stats, stream)]
+        abi.check(self._lib.rt_lightmap_bake_filtered_device(self.h, C.byref(p), C.byref(f), *v), self._lib)
+
+    def filter(self, rgba: np.ndarray, variance: np.ndarray | None, want_variance: bool = True, out_rgba: np.ndarray | None = None,
+               **params) -> dict:
+        """rt_lightmap_filter of a (H, W, 4) float32 plane (alpha 1 = a texel to filter) with the (H, W) float32 variance of its luminance
+        (None: only with sigma_luminance = inf), guided by the lightmap's own texels: {"rgba", "variance"} (None if not wanted). out_rgba:
+        where the result goes (may be rgba). `params`: lightmap_filter_params'."""
+        shape = (self.height, self.width, 4)
+        planes = [("rgba", rgba, shape)]
+        if variance is not None:
+            planes.append(("variance", variance, shape[:2]))
+        if out_rgba is not None:
+            planes.append(("out_rgba", out_rgba, shape))
+        for name, a, want in planes:
+            if not isinstance(a, np.ndarray) or a.dtype != np.float32 or a.shape != want or not a.flags.c_contiguous:
+                raise ValueError(f"{name} must be a C-contiguous float32 array of shape {want}")
+        f = self._filter_params(params)
+        out = np.zeros(shape, np.float32) if out_rgba is None else out_rgba
+        var = np.zeros(shape[:2], np.float32) if want_variance else None
+        abi.check(self._lib.rt_lightmap_filter(self.h, C.byref(f), abi.fptr(rgba), abi.fptr(variance) if variance is not None else None,
+                                               abi.fptr(out), abi.fptr(var) if want_variance else None), self._lib)
+        return {"rgba": out, "variance": var}
+
+    def filter_device(self, d_rgba: int, d_variance: int, d_out_rgba: int, d_out_variance: int = 0, stream: int = 0, **params) -> None:
+        """rt_lightmap_filter_device on DEVICE pointers, enqueued on `stream`; d_variance 0 only with sigma_luminance = inf."""
+        f = self._filter_params(params)
+        v = [C.c_void_p(x or None) for x in (d_rgba, d_variance, d_out_rgba, d_out_variance, stream)]
+        abi.check(self._lib.rt_lightmap_filter_device(self.h, C.byref(f), *v), self._lib)
 
     def close(self):
         if self.h:

@@ -1,0 +1,363 @@
+"""Lightmap filtering on the GPU (include/rt_mi355x.h: RT_LIGHTMAP_FILTER, rt_lightmap_bake_filtered[_device], rt_lightmap_filter[_device];
+the kernels k_lm_resolve_var, k_lm_filter_in, k_lm_filter_copy and k_lm_atrous of csrc/rt_lightmap.hip). rt_lightmap_filter is compared with
+lm_filter_model over the guides of texel_model, rt_lightmap_bake_filtered with the chain dilate_model(lm_filter_model(lm_variance_model +
+resolve_model(Scene.gather_paths(...)))). Every comparison but the last test's is assert_array_equal; the last holds the filter at the
+Python defaults to the error bound DESIGN.md §20 derives from eight seeds."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import test_gpu_lightmap as G
+from rtamd import abi, bake
+from rtamd.renderer import Lightmap, Scene
+from test_lightmap import CORNELL_ATLASES, NONE, dilate_model, owner_model, resolve_model, stats_model, texel_model
+from test_lightmap_filter import lm_filter_model, lm_variance_model
+
+pytestmark = pytest.mark.gpu
+f32 = np.float32
+INF = float("inf")
+ATLASES = [(1, 1), (7, 5), (65, 33), (64, 64)]  # below a tile, across a tile edge on both axes, steps larger than the atlas
+# (sigma_luminance, sigma_normal, sigma_position): each finite and +inf; no variance plane goes with the +inf luminance cases
+SIGMAS = [(4.0, 0.3, 1.5), (INF, 0.3, 1.5), (4.0, INF, 1.5), (4.0, 0.3, INF), (INF, INF, INF)]
+ITERATIONS = [0, 1, 2, 5]
+SAMPLES, DEPTH, SEED = 2, 5, 11
+# filtered / raw RMSE at the Python defaults. scripts/lightmap_filter_probe.py measured the ratio for the seeds 11 .. 18 (DESIGN.md §20,
+# profiles/lightmap_filter_probe.json): 0.3573, 0.3405, 0.3104, 0.3331, 0.3221, 0.3135, 0.3357, 0.3418. The bound is the largest times 1.25,
+# the margin for seeds the eight did not draw.
+QUALITY_BOUND = 1.25 * 0.35731
+
+_SCENES = {}
+
+
+@pytest.fixture(scope="module")
+def gpu(rtlib):
+    assert rtlib.rt_device_count() > 0, "GPU tests need a device; the product has no CPU fallback"
+    yield 0
+    for s in _SCENES.values():
+        s.close()
+    _SCENES.clear()
+
+
+def device_scene(key, sd, gpu):
+    if key not in _SCENES:
+        _SCENES[key] = Scene(sd, device=gpu)
+    return _SCENES[key]
+
+
+def case(name, W, H):
+    """-> (scene key, description, lm_uv) of a synthetic UV set of tests/test_gpu_lightmap.py or of the Cornell box under the grid unwrap"""
+    if name == "cornell":
+        sd = G.named_desc("cornell")
+        return "cornell", sd, bake.triangle_grid_uvs(sd.n_triangles, W, H)
+    uv = G.uv_case(name, W, H)
+    return ("synthetic", len(uv)), G.synthetic_desc(len(uv)), uv
+
+
+def planes(W, H, seed):
+    """a radiance plane with alpha 1 on most texels, 0 and 0.5 on others, and a variance plane"""
+    g = np.random.default_rng(seed)
+    rgba = (g.random((H, W, 4), dtype=f32) * f32(2)).astype(f32)
+    rgba[..., 3] = g.choice(np.array([1.0, 1.0, 1.0, 1.0, 0.0, 0.5], f32), size=(H, W))
+    var = (g.random((H, W), dtype=f32) * f32(0.05)).astype(f32)
+    return rgba, var
+
+
+def guides_and_mask(sd, uv, W, H, rgba):
+    owner = owner_model(uv, W, H)
+    pos, nrm = texel_model(sd, uv, W, H, owner)
+    mask = (rgba[..., 3].reshape(-1) == 1) & (owner != NONE) & np.isfinite(pos).all(1) & np.isfinite(nrm).all(1)
+    return owner, pos.reshape(H, W, 3), nrm.reshape(H, W, 3), mask.reshape(H, W)
+
+
+def assert_filter(lm, sd, uv, W, H, what, iterations=ITERATIONS, sigmas=SIGMAS, seed=5):
+    rgba, var = planes(W, H, seed)
+    owner, pos, nrm, mask = guides_and_mask(sd, uv, W, H, rgba)
+    for it in iterations:
+        for sl, sn, sx in sigmas:
+            v = None if np.isinf(sl) else var
+            want, want_v = lm_filter_model(rgba[..., :3], v, mask, pos, nrm, it, sl, sn, sx)
+            got = lm.filter(rgba, v, iterations=it, sigma_luminance=sl, sigma_normal=sn, sigma_position=sx)
+            np.testing.assert_array_equal(got["rgba"], want, err_msg=f"{what}: rgba, {it} iterations, sigmas {sl, sn, sx}")
+            np.testing.assert_array_equal(got["variance"], want_v, err_msg=f"{what}: variance, {it} iterations, sigmas {sl, sn, sx}")
+    return rgba, var, owner, mask
+
+
+# ---- 1. rt_lightmap_filter against the model -----------------------------------------------------------------------------------------------
+# (the grid unwrap cannot give the Cornell box's 116 triangles a cell on the two small atlases)
+FILTER_CASES = [(a, n) for a in ATLASES for n in ("mixed", "mixed_without_the_whole", "grid", "cornell") if n != "cornell" or a[0] >= 64]
+
+
+@pytest.mark.parametrize("atlas,name", FILTER_CASES, ids=lambda v: v if isinstance(v, str) else f"{v[0]}x{v[1]}")
+def test_filter_on_synthetic_planes_equals_the_model(gpu, atlas, name):
+    W, H = atlas
+    key, sd, uv = case(name, W, H)
+    lm = Lightmap(device_scene(key, sd, gpu), uv, W, H, filter=True)
+    rgba, var, owner, mask = assert_filter(lm, sd, uv, W, H, f"{name} {W}x{H}")
+    lm.close()
+    a1 = rgba[..., 3].reshape(-1) == 1
+    if W >= 64:
+        assert mask.sum() > 100 and (~mask).sum() > 100
+    if name in ("mixed_without_the_whole", "grid", "cornell") and W >= 64:
+        assert (a1 & (owner == NONE)).sum() > 10  # texels with alpha 1 and no owner: outside M
+
+
+def test_filter_in_place_and_without_a_variance_output(gpu):
+    W, H = 65, 33
+    key, sd, uv = case("grid", W, H)
+    lm = Lightmap(device_scene(key, sd, gpu), uv, W, H, filter=True)
+    rgba, var = planes(W, H, 9)
+    _, pos, nrm, mask = guides_and_mask(sd, uv, W, H, rgba)
+    for it in ITERATIONS:
+        want, want_v = lm_filter_model(rgba[..., :3], var, mask, pos, nrm, it, 4.0, 0.3, 1.5)
+        buf = rgba.copy()
+        got = lm.filter(buf, var, out_rgba=buf, want_variance=False, iterations=it, sigma_luminance=4.0, sigma_normal=0.3, sigma_position=1.5)
+        assert got["rgba"] is buf and got["variance"] is None
+        np.testing.assert_array_equal(buf, want)
+        got = lm.filter(rgba, var, iterations=it, sigma_luminance=4.0, sigma_normal=0.3, sigma_position=1.5)
+        np.testing.assert_array_equal(got["variance"], want_v)
+    lm.close()
+
+
+def zero_normal_cornell():
+    """the Cornell box with the vertex normals of one instance zeroed: its texels have NaN normals (tests/test_gpu_lightmap.py)"""
+    sd0 = G.named_desc("cornell")
+    verts = np.unique(np.asarray(sd0.indices)[np.asarray(sd0.tri_instance) == 2])
+    normals = np.array(sd0.normals, f32, copy=True)
+    normals[verts] = 0.0
+    return sd0.updated(normals=normals)
+
+
+def test_texels_with_nan_guides_leave_the_mask(gpu):
+    W, H = CORNELL_ATLASES[0]
+    sd = zero_normal_cornell()
+    uv = bake.triangle_grid_uvs(sd.n_triangles, W, H)
+    s = Scene(sd, device=gpu)
+    lm = Lightmap(s, uv, W, H, max_repeats=2, filter=True)
+    rgba, var, owner, mask = assert_filter(lm, sd, uv, W, H, "zero normals", iterations=[0, 2], sigmas=SIGMAS[:2])
+    dark = (owner != NONE) & np.isin(owner, np.flatnonzero(np.asarray(sd.tri_instance) == 2))
+    a1 = rgba[..., 3].reshape(-1) == 1
+    assert (dark & a1).sum() >= 2 and not mask.reshape(-1)[dark].any()
+    # ... and in a filtered bake they are covered, not sampled, and filled from filtered neighbours
+    for dilate in (0, 4):
+        want, want_v, stats = filtered_chain(s, sd, uv, W, H, 2, 0, dilate, 2, (4.0, 0.3, 1.5), key="filter zero normals")
+        got = lm.bake_filtered(SAMPLES, DEPTH, SEED, repeats=2, dilate=dilate, iterations=2, sigma_luminance=4.0, sigma_normal=0.3,
+                               sigma_position=1.5)
+        np.testing.assert_array_equal(got["rgba"], want)
+        np.testing.assert_array_equal(got["variance"], want_v)
+        assert got["stats"] == stats and stats["covered"] - stats["sampled"] == dark.sum()
+    lm.close(), s.close()
+
+
+# ---- 2. the filtered bake against its chain ------------------------------------------------------------------------------------------------------
+def filtered_chain(s, sd, uv, W, H, repeats, rr_start, dilate, iterations, sigmas, key):
+    """The filtered bake as the contract states it, over the library's own gather -> (rgba (H, W, 4), variance (H, W), stats)"""
+    G.chain(s.gather_paths, sd, uv, W, H, SAMPLES, DEPTH, SEED, repeats, rr_start, 0, key=key)  # leaves the gather's outputs under the key
+    rad, rays = G._GATHERED[key]
+    owner = owner_model(uv, W, H)
+    pos, nrm = texel_model(sd, uv, W, H, owner)
+    raw = resolve_model(owner, rad, rays, repeats).reshape(H, W, 4)
+    sampled = raw[..., 3] == 1
+    var = lm_variance_model(rad, repeats, sampled.reshape(-1)).reshape(H, W)
+    sl, sn, sx = sigmas
+    filt, var = lm_filter_model(raw[..., :3], var, sampled, pos.reshape(H, W, 3), nrm.reshape(H, W, 3), iterations, sl, sn, sx)
+    np.testing.assert_array_equal(filt[..., 3], raw[..., 3])
+    rgba = dilate_model(filt, dilate)
+    return rgba, var, stats_model(owner, rays, rgba, repeats)
+
+
+@pytest.fixture(scope="module", params=CORNELL_ATLASES, ids=lambda a: f"{a[0]}x{a[1]}")
+def cornell(gpu, request):
+    W, H = request.param
+    sd = G.named_desc("cornell")
+    uv = bake.triangle_grid_uvs(sd.n_triangles, W, H)
+    s = device_scene("cornell", sd, gpu)
+    lm = Lightmap(s, uv, W, H, max_repeats=3, filter=True)
+    yield sd, s, uv, W, H, lm
+    lm.close()
+
+
+@pytest.mark.parametrize("dilate", [0, 4])
+@pytest.mark.parametrize("repeats", [2, 3])
+def test_a_filtered_bake_is_its_chain_over_the_librarys_own_gather(cornell, repeats, dilate):
+    sd, s, uv, W, H, lm = cornell
+    for it, sigmas in ((2, (4.0, 0.3, 1.5)), (5, (2.0, 0.25, INF)), (1, (INF, INF, 0.5))):
+        want, want_v, stats = filtered_chain(s, sd, uv, W, H, repeats, 0, dilate, it, sigmas, key=("filter cornell", W, repeats))
+        got = lm.bake_filtered(SAMPLES, DEPTH, SEED, repeats=repeats, dilate=dilate, iterations=it, sigma_luminance=sigmas[0],
+                               sigma_normal=sigmas[1], sigma_position=sigmas[2])
+        np.testing.assert_array_equal(got["rgba"], want, err_msg=f"{it} iterations")
+        np.testing.assert_array_equal(got["variance"], want_v, err_msg=f"{it} iterations")
+        assert got["stats"] == stats
+        a = want[..., 3]
+        assert stats["sampled"] == (a == 1).sum() > 116 and (stats["filled"] > 0) == (dilate > 0)
+        assert (want_v[a == 1] > 0).any() and (want_v[a != 1] == 0).all()  # the variance is 0 outside M, filled texels included
+    raw = lm.bake(SAMPLES, DEPTH, SEED, repeats=repeats, dilate=dilate)
+    assert not np.array_equal(raw["rgba"], got["rgba"])
+
+
+def test_no_iterations_and_no_parameters_are_the_unfiltered_bake_with_the_variance_of_its_mean(cornell):
+    sd, s, uv, W, H, lm = cornell
+    for repeats in (1, 2, 3):  # below and at max_repeats; one repeat is allowed where nothing is filtered: its variance is 0
+        raw = lm.bake(SAMPLES, DEPTH, SEED, repeats=repeats, rr_start=2, dilate=3)
+        key = ("filter cornell rr2", W, repeats)
+        G.chain(s.gather_paths, sd, uv, W, H, SAMPLES, DEPTH, SEED, repeats, 2, 0, key=key)
+        rad, rays = G._GATHERED[key]
+        sampled = resolve_model(owner_model(uv, W, H), rad, rays, repeats)[:, 3] == 1
+        var = lm_variance_model(rad, repeats, sampled).reshape(H, W)
+        assert (var == 0).all() == (repeats == 1)
+        got = lm.bake_filtered(SAMPLES, DEPTH, SEED, repeats=repeats, rr_start=2, dilate=3, iterations=0)
+        np.testing.assert_array_equal(got["rgba"], raw["rgba"])
+        np.testing.assert_array_equal(got["variance"], var)
+        assert got["stats"] == raw["stats"]
+        p = abi.rt_lightmap_params(SAMPLES, DEPTH, 2, repeats, SEED, 3)
+        rgba, v, st = np.full((H, W, 4), 7, f32), np.full((H, W), 7, f32), abi.rt_lightmap_stats()
+        abi.check(lm._lib.rt_lightmap_bake_filtered(lm.h, C.byref(p), None, abi.fptr(rgba), abi.fptr(v), C.byref(st)), lm._lib)
+        np.testing.assert_array_equal(rgba, raw["rgba"])
+        np.testing.assert_array_equal(v, var)
+        assert {"covered": st.covered, "sampled": st.sampled, "filled": st.filled, "rays": st.rays} == raw["stats"]
+        abi.check(lm._lib.rt_lightmap_bake_filtered(lm.h, C.byref(p), None, abi.fptr(rgba), None, None), lm._lib)  # no variance, no stats
+        np.testing.assert_array_equal(rgba, raw["rgba"])
+    for kw, word in (({"repeats": 4}, "max_repeats"), ({"repeats": 1}, "repeats >= 2"), ({"repeats": 0}, "repeats"), ({"dilate": 17}, "dilate"),
+                     ({"iterations": 11}, "iterations"), ({"sigma_normal": 0.0}, "sigma")):
+        with pytest.raises(abi.RtError) as e:
+            lm.bake_filtered(SAMPLES, DEPTH, SEED, **kw)
+        assert e.value.status == abi.RT_ERR_INVALID and word in str(e.value), kw
+    assert lm.bake_filtered(SAMPLES, DEPTH, SEED, repeats=3)["stats"]["sampled"] > 0  # max_repeats itself, at the defaults
+
+
+# ---- 3. device forms, moving scenes, lightmaps without the flag ----------------------------------------------------------------------------------
+def test_the_device_forms_on_a_stream_equal_the_host_forms(cornell):
+    import torch
+    sd, s, uv, W, H, lm = cornell
+    kw = dict(iterations=3, sigma_luminance=4.0, sigma_normal=0.3, sigma_position=1.5)
+    host = lm.bake_filtered(SAMPLES, DEPTH, SEED, repeats=3, rr_start=2, dilate=3, **kw)
+    st = torch.cuda.Stream(device=0)
+    for full in (True, False):
+        rgba = torch.full((H, W, 4), 7.0, dtype=torch.float32, device="cuda")
+        var = torch.full((H, W), 7.0, dtype=torch.float32, device="cuda")
+        stats = torch.full((3,), 0x5555555555555555, dtype=torch.int64, device="cuda")
+        torch.cuda.synchronize()
+        lm.bake_filtered_device(rgba.data_ptr(), SAMPLES, DEPTH, SEED, repeats=3, rr_start=2, dilate=3, d_variance=var.data_ptr() if full else 0,
+                                d_stats=stats.data_ptr() if full else 0, stream=st.cuda_stream, **kw)
+        torch.cuda.synchronize()
+        np.testing.assert_array_equal(rgba.cpu().numpy(), host["rgba"])
+        words = stats.cpu().numpy().view(np.uint32)
+        if full:
+            np.testing.assert_array_equal(var.cpu().numpy(), host["variance"])
+            got = {"covered": int(words[0]), "sampled": int(words[1]), "filled": int(words[2]), "rays": int(stats.cpu().numpy().view(np.uint64)[2])}
+            assert got == host["stats"] and words[3] == 0
+        else:
+            assert (words == 0x55555555).all() and (var.cpu().numpy() == 7).all()
+    src, v = planes(W, H, 13)
+    for sl in (4.0, INF):
+        want = lm.filter(src, None if np.isinf(sl) else v, **dict(kw, sigma_luminance=sl))
+        d_src, d_var = torch.from_numpy(src).cuda(), torch.from_numpy(v).cuda()
+        d_out, d_ov = torch.full((H, W, 4), 7.0, dtype=torch.float32, device="cuda"), torch.full((H, W), 7.0, dtype=torch.float32, device="cuda")
+        torch.cuda.synchronize()
+        lm.filter_device(d_src.data_ptr(), 0 if np.isinf(sl) else d_var.data_ptr(), d_out.data_ptr(), d_ov.data_ptr(), stream=st.cuda_stream,
+                         **dict(kw, sigma_luminance=sl))
+        torch.cuda.synchronize()
+        np.testing.assert_array_equal(d_out.cpu().numpy(), want["rgba"])
+        np.testing.assert_array_equal(d_ov.cpu().numpy(), want["variance"])
+        np.testing.assert_array_equal(d_src.cpu().numpy(), src)  # the inputs are left alone
+        lm.filter_device(d_src.data_ptr(), d_var.data_ptr(), d_src.data_ptr(), 0, stream=st.cuda_stream, **dict(kw, sigma_luminance=sl))  # in place
+        torch.cuda.synchronize()
+        np.testing.assert_array_equal(d_src.cpu().numpy(), want["rgba"])
+
+
+def test_an_update_waits_for_a_pending_filter_and_the_next_filter_sees_the_moved_guides(gpu):
+    import torch
+    from test_scene_update import spin_about_centre
+    sd = G.named_desc("cornell")
+    W, H = CORNELL_ATLASES[0]
+    uv = bake.triangle_grid_uvs(sd.n_triangles, W, H)
+    s = Scene(sd, device=gpu, updatable=True)
+    lm = Lightmap(s, uv, W, H, max_repeats=2, filter=True)
+    kw = dict(iterations=3, sigma_luminance=4.0, sigma_normal=0.3, sigma_position=1.5)
+    rgba, var = planes(W, H, 17)
+
+    def model(desc):
+        _, pos, nrm, mask = guides_and_mask(desc, uv, W, H, rgba)
+        return lm_filter_model(rgba[..., :3], var, mask, pos, nrm, 3, 4.0, 0.3, 1.5)
+
+    before, before_v = model(sd)
+    got = lm.filter(rgba, var, **kw)
+    np.testing.assert_array_equal(got["rgba"], before)
+    st = torch.cuda.Stream(device=0)
+    d_src, d_var = torch.from_numpy(rgba).cuda(), torch.from_numpy(var).cuda()
+    d_out, d_ov = torch.zeros((H, W, 4), dtype=torch.float32, device="cuda"), torch.zeros((H, W), dtype=torch.float32, device="cuda")
+    torch.cuda.synchronize()
+    with torch.cuda.stream(st):
+        torch.cuda._sleep(200_000_000)  # ~0.1 s of spinning in front of the filter
+    lm.filter_device(d_src.data_ptr(), d_var.data_ptr(), d_out.data_ptr(), d_ov.data_ptr(), stream=st.cuda_stream, **kw)
+    s.update(instances=spin_about_centre(sd, 25.0))  # waits for the filter's k_lm_texels: the scene's event on the stream
+    torch.cuda.synchronize()
+    np.testing.assert_array_equal(d_out.cpu().numpy(), before)
+    np.testing.assert_array_equal(d_ov.cpu().numpy(), before_v)
+    after, after_v = model(s.desc)
+    assert not np.array_equal(after, before)
+    got = lm.filter(rgba, var, **kw)
+    np.testing.assert_array_equal(got["rgba"], after)
+    np.testing.assert_array_equal(got["variance"], after_v)
+    lm.close(), s.close()
+
+
+def test_a_lightmap_without_the_flag_refuses_the_four_calls_and_bakes_as_before(gpu):
+    W, H = CORNELL_ATLASES[0]
+    sd = G.named_desc("cornell")
+    uv = bake.triangle_grid_uvs(sd.n_triangles, W, H)
+    s = device_scene("cornell", sd, gpu)
+    rgba, var = planes(W, H, 3)
+    buf = np.zeros(16, np.uint8)
+    for make in (lambda: Lightmap(s, uv, W, H, max_repeats=2), lambda: _create_ex(s, uv, W, H, 2, 0)):
+        lm = make()
+        calls = (lambda: lm.bake_filtered(SAMPLES, DEPTH, SEED), lambda: lm.filter(rgba, var),
+                 lambda: lm.bake_filtered_device(buf.ctypes.data, SAMPLES, DEPTH, SEED),
+                 lambda: lm.filter_device(buf.ctypes.data, buf.ctypes.data, buf.ctypes.data))
+        for call in calls:
+            with pytest.raises(abi.RtError) as e:
+                call()
+            assert e.value.status == abi.RT_ERR_INVALID and "RT_LIGHTMAP_FILTER" in str(e.value)
+        want, stats = G.chain(s.gather_paths, sd, uv, W, H, SAMPLES, DEPTH, SEED, 2, 0, 2, key=("filter cornell", W, 2))
+        got = lm.bake(SAMPLES, DEPTH, SEED, repeats=2, dilate=2)
+        np.testing.assert_array_equal(got["rgba"], want)
+        assert got["stats"] == stats
+        lm.close()
+    h = C.c_void_p()
+    u = np.ascontiguousarray(uv, f32)
+    assert s._lib.rt_lightmap_create_ex(s.h, W, H, 1, abi.fptr(u), 2, C.byref(h)) == abi.RT_ERR_INVALID and not h.value
+
+
+def _create_ex(s, uv, W, H, max_repeats, flags):
+    """a Lightmap made by rt_lightmap_create_ex with the given flags"""
+    lm = Lightmap.__new__(Lightmap)
+    lm._uv = np.ascontiguousarray(uv, f32)
+    lm._lib, lm.scene, lm.width, lm.height, lm.max_repeats, lm.h = s._lib, s, W, H, max_repeats, C.c_void_p()
+    abi.check(s._lib.rt_lightmap_create_ex(s.h, W, H, max_repeats, abi.fptr(lm._uv), flags, C.byref(lm.h)), s._lib)
+    return lm
+
+
+# ---- 4. what the filter is for --------------------------------------------------------------------------------------------------------------------
+def rmse(a, ref, on):
+    d = a[..., :3][on].astype(np.float64) - ref[..., :3][on].astype(np.float64)
+    return float(np.sqrt((d * d).mean()))
+
+
+def test_the_filter_at_the_defaults_brings_a_sixteen_path_bake_closer_to_a_thousand_path_bake(gpu):
+    """The Cornell box under the grid unwrap on 256 x 256, depth 5: a bake of 4 samples x 4 repeats, raw and filtered at the Python defaults,
+    against 256 samples x 4 repeats of the same library. RMSE over the sampled texels; the bound is QUALITY_BOUND above."""
+    W = H = 256
+    sd = G.named_desc("cornell")
+    uv = bake.triangle_grid_uvs(sd.n_triangles, W, H)
+    s = device_scene("cornell", sd, gpu)
+    lm = Lightmap(s, uv, W, H, max_repeats=4, filter=True)
+    ref = lm.bake(256, 5, 1001, repeats=4)
+    raw = lm.bake(4, 5, SEED, repeats=4)
+    flt = lm.bake_filtered(4, 5, SEED, repeats=4)
+    lm.close()
+    on = ref["rgba"][..., 3] == 1
+    np.testing.assert_array_equal(raw["rgba"][..., 3] == 1, on)
+    np.testing.assert_array_equal(flt["rgba"][..., 3] == 1, on)
+    e_raw, e_flt = rmse(raw["rgba"], ref["rgba"], on), rmse(flt["rgba"], ref["rgba"], on)
+    print(f"sampled {on.sum()}, rmse raw {e_raw:.6f}, filtered {e_flt:.6f}, ratio {e_flt / e_raw:.4f}, bound {QUALITY_BOUND}")
+    assert e_flt / e_raw <= QUALITY_BOUND

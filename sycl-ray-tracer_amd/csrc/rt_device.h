@@ -206,6 +206,13 @@ RT_DEV void tri_test(const uint8_t* __restrict__ tr, f3 o, f3 d, Hit& best) {
 // one loop) was 27 %. The box test is a padded-box cull: it uses fma and an approximate reciprocal on
 // purpose (never visible in results).
 constexpr int32_t kTravDone = (int32_t)0x80000000;
+// The vote's weights: an inner step while inner lanes * kVoteInner >= leaf lanes * kVoteLeaf (trav_step_wave). Compile-time constants — the
+// products are an s_mul and an s_lshl; a sweep builds one developer library per pair (-DRT_VOTE_INNER=.. -DRT_VOTE_LEAF=..).
+#if defined(RT_DEVELOPER_KNOBS) && defined(RT_VOTE_INNER) && defined(RT_VOTE_LEAF)
+constexpr uint32_t kVoteInner = RT_VOTE_INNER, kVoteLeaf = RT_VOTE_LEAF;
+#else
+constexpr uint32_t kVoteInner = 3u, kVoteLeaf = 4u;
+#endif
 struct Trav {
     f3 o, d;              // ray (d unnormalised, as stored)
     float ix, iy, iz;     // 1/d (|d| clamped away from 0)
@@ -316,6 +323,10 @@ RT_DEV uint32_t sel(lmask m, uint32_t a, uint32_t b) {
     return d;
 }
 RT_DEV int32_t sel(lmask m, int32_t a, int32_t b) { return (int32_t)sel(m, (uint32_t)a, (uint32_t)b); }
+// This lane's bit of a wave-uniform mask as a branch condition: s_and_saveexec on the SGPR pair itself. (A `bool` that is and-ed with another and
+// balloted again, or kept across a loop, is turned into v_cndmask 0/1 + v_cmp_ne per use: two half-rate instructions for a mask the wave holds.)
+RT_DEV bool in_mask(lmask m) { return __builtin_amdgcn_inverse_ballot_w64(m); }
+RT_DEV uint32_t count(lmask m) { return (uint32_t)__builtin_popcountll(m); } // s_bcnt1
 
 // The direction signs of the wave's 64 rays as three lane masks. A ray's signs do not change while it is traversed, so the kernels
 // take them ONCE per traversal phase, in wave-uniform control flow after the shading round that started the rays (trav_signs), and
@@ -395,8 +406,12 @@ RT_DEV void trav_inner(const SceneDev& S, Trav& T, const TravStack& stack, const
     {                                                                                                    \
         const float tn = __builtin_fmaxf(__builtin_fmaxf(__builtin_fmaf(CVT(qnx), ax, bx), __builtin_fmaf(CVT(qny), ay, by)), \
                                          __builtin_fmaxf(__builtin_fmaf(CVT(qnz), az, bz), 0.0f));       \
-        const float tf = __builtin_fminf(__builtin_fminf(__builtin_fmaf(CVT(qfx), ax, bx), __builtin_fmaf(CVT(qfy), ay, by)), \
-                                         __builtin_fminf(__builtin_fmaf(CVT(qfz), az, bz), T.best.t));   \
+        /* SKIP (the one-launch kernels): the closest hit last — as the third operand of v_min3_f32 it is not quieted first (v_max_f32 t, t, once */ \
+        /* per step), as hipcc does for an operand of __builtin_fminf that it cannot prove to be no signalling NaN; the minimum of the four values */ \
+        /* is the same. The other users keep the pairing they had: the per-bounce kernels measured 0.3 % slower with the new one. */ \
+        const float fx = __builtin_fmaf(CVT(qfx), ax, bx), fy = __builtin_fmaf(CVT(qfy), ay, by), fz = __builtin_fmaf(CVT(qfz), az, bz); \
+        const float tf = SKIP ? __builtin_fminf(__builtin_fminf(__builtin_fminf(fx, fy), fz), T.best.t)  \
+                              : __builtin_fminf(__builtin_fminf(fx, fy), __builtin_fminf(fz, T.best.t)); \
         K = sel(SKIP ? (lanes(tn <= tf) & lanes(CW != skip)) : lanes(tn <= tf), inf, tn);                \
     }
     if (SKIP) asm volatile("s_waitcnt vmcnt(0)" : "+v"(chw));
@@ -473,22 +488,39 @@ RT_DEV void trav_leaf(const SceneDev& S, Trav& T, const TravStack& stack) {
     }
 }
 
-// One wave-uniform step. Returns the number of lanes still traversing BEFORE the step (0 = all done).
+// The classes of the wave's lanes are lane masks, and the vote is scalar arithmetic on their counts: no lane holds a `bool` of its own.
+struct TravClasses {
+    lmask inner, leaf;
+};
+RT_DEV lmask trav_done(const Trav& T) { return lanes(T.cur == kTravDone); }
+RT_DEV TravClasses trav_classes(const Trav& T) { return TravClasses{lanes(T.cur >= 0), lanes((uint32_t)T.cur > (uint32_t)kTravDone)}; }
+// ... for a caller that holds trav_done(T) of the same T.cur (the traversal phase's exit test): a lane of the wave that is neither at an inner
+// node nor done is at a leaf — two scalar instructions instead of a vector compare
+RT_DEV TravClasses trav_classes(const Trav& T, lmask done) {
+    const lmask inner = lanes(T.cur >= 0);
+    return TravClasses{inner, lanes(true) & ~(inner | done)};
+}
+// One wave-uniform step on the classes `c` of T.cur. Returns the number of lanes still traversing BEFORE the step (0 = all done).
+// (The vote stands in the `if` itself: held in a named bool ahead of it, hipcc allocated the loop of k_megakernel with 70 more copies and
+// 32 to 48 bytes more scratch — profiles/wave_loop_static.txt.)
 template <bool STATS = false, bool LEAF_BATCH = false, bool SKIP = false>
-RT_DEV uint32_t trav_step_wave(const SceneDev& S, Trav& T, const TravStack& stack, const TopTree& top, const TravSigns& sg, WaveStats* ws = nullptr) {
-    const bool inner = T.cur >= 0;
-    const bool leaf = T.cur < 0 && T.cur != kTravDone;
-    const uint32_t ni = (uint32_t)__popcll(__ballot(inner)), nl = (uint32_t)__popcll(__ballot(leaf));
+RT_DEV uint32_t trav_step_wave(const SceneDev& S, Trav& T, const TravStack& stack, const TopTree& top, const TravSigns& sg, const TravClasses& c, WaveStats* ws = nullptr) {
+    const uint32_t ni = count(c.inner), nl = count(c.leaf);
     // the vote, weighted 3 : 4 — a leaf step as soon as the leaf lanes exceed 3/4 of the inner lanes: a lane parked at a leaf is idle for as
     // many iterations as the vote goes against it (plain majority: -1.2 %; EXPERIMENTS.md)
-    if (ni * 3u >= nl * 4u && !(LEAF_BATCH && nl >= 64u)) {
-        if (STATS && ni) ws->inner_steps++, ws->inner_lanes += ni, ws->top_lanes += (uint32_t)__popcll(__ballot(inner && T.cur < (SKIP ? top.count : kTopNodes) * 64));
-        if (inner) trav_inner<SKIP>(S, T, stack, top, sg);
+    if (ni * kVoteInner >= nl * kVoteLeaf && !(LEAF_BATCH && nl >= 64u)) {
+        if (STATS && ni) ws->inner_steps++, ws->inner_lanes += ni, ws->top_lanes += count(c.inner & lanes(T.cur < (SKIP ? top.count : kTopNodes) * 64));
+        if (in_mask(c.inner)) trav_inner<SKIP>(S, T, stack, top, sg);
     } else {
-        if (STATS) ws->leaf_steps++, ws->leaf_lanes += (uint32_t)__popcll(__ballot(leaf));
-        if (leaf) trav_leaf<LEAF_BATCH>(S, T, stack);
+        if (STATS) ws->leaf_steps++, ws->leaf_lanes += nl;
+        if (in_mask(c.leaf)) trav_leaf<LEAF_BATCH>(S, T, stack);
     }
     return ni + nl;
+}
+// ... on the classes it takes itself (two compares)
+template <bool STATS = false, bool LEAF_BATCH = false, bool SKIP = false>
+RT_DEV uint32_t trav_step_wave(const SceneDev& S, Trav& T, const TravStack& stack, const TopTree& top, const TravSigns& sg, WaveStats* ws = nullptr) {
+    return trav_step_wave<STATS, LEAF_BATCH, SKIP>(S, T, stack, top, sg, trav_classes(T), ws);
 }
 
 // run to completion (rt_intersect_batch; lanes that finish early wait for the wave)

@@ -95,10 +95,13 @@ RT_DEV void path_rounds(SceneDev S, Q q) {
         // TRAVERSE until E::kShadePct of the lanes that have a ray are waiting for shading
         const TravSigns sg = trav_signs(T); // every ray of this traversal phase has been started by now
         const uint32_t shade_at = n_live * E::kShadePct;
+        const lmask live_m = lanes(live);
         for (;;) {
-            if ((uint32_t)__popcll(__ballot(live && T.cur == kTravDone)) * 100u >= shade_at) break;
+            const lmask done = trav_done(T);
+            if (count(done & live_m) * 100u >= shade_at) break;
+            (void)trav_step_wave<false, true>(S, T, stack, top, sg, trav_classes(T, done));
 #pragma unroll
-            for (int k = 0; k < E::kUnroll; ++k) (void)trav_step_wave<false, true>(S, T, stack, top, sg);
+            for (int k = 1; k < E::kUnroll; ++k) (void)trav_step_wave<false, true>(S, T, stack, top, sg);
         }
         // SHADE the lanes whose traversal is complete
         __builtin_amdgcn_s_setprio(0);

@@ -358,7 +358,10 @@ RT_DEV TravSigns trav_signs(const Trav& T) { return TravSigns{lanes(T.ix < 0.0f)
 // SKIP (k_megakernel, k_wf_finish: the origin skip, rt_types.h: SkipRec): a child whose word equals the lane's skip word — kept in the
 // LDS word above its stack, written where the ray is started (rt_bounce.h: origin_skip) — counts as missed: one compare per child into an
 // SGPR pair, and-ed on the scalar unit into the hit mask. The child words are then needed at the keys, not only at the sort.
-template <bool SKIP = false>
+// MISS_KEYS (with SKIP; k_megakernel): the hit masks as below, but a missed child still gets its +inf key and the comparators swap on the
+// bare compare. Four selects more and five scalar instructions fewer per step; which of the two is faster is the register allocation of
+// the kernel around the step (EXPERIMENTS.md, "The inner step").
+template <bool SKIP = false, bool MISS_KEYS = false>
 RT_DEV void trav_inner(const SceneDev& S, Trav& T, const TravStack& stack, const TopTree& top, const TravSigns& sg) {
     const float inf = __builtin_huge_valf();
     uint32_t skip = kSkipNone;
@@ -402,7 +405,10 @@ RT_DEV void trav_inner(const SceneDev& S, Trav& T, const TravStack& stack, const
     // of origin * inv - o * inv on all three axes at once (entry == exit), and out there the padded boxes are no longer conservative
     // for any child, absent or not — so the child words are not tested here (an explicit kChildEmpty test per slot was measured at
     // 12 issue cycles of ~500 per step).
-#define RT_CHILD(K, CVT, CW)                                                                              \
+    // SKIP (the one-launch kernels): whether a child was hit is a lane mask (h0..h3), not a +inf key — the wave holds these facts as SGPR pairs
+    // already, and the sort and the pushes below read them there. Without MISS_KEYS a missed child has no key at all.
+    lmask h0 = 0ull, h1 = 0ull, h2 = 0ull, h3 = 0ull;
+#define RT_CHILD(K, H, CVT, CW)                                                                           \
     {                                                                                                    \
         const float tn = __builtin_fmaxf(__builtin_fmaxf(__builtin_fmaf(CVT(qnx), ax, bx), __builtin_fmaf(CVT(qny), ay, by)), \
                                          __builtin_fmaxf(__builtin_fmaf(CVT(qnz), az, bz), 0.0f));       \
@@ -412,13 +418,14 @@ RT_DEV void trav_inner(const SceneDev& S, Trav& T, const TravStack& stack, const
         const float fx = __builtin_fmaf(CVT(qfx), ax, bx), fy = __builtin_fmaf(CVT(qfy), ay, by), fz = __builtin_fmaf(CVT(qfz), az, bz); \
         const float tf = SKIP ? __builtin_fminf(__builtin_fminf(__builtin_fminf(fx, fy), fz), T.best.t)  \
                               : __builtin_fminf(__builtin_fminf(fx, fy), __builtin_fminf(fz, T.best.t)); \
-        K = sel(SKIP ? (lanes(tn <= tf) & lanes(CW != skip)) : lanes(tn <= tf), inf, tn);                \
+        if (SKIP) H = lanes(tn <= tf) & lanes(CW != skip), K = MISS_KEYS ? sel(H, inf, tn) : tn;         \
+        else K = sel(lanes(tn <= tf), inf, tn);                                                          \
     }
     if (SKIP) asm volatile("s_waitcnt vmcnt(0)" : "+v"(chw));
-    RT_CHILD(k0, ub0, chw.x)
-    RT_CHILD(k1, ub1, chw.y)
-    RT_CHILD(k2, ub2, chw.z)
-    RT_CHILD(k3, ub3, chw.w)
+    RT_CHILD(k0, h0, ub0, chw.x)
+    RT_CHILD(k1, h1, ub1, chw.y)
+    RT_CHILD(k2, h2, ub2, chw.z)
+    RT_CHILD(k3, h3, ub3, chw.w)
 #undef RT_CHILD
     // sorting network on (entry distance, child); misses carry +inf and sink to the end. One comparator = one compare into an
     // SGPR pair + four e64 selects on it (18 cycles).
@@ -431,6 +438,48 @@ RT_DEV void trav_inner(const SceneDev& S, Trav& T, const TravStack& stack, const
     }
     if (!SKIP) asm volatile("s_waitcnt vmcnt(0)" : "+v"(chw));
     int32_t c0 = (int32_t)chw.x, c1 = (int32_t)chw.y, c2 = (int32_t)chw.z, c3 = (int32_t)chw.w;
+    if (SKIP) {
+        // The same three comparators on (hit mask, key, child). With +inf keys a comparator swaps iff KB < KA: never when both missed, always
+        // when only B was hit, never when only A was. On the masks that is  sw = hB & (~hA | lanes(KB < KA))  — two scalar instructions, the
+        // same swaps, and no key of a miss is read (MISS_KEYS: the keys are there and the swap is the compare). Whatever sw was, the
+        // minimum slot is occupied afterwards iff hA | hB and the maximum slot iff hA & hB, so `descend` and the three push decisions are
+        // six s_or / s_and, not four v_cmp against +inf; the keys the last comparator would write, and the maxima of the first two, feed
+        // nothing any more and their selects are not emitted. (A hit child with key +inf — tn = tf = best.t = +inf — counted as missed
+        // before and is visited now; it holds nothing, and its box test needs |o| * |1 / d| to overflow.)
+        // The near clamp of tn stays: on bit patterns as signed integers, max(n, 0) <= f would pass an absent child's inverted box behind
+        // the origin, whose word is kTravDone (tests/test_inner_step_model.py).
+#define RT_CE_M(KA, HA, CA, KB, HB, CB)                                              \
+    {                                                                               \
+        const lmask sw = MISS_KEYS ? lanes(KB < KA) : HB & (~HA | lanes(KB < KA));  \
+        KA = sel(sw, KA, KB);                                                       \
+        const int32_t ca = sel(sw, CA, CB), cb = sel(sw, CB, CA);                   \
+        CA = ca, CB = cb;                                                           \
+        const lmask lo = HA | HB, hi = HA & HB;                                     \
+        HA = lo, HB = hi;                                                           \
+    }
+        RT_CE_M(k0, h0, c0, k1, h1, c1)
+        RT_CE_M(k2, h2, c2, k3, h3, c3)
+        RT_CE_M(k0, h0, c0, k2, h2, c2)
+#undef RT_CE_M
+        // h0: descend; h1, h2, h3: slots 1 .. 3 hold a hit (not a sorted prefix: each is asked on its own, as below)
+        if (lanes(!stack_shallow(stack, T, 3u)) == 0ull) {
+            *lds_at(T.sp) = c3;
+            T.sp = sel(h3, T.sp, T.sp + stack.pitch);
+            *lds_at(T.sp) = c2;
+            T.sp = sel(h2, T.sp, T.sp + stack.pitch);
+            *lds_at(T.sp) = c1;
+            T.sp = sel(h1, T.sp, T.sp + stack.pitch);
+            if (in_mask(h0)) T.cur = c0;
+            else trav_pop_lds(T, stack);
+        } else {
+            if (in_mask(h3)) stk_push(stack, T, c3);
+            if (in_mask(h2)) stk_push(stack, T, c2);
+            if (in_mask(h1)) stk_push(stack, T, c1);
+            if (in_mask(h0)) T.cur = c0;
+            else trav_pop(T, stack);
+        }
+        return;
+    }
     RT_CE(k0, c0, k1, c1)
     RT_CE(k2, c2, k3, c3)
     RT_CE(k0, c0, k2, c2)
@@ -503,14 +552,14 @@ RT_DEV TravClasses trav_classes(const Trav& T, lmask done) {
 // One wave-uniform step on the classes `c` of T.cur. Returns the number of lanes still traversing BEFORE the step (0 = all done).
 // (The vote stands in the `if` itself: held in a named bool ahead of it, hipcc allocated the loop of k_megakernel with 70 more copies and
 // 32 to 48 bytes more scratch — profiles/wave_loop_static.txt.)
-template <bool STATS = false, bool LEAF_BATCH = false, bool SKIP = false>
+template <bool STATS = false, bool LEAF_BATCH = false, bool SKIP = false, bool MISS_KEYS = false>
 RT_DEV uint32_t trav_step_wave(const SceneDev& S, Trav& T, const TravStack& stack, const TopTree& top, const TravSigns& sg, const TravClasses& c, WaveStats* ws = nullptr) {
     const uint32_t ni = count(c.inner), nl = count(c.leaf);
     // the vote, weighted 3 : 4 — a leaf step as soon as the leaf lanes exceed 3/4 of the inner lanes: a lane parked at a leaf is idle for as
     // many iterations as the vote goes against it (plain majority: -1.2 %; EXPERIMENTS.md)
     if (ni * kVoteInner >= nl * kVoteLeaf && !(LEAF_BATCH && nl >= 64u)) {
         if (STATS && ni) ws->inner_steps++, ws->inner_lanes += ni, ws->top_lanes += count(c.inner & lanes(T.cur < (SKIP ? top.count : kTopNodes) * 64));
-        if (in_mask(c.inner)) trav_inner<SKIP>(S, T, stack, top, sg);
+        if (in_mask(c.inner)) trav_inner<SKIP, MISS_KEYS>(S, T, stack, top, sg);
     } else {
         if (STATS) ws->leaf_steps++, ws->leaf_lanes += nl;
         if (in_mask(c.leaf)) trav_leaf<LEAF_BATCH>(S, T, stack);
@@ -518,9 +567,9 @@ RT_DEV uint32_t trav_step_wave(const SceneDev& S, Trav& T, const TravStack& stac
     return ni + nl;
 }
 // ... on the classes it takes itself (two compares)
-template <bool STATS = false, bool LEAF_BATCH = false, bool SKIP = false>
+template <bool STATS = false, bool LEAF_BATCH = false, bool SKIP = false, bool MISS_KEYS = false>
 RT_DEV uint32_t trav_step_wave(const SceneDev& S, Trav& T, const TravStack& stack, const TopTree& top, const TravSigns& sg, WaveStats* ws = nullptr) {
-    return trav_step_wave<STATS, LEAF_BATCH, SKIP>(S, T, stack, top, sg, trav_classes(T), ws);
+    return trav_step_wave<STATS, LEAF_BATCH, SKIP, MISS_KEYS>(S, T, stack, top, sg, trav_classes(T), ws);
 }
 
 // run to completion (rt_intersect_batch; lanes that finish early wait for the wave)

@@ -408,9 +408,10 @@ __global__ void __launch_bounds__(kMegaBlock, kMegaWaves) k_megakernel(SceneDev 
             if (STATS >= 2) ws.live_lane_steps += n_live * (uint32_t)kMegaUnroll;
             if (STATS == 1) ws.inner_steps += (uint32_t)kMegaUnroll; // (timing only: steps of either kind, counted per loop iteration)
             refill.stepped();
-            (void)trav_step_wave<(STATS >= 2), true, true>(S, T, stack, top, sg, trav_classes(T, done), &ws); // the exit test's mask gives this step its leaf class
+            // (MISS_KEYS: without the +inf keys hipcc spills six registers more in the round of <0, true, 0>: -0.6 %, profiles/inner_step_masks_bench.txt)
+            (void)trav_step_wave<(STATS >= 2), true, true, true>(S, T, stack, top, sg, trav_classes(T, done), &ws); // the exit test's mask gives this step its leaf class
 #pragma unroll
-            for (int k = 1; k < kMegaUnroll; ++k) (void)trav_step_wave<(STATS >= 2), true, true>(S, T, stack, top, sg, &ws); // the exit test is checked every kMegaUnroll steps
+            for (int k = 1; k < kMegaUnroll; ++k) (void)trav_step_wave<(STATS >= 2), true, true, true>(S, T, stack, top, sg, &ws); // the exit test is checked every kMegaUnroll steps
         }
         if (STATS) {
             ws.shade_rounds++;

@@ -439,6 +439,74 @@ int  rt_lightmap_filter(rt_lightmap* lm, const rt_lightmap_filter_params* f, con
 int  rt_lightmap_filter_device(rt_lightmap* lm, const rt_lightmap_filter_params* f, const void* d_rgba, const void* d_variance,
                                void* d_out_rgba, void* d_out_variance, void* stream);
 
+/* ---- Irradiance probe volumes: nine spherical-harmonic coefficients (bands 0 to 2) of the arriving radiance at every probe of a regular
+ * grid, baked around one path query on one stream, and sampled at caller-supplied points: light for what has no parametrisation of its own
+ * (moving objects, particles, a mesh dropped into a baked scene). Probe p = (iz * count[1] + iy) * count[0] + ix sits at
+ * origin + ((float)ix, (float)iy, (float)iz) * spacing, one fp32 multiply and one add per axis. A table is probes * 9 float4: coefficient k
+ * of probe p at float4 p * 9 + k, rgb in .xyz; the .w of coefficient 0 is the probe's validity (1.0f or 0.0f), the other .w are 0, so one
+ * probe is 144 contiguous bytes. Every operation below is one R1 fp32 operation of DESIGN.md §3, left to right as bracketed, never
+ * contracted; sqrt and the divisions are correctly rounded; there is no transcendental function. next(a) is the renderers' xorshift32 draw.
+ *   1. Entries. Probe p and direction j make entry e = p * dirs + j with the probe's position and the state
+ *      (seed + (e + 1) * 0x9E3779B9) mod 2^32, 0 replaced by 0x9E3779B9 (the lightmap's rule).
+ *   2. Direction, uniform on the sphere (Marsaglia 1972), drawn from the entry's state a. At most 8 tries: x1 = -1.0f + 2.0f * next(a), then
+ *      x2 likewise, s = x1 * x1 + x2 * x2; the first try with s < 1.0f ends them. If all 8 were rejected (about 4.5e-6 of the entries), the
+ *      last pair is scaled, x1 = x1 * 0.70710677f and x2 likewise, and s recomputed: it is then at most 1, and the 16 draws stay taken.
+ *      r = sqrt(1.0f - s); d = ((2.0f * x1) * r, (2.0f * x2) * r, 1.0f - 2.0f * s). The state after these draws is the entry's path state.
+ *   3. Paths. One rt_trace_paths_device over the probes * dirs entries (org = the position, dir = d, rng = the path state): samples = 1,
+ *      max_depth and rr_start as given, rng_out NULL, rays kept. A probe outside the contract range is rejected there, all its entries
+ *      together; it is then INVALID: its nine coefficients are 0 and its validity is 0.
+ *   4. Projection. For a valid probe, coefficient k and channel c: C = +0; for j = 0 .. dirs-1 in order, C = C + radiance[e][c] * Y_k(d_e),
+ *      d_e the fp32 direction of step 2 (not the half the path query stores); coef = C * (12.566371f / (float)dirs). With (x, y, z) = d:
+ *        Y0 = 0.2820948f                Y1 = 0.48860252f * y             Y2 = 0.48860252f * z
+ *        Y3 = 0.48860252f * x           Y4 = 1.0925485f * (x * y)        Y5 = 1.0925485f * (y * z)
+ *        Y6 = 0.31539157f * (3.0f * (z * z) - 1.0f)                      Y7 = 1.0925485f * (x * z)
+ *        Y8 = 0.54627424f * (x * x - y * y)
+ *      One lane owns one (probe, k) and sums its directions in order: no cross-lane reduction, no atomics. Non-finite radiance does what
+ *      the arithmetic gives.
+ *   5. Stats: probes, valid, and rays = the sum of the entries' ray counts over the valid probes. d_stats holds the same 16 bytes.
+ *   6. Sample, per point q with normal n (used as given, as the gather's is). Per axis: g = (q - origin) / spacing, g = fmin(fmax(g, 0.0f),
+ *      (float)(count - 1)); i0 = min((int)g, count - 2), or 0 when count == 1; f = g - (float)i0; the weights are (1.0f - f, f). The eight
+ *      corners in z-outer, y, x-inner order, corner weight w = (wx * wy) * wz; an invalid probe, and the upper corner of an axis with
+ *      count == 1, are skipped. W and S_k (per channel) sum w and w * coef_k in corner order from +0; C_k = S_k / W; W == 0 gives (0, 0, 0).
+ *      E = +0; for k = 0 .. 8: E = E + (B_k * C_k) * Y_k(n), B = 1.0f (k = 0), 0.6666667f (k = 1 .. 3), 0.25f (k = 4 .. 8): Ramamoorthi and
+ *      Hanrahan's cosine-lobe factors over pi. out = fmaxf(E, 0.0f). A point or normal with a component that is not finite gives three NaNs.
+ * The result is irradiance over pi: what a white Lambertian surface there would scatter. albedo x result is the caller's, the convention of
+ * the gather and the lightmap. A point outside the volume is clamped onto it.
+ * rt_probe_volume_entries[_device] return steps 1 and 2: pos, dir (3 * probes * dirs floats each) and state (probes * dirs words); any may be
+ * NULL, not all three. rt_probe_volume_bake[_device] run steps 1 to 5; the table stays in the volume, and out_sh (probes * 36 floats; the device
+ * pointer 16-byte aligned) receives a copy when it is not NULL; stats / d_stats may be NULL. rt_probe_volume_set_sh[_device] load a table
+ * (a saved bake, or a synthetic one) and rt_probe_volume_get_sh[_device] copy it out. rt_probe_volume_sample[_device] run step 6 on n points:
+ * pos, normal and out_rgb are 3n floats each; n == 0 is RT_OK with nothing launched.
+ * The volume owns every device buffer it needs, allocated by rt_probe_volume_create: no later call allocates. Per entry, max_dirs of them per
+ * probe: pos, dir, state, radiance and ray count (12 + 12 + 4 + 12 + 4 = 44 bytes); per probe the table's 144 bytes; and 65,536 x 36 bytes
+ * through which the host form of sample stages its points a piece at a time. The host forms run on the volume's stream and synchronise; the
+ * device forms enqueue on `stream` (NULL = the null stream) and return. Calls on one volume are serialised by the volume: each records an
+ * event that the next call's stream waits for. The bake records the scene's per-stream event through rt_trace_paths_device, so
+ * rt_scene_update waits for it, and a bake after an update sees the moved geometry. A volume is destroyed before its scene.
+ * Refused with RT_ERR_INVALID before any HIP call, in this order: NULL handles or required pointers; a count outside 1 .. 256; a spacing that
+ * is not finite or not > 0; an origin that is not finite; max_dirs outside 1 .. 65536; probes * max_dirs >= 2^31; flags other than 0;
+ * dirs == 0 or dirs > max_dirs; max_depth == 0; sample or get_sh before any bake or set_sh. After these, rt_probe_volume_create returns
+ * RT_ERR_NO_DEVICE for a host-only scene.
+ * Limits: the validity flag is the only visibility handling (no depth moments, so light leaks through thin walls between probes); a probe
+ * inside a solid is valid and dark, not moved; bands 0 to 2 only, no L1-only table; no windowing against ringing; a bake is whole, not
+ * incremental; one device. */
+typedef struct rt_probe_volume rt_probe_volume;
+typedef struct rt_probe_volume_desc { float origin[3]; float spacing[3]; uint32_t count[3]; uint32_t max_dirs; } rt_probe_volume_desc; /* 40 bytes */
+typedef struct rt_probe_bake_params { uint32_t dirs, max_depth, rr_start, seed; } rt_probe_bake_params;                              /* 16 bytes */
+typedef struct rt_probe_stats       { uint32_t probes, valid; uint64_t rays; } rt_probe_stats;                                      /* 16 bytes */
+int  rt_probe_volume_create(rt_scene* scene, const rt_probe_volume_desc* desc, uint32_t flags, rt_probe_volume** out);
+void rt_probe_volume_destroy(rt_probe_volume* vol);
+int  rt_probe_volume_entries(rt_probe_volume* vol, const rt_probe_bake_params* p, float* pos, float* dir, uint32_t* state);
+int  rt_probe_volume_entries_device(rt_probe_volume* vol, const rt_probe_bake_params* p, void* d_pos, void* d_dir, void* d_state, void* stream);
+int  rt_probe_volume_bake(rt_probe_volume* vol, const rt_probe_bake_params* p, float* out_sh, rt_probe_stats* stats);
+int  rt_probe_volume_bake_device(rt_probe_volume* vol, const rt_probe_bake_params* p, void* d_out_sh, void* d_stats, void* stream);
+int  rt_probe_volume_set_sh(rt_probe_volume* vol, const float* sh);
+int  rt_probe_volume_set_sh_device(rt_probe_volume* vol, const void* d_sh, void* stream);
+int  rt_probe_volume_get_sh(rt_probe_volume* vol, float* sh);
+int  rt_probe_volume_get_sh_device(rt_probe_volume* vol, void* d_sh, void* stream);
+int  rt_probe_volume_sample(rt_probe_volume* vol, uint32_t n, const float* pos, const float* normal, float* out_rgb);
+int  rt_probe_volume_sample_device(rt_probe_volume* vol, uint32_t n, const void* d_pos, const void* d_normal, void* d_out_rgb, void* stream);
+
 /* ---- Renderers: == IRenderer implementations (src/render.hpp:11-18) ------------------------ */
 enum {
     RT_RENDERER_MEGAKERNEL = 0, /* MegakernelRenderer (src/render_megakernel.hpp:13-19) */

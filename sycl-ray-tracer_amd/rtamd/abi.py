@@ -263,6 +263,32 @@ class rt_lightmap_filter_params(C.Structure):
     ]
 
 
+class rt_probe_volume_desc(C.Structure):
+    _fields_ = [
+        ("origin", C.c_float * 3),
+        ("spacing", C.c_float * 3),
+        ("count", C.c_uint32 * 3),
+        ("max_dirs", C.c_uint32),
+    ]
+
+
+class rt_probe_bake_params(C.Structure):
+    _fields_ = [
+        ("dirs", C.c_uint32),
+        ("max_depth", C.c_uint32),
+        ("rr_start", C.c_uint32),
+        ("seed", C.c_uint32),
+    ]
+
+
+class rt_probe_stats(C.Structure):
+    _fields_ = [
+        ("probes", C.c_uint32),
+        ("valid", C.c_uint32),
+        ("rays", C.c_uint64),
+    ]
+
+
 RT_LIGHTMAP_FILTER = 1
 RT_LIGHTMAP_MAX_SIZE = 8192
 RT_LIGHTMAP_MAX_DILATE = 16
@@ -271,6 +297,9 @@ assert C.sizeof(rt_ray_query) == 72
 assert C.sizeof(rt_lightmap_params) == 24
 assert C.sizeof(rt_lightmap_stats) == 24
 assert C.sizeof(rt_lightmap_filter_params) == 16
+assert C.sizeof(rt_probe_volume_desc) == 40
+assert C.sizeof(rt_probe_bake_params) == 16
+assert C.sizeof(rt_probe_stats) == 16
 assert C.sizeof(rt_path_query) == 64
 assert C.sizeof(rt_gather_query) == 64
 assert C.sizeof(rt_denoise_params) == 20
@@ -314,6 +343,18 @@ PROTOTYPES = {
     "rt_lightmap_filter": (C.c_int, [C.c_void_p, _P(rt_lightmap_filter_params), _P(C.c_float), _P(C.c_float), _P(C.c_float), _P(C.c_float)]),
     "rt_lightmap_filter_device": (C.c_int, [C.c_void_p, _P(rt_lightmap_filter_params), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.c_void_p]),
+    "rt_probe_volume_create": (C.c_int, [C.c_void_p, _P(rt_probe_volume_desc), C.c_uint32, _P(C.c_void_p)]),
+    "rt_probe_volume_destroy": (None, [C.c_void_p]),
+    "rt_probe_volume_entries": (C.c_int, [C.c_void_p, _P(rt_probe_bake_params), _P(C.c_float), _P(C.c_float), _P(C.c_uint32)]),
+    "rt_probe_volume_entries_device": (C.c_int, [C.c_void_p, _P(rt_probe_bake_params), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_probe_volume_bake": (C.c_int, [C.c_void_p, _P(rt_probe_bake_params), _P(C.c_float), _P(rt_probe_stats)]),
+    "rt_probe_volume_bake_device": (C.c_int, [C.c_void_p, _P(rt_probe_bake_params), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_probe_volume_set_sh": (C.c_int, [C.c_void_p, _P(C.c_float)]),
+    "rt_probe_volume_set_sh_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_probe_volume_get_sh": (C.c_int, [C.c_void_p, _P(C.c_float)]),
+    "rt_probe_volume_get_sh_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_probe_volume_sample": (C.c_int, [C.c_void_p, C.c_uint32, _P(C.c_float), _P(C.c_float), _P(C.c_float)]),
+    "rt_probe_volume_sample_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rt_renderer_create": (C.c_int, [C.c_int, C.c_void_p, C.c_int32, C.c_int32, C.c_uint32, C.c_uint32,
                                      C.c_uint32, _P(C.c_void_p)]),
     "rt_renderer_destroy": (None, [C.c_void_p]),

@@ -83,3 +83,28 @@ def triangle_grid_uvs(n_triangles: int, width: int, height: int, gutter: int = 1
     uv = np.stack([px / f32(w), py / f32(h)], 2)
     assert uv.dtype == f32
     return np.ascontiguousarray(uv)
+
+
+def probe_grid(sd: SceneDesc, spacing: float, margin: float = 0.0):
+    """A probe grid for renderer.ProbeVolume fitted to the scene's bounds: (origin (3,) float32, count (3,) of int). The probes start
+    `margin` inside the low corner of the world triangles' bounds and step by `spacing` while they stay `margin` inside the high corner; an
+    axis thinner than 2 * margin gets one probe at its middle. Raises ValueError where an axis would need more than 256 probes."""
+    if not spacing > 0 or margin < 0:
+        raise ValueError("spacing must be above 0, margin not negative")
+    v = np.asarray(sd.world_triangles(), np.float64).reshape(-1, 3)
+    if len(v) == 0:
+        raise ValueError("the scene has no triangles to fit a grid to")
+    lo, hi = v.min(0) + margin, v.max(0) - margin
+    thin = hi < lo
+    lo = np.where(thin, 0.5 * (lo + hi), lo)
+    count = np.where(thin, 1, np.floor((hi - lo) / spacing + 1e-9).astype(np.int64) + 1)
+    if (count > 256).any():
+        raise ValueError(f"spacing {spacing} needs {int(count.max())} probes on an axis: 256 at most")
+    return lo.astype(f32), tuple(int(c) for c in count)
+
+
+def shade_vertices_from_volume(volume, sd: SceneDesc) -> np.ndarray:
+    """bake_vertices' counterpart for a mesh that is NOT in the baked scene: the probe volume's irradiance over pi at every triangle corner
+    of `sd` for its shading normal, (T, 3, 3) float32 [triangle, corner, rgb], one ProbeVolume.sample call over vertex_points(sd)."""
+    pos, nrm = vertex_points(sd)
+    return volume.sample(pos.reshape(-1, 3), nrm.reshape(-1, 3)).reshape(-1, 3, 3)

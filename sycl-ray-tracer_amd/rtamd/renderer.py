@@ -733,6 +733,121 @@ class Lightmap:
             pass
 
 
+class ProbeVolume:
+    """rt_probe_volume: a count[0] x count[1] x count[2] grid of irradiance probes over `scene`, nine spherical-harmonic coefficients each
+    (include/rt_mi355x.h: rt_probe_volume_bake). Probe (ix, iy, iz) sits at origin + (ix, iy, iz) * spacing; `spacing` is one number or one
+    per axis. max_dirs: the most directions per probe a bake may ask for (rtamd.bake.probe_grid fits origin and count to a scene). A table
+    is (probes, 9, 4) float32, probe index (iz * count[1] + iy) * count[0] + ix, validity in [:, 0, 3]. Close it before its scene."""
+
+    def __init__(self, scene: Scene, origin, spacing, count, max_dirs: int = 64):
+        origin, count = np.asarray(origin, np.float64), np.asarray(count)
+        spacing = np.asarray(spacing, np.float64)
+        if spacing.ndim == 0:
+            spacing = np.repeat(spacing, 3)
+        if origin.shape != (3,) or spacing.shape != (3,):
+            raise ValueError("origin must hold 3 numbers, spacing 1 or 3")
+        if count.shape != (3,) or count.dtype.kind not in "ui":
+            raise ValueError("count must hold 3 integers")
+        if (count < 0).any() or (count > 0xFFFFFFFF).any() or not 0 <= int(max_dirs) <= 0xFFFFFFFF:
+            raise ValueError("count and max_dirs must fit 32 unsigned bits")
+        self._lib = scene._lib
+        self.scene = scene
+        self.desc = abi.rt_probe_volume_desc((C.c_float * 3)(*origin), (C.c_float * 3)(*spacing), (C.c_uint32 * 3)(*[int(c) for c in count]),
+                                             int(max_dirs))
+        self.origin, self.spacing = np.array(list(self.desc.origin), np.float32), np.array(list(self.desc.spacing), np.float32)
+        self.count, self.max_dirs = tuple(int(c) for c in count), int(max_dirs)
+        self.probes = self.count[0] * self.count[1] * self.count[2]
+        self.h = C.c_void_p()
+        abi.check(self._lib.rt_probe_volume_create(scene.h, C.byref(self.desc), 0, C.byref(self.h)), self._lib)
+
+    @staticmethod
+    def _params(dirs, max_depth, rr_start, seed):
+        return abi.rt_probe_bake_params(int(dirs), int(max_depth), int(rr_start), int(seed) & 0xFFFFFFFF)
+
+    def positions(self) -> np.ndarray:
+        """The probes' positions, (probes, 3) float32, in the contract's arithmetic (one fp32 multiply and one add per axis)."""
+        iz, iy, ix = np.meshgrid(*(np.arange(c) for c in self.count[::-1]), indexing="ij")
+        idx = np.stack([ix, iy, iz], -1).reshape(-1, 3).astype(np.float32)
+        return self.origin[None, :] + idx * self.spacing[None, :]
+
+    def entries(self, dirs: int, seed: int) -> dict:
+        """rt_probe_volume_entries: {"pos": (probes * dirs, 3) float32, "dir": (probes * dirs, 3) float32, the uniform directions, "state":
+        (probes * dirs,) uint32, the states the paths start with}, entry e = p * dirs + j."""
+        n = self.probes * max(int(dirs), 0)
+        out = {"pos": np.zeros((n, 3), np.float32), "dir": np.zeros((n, 3), np.float32), "state": np.zeros(n, np.uint32)}
+        p = self._params(dirs, 1, 0, seed)
+        abi.check(self._lib.rt_probe_volume_entries(self.h, C.byref(p), abi.fptr(out["pos"]), abi.fptr(out["dir"]), abi.u32ptr(out["state"])),
+                  self._lib)
+        return out
+
+    def entries_device(self, dirs: int, seed: int, d_pos: int = 0, d_dir: int = 0, d_state: int = 0, stream: int = 0) -> None:
+        """rt_probe_volume_entries_device on DEVICE pointers (e.g. torch .data_ptr()), enqueued on `stream`; 0 = NULL (not written)."""
+        p = self._params(dirs, 1, 0, seed)
+        v = [C.c_void_p(x or None) for x in (d_pos, d_dir, d_state, stream)]
+        abi.check(self._lib.rt_probe_volume_entries_device(self.h, C.byref(p), *v), self._lib)
+
+    def bake(self, dirs: int, max_depth: int, rr_start: int = 0, seed: int = 0):
+        """rt_probe_volume_bake -> (sh (probes, 9, 4) float32, {"probes", "valid", "rays"}); the table also stays in the volume."""
+        p = self._params(dirs, max_depth, rr_start, seed)
+        sh = np.zeros((self.probes, 9, 4), np.float32)
+        st = abi.rt_probe_stats()
+        abi.check(self._lib.rt_probe_volume_bake(self.h, C.byref(p), abi.fptr(sh), C.byref(st)), self._lib)
+        return sh, {"probes": st.probes, "valid": st.valid, "rays": st.rays}
+
+    def bake_device(self, dirs: int, max_depth: int, rr_start: int = 0, seed: int = 0, d_sh: int = 0, d_stats: int = 0, stream: int = 0) -> None:
+        """rt_probe_volume_bake_device, enqueued on `stream`: d_sh probes * 36 floats or 0, d_stats 16 bytes (rt_probe_stats) or 0."""
+        p = self._params(dirs, max_depth, rr_start, seed)
+        v = [C.c_void_p(x or None) for x in (d_sh, d_stats, stream)]
+        abi.check(self._lib.rt_probe_volume_bake_device(self.h, C.byref(p), *v), self._lib)
+
+    def set_sh(self, sh: np.ndarray) -> None:
+        """rt_probe_volume_set_sh: load a (probes, 9, 4) float32 table (a saved bake, or a synthetic one)."""
+        if not isinstance(sh, np.ndarray) or sh.dtype != np.float32 or sh.shape != (self.probes, 9, 4):
+            raise ValueError(f"sh must be a float32 array of shape ({self.probes}, 9, 4)")
+        sh = np.ascontiguousarray(sh)
+        abi.check(self._lib.rt_probe_volume_set_sh(self.h, abi.fptr(sh)), self._lib)
+
+    def set_sh_device(self, d_sh: int, stream: int = 0) -> None:
+        abi.check(self._lib.rt_probe_volume_set_sh_device(self.h, C.c_void_p(d_sh or None), C.c_void_p(stream or None)), self._lib)
+
+    def get_sh(self) -> np.ndarray:
+        sh = np.zeros((self.probes, 9, 4), np.float32)
+        abi.check(self._lib.rt_probe_volume_get_sh(self.h, abi.fptr(sh)), self._lib)
+        return sh
+
+    def get_sh_device(self, d_sh: int, stream: int = 0) -> None:
+        abi.check(self._lib.rt_probe_volume_get_sh_device(self.h, C.c_void_p(d_sh or None), C.c_void_p(stream or None)), self._lib)
+
+    def sample(self, pos: np.ndarray, normal: np.ndarray) -> np.ndarray:
+        """rt_probe_volume_sample: pos, normal (n, 3) -> (n, 3) float32, irradiance over pi at the points for those normals (used as
+        given): what a white Lambertian surface there would scatter."""
+        pos, normal = np.asarray(pos), np.asarray(normal)
+        if pos.ndim != 2 or pos.shape[1] != 3 or normal.shape != pos.shape:
+            raise ValueError("pos and normal must both be (n, 3)")
+        if pos.dtype.kind != "f" or normal.dtype.kind != "f":
+            raise ValueError("pos and normal must be floating-point arrays")
+        pos, normal = np.ascontiguousarray(pos, np.float32), np.ascontiguousarray(normal, np.float32)
+        out = np.zeros(pos.shape, np.float32)
+        abi.check(self._lib.rt_probe_volume_sample(self.h, pos.shape[0], abi.fptr(pos), abi.fptr(normal), abi.fptr(out)), self._lib)
+        return out
+
+    def sample_device(self, n: int, d_pos: int, d_normal: int, d_rgb: int, stream: int = 0) -> None:
+        """rt_probe_volume_sample_device on DEVICE pointers, 3n floats each, enqueued on `stream`."""
+        v = [C.c_void_p(x or None) for x in (d_pos, d_normal, d_rgb, stream)]
+        abi.check(self._lib.rt_probe_volume_sample_device(self.h, int(n), *v), self._lib)
+
+    def close(self):
+        if self.h:
+            self._lib.rt_probe_volume_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 # The denoiser's defaults (DESIGN.md §13: chosen by scripts/denoise_probe.py's sweep on the atrium and the Cornell box). sigma_position is
 # DENOISE_POSITION_FRACTION of the scene's scale (Scene.scale()); host/main.cpp's --denoise uses the same values.
 DENOISE_ITERATIONS = 5

@@ -237,6 +237,61 @@ typedef struct rt_ray_query {
 int rt_trace_rays(rt_scene* scene, const rt_ray_query* q);
 int rt_trace_rays_device(rt_scene* scene, const rt_ray_query* q, void* stream);
 
+/* ---- Closest-point queries: the nearest triangle to caller-supplied points (probe clearance, texels under another surface, collision of
+ * dynamic objects and particles, distance fields). The ABI is SQUARED throughout — no square root appears anywhere — so that a caller can
+ * place a radius exactly on a result.
+ * The contract (csrc/rt_closest_point.h, one text for the kernel and the host walk). For a point p and a triangle as the kernels hold it,
+ * (v0, e1 = v1 - v0, e2 = v2 - v0), Ericson's region walk, every operation ONE fp32 operation evaluated left to right as bracketed, never
+ * contracted; dot(a, b) = (ax*bx + ay*by) + az*bz; divisions correctly rounded:
+ *     ap = p - v0;  d1 = dot(e1, ap);  d2 = dot(e2, ap)
+ *     bp = ap - e1; d3 = dot(e1, bp);  d4 = dot(e2, bp)
+ *     cp = ap - e2; d5 = dot(e1, cp);  d6 = dot(e2, cp)
+ *     vc = d1*d4 - d3*d2;  vb = d5*d2 - d1*d6;  va = d3*d6 - d5*d4
+ *     the first region that holds, in this order:
+ *       d1 <= 0 && d2 <= 0                         (u, v) = (0, 0)
+ *       d3 >= 0 && d4 <= d3                        (1, 0)
+ *       vc <= 0 && d1 >= 0 && d3 <= 0              (d1 / (d1 - d3), 0)
+ *       d6 >= 0 && d5 <= d6                        (0, 1)
+ *       vb <= 0 && d2 >= 0 && d6 <= 0              (0, d2 / (d2 - d6))
+ *       va <= 0 && (d4-d3) >= 0 && (d5-d6) >= 0    w = (d4-d3) / ((d4-d3) + (d5-d6)); (1.0f - w, w)
+ *       else                                       den = (va + vb) + vc; (vb / den, vc / den)
+ *     r = (ap - u*e1) - v*e2   (per component);   dist2 = dot(r, r);   point = p - r
+ * (u, v) are barycentrics along e1 / e2, as rt_intersect_batch returns them. A triangle COUNTS iff dist2 <= max_dist2[i]; a NaN dist2 never
+ * counts (a degenerate triangle can give one). The winner is the lowest dist2, ties to the lowest global triangle index. The result is the
+ * brute-force minimum of this expression over all triangles, bit for bit: the tree only culls.
+ *   A miss (nothing counts): dist2 = +inf, u = v = 0, tri = 0xFFFFFFFF, point = three quiet NaNs.
+ *   max_dist2 == NULL means +inf for every entry; a negative max_dist2 is a miss (-0.0 admits dist2 == 0).
+ * THE LIMIT: the result is this arithmetic, not the real closest point. On slivers the point lies on the triangle but may not be the
+ * nearest point of it (measured on the CPU: thousands of ulp of the scene scale where |e1||e2| / |e1 x e2| is about 10^4). Bounded for every
+ * triangle, slivers included, is the other side: sqrt(dist2) >= d_true - 8 * 2^-24 * (|ap| + |e1| + |e2|), and the cull leans on it alone.
+ * Rejected entries: a pos outside the contract range or not finite (rt_intersect_batch), or a NaN max_dist2. rt_closest_points returns
+ * RT_ERR_INVALID naming the first of them and writes nothing; rt_closest_points_device marks each instead — dist2 = NaN, tri =
+ * RT_TRI_REJECTED (u, v, point unwritten) — and answers the others.
+ * n == 0: RT_OK, nothing launched. RT_ERR_INVALID: NULL scene, query or pos, every output NULL; RT_ERR_NO_DEVICE: a host-only scene (the
+ * arguments are checked first). Any output may be NULL: it is not written.
+ * rt_closest_points takes host arrays, stages them through device buffers, runs on the null stream and synchronises.
+ * rt_closest_points_device takes device arrays and behaves as rt_trace_rays_device does: no allocation, no synchronisation, no host copy;
+ * it shares the scene's cursors and per-stream event with the other queries, and rt_scene_update waits for it. */
+typedef struct rt_point_query {
+    uint32_t n;
+    const float* pos;        /* 3n, xyz per point                                       */
+    const float* max_dist2;  /* n squared radii, or NULL = +inf for every entry          */
+    float* dist2;            /* n each; NULL = not written                              */
+    float* u;
+    float* v;
+    uint32_t* tri;
+    float* point;            /* 3n                                                      */
+} rt_point_query;
+int rt_closest_points(rt_scene* scene, const rt_point_query* q);
+int rt_closest_points_device(rt_scene* scene, const rt_point_query* q, void* stream);
+/* Diagnostic, host only (works on a scene built with device < 0; brings the host copy of an updated device scene up to date first): the
+ * same queries on the host. use_bvh = 0: the brute force over the triangles with the contract's text. use_bvh = 1: the walk the kernel
+ * makes — the decoded child boxes, its cull rule and child order — counting node visits and triangle tests (either may be NULL). Entries are
+ * not refused here (a NaN max_dist2 is a miss); any output may be NULL; max_dist2 NULL = +inf. This is how the cull is shown conservative
+ * without a GPU, and the expected side of the GPU tests. */
+int rt_scene_closest_host(const rt_scene* scene, uint32_t n, const float* pos, const float* max_dist2, int use_bvh, float* dist2, float* u,
+                          float* v, uint32_t* tri, float* point, uint64_t* node_visits, uint64_t* tri_tests);
+
 /* ---- Path queries: radiance along caller-supplied rays (light probes, irradiance volumes, baking, reflection captures, radiance caches).
  * Entry i runs `samples` paths of at most `max_depth` rays from (org[i], dir[i]) with the renderers' own bounce (materials, textures, sky,
  * Russian roulette) on the xorshift32 state rng[i], each path continuing the state the one before left:

@@ -1,0 +1,295 @@
+// rt_closest.hip — closest-point queries: rt_closest_points[_device], the nearest triangle to caller-supplied points, their kernel k_closest
+// and the C entry of the host diagnostic rt_scene_closest_host (the walk itself: scene_check.cpp: closest_host).
+// (A unit of its own, as rt_query.hip is: the render kernels' listings do not change. The contract — the fp32 text of one candidate, the
+// winner rule and the cull — is rt_closest_point.h, shared with the host walk. DESIGN.md §22.)
+#include "rt_query_launch.h"
+#include "rt_device.h"
+#include "rt_closest_point.h"
+
+namespace rt {
+
+constexpr uint32_t kClosestBlock = 512; // threads per workgroup: 8 independent waves share one LDS copy of the top of the BVH (as k_query)
+constexpr uint32_t kClosestWaves = 6;   // waves per SIMD the kernel is compiled for: three workgroups' LDS fill a CU (46,400 bytes each)
+constexpr uint32_t kClosestRefill = 16; // idle lanes of a wave that end its traversal phase: they write their results and take new points
+
+// what a launch reads and writes (include/rt_mi355x.h: rt_point_query; NULL outputs are not written)
+struct PointDev {
+    const float* pos;
+    const float* max_dist2;
+    float* dist2;
+    float* u;
+    float* v;
+    uint32_t* tri;
+    float* point;
+    unsigned long long* cursor; // kQueryHeads shard cursors, kQueryHeadStride words apart; 0 at the launch (reset on its stream)
+    unsigned long long n;
+    ContractRange range; // rt_frame.hip: contract_range of the scene
+};
+
+// The traversal state is the ray traversal's (rt_device.h: Trav), so that the stack helpers take it: o = the point, best.t = the winner's
+// dist2 (max_dist2 until a triangle counts), best.u / v / tri = the winner's; the ray's other fields are never written or read. `r` beside
+// it: p - point of the winner (the point is formed where the result is written).
+RT_DEV void closest_begin(Trav& T, f3 p, float max_dist2, const TravStack& st) {
+    T.o = p;
+    T.best.t = max_dist2;
+    T.best.u = T.best.v = 0.0f;
+    T.best.tri = kNoTri;
+    T.cur = 0; // root
+    T.sp = stack_base(st);
+}
+
+// Inner step. The node from the LDS top or from memory (plain loads); per child the two decoded planes per axis (child_plane's value: q * s is
+// exact, so the fma rounds once, as origin + q * s does), e = max(lo - p, p - hi, 0), lb = e . e (fused: cull arithmetic). A child is
+// entered iff its WORD says it exists and closest_enters(lb, best): an absent child's inverted box (qlo = 255, qhi = 0) misses every ray by
+// itself but gives a point a finite lb, and its word, kChildEmpty, is kTravDone — descending into it would end the lane's traversal with a
+// wrong answer. A child not entered carries +inf and sinks to the end of the sorting network (five comparators: a full sort, nearest
+// first; an entered child's key is clamped below +inf); the others are pushed far to near, three pushes at most, with trav_inner's
+// unconditional writes where every lane of the step stays inside the LDS part of its stack.
+RT_DEV void closest_inner(const SceneDev& S, Trav& T, const TravStack& stack, const TopTree& top) {
+    const float inf = __builtin_huge_valf();
+    u32x4 w0, w1, w2, chw;
+    if (T.cur < top.count * 64) { // top of the tree: LDS, 16 bytes per node and plane
+        const uint32_t o = (uint32_t)T.cur >> 2;
+        w0 = *(lds_u32x4*)(size_t)((uint32_t)(size_t)top.w0 + o), w1 = *(lds_u32x4*)(size_t)((uint32_t)(size_t)top.w1 + o);
+        w2 = *(lds_u32x4*)(size_t)((uint32_t)(size_t)top.w2 + o), chw = *(lds_u32x4*)(size_t)((uint32_t)(size_t)top.ch + o);
+    } else {
+        const u32x4* np = reinterpret_cast<const u32x4*>(reinterpret_cast<const uint8_t*>(S.nodes) + (uint32_t)T.cur);
+        w0 = np[0], w1 = np[1], w2 = np[2], chw = np[3];
+    }
+    const float gx = __uint_as_float(w0.x), gy = __uint_as_float(w0.y), gz = __uint_as_float(w0.z);
+    const float sx = __builtin_fabsf(__uint_as_float(w0.w)), sy = __builtin_fabsf(__uint_as_float(w2.z)), sz = __builtin_fabsf(__uint_as_float(w2.w));
+    const float best = T.best.t;
+    float k0, k1, k2, k3;
+#define RT_CHILD(K, CVT, CW)                                                                              \
+    {                                                                                                    \
+        const float ex = __builtin_fmaxf(__builtin_fmaxf(__builtin_fmaf(CVT(w1.x), sx, gx) - T.o.x, T.o.x - __builtin_fmaf(CVT(w1.y), sx, gx)), 0.0f); \
+        const float ey = __builtin_fmaxf(__builtin_fmaxf(__builtin_fmaf(CVT(w1.z), sy, gy) - T.o.y, T.o.y - __builtin_fmaf(CVT(w1.w), sy, gy)), 0.0f); \
+        const float ez = __builtin_fmaxf(__builtin_fmaxf(__builtin_fmaf(CVT(w2.x), sz, gz) - T.o.z, T.o.z - __builtin_fmaf(CVT(w2.y), sz, gz)), 0.0f); \
+        const float lb = __builtin_fmaf(ez, ez, __builtin_fmaf(ey, ey, ex * ex));                        \
+        const bool enter = (int32_t)(CW) != kChildEmpty && closest_enters(lb, best);                     \
+        K = sel(lanes(enter), inf, __builtin_fminf(lb, __FLT_MAX__));                                    \
+    }
+    RT_CHILD(k0, ub0, chw.x)
+    RT_CHILD(k1, ub1, chw.y)
+    RT_CHILD(k2, ub2, chw.z)
+    RT_CHILD(k3, ub3, chw.w)
+#undef RT_CHILD
+    int32_t c0 = (int32_t)chw.x, c1 = (int32_t)chw.y, c2 = (int32_t)chw.z, c3 = (int32_t)chw.w;
+#define RT_CE(KA, CA, KB, CB)                                                        \
+    {                                                                               \
+        const lmask sw = lanes(KB < KA);                                            \
+        const float ka = sel(sw, KA, KB), kb = sel(sw, KB, KA);                     \
+        const int32_t ca = sel(sw, CA, CB), cb = sel(sw, CB, CA);                   \
+        KA = ka, KB = kb, CA = ca, CB = cb;                                         \
+    }
+    RT_CE(k0, c0, k1, c1)
+    RT_CE(k2, c2, k3, c3)
+    RT_CE(k0, c0, k2, c2)
+    RT_CE(k1, c1, k3, c3)
+    RT_CE(k1, c1, k2, c2)
+#undef RT_CE
+    const bool descend = k0 < inf;
+    if (lanes(!stack_shallow(stack, T, 3u)) == 0ull) { // every lane of this step: LDS only
+        *lds_at(T.sp) = c3; // farthest first; the word is written in any case, only the stack pointer depends on the key
+        T.sp = sel(lanes(k3 < inf), T.sp, T.sp + stack.pitch);
+        *lds_at(T.sp) = c2;
+        T.sp = sel(lanes(k2 < inf), T.sp, T.sp + stack.pitch);
+        *lds_at(T.sp) = c1;
+        T.sp = sel(lanes(k1 < inf), T.sp, T.sp + stack.pitch);
+        if (descend) T.cur = c0;
+        else trav_pop_lds(T, stack);
+    } else {
+        if (k3 < inf) stk_push(stack, T, c3);
+        if (k2 < inf) stk_push(stack, T, c2);
+        if (k1 < inf) stk_push(stack, T, c1);
+        if (descend) T.cur = c0;
+        else trav_pop(T, stack);
+    }
+}
+
+// one candidate: the contract's text on the record's ten live dwords, then the winner rule
+RT_DEV void closest_test_regs(float4 a, float4 b, float2 c, Trav& T, f3& r) {
+    const float p[3] = {T.o.x, T.o.y, T.o.z};
+    const float v0[3] = {a.x, a.y, a.z}, e1[3] = {a.w, b.x, b.y}, e2[3] = {b.z, b.w, c.x};
+    const uint32_t gidx = __float_as_uint(c.y);
+    const ClosestPoint cand = closest_point_on_record(p, v0, e1, e2);
+    if (closest_better(cand.dist2, gidx, T.best.t, T.best.tri)) {
+        T.best.t = cand.dist2, T.best.u = cand.u, T.best.v = cand.v, T.best.tri = gidx;
+        r = mk3(cand.r[0], cand.r[1], cand.r[2]);
+    }
+}
+
+// Leaf step: the whole leaf (1-2 records) as trav_leaf<true> reads it — five unconditional 16-byte loads of 80 contiguous bytes (a leaf of
+// one record reads 40 bytes of its neighbour and ignores them; the buffer ends in 48 bytes of padding) — then one or two candidates.
+RT_DEV void closest_leaf(const SceneDev& S, Trav& T, f3& r, const TravStack& stack) {
+    static_assert(kMaxLeafTris == 2 && kTriBytes == 40, "the whole-leaf step reads a leaf as 80 contiguous bytes");
+    const uint32_t code = (uint32_t)~T.cur;
+    const uint32_t first = code >> 2, rem = code & 3u;
+    const uint8_t* p4 = S.tris + (size_t)first * kTriBytes;
+    const float4 l0 = tri_ld4(p4), l1 = tri_ld4(p4 + 16), l2 = tri_ld4(p4 + 32), l3 = tri_ld4(p4 + 48), l4 = tri_ld4(p4 + 64);
+    const bool two = rem != 0u;
+    closest_test_regs(l0, l1, make_float2(l2.x, l2.y), T, r);
+    if (__ballot(two) != 0ull) {
+        if (two) closest_test_regs(make_float4(l2.z, l2.w, l3.x, l3.y), make_float4(l3.z, l3.w, l4.x, l4.y), make_float2(l4.z, l4.w), T, r);
+    }
+    if (lanes(!stack_shallow(stack, T, 0u)) == 0ull) trav_pop_lds(T, stack);
+    else trav_pop(T, stack);
+}
+
+// Persistent waves, k_query's frame: a wave claims kQueryChunk points at a time from a shard cursor and hands them to its idle lanes,
+// runs one wave-uniform step kind per iteration (the ray traversal's vote on trav_classes) until kClosestRefill of its lanes are idle,
+// writes their results and refills them. Once every shard is exhausted the wave goes on until all its lanes are done and ends. No wave
+// waits for another: the barrier of RT_TRAVERSAL_LDS comes before the loop.
+// A popped child is not tested against the winner again (the stack holds words, no keys): its node is visited, and there its children
+// meet the current best.
+__global__ void __launch_bounds__(kClosestBlock, kClosestWaves) k_closest(SceneDev S, PointDev q) {
+    RT_TRAVERSAL_LDS(kClosestBlock)
+    Trav T;
+    T.cur = kTravDone;
+    f3 r = mk3(0.0f, 0.0f, 0.0f);
+    unsigned long long pt = 0; // the lane's entry while `busy`
+    bool busy = false;
+    // wave-uniform: the shard drawn on, shards found exhausted, the claimed entries not yet handed out [cb, ce)
+    uint32_t head = blockIdx.x % kQueryHeads, heads_done = 0;
+    unsigned long long cb = 0, ce = 0;
+    for (;;) {
+        // REFILL every idle lane (or until every shard is exhausted)
+        for (;;) {
+            const lmask idle = __ballot(!busy);
+            const uint32_t cnt = (uint32_t)__popcll(idle);
+            if (cnt == 0u) break;
+            while (cb == ce && heads_done < kQueryHeads) { // claim: the next chunk of this shard, or move on to the next shard
+                const unsigned long long lo = q.n * head / kQueryHeads, len = q.n * (head + 1u) / kQueryHeads - lo;
+                unsigned long long o = 0;
+                if ((threadIdx.x & 63u) == 0u) o = atomicAdd(q.cursor + head * kQueryHeadStride, (unsigned long long)kQueryChunk);
+                const unsigned long long at = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(o < len ? o : len)); // (o < 2^32: n is 32 bits, every wave overshoots a shard once)
+                if (at < len) {
+                    cb = lo + at, ce = lo + (at + kQueryChunk < len ? at + kQueryChunk : len);
+                } else {
+                    head = head + 1u == kQueryHeads ? 0u : head + 1u, heads_done++;
+                }
+            }
+            if (cb == ce) break; // every shard exhausted
+            const uint32_t take = ce - cb < cnt ? (uint32_t)(ce - cb) : cnt;
+            const uint32_t rank = lane_rank(idle);
+            if (!busy && rank < take) {
+                const unsigned long long i = cb + rank;
+                const f3 p = mk3(q.pos[3 * i], q.pos[3 * i + 1], q.pos[3 * i + 2]);
+                const float md = q.max_dist2 ? q.max_dist2[i] : __builtin_huge_valf();
+                if (in_contract_range(q.range, p.x, p.y, p.z) && md == md) {
+                    closest_begin(T, p, md, stack);
+                    pt = i, busy = true;
+                } else { // rejected: marked, never walked (the lane stays idle and takes the next entry)
+                    if (q.dist2) q.dist2[i] = __builtin_nanf("");
+                    if (q.tri) q.tri[i] = RT_TRI_REJECTED;
+                }
+            }
+            cb += take;
+        }
+        const bool exhausted = cb == ce && heads_done == kQueryHeads;
+        if (__ballot(busy) == 0ull) break; // (a lane is idle after the refill only when every shard is exhausted)
+        const uint32_t stop = exhausted ? 64u : kClosestRefill;
+        while (count(trav_done(T)) < stop) {
+            const TravClasses c = trav_classes(T);
+            const uint32_t ni = count(c.inner), nl = count(c.leaf);
+            if (ni * kVoteInner >= nl * kVoteLeaf && !(nl >= 64u)) {
+                if (in_mask(c.inner)) closest_inner(S, T, stack, top);
+            } else {
+                if (in_mask(c.leaf)) closest_leaf(S, T, r, stack);
+            }
+        }
+        if (busy && T.cur == kTravDone) {
+            const bool hit = T.best.tri != kNoTri;
+            const float nan = __builtin_nanf("");
+            if (q.dist2) q.dist2[pt] = hit ? T.best.t : __builtin_huge_valf(); // a miss: best.t still holds max_dist2
+            if (q.u) q.u[pt] = T.best.u;
+            if (q.v) q.v[pt] = T.best.v;
+            if (q.tri) q.tri[pt] = T.best.tri;
+            if (q.point) {
+                q.point[3 * pt] = hit ? T.o.x - r.x : nan;
+                q.point[3 * pt + 1] = hit ? T.o.y - r.y : nan;
+                q.point[3 * pt + 2] = hit ? T.o.z - r.z : nan;
+            }
+            busy = false;
+        }
+    }
+}
+
+} // namespace rt
+
+namespace {
+
+// the refusals, in rt_trace_rays' order (rt_query.hip: query_check)
+int point_check(const rt_scene* s, const rt_point_query* q) {
+    if (!s || !q) return fail(RT_ERR_INVALID, "null argument");
+    if (q->n == 0) return RT_OK;
+    if (!q->pos) return fail(RT_ERR_INVALID, "null pos");
+    if (!q->dist2 && !q->u && !q->v && !q->tri && !q->point) return fail(RT_ERR_INVALID, "closest-point query with every output NULL");
+    if (s->device < 0) return fail(RT_ERR_NO_DEVICE, "scene was built host-only (device < 0)");
+    return RT_OK;
+}
+
+// fills the launch struct and hands it to the shared launch (PRE: point_check passed, n > 0, pointers on the scene's device)
+int point_enqueue(rt_scene* s, const rt_point_query* q, hipStream_t st) {
+    PointDev d{};
+    d.pos = q->pos, d.max_dist2 = q->max_dist2;
+    d.dist2 = q->dist2, d.u = q->u, d.v = q->v, d.tri = q->tri, d.point = q->point;
+    d.n = q->n;
+    return query_launch(s, kQueryKindPoint, k_closest, kClosestBlock, d, q->n, st, s->query_grid[kQueryKindPoint] ? nullptr : dev_knob("RT_CLOSEST_GRID"));
+}
+
+} // namespace
+
+extern "C" {
+
+int rt_closest_points(rt_scene* s, const rt_point_query* q) {
+    if (const int rc = point_check(s, q)) return rc;
+    const uint32_t n = q->n;
+    if (n == 0) return RT_OK;
+    const ContractRange range = contract_range(s->hs);
+    for (uint32_t i = 0; i < n; ++i) {
+        const float* p = q->pos + 3 * (size_t)i;
+        if (!in_contract_range(range, p[0], p[1], p[2]))
+            return fail(RT_ERR_INVALID, "point " + std::to_string(i) + ": more than 100 scene scales outside the scene's bounds or not finite (outside the range of the closest-point contract)");
+        if (q->max_dist2 && std::isnan(q->max_dist2[i])) return fail(RT_ERR_INVALID, "point " + std::to_string(i) + ": max_dist2 is NaN");
+    }
+    HIPCHK(hipSetDevice(s->device));
+    DevBuf b_pos, b_md, b_d2, b_u, b_v, b_tri, b_pt;
+    HIPCHK(b_pos.alloc((size_t)n * 12));
+    HIPCHK(hipMemcpy(b_pos.p, q->pos, (size_t)n * 12, hipMemcpyHostToDevice));
+    rt_point_query d{};
+    d.n = n;
+    d.pos = b_pos.as<float>();
+    if (q->max_dist2) {
+        HIPCHK(b_md.alloc((size_t)n * 4));
+        HIPCHK(hipMemcpy(b_md.p, q->max_dist2, (size_t)n * 4, hipMemcpyHostToDevice));
+        d.max_dist2 = b_md.as<float>();
+    }
+    struct Out { void* host; DevBuf* buf; size_t bytes; };
+    const Out outs[5] = {{q->dist2, &b_d2, 4}, {q->u, &b_u, 4}, {q->v, &b_v, 4}, {q->tri, &b_tri, 4}, {q->point, &b_pt, 12}};
+    for (const Out& o : outs)
+        if (o.host) HIPCHK(o.buf->alloc((size_t)n * o.bytes));
+    d.dist2 = b_d2.as<float>(), d.u = b_u.as<float>(), d.v = b_v.as<float>(), d.tri = b_tri.as<uint32_t>(), d.point = b_pt.as<float>();
+    if (const int rc = point_enqueue(s, &d, 0)) return rc;
+    HIPCHK(hipStreamSynchronize(0));
+    for (const Out& o : outs)
+        if (o.host) HIPCHK(hipMemcpy(o.host, o.buf->p, (size_t)n * o.bytes, hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+int rt_closest_points_device(rt_scene* s, const rt_point_query* q, void* stream) {
+    if (const int rc = point_check(s, q)) return rc;
+    if (q->n == 0) return RT_OK;
+    return point_enqueue(s, q, (hipStream_t)stream);
+}
+
+int rt_scene_closest_host(const rt_scene* s, uint32_t n, const float* pos, const float* max_dist2, int use_bvh, float* dist2, float* u, float* v,
+                          uint32_t* tri, float* point, uint64_t* node_visits, uint64_t* tri_tests) {
+    if (!s || (n && !pos)) return fail(RT_ERR_INVALID, "null argument");
+    if (const int rc0 = sync_host_copy(s)) return rc0;
+    std::string err;
+    const int rc = no_throw([&] { return closest_host(s->hs, n, pos, max_dist2, use_bvh, dist2, u, v, tri, point, node_visits, tri_tests, err); });
+    return rc == RT_OK ? RT_OK : fail(rc, err.empty() ? g_err : err);
+}
+
+} // extern "C"

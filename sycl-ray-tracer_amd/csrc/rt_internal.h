@@ -17,7 +17,9 @@
 //   rt_denoiser.h, rt_temporal_pixel.h the two objects' own state; the second also holds the one host path of a temporal call (temporal_call)
 //   rt_path_query.hip path queries, radiance along caller-supplied rays (rt_trace_paths[_device]) and their kernel
 //   rt_path_gather.hip gather queries, diffuse-lobe radiance at caller-supplied points (rt_gather_paths[_device]) and their kernel
-//   rt_query_launch.h what those three units share on the host: grid sizing, the launch on the shared cursors, the path / gather checks and staging
+//   rt_closest.hip closest-point queries, the nearest triangle to caller-supplied points (rt_closest_points[_device], rt_scene_closest_host) and their kernel
+//   rt_closest_point.h the contract of those queries, one fp32 text for the kernel and the host walk (scene_check.cpp: closest_host)
+//   rt_query_launch.h what those four units share on the host: grid sizing, the launch on the shared cursors, the path / gather checks and staging
 //   rt_path_rounds.h  the kernel body the last two share (path_rounds<E>)
 //   rt_lightmap.hip lightmap baking around one gather query (rt_lightmap_*): UV coverage, texel guides, resolve and dilation kernels
 #pragma once
@@ -147,7 +149,7 @@ struct SceneUpdate {
     bool host_stale = false; // the host copy (hs.nodes, tris, wverts, shade, sah_cost) lags a device update
 };
 
-// The cursors of the three query kinds (rt_query.hip, rt_path_query.hip, rt_path_gather.hip). A launch's entries are cut into kQueryHeads
+// The cursors of the query kinds (rt_query.hip, rt_path_query.hip, rt_path_gather.hip, rt_closest.hip). A launch's entries are cut into kQueryHeads
 // contiguous shards, each with a cursor of its own on a 128-byte line; a wave claims kQueryChunk entries per atomic. It starts at shard
 // blockIdx % kQueryHeads — workgroups are dealt round-robin to the 8 XCDs, so each shard is drawn on by one XCD — and moves on to the next
 // shard when its own is exhausted. The first version had ONE cursor and claimed as many rays as the wave had idle lanes: ~6,000 waves drawing
@@ -156,7 +158,7 @@ constexpr uint32_t kQueryCursorBytes = 32u * 128u;
 constexpr uint32_t kQueryChunk = 64, kQueryHeads = 32, kQueryHeadStride = 16; // (stride in 8-byte words)
 static_assert(kQueryHeads * kQueryHeadStride * 8u == kQueryCursorBytes, "the scene's cursor block holds one 128-byte line per shard");
 // the query kernels, each with a persistent grid of its own (rt_scene::query_grid)
-enum QueryKind : int { kQueryKindClosest = 0, kQueryKindAny = 1, kQueryKindPath = 2, kQueryKindGather = 3, kQueryKinds = 4 };
+enum QueryKind : int { kQueryKindClosest = 0, kQueryKindAny = 1, kQueryKindPath = 2, kQueryKindGather = 3, kQueryKindPoint = 4, kQueryKinds = 5 };
 
 struct rt_scene {
     HostScene hs;

@@ -105,4 +105,9 @@ int check_bvh(const HostScene& hs, std::string& err);
 int count_visits(const HostScene& hs, uint32_t n, const float* org, const float* dir, int mode, uint64_t* node_visits, uint64_t* tri_tests, float* t_out,
                  uint32_t* tri_out, std::string& err);
 
+// Diagnostic used by rt_scene_closest_host: closest-point queries on the host (rt_closest_point.h), by brute force over the leaf records
+// (use_bvh 0) or by the walk k_closest makes, counted (use_bvh 1). Any output may be NULL; max_dist2 NULL = +inf.
+int closest_host(const HostScene& hs, uint32_t n, const float* pos, const float* max_dist2, int use_bvh, float* dist2, float* u, float* v, uint32_t* tri,
+                 float* point, uint64_t* node_visits, uint64_t* tri_tests, std::string& err);
+
 } // namespace rt

@@ -1,6 +1,7 @@
 // scene_check.cpp — host diagnostics of a built scene: the two surface-area costs rt_scene_info reports, the structural check behind
 // rt_scene_check_bvh and the node-visit count behind rt_scene_count_visits. Nothing here decides anything about a tree or a render.
 #include "scene_build.h"
+#include "rt_closest_point.h"
 
 #include <algorithm>
 #include <cmath>
@@ -351,6 +352,76 @@ int count_visits(const HostScene& hs, uint32_t n, const float* org, const float*
         }
         if (t_out) t_out[i] = best;
         if (tri_out) tri_out[i] = best_tri;
+    }
+    if (node_visits) *node_visits = visits;
+    if (tri_tests) *tri_tests = tests;
+    return RT_OK;
+}
+
+// ---- closest-point queries on the host (rt_scene_closest_host; rt_closest_point.h) -------------------------------------------------------
+// use_bvh = 0: the brute force over hs.tris with the contract's one text — a pre-split triangle's records all give the same candidate, so
+// the leaf-ordered array stands for the triangle list. use_bvh = 1: the walk k_closest makes (rt_closest.hip) — the decoded child boxes, the
+// kernel's cull rule (closest_enters), its sorting network on (lb, child) with +inf for a child not entered, the others stacked far to near,
+// no second look at a popped child — counting node visits and triangle tests. Entries are not refused here: a NaN max_dist2 is a miss.
+int closest_host(const HostScene& hs, uint32_t n, const float* pos, const float* max_dist2, int use_bvh, float* dist2_out, float* u_out, float* v_out,
+                 uint32_t* tri_out, float* point_out, uint64_t* node_visits, uint64_t* tri_tests, std::string& err) {
+    if (use_bvh != 0 && use_bvh != 1) { err = "use_bvh: 0 brute force, 1 the kernel's walk"; return RT_ERR_INVALID; }
+    if (use_bvh && hs.nodes.empty()) { err = "no tree"; return RT_ERR_INVALID; }
+    const float inf = std::numeric_limits<float>::infinity(), nan = std::numeric_limits<float>::quiet_NaN();
+    uint64_t visits = 0, tests = 0;
+    std::vector<int32_t> stack;
+    for (uint32_t i = 0; i < n; ++i) {
+        const float p[3] = {pos[3 * (size_t)i], pos[3 * (size_t)i + 1], pos[3 * (size_t)i + 2]};
+        float best = max_dist2 ? max_dist2[i] : inf;
+        uint32_t best_tri = kNoTri;
+        ClosestPoint win{inf, 0.0f, 0.0f, {0.0f, 0.0f, 0.0f}};
+        auto test = [&](const TriRec& tr) {
+            tests++;
+            const ClosestPoint c = closest_point_on_record(p, tr.v0, tr.e1, tr.e2);
+            if (closest_better(c.dist2, tr.global_index, best, best_tri)) best = c.dist2, best_tri = tr.global_index, win = c;
+        };
+        if (!use_bvh) {
+            for (const TriRec& tr : hs.tris) test(tr);
+        } else {
+            stack.clear();
+            int32_t cur = 0;
+            for (;;) {
+                if (cur >= 0) {
+                    visits++;
+                    const BvhNode& nd = hs.nodes[(size_t)cur];
+                    float key[4];
+                    int32_t ch[4];
+                    for (int k = 0; k < 4; ++k) {
+                        ch[k] = nd.child[k], key[k] = inf;
+                        if (nd.child[k] == kChildEmpty) continue; // (its inverted box gives a finite lb: the word is what says it is absent)
+                        float lb = 0.0f;
+                        for (int a = 0; a < 3; ++a) {
+                            const float lo = child_plane(nd, k, a, 0), hi = child_plane(nd, k, a, 1);
+                            const float e = std::max(std::max(lo - p[a], p[a] - hi), 0.0f);
+                            lb = std::fma(e, e, lb);
+                        }
+                        if (closest_enters(lb, best)) key[k] = std::min(lb, std::numeric_limits<float>::max()); // (an lb that overflowed is still a key)
+                    }
+                    auto ce = [&](int a, int b) { if (key[b] < key[a]) std::swap(key[a], key[b]), std::swap(ch[a], ch[b]); };
+                    ce(0, 1), ce(2, 3), ce(0, 2), ce(1, 3), ce(1, 2);
+                    for (int k = 3; k >= 1; --k)
+                        if (key[k] < inf) stack.push_back(ch[k]);
+                    if (key[0] < inf) { cur = ch[0]; continue; }
+                } else {
+                    const LeafRange leaf = leaf_range(cur);
+                    for (uint32_t k = 0; k < leaf.count; ++k) test(hs.tris[leaf.first + k]);
+                }
+                if (stack.empty()) break;
+                cur = stack.back(), stack.pop_back();
+            }
+        }
+        const bool hit = best_tri != kNoTri;
+        if (dist2_out) dist2_out[i] = hit ? best : inf;
+        if (u_out) u_out[i] = hit ? win.u : 0.0f;
+        if (v_out) v_out[i] = hit ? win.v : 0.0f;
+        if (tri_out) tri_out[i] = best_tri;
+        if (point_out)
+            for (int a = 0; a < 3; ++a) point_out[3 * (size_t)i + a] = hit ? p[a] - win.r[a] : nan;
     }
     if (node_visits) *node_visits = visits;
     if (tri_tests) *tri_tests = tests;

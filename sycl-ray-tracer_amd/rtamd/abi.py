@@ -203,6 +203,19 @@ class rt_ray_query(C.Structure):
     ]
 
 
+class rt_point_query(C.Structure):
+    _fields_ = [
+        ("n", C.c_uint32),
+        ("pos", C.c_void_p),
+        ("max_dist2", C.c_void_p),
+        ("dist2", C.c_void_p),
+        ("u", C.c_void_p),
+        ("v", C.c_void_p),
+        ("tri", C.c_void_p),
+        ("point", C.c_void_p),
+    ]
+
+
 class rt_path_query(C.Structure):
     _fields_ = [
         ("n", C.c_uint32),
@@ -294,6 +307,7 @@ RT_LIGHTMAP_MAX_SIZE = 8192
 RT_LIGHTMAP_MAX_DILATE = 16
 
 assert C.sizeof(rt_ray_query) == 72
+assert C.sizeof(rt_point_query) == 64
 assert C.sizeof(rt_lightmap_params) == 24
 assert C.sizeof(rt_lightmap_stats) == 24
 assert C.sizeof(rt_lightmap_filter_params) == 16
@@ -325,6 +339,10 @@ PROTOTYPES = {
                                      _P(C.c_float), _P(C.c_float), _P(C.c_uint32)]),
     "rt_trace_rays": (C.c_int, [C.c_void_p, _P(rt_ray_query)]),
     "rt_trace_rays_device": (C.c_int, [C.c_void_p, _P(rt_ray_query), C.c_void_p]),
+    "rt_closest_points": (C.c_int, [C.c_void_p, _P(rt_point_query)]),
+    "rt_closest_points_device": (C.c_int, [C.c_void_p, _P(rt_point_query), C.c_void_p]),
+    "rt_scene_closest_host": (C.c_int, [C.c_void_p, C.c_uint32, _P(C.c_float), _P(C.c_float), C.c_int, _P(C.c_float), _P(C.c_float),
+                                         _P(C.c_float), _P(C.c_uint32), _P(C.c_float), _P(C.c_uint64), _P(C.c_uint64)]),
     "rt_trace_paths": (C.c_int, [C.c_void_p, _P(rt_path_query)]),
     "rt_trace_paths_device": (C.c_int, [C.c_void_p, _P(rt_path_query), C.c_void_p]),
     "rt_gather_paths": (C.c_int, [C.c_void_p, _P(rt_gather_query)]),

@@ -103,6 +103,32 @@ def probe_grid(sd: SceneDesc, spacing: float, margin: float = 0.0):
     return lo.astype(f32), tuple(int(c) for c in count)
 
 
+def grid_points(origin, spacing, count) -> np.ndarray:
+    """The points of a count[0] x count[1] x count[2] grid, (points, 3) float32: origin + (float)i * spacing per axis, one fp32 multiply
+    and one add, in the probe volume's order p = (iz * count[1] + iy) * count[0] + ix (renderer.ProbeVolume.positions). `spacing` is one
+    number or one per axis."""
+    origin, spacing, count = np.asarray(origin, np.float64), np.asarray(spacing, np.float64), np.asarray(count)
+    if spacing.ndim == 0:
+        spacing = np.repeat(spacing, 3)
+    if origin.shape != (3,) or spacing.shape != (3,):
+        raise ValueError("origin must hold 3 numbers, spacing 1 or 3")
+    if count.shape != (3,) or count.dtype.kind not in "ui" or (count < 0).any():
+        raise ValueError("count must hold 3 integers, none negative")
+    iz, iy, ix = np.meshgrid(*(np.arange(int(c)) for c in count[::-1]), indexing="ij")
+    idx = np.stack([ix, iy, iz], -1).reshape(-1, 3).astype(f32)
+    return np.ascontiguousarray(origin.astype(f32)[None, :] + idx * spacing.astype(f32)[None, :])
+
+
+def distance_grid(scene: Scene, origin, spacing, count, max_dist=None):
+    """The distance from every point of a grid to the scene's nearest triangle: (dist (cz, cy, cx) float32, tri (cz, cy, cx) uint32), one
+    Scene.closest_points call over grid_points(origin, spacing, count). With a ProbeVolume's own origin, spacing and count it is the
+    clearance of the volume's probes, in their order. max_dist: a radius beyond which a point is a miss (dist +inf, tri 0xFFFFFFFF)."""
+    pts = grid_points(origin, spacing, count)
+    shape = tuple(int(c) for c in np.asarray(count)[::-1])
+    out = scene.closest_points(pts, max_dist)
+    return out["dist"].reshape(shape), out["tri"].reshape(shape)
+
+
 def shade_vertices_from_volume(volume, sd: SceneDesc) -> np.ndarray:
     """bake_vertices' counterpart for a mesh that is NOT in the baked scene: the probe volume's irradiance over pi at every triangle corner
     of `sd` for its shading normal, (T, 3, 3) float32 [triangle, corner, rgb], one ProbeVolume.sample call over vertex_points(sd)."""

@@ -135,6 +135,63 @@ class Scene:
                              occluded=d_occluded or None)
         abi.check(self._lib.rt_trace_rays_device(self.h, C.byref(q), C.c_void_p(stream or None)), self._lib)
 
+    def closest_points(self, pos: np.ndarray, max_dist=None) -> dict:
+        """rt_closest_points on host arrays: pos (n, 3) float32; max_dist a radius (one number or (n,)), squared here in fp32, or None
+        (+inf). Returns {"dist2", "u", "v": (n,) float32, "tri": (n,) uint32, "point": (n, 3) float32, "dist": sqrt(dist2)}: the nearest
+        triangle within the radius, a miss (dist2 = +inf, tri = 0xFFFFFFFF, point NaN) where there is none (include/rt_mi355x.h:
+        rt_point_query)."""
+        pos = np.asarray(pos)
+        if pos.ndim != 2 or pos.shape[1] != 3:
+            raise ValueError("pos must be (n, 3)")
+        n = pos.shape[0]
+        pos = np.ascontiguousarray(pos, np.float32)
+        q = abi.rt_point_query(n=n, pos=pos.ctypes.data)
+        if max_dist is not None:
+            md = np.asarray(max_dist, np.float32)
+            if md.ndim == 0:
+                md = np.full(n, md, np.float32)
+            if md.shape != (n,):
+                raise ValueError("max_dist must be one radius or hold one per point, shape (n,)")
+            md2 = np.ascontiguousarray(md * md)  # (a negative radius squares to a positive one: refused here, the ABI's radius is squared)
+            if (md < 0).any():
+                raise ValueError("max_dist must not be negative")
+            q.max_dist2 = md2.ctypes.data
+        out = {"dist2": np.zeros(n, np.float32), "u": np.zeros(n, np.float32), "v": np.zeros(n, np.float32), "tri": np.zeros(n, np.uint32),
+               "point": np.zeros((n, 3), np.float32)}
+        for name, a in out.items():
+            setattr(q, name, a.ctypes.data)
+        abi.check(self._lib.rt_closest_points(self.h, C.byref(q)), self._lib)
+        out["dist"] = np.sqrt(out["dist2"])
+        return out
+
+    def closest_points_device(self, n: int, d_pos: int, d_max_dist2: int = 0, d_dist2: int = 0, d_u: int = 0, d_v: int = 0, d_tri: int = 0,
+                              d_point: int = 0, stream: int = 0) -> None:
+        """rt_closest_points_device on DEVICE pointers (e.g. torch .data_ptr()), enqueued on `stream`; 0 = NULL (no radius / output not
+        written). d_max_dist2 holds SQUARED radii. Rejected entries are marked: dist2 = NaN, tri = abi.RT_TRI_REJECTED."""
+        q = abi.rt_point_query(n=int(n), pos=d_pos or None, max_dist2=d_max_dist2 or None, dist2=d_dist2 or None, u=d_u or None, v=d_v or None,
+                               tri=d_tri or None, point=d_point or None)
+        abi.check(self._lib.rt_closest_points_device(self.h, C.byref(q), C.c_void_p(stream or None)), self._lib)
+
+    def closest_host(self, pos: np.ndarray, max_dist2=None, use_bvh: bool = False) -> dict:
+        """rt_scene_closest_host (host diagnostic, needs no GPU): the same query by brute force (use_bvh False) or by the kernel's walk of
+        the tree, counted. max_dist2 (n,) SQUARED radii or None. Returns closest_points' arrays (without "dist") and "node_visits",
+        "tri_tests"."""
+        pos = np.ascontiguousarray(pos, np.float32).reshape(-1, 3)
+        n = pos.shape[0]
+        md = None
+        if max_dist2 is not None:
+            md = np.ascontiguousarray(max_dist2, np.float32).reshape(-1)
+            if md.shape[0] != n:
+                raise ValueError("max_dist2 must hold one value per point")
+        out = {"dist2": np.zeros(n, np.float32), "u": np.zeros(n, np.float32), "v": np.zeros(n, np.float32), "tri": np.zeros(n, np.uint32),
+               "point": np.zeros((n, 3), np.float32)}
+        nv, nt = C.c_uint64(0), C.c_uint64(0)
+        abi.check(self._lib.rt_scene_closest_host(self.h, n, abi.fptr(pos), abi.fptr(md) if md is not None else None, 1 if use_bvh else 0,
+                                                  abi.fptr(out["dist2"]), abi.fptr(out["u"]), abi.fptr(out["v"]), abi.u32ptr(out["tri"]),
+                                                  abi.fptr(out["point"]), C.byref(nv), C.byref(nt)), self._lib)
+        out["node_visits"], out["tri_tests"] = int(nv.value), int(nt.value)
+        return out
+
     def _paths(self, call, query, names, fields, what, in0, in1, rng, max_depth, samples, rr_start) -> dict:
         """trace_paths and gather_paths: two (n, 3) float32 inputs (`names` in the messages, `fields` of `query`) and one xorshift32 state
         per ray or entry (`what`), through the host-array entry point `call`."""

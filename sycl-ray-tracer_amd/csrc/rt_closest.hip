@@ -2,8 +2,10 @@
 // and the C entry of the host diagnostic rt_scene_closest_host (the walk itself: scene_check.cpp: closest_host).
 // (A unit of its own, as rt_query.hip is: the render kernels' listings do not change. The contract — the fp32 text of one candidate, the
 // winner rule and the cull — is rt_closest_point.h, shared with the host walk. DESIGN.md §22.)
+// The kernel's body is query_frame (rt_query_frame.h), shared with k_query, with the claim every query kernel shares; the launch and the host
+// form's staging are rt_query_launch.h's. What is this unit's own: an entry is a point with a max_dist2, and the inner and leaf steps.
 #include "rt_query_launch.h"
-#include "rt_device.h"
+#include "rt_query_frame.h"
 #include "rt_closest_point.h"
 
 namespace rt {
@@ -22,7 +24,7 @@ struct PointDev {
     uint32_t* tri;
     float* point;
     unsigned long long* cursor; // kQueryHeads shard cursors, kQueryHeadStride words apart; 0 at the launch (reset on its stream)
-    unsigned long long n;
+    uint32_t n;
     ContractRange range; // rt_frame.hip: contract_range of the scene
 };
 
@@ -136,84 +138,53 @@ RT_DEV void closest_leaf(const SceneDev& S, Trav& T, f3& r, const TravStack& sta
     else trav_pop(T, stack);
 }
 
-// Persistent waves, k_query's frame: a wave claims kQueryChunk points at a time from a shard cursor and hands them to its idle lanes,
-// runs one wave-uniform step kind per iteration (the ray traversal's vote on trav_classes) until kClosestRefill of its lanes are idle,
-// writes their results and refills them. Once every shard is exhausted the wave goes on until all its lanes are done and ends. No wave
-// waits for another: the barrier of RT_TRAVERSAL_LDS comes before the loop.
+// query_frame's policy (rt_query_frame.h): an entry is a point and its max_dist2, the point inside the contract's range and max_dist2 no
+// NaN; a step is one wave-uniform step kind, an inner or a leaf step, by the ray traversal's vote on trav_classes.
 // A popped child is not tested against the winner again (the stack holds words, no keys): its node is visited, and there its children
 // meet the current best.
-__global__ void __launch_bounds__(kClosestBlock, kClosestWaves) k_closest(SceneDev S, PointDev q) {
-    RT_TRAVERSAL_LDS(kClosestBlock)
-    Trav T;
-    T.cur = kTravDone;
-    f3 r = mk3(0.0f, 0.0f, 0.0f);
-    unsigned long long pt = 0; // the lane's entry while `busy`
-    bool busy = false;
-    // wave-uniform: the shard drawn on, shards found exhausted, the claimed entries not yet handed out [cb, ce)
-    uint32_t head = blockIdx.x % kQueryHeads, heads_done = 0;
-    unsigned long long cb = 0, ce = 0;
-    for (;;) {
-        // REFILL every idle lane (or until every shard is exhausted)
-        for (;;) {
-            const lmask idle = __ballot(!busy);
-            const uint32_t cnt = (uint32_t)__popcll(idle);
-            if (cnt == 0u) break;
-            while (cb == ce && heads_done < kQueryHeads) { // claim: the next chunk of this shard, or move on to the next shard
-                const unsigned long long lo = q.n * head / kQueryHeads, len = q.n * (head + 1u) / kQueryHeads - lo;
-                unsigned long long o = 0;
-                if ((threadIdx.x & 63u) == 0u) o = atomicAdd(q.cursor + head * kQueryHeadStride, (unsigned long long)kQueryChunk);
-                const unsigned long long at = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(o < len ? o : len)); // (o < 2^32: n is 32 bits, every wave overshoots a shard once)
-                if (at < len) {
-                    cb = lo + at, ce = lo + (at + kQueryChunk < len ? at + kQueryChunk : len);
-                } else {
-                    head = head + 1u == kQueryHeads ? 0u : head + 1u, heads_done++;
-                }
-            }
-            if (cb == ce) break; // every shard exhausted
-            const uint32_t take = ce - cb < cnt ? (uint32_t)(ce - cb) : cnt;
-            const uint32_t rank = lane_rank(idle);
-            if (!busy && rank < take) {
-                const unsigned long long i = cb + rank;
-                const f3 p = mk3(q.pos[3 * i], q.pos[3 * i + 1], q.pos[3 * i + 2]);
-                const float md = q.max_dist2 ? q.max_dist2[i] : __builtin_huge_valf();
-                if (in_contract_range(q.range, p.x, p.y, p.z) && md == md) {
-                    closest_begin(T, p, md, stack);
-                    pt = i, busy = true;
-                } else { // rejected: marked, never walked (the lane stays idle and takes the next entry)
-                    if (q.dist2) q.dist2[i] = __builtin_nanf("");
-                    if (q.tri) q.tri[i] = RT_TRI_REJECTED;
-                }
-            }
-            cb += take;
+struct PointPhase {};
+struct PointFrame {
+    static constexpr uint32_t kBlock = kClosestBlock, kRefill = kClosestRefill;
+    struct Lane { f3 r; }; // p - point of the winner
+    RT_DEV static bool start(const PointDev& q, uint32_t i, Trav& T, const TravStack& stack) {
+        const size_t k = 3 * (size_t)i;
+        const f3 p = mk3(q.pos[k], q.pos[k + 1], q.pos[k + 2]);
+        const float md = q.max_dist2 ? q.max_dist2[i] : __builtin_huge_valf();
+        if (in_contract_range(q.range, p.x, p.y, p.z) && md == md) {
+            closest_begin(T, p, md, stack);
+            return true;
         }
-        const bool exhausted = cb == ce && heads_done == kQueryHeads;
-        if (__ballot(busy) == 0ull) break; // (a lane is idle after the refill only when every shard is exhausted)
-        const uint32_t stop = exhausted ? 64u : kClosestRefill;
-        while (count(trav_done(T)) < stop) {
-            const TravClasses c = trav_classes(T);
-            const uint32_t ni = count(c.inner), nl = count(c.leaf);
-            if (ni * kVoteInner >= nl * kVoteLeaf && !(nl >= 64u)) {
-                if (in_mask(c.inner)) closest_inner(S, T, stack, top);
-            } else {
-                if (in_mask(c.leaf)) closest_leaf(S, T, r, stack);
-            }
-        }
-        if (busy && T.cur == kTravDone) {
-            const bool hit = T.best.tri != kNoTri;
-            const float nan = __builtin_nanf("");
-            if (q.dist2) q.dist2[pt] = hit ? T.best.t : __builtin_huge_valf(); // a miss: best.t still holds max_dist2
-            if (q.u) q.u[pt] = T.best.u;
-            if (q.v) q.v[pt] = T.best.v;
-            if (q.tri) q.tri[pt] = T.best.tri;
-            if (q.point) {
-                q.point[3 * pt] = hit ? T.o.x - r.x : nan;
-                q.point[3 * pt + 1] = hit ? T.o.y - r.y : nan;
-                q.point[3 * pt + 2] = hit ? T.o.z - r.z : nan;
-            }
-            busy = false;
+        if (q.dist2) q.dist2[i] = __builtin_nanf(""); // rejected: marked, never walked
+        if (q.tri) q.tri[i] = RT_TRI_REJECTED;
+        return false;
+    }
+    RT_DEV static PointPhase phase(const Trav&) { return {}; }
+    RT_DEV static void step(const SceneDev& S, Trav& T, Lane& x, const TravStack& stack, const TopTree& top, PointPhase) {
+        const TravClasses c = trav_classes(T);
+        const uint32_t ni = count(c.inner), nl = count(c.leaf);
+        if (ni * kVoteInner >= nl * kVoteLeaf && !(nl >= 64u)) {
+            if (in_mask(c.inner)) closest_inner(S, T, stack, top);
+        } else {
+            if (in_mask(c.leaf)) closest_leaf(S, T, x.r, stack);
         }
     }
-}
+    RT_DEV static void store(const PointDev& q, uint32_t i, const Trav& T, const Lane& x) {
+        const bool hit = T.best.tri != kNoTri;
+        const float nan = __builtin_nanf("");
+        const size_t k = 3 * (size_t)i;
+        if (q.dist2) q.dist2[i] = hit ? T.best.t : __builtin_huge_valf(); // a miss: best.t still holds max_dist2
+        if (q.u) q.u[i] = T.best.u;
+        if (q.v) q.v[i] = T.best.v;
+        if (q.tri) q.tri[i] = T.best.tri;
+        if (q.point) {
+            q.point[k] = hit ? T.o.x - x.r.x : nan;
+            q.point[k + 1] = hit ? T.o.y - x.r.y : nan;
+            q.point[k + 2] = hit ? T.o.z - x.r.z : nan;
+        }
+    }
+};
+
+__global__ void __launch_bounds__(kClosestBlock, kClosestWaves) k_closest(SceneDev S, PointDev q) { query_frame<PointFrame>(S, q); }
 
 } // namespace rt
 
@@ -225,8 +196,7 @@ int point_check(const rt_scene* s, const rt_point_query* q) {
     if (q->n == 0) return RT_OK;
     if (!q->pos) return fail(RT_ERR_INVALID, "null pos");
     if (!q->dist2 && !q->u && !q->v && !q->tri && !q->point) return fail(RT_ERR_INVALID, "closest-point query with every output NULL");
-    if (s->device < 0) return fail(RT_ERR_NO_DEVICE, "scene was built host-only (device < 0)");
-    return RT_OK;
+    return refuse_host_only(s);
 }
 
 // fills the launch struct and hands it to the shared launch (PRE: point_check passed, n > 0, pointers on the scene's device)
@@ -253,28 +223,14 @@ int rt_closest_points(rt_scene* s, const rt_point_query* q) {
             return fail(RT_ERR_INVALID, "point " + std::to_string(i) + ": more than 100 scene scales outside the scene's bounds or not finite (outside the range of the closest-point contract)");
         if (q->max_dist2 && std::isnan(q->max_dist2[i])) return fail(RT_ERR_INVALID, "point " + std::to_string(i) + ": max_dist2 is NaN");
     }
-    HIPCHK(hipSetDevice(s->device));
-    DevBuf b_pos, b_md, b_d2, b_u, b_v, b_tri, b_pt;
-    HIPCHK(b_pos.alloc((size_t)n * 12));
-    HIPCHK(hipMemcpy(b_pos.p, q->pos, (size_t)n * 12, hipMemcpyHostToDevice));
-    rt_point_query d{};
-    d.n = n;
-    d.pos = b_pos.as<float>();
-    if (q->max_dist2) {
-        HIPCHK(b_md.alloc((size_t)n * 4));
-        HIPCHK(hipMemcpy(b_md.p, q->max_dist2, (size_t)n * 4, hipMemcpyHostToDevice));
-        d.max_dist2 = b_md.as<float>();
-    }
-    struct Out { void* host; DevBuf* buf; size_t bytes; };
-    const Out outs[5] = {{q->dist2, &b_d2, 4}, {q->u, &b_u, 4}, {q->v, &b_v, 4}, {q->tri, &b_tri, 4}, {q->point, &b_pt, 12}};
-    for (const Out& o : outs)
-        if (o.host) HIPCHK(o.buf->alloc((size_t)n * o.bytes));
-    d.dist2 = b_d2.as<float>(), d.u = b_u.as<float>(), d.v = b_v.as<float>(), d.tri = b_tri.as<uint32_t>(), d.point = b_pt.as<float>();
-    if (const int rc = point_enqueue(s, &d, 0)) return rc;
-    HIPCHK(hipStreamSynchronize(0));
-    for (const Out& o : outs)
-        if (o.host) HIPCHK(hipMemcpy(o.host, o.buf->p, (size_t)n * o.bytes, hipMemcpyDeviceToHost));
-    return RT_OK;
+    const StageIn ins[2] = {{q->pos, 12}, {q->max_dist2, 4}};
+    const StageOut outs[5] = {{q->dist2, 4}, {q->u, 4}, {q->v, 4}, {q->tri, 4}, {q->point, 12}};
+    return query_staged(s, n, ins, outs, [&](void* const* in, void* const* out) {
+        rt_point_query d{};
+        d.n = n, d.pos = (const float*)in[0], d.max_dist2 = (const float*)in[1];
+        d.dist2 = (float*)out[0], d.u = (float*)out[1], d.v = (float*)out[2], d.tri = (uint32_t*)out[3], d.point = (float*)out[4];
+        return point_enqueue(s, &d, 0);
+    });
 }
 
 int rt_closest_points_device(rt_scene* s, const rt_point_query* q, void* stream) {

@@ -19,8 +19,8 @@
 //   rt_path_gather.hip gather queries, diffuse-lobe radiance at caller-supplied points (rt_gather_paths[_device]) and their kernel
 //   rt_closest.hip closest-point queries, the nearest triangle to caller-supplied points (rt_closest_points[_device], rt_scene_closest_host) and their kernel
 //   rt_closest_point.h the contract of those queries, one fp32 text for the kernel and the host walk (scene_check.cpp: closest_host)
-//   rt_query_launch.h what those four units share on the host: grid sizing, the launch on the shared cursors, the path / gather checks and staging
-//   rt_path_rounds.h  the kernel body the last two share (path_rounds<E>)
+//   rt_query_launch.h what those four units share on the host: grid sizing, the launch on the shared cursors, the host forms' staging, the path / gather checks
+//   rt_path_rounds.h  the kernel body the last two share (path_rounds<E>); rt_query_frame.h the one rt_query.hip and rt_closest.hip share (query_frame<P>) and the claim of entries, shared by all four
 //   rt_lightmap.hip lightmap baking around one gather query (rt_lightmap_*): UV coverage, texel guides, resolve and dilation kernels
 #pragma once
 #include <hip/hip_runtime.h>

@@ -63,12 +63,7 @@ namespace {
 
 PathArgs path_args(const rt_path_query& q) { return {q.n, q.max_depth, q.samples, q.rr_start, q.org, q.dir, q.rng, q.rng_out, q.radiance, q.rays}; }
 
-int path_refuse(const ContractRange& range, const PathArgs& a, uint32_t i) {
-    const float* o = a.in0 + 3 * (size_t)i;
-    if (!in_contract_range(range, o[0], o[1], o[2]))
-        return fail(RT_ERR_INVALID, "ray " + std::to_string(i) + ": origin more than 100 scene scales outside the scene's bounds or not finite (outside the range of the closest-hit contract)");
-    return RT_OK;
-}
+int path_refuse(const ContractRange& range, const PathArgs& a, uint32_t i) { return refuse_ray_origin(range, a.in0, i); }
 
 int path_enqueue(rt_scene* s, const PathArgs& a, hipStream_t st) {
     PathDev d{};

@@ -1,6 +1,7 @@
 // rt_path_rounds.h — the body k_path_query (rt_path_query.hip) and k_path_gather (rt_path_gather.hip) share: persistent waves around
 // k_megakernel's traversal and shading rounds, over a list of entries instead of a pixel grid. Each of the two units keeps its launch struct, a
-// policy struct E and a one-line __global__ wrapper; what differs between them is in E alone:
+// policy struct E and a one-line __global__ wrapper (the claim of entries and their hand-out to idle lanes is rt_query_frame.h's, shared
+// with the other query kernels); what differs between them is in E alone:
 //   E::load(q, i)         the floats of entry i, in a type of E's choosing that only E's other functions look into
 //   E::ok(q, e)           whether the entry is traced (a rejected one is marked, never traced, and its lane takes the next entry)
 //   E::first(q, i, e, a)  the first ray of the entry's first path, from the floats just loaded; `a` is the entry's RNG word, advanced by what is drawn
@@ -12,10 +13,11 @@
 #pragma once
 #include "rt_internal.h"
 #include "rt_bounce.h"
+#include "rt_query_frame.h"
 
 namespace rt {
 
-// render_pixel's loops over an entry list. k_query's persistent waves — a wave claims kQueryChunk entries at a time from a shard cursor and
+// render_pixel's loops over an entry list. The query kernels' persistent waves — a wave claims kQueryChunk entries at a time from a shard cursor and
 // hands them to its idle lanes — around k_megakernel's rounds: the lanes with a ray take whole-leaf traversal steps until E::kShadePct of
 // them hold a finished traversal; those shade (shade_bounce with the staged tables, then the roulette) and either start the next bounce,
 // restart with E::next for the entry's next path, or store the entry's result and fall idle. After a round that leaves E::kRefill lanes
@@ -41,53 +43,29 @@ RT_DEV void path_rounds(SceneDev S, Q q) {
     uint32_t ent = 0; // the lane's entry while `live`
     uint32_t rng = 0, s = 0, depth = 0, n_rays = 0;
     bool live = false;
-    // wave-uniform: the shard drawn on, shards found exhausted, the claimed entries not yet handed out [cb, ce)
-    uint32_t head = blockIdx.x % kQueryHeads, heads_done = 0;
-    uint32_t cb = 0, ce = 0;
+    Claim claim = claim_begin(); // wave-uniform (rt_query_frame.h)
     for (;;) {
         // REFILL every idle lane (or until every shard is exhausted) once E::kRefill lanes are idle; a wave without a live lane always does
-        if (heads_done < kQueryHeads || cb != ce) {
+        if (claim_open(claim)) {
             const uint32_t n_idle = (uint32_t)__popcll(__ballot(!live));
             if (n_idle >= E::kRefill || n_idle == 64u) {
-                for (;;) {
-                    const lmask idle = __ballot(!live);
-                    const uint32_t cnt = (uint32_t)__popcll(idle);
-                    if (cnt == 0u) break;
-                    while (cb == ce && heads_done < kQueryHeads) { // claim: the next chunk of this shard, or move on to the next shard
-                        const uint32_t lo = (uint32_t)((unsigned long long)q.n * head / kQueryHeads);
-                        const uint32_t len = (uint32_t)((unsigned long long)q.n * (head + 1u) / kQueryHeads) - lo;
-                        unsigned long long o = 0;
-                        if ((threadIdx.x & 63u) == 0u) o = atomicAdd(q.cursor + head * kQueryHeadStride, (unsigned long long)kQueryChunk);
-                        const uint32_t at = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(o < len ? o : len)); // (o < 2^32: n is 32 bits, every wave overshoots a shard once)
-                        if (at < len) {
-                            cb = lo + at, ce = lo + (len - at > kQueryChunk ? at + kQueryChunk : len);
-                        } else {
-                            head = head + 1u == kQueryHeads ? 0u : head + 1u, heads_done++;
-                        }
+                claim = claim_refill(claim, ClaimList{q.cursor, q.n}, [&] { return !live; }, [&](uint32_t i) {
+                    const auto e = E::load(q, i);
+                    uint32_t a = q.rng[i];
+                    if (E::ok(q, e)) {
+                        r = E::first(q, i, e, a);
+                        rng = a, s = 0, depth = 0;
+                        *color_r = 0.0f, *color_g = 0.0f, *color_b = 0.0f;
+                        n_rays = 0u;
+                        trav_begin(T, r.org, ray_dir(r), stack);
+                        ent = i, live = true;
+                    } else { // rejected: marked, never traced, no draw taken (the lane stays idle and takes the next entry)
+                        const float nan = __builtin_nanf("");
+                        q.radiance[3 * (size_t)i] = nan, q.radiance[3 * (size_t)i + 1] = nan, q.radiance[3 * (size_t)i + 2] = nan;
+                        if (q.rays) q.rays[i] = 0xFFFFFFFFu;
+                        if (q.rng_out) q.rng_out[i] = a;
                     }
-                    if (cb == ce) break; // every shard exhausted
-                    const uint32_t take = ce - cb < cnt ? ce - cb : cnt;
-                    const uint32_t rank = lane_rank(idle);
-                    if (!live && rank < take) {
-                        const uint32_t i = cb + rank; // < n: [cb, ce) lies inside its shard
-                        const auto e = E::load(q, i);
-                        uint32_t a = q.rng[i];
-                        if (E::ok(q, e)) {
-                            r = E::first(q, i, e, a);
-                            rng = a, s = 0, depth = 0;
-                            *color_r = 0.0f, *color_g = 0.0f, *color_b = 0.0f;
-                            n_rays = 0u;
-                            trav_begin(T, r.org, ray_dir(r), stack);
-                            ent = i, live = true;
-                        } else { // rejected: marked, never traced, no draw taken (the lane stays idle and takes the next entry)
-                            const float nan = __builtin_nanf("");
-                            q.radiance[3 * (size_t)i] = nan, q.radiance[3 * (size_t)i + 1] = nan, q.radiance[3 * (size_t)i + 2] = nan;
-                            if (q.rays) q.rays[i] = 0xFFFFFFFFu;
-                            if (q.rng_out) q.rng_out[i] = a;
-                        }
-                    }
-                    cb += take;
-                }
+                });
             }
         }
         const uint32_t n_live = (uint32_t)__popcll(__ballot(live));

@@ -1,6 +1,6 @@
-// rt_query_launch.h — the host half rt_query.hip, rt_path_query.hip and rt_path_gather.hip share: the sizing of a query kernel's persistent
-// grid, the launch on the scene's shared cursors (rt_scene_update relies on its event), and what path and gather queries have in common
-// beyond that: the argument checks and the staging of the host form.
+// rt_query_launch.h — the host half rt_query.hip, rt_closest.hip, rt_path_query.hip and rt_path_gather.hip share: the sizing of a query
+// kernel's persistent grid, the launch on the scene's shared cursors (rt_scene_update relies on its event), the staging of a host form
+// (query_staged) and the refusals two kinds word alike; and what path and gather queries have in common beyond that: the argument checks.
 #pragma once
 #include "rt_internal.h"
 
@@ -38,6 +38,43 @@ int query_launch(rt_scene* s, QueryKind kind, void (*kernel)(SceneDev, Dev), uin
     return RT_OK;
 }
 
+// The host form of a query: the caller's arrays are staged on the scene's device around one launch on the null stream. A buffer holds
+// `bytes` per entry; host == NULL: not allocated and not copied, so the launch sees its NULL. An output with in_place >= 0 has no buffer
+// of its own: the kernel writes it into that input's (the path kinds' rng -> rng_out; only the list says so). In order: hipSetDevice,
+// the allocations, the copies in, enqueue(in, out) with the device pointers by list index, hipStreamSynchronize(0), the copies out. PRE: checks passed, n > 0.
+struct StageIn { const void* host; size_t bytes; };
+struct StageOut { void* host; size_t bytes; int in_place = -1; };
+template <size_t NI, size_t NO, class Enqueue>
+int query_staged(rt_scene* s, size_t n, const StageIn (&ins)[NI], const StageOut (&outs)[NO], Enqueue enqueue) {
+    HIPCHK(hipSetDevice(s->device));
+    DevBuf b_in[NI], b_out[NO];
+    void *in[NI], *out[NO];
+    for (size_t k = 0; k < NI; ++k) {
+        if (ins[k].host) HIPCHK(b_in[k].alloc(n * ins[k].bytes));
+        in[k] = b_in[k].p;
+    }
+    for (size_t k = 0; k < NO; ++k) {
+        if (outs[k].host && outs[k].in_place < 0) HIPCHK(b_out[k].alloc(n * outs[k].bytes));
+        out[k] = outs[k].host && outs[k].in_place >= 0 ? in[outs[k].in_place] : b_out[k].p;
+    }
+    for (size_t k = 0; k < NI; ++k)
+        if (ins[k].host) HIPCHK(hipMemcpy(in[k], ins[k].host, n * ins[k].bytes, hipMemcpyHostToDevice));
+    if (const int rc = enqueue(in, out)) return rc;
+    HIPCHK(hipStreamSynchronize(0));
+    for (size_t k = 0; k < NO; ++k)
+        if (outs[k].host) HIPCHK(hipMemcpy(outs[k].host, out[k], n * outs[k].bytes, hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+// the refusals with one wording in every kind
+inline int refuse_host_only(const rt_scene* s) { return s->device < 0 ? fail(RT_ERR_NO_DEVICE, "scene was built host-only (device < 0)") : RT_OK; }
+inline int refuse_ray_origin(const ContractRange& range, const float* org, uint32_t i) {
+    const float* o = org + 3 * (size_t)i;
+    if (!in_contract_range(range, o[0], o[1], o[2]))
+        return fail(RT_ERR_INVALID, "ray " + std::to_string(i) + ": origin more than 100 scene scales outside the scene's bounds or not finite (outside the range of the closest-hit contract)");
+    return RT_OK;
+}
+
 // A path or a gather query by role (include/rt_mi355x.h: rt_path_query, rt_gather_query): in0 / in1 are org / dir or pos / normal.
 struct PathArgs {
     uint32_t n, max_depth, samples, rr_start;
@@ -63,8 +100,7 @@ inline int path_args_check(const rt_scene* s, const PathArgs& a, const PathKind&
     if (!a.in0 || !a.in1) return fail(RT_ERR_INVALID, std::string("null ") + k.inputs);
     if (!a.rng) return fail(RT_ERR_INVALID, std::string("null rng: every ") + k.entry + " needs its xorshift32 state");
     if (!a.radiance) return fail(RT_ERR_INVALID, "null radiance output");
-    if (s->device < 0) return fail(RT_ERR_NO_DEVICE, "scene was built host-only (device < 0)");
-    return RT_OK;
+    return refuse_host_only(s);
 }
 
 // the device form: check, enqueue
@@ -73,7 +109,7 @@ inline int paths_device(rt_scene* s, const PathArgs& a, const PathKind& k, hipSt
     return a.n == 0 ? RT_OK : k.enqueue(s, a, st);
 }
 
-// the host form: check, refuse per entry, stage the inputs, run on the null stream, copy the outputs back
+// the host form: check, refuse per entry, stage (query_staged)
 inline int paths_host(rt_scene* s, const PathArgs& a, const PathKind& k) {
     if (const int rc = path_args_check(s, a, k)) return rc;
     const size_t n = a.n;
@@ -81,26 +117,14 @@ inline int paths_host(rt_scene* s, const PathArgs& a, const PathKind& k) {
     const ContractRange range = contract_range(s->hs);
     for (uint32_t i = 0; i < a.n; ++i)
         if (const int rc = k.refuse(range, a, i)) return rc;
-    HIPCHK(hipSetDevice(s->device));
-    DevBuf b_in0, b_in1, b_rng, b_rad, b_rays;
-    HIPCHK(b_in0.alloc(n * 12));
-    HIPCHK(b_in1.alloc(n * 12));
-    HIPCHK(b_rng.alloc(n * 4));
-    HIPCHK(b_rad.alloc(n * 12));
-    HIPCHK(hipMemcpy(b_in0.p, a.in0, n * 12, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(b_in1.p, a.in1, n * 12, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(b_rng.p, a.rng, n * 4, hipMemcpyHostToDevice));
-    PathArgs d = a;
-    d.in0 = b_in0.as<float>(), d.in1 = b_in1.as<float>(), d.rng = b_rng.as<uint32_t>(), d.radiance = b_rad.as<float>();
-    d.rng_out = a.rng_out ? b_rng.as<uint32_t>() : nullptr; // in place on the device
-    if (a.rays) HIPCHK(b_rays.alloc(n * 4));
-    d.rays = b_rays.as<uint32_t>();
-    if (const int rc = k.enqueue(s, d, 0)) return rc;
-    HIPCHK(hipStreamSynchronize(0));
-    HIPCHK(hipMemcpy(a.radiance, b_rad.p, n * 12, hipMemcpyDeviceToHost));
-    if (a.rng_out) HIPCHK(hipMemcpy(a.rng_out, b_rng.p, n * 4, hipMemcpyDeviceToHost));
-    if (a.rays) HIPCHK(hipMemcpy(a.rays, b_rays.p, n * 4, hipMemcpyDeviceToHost));
-    return RT_OK;
+    const StageIn ins[3] = {{a.in0, 12}, {a.in1, 12}, {a.rng, 4}};
+    const StageOut outs[3] = {{a.radiance, 12}, {a.rng_out, 4, 2}, {a.rays, 4}}; // rng_out: in place on the device, in rng's buffer
+    return query_staged(s, n, ins, outs, [&](void* const* in, void* const* out) {
+        PathArgs d = a;
+        d.in0 = (const float*)in[0], d.in1 = (const float*)in[1], d.rng = (const uint32_t*)in[2];
+        d.radiance = (float*)out[0], d.rng_out = (uint32_t*)out[1], d.rays = (uint32_t*)out[2];
+        return k.enqueue(s, d, 0);
+    });
 }
 
 } // namespace rtlib

@@ -223,6 +223,33 @@ def test_sizes(gpu, scene_cache, n):
     s.close()
 
 
+@pytest.mark.parametrize("grid", [1, 3])
+def test_the_persistent_regime_refills_every_wave_many_times(gpu, devlib, oracle, scene_cache, monkeypatch, grid):
+    """RT_QUERY_GRID (developer library only) caps the persistent grid of both kernels. With one workgroup eight waves share 5,000 rays of
+    the mix (32 shards of three chunks): every wave refills beside live lanes many times, and drains at the end. Both modes, without a tmax and with short,
+    exact, random and unbounded ones side by side, against the oracle's brute force and against rt_intersect_batch."""
+    monkeypatch.setenv("RT_QUERY_GRID", str(grid))
+    sd = scene_cache("atrium", detail=1)
+    org, dirs, e = oracle_mix(oracle, scene_cache, "atrium", {"detail": 1})
+    n = 5000
+    org, dirs, e = org[:n], dirs[:n], tuple(a[:n] for a in e)
+    s = Scene(sd, device=gpu, lib=devlib)
+    assert_closest(s.intersect(org, dirs), e, f"grid {grid} rt_intersect_batch")
+    assert_closest(trace_dev(s, org, dirs), e, f"grid {grid}")
+    np.testing.assert_array_equal(trace_dev(s, org, dirs, any_hit=True), (e[3] != NO_TRI).astype(np.uint8))
+    rng = np.random.default_rng(grid)
+    hit = e[3] != NO_TRI
+    finite_t = np.where(hit, e[0], np.float32(1.0))
+    kind = rng.integers(0, 4, n)
+    tmax = np.select([kind == 0, kind == 1, kind == 2], [np.float32(1e-3), finite_t, rng.uniform(0, 2, n) * finite_t], np.inf).astype(np.float32)
+    ex = expected(e, tmax)
+    assert 0 < ex[4].sum() < hit.sum()
+    assert_closest(trace_dev(s, org, dirs, tmax), ex[:4], f"grid {grid}, tmax mix")
+    np.testing.assert_array_equal(trace_dev(s, org, dirs, tmax, any_hit=True), ex[4])
+    assert_closest(s.trace(org, dirs, tmax), ex[:4], f"grid {grid}, tmax mix, host form")
+    s.close()
+
+
 def test_torch_stream_and_null_outputs(gpu, scene_cache):
     """Tensors on a non-default stream; outputs passed as NULL, and those of the other mode, are not written."""
     import torch

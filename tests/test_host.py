@@ -36,7 +36,7 @@ def test_product_library_reads_three_environment_variables_only(rtlib, devlib):
         return set(m.decode() for m in re.findall(rb"(?<![A-Za-z0-9_])((?:RT|GPU)_[A-Z0-9_]{4,})\x00", Path(path).read_bytes()))
     product, dev = env_names(abi.LIB_PATH), env_names(abi.DEV_LIB_PATH)
     assert product == {"GPU_MAX_HW_QUEUES", "RT_PROFILE_KERNELS", "RT_KERNEL_STATS"}, product
-    assert {"RT_INJECT_ALLOC_FAILURE", "RT_WF_FINISH_DEPTH", "RT_MEGA_OCC", "RT_BVH_SPLIT_BUDGET", "RT_MEGA_SLICE_BOUNDS"} <= dev and product <= dev
+    assert {"RT_INJECT_ALLOC_FAILURE", "RT_WF_FINISH_DEPTH", "RT_MEGA_OCC", "RT_BVH_SPLIT_BUDGET", "RT_MEGA_SLICE_BOUNDS", "RT_QUERY_GRID"} <= dev and product <= dev
     assert devlib.rt_abi_version() == rtlib.rt_abi_version()
     for n in _declared_functions():
         assert hasattr(devlib, n)

@@ -9,7 +9,7 @@ Two atlases, because rtamd.bake.triangle_grid_uvs cannot lay the detail-4 atrium
 Per atlas, in this order: the bare rt_gather_paths_device over the bake's own entries (positions and normals from rt_lightmap_texels_device,
 the states of rtamd.bake.corner_seeds), rt_lightmap_bake_device without dilation, the bare gather again (the two gather windows are the
 run-to-run spread the bake's overhead is held against), rt_lightmap_texels_device (the owner plane's fill, k_lm_owner and k_lm_texels),
-and the bake with 8 dilation passes. The kernels the interface does not start alone are differences of medians: k_lm_resolve = bake -
+and the bake with 8 dilation passes. The kernels the interface does not start alone are differences of medians: k_lm_resolve<false> = bake -
 texels - gather (the bake's k_lm_texels also writes the states), one k_lm_dilate pass = (bake with 8 passes - bake) / 8.
 k_lm_owner alone: one triangle over an 8192 x 8192 atlas, rt_lightmap_texels_device beside the same call on a triangle without area (the
 fill and k_lm_texels over empty texels, k_lm_owner returning at once); the difference is the covering triangle's k_lm_owner and the

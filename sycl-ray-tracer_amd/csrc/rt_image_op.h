@@ -1,18 +1,14 @@
 // rt_image_op.h — what the image-space passes share: the denoiser (rt_denoise.hip, rt_variance.hip) and the temporal accumulator (rt_temporal.hip,
 // rt_temporal_moments.hip). An image op is an object for W x H frames on one device with a stream of its own for its host entry points, staging
-// planes for their arguments, and ONE event recorded behind every call: the next call, on whatever stream, waits for it before it touches the
-// planes the object owns (scratch, history sets, staging). That rule is begin_call / end_call, and every entry point goes through them.
+// planes for their arguments, and the bracket every call goes through (CallBracket, rt_internal.h): the next call, on whatever stream, waits for
+// the last before it touches the planes the object owns (scratch, history sets, staging).
 #pragma once
 #include "rt_internal.h"
 #include "rt_device.h"
 
-struct ImageOp {
-    int device = -1;
+struct ImageOp : CallBracket {
     int32_t width = 0, height = 0;
-    uint32_t flags = 0;           // RT_DENOISER_* / RT_TEMPORAL_*
-    hipStream_t stream = nullptr; // the host entry points run here
-    hipEvent_t ev_last = nullptr; // recorded behind every call: the next call's stream waits for it
-    bool recorded = false;
+    uint32_t flags = 0; // RT_DENOISER_* / RT_TEMPORAL_*
     // the host entry points' device copies of their arguments (four 16-byte input planes, the fp32 and unorm8 outputs), allocated at creation: no
     // call allocates
     float4* d_host_in = nullptr;
@@ -72,34 +68,14 @@ inline int image_op_open(ImageOp* op, int device, int32_t width, int32_t height,
     if (hipMalloc((void**)&op->d_host_in, 4 * n * 16u) != hipSuccess || hipMalloc((void**)&op->d_host_f32, n * 16u) != hipSuccess ||
         hipMalloc((void**)&op->d_host_u8, n * 4u) != hipSuccess)
         return fail(RT_ERR_OOM, oom_msg);
-    if (hipStreamCreateWithFlags(&op->stream, hipStreamNonBlocking) != hipSuccess ||
-        hipEventCreateWithFlags(&op->ev_last, hipEventDisableTiming) != hipSuccess)
-        return fail(RT_ERR_HIP, "hipStreamCreate / hipEventCreate failed");
-    return RT_OK;
+    return bracket_open(op);
 }
 
 // waits for the last call and releases the shared members; true: the device is current and the caller frees its own planes
 inline bool image_op_close(ImageOp* op) {
-    if (op->device < 0 || hipSetDevice(op->device) != hipSuccess) return false;
-    if (op->recorded) (void)hipEventSynchronize(op->ev_last);
+    if (!bracket_close(op)) return false;
     (void)hipFree(op->d_host_in), (void)hipFree(op->d_host_f32), (void)hipFree(op->d_host_u8);
-    if (op->ev_last) (void)hipEventDestroy(op->ev_last);
-    if (op->stream) (void)hipStreamDestroy(op->stream);
     return true;
-}
-
-// The bracket of every call on `st`: the previous call, on any stream, is done with the object's planes before this one's first command ...
-inline int begin_call(ImageOp* op, hipStream_t st) {
-    HIPCHK(hipSetDevice(op->device));
-    if (op->recorded) HIPCHK(hipStreamWaitEvent(st, op->ev_last, 0));
-    return RT_OK;
-}
-// ... and the next one waits for this one's last
-inline int end_call(ImageOp* op, hipStream_t st) {
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(op->ev_last, st));
-    op->recorded = true;
-    return RT_OK;
 }
 
 // the four 16-byte input planes of a host call -> d_host_in, plane k at d_host_in + k * pixels() (behind the wait: a _device call may still read them)

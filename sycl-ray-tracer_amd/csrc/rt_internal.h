@@ -12,7 +12,7 @@
 //   rt_query.hip   ray queries with a per-ray tmax (rt_trace_rays[_device]) and their kernel
 //   rt_temporal.hip the temporal accumulator (rt_temporal_*) and its kernel
 //   rt_temporal_moments.hip k_temporal_moments: the same pixel (rt_temporal_pixel_body.h) plus the luminance moments (rt_temporal_accumulate_moments[_device])
-//   rt_image_op.h  what those four units share: the object's stream, event and staging planes, the bracket of a call, the 64 x 4 launch shape
+//   rt_image_op.h  what those four units share: the object's staging planes on the bracket of a call (CallBracket, below), the 64 x 4 launch shape
 //   rt_atrous_pixel.h the a-trous pixel of rt_denoise.hip's and rt_variance.hip's kernels (atrous_pixel<GUIDED, SQUARE, LAST>) and the loop over its iterations
 //   rt_denoiser.h, rt_temporal_pixel.h the two objects' own state; the second also holds the one host path of a temporal call (temporal_call)
 //   rt_path_query.hip path queries, radiance along caller-supplied rays (rt_trace_paths[_device]) and their kernel
@@ -194,6 +194,47 @@ inline int scene_stream_event(rt_scene* s, hipStream_t st, hipEvent_t* out) {
         return fail(RT_ERR_OOM, "host allocation failed");
     }
     *out = ev;
+    return RT_OK;
+}
+} // namespace rtlib
+
+// The base of an object whose calls come on any stream (ImageOp, rt_lightmap, rt_probe_volume): a stream of its own for its host entry points
+// and ONE event recorded behind every call. The next call, on whatever stream, waits for it before it touches what the object owns. That rule is
+// begin_call / end_call, and every entry point of such an object goes through them.
+struct CallBracket {
+    int device = -1;
+    hipStream_t stream = nullptr; // the host entry points run here
+    hipEvent_t ev_last = nullptr; // recorded behind every call: the next call's stream waits for it
+    bool recorded = false;
+};
+
+namespace rtlib {
+// the stream and the event of a new object. PRE: b->device is set and current. Whatever this returns, bracket_close releases what was made
+inline int bracket_open(CallBracket* b) {
+    if (hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking) != hipSuccess ||
+        hipEventCreateWithFlags(&b->ev_last, hipEventDisableTiming) != hipSuccess)
+        return fail(RT_ERR_HIP, "hipStreamCreate / hipEventCreate failed");
+    return RT_OK;
+}
+// waits for the last call and destroys both; true: the device is current and the caller frees its own buffers
+inline bool bracket_close(CallBracket* b) {
+    if (b->device < 0 || hipSetDevice(b->device) != hipSuccess) return false;
+    if (b->recorded) (void)hipEventSynchronize(b->ev_last);
+    if (b->ev_last) (void)hipEventDestroy(b->ev_last);
+    if (b->stream) (void)hipStreamDestroy(b->stream);
+    return true;
+}
+// The bracket of every call on `st`: the previous call, on any stream, is done with the object's buffers before this one's first command ...
+inline int begin_call(CallBracket* b, hipStream_t st) {
+    HIPCHK(hipSetDevice(b->device));
+    if (b->recorded) HIPCHK(hipStreamWaitEvent(st, b->ev_last, 0));
+    return RT_OK;
+}
+// ... and the next one waits for this one's last (a launch of this call that failed is reported here at the latest)
+inline int end_call(CallBracket* b, hipStream_t st) {
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(b->ev_last, st));
+    b->recorded = true;
     return RT_OK;
 }
 } // namespace rtlib

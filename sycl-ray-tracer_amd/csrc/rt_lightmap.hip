@@ -2,10 +2,10 @@
 // lightmap created with RT_LIGHTMAP_FILTER rt_lightmap_bake_filtered[_device] and rt_lightmap_filter[_device], and their kernels.
 // The atlas-side half of a lightmap bake around one gather query (rt_path_gather.hip, called through its public entry point): which triangle
 // owns a texel (k_lm_owner), where the texel lies on it and with which shading normal, and the states of its entries (k_lm_texels), the mean
-// of the entries' radiances (k_lm_resolve) and the filling of the gutters (k_lm_dilate). The arithmetic is the contract stated at
+// of the entries' radiances (k_lm_resolve<false>) and the filling of the gutters (k_lm_dilate). The arithmetic is the contract stated at
 // rt_lightmap_bake in include/rt_mi355x.h; the numpy model that pins it bit for bit is tests/test_lightmap.py. No traversal, no LDS, no
 // float atomics in this unit: the owner plane is an integer minimum, the statistics are ballots and integer sums.
-// The filter (the contract's steps 5a and 5b, the model tests/test_lightmap_filter.py): k_lm_resolve_var is k_lm_resolve with the variance of
+// The filter (the contract's steps 5a and 5b, the model tests/test_lightmap_filter.py): k_lm_resolve<true> is the same text with the variance of
 // the texel's mean in .w and the two guide planes, k_lm_atrous one a-trous iteration in texel space, one launch per iteration, the kernel
 // boundary the only hand-off, in rt_image_op.h's 64 x 4 tile shape. Its tap loop is this unit's own: the mask is a plane (.w of the position
 // guide), the variance prefilter is renormalised over the mask, the values are linear and there is no albedo. The helpers it is made of
@@ -14,9 +14,8 @@
 #include "rt_device.h"
 #include "rt_atrous_pixel.h"
 
-struct rt_lightmap {
+struct rt_lightmap : CallBracket { // the host forms run on its stream
     rt_scene* scene = nullptr;
-    int device = -1;
     int32_t width = 0, height = 0;
     uint32_t max_repeats = 0;
     uint32_t n_tris = 0;
@@ -38,9 +37,6 @@ struct rt_lightmap {
     float* d_host_var_in = nullptr;
     float* d_host_var_out = nullptr;
     rt_lightmap_stats* d_stats = nullptr;
-    hipStream_t stream = nullptr;    // the host forms run here
-    hipEvent_t ev_last = nullptr;    // recorded behind every call: the next call's stream waits for it
-    bool recorded = false;
 };
 
 namespace rt {
@@ -172,12 +168,18 @@ __global__ void __launch_bounds__(kLmBlock) k_lm_texels(SceneDev S, const float*
 RT_DEV uint32_t lm_count(bool flag) { return (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(flag)); }
 
 // One wave per kLmWaveTexels texels, kLmLaneTexels per lane, 64 consecutive texels at a time: the mean of a texel's entries' radiances where
-// it has an owner and no entry was rejected, alpha 1; else zeros. The statistics: covered and sampled texels as ballots, the rays of the
-// entries not rejected as a wave sum; lane 0 adds them at the end. (One wave per 64 texels made 3 atomics per 64 texels on one cache line:
-// 5.9 ms of an 80 ms bake at 4096 x 4096)
+// it has an owner and no entry was rejected; else zeros. The statistics: covered and sampled texels as ballots, the rays of the entries not
+// rejected as a wave sum; lane 0 adds them at the end. (One wave per 64 texels made 3 atomics per 64 texels on one cache line: 5.9 ms of an
+// 80 ms bake at 4096 x 4096)
+// VAR = false (rt_lightmap_bake): .w of the output is alpha, 1 where sampled; pos, nrm, gpos and gnrm are not looked at.
+// VAR = true (the filter's step 5a): .w is the variance of the texel's mean luminance (0 where not sampled, and for one repeat); the mask goes
+// to .w of the position guide, 1 where sampled. The guides are the texel's first entry's.
+template <bool VAR>
 __global__ void __launch_bounds__(kLmStatBlock) k_lm_resolve(const uint32_t* __restrict__ owner, const float* __restrict__ rad,
                                                               const uint32_t* __restrict__ rays, uint32_t n, uint32_t repeats,
-                                                              float4* __restrict__ out, rt_lightmap_stats* __restrict__ stats) {
+                                                              float4* __restrict__ out, rt_lightmap_stats* __restrict__ stats,
+                                                              const float* __restrict__ pos, const float* __restrict__ nrm,
+                                                              float4* __restrict__ gpos, float4* __restrict__ gnrm) {
     uint32_t n_cov = 0, n_smp = 0;
     unsigned long long traced = 0;
     for (uint32_t j = 0; j < kLmLaneTexels; ++j) {
@@ -194,15 +196,36 @@ __global__ void __launch_bounds__(kLmStatBlock) k_lm_resolve(const uint32_t* __r
             sampled = covered && !rejected;
             float4 o = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
             if (sampled) {
-                float tx = 0.0f, ty = 0.0f, tz = 0.0f;
+                const float d = (float)repeats;
+                float tx = 0.0f, ty = 0.0f, tz = 0.0f, tl = 0.0f;
                 for (uint32_t k = 0; k < repeats; ++k) {
                     const float* r = rad + 3 * (size_t)(i * repeats + k);
                     tx = tx + r[0], ty = ty + r[1], tz = tz + r[2];
+                    if (VAR) tl = tl + luminance(make_float4(r[0], r[1], r[2], 0.0f));
                 }
-                const float d = (float)repeats;
-                o = make_float4(tx / d, ty / d, tz / d, 1.0f);
+                float w = 1.0f;
+                if (VAR) {
+                    w = 0.0f;
+                    if (repeats > 1) {
+                        const float m = tl / d;
+                        float s = 0.0f;
+                        for (uint32_t k = 0; k < repeats; ++k) {
+                            const float* r = rad + 3 * (size_t)(i * repeats + k);
+                            const float dl = luminance(make_float4(r[0], r[1], r[2], 0.0f)) - m;
+                            s = s + dl * dl;
+                        }
+                        w = s / (d * (float)(repeats - 1u));
+                    }
+                }
+                o = make_float4(tx / d, ty / d, tz / d, w);
             }
             out[i] = o;
+            if (VAR) {
+                const float* p = pos + 3 * (size_t)(i * repeats);
+                const float* q = nrm + 3 * (size_t)(i * repeats);
+                gpos[i] = make_float4(p[0], p[1], p[2], sampled ? 1.0f : 0.0f);
+                gnrm[i] = make_float4(q[0], q[1], q[2], 0.0f);
+            }
         }
         n_cov += lm_count(covered), n_smp += lm_count(sampled);
     }
@@ -255,66 +278,6 @@ __global__ void __launch_bounds__(kLmStatBlock) k_lm_dilate(const float4* __rest
 }
 
 // ---- the filter (RT_LIGHTMAP_FILTER) ---------------------------------------------------------------------------------------------------------
-// k_lm_resolve with step 5a: the same dealing of texels and the same statistics; .w of the output is the variance of the texel's mean
-// luminance (0 where not sampled, and for one repeat), not alpha: the mask goes to .w of the position guide, 1 where sampled. The guides are
-// the texel's first entry's.
-__global__ void __launch_bounds__(kLmStatBlock) k_lm_resolve_var(const uint32_t* __restrict__ owner, const float* __restrict__ rad,
-                                                                  const uint32_t* __restrict__ rays, const float* __restrict__ pos,
-                                                                  const float* __restrict__ nrm, uint32_t n, uint32_t repeats,
-                                                                  float4* __restrict__ out, float4* __restrict__ gpos, float4* __restrict__ gnrm,
-                                                                  rt_lightmap_stats* __restrict__ stats) {
-    uint32_t n_cov = 0, n_smp = 0;
-    unsigned long long traced = 0;
-    for (uint32_t j = 0; j < kLmLaneTexels; ++j) {
-        const uint32_t i = blockIdx.x * kLmWaveTexels + j * kLmStatBlock + threadIdx.x; // below 2^26 + kLmWaveTexels
-        bool covered = false, sampled = false;
-        if (i < n) {
-            covered = owner[i] != kNoTri;
-            bool rejected = false;
-            for (uint32_t k = 0; k < repeats; ++k) {
-                const uint32_t r = rays[i * repeats + k];
-                if (r == 0xFFFFFFFFu) rejected = true;
-                else traced += r;
-            }
-            sampled = covered && !rejected;
-            float4 o = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-            if (sampled) {
-                const float d = (float)repeats;
-                float tx = 0.0f, ty = 0.0f, tz = 0.0f, tl = 0.0f;
-                for (uint32_t k = 0; k < repeats; ++k) {
-                    const float* r = rad + 3 * (size_t)(i * repeats + k);
-                    tx = tx + r[0], ty = ty + r[1], tz = tz + r[2];
-                    tl = tl + luminance(make_float4(r[0], r[1], r[2], 0.0f));
-                }
-                float var = 0.0f;
-                if (repeats > 1) {
-                    const float m = tl / d;
-                    float s = 0.0f;
-                    for (uint32_t k = 0; k < repeats; ++k) {
-                        const float* r = rad + 3 * (size_t)(i * repeats + k);
-                        const float dl = luminance(make_float4(r[0], r[1], r[2], 0.0f)) - m;
-                        s = s + dl * dl;
-                    }
-                    var = s / (d * (float)(repeats - 1u));
-                }
-                o = make_float4(tx / d, ty / d, tz / d, var);
-            }
-            out[i] = o;
-            const float* p = pos + 3 * (size_t)(i * repeats);
-            const float* q = nrm + 3 * (size_t)(i * repeats);
-            gpos[i] = make_float4(p[0], p[1], p[2], sampled ? 1.0f : 0.0f);
-            gnrm[i] = make_float4(q[0], q[1], q[2], 0.0f);
-        }
-        n_cov += lm_count(covered), n_smp += lm_count(sampled);
-    }
-    for (int off = 32; off > 0; off >>= 1) traced += __shfl_xor(traced, off, 64);
-    if (threadIdx.x == 0) {
-        if (n_cov) atomicAdd(&stats->covered, n_cov);
-        if (n_smp) atomicAdd(&stats->sampled, n_smp);
-        if (traced) atomicAdd((unsigned long long*)&stats->rays, traced);
-    }
-}
-
 // rt_lightmap_filter's planes from the caller's: one thread per texel. In M (alpha 1, an owner, six finite guide floats): rgb with the variance
 // in .w (0 without a variance plane); else zeros. The guides are k_lm_texels' for one repeat. `out` may be `rgba`: a thread reads its texel first.
 __global__ void __launch_bounds__(kLmBlock) k_lm_filter_in(const float4* rgba, const float* __restrict__ var, const uint32_t* __restrict__ owner,
@@ -481,67 +444,24 @@ int enqueue_texels(rt_lightmap* lm, uint32_t repeats, uint32_t seed, uint32_t* t
     return RT_OK;
 }
 
-int begin_call(rt_lightmap* lm, hipStream_t st) {
-    HIPCHK(hipSetDevice(lm->device));
-    if (lm->recorded) HIPCHK(hipStreamWaitEvent(st, lm->ev_last, 0)); // the previous call (any stream) is done with the lightmap's buffers
-    return RT_OK;
-}
-
-int end_call(rt_lightmap* lm, hipStream_t st) {
-    HIPCHK(hipEventRecord(lm->ev_last, st));
-    lm->recorded = true;
-    return RT_OK;
-}
-
-// rt_lightmap_texels[_device]: the planes into tri / pos / nrm (device pointers, any may be null), and the scene's event behind the kernel
-// that read its geometry. PRE: the arguments were checked
-int texels_enqueue(rt_lightmap* lm, uint32_t* tri, float* pos, float* nrm, hipStream_t st) {
-    if (const int rc = begin_call(lm, st)) return rc;
+// A call that reads the scene's geometry without a gather: the owner plane and the planes of one entry per texel into tri / pos / nrm (device
+// pointers, any may be null), and the scene's event for st behind the kernel that read the geometry. PRE: the call's bracket is open
+int enqueue_geometry(rt_lightmap* lm, uint32_t* tri, float* pos, float* nrm, hipStream_t st) {
     hipEvent_t ev = nullptr;
     if (const int rc = scene_stream_event(lm->scene, st, &ev)) return rc;
     if (const int rc = enqueue_texels(lm, 1u, 0u, tri, pos, nrm, nullptr, st)) return rc;
     HIPCHK(hipEventRecord(ev, st));
-    return end_call(lm, st);
-}
-
-// rt_lightmap_bake[_device]: the whole chain on st. out: the device plane the result goes to, or null (the host form: *result tells which
-// of the lightmap's own planes holds it). PRE: the arguments were checked
-int bake_enqueue(rt_lightmap* lm, const rt_lightmap_params* p, float4* out, rt_lightmap_stats* stats, hipStream_t st, float4** result) {
-    if (const int rc = begin_call(lm, st)) return rc;
-    const int32_t W = lm->width, H = lm->height;
-    const uint32_t n = (uint32_t)W * (uint32_t)H, R = p->repeats;
-    if (const int rc = enqueue_texels(lm, R, p->seed, nullptr, lm->d_pos, lm->d_nrm, lm->d_state, st)) return rc;
-    rt_gather_query q{};
-    q.n = n * R, q.max_depth = p->max_depth, q.samples = p->samples, q.rr_start = p->rr_start;
-    q.pos = lm->d_pos, q.normal = lm->d_nrm, q.rng = lm->d_state, q.rng_out = nullptr, q.radiance = lm->d_rad, q.rays = lm->d_rays;
-    if (const int rc = rt_gather_paths_device(lm->scene, &q, st)) return rc; // records the scene's event for st behind k_lm_texels too
-    HIPCHK(hipSetDevice(lm->device));
-    rt_lightmap_stats* d_stats = stats ? stats : lm->d_stats;
-    HIPCHK(hipMemsetAsync(d_stats, 0, sizeof(rt_lightmap_stats), st));
-    float4* last = out ? out : lm->d_plane[p->dilate & 1u];
-    const dim3 grid((n + kLmWaveTexels - 1u) / kLmWaveTexels), block(kLmStatBlock);
-    hipLaunchKernelGGL(k_lm_resolve, grid, block, 0, st, (const uint32_t*)lm->d_owner, (const float*)lm->d_rad, (const uint32_t*)lm->d_rays, n, R,
-                       p->dilate ? lm->d_plane[0] : last, d_stats);
-    HIPCHK(hipGetLastError());
-    for (uint32_t j = 0; j < p->dilate; ++j) {
-        const float4* src = lm->d_plane[j & 1u];
-        if (j + 1 == p->dilate) hipLaunchKernelGGL(k_lm_dilate<true>, grid, block, 0, st, src, W, H, last, d_stats);
-        else hipLaunchKernelGGL(k_lm_dilate<false>, grid, block, 0, st, src, W, H, lm->d_plane[(j + 1u) & 1u], d_stats);
-        HIPCHK(hipGetLastError());
-    }
-    if (result) *result = last;
-    return end_call(lm, st);
-}
-
-int bake_check(const rt_lightmap* lm, const rt_lightmap_params* p, const void* out) {
-    if (const int rc = check_params(p)) return rc;
-    if (!lm || !out) return fail(RT_ERR_INVALID, "null argument");
-    if (p->repeats > lm->max_repeats) return fail(RT_ERR_INVALID, "repeats exceeds the max_repeats the lightmap was created with");
     return RT_OK;
 }
 
-// ---- the filter's calls (RT_LIGHTMAP_FILTER) -------------------------------------------------------------------------------------------------
-// (the entry points judge the parameters first: they need no lightmap)
+// rt_lightmap_texels[_device]. PRE: the arguments were checked
+int texels_enqueue(rt_lightmap* lm, uint32_t* tri, float* pos, float* nrm, hipStream_t st) {
+    if (const int rc = begin_call(lm, st)) return rc;
+    if (const int rc = enqueue_geometry(lm, tri, pos, nrm, st)) return rc;
+    return end_call(lm, st);
+}
+
+// ---- the checks (the entry points judge the parameters first: they need no lightmap) ------------------------------------------------------
 int check_filter_params(const rt_lightmap_filter_params* f) {
     if (f->iterations > kMaxIterations) return fail(RT_ERR_INVALID, "iterations must be 0 .. 10");
     const float s[3] = {f->sigma_luminance, f->sigma_normal, f->sigma_position};
@@ -555,16 +475,24 @@ int check_filter_flag(const rt_lightmap* lm) {
     return RT_OK;
 }
 
-// f null: no filter (rt_lightmap_bake_filtered's identity)
-int bake_filtered_check(const rt_lightmap* lm, const rt_lightmap_params* p, const rt_lightmap_filter_params* f, const void* out) {
+// The filter stage of a bake (rt_lightmap_bake_filtered[_device]); rt_lightmap_bake[_device] has none. f null: no filter, that call's identity,
+// which still keeps the variance and the guides. out_var: a device plane or null
+struct FilterStage {
+    const rt_lightmap_filter_params* f;
+    float* out_var;
+};
+
+// fs null: rt_lightmap_bake[_device]
+int bake_check(const rt_lightmap* lm, const rt_lightmap_params* p, const FilterStage* fs, const void* out) {
     if (const int rc = check_params(p)) return rc;
-    if (f) {
-        if (const int rc = check_filter_params(f)) return rc;
-        if (f->iterations > 0 && !std::isinf(f->sigma_luminance) && p->repeats < 2)
+    if (fs && fs->f) {
+        if (const int rc = check_filter_params(fs->f)) return rc;
+        if (fs->f->iterations > 0 && !std::isinf(fs->f->sigma_luminance) && p->repeats < 2)
             return fail(RT_ERR_INVALID, "a finite sigma_luminance needs repeats >= 2: one entry per texel has no noise estimate");
     }
     if (!lm || !out) return fail(RT_ERR_INVALID, "null argument");
-    if (const int rc = check_filter_flag(lm)) return rc;
+    if (fs)
+        if (const int rc = check_filter_flag(lm)) return rc;
     if (p->repeats > lm->max_repeats) return fail(RT_ERR_INVALID, "repeats exceeds the max_repeats the lightmap was created with");
     return RT_OK;
 }
@@ -577,6 +505,7 @@ int filter_check(const rt_lightmap* lm, const rt_lightmap_filter_params* f, cons
     return check_filter_flag(lm);
 }
 
+// ---- the filter (RT_LIGHTMAP_FILTER) ---------------------------------------------------------------------------------------------------------
 // the plane the filter's result lies in where it stays in the lightmap: the last launch reads d_plane[(iters - 1) & 1], or d_plane[0] without one
 uint32_t filtered_plane(const rt_lightmap_filter_params* f) { return f && f->iterations ? (f->iterations & 1u) : 1u; }
 
@@ -608,10 +537,11 @@ int enqueue_filter(rt_lightmap* lm, const rt_lightmap_filter_params* f, float4* 
     return RT_OK;
 }
 
-// rt_lightmap_bake_filtered[_device]: bake_enqueue with the resolve that keeps the variance and the guides, and the filter in front of the
-// dilation. out / result as bake_enqueue's; out_var: a device plane or null. PRE: the arguments were checked
-int bake_filtered_enqueue(rt_lightmap* lm, const rt_lightmap_params* p, const rt_lightmap_filter_params* f, float4* out, float* out_var,
-                          rt_lightmap_stats* stats, hipStream_t st, float4** result) {
+// rt_lightmap_bake[_device] (fs null) and rt_lightmap_bake_filtered[_device]: the whole chain on st. The resolve, with a filter stage the one that
+// keeps the variance and the guides and behind it the filter, leaves its plane in d_plane[first]; the dilation ping-pongs on from there. out: the
+// device plane the result goes to, or null (the host form: *result tells which of the lightmap's own planes holds it). PRE: the arguments were checked
+int bake_enqueue(rt_lightmap* lm, const rt_lightmap_params* p, const FilterStage* fs, float4* out, rt_lightmap_stats* stats, hipStream_t st,
+                 float4** result) {
     if (const int rc = begin_call(lm, st)) return rc;
     const int32_t W = lm->width, H = lm->height;
     const uint32_t n = (uint32_t)W * (uint32_t)H, R = p->repeats;
@@ -623,38 +553,50 @@ int bake_filtered_enqueue(rt_lightmap* lm, const rt_lightmap_params* p, const rt
     HIPCHK(hipSetDevice(lm->device));
     rt_lightmap_stats* d_stats = stats ? stats : lm->d_stats;
     HIPCHK(hipMemsetAsync(d_stats, 0, sizeof(rt_lightmap_stats), st));
-    const uint32_t fp = filtered_plane(f);
-    float4* last = out ? out : lm->d_plane[(fp + p->dilate) & 1u];
+    const uint32_t first = fs ? filtered_plane(fs->f) : 0u, dilate = p->dilate;
+    float4* last = out ? out : lm->d_plane[(first + dilate) & 1u];
+    float4* undilated = dilate ? lm->d_plane[first] : last;
     const dim3 grid((n + kLmWaveTexels - 1u) / kLmWaveTexels), block(kLmStatBlock);
-    hipLaunchKernelGGL(k_lm_resolve_var, grid, block, 0, st, (const uint32_t*)lm->d_owner, (const float*)lm->d_rad, (const uint32_t*)lm->d_rays,
-                       (const float*)lm->d_pos, (const float*)lm->d_nrm, n, R, lm->d_plane[0], lm->d_gpos, lm->d_gnrm, d_stats);
+    hipLaunchKernelGGL(fs ? k_lm_resolve<true> : k_lm_resolve<false>, grid, block, 0, st, (const uint32_t*)lm->d_owner, (const float*)lm->d_rad,
+                       (const uint32_t*)lm->d_rays, n, R, fs ? lm->d_plane[0] : undilated, d_stats, (const float*)lm->d_pos, (const float*)lm->d_nrm,
+                       lm->d_gpos, lm->d_gnrm);
     HIPCHK(hipGetLastError());
-    if (const int rc = enqueue_filter(lm, f, p->dilate ? lm->d_plane[fp] : last, out_var, st)) return rc;
-    for (uint32_t j = 0; j < p->dilate; ++j) {
-        const float4* src = lm->d_plane[(fp + j) & 1u];
-        if (j + 1 == p->dilate) hipLaunchKernelGGL(k_lm_dilate<true>, grid, block, 0, st, src, W, H, last, d_stats);
-        else hipLaunchKernelGGL(k_lm_dilate<false>, grid, block, 0, st, src, W, H, lm->d_plane[(fp + j + 1u) & 1u], d_stats);
+    if (fs)
+        if (const int rc = enqueue_filter(lm, fs->f, undilated, fs->out_var, st)) return rc;
+    for (uint32_t j = 0; j < dilate; ++j) {
+        const float4* src = lm->d_plane[(first + j) & 1u];
+        if (j + 1 == dilate) hipLaunchKernelGGL(k_lm_dilate<true>, grid, block, 0, st, src, W, H, last, d_stats);
+        else hipLaunchKernelGGL(k_lm_dilate<false>, grid, block, 0, st, src, W, H, lm->d_plane[(first + j + 1u) & 1u], d_stats);
         HIPCHK(hipGetLastError());
     }
     if (result) *result = last;
     return end_call(lm, st);
 }
 
-// rt_lightmap_filter[_device]: the lightmap's guides as they are now, the caller's planes cut to the mask, the filter. All pointers are device
-// pointers; var and out_var may be null. PRE: the arguments were checked
+// rt_lightmap_filter[_device] behind the wait: the lightmap's guides as they are now, the caller's planes cut to the mask, the filter, the call's
+// end. All pointers are device pointers; var and out_var may be null. PRE: the arguments were checked and the call's bracket is open (the host
+// form has staged its arguments in it)
 int filter_enqueue(rt_lightmap* lm, const rt_lightmap_filter_params* f, const float4* rgba, const float* var, float4* out, float* out_var,
                    hipStream_t st) {
-    if (const int rc = begin_call(lm, st)) return rc;
-    hipEvent_t ev = nullptr;
-    if (const int rc = scene_stream_event(lm->scene, st, &ev)) return rc;
-    if (const int rc = enqueue_texels(lm, 1u, 0u, nullptr, lm->d_pos, lm->d_nrm, nullptr, st)) return rc;
-    HIPCHK(hipEventRecord(ev, st));
+    if (const int rc = enqueue_geometry(lm, nullptr, lm->d_pos, lm->d_nrm, st)) return rc;
     const uint32_t n = (uint32_t)lm->width * (uint32_t)lm->height;
     hipLaunchKernelGGL(k_lm_filter_in, dim3((n + kLmBlock - 1u) / kLmBlock), dim3(kLmBlock), 0, st, rgba, var, (const uint32_t*)lm->d_owner,
                        (const float*)lm->d_pos, (const float*)lm->d_nrm, n, lm->d_plane[0], lm->d_gpos, lm->d_gnrm);
     HIPCHK(hipGetLastError());
     if (const int rc = enqueue_filter(lm, f, out, out_var, st)) return rc;
     return end_call(lm, st);
+}
+
+// The end of the host forms, behind the call on the lightmap's stream: the rgba plane, the variance plane from its staging and the statistics
+// (each of the last two where its pointer is not null) to the host, and the stream has run dry
+int host_results(rt_lightmap* lm, const float4* d_rgba, float* out_rgba, float* out_variance, rt_lightmap_stats* stats) {
+    hipStream_t st = lm->stream;
+    const size_t n = (size_t)lm->width * (size_t)lm->height;
+    HIPCHK(hipMemcpyAsync(out_rgba, d_rgba, n * 16u, hipMemcpyDeviceToHost, st));
+    if (out_variance) HIPCHK(hipMemcpyAsync(out_variance, lm->d_host_var_out, n * 4u, hipMemcpyDeviceToHost, st));
+    if (stats) HIPCHK(hipMemcpyAsync(stats, lm->d_stats, sizeof(rt_lightmap_stats), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return RT_OK;
 }
 
 } // namespace
@@ -702,10 +644,9 @@ int rt_lightmap_create_ex(rt_scene* s, int32_t width, int32_t height, uint32_t m
             rt_lightmap_destroy(lm);
             return fail(RT_ERR_HIP, "hipMemcpy of the lightmap's UVs and vertices failed");
         }
-        if (hipStreamCreateWithFlags(&lm->stream, hipStreamNonBlocking) != hipSuccess ||
-            hipEventCreateWithFlags(&lm->ev_last, hipEventDisableTiming) != hipSuccess) {
+        if (const int rc = bracket_open(lm)) {
             rt_lightmap_destroy(lm);
-            return fail(RT_ERR_HIP, "hipStreamCreate / hipEventCreate failed");
+            return rc;
         }
         *out = lm;
         return (int)RT_OK;
@@ -714,15 +655,11 @@ int rt_lightmap_create_ex(rt_scene* s, int32_t width, int32_t height, uint32_t m
 
 void rt_lightmap_destroy(rt_lightmap* lm) {
     if (!lm) return;
-    if (lm->device >= 0 && hipSetDevice(lm->device) == hipSuccess) {
-        if (lm->recorded) (void)hipEventSynchronize(lm->ev_last);
+    if (bracket_close(lm))
         for (void* p : {(void*)lm->d_uv, (void*)lm->d_wv, (void*)lm->d_owner, (void*)lm->d_pos, (void*)lm->d_nrm, (void*)lm->d_state, (void*)lm->d_rad,
                         (void*)lm->d_rays, (void*)lm->d_plane[0], (void*)lm->d_plane[1], (void*)lm->d_stats, (void*)lm->d_gpos, (void*)lm->d_gnrm,
                         (void*)lm->d_host_rgba, (void*)lm->d_host_var_in, (void*)lm->d_host_var_out})
             (void)hipFree(p);
-        if (lm->ev_last) (void)hipEventDestroy(lm->ev_last);
-        if (lm->stream) (void)hipStreamDestroy(lm->stream);
-    }
     delete lm;
 }
 
@@ -746,39 +683,32 @@ int rt_lightmap_texels_device(rt_lightmap* lm, void* d_tri, void* d_pos, void* d
 }
 
 int rt_lightmap_bake(rt_lightmap* lm, const rt_lightmap_params* p, float* out_rgba, rt_lightmap_stats* stats) {
-    if (const int rc = bake_check(lm, p, out_rgba)) return rc;
-    hipStream_t st = lm->stream;
+    if (const int rc = bake_check(lm, p, nullptr, out_rgba)) return rc;
     float4* result = nullptr;
-    if (const int rc = bake_enqueue(lm, p, nullptr, nullptr, st, &result)) return rc;
-    HIPCHK(hipMemcpyAsync(out_rgba, result, (size_t)lm->width * (size_t)lm->height * 16u, hipMemcpyDeviceToHost, st));
-    if (stats) HIPCHK(hipMemcpyAsync(stats, lm->d_stats, sizeof(rt_lightmap_stats), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    return RT_OK;
+    if (const int rc = bake_enqueue(lm, p, nullptr, nullptr, nullptr, lm->stream, &result)) return rc;
+    return host_results(lm, result, out_rgba, nullptr, stats);
 }
 
 int rt_lightmap_bake_device(rt_lightmap* lm, const rt_lightmap_params* p, void* d_out_rgba, void* d_stats, void* stream) {
-    if (const int rc = bake_check(lm, p, d_out_rgba)) return rc;
-    return bake_enqueue(lm, p, (float4*)d_out_rgba, (rt_lightmap_stats*)d_stats, (hipStream_t)stream, nullptr);
+    if (const int rc = bake_check(lm, p, nullptr, d_out_rgba)) return rc;
+    return bake_enqueue(lm, p, nullptr, (float4*)d_out_rgba, (rt_lightmap_stats*)d_stats, (hipStream_t)stream, nullptr);
 }
 
 int rt_lightmap_bake_filtered(rt_lightmap* lm, const rt_lightmap_params* p, const rt_lightmap_filter_params* f, float* out_rgba, float* out_variance,
                               rt_lightmap_stats* stats) {
-    if (const int rc = bake_filtered_check(lm, p, f, out_rgba)) return rc;
-    hipStream_t st = lm->stream;
+    FilterStage fs{f, nullptr};
+    if (const int rc = bake_check(lm, p, &fs, out_rgba)) return rc;
+    fs.out_var = out_variance ? lm->d_host_var_out : nullptr;
     float4* result = nullptr;
-    if (const int rc = bake_filtered_enqueue(lm, p, f, nullptr, out_variance ? lm->d_host_var_out : nullptr, nullptr, st, &result)) return rc;
-    const size_t n = (size_t)lm->width * (size_t)lm->height;
-    HIPCHK(hipMemcpyAsync(out_rgba, result, n * 16u, hipMemcpyDeviceToHost, st));
-    if (out_variance) HIPCHK(hipMemcpyAsync(out_variance, lm->d_host_var_out, n * 4u, hipMemcpyDeviceToHost, st));
-    if (stats) HIPCHK(hipMemcpyAsync(stats, lm->d_stats, sizeof(rt_lightmap_stats), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    return RT_OK;
+    if (const int rc = bake_enqueue(lm, p, &fs, nullptr, nullptr, lm->stream, &result)) return rc;
+    return host_results(lm, result, out_rgba, out_variance, stats);
 }
 
 int rt_lightmap_bake_filtered_device(rt_lightmap* lm, const rt_lightmap_params* p, const rt_lightmap_filter_params* f, void* d_out_rgba,
                                      void* d_out_variance, void* d_stats, void* stream) {
-    if (const int rc = bake_filtered_check(lm, p, f, d_out_rgba)) return rc;
-    return bake_filtered_enqueue(lm, p, f, (float4*)d_out_rgba, (float*)d_out_variance, (rt_lightmap_stats*)d_stats, (hipStream_t)stream, nullptr);
+    const FilterStage fs{f, (float*)d_out_variance};
+    if (const int rc = bake_check(lm, p, &fs, d_out_rgba)) return rc;
+    return bake_enqueue(lm, p, &fs, (float4*)d_out_rgba, (rt_lightmap_stats*)d_stats, (hipStream_t)stream, nullptr);
 }
 
 int rt_lightmap_filter(rt_lightmap* lm, const rt_lightmap_filter_params* f, const float* rgba, const float* variance, float* out_rgba,
@@ -792,15 +722,13 @@ int rt_lightmap_filter(rt_lightmap* lm, const rt_lightmap_filter_params* f, cons
     if (const int rc = filter_enqueue(lm, f, lm->d_host_rgba, variance ? lm->d_host_var_in : nullptr, lm->d_host_rgba,
                                       out_variance ? lm->d_host_var_out : nullptr, st))
         return rc;
-    HIPCHK(hipMemcpyAsync(out_rgba, lm->d_host_rgba, n * 16u, hipMemcpyDeviceToHost, st));
-    if (out_variance) HIPCHK(hipMemcpyAsync(out_variance, lm->d_host_var_out, n * 4u, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    return RT_OK;
+    return host_results(lm, lm->d_host_rgba, out_rgba, out_variance, nullptr);
 }
 
 int rt_lightmap_filter_device(rt_lightmap* lm, const rt_lightmap_filter_params* f, const void* d_rgba, const void* d_variance, void* d_out_rgba,
                               void* d_out_variance, void* stream) {
     if (const int rc = filter_check(lm, f, d_rgba, d_variance, d_out_rgba)) return rc;
+    if (const int rc = begin_call(lm, (hipStream_t)stream)) return rc;
     return filter_enqueue(lm, f, (const float4*)d_rgba, (const float*)d_variance, (float4*)d_out_rgba, (float*)d_out_variance, (hipStream_t)stream);
 }
 

@@ -10,9 +10,8 @@
 #include "rt_internal.h"
 #include "rt_device.h"
 
-struct rt_probe_volume {
+struct rt_probe_volume : CallBracket { // the host forms run on its stream
     rt_scene* scene = nullptr;
-    int device = -1;
     rt_probe_volume_desc desc{};
     uint32_t probes = 0;
     float* d_pos = nullptr;          // 3 floats per entry (max_dirs entries per probe)
@@ -24,9 +23,6 @@ struct rt_probe_volume {
     rt_probe_stats* d_stats = nullptr;
     float* d_host_pts = nullptr;     // the host form of sample: kPvStagePoints points at a time, pos | normal | rgb
     bool has_table = false;          // a bake or a set_sh was enqueued
-    hipStream_t stream = nullptr;    // the host forms run here
-    hipEvent_t ev_last = nullptr;    // recorded behind every call: the next call's stream waits for it
-    bool recorded = false;
 };
 
 namespace rt {
@@ -235,15 +231,10 @@ int check_bake_params(const rt_probe_volume* v, const rt_probe_bake_params* p) {
     return RT_OK;
 }
 
-int begin_call(rt_probe_volume* v, hipStream_t st) {
-    HIPCHK(hipSetDevice(v->device));
-    if (v->recorded) HIPCHK(hipStreamWaitEvent(st, v->ev_last, 0)); // the previous call (any stream) is done with the volume's buffers
-    return RT_OK;
-}
-
-int end_call(rt_probe_volume* v, hipStream_t st) {
-    HIPCHK(hipEventRecord(v->ev_last, st));
-    v->recorded = true;
+// the end of a host form whose copies lie inside the bracket: the call's end, then the stream has run dry
+int end_call_host(rt_probe_volume* v) {
+    if (const int rc = end_call(v, v->stream)) return rc;
+    HIPCHK(hipStreamSynchronize(v->stream));
     return RT_OK;
 }
 
@@ -322,10 +313,9 @@ int rt_probe_volume_create(rt_scene* s, const rt_probe_volume_desc* d, uint32_t 
             rt_probe_volume_destroy(v);
             return fail(RT_ERR_OOM, "hipMalloc of the probe volume's buffers failed");
         }
-        if (hipStreamCreateWithFlags(&v->stream, hipStreamNonBlocking) != hipSuccess ||
-            hipEventCreateWithFlags(&v->ev_last, hipEventDisableTiming) != hipSuccess) {
+        if (const int rc = bracket_open(v)) {
             rt_probe_volume_destroy(v);
-            return fail(RT_ERR_HIP, "hipStreamCreate / hipEventCreate failed");
+            return rc;
         }
         *out = v;
         return (int)RT_OK;
@@ -334,14 +324,10 @@ int rt_probe_volume_create(rt_scene* s, const rt_probe_volume_desc* d, uint32_t 
 
 void rt_probe_volume_destroy(rt_probe_volume* v) {
     if (!v) return;
-    if (v->device >= 0 && hipSetDevice(v->device) == hipSuccess) {
-        if (v->recorded) (void)hipEventSynchronize(v->ev_last);
+    if (bracket_close(v))
         for (void* p : {(void*)v->d_pos, (void*)v->d_dir, (void*)v->d_state, (void*)v->d_rad, (void*)v->d_rays, (void*)v->d_sh, (void*)v->d_stats,
                         (void*)v->d_host_pts})
             (void)hipFree(p);
-        if (v->ev_last) (void)hipEventDestroy(v->ev_last);
-        if (v->stream) (void)hipStreamDestroy(v->stream);
-    }
     delete v;
 }
 
@@ -355,9 +341,7 @@ int rt_probe_volume_entries(rt_probe_volume* v, const rt_probe_bake_params* p, f
     if (pos) HIPCHK(hipMemcpyAsync(pos, v->d_pos, n * 12u, hipMemcpyDeviceToHost, st));
     if (dir) HIPCHK(hipMemcpyAsync(dir, v->d_dir, n * 12u, hipMemcpyDeviceToHost, st));
     if (state) HIPCHK(hipMemcpyAsync(state, v->d_state, n * 4u, hipMemcpyDeviceToHost, st));
-    if (const int rc = end_call(v, st)) return rc;
-    HIPCHK(hipStreamSynchronize(st));
-    return RT_OK;
+    return end_call_host(v);
 }
 
 int rt_probe_volume_entries_device(rt_probe_volume* v, const rt_probe_bake_params* p, void* d_pos, void* d_dir, void* d_state, void* stream) {
@@ -390,9 +374,7 @@ int rt_probe_volume_set_sh(rt_probe_volume* v, const float* sh) {
     if (const int rc = begin_call(v, st)) return rc;
     HIPCHK(hipMemcpyAsync(v->d_sh, sh, (size_t)v->probes * 144u, hipMemcpyHostToDevice, st));
     v->has_table = true;
-    if (const int rc = end_call(v, st)) return rc;
-    HIPCHK(hipStreamSynchronize(st));
-    return RT_OK;
+    return end_call_host(v);
 }
 
 int rt_probe_volume_set_sh_device(rt_probe_volume* v, const void* d_sh, void* stream) {
@@ -410,9 +392,7 @@ int rt_probe_volume_get_sh(rt_probe_volume* v, float* sh) {
     hipStream_t st = v->stream;
     if (const int rc = begin_call(v, st)) return rc;
     HIPCHK(hipMemcpyAsync(sh, v->d_sh, (size_t)v->probes * 144u, hipMemcpyDeviceToHost, st));
-    if (const int rc = end_call(v, st)) return rc;
-    HIPCHK(hipStreamSynchronize(st));
-    return RT_OK;
+    return end_call_host(v);
 }
 
 int rt_probe_volume_get_sh_device(rt_probe_volume* v, void* d_sh, void* stream) {
@@ -439,9 +419,7 @@ int rt_probe_volume_sample(rt_probe_volume* v, uint32_t n, const float* pos, con
         if (const int rc = enqueue_sample(v, m, d_pos, d_nrm, d_out, st)) return rc;
         HIPCHK(hipMemcpyAsync(out_rgb + 3 * (size_t)i0, d_out, (size_t)m * 12u, hipMemcpyDeviceToHost, st));
     }
-    if (const int rc = end_call(v, st)) return rc;
-    HIPCHK(hipStreamSynchronize(st));
-    return RT_OK;
+    return end_call_host(v);
 }
 
 int rt_probe_volume_sample_device(rt_probe_volume* v, uint32_t n, const void* d_pos, const void* d_normal, void* d_out_rgb, void* stream) {

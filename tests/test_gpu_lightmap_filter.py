@@ -1,5 +1,5 @@
 """Lightmap filtering on the GPU (include/rt_mi355x.h: RT_LIGHTMAP_FILTER, rt_lightmap_bake_filtered[_device], rt_lightmap_filter[_device];
-the kernels k_lm_resolve_var, k_lm_filter_in, k_lm_filter_copy and k_lm_atrous of csrc/rt_lightmap.hip). rt_lightmap_filter is compared with
+the kernels k_lm_resolve<true>, k_lm_filter_in, k_lm_filter_copy and k_lm_atrous of csrc/rt_lightmap.hip). rt_lightmap_filter is compared with
 lm_filter_model over the guides of texel_model, rt_lightmap_bake_filtered with the chain dilate_model(lm_filter_model(lm_variance_model +
 resolve_model(Scene.gather_paths(...)))). Every comparison but the last test's is assert_array_equal; the last holds the filter at the
 Python defaults to the error bound DESIGN.md §20 derives from eight seeds."""
@@ -193,6 +193,40 @@ def test_a_filtered_bake_is_its_chain_over_the_librarys_own_gather(cornell, repe
         assert (want_v[a == 1] > 0).any() and (want_v[a != 1] == 0).all()  # the variance is 0 outside M, filled texels included
     raw = lm.bake(SAMPLES, DEPTH, SEED, repeats=repeats, dilate=dilate)
     assert not np.array_equal(raw["rgba"], got["rgba"])
+
+
+@pytest.mark.parametrize("iterations", [0, 1, 2])
+def test_every_parity_of_the_result_plane_in_the_host_form_and_in_a_callers_plane(cornell, iterations):
+    """The chain leaves its result in plane (first + dilate) & 1 of the lightmap's two, first being the plane the filter ends in: 1 for no
+    and for an odd number of iterations, 0 for an even one. Both values of first with dilate 0, odd and even, in the host form (the result read
+    from the lightmap's own plane) and in the device form on a stream (the result in the caller's plane, the planes before it the lightmap's)."""
+    import torch
+    sd, s, uv, W, H, lm = cornell
+    sigmas = (4.0, 0.3, 1.5)
+    kw = dict(repeats=2, iterations=iterations, sigma_luminance=sigmas[0], sigma_normal=sigmas[1], sigma_position=sigmas[2])
+    st = torch.cuda.Stream(device=0)
+    for dilate in (0, 1, 2):
+        what = f"{iterations} iterations, dilate {dilate}"
+        want, want_v, stats = filtered_chain(s, sd, uv, W, H, 2, 0, dilate, iterations, sigmas, key=("filter cornell", W, 2))
+        host = lm.bake_filtered(SAMPLES, DEPTH, SEED, dilate=dilate, **kw)
+        np.testing.assert_array_equal(host["rgba"], want, err_msg=what)
+        np.testing.assert_array_equal(host["variance"], want_v, err_msg=what)
+        assert host["stats"] == stats and (stats["filled"] > 0) == (dilate > 0), what
+        rgba = torch.full((H, W, 4), 7.0, dtype=torch.float32, device="cuda")
+        var = torch.full((H, W), 7.0, dtype=torch.float32, device="cuda")
+        d_stats = torch.full((3,), 0x5555555555555555, dtype=torch.int64, device="cuda")
+        torch.cuda.synchronize()
+        lm.bake_filtered_device(rgba.data_ptr(), SAMPLES, DEPTH, SEED, dilate=dilate, d_variance=var.data_ptr(), d_stats=d_stats.data_ptr(),
+                                stream=st.cuda_stream, **kw)
+        torch.cuda.synchronize()
+        words = d_stats.cpu().numpy().view(np.uint32)
+        got = {"covered": int(words[0]), "sampled": int(words[1]), "filled": int(words[2]), "rays": int(d_stats.cpu().numpy().view(np.uint64)[2])}
+        np.testing.assert_array_equal(rgba.cpu().numpy(), want, err_msg=what)
+        np.testing.assert_array_equal(var.cpu().numpy(), want_v, err_msg=what)
+        assert got == stats and words[3] == 0, what
+        np.testing.assert_array_equal(rgba.cpu().numpy(), host["rgba"], err_msg=what)
+        np.testing.assert_array_equal(var.cpu().numpy(), host["variance"], err_msg=what)
+        assert got == host["stats"], what
 
 
 def test_no_iterations_and_no_parameters_are_the_unfiltered_bake_with_the_variance_of_its_mean(cornell):

@@ -6,7 +6,8 @@ On the atrium (detail 4, the bench scene) at 1920x1080 and 64 spp, one process:
   - rt_scene_create wall time with each builder (SAH and LBVH on the host, LBVH_GPU on the device), the median of a few;
   - sah_cost and the frame time (device_ms, median of 3 after a warm-up frame) of the built scene, of the refit scene turned by DEG, and of
     a fresh SAH build of the turned scene (the same image: the frame is independent of the tree).
-Usage: python scripts/refit_probe.py [DEG] [RENDERER] > out.txt   (DEG 30 by default, RENDERER wavefront | megakernel)"""
+Usage: python scripts/refit_probe.py [DEG] [RENDERER] [updates] > out.txt   (DEG 30 by default, RENDERER wavefront | megakernel; "updates":
+the update and creation times only, no frames — what an A/B of two libraries, RT_MI355X_LIB, repeats run by run)"""
 import json
 import statistics
 import sys
@@ -85,6 +86,9 @@ def main():
         dev.append(st.device_ms)
     out["update_positions_normals"] = dict(device_ms=spread(dev), wall_ms=spread(wall), launches=st.launches)
     s.close()
+    if "updates" in sys.argv[3:]:
+        print(json.dumps(out))
+        return
 
     # tree quality: the built scene, the refit scene turned by DEG, a fresh build of the turned scene
     s = Scene(sd, 0, abi.RT_BVH_SAH, updatable=True)

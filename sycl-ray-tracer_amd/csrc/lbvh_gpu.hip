@@ -24,6 +24,7 @@
 
 #include "bvh_quantise.h"
 #include "scene_build.h"
+#include "scene_rules.h"
 
 namespace rt {
 namespace {
@@ -52,12 +53,7 @@ __global__ void __launch_bounds__(256) k_prims(uint32_t n, const float* __restri
                                                 uint32_t* __restrict__ vals) {
     const uint32_t t = blockIdx.x * 256u + threadIdx.x;
     if (t >= n) return;
-    const float* w = wverts + 9 * (size_t)t;
-    Box3 b;
-    for (int a = 0; a < 3; ++a) {
-        b.lo[a] = fminf(w[a], fminf(w[3 + a], w[6 + a]));
-        b.hi[a] = fmaxf(w[a], fmaxf(w[3 + a], w[6 + a]));
-    }
+    const Box3 b = rt::tri_box(wverts + 9 * (size_t)t);
     tri_box[t] = b;
     const float c[3] = {0.5f * (b.lo[0] + b.hi[0]), 0.5f * (b.lo[1] + b.hi[1]), 0.5f * (b.lo[2] + b.hi[2])};
     const float ci[3] = {cext_inv.x, cext_inv.y, cext_inv.z}, cl[3] = {clo.x, clo.y, clo.z};

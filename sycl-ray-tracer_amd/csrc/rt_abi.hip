@@ -2,6 +2,7 @@
 // launches is rt_frame.hip; the gather rt_comm.hip; the probes rt_probes.hip.
 #include "bvh_quantise.h"
 #include "rt_internal.h"
+#include "rt_scene_image.h"
 
 namespace rtlib {
 thread_local std::string g_err;
@@ -71,97 +72,64 @@ int rt_scene_create_ex(const rt_scene_desc* desc, int device, int bvh_kind, uint
         int rc0 = device_ok(device);
         if (rc0 != RT_OK) return rc0;
     }
-    rt_scene* s = new (std::nothrow) rt_scene();
+    std::unique_ptr<rt_scene, decltype(&rt_scene_destroy)> s(new (std::nothrow) rt_scene(), &rt_scene_destroy); // (every early return frees what the scene holds by then)
     if (!s) return fail(RT_ERR_OOM, "host allocation failed");
     std::string err;
     int rc = RT_OK;
     try {
         rc = build_host_scene(desc, bvh_kind, s->hs, err);
     } catch (const std::bad_alloc&) {
-        delete s;
         return fail(RT_ERR_OOM, "host allocation failed while building the scene");
     } catch (const std::exception& e) { // nothing may cross the C ABI as an exception
-        delete s;
         return fail(RT_ERR_INVALID, std::string("scene build failed: ") + e.what());
     }
-    if (rc != RT_OK) {
-        delete s;
-        return fail(rc, err);
-    }
+    if (rc != RT_OK) return fail(rc, err);
+    const bool updatable = (flags & RT_SCENE_UPDATABLE) != 0;
     // the origin skip (rt_types.h: SkipRec): static host-built trees only — vertices that move break coplanarity, and a device-built tree has no host pass
     rc = no_throw([&] {
-        if ((flags & RT_SCENE_UPDATABLE) || s->hs.built_by == RT_BVH_LBVH_GPU) clear_skip_table(s->hs);
+        if (updatable || s->hs.built_by == RT_BVH_LBVH_GPU) clear_skip_table(s->hs);
         else build_skip_table(s->hs);
         return (int)RT_OK;
     });
-    if (rc != RT_OK) {
-        delete s;
-        return rc;
-    }
+    if (rc != RT_OK) return rc;
     s->device = device;
     if (device >= 0) {
-        rc = device_ok(device);
-        if (rc == RT_OK) {
-            if (s->hs.nodes.size() > (size_t)(0x7FFFFFFF / 64)) { // (a tree of 33 M nodes: ~130 M triangles)
-                rt_scene_destroy(s);
-                return fail(RT_ERR_INVALID, "BVH too large for 32-bit node offsets");
-            }
-            std::vector<BvhNode> dn(s->hs.nodes);
-            for (BvhNode& n : dn)
-                for (int k = 0; k < 4; ++k)
-                    if (n.child[k] >= 0) n.child[k] *= 64;
-            rc = upload(dn, &s->dev.nodes, s->device_bytes);
-        }
-        if (rc == RT_OK) { // the device's triangle records: the host records' ten live dwords at a kTriBytes stride
-            std::vector<uint8_t> packed(s->hs.tris.size() * (size_t)kTriBytes + 48, 0); // + 48: the whole-leaf step reads 80 bytes at every leaf, also at a last leaf of one record
-            for (size_t i = 0; i < s->hs.tris.size(); ++i) std::memcpy(packed.data() + i * kTriBytes, &s->hs.tris[i], std::min<size_t>(kTriBytes, sizeof(TriRec)));
-            rc = upload(packed, &s->dev.tris, s->device_bytes);
-        }
-        if (rc == RT_OK) rc = upload(s->hs.shade, &s->dev.shade, s->device_bytes);
-        if (rc == RT_OK) rc = upload(s->hs.skip, &s->dev.skip, s->device_bytes);
-        if (rc == RT_OK) { // (an updatable scene's table has room for a row per instance: the distinct matrices may grow)
-            std::vector<InstRec> rows(s->hs.inst);
-            if (flags & RT_SCENE_UPDATABLE) rows.resize(std::max<size_t>(rows.size(), desc->n_instances));
-            rc = upload(rows, &s->dev.inst, s->device_bytes);
-        }
-        if (rc == RT_OK) rc = upload(s->hs.mats, &s->dev.mats, s->device_bytes);
-        if (rc == RT_OK) rc = upload(s->hs.tex, &s->dev.tex, s->device_bytes);
-        if (rc == RT_OK && hipMalloc((void**)&s->d_query_cursor, kQueryCursorBytes) != hipSuccess) // rt_query.hip
-            rc = fail(RT_ERR_OOM, "device allocation failed (the ray-query cursors)");
-        if (rc != RT_OK) {
-            rt_scene_destroy(s);
-            return rc;
-        }
-        s->dev.n_nodes = (uint32_t)s->hs.nodes.size();
-        s->dev.n_tris = (uint32_t)(s->hs.wverts.size() / 9);
-        std::memcpy(s->dev.sky, s->hs.sky, 12);
-        s->dev.packed_mat = s->hs.packed_mat ? 1u : 0u;
-        // what the shading kernels stage in LDS (rt_device.h: ShadeTables): the head of the distinct-matrix table and of the material table
-        const bool stage = s->hs.packed_mat && s->hs.n_layers <= 65536u; // (the staged material keeps its layer in 16 bits)
-        s->dev.lds_nm = stage ? (uint32_t)std::min<size_t>(s->hs.inst.size(), kLdsNm) : 0u;
-        s->dev.lds_mats = stage ? (uint32_t)std::min<size_t>(s->hs.mats.size(), kLdsMats) : 0u;
-        scene_cells(s->hs, s->dev);
+        if ((rc = device_ok(device)) != RT_OK) return rc;
+        if (const char* e = dev_knob("RT_INJECT_ALLOC_FAILURE")) s->alloc.inject = std::atoi(e);
+        rc = no_throw([&]() -> int { // the device image (rt_scene_image.h)
+            const HostScene& hs = s->hs;
+            if (hs.nodes.size() > kMaxDeviceNodes) return fail(RT_ERR_INVALID, "BVH too large for 32-bit node offsets");
+            SceneAlloc& al = s->alloc;
+            uint64_t& bytes = s->device_bytes;
+            if (const int e = s->d_nodes.upload(al, device_nodes(hs.nodes), bytes)) return e;
+            if (const int e = s->d_tris.upload(al, pack_tris(hs.tris), bytes)) return e;
+            if (const int e = s->d_shade.upload(al, hs.shade, bytes)) return e;
+            if (const int e = s->d_skip.upload(al, hs.skip, bytes)) return e;
+            std::vector<InstRec> rows(hs.inst); // (an updatable scene's table has room for a row per instance: the distinct matrices may grow)
+            if (updatable) rows.resize(std::max<size_t>(rows.size(), desc->n_instances));
+            if (const int e = s->d_inst.upload(al, rows, bytes)) return e;
+            if (const int e = s->d_mats.upload(al, hs.mats, bytes)) return e;
+            if (const int e = s->d_tex.upload(al, hs.tex, bytes)) return e;
+            uint64_t uncounted = 0; // (the query cursors, rt_query_launch.h, are no part of device_bytes)
+            if (s->d_query_cursor.upload(al, nullptr, kQueryCursorBytes / 8u, uncounted) != RT_OK)
+                return fail(RT_ERR_OOM, "device allocation failed (the ray-query cursors)");
+            s->dev.nodes = s->d_nodes.get(), s->dev.tris = s->d_tris.get(), s->dev.shade = s->d_shade.get(), s->dev.skip = s->d_skip.get();
+            s->dev.inst = s->d_inst.get(), s->dev.mats = s->d_mats.get(), s->dev.tex = s->d_tex.get();
+            scene_scalars(hs, s->dev);
+            return RT_OK;
+        });
+        if (rc != RT_OK) return rc;
     }
-    if (flags & RT_SCENE_UPDATABLE) {
-        rc = no_throw([&] { return init_scene_update(s, desc, (flags & RT_SCENE_KEEP_PREVIOUS) != 0); });
-        if (rc != RT_OK) {
-            rt_scene_destroy(s);
-            return rc;
-        }
-    }
-    *out = s;
+    if (updatable && (rc = no_throw([&] { return init_scene_update(s.get(), desc, (flags & RT_SCENE_KEEP_PREVIOUS) != 0); })) != RT_OK) return rc;
+    *out = s.release();
     return RT_OK;
 }
 
+// the scene's device current, every reader's last launch done (rt_scene::readers); the members then free what they own
 void rt_scene_destroy(rt_scene* s) {
     if (!s) return;
-    if (s->device >= 0 && hipSetDevice(s->device) == hipSuccess) {
-        for (auto& se : s->ev_gbuffer) (void)hipEventSynchronize(se.second), (void)hipEventDestroy(se.second);
-        (void)hipFree((void*)s->dev.nodes), (void)hipFree((void*)s->dev.tris), (void)hipFree((void*)s->dev.shade);
-        (void)hipFree((void*)s->dev.inst), (void)hipFree((void*)s->dev.mats), (void)hipFree((void*)s->dev.tex);
-        (void)hipFree((void*)s->d_query_cursor), (void)hipFree((void*)s->dev.skip);
-    }
-    free_scene_update(s);
+    if (s->device >= 0 && hipSetDevice(s->device) == hipSuccess)
+        for (auto& se : s->readers) (void)hipEventSynchronize(se.second), (void)hipEventDestroy(se.second);
     delete s;
 }
 

@@ -40,7 +40,7 @@ int gbuffer_enqueue(rt_scene* s, const rt_camera* cam, float4* alb, float4* nrm,
     if (const int rc = scene_stream_event(s, st, &ev)) return rc;
     const CameraDev c = to_dev(*cam);
     const uint32_t n = (uint32_t)cam->width * (uint32_t)cam->height;
-    if (prev) launch_gbuffer_motion(s->dev, c, n, alb, nrm, pos, s->upd->d_wv_prev, prev, st); // (rt_gbuffer_motion.hip)
+    if (prev) launch_gbuffer_motion(s->dev, c, n, alb, nrm, pos, s->upd->d_wv_prev.get(), prev, st); // (rt_gbuffer_motion.hip)
     else hipLaunchKernelGGL(k_gbuffer, dim3((n + 255u) / 256u), dim3(256), 0, st, s->dev, c, alb, nrm, pos);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(ev, st));

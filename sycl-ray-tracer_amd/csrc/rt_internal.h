@@ -4,7 +4,8 @@
 //   rt_frame.hip   tile buffers, schedules, the launches of a frame (the only unit that includes the render kernels, rt_kernels.h)
 //   rt_comm.hip    the multi-GPU frame gather (RCCL) and its de-interleave kernel
 //   rt_probes.hip  rt_intersect_batch and the rt_probe_* entry points with their kernels (rt_probe_kernels.h)
-//   rt_update.hip  dynamic scenes: rt_scene_create_ex's updatable state, rt_scene_update and its refit kernels
+//   rt_update.hip  dynamic scenes: rt_scene_create_ex's updatable state, rt_scene_update and its refit kernels, the host copy's refresh
+//   rt_scene_image.h what those two share: the device form of a built scene's arrays, the scalars of SceneDev (the geometry rules: scene_rules.h)
 //   rt_gbuffer.hip the primary-hit G-buffer (rt_scene_gbuffer[_device], rt_scene_gbuffer_motion[_device]) and k_gbuffer
 //   rt_gbuffer_motion.hip k_gbuffer_motion: the same pixel (rt_gbuffer_pixel.h) plus the motion guide
 //   rt_denoise.hip the a-trous denoiser (rt_denoiser_*, rt_denoise[_device]) and its kernels
@@ -30,6 +31,7 @@
 #include <cstdio>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <new>
 #include <string>
@@ -78,6 +80,15 @@ inline int device_ok(int device) {
     return RT_OK;
 }
 
+// Every allocation of one scene creation (rt_scene_create_ex, the updatable state included). Test hook, DEVELOPER builds only (rt_knobs.h), as
+// for the renderer's tile buffers (rt_frame.hip): RT_INJECT_ALLOC_FAILURE=k fails the k-th as out of memory, without calling the runtime.
+struct SceneAlloc {
+    int inject = 0, n = 0;
+    bool fails() { return inject && ++n == inject; }
+    hipError_t device(void** p, size_t bytes) { return fails() ? hipErrorOutOfMemory : hipMalloc(p, bytes); }
+    hipError_t pinned(void** p, size_t bytes) { return fails() ? hipErrorOutOfMemory : hipHostMalloc(p, bytes); }
+};
+
 // device allocation that frees itself on every return path of the C entry points
 struct DevBuf {
     void* p = nullptr;
@@ -92,17 +103,31 @@ struct DevBuf {
     T* as() const { return static_cast<T*>(p); }
 };
 
+// A typed array its object owns, device memory (DevArray) or pinned host memory (PinnedArray): freed with the object, handed over by a move
+// (the update's pointer swaps; the move members delete the copies).
+template <typename T, hipError_t (*FREE)(void*)>
+struct Owned {
+    T* p = nullptr;
+    Owned() = default;
+    Owned(Owned&& o) noexcept : p(o.p) { o.p = nullptr; }
+    Owned& operator=(Owned&& o) noexcept { return std::swap(p, o.p), *this; }
+    ~Owned() { if (p) (void)FREE(p); }
+    T* get() const { return p; }
+};
+template <typename T> using PinnedArray = Owned<T, hipHostFree>;
+// A scene's array. One of no elements still has one, so that no device pointer is ever null; `bytes` is the scene's account of its device
+// memory (rt_scene_info_t::device_bytes). src may be null: allocated only.
 template <typename T>
-int upload(const std::vector<T>& v, const T** out, uint64_t& bytes) {
-    *out = nullptr;
-    const size_t n = std::max<size_t>(v.size(), 1);
-    void* p = nullptr;
-    HIPCHK(hipMalloc(&p, n * sizeof(T)));
-    *out = (const T*)p; // owned by the scene from here on: rt_scene_destroy frees it even if the copy fails
-    bytes += n * sizeof(T);
-    if (!v.empty()) HIPCHK(hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-    return RT_OK;
-}
+struct DevArray : Owned<T, hipFree> {
+    int upload(SceneAlloc& a, const T* src, size_t count, uint64_t& bytes) {
+        const size_t b = std::max<size_t>(count, 1) * sizeof(T);
+        HIPCHK(a.device((void**)&this->p, b));
+        bytes += b;
+        if (src && count) HIPCHK(hipMemcpy(this->p, src, count * sizeof(T), hipMemcpyHostToDevice));
+        return RT_OK;
+    }
+    int upload(SceneAlloc& a, const std::vector<T>& v, uint64_t& bytes) { return upload(a, v.data(), v.size(), bytes); }
+};
 
 } // namespace rtlib
 
@@ -122,6 +147,7 @@ using namespace rtlib;
 //   box              the exact box of every node, 6 floats (24 bytes) per node
 //   levels           the nodes by height (level_start on the host)
 //   red              the transform's reduction: 6 ordered 64-bit keys (bounds, first occurrence) + a non-finite flag
+// Everything frees itself with the object (rt_scene_destroy has made the scene's device current by then).
 struct SceneUpdate {
     std::vector<rt_instance> instances;
     std::vector<uint64_t> inst_use;
@@ -130,23 +156,15 @@ struct SceneUpdate {
     uint32_t n_vertices = 0;
     std::vector<float> positions, normals; // host-only scenes
     std::vector<uint32_t> indices, tri_instance;
-    float* d_pos = nullptr;
-    float* d_pos_stage = nullptr;
-    uint32_t* d_idx = nullptr;
-    uint32_t* d_tri_inst = nullptr;
-    float* d_xf = nullptr;
-    float* d_xf_stage = nullptr;
-    uint32_t* d_islot = nullptr;
-    float* d_wv = nullptr;
-    float* d_wv_prev = nullptr;
+    DevArray<float> d_pos, d_pos_stage, d_xf, d_xf_stage, d_wv, d_wv_prev, d_box;
+    DevArray<uint32_t> d_idx, d_tri_inst, d_islot, d_levels;
+    DevArray<unsigned long long> d_red;
+    PinnedArray<unsigned long long> h_red;
     bool keep_previous = false;
-    float* d_box = nullptr;
-    uint32_t* d_levels = nullptr;
-    unsigned long long* d_red = nullptr;
-    unsigned long long* h_red = nullptr; // pinned
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool host_stale = false; // the host copy (hs.nodes, tris, wverts, shade, sah_cost) lags a device update
+    ~SceneUpdate() { if (ev0) (void)hipEventDestroy(ev0); if (ev1) (void)hipEventDestroy(ev1); if (stream) (void)hipStreamDestroy(stream); }
 };
 
 // The cursors of the query kinds (rt_query.hip, rt_path_query.hip, rt_path_gather.hip, rt_closest.hip). A launch's entries are cut into kQueryHeads
@@ -165,30 +183,36 @@ struct rt_scene {
     int device = -1;
     SceneDev dev{};
     uint64_t device_bytes = 0;
-    SceneUpdate* upd = nullptr; // RT_SCENE_UPDATABLE only
+    std::unique_ptr<SceneUpdate> upd; // RT_SCENE_UPDATABLE only
     uint64_t generation = 0;    // bumped by every rt_scene_update: renderers drop what belongs to an older one
     uint32_t frames_pending = 0; // frames of its renderers between _begin and _end (an update is refused meanwhile)
-    // one event per stream a G-buffer or a ray query was enqueued on (rt_scene_gbuffer[_device], rt_trace_rays[_device]), recorded behind
-    // every launch there: rt_scene_update waits for all of them, so no launch on any stream still reads the scene when it is rewritten
-    std::vector<std::pair<hipStream_t, hipEvent_t>> ev_gbuffer;
+    // One event per stream that anything but a renderer's frame reads the scene on, recorded behind every such launch there: the G-buffers
+    // (rt_scene_gbuffer[_motion][_device]), the ray, path, gather and closest-point queries (rt_trace_rays, rt_trace_paths, rt_gather_paths,
+    // rt_closest_points, each with its _device form; a probe volume bakes through the gather query) and the lightmap's own launches. rt_scene_update
+    // and rt_scene_destroy wait for all of them, so no launch on any stream still reads the scene when it is rewritten or freed
+    std::vector<std::pair<hipStream_t, hipEvent_t>> readers;
     // ray, path and gather queries (rt_query_launch.h): the cursors their launches share (kQueryCursorBytes of device memory, device scenes only), the
     // stream of the last query launch (a launch on another stream waits for it on the device: they share the cursors), every query kernel's
     // persistent grid (0 = not sized)
-    unsigned long long* d_query_cursor = nullptr;
+    DevArray<unsigned long long> d_query_cursor;
     hipStream_t query_stream = nullptr;
     bool query_launched = false;
     uint32_t query_grid[kQueryKinds] = {};
+    // the owners of what `dev` points to (SceneDev goes to the kernels by value and keeps plain pointers), and the creation's allocator
+    DevArray<BvhNode> d_nodes; DevArray<uint8_t> d_tris, d_tex;
+    DevArray<ShadeRec> d_shade; DevArray<SkipRec> d_skip; DevArray<InstRec> d_inst; DevArray<MatRec> d_mats;
+    SceneAlloc alloc;
 };
 
 namespace rtlib {
-// the scene's event for stream st (rt_scene::ev_gbuffer), created on the stream's first use
+// the scene's event for stream st (rt_scene::readers), created on the stream's first use
 inline int scene_stream_event(rt_scene* s, hipStream_t st, hipEvent_t* out) {
-    for (const auto& se : s->ev_gbuffer)
+    for (const auto& se : s->readers)
         if (se.first == st) return *out = se.second, RT_OK;
     hipEvent_t ev = nullptr;
     HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
     try {
-        s->ev_gbuffer.emplace_back(st, ev);
+        s->readers.emplace_back(st, ev);
     } catch (const std::bad_alloc&) {
         (void)hipEventDestroy(ev);
         return fail(RT_ERR_OOM, "host allocation failed");
@@ -458,7 +482,6 @@ inline bool carry_is_current(const rt_renderer* r) { return r->scene_gen == r->s
 void launch_gbuffer_motion(const SceneDev& S, const CameraDev& c, uint32_t n, float4* alb, float4* nrm, float4* pos, const float* prev_wv, float4* prev,
                            hipStream_t st);
 // rt_update.hip
-void free_scene_update(rt_scene* s);
 int init_scene_update(rt_scene* s, const rt_scene_desc* d, bool keep_previous);
 uint32_t scene_inst_capacity(const rt_scene* s); // rows the device's instance table is allocated with
 // brings the host copy up to date after device updates (rt_scene_info, rt_scene_check_bvh, rt_scene_count_visits, rt_dev_scene_*)

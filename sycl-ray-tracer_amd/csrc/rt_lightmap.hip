@@ -425,7 +425,7 @@ int check_params(const rt_lightmap_params* p) {
 }
 
 // the scene's world-space vertices as they are now: the scene's own on an updatable scene (an update may swap the pointer), else the copy
-const float* world_vertices_of(const rt_lightmap* lm) { return lm->scene->upd ? lm->scene->upd->d_wv : lm->d_wv; }
+const float* world_vertices_of(const rt_lightmap* lm) { return lm->scene->upd ? lm->scene->upd->d_wv.get() : lm->d_wv; }
 
 // The owner plane and the texels' entries on st; the caller records the events. PRE: on the lightmap's device, st waited for ev_last.
 int enqueue_texels(rt_lightmap* lm, uint32_t repeats, uint32_t seed, uint32_t* tri, float* pos, float* nrm, uint32_t* state, hipStream_t st) {

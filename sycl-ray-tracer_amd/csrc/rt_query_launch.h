@@ -27,10 +27,10 @@ int query_launch(rt_scene* s, QueryKind kind, void (*kernel)(SceneDev, Dev), uin
         if (const int rc = scene_stream_event(s, s->query_stream, &prev)) return rc;
         HIPCHK(hipStreamWaitEvent(st, prev, 0));
     }
-    d.cursor = s->d_query_cursor;
+    d.cursor = s->d_query_cursor.get();
     d.range = contract_range(s->hs);
     const uint32_t grid = (uint32_t)std::min<uint64_t>(s->query_grid[kind], (n + block - 1u) / block);
-    HIPCHK(hipMemsetAsync(s->d_query_cursor, 0, kQueryCursorBytes, st));
+    HIPCHK(hipMemsetAsync(s->d_query_cursor.get(), 0, kQueryCursorBytes, st));
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), 0, st, s->dev, d);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(ev, st));

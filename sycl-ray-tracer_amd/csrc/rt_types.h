@@ -1,6 +1,7 @@
 // rt_types.h — data layouts of the device-resident scene and of the kernel parameter block.
 // Shared by the host builder (scene_build.cpp, scene_check.cpp) and the HIP kernels (rt_kernels.h, rt_device.h).
 #pragma once
+#include <cstddef>
 #include <cstdint>
 
 namespace rt {
@@ -71,7 +72,10 @@ RT_HD Box3 child_box(const BvhNode& n, int k) {
 
 // In the DEVICE copy of the node array a child word >= 0 is the child node's BYTE offset (index * 64), so that the inner step
 // addresses the node with no arithmetic of its own — a 32-bit offset on the scalar base for global memory (the index form cost a
-// 64-bit shift and a 64-bit add per step), one right shift for the LDS copy of the tree's top. The host array keeps indices.
+// 64-bit shift and a 64-bit add per step), one right shift for the LDS copy of the tree's top. The host array keeps indices. These two
+// functions are that rule (leaf codes and kChildEmpty, negative, are the same word in both forms; SkipRec::ref holds the device's form).
+RT_HD uint32_t device_child_word(int32_t child) { return child >= 0 ? (uint32_t)child * 64u : (uint32_t)child; }
+RT_HD int32_t host_child_word(uint32_t word) { return (int32_t)word >= 0 ? (int32_t)(word / 64u) : (int32_t)word; }
 constexpr int kMaxLeafTris = 2;    // 1..4 (the leaf code keeps count - 1 in two bits). 4 -> 2: +1.1 % on the atrium — a whole-leaf step runs as many tests as the wave's LARGEST leaf
 constexpr int kTopNodes = 341;    // nodes at the head of the node array laid out top first — by surface area: scene_build.cpp; by level: lbvh_gpu.hip — and staged in LDS by the traversal kernels (rt_device.h)
 constexpr int kStackSize = 64;      // traversal stack entries per ray; builders keep depth < 64
@@ -111,6 +115,10 @@ static_assert(sizeof(TriRec) == 48, "TriRec must be 48 bytes");
 // What the device reads per triangle: the record's ten live dwords, packed (the two padding words were 17 % of the
 // triangle traffic): bytes 0-15 (v0.xyz, e1.x), 16-31 (e1.yz, e2.xy), 32-39 (e2.z, global index) at a 40-byte stride (8-byte aligned).
 constexpr uint32_t kTriBytes = 40;
+// record r of the packed array: its nine floats, and the word behind them
+RT_HD const float* packed_tri(const uint8_t* tris, size_t r) { return reinterpret_cast<const float*>(tris + r * kTriBytes); }
+RT_HD float* packed_tri(uint8_t* tris, size_t r) { return reinterpret_cast<float*>(tris + r * kTriBytes); }
+RT_HD uint32_t packed_global_index(const uint8_t* tris, size_t r) { return reinterpret_cast<const uint32_t*>(tris + r * kTriBytes)[9]; }
 
 // ---- per-triangle shading attributes, GLOBAL order: 64 bytes ------------------------------------
 // What trace_ray gathers through index_buffer/normal_buffer/uv_buffer (src/trace_ray.hpp:34-45),

@@ -2,17 +2,19 @@
 // refresh of the host copy. A unit of its own, so that the render kernels (rt_frame.hip) compile to the same code as without it.
 //
 // An update keeps the BVH's topology (child words, leaf codes, node order) and recomputes everything geometric in place, in two phases:
-//   1. k_upd_transform: every triangle's world-space vertices, with the host builder's expression ((m0*x + m4*y) + m8*z) + m12
-//      (scene_build.cpp: world_vertices, -ffp-contract=off), into the scratch array `wv`; in the same pass the scene's bounds as ordered keys that also
+//   1. k_upd_transform: every triangle's world-space vertices, with the host builder's expression (scene_rules.h: world_coord, compiled
+//      with -ffp-contract=off on either side), into the scratch array `wv`; in the same pass the scene's bounds as ordered keys that also
 //      carry the first occurrence (the host's std::min / std::max keep the first of equal values: the sign of a zero bound depends on it)
 //      and a non-finite flag. The host reads back 7 words and applies rt_scene_create's test. A refusal restores `wv` and stops here:
 //      nothing else of the scene has been written.
 //   2. k_upd_records rewrites v0 / e1 / e2 of every leaf record, k_upd_refit the nodes, one launch per height level (a node's children lie in
 //      lower levels, so the kernel boundary is the only hand-off between workgroups: no atomics, no fences), k_upd_words / k_upd_normals the
 //      shading records where the instance table's rows moved / where normals were given.
-// Every write lands in a buffer that exists since rt_scene_create: no device pointer of SceneDev changes.
-#include "bvh_quantise.h"
+// Every write lands in a buffer that exists since rt_scene_create: no device pointer of SceneDev changes. The kernels call the rules the host
+// builder and the host refit use (scene_rules.h); the device form of the arrays they rewrite is rt_scene_image.h's.
 #include "rt_internal.h"
+#include "rt_scene_image.h"
+#include "scene_rules.h"
 
 #include <algorithm>
 #include <limits>
@@ -61,7 +63,7 @@ __global__ void __launch_bounds__(256) k_upd_transform(uint32_t n_tris, const fl
             const uint32_t vi = idx[3 * (size_t)t + k];
             const float x = pos[3 * (size_t)vi], y = pos[3 * (size_t)vi + 1], z = pos[3 * (size_t)vi + 2];
             for (int a = 0; a < 3; ++a) {
-                const float p = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(m[a], x), __fmul_rn(m[4 + a], y)), __fmul_rn(m[8 + a], z)), m[12 + a]);
+                const float p = world_coord(m, a, x, y, z);
                 if (WRITE) wv[9 * (size_t)t + 3 * k + a] = p;
                 bad |= isfinite(p) ? 0u : 1u;
                 const uint32_t v = 3u * t + (uint32_t)k;
@@ -95,58 +97,30 @@ __global__ void __launch_bounds__(256) k_upd_transform(uint32_t n_tris, const fl
     }
 }
 
-// Phase 2a: the leaf records' v0, e1 = v1 - v0, e2 = v2 - v0 (kTriBytes layout: v0.xyz e1.xyz e2.xyz global_index), in place.
+// Phase 2a: the leaf records' v0 / e1 / e2 (scene_rules.h: tri_record), in place in the packed array.
 __global__ void __launch_bounds__(256) k_upd_records(uint32_t n_recs, uint8_t* __restrict__ tris, const float* __restrict__ wv) {
     const uint32_t r = blockIdx.x * 256u + threadIdx.x;
     if (r >= n_recs) return;
-    float* rec = reinterpret_cast<float*>(tris + (size_t)r * kTriBytes);
-    const uint32_t g = reinterpret_cast<const uint32_t*>(rec)[9];
+    const uint32_t g = packed_global_index(tris, r);
     if (g == kNoTri) return; // the empty scene's dummy record
-    const float* w = wv + 9 * (size_t)g;
-    for (int a = 0; a < 3; ++a) {
-        rec[a] = w[a];
-        rec[3 + a] = __fsub_rn(w[3 + a], w[a]);
-        rec[6 + a] = __fsub_rn(w[6 + a], w[a]);
-    }
+    float* rec = packed_tri(tris, r);
+    tri_record(wv + 9 * (size_t)g, rec, rec + 3, rec + 6);
 }
 
-// Phase 2b: one height level of the refit. A node's exact child boxes: the union of a leaf's triangles' boxes (every record bounds its
-// whole triangle), or the exact box an inner child stored one launch earlier. Words 0..11 are re-quantised with the new pad; the child
-// words stay.
+// Phase 2b: one height level of the refit (scene_rules.h: refit_node). An inner child's exact box was stored one launch earlier.
 __global__ void __launch_bounds__(128) k_upd_refit(uint32_t n, const uint32_t* __restrict__ level, BvhNode* __restrict__ nodes,
                                                     const uint8_t* __restrict__ tris, const float* __restrict__ wv, Box3* __restrict__ box,
                                                     float pad, unsigned long long* __restrict__ failed) {
     const uint32_t i = blockIdx.x * 128u + threadIdx.x;
     if (i >= n) return;
     const uint32_t ni = level[i];
-    BvhNode nd = nodes[ni];
-    Box3 kb[4];
-    int nk = 0;
-    for (int k = 0; k < 4 && nd.child[k] != kChildEmpty; ++k, ++nk) {
-        const int32_t c = nd.child[k];
-        if (c >= 0) {
-            kb[k] = box[(uint32_t)c / 64u]; // (the device's child words are byte offsets)
-        } else {
-            const LeafRange leaf = leaf_range(c);
-            for (int a = 0; a < 3; ++a) kb[k].lo[a] = INFINITY, kb[k].hi[a] = -INFINITY;
-            for (uint32_t r = leaf.first; r < leaf.first + leaf.count; ++r) {
-                const uint32_t g = *reinterpret_cast<const uint32_t*>(tris + (size_t)r * kTriBytes + 36);
-                const float* w = wv + 9 * (size_t)g;
-                for (int a = 0; a < 3; ++a) {
-                    kb[k].lo[a] = fminf(kb[k].lo[a], fminf(w[a], fminf(w[3 + a], w[6 + a])));
-                    kb[k].hi[a] = fmaxf(kb[k].hi[a], fmaxf(w[a], fmaxf(w[3 + a], w[6 + a])));
-                }
-            }
-        }
-    }
-    if (nk == 0) return;
-    Box3 u = kb[0];
-    for (int k = 1; k < nk; ++k)
-        for (int a = 0; a < 3; ++a) u.lo[a] = fminf(u.lo[a], kb[k].lo[a]), u.hi[a] = fmaxf(u.hi[a], kb[k].hi[a]);
-    box[ni] = u;
+    const BvhNode nd = nodes[ni];
     BvhNode q;
-    if (!quantise_node(q, nk, kb, pad)) atomicOr(failed, 1ull);
-    for (int k = 0; k < 4; ++k) q.child[k] = nd.child[k];
+    const RefitResult res = refit_node(
+        nd, [=](int32_t child) { return box[host_child_word((uint32_t)child)]; },
+        [=](uint32_t r) { return wv + 9 * (size_t)packed_global_index(tris, r); }, pad, box[ni], q);
+    if (res == kRefitEmpty) return;
+    if (res == kRefitRefused) atomicOr(failed, 1ull);
     nodes[ni] = q;
 }
 
@@ -164,31 +138,20 @@ __global__ void __launch_bounds__(256) k_upd_normals(uint32_t n_tris, const uint
                                                       ShadeRec* __restrict__ shade) {
     const uint32_t t = blockIdx.x * 256u + threadIdx.x;
     if (t >= n_tris) return;
-    ShadeRec& s = shade[t];
-    float* dst[3] = {s.n0, s.n1, s.n2};
-    for (int k = 0; k < 3; ++k) {
-        const uint32_t vi = idx[3 * (size_t)t + k];
-        for (int a = 0; a < 3; ++a) dst[k][a] = nrm[3 * (size_t)vi + a];
-    }
+    shade_normals(shade[t], idx + 3 * (size_t)t, nrm);
 }
 
-template <typename T>
-hipError_t dev_alloc(T** p, size_t count, uint64_t& bytes) {
-    const size_t b = std::max<size_t>(count, 1) * sizeof(T);
-    const hipError_t e = hipMalloc((void**)p, b);
-    if (e == hipSuccess) bytes += b;
-    return e;
+// the 16 floats of every instance's transform, as k_upd_transform reads them
+std::vector<float> transforms_of(const rt_instance* inst, size_t n) {
+    std::vector<float> xf(16 * n);
+    for (size_t i = 0; i < n; ++i) std::memcpy(&xf[16 * i], inst[i].transform, 64);
+    return xf;
 }
 
-uint32_t shading_word(const rt_scene* s, uint32_t inst) {
-    const SceneUpdate& u = *s->upd;
-    return s->hs.packed_mat ? (u.inst_slot[inst] | (u.instances[inst].material << kPackedInstBits)) : inst;
-}
-
-// the new instance table; returns whether any instance's row moved
-bool regroup(rt_scene* s, const std::vector<rt_instance>& inst, std::vector<InstRec>& rows, std::vector<uint32_t>& slot) {
-    shading_rows(inst.data(), (uint32_t)inst.size(), s->upd->inst_use, s->hs.packed_mat, rows, slot);
-    return slot != s->upd->inst_slot;
+// The end of an accepted update, host or device: the instances and their rows as they are now, the statistics; a device scene's host copy lags.
+void commit_update(rt_scene* s, const std::vector<rt_instance>& inst, const std::vector<uint32_t>& slot, const rt_update_stats& done, rt_update_stats* stats) {
+    s->upd->inst_slot = slot, s->upd->instances = inst, s->upd->host_stale = s->device >= 0;
+    if (stats) *stats = done;
 }
 
 // ---- host-only scenes: the same update in host arithmetic (the CPU reference of the device path) ---------------------------------------
@@ -196,13 +159,14 @@ int update_host(rt_scene* s, const std::vector<rt_instance>& inst, const rt_scen
     SceneUpdate& up = *s->upd;
     HostScene& hs = s->hs;
     const uint32_t T = (uint32_t)up.tri_instance.size();
-    const float* pos = (u->n_vertices && u->positions) ? u->positions : up.positions.data();
+    const bool new_pos = u->n_vertices && u->positions, new_nrm = u->n_vertices && u->normals;
+    // phase 1: the world-space vertices, their bounds and the pad, or a refusal
     std::vector<float> wv;
-    world_vertices(T, up.indices.data(), up.tri_instance.data(), inst.data(), pos, wv);
+    world_vertices(T, up.indices.data(), up.tri_instance.data(), inst.data(), new_pos ? u->positions : up.positions.data(), wv);
     float lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0}, pad = hs.pad;
     std::string err;
     if (T && !world_bounds(wv, lo, hi, pad, err)) return fail(RT_ERR_INVALID, err);
-    // accepted: from here on the scene changes
+    // phase 2: the update is accepted
     HostScene next = hs; // (a quantisation failure below leaves the scene as it was)
     if (T) {
         next.wverts.swap(wv);
@@ -211,145 +175,128 @@ int update_host(rt_scene* s, const std::vector<rt_instance>& inst, const rt_scen
         std::vector<float> box;
         if (!refit_host(next, up.level_nodes, box, err)) return fail(RT_ERR_INVALID, err);
     }
-    std::vector<InstRec> rows;
     std::vector<uint32_t> slot;
-    regroup(s, inst, rows, slot);
-    next.inst = rows;
-    if (u->n_vertices && u->normals)
-        for (uint32_t t = 0; t < T; ++t) {
-            ShadeRec& sr = next.shade[t];
-            float* dst[3] = {sr.n0, sr.n1, sr.n2};
-            for (int k = 0; k < 3; ++k) std::memcpy(dst[k], u->normals + 3 * (size_t)up.indices[3 * (size_t)t + k], 12);
-        }
+    shading_rows(inst.data(), (uint32_t)inst.size(), up.inst_use, hs.packed_mat, next.inst, slot);
+    for (uint32_t t = 0; t < T; ++t) {
+        const uint32_t i = up.tri_instance[t];
+        next.shade[t].instance = shading_word(hs.packed_mat, slot[i], inst[i].material, i);
+        if (new_nrm) shade_normals(next.shade[t], &up.indices[3 * (size_t)t], u->normals);
+    }
     hs = std::move(next);
-    up.inst_slot = slot;
-    up.instances = inst;
-    for (uint32_t t = 0; t < T; ++t) hs.shade[t].instance = shading_word(s, up.tri_instance[t]);
-    if (u->n_vertices && u->positions) up.positions.assign(u->positions, u->positions + 3 * (size_t)up.n_vertices);
-    if (u->n_vertices && u->normals) up.normals.assign(u->normals, u->normals + 3 * (size_t)up.n_vertices);
-    if (stats) stats->device_ms = 0.0, stats->launches = 0, stats->refit_nodes = T ? (uint32_t)up.level_nodes.size() : 0u;
+    if (new_pos) up.positions.assign(u->positions, u->positions + 3 * (size_t)up.n_vertices);
+    if (new_nrm) up.normals.assign(u->normals, u->normals + 3 * (size_t)up.n_vertices);
+    commit_update(s, inst, slot, rt_update_stats{0.0, 0u, T ? (uint32_t)up.level_nodes.size() : 0u}, stats);
     return RT_OK;
 }
 
 // ---- device scenes -----------------------------------------------------------------------------------------------------------------------
+template <bool WRITE>
+void launch_transform(const SceneUpdate& up, uint32_t T, const float* pos, const float* xf) {
+    hipLaunchKernelGGL(k_upd_transform<WRITE>, dim3((T + 255u) / 256u), dim3(256), 0, up.stream, T, pos, (const uint32_t*)up.d_idx.get(),
+                       (const uint32_t*)up.d_tri_inst.get(), xf, up.d_wv.get(), up.d_red.get());
+}
+
 int update_device(rt_scene* s, const std::vector<rt_instance>& inst, const rt_scene_update_desc* u, rt_update_stats* stats) {
     SceneUpdate& up = *s->upd;
     HostScene& hs = s->hs;
     HIPCHK(hipSetDevice(s->device));
     const uint32_t T = (uint32_t)(hs.wverts.size() / 9), I = (uint32_t)inst.size();
     const uint32_t n_recs = s->dev.n_tris ? (uint32_t)hs.tris.size() : 0u; // (hs.tris.size() never changes: the leaf records are kept)
-    hipStream_t st = up.stream;
-    uint32_t launches = 0;
-    HIPCHK(hipEventRecord(up.ev0, st));
-    const bool new_xf = u->n_instances != 0, new_pos = u->n_vertices && u->positions;
-    std::vector<float> xf;
-    if (new_xf) {
-        xf.resize(16 * (size_t)I);
-        for (uint32_t i = 0; i < I; ++i) std::memcpy(&xf[16 * (size_t)i], inst[i].transform, 64);
-        HIPCHK(hipMemcpyAsync(up.d_xf_stage, xf.data(), xf.size() * 4, hipMemcpyHostToDevice, st));
-    }
-    if (new_pos) HIPCHK(hipMemcpyAsync(up.d_pos_stage, u->positions, 12 * (size_t)up.n_vertices, hipMemcpyHostToDevice, st));
-    const float* xf_new = new_xf ? up.d_xf_stage : up.d_xf;
-    const float* pos_new = new_pos ? up.d_pos_stage : up.d_pos;
-    float lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0}, pad = hs.pad;
     const uint32_t g256 = (T + 255u) / 256u;
+    hipStream_t st = up.stream;
+    unsigned long long* h_red = up.h_red.get();
+    rt_update_stats done{};
+    HIPCHK(hipEventRecord(up.ev0, st));
+    // what the update brings goes into the staging buffers
+    const bool new_xf = u->n_instances != 0, new_pos = u->n_vertices && u->positions, new_nrm = u->n_vertices && u->normals;
+    const std::vector<float> xf = new_xf ? transforms_of(inst.data(), I) : std::vector<float>();
+    if (new_xf) HIPCHK(hipMemcpyAsync(up.d_xf_stage.get(), xf.data(), xf.size() * 4, hipMemcpyHostToDevice, st));
+    if (new_pos) HIPCHK(hipMemcpyAsync(up.d_pos_stage.get(), u->positions, 12 * (size_t)up.n_vertices, hipMemcpyHostToDevice, st));
+    const float* xf_new = new_xf ? up.d_xf_stage.get() : up.d_xf.get();
+    const float* pos_new = new_pos ? up.d_pos_stage.get() : up.d_pos.get();
+    float lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0}, pad = hs.pad;
     if (T) {
-        // phase 1
-        for (int a = 0; a < 3; ++a) up.h_red[a] = ~0ull, up.h_red[3 + a] = 0ull;
-        up.h_red[6] = up.h_red[7] = 0ull;
-        HIPCHK(hipMemcpyAsync(up.d_red, up.h_red, kRedWords * 8, hipMemcpyHostToDevice, st));
-        if (up.keep_previous) // test first, write after (below): the current vertices are still needed as the previous ones
-            hipLaunchKernelGGL(k_upd_transform<false>, dim3(g256), dim3(256), 0, st, T, pos_new, (const uint32_t*)up.d_idx, (const uint32_t*)up.d_tri_inst, xf_new, up.d_wv, up.d_red);
-        else
-            hipLaunchKernelGGL(k_upd_transform<true>, dim3(g256), dim3(256), 0, st, T, pos_new, (const uint32_t*)up.d_idx, (const uint32_t*)up.d_tri_inst, xf_new, up.d_wv, up.d_red);
-        ++launches;
+        // phase 1: the world-space vertices, their bounds and the pad, or a refusal
+        for (int a = 0; a < 3; ++a) h_red[a] = ~0ull, h_red[3 + a] = 0ull;
+        h_red[6] = h_red[7] = 0ull;
+        HIPCHK(hipMemcpyAsync(up.d_red.get(), h_red, kRedWords * 8, hipMemcpyHostToDevice, st));
+        if (up.keep_previous) launch_transform<false>(up, T, pos_new, xf_new); // test first, write after (below): the current vertices are still needed as the previous ones
+        else launch_transform<true>(up, T, pos_new, xf_new);
+        ++done.launches;
         HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(up.h_red, up.d_red, kRedWords * 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(h_red, up.d_red.get(), kRedWords * 8, hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
-        for (int a = 0; a < 3; ++a) lo[a] = key_value(up.h_red[a]), hi[a] = key_value(up.h_red[3 + a]);
+        for (int a = 0; a < 3; ++a) lo[a] = key_value(h_red[a]), hi[a] = key_value(h_red[3 + a]);
         std::string err;
-        const bool ok = up.h_red[6] == 0 ? scene_padding(lo, hi, pad, err) : (err = "non-finite world-space vertex", false);
+        const bool ok = h_red[6] == 0 ? scene_padding(lo, hi, pad, err) : (err = "non-finite world-space vertex", false);
         if (!ok && up.keep_previous) return fail(RT_ERR_INVALID, err); // refused: nothing was written
         if (!ok) { // refused: the scratch vertices go back to the scene's own, nothing else was written
-            hipLaunchKernelGGL(k_upd_transform<true>, dim3(g256), dim3(256), 0, st, T, (const float*)up.d_pos, (const uint32_t*)up.d_idx,
-                               (const uint32_t*)up.d_tri_inst, (const float*)up.d_xf, up.d_wv, up.d_red);
+            launch_transform<true>(up, T, up.d_pos.get(), up.d_xf.get());
             HIPCHK(hipGetLastError());
             HIPCHK(hipStreamSynchronize(st));
             return fail(RT_ERR_INVALID, err);
         }
         if (up.keep_previous) { // accepted: the current vertices become the previous ones (a pointer swap), the new ones are written over the older copy
             std::swap(up.d_wv, up.d_wv_prev);
-            hipLaunchKernelGGL(k_upd_transform<true>, dim3(g256), dim3(256), 0, st, T, pos_new, (const uint32_t*)up.d_idx, (const uint32_t*)up.d_tri_inst, xf_new, up.d_wv,
-                               up.d_red); // (its reduction repeats the one read above: words 0 .. 6, nobody reads them again)
-            ++launches;
+            launch_transform<true>(up, T, pos_new, xf_new); // (its reduction repeats the one read above: words 0 .. 6, nobody reads them again)
+            ++done.launches;
             HIPCHK(hipGetLastError());
         }
     }
     // phase 2: the update is accepted
     if (new_xf) std::swap(up.d_xf, up.d_xf_stage);
     if (new_pos) std::swap(up.d_pos, up.d_pos_stage);
-    uint32_t refit_nodes = 0;
-    if (T) {
-        hipLaunchKernelGGL(k_upd_records, dim3((n_recs + 255u) / 256u), dim3(256), 0, st, n_recs, (uint8_t*)s->dev.tris, (const float*)up.d_wv);
-        ++launches;
-        up.h_red[7] = 0ull;
-        HIPCHK(hipMemcpyAsync(up.d_red + 7, up.h_red + 7, 8, hipMemcpyHostToDevice, st));
+    if (T) { // the leaf records, then the nodes level by level
+        hipLaunchKernelGGL(k_upd_records, dim3((n_recs + 255u) / 256u), dim3(256), 0, st, n_recs, s->d_tris.get(), (const float*)up.d_wv.get());
+        ++done.launches;
+        h_red[7] = 0ull;
+        HIPCHK(hipMemcpyAsync(up.d_red.get() + 7, h_red + 7, 8, hipMemcpyHostToDevice, st));
         for (size_t h = 0; h + 1 < up.level_start.size(); ++h) {
             const uint32_t n = up.level_start[h + 1] - up.level_start[h];
             if (!n) continue;
-            hipLaunchKernelGGL(k_upd_refit, dim3((n + 127u) / 128u), dim3(128), 0, st, n, (const uint32_t*)(up.d_levels + up.level_start[h]),
-                               (BvhNode*)s->dev.nodes, (const uint8_t*)s->dev.tris, (const float*)up.d_wv, (Box3*)up.d_box, pad, up.d_red + 7);
-            ++launches;
-            refit_nodes += n;
+            hipLaunchKernelGGL(k_upd_refit, dim3((n + 127u) / 128u), dim3(128), 0, st, n, (const uint32_t*)(up.d_levels.get() + up.level_start[h]),
+                               s->d_nodes.get(), (const uint8_t*)s->d_tris.get(), (const float*)up.d_wv.get(), (Box3*)up.d_box.get(), pad, up.d_red.get() + 7);
+            ++done.launches;
+            done.refit_nodes += n;
         }
         HIPCHK(hipGetLastError());
     }
+    // the instance table, and the shading records where its rows moved / where normals came
     std::vector<InstRec> rows;
-    std::vector<uint32_t> slot;
-    const bool moved = regroup(s, inst, rows, slot);
+    std::vector<uint32_t> slot, words;
+    shading_rows(inst.data(), I, up.inst_use, hs.packed_mat, rows, slot);
+    const bool moved = slot != up.inst_slot;
     if (new_xf) {
         if (rows.size() > scene_inst_capacity(s)) return fail(RT_ERR_INVALID, "internal: instance table capacity exceeded");
-        HIPCHK(hipMemcpyAsync((void*)s->dev.inst, rows.data(), rows.size() * sizeof(InstRec), hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(s->d_inst.get(), rows.data(), rows.size() * sizeof(InstRec), hipMemcpyHostToDevice, st));
     }
-    up.inst_slot = slot;
-    up.instances = inst;
     if (moved && T) {
-        std::vector<uint32_t> words(I);
-        for (uint32_t i = 0; i < I; ++i) words[i] = shading_word(s, i);
-        HIPCHK(hipMemcpyAsync(up.d_islot, words.data(), (size_t)I * 4, hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(k_upd_words, dim3(g256), dim3(256), 0, st, T, (const uint32_t*)up.d_tri_inst, (const uint32_t*)up.d_islot,
-                           (ShadeRec*)s->dev.shade);
-        ++launches;
+        words.resize(I);
+        for (uint32_t i = 0; i < I; ++i) words[i] = shading_word(hs.packed_mat, slot[i], inst[i].material, i);
+        HIPCHK(hipMemcpyAsync(up.d_islot.get(), words.data(), (size_t)I * 4, hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(k_upd_words, dim3(g256), dim3(256), 0, st, T, (const uint32_t*)up.d_tri_inst.get(), (const uint32_t*)up.d_islot.get(), s->d_shade.get());
+        ++done.launches;
     }
-    if (u->n_vertices && u->normals && T) {
-        HIPCHK(hipMemcpyAsync(up.d_pos_stage, u->normals, 12 * (size_t)up.n_vertices, hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(k_upd_normals, dim3(g256), dim3(256), 0, st, T, (const uint32_t*)up.d_idx, (const float*)up.d_pos_stage,
-                           (ShadeRec*)s->dev.shade);
-        ++launches;
+    if (new_nrm && T) {
+        HIPCHK(hipMemcpyAsync(up.d_pos_stage.get(), u->normals, 12 * (size_t)up.n_vertices, hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(k_upd_normals, dim3(g256), dim3(256), 0, st, T, (const uint32_t*)up.d_idx.get(), (const float*)up.d_pos_stage.get(), s->d_shade.get());
+        ++done.launches;
     }
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(up.ev1, st));
     HIPCHK(hipStreamSynchronize(st));
-    if (T) {
-        HIPCHK(hipMemcpy(up.h_red + 7, up.d_red + 7, 8, hipMemcpyDeviceToHost));
-        if (up.h_red[7]) { // cannot happen within the padded bounds rt_scene_create accepts; reported all the same
-            up.host_stale = true;
-            ++s->generation;
-            return fail(RT_ERR_INVALID, "internal: a refit node's child boxes could not be quantised");
-        }
-    }
+    if (T) HIPCHK(hipMemcpy(h_red + 7, up.d_red.get() + 7, 8, hipMemcpyDeviceToHost));
     float ms = 0.0f;
     HIPCHK(hipEventElapsedTime(&ms, up.ev0, up.ev1));
-    hs.inst = rows;
-    const bool stage = hs.packed_mat && hs.n_layers <= 65536u; // as rt_scene_create decides it
-    s->dev.lds_nm = stage ? (uint32_t)std::min<size_t>(hs.inst.size(), kLdsNm) : 0u;
-    if (T) {
-        std::memcpy(hs.bounds_lo, lo, 12), std::memcpy(hs.bounds_hi, hi, 12);
-        hs.pad = pad;
-        scene_cells(hs, s->dev);
+    done.device_ms = (double)ms;
+    commit_update(s, inst, slot, done, stats);
+    if (T && h_red[7]) { // cannot happen within the padded bounds rt_scene_create accepts; reported all the same
+        ++s->generation;
+        return fail(RT_ERR_INVALID, "internal: a refit node's child boxes could not be quantised");
     }
-    up.host_stale = true;
-    if (stats) stats->device_ms = (double)ms, stats->launches = launches, stats->refit_nodes = refit_nodes;
+    hs.inst = rows;
+    if (T) std::memcpy(hs.bounds_lo, lo, 12), std::memcpy(hs.bounds_hi, hi, 12), hs.pad = pad;
+    scene_scalars(hs, s->dev);
     return RT_OK;
 }
 
@@ -359,24 +306,8 @@ uint32_t scene_inst_capacity(const rt_scene* s) {
     return (uint32_t)std::max<size_t>(std::max<size_t>(s->hs.inst.size(), s->upd ? s->upd->instances.size() : 0), 1);
 }
 
-void free_scene_update(rt_scene* s) {
-    SceneUpdate* u = s->upd;
-    if (!u) return;
-    if (s->device >= 0 && hipSetDevice(s->device) == hipSuccess) {
-        for (void* p : {(void*)u->d_pos, (void*)u->d_pos_stage, (void*)u->d_idx, (void*)u->d_tri_inst, (void*)u->d_xf, (void*)u->d_xf_stage,
-                        (void*)u->d_islot, (void*)u->d_wv, (void*)u->d_wv_prev, (void*)u->d_box, (void*)u->d_levels, (void*)u->d_red})
-            if (p) (void)hipFree(p);
-        if (u->h_red) (void)hipHostFree(u->h_red);
-        if (u->ev0) (void)hipEventDestroy(u->ev0);
-        if (u->ev1) (void)hipEventDestroy(u->ev1);
-        if (u->stream) (void)hipStreamDestroy(u->stream);
-    }
-    delete u;
-    s->upd = nullptr;
-}
-
 int init_scene_update(rt_scene* s, const rt_scene_desc* d, bool keep_previous) {
-    s->upd = new SceneUpdate();
+    s->upd.reset(new SceneUpdate());
     SceneUpdate& u = *s->upd;
     u.keep_previous = keep_previous;
     const uint32_t T = d->n_triangles, I = d->n_instances, V = d->n_vertices;
@@ -399,39 +330,29 @@ int init_scene_update(rt_scene* s, const rt_scene_desc* d, bool keep_previous) {
         return RT_OK;
     }
     HIPCHK(hipSetDevice(s->device));
+    SceneAlloc& al = s->alloc;
     uint64_t& b = s->device_bytes;
     const size_t n_nodes = s->hs.nodes.size();
-    HIPCHK(dev_alloc(&u.d_pos, 3 * (size_t)V, b));
-    HIPCHK(dev_alloc(&u.d_pos_stage, 3 * (size_t)V, b));
-    HIPCHK(dev_alloc(&u.d_idx, 3 * (size_t)T, b));
-    HIPCHK(dev_alloc(&u.d_tri_inst, T, b));
-    HIPCHK(dev_alloc(&u.d_xf, 16 * (size_t)I, b));
-    HIPCHK(dev_alloc(&u.d_xf_stage, 16 * (size_t)I, b));
-    HIPCHK(dev_alloc(&u.d_islot, I, b));
-    HIPCHK(dev_alloc(&u.d_wv, 9 * (size_t)T, b));
-    if (keep_previous && T) HIPCHK(dev_alloc(&u.d_wv_prev, 9 * (size_t)T, b)); // + 36 bytes per triangle
-    HIPCHK(dev_alloc(&u.d_box, 6 * n_nodes, b));
-    HIPCHK(dev_alloc(&u.d_levels, u.level_nodes.size(), b));
-    HIPCHK(dev_alloc(&u.d_red, kRedWords, b));
-    HIPCHK(hipHostMalloc((void**)&u.h_red, kRedWords * 8));
+    const float* wv = T ? s->hs.wverts.data() : nullptr; // (before the first update previous == current)
+    const std::vector<float> xf = transforms_of(d->instances, I);
+    int rc = u.d_pos.upload(al, T ? d->positions : nullptr, 3 * (size_t)V, b);
+    if (!rc) rc = u.d_pos_stage.upload(al, nullptr, 3 * (size_t)V, b);
+    if (!rc) rc = u.d_idx.upload(al, d->indices, 3 * (size_t)T, b);
+    if (!rc) rc = u.d_tri_inst.upload(al, d->tri_instance, T, b);
+    if (!rc) rc = u.d_xf.upload(al, xf, b);
+    if (!rc) rc = u.d_xf_stage.upload(al, nullptr, xf.size(), b);
+    if (!rc) rc = u.d_islot.upload(al, nullptr, I, b);
+    if (!rc) rc = u.d_wv.upload(al, wv, 9 * (size_t)T, b);
+    if (!rc && keep_previous && T) rc = u.d_wv_prev.upload(al, wv, 9 * (size_t)T, b); // + 36 bytes per triangle
+    if (!rc) rc = u.d_box.upload(al, nullptr, 6 * n_nodes, b);
+    if (!rc) rc = u.d_levels.upload(al, u.level_nodes, b);
+    if (!rc) rc = u.d_red.upload(al, nullptr, kRedWords, b);
+    if (rc) return rc;
+    HIPCHK(al.pinned((void**)&u.h_red.p, kRedWords * 8));
     HIPCHK(hipStreamCreateWithFlags(&u.stream, hipStreamNonBlocking));
     HIPCHK(hipEventCreate(&u.ev0));
     HIPCHK(hipEventCreate(&u.ev1));
-    if (T) {
-        HIPCHK(hipMemcpy(u.d_pos, d->positions, 12 * (size_t)V, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(u.d_idx, d->indices, 12 * (size_t)T, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(u.d_tri_inst, d->tri_instance, 4 * (size_t)T, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(u.d_wv, s->hs.wverts.data(), 4 * s->hs.wverts.size(), hipMemcpyHostToDevice));
-        if (keep_previous) HIPCHK(hipMemcpy(u.d_wv_prev, s->hs.wverts.data(), 4 * s->hs.wverts.size(), hipMemcpyHostToDevice)); // before the first update previous == current
-    }
-    if (I) {
-        std::vector<float> xf(16 * (size_t)I);
-        for (uint32_t i = 0; i < I; ++i) std::memcpy(&xf[16 * (size_t)i], d->instances[i].transform, 64);
-        HIPCHK(hipMemcpy(u.d_xf, xf.data(), xf.size() * 4, hipMemcpyHostToDevice));
-    }
-    if (!u.level_nodes.empty())
-        HIPCHK(hipMemcpy(u.d_levels, u.level_nodes.data(), 4 * u.level_nodes.size(), hipMemcpyHostToDevice));
-    HIPCHK(hipMemset(u.d_box, 0, 24 * std::max<size_t>(n_nodes, 1)));
+    HIPCHK(hipMemset(u.d_box.get(), 0, 24 * std::max<size_t>(n_nodes, 1)));
     return RT_OK;
 }
 
@@ -443,18 +364,16 @@ int sync_host_copy(const rt_scene* cs) {
         HostScene& hs = s->hs;
         HIPCHK(hipSetDevice(s->device));
         std::vector<BvhNode> nodes(hs.nodes.size());
-        std::vector<uint8_t> packed(hs.tris.size() * (size_t)kTriBytes);
+        std::vector<uint8_t> packed(packed_tri_bytes(hs.tris.size()));
         std::vector<float> wv(hs.wverts.size()), box(6 * hs.nodes.size());
         std::vector<ShadeRec> shade(hs.shade.size());
-        HIPCHK(hipMemcpy(nodes.data(), s->dev.nodes, nodes.size() * sizeof(BvhNode), hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(packed.data(), s->dev.tris, packed.size(), hipMemcpyDeviceToHost));
-        if (!wv.empty()) HIPCHK(hipMemcpy(wv.data(), up.d_wv, wv.size() * 4, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(box.data(), up.d_box, box.size() * 4, hipMemcpyDeviceToHost));
-        if (!shade.empty()) HIPCHK(hipMemcpy(shade.data(), s->dev.shade, shade.size() * sizeof(ShadeRec), hipMemcpyDeviceToHost));
-        for (BvhNode& n : nodes)
-            for (int k = 0; k < 4; ++k)
-                if (n.child[k] >= 0) n.child[k] /= 64;
-        for (size_t r = 0; r < hs.tris.size(); ++r) std::memcpy(&hs.tris[r], packed.data() + r * kTriBytes, kTriBytes);
+        HIPCHK(hipMemcpy(nodes.data(), s->d_nodes.get(), nodes.size() * sizeof(BvhNode), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(packed.data(), s->d_tris.get(), packed.size(), hipMemcpyDeviceToHost));
+        if (!wv.empty()) HIPCHK(hipMemcpy(wv.data(), up.d_wv.get(), wv.size() * 4, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(box.data(), up.d_box.get(), box.size() * 4, hipMemcpyDeviceToHost));
+        if (!shade.empty()) HIPCHK(hipMemcpy(shade.data(), s->d_shade.get(), shade.size() * sizeof(ShadeRec), hipMemcpyDeviceToHost));
+        host_nodes(nodes);
+        unpack_tris(packed, hs.tris);
         hs.nodes.swap(nodes);
         hs.wverts.swap(wv);
         hs.shade.swap(shade);
@@ -478,9 +397,9 @@ extern "C" int rt_scene_update(rt_scene* s, const rt_scene_update_desc* u, rt_up
     if (u->n_vertices && !u->positions && !u->normals) return fail(RT_ERR_INVALID, "n_vertices given with neither positions nor normals");
     for (uint32_t i = 0; i < u->n_instances; ++i)
         if (u->instances[i].material != up.instances[i].material) return fail(RT_ERR_INVALID, "an update cannot change an instance's material");
-    if (!s->ev_gbuffer.empty()) { // G-buffer and ray-query launches still reading the scene (rt_scene_gbuffer_device, rt_trace_rays_device, any stream) finish before anything is rewritten
+    if (!s->readers.empty()) { // the G-buffer, query and lightmap launches still reading the scene, on any stream (rt_scene::readers), finish before anything is rewritten
         HIPCHK(hipSetDevice(s->device));
-        for (const auto& se : s->ev_gbuffer) HIPCHK(hipEventSynchronize(se.second));
+        for (const auto& se : s->readers) HIPCHK(hipEventSynchronize(se.second));
     }
     return no_throw([&]() -> int {
         std::vector<rt_instance> inst = up.instances;

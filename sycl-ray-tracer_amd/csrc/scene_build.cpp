@@ -10,6 +10,7 @@
 // The diagnostics of a built scene (costs, check_bvh, count_visits) are in scene_check.cpp.
 #include "scene_build.h"
 #include "bvh_quantise.h"
+#include "scene_rules.h"
 #include "rt_knobs.h"
 
 #include <algorithm>
@@ -804,28 +805,22 @@ void fill_tables(const rt_scene_desc& d, HostScene& hs, std::vector<uint32_t>& i
     }
 }
 
-// world vertices, the triangle records in global order (e1 = v1 - v0, e2 = v2 - v0: part of the contract too) and the shading records
+// world vertices, the triangle records in global order and the shading records (each rule: scene_rules.h)
 void flatten(const rt_scene_desc& d, const std::vector<uint32_t>& inst_slot, HostScene& hs, std::vector<TriRec>& gtris) {
     const uint32_t T = d.n_triangles;
     world_vertices(T, d.indices, d.tri_instance, d.instances, d.positions, hs.wverts);
     hs.shade.resize(T);
     gtris.assign(T, TriRec{});
     for (uint32_t t = 0; t < T; ++t) {
-        const float* p = &hs.wverts[9 * (size_t)t];
         TriRec& tr = gtris[t];
-        for (int a = 0; a < 3; ++a) {
-            tr.v0[a] = p[a];
-            tr.e1[a] = p[3 + a] - p[a];
-            tr.e2[a] = p[6 + a] - p[a];
-        }
+        tri_record(&hs.wverts[9 * (size_t)t], tr.v0, tr.e1, tr.e2);
         tr.global_index = t;
         ShadeRec& s = hs.shade[t];
-        const uint32_t ii = d.tri_instance[t], i0 = d.indices[3 * t], i1 = d.indices[3 * t + 1], i2 = d.indices[3 * t + 2];
-        std::memcpy(s.n0, d.normals + 3 * i0, 12), std::memcpy(s.n1, d.normals + 3 * i1, 12);
-        std::memcpy(s.n2, d.normals + 3 * i2, 12);
-        std::memcpy(s.uv0, d.uvs + 2 * i0, 8), std::memcpy(s.uv1, d.uvs + 2 * i1, 8);
-        std::memcpy(s.uv2, d.uvs + 2 * i2, 8);
-        s.instance = hs.packed_mat ? (inst_slot[ii] | (d.instances[ii].material << kPackedInstBits)) : ii;
+        const uint32_t ii = d.tri_instance[t], *idx = d.indices + 3 * (size_t)t;
+        shade_normals(s, idx, d.normals);
+        std::memcpy(s.uv0, d.uvs + 2 * idx[0], 8), std::memcpy(s.uv1, d.uvs + 2 * idx[1], 8);
+        std::memcpy(s.uv2, d.uvs + 2 * idx[2], 8);
+        s.instance = shading_word(hs.packed_mat, inst_slot[ii], d.instances[ii].material, ii);
     }
 }
 
@@ -863,10 +858,7 @@ void world_vertices(uint32_t n_tris, const uint32_t* indices, const uint32_t* tr
         for (int k = 0; k < 3; ++k) {
             const uint32_t vi = indices[3 * (size_t)t + k];
             const float x = positions[3 * (size_t)vi], y = positions[3 * (size_t)vi + 1], z = positions[3 * (size_t)vi + 2];
-            float* p = &wv[9 * (size_t)t + 3 * k];
-            p[0] = ((m[0] * x + m[4] * y) + m[8] * z) + m[12];
-            p[1] = ((m[1] * x + m[5] * y) + m[9] * z) + m[13];
-            p[2] = ((m[2] * x + m[6] * y) + m[10] * z) + m[14];
+            for (int a = 0; a < 3; ++a) wv[9 * (size_t)t + 3 * k + a] = world_coord(m, a, x, y, z);
         }
     }
 }
@@ -880,14 +872,6 @@ bool world_bounds(const std::vector<float>& wv, float lo[3], float hi[3], float&
         lo[a] = std::min(lo[a], wv[i]), hi[a] = std::max(hi[a], wv[i]);
     }
     return scene_padding(lo, hi, pad, err);
-}
-
-void scene_cells(const HostScene& hs, SceneDev& dev) {
-    for (int a = 0; a < 3; ++a) {
-        const float ext = hs.bounds_hi[a] - hs.bounds_lo[a];
-        dev.cell_lo[a] = hs.bounds_lo[a];
-        dev.cell_scale[a] = ext > 0.0f && std::isfinite(ext) ? 4.0f / ext : 0.0f;
-    }
 }
 
 // The device's instance table. Packed shading word (the rule, rt_types.h): the material index travels in the word, so what is left of an
@@ -983,24 +967,20 @@ void record_boxes(HostScene& hs) {
     hs.rec_lo.assign(3 * hs.tris.size(), 0.0f), hs.rec_hi.assign(3 * hs.tris.size(), 0.0f);
     for (size_t r = 0; r < hs.tris.size(); ++r) {
         if (hs.tris[r].global_index == kNoTri) continue;
-        const float* w = &hs.wverts[9 * (size_t)hs.tris[r].global_index];
-        for (int a = 0; a < 3; ++a)
-            hs.rec_lo[3 * r + a] = std::min(w[a], std::min(w[3 + a], w[6 + a])), hs.rec_hi[3 * r + a] = std::max(w[a], std::max(w[3 + a], w[6 + a]));
+        const Box3 b = tri_box(&hs.wverts[9 * (size_t)hs.tris[r].global_index]);
+        std::memcpy(&hs.rec_lo[3 * r], b.lo, 12), std::memcpy(&hs.rec_hi[3 * r], b.hi, 12);
     }
 }
 
 Box3 leaf_bounds(const HostScene& hs, int32_t child) {
     const bool split = hs.rec_lo.size() == 3 * hs.tris.size() && hs.rec_hi.size() == 3 * hs.tris.size() && hs.n_split_triangles > 0;
     const LeafRange leaf = leaf_range(child);
-    Box3 b{{INFINITY, INFINITY, INFINITY}, {-INFINITY, -INFINITY, -INFINITY}};
+    Box3 b = empty_box();
     for (uint32_t r = leaf.first; r < leaf.first + leaf.count; ++r) {
-        if (split) {
-            for (int a = 0; a < 3; ++a) b.lo[a] = std::min(b.lo[a], hs.rec_lo[3 * (size_t)r + a]), b.hi[a] = std::max(b.hi[a], hs.rec_hi[3 * (size_t)r + a]);
-        } else {
-            const float* w = &hs.wverts[9 * (size_t)hs.tris[r].global_index];
-            for (int v = 0; v < 3; ++v)
-                for (int a = 0; a < 3; ++a) b.lo[a] = std::min(b.lo[a], w[3 * v + a]), b.hi[a] = std::max(b.hi[a], w[3 * v + a]);
-        }
+        Box3 rb;
+        if (split) std::memcpy(rb.lo, &hs.rec_lo[3 * (size_t)r], 12), std::memcpy(rb.hi, &hs.rec_hi[3 * (size_t)r], 12);
+        else rb = tri_box(&hs.wverts[9 * (size_t)hs.tris[r].global_index]);
+        grow(b, rb);
     }
     return b;
 }
@@ -1008,26 +988,18 @@ Box3 leaf_bounds(const HostScene& hs, int32_t child) {
 bool refit_host(HostScene& hs, const std::vector<uint32_t>& level_nodes, std::vector<float>& box, std::string& err) {
     // leaf records: the packed v0 / e1 / e2 of their triangle, and the whole triangle's box (a pre-split triangle's pieces mean nothing now)
     record_boxes(hs);
-    for (TriRec& tr : hs.tris) {
-        if (tr.global_index == kNoTri) continue;
-        const float* w = &hs.wverts[9 * (size_t)tr.global_index];
-        for (int a = 0; a < 3; ++a) tr.v0[a] = w[a], tr.e1[a] = w[3 + a] - w[a], tr.e2[a] = w[6 + a] - w[a];
-    }
+    for (TriRec& tr : hs.tris)
+        if (tr.global_index != kNoTri) tri_record(&hs.wverts[9 * (size_t)tr.global_index], tr.v0, tr.e1, tr.e2);
     box.assign(6 * hs.nodes.size(), 0.0f);
+    const auto inner_box = [&](int32_t child) { Box3 b; std::memcpy(&b, &box[6 * (size_t)child], sizeof(Box3)); return b; };
+    const auto tri_of = [&](uint32_t r) { return &hs.wverts[9 * (size_t)hs.tris[r].global_index]; };
     for (uint32_t i : level_nodes) {
-        BvhNode& n = hs.nodes[i];
-        Box3 kb[4];
-        int nk = 0;
-        for (int k = 0; k < 4 && n.child[k] != kChildEmpty; ++k, ++nk) {
-            if (n.child[k] >= 0) std::memcpy(&kb[k], &box[6 * (size_t)n.child[k]], sizeof(Box3));
-            else kb[k] = leaf_bounds(hs, n.child[k]);
-            float* b = &box[6 * (size_t)i];
-            for (int a = 0; a < 3; ++a) b[a] = k ? std::min(b[a], kb[k].lo[a]) : kb[k].lo[a], b[3 + a] = k ? std::max(b[3 + a], kb[k].hi[a]) : kb[k].hi[a];
-        }
-        if (nk == 0) continue; // the empty scene's root
-        BvhNode q = n;
-        if (!quantise_node(q, nk, kb, hs.pad)) { err = "a refit node's child boxes could not be quantised"; return false; }
-        std::memcpy(&n, &q, 48); // words 0..11; the child words stay
+        Box3 u; BvhNode q;
+        const RefitResult res = refit_node(hs.nodes[i], inner_box, tri_of, hs.pad, u, q);
+        if (res == kRefitEmpty) continue; // the empty scene's root
+        if (res == kRefitRefused) { err = "a refit node's child boxes could not be quantised"; return false; }
+        std::memcpy(&box[6 * (size_t)i], &u, sizeof(Box3));
+        hs.nodes[i] = q;
     }
     hs.sah_cost = refit_sah_cost(hs, box);
     return true;

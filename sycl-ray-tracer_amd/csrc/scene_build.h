@@ -47,8 +47,6 @@ void world_vertices(uint32_t n_tris, const uint32_t* indices, const uint32_t* tr
 // Refuses non-finite vertices, reduces the rest to the scene's bounds (std::min / std::max: the first of equal values stays, the sign of a
 // zero bound depends on it) and derives the box padding (scene_padding). Returns false with err set.
 bool world_bounds(const std::vector<float>& wv, float lo[3], float hi[3], float& pad, std::string& err);
-// The ray re-ordering cells of a device scene (SceneDev::cell_lo / cell_scale) from the scene's bounds.
-void scene_cells(const HostScene& hs, SceneDev& dev);
 // rec_lo / rec_hi of every leaf record as the whole triangle's box (what a refit leaves of a pre-split triangle's pieces).
 void record_boxes(HostScene& hs);
 // Exact bounds of a leaf child: the union of its records' boxes — the box of the triangle's pieces in that leaf where the tree is pre-split,
@@ -82,8 +80,6 @@ double refit_sah_cost(const HostScene& hs, const std::vector<float>& box);
 double decoded_sah_cost(const HostScene& hs);
 
 // ---- the origin skip (rt_types.h: SkipRec) ------------------------------------------------------------------------------------
-// A child word as the device's nodes store it (rt_abi.hip: rt_scene_create_ex): what SkipRec::ref is compared with.
-inline uint32_t device_child_word(int32_t child) { return child >= 0 ? (uint32_t)child * 64u : (uint32_t)child; }
 constexpr uint32_t kSkipMaxRecords = 128; // the largest subtree (leaf records) an entry may name: proving one flat costs a pass over it per triangle
 // (scene_check.cpp) The proof behind one entry, in double: every leaf record below `child` — the triangle (v0, v0 + e1, v0 + e2) the kernels
 // test — lies within `dev` of the plane through p with normal n, is no sliver (|e1||e2| / |e1 x e2| <= 256), has an area and a normal within

@@ -1,6 +1,7 @@
 // scene_check.cpp — host diagnostics of a built scene: the two surface-area costs rt_scene_info reports, the structural check behind
 // rt_scene_check_bvh and the node-visit count behind rt_scene_count_visits. Nothing here decides anything about a tree or a render.
 #include "scene_build.h"
+#include "scene_rules.h"
 #include "rt_closest_point.h"
 
 #include <algorithm>
@@ -11,17 +12,12 @@
 namespace rt {
 namespace {
 
-void grow(Box3& r, const Box3& c) {
-    for (int a = 0; a < 3; ++a) r.lo[a] = std::min(r.lo[a], c.lo[a]), r.hi[a] = std::max(r.hi[a], c.hi[a]);
-}
-
 // Depth-first walk below `child`: r receives the exact bounds of everything below it, visit(node, k, box) the exact subtree box of every
 // child k of every inner node on the way (children before their parents). enter(child, depth) runs before a child is read; either
 // callback stops the walk by returning false, and so does the walk itself.
 template <class Enter, class Visit>
 bool exact_boxes(const HostScene& hs, int32_t child, uint32_t depth, Box3& r, Enter&& enter, Visit&& visit) {
-    const float inf = std::numeric_limits<float>::infinity();
-    r = Box3{{inf, inf, inf}, {-inf, -inf, -inf}};
+    r = empty_box();
     if (!enter(child, depth)) return false;
     if (child < 0) {
         r = leaf_bounds(hs, child);
@@ -45,7 +41,7 @@ double decoded_sah_cost(const HostScene& hs) {
     double cost = 0.0, root_area = 0.0;
     for (size_t i = 0; i < hs.nodes.size(); ++i) {
         const BvhNode& n = hs.nodes[i];
-        Box3 nb{{INFINITY, INFINITY, INFINITY}, {-INFINITY, -INFINITY, -INFINITY}};
+        Box3 nb = empty_box();
         for (int k = 0; k < 4; ++k) {
             if (n.child[k] == kChildEmpty) continue;
             const Box3 b = child_box(n, k);
@@ -160,13 +156,8 @@ bool check_skip_table(const HostScene& hs, std::string& err) {
         const SkipRec& e = hs.skip[t];
         if (e.ref == kSkipNone) continue;
         const std::string at = "origin-skip entry of triangle " + std::to_string(t);
-        int32_t child;
-        if ((int32_t)e.ref < 0) {
-            child = (int32_t)e.ref;
-        } else {
-            if (e.ref % 64u || e.ref / 64u >= hs.nodes.size() || !is_word[e.ref / 64u]) { err = at + ": not a child word"; return false; }
-            child = (int32_t)(e.ref / 64u);
-        }
+        const int32_t child = host_child_word(e.ref);
+        if (child >= 0 && (device_child_word(child) != e.ref || (size_t)child >= hs.nodes.size() || !is_word[(size_t)child])) { err = at + ": not a child word"; return false; }
         std::vector<uint32_t> recs;
         if (!records_below(hs, child, 0, recs)) { err = at + ": names no subtree of at most " + std::to_string(kSkipMaxRecords) + " records"; return false; }
         bool member = false;

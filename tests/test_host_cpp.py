@@ -331,3 +331,21 @@ def test_node_globals_are_composed_from_the_node_up_and_the_camera_through_a_qua
     minus_z = -cam_global[8:11].astype(np.float64); minus_z /= np.linalg.norm(minus_z)
     assert np.abs(np.array(want_dir) - minus_z).max() > 1e-3  # a scaled chain: the rotation the quaternion extracts is not the matrix's third column
     assert abs(np.linalg.norm(want_dir) - 1.0) < 1e-6
+
+
+def test_scene_rules_against_the_host_builder_under_asan_ubsan(tmp_path):
+    """csrc/scene_rules.h, the one text of the scene's geometry rules, in a stand-alone host program (tests/tools/scene_rules_check.cpp) on a small
+    random tree over two instances, for the builders whose unions are exact (LBVH, SAH without pre-split triangles). The world vertices, leaf
+    records, record boxes, shading words and normals the rules give are flatten()'s bit for bit; refit_host and refit_node applied node by
+    node reproduce words 0..11 of every built node and every leaf record on unchanged vertices; with every vertex moved each node's decoded
+    child boxes contain their children's exact boxes. Host compiler of the library's build, -ffp-contract=off as there, AddressSanitizer + UBSan on the host code (the program has none for a device)."""
+    csrc = REPO / "sycl-ray-tracer_amd" / "csrc"
+    exe = tmp_path / "scene_rules_check"
+    srcs = [str(REPO / "tests" / "tools" / "scene_rules_check.cpp"), str(csrc / "scene_build.cpp"), str(csrc / "scene_check.cpp")]
+    subprocess.run(["/opt/rocm/bin/hipcc", "-x", "c++", "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-fno-fast-math", "-Xarch_host", "-fsanitize=address,undefined",
+                    "-fno-sanitize-recover=undefined", f"-I{csrc}", f"-I{REPO / 'include'}", "-o", str(exe)] + srcs, check=True, capture_output=True)
+    env = {"ASAN_OPTIONS": "detect_leaks=1:halt_on_error=1", "UBSAN_OPTIONS": "halt_on_error=1:print_stacktrace=1"}
+    p = subprocess.run([str(exe)], capture_output=True, text=True, env=env, timeout=300)
+    assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
+    assert "runtime error" not in p.stderr and "AddressSanitizer" not in p.stderr, p.stderr[-4000:]
+    assert p.stdout.split()[0] == "ok" and int(p.stdout.split()[1]) > 500, p.stdout

@@ -177,9 +177,33 @@ SCENES = [("cornell", {}), ("table", {}), ("atrium", {"detail": 1}), ("atrium", 
           ("atrium_tilted", {"detail": 1})]
 
 
+def soup_scene(name, tris):
+    """A one-instance scene of the given (n, 3, 3) triangles."""
+    sb = scenes.SceneBuilder(name)
+    mat = sb.add_material(scenes.Material(abi.RT_MAT_DIFFUSE, (0.6, 0.5, 0.4)))
+    pos = np.asarray(tris, f32).reshape(-1, 3)
+    nrm = np.tile(np.array([[0, 0, 1]], f32), (pos.shape[0], 1))
+    sb.add_instance(sb.add_mesh(pos, nrm, np.zeros((pos.shape[0], 2), f32), np.arange(pos.shape[0], dtype=np.uint32)), mat)
+    sb.camera = scenes.CameraPose((0.5, 0.5, 3.0), (0, 0, -1), 1.2)
+    return sb.build()
+
+
+def last_leaf_count(tree):
+    """The number of records in the leaf that ends the leaf-ordered record array."""
+    words = tree["nodes"][:, 12:].ravel()
+    codes = ~words[(words & K_CHILD_EMPTY != 0) & (words != K_CHILD_EMPTY)]
+    first, count = codes >> 2, (codes & 3) + 1
+    assert int((first + count).max()) == len(tree["global_index"])
+    return int(count[np.argmax(first)])
+
+
 def get_scene(scene_cache, name, kw):
     if name == "table":
         return scene_cache("tables", n_mats=25, n_rows=6)
+    if name == "one_triangle":  # (the device builder refuses it: the host builds the tree)
+        return soup_scene(name, [[[0, 0, 0], [1, 0, 0], [0, 1, 0.5]]])
+    if name == "odd_tail":  # three triangles, two of them close: the last leaf of the record array holds one record
+        return soup_scene(name, [_box_tri((x, 0, 0), (x + 0.5, 1, 1)) for x in (0.0, 1.0, 10.0)])
     return scene_cache(name, **kw)
 
 

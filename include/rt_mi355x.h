@@ -562,6 +562,105 @@ int  rt_probe_volume_get_sh_device(rt_probe_volume* vol, void* d_sh, void* strea
 int  rt_probe_volume_sample(rt_probe_volume* vol, uint32_t n, const float* pos, const float* normal, float* out_rgb);
 int  rt_probe_volume_sample_device(rt_probe_volume* vol, uint32_t n, const void* d_pos, const void* d_normal, void* d_out_rgb, void* stream);
 
+/* ---- Reflection probes: cube-map captures of the arriving radiance at `count` positions of one scene, baked around one path query on one
+ * stream, prefiltered into a chain of levels for growing roughness, and sampled along caller-supplied directions: glossy light for what has
+ * no parametrisation of its own (moving objects, particles, a rasterised pass that wants the scene's light along a reflection vector). With
+ * the lightmap (static diffuse) and the probe volume (dynamic diffuse) this is the third part of the baked-lighting set.
+ * Layout. Level l has six faces of S_l = size >> l texels on an edge. A probe's chain is its levels in order, l = 0 .. levels-1; within a
+ * level the faces run 0 to 5, then y, then x: texel ((f * S_l) + y) * S_l + x. One float4 per texel: rgb in .xyz and the probe's validity in
+ * .w, 1.0f or 0.0f. Probes are consecutive: probe p's chain starts at float4 p * C, C = the sum of 6 * S_l * S_l over the levels.
+ * Face f at face coordinates (s, t) in [-1, 1]^2 has the unnormalised direction
+ *     0 (+x): ( 1, -t, -s)     1 (-x): (-1, -t,  s)     2 (+y): ( s,  1,  t)     3 (-y): ( s, -1, -t)     4 (+z): ( s, -t,  1)     5 (-z): (-s, -t, -1)
+ * and texel (x, y) of level l has its centre at s = ((float)x + 0.5f) * (2.0f / (float)S_l) - 1.0f, t likewise from y.
+ * Every operation below is one R1 fp32 operation of DESIGN.md §3, left to right as bracketed, never contracted; sqrt and the divisions are
+ * correctly rounded; dot(a, b) = (a.x * b.x + a.y * b.y) + a.z * b.z; there is no transcendental function. next(a) is the renderers'
+ * xorshift32 draw. unit(v): i = 1.0f / sqrt(dot(v, v)) (two roundings), the direction v * i and the weight (i * i) * i, with v the face
+ * direction as the table above writes it (its component order is the dot's).
+ *   1. Entries. T = ((p * 6 + f) * size + y) * size + x is the global index of a level-0 texel; texel T and sample j make entry
+ *      e = T * spt + j with the state a = (seed + (e + 1) * 0x9E3779B9) mod 2^32, 0 replaced by 0x9E3779B9 (the lightmap's rule).
+ *      u1 = next(a), u2 = next(a); s = ((float)x + u1) * (2.0f / (float)size) - 1.0f, t likewise from y and u2. org = the probe's position,
+ *      dir = face f's direction at (s, t), unnormalised (the path query stores its own half copy); the entry's path state is a after the
+ *      two draws.
+ *   2. Paths. One rt_trace_paths_device over the count * 6 * size^2 * spt entries: samples = 1, max_depth and rr_start as given, rng_out
+ *      NULL, rays kept. A probe outside the contract range is rejected there, all its entries together; it is then INVALID: every texel of
+ *      every level is four zeros.
+ *   3. Resolve, per level-0 texel of a valid probe and per channel: C = +0; for j = 0 .. spt-1 in order, C = C + r, r the entry's radiance,
+ *      replaced by fminf(r, clamp) first when clamp > 0; texel = C / (float)spt, .w = 1.
+ *   4. Prefilter, for l = 1 .. levels-1 and every texel of level l of a valid probe. n = unit(the output texel's centre direction)'s
+ *      direction. The table holds, per level-0 texel k in layout order, (d_k, o_k) = unit(its centre direction): o_k is the texel's solid
+ *      angle up to a constant that cancels. q_l = 2 * (levels - l) - 1 squarings: the lobe is cos^(2^q_l), from cos^2 at the last level
+ *      to cos^(2^(2 * levels - 3)) at level 1. W = A = +0; for k = 0 .. 6 * size^2 - 1 in order: c = dot(n, d_k); a term with !(c > 0) is
+ *      skipped (by a select: it multiplies nothing, so a non-finite texel behind the lobe does not reach the sum); otherwise c is squared q_l
+ *      times (c = c * c), w = c * o_k, W = W + w, and per channel A = A + w * texel_k. out = A / W, .w = 1. The sum is one lane's, in layout
+ *      order, with no cross-lane reduction and no atomics. Every level is made from level 0, not from the level below. The table depends
+ *      on size alone and is built once, at creation, by a kernel in this arithmetic.
+ *   5. Stats: probes, valid, and rays = the sum of the entries' ray counts over the valid probes. d_stats holds the same 16 bytes.
+ *   6. Sample, per point: a probe index, a position (optional), a direction r (any length) and a level of detail lod.
+ *      Invalid inputs: probe_index >= count, a non-finite component of pos, r or lod, and a lookup direction (below) whose largest
+ *      |component| is 0 or that is not finite, each give three NaNs. Otherwise an invalid probe gives (0, 0, 0).
+ *      Parallax box, when the probes were created with boxes and pos is not NULL: per axis a, t_a = ((r_a > 0 ? max_a : min_a) - pos_a) / r_a,
+ *      or +inf when r_a == 0; t = fminf(fminf(t_x, t_y), t_z). If t > 0 and finite, the lookup direction is L_a = (pos_a + r_a * t) -
+ *      centre_a, the point where the ray leaves the box seen from the probe; otherwise L = r, as it is without a box or without pos.
+ *      Face: the major axis is the largest |L_a|, ties to x, then y (x if |L_x| >= |L_y| and |L_x| >= |L_z|, else y if |L_y| >= |L_z|); m is
+ *      that |component|, the face the axis' by the component's sign, and (s, t) the inverse of the table, each one division by m:
+ *      0: (-L_z / m, -L_y / m)   1: (L_z / m, -L_y / m)   2: (L_x / m, L_z / m)   3: (L_x / m, -L_z / m)   4: (L_x / m, -L_y / m)   5: (-L_x / m, -L_y / m).
+ *      Levels: lod = fminf(fmaxf(lod, 0.0f), (float)(levels - 1)); l0 = min((int)lod, levels - 2); fl = lod - (float)l0.
+ *      Per level, bilinear inside the face: fx = (s + 1.0f) * (0.5f * (float)S_l) - 0.5f, clamped to [0, S_l - 1] (fminf(fmaxf(..)));
+ *      x0 = min((int)fx, S_l - 2); g = fx - (float)x0; the weights are wx = (1.0f - g, g); y likewise from t. V = +0; over the taps
+ *      (y0, x0), (y0, x0 + 1), (y0 + 1, x0), (y0 + 1, x0 + 1) in this order, V = V + (wy * wx) * texel per channel. Nothing is filtered
+ *      across face edges. out = a * (1.0f - fl) + b * fl, a and b the values of levels l0 and l0 + 1; with levels == 1, out = a.
+ * Radiance is linear and nothing multiplies by a material: the specular colour x result is the caller's.
+ * rt_reflection_probes_entries[_device] return step 1: pos, dir (3 floats per entry each) and state (a word per entry) for
+ * count * 6 * size^2 * spt entries; any may be NULL, not all three. rt_reflection_probes_bake[_device] run steps 1 to 5; the chain stays in
+ * the object, and out_chain (count * C * 4 floats; the device pointer 16-byte aligned) receives a copy when it is not NULL; stats / d_stats
+ * may be NULL. rt_reflection_probes_set_level0[_device] load level 0 of every probe (count * 6 * size^2 * 4 floats, probes consecutive; a
+ * synthetic capture or a saved one; .w of a probe's first texel is its validity): the levels above become STALE.
+ * rt_reflection_probes_prefilter[_device] run step 4 alone on the level 0 held (an invalid probe's higher levels become zeros).
+ * rt_reflection_probes_get_chain[_device] copy the whole chain out. rt_reflection_probes_sample[_device] run step 6 on n points:
+ * probe_index n words, pos 3n floats or NULL, dir 3n floats, lod n floats, out_rgb 3n floats; n == 0 is RT_OK with nothing launched.
+ * The object owns every device buffer it needs, allocated by rt_reflection_probes_create: no later call allocates. Per entry, max_spt of
+ * them per level-0 texel: pos, dir, state, radiance and ray count (12 + 12 + 4 + 12 + 4 = 44 bytes); per chain texel 16 bytes; the table's
+ * 6 * size^2 float4; the positions and boxes (36 bytes per probe); and 65,536 x 44 bytes through which the host form of sample stages its
+ * points a piece at a time. pos (3 * count floats) and box (NULL, or 6 * count floats, min then max per probe) are copied at creation. The
+ * host forms run on the object's stream and synchronise; the device forms enqueue on `stream` (NULL = the null stream) and return. Calls on
+ * one object are serialised by the object: each records an event that the next call's stream waits for. The bake records the scene's
+ * per-stream event through rt_trace_paths_device, so rt_scene_update waits for it, and a bake after an update sees the moved geometry. The
+ * object is destroyed before its scene.
+ * Refused with RT_ERR_INVALID before any HIP call, in this order: NULL handles or required pointers; count outside 1 .. 4096; size not a
+ * power of two in 8 .. 128; levels outside 1 .. log2(size) - 1 (the smallest face is 4); max_spt outside 1 .. 1024;
+ * count * 6 * size^2 * max_spt >= 2^31; a position or box value that is not finite, or a box with min > max; flags other than 0; spt == 0 or
+ * spt > max_spt; max_depth == 0; a clamp that is NaN or negative; prefilter, get_chain or sample before any bake or set_level0; sample with
+ * stale levels (after set_level0 without a prefilter, when levels > 1). After these, rt_reflection_probes_create returns RT_ERR_NO_DEVICE for
+ * a host-only scene.
+ * Limits: no filtering across cube-face edges (a seam shows at high roughness); a cosine-power lobe about the lookup direction, no GGX and
+ * no importance sampling; the caller chooses and blends probes per point; probes do not move after creation; a bake is whole (every entry
+ * at once, not in batches; not incremental); fp32 storage; one device. */
+typedef struct rt_reflection_probes rt_reflection_probes;
+typedef struct rt_reflection_probes_desc {
+    uint32_t count, size, levels, max_spt;
+    const float* pos;       /* 3 * count                                                       */
+    const float* box;       /* NULL, or 6 * count: min then max per probe                      */
+} rt_reflection_probes_desc;                                                                                                        /* 32 bytes */
+typedef struct rt_reflection_bake_params { uint32_t spt, max_depth, rr_start, seed; float clamp; } rt_reflection_bake_params;        /* 20 bytes */
+typedef struct rt_reflection_stats       { uint32_t probes, valid; uint64_t rays; } rt_reflection_stats;                            /* 16 bytes */
+int  rt_reflection_probes_create(rt_scene* scene, const rt_reflection_probes_desc* desc, uint32_t flags, rt_reflection_probes** out);
+void rt_reflection_probes_destroy(rt_reflection_probes* probes);
+int  rt_reflection_probes_entries(rt_reflection_probes* probes, const rt_reflection_bake_params* p, float* pos, float* dir, uint32_t* state);
+int  rt_reflection_probes_entries_device(rt_reflection_probes* probes, const rt_reflection_bake_params* p, void* d_pos, void* d_dir, void* d_state,
+                                         void* stream);
+int  rt_reflection_probes_bake(rt_reflection_probes* probes, const rt_reflection_bake_params* p, float* out_chain, rt_reflection_stats* stats);
+int  rt_reflection_probes_bake_device(rt_reflection_probes* probes, const rt_reflection_bake_params* p, void* d_out_chain, void* d_stats, void* stream);
+int  rt_reflection_probes_set_level0(rt_reflection_probes* probes, const float* level0);
+int  rt_reflection_probes_set_level0_device(rt_reflection_probes* probes, const void* d_level0, void* stream);
+int  rt_reflection_probes_prefilter(rt_reflection_probes* probes);
+int  rt_reflection_probes_prefilter_device(rt_reflection_probes* probes, void* stream);
+int  rt_reflection_probes_get_chain(rt_reflection_probes* probes, float* chain);
+int  rt_reflection_probes_get_chain_device(rt_reflection_probes* probes, void* d_chain, void* stream);
+int  rt_reflection_probes_sample(rt_reflection_probes* probes, uint32_t n, const uint32_t* probe_index, const float* pos, const float* dir,
+                                 const float* lod, float* out_rgb);
+int  rt_reflection_probes_sample_device(rt_reflection_probes* probes, uint32_t n, const void* d_probe_index, const void* d_pos, const void* d_dir,
+                                        const void* d_lod, void* d_out_rgb, void* stream);
+
 /* ---- Renderers: == IRenderer implementations (src/render.hpp:11-18) ------------------------ */
 enum {
     RT_RENDERER_MEGAKERNEL = 0, /* MegakernelRenderer (src/render_megakernel.hpp:13-19) */

@@ -5,4 +5,7 @@ def __getattr__(name):
     if name == "ProbeVolume":  # rtamd.ProbeVolume, without importing numpy and the ctypes layer for `import rtamd` alone
         from .renderer import ProbeVolume
         return ProbeVolume
+    if name == "ReflectionProbes":
+        from .renderer import ReflectionProbes
+        return ReflectionProbes
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

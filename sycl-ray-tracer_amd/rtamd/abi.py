@@ -302,6 +302,35 @@ class rt_probe_stats(C.Structure):
     ]
 
 
+class rt_reflection_probes_desc(C.Structure):
+    _fields_ = [
+        ("count", C.c_uint32),
+        ("size", C.c_uint32),
+        ("levels", C.c_uint32),
+        ("max_spt", C.c_uint32),
+        ("pos", C.POINTER(C.c_float)),
+        ("box", C.POINTER(C.c_float)),
+    ]
+
+
+class rt_reflection_bake_params(C.Structure):
+    _fields_ = [
+        ("spt", C.c_uint32),
+        ("max_depth", C.c_uint32),
+        ("rr_start", C.c_uint32),
+        ("seed", C.c_uint32),
+        ("clamp", C.c_float),
+    ]
+
+
+class rt_reflection_stats(C.Structure):
+    _fields_ = [
+        ("probes", C.c_uint32),
+        ("valid", C.c_uint32),
+        ("rays", C.c_uint64),
+    ]
+
+
 RT_LIGHTMAP_FILTER = 1
 RT_LIGHTMAP_MAX_SIZE = 8192
 RT_LIGHTMAP_MAX_DILATE = 16
@@ -314,6 +343,9 @@ assert C.sizeof(rt_lightmap_filter_params) == 16
 assert C.sizeof(rt_probe_volume_desc) == 40
 assert C.sizeof(rt_probe_bake_params) == 16
 assert C.sizeof(rt_probe_stats) == 16
+assert C.sizeof(rt_reflection_probes_desc) == 32
+assert C.sizeof(rt_reflection_bake_params) == 20
+assert C.sizeof(rt_reflection_stats) == 16
 assert C.sizeof(rt_path_query) == 64
 assert C.sizeof(rt_gather_query) == 64
 assert C.sizeof(rt_denoise_params) == 20
@@ -373,6 +405,21 @@ PROTOTYPES = {
     "rt_probe_volume_get_sh_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "rt_probe_volume_sample": (C.c_int, [C.c_void_p, C.c_uint32, _P(C.c_float), _P(C.c_float), _P(C.c_float)]),
     "rt_probe_volume_sample_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_reflection_probes_create": (C.c_int, [C.c_void_p, _P(rt_reflection_probes_desc), C.c_uint32, _P(C.c_void_p)]),
+    "rt_reflection_probes_destroy": (None, [C.c_void_p]),
+    "rt_reflection_probes_entries": (C.c_int, [C.c_void_p, _P(rt_reflection_bake_params), _P(C.c_float), _P(C.c_float), _P(C.c_uint32)]),
+    "rt_reflection_probes_entries_device": (C.c_int, [C.c_void_p, _P(rt_reflection_bake_params), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_reflection_probes_bake": (C.c_int, [C.c_void_p, _P(rt_reflection_bake_params), _P(C.c_float), _P(rt_reflection_stats)]),
+    "rt_reflection_probes_bake_device": (C.c_int, [C.c_void_p, _P(rt_reflection_bake_params), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_reflection_probes_set_level0": (C.c_int, [C.c_void_p, _P(C.c_float)]),
+    "rt_reflection_probes_set_level0_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_reflection_probes_prefilter": (C.c_int, [C.c_void_p]),
+    "rt_reflection_probes_prefilter_device": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "rt_reflection_probes_get_chain": (C.c_int, [C.c_void_p, _P(C.c_float)]),
+    "rt_reflection_probes_get_chain_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_reflection_probes_sample": (C.c_int, [C.c_void_p, C.c_uint32, _P(C.c_uint32), _P(C.c_float), _P(C.c_float), _P(C.c_float), _P(C.c_float)]),
+    "rt_reflection_probes_sample_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                     C.c_void_p]),
     "rt_renderer_create": (C.c_int, [C.c_int, C.c_void_p, C.c_int32, C.c_int32, C.c_uint32, C.c_uint32,
                                      C.c_uint32, _P(C.c_void_p)]),
     "rt_renderer_destroy": (None, [C.c_void_p]),

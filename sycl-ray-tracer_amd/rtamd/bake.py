@@ -134,3 +134,27 @@ def shade_vertices_from_volume(volume, sd: SceneDesc) -> np.ndarray:
     of `sd` for its shading normal, (T, 3, 3) float32 [triangle, corner, rgb], one ProbeVolume.sample call over vertex_points(sd)."""
     pos, nrm = vertex_points(sd)
     return volume.sample(pos.reshape(-1, 3), nrm.reshape(-1, 3)).reshape(-1, 3, 3)
+
+
+def lod_for_roughness(levels: int, roughness):
+    """The level of detail of a renderer.ReflectionProbes chain for a surface roughness a in [0, 1], float32, one per roughness: the Phong
+    exponent 2 / a^2 - 2 matched against the levels' lobes. Level l >= 1 is prefiltered with cos^(2^q_l), q_l = 2 * (levels - l) - 1, a power
+    a quarter of the level's below, and level 0 continues that sequence (q_0 = 2 * levels - 1: its texels are the lobe); between two levels
+    the lod is linear in log2 of the exponent, below the last level's power it is levels - 1, above level 0's it is 0. Host arithmetic in
+    float64, outside the bit-exact contract."""
+    if int(levels) < 1:
+        raise ValueError("levels must be at least 1")
+    a = np.clip(np.asarray(roughness, np.float64), 0.0, 1.0)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        q = np.log2(np.maximum(2.0 / (a * a) - 2.0, 0.0))  # a = 0: +inf, a = 1: -inf
+    return np.clip(int(levels) - 0.5 * (q + 1.0), 0.0, float(int(levels) - 1)).astype(f32)
+
+
+def reflect_dirs(view, normal) -> np.ndarray:
+    """view - 2 * dot(view, normal) * normal per row, (n, 3) float32: the direction ReflectionProbes.sample looks up for a view vector that
+    points at the surface and a unit normal."""
+    view, normal = np.asarray(view, f32), np.asarray(normal, f32)
+    if view.ndim != 2 or view.shape[1] != 3 or normal.shape != view.shape:
+        raise ValueError("view and normal must both be (n, 3)")
+    d = (view * normal).sum(1, dtype=f32)
+    return np.ascontiguousarray(view - (f32(2.0) * d)[:, None] * normal)

@@ -905,6 +905,148 @@ class ProbeVolume:
             pass
 
 
+class ReflectionProbes:
+    """rt_reflection_probes: cube-map captures at `positions` (count, 3) over `scene`, each a chain of `levels` levels with faces of
+    size >> l texels, prefiltered for growing roughness (include/rt_mi355x.h: rt_reflection_probes_bake). boxes: None, or (count, 6), min then
+    max per probe, the parallax boxes of sample. max_spt: the most samples per level-0 texel a bake may ask for. A chain is
+    (count, chain_texels, 4) float32, level l of a probe at [level_offset(l) : level_offset(l + 1)] as (6, S_l, S_l, 4), validity in .w
+    (rtamd.bake.lod_for_roughness and reflect_dirs give sample's lod and direction). Close it before its scene."""
+
+    def __init__(self, scene: Scene, positions, size: int, levels: int, max_spt: int = 1, boxes=None):
+        pos = np.asarray(positions)
+        if pos.ndim != 2 or pos.shape[1] != 3 or pos.dtype.kind not in "fiu":
+            raise ValueError("positions must be (count, 3) numbers")
+        if boxes is not None:
+            boxes = np.asarray(boxes)
+            if boxes.shape != (pos.shape[0], 6) or boxes.dtype.kind not in "fiu":
+                raise ValueError("boxes must be (count, 6) numbers: min then max per probe")
+        for v in (size, levels, max_spt):
+            if not 0 <= int(v) <= 0xFFFFFFFF:
+                raise ValueError("size, levels and max_spt must fit 32 unsigned bits")
+        self._lib = scene._lib
+        self.scene = scene
+        self.positions = np.ascontiguousarray(pos, np.float32)
+        self.boxes = None if boxes is None else np.ascontiguousarray(boxes, np.float32)
+        self.count, self.size, self.levels, self.max_spt = int(pos.shape[0]), int(size), int(levels), int(max_spt)
+        self.face0 = 6 * self.size * self.size
+        self.chain_texels = sum(6 * (self.size >> l) ** 2 for l in range(self.levels))
+        self.desc = abi.rt_reflection_probes_desc(self.count, self.size, self.levels, self.max_spt, abi.fptr(self.positions),
+                                                  abi.fptr(self.boxes) if self.boxes is not None else None)
+        self.h = C.c_void_p()
+        abi.check(self._lib.rt_reflection_probes_create(scene.h, C.byref(self.desc), 0, C.byref(self.h)), self._lib)
+
+    @staticmethod
+    def _params(spt, max_depth, rr_start, seed, clamp):
+        return abi.rt_reflection_bake_params(int(spt), int(max_depth), int(rr_start), int(seed) & 0xFFFFFFFF, float(clamp))
+
+    def level_offset(self, l: int) -> int:
+        """The texels of a probe's chain in front of level l (l == levels: the chain's length)."""
+        return sum(6 * (self.size >> m) ** 2 for m in range(int(l)))
+
+    def level(self, chain: np.ndarray, l: int) -> np.ndarray:
+        """Level l of every probe of a chain, (count, 6, S_l, S_l, 4): a view."""
+        S = self.size >> int(l)
+        return chain[:, self.level_offset(l):self.level_offset(l + 1)].reshape(self.count, 6, S, S, 4)
+
+    def entries(self, spt: int, seed: int) -> dict:
+        """rt_reflection_probes_entries: {"pos", "dir": (entries, 3) float32, the probes' positions and the jittered face directions, "state":
+        (entries,) uint32, the states the paths start with}, entry e = (((p * 6 + f) * size + y) * size + x) * spt + j."""
+        n = self.count * self.face0 * max(int(spt), 0)
+        out = {"pos": np.zeros((n, 3), np.float32), "dir": np.zeros((n, 3), np.float32), "state": np.zeros(n, np.uint32)}
+        p = self._params(spt, 1, 0, seed, 0.0)
+        abi.check(self._lib.rt_reflection_probes_entries(self.h, C.byref(p), abi.fptr(out["pos"]), abi.fptr(out["dir"]), abi.u32ptr(out["state"])),
+                  self._lib)
+        return out
+
+    def entries_device(self, spt: int, seed: int, d_pos: int = 0, d_dir: int = 0, d_state: int = 0, stream: int = 0) -> None:
+        """rt_reflection_probes_entries_device on DEVICE pointers (e.g. torch .data_ptr()), enqueued on `stream`; 0 = NULL (not written)."""
+        p = self._params(spt, 1, 0, seed, 0.0)
+        v = [C.c_void_p(x or None) for x in (d_pos, d_dir, d_state, stream)]
+        abi.check(self._lib.rt_reflection_probes_entries_device(self.h, C.byref(p), *v), self._lib)
+
+    def bake(self, spt: int, max_depth: int, rr_start: int = 0, seed: int = 0, clamp: float = 0.0):
+        """rt_reflection_probes_bake -> (chain (count, chain_texels, 4) float32, {"probes", "valid", "rays"}); the chain also stays in the object."""
+        p = self._params(spt, max_depth, rr_start, seed, clamp)
+        chain = np.zeros((self.count, self.chain_texels, 4), np.float32)
+        st = abi.rt_reflection_stats()
+        abi.check(self._lib.rt_reflection_probes_bake(self.h, C.byref(p), abi.fptr(chain), C.byref(st)), self._lib)
+        return chain, {"probes": st.probes, "valid": st.valid, "rays": st.rays}
+
+    def bake_device(self, spt: int, max_depth: int, rr_start: int = 0, seed: int = 0, clamp: float = 0.0, d_chain: int = 0, d_stats: int = 0,
+                    stream: int = 0) -> None:
+        """rt_reflection_probes_bake_device, enqueued on `stream`: d_chain count * chain_texels * 4 floats or 0, d_stats 16 bytes or 0."""
+        p = self._params(spt, max_depth, rr_start, seed, clamp)
+        v = [C.c_void_p(x or None) for x in (d_chain, d_stats, stream)]
+        abi.check(self._lib.rt_reflection_probes_bake_device(self.h, C.byref(p), *v), self._lib)
+
+    def set_level0(self, level0: np.ndarray) -> None:
+        """rt_reflection_probes_set_level0: load a (count, 6, size, size, 4) float32 level 0 (a saved capture, or a synthetic one); the levels
+        above it are stale until prefilter()."""
+        if not isinstance(level0, np.ndarray) or level0.dtype != np.float32 or level0.shape != (self.count, 6, self.size, self.size, 4):
+            raise ValueError(f"level0 must be a float32 array of shape ({self.count}, 6, {self.size}, {self.size}, 4)")
+        level0 = np.ascontiguousarray(level0)
+        abi.check(self._lib.rt_reflection_probes_set_level0(self.h, abi.fptr(level0)), self._lib)
+
+    def set_level0_device(self, d_level0: int, stream: int = 0) -> None:
+        abi.check(self._lib.rt_reflection_probes_set_level0_device(self.h, C.c_void_p(d_level0 or None), C.c_void_p(stream or None)), self._lib)
+
+    def prefilter(self) -> None:
+        """rt_reflection_probes_prefilter: the levels above 0 from the level 0 held."""
+        abi.check(self._lib.rt_reflection_probes_prefilter(self.h), self._lib)
+
+    def prefilter_device(self, stream: int = 0) -> None:
+        abi.check(self._lib.rt_reflection_probes_prefilter_device(self.h, C.c_void_p(stream or None)), self._lib)
+
+    def get_chain(self) -> np.ndarray:
+        chain = np.zeros((self.count, self.chain_texels, 4), np.float32)
+        abi.check(self._lib.rt_reflection_probes_get_chain(self.h, abi.fptr(chain)), self._lib)
+        return chain
+
+    def get_chain_device(self, d_chain: int, stream: int = 0) -> None:
+        abi.check(self._lib.rt_reflection_probes_get_chain_device(self.h, C.c_void_p(d_chain or None), C.c_void_p(stream or None)), self._lib)
+
+    def sample(self, probe_index: np.ndarray, dirs: np.ndarray, lod, pos=None) -> np.ndarray:
+        """rt_reflection_probes_sample: probe_index (n,) integers, dirs (n, 3), lod (n,) or one number, pos None or (n, 3) (with boxes: the
+        parallax correction) -> (n, 3) float32, the radiance along the directions."""
+        idx, dirs = np.asarray(probe_index), np.asarray(dirs)
+        if dirs.ndim != 2 or dirs.shape[1] != 3 or dirs.dtype.kind != "f":
+            raise ValueError("dirs must be a floating-point (n, 3) array")
+        n = dirs.shape[0]
+        if idx.shape != (n,) or idx.dtype.kind not in "ui" or (n and (idx.min() < 0 or idx.max() > 0xFFFFFFFF)):
+            raise ValueError("probe_index must be (n,) integers that fit 32 unsigned bits")
+        lod = np.asarray(lod)
+        if lod.ndim == 0:
+            lod = np.repeat(lod, n)
+        if lod.shape != (n,) or lod.dtype.kind not in "fiu":
+            raise ValueError("lod must be one number or (n,) numbers")
+        if pos is not None:
+            pos = np.asarray(pos)
+            if pos.shape != dirs.shape or pos.dtype.kind != "f":
+                raise ValueError("pos must be a floating-point (n, 3) array, as dirs")
+            pos = np.ascontiguousarray(pos, np.float32)
+        idx, dirs, lod = np.ascontiguousarray(idx, np.uint32), np.ascontiguousarray(dirs, np.float32), np.ascontiguousarray(lod, np.float32)
+        out = np.zeros((n, 3), np.float32)
+        abi.check(self._lib.rt_reflection_probes_sample(self.h, n, abi.u32ptr(idx), abi.fptr(pos) if pos is not None else None, abi.fptr(dirs),
+                                                        abi.fptr(lod), abi.fptr(out)), self._lib)
+        return out
+
+    def sample_device(self, n: int, d_index: int, d_pos: int, d_dir: int, d_lod: int, d_rgb: int, stream: int = 0) -> None:
+        """rt_reflection_probes_sample_device on DEVICE pointers (d_pos 0 = NULL: no parallax correction), enqueued on `stream`."""
+        v = [C.c_void_p(x or None) for x in (d_index, d_pos, d_dir, d_lod, d_rgb, stream)]
+        abi.check(self._lib.rt_reflection_probes_sample_device(self.h, int(n), *v), self._lib)
+
+    def close(self):
+        if self.h:
+            self._lib.rt_reflection_probes_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 # The denoiser's defaults (DESIGN.md §13: chosen by scripts/denoise_probe.py's sweep on the atrium and the Cornell box). sigma_position is
 # DENOISE_POSITION_FRACTION of the scene's scale (Scene.scale()); host/main.cpp's --denoise uses the same values.
 DENOISE_ITERATIONS = 5

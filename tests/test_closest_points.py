@@ -1,7 +1,8 @@
 """Closest-point queries (include/rt_mi355x.h: rt_closest_points[_device], rt_scene_closest_host) without a GPU: the exported entry points
 and the struct layout, the refusals in front of the device, the Python wrappers, the numpy model of the contract (closest_model, shared
 with tests/test_gpu_closest_points.py) against the host brute force, ties, degenerate triangles and radii on the boundary, the underestimate
-bound the cull leans on, and the host walk of the tree (the kernel's cull rule) against the brute force on every builder."""
+bound the cull leans on, and the host walk of the tree (the kernel's cull rule) against the brute force on every builder — and, at the
+end, on the scenes of tests/closest_scenes.py, the trees tests/test_gpu_closest_points_trees.py holds the kernel's own steps on."""
 import ctypes as C
 import re
 import subprocess
@@ -516,3 +517,115 @@ def test_closest_kernel_has_the_resources_design_states_and_no_scratch_beyond_th
     assert 1 <= len(scratch) <= 8 and all(re.fullmatch(r"scratch_(load|store)_dword v\d+, v\d+, off", ln) for ln in scratch), scratch
     assert got["occupancy"] == 6 and got["vgpr_count"] <= 80 and 3 * got["group_segment_fixed_size"] <= 160 * 1024
     assert "global_load_dwordx4 %" not in (REPO / "sycl-ray-tracer_amd" / "csrc" / "rt_closest.hip").read_text()
+
+
+# ---- the trees the kernel's own steps are held on (tests/test_gpu_closest_points_trees.py): their host statement ----------------------------
+# tests/closest_scenes.py imports this module, so it is imported inside the functions here.
+TREE_CASES = ["pile", "offset_near", "offset_far", "mixed", "mixed_corner", "duplicates"]
+_tree_cache = {}
+
+
+def _tree_case(case):
+    """-> dict(sd, pos, wv, mask, model): the scene, its 4,096 points (the pile: 1,024 more in its free corner; the offset atria: 2,048), and on the mixed and the
+    duplicate scenes closest_model without a radius. Built once per case and shared by the builders; nothing changes it."""
+    import closest_scenes as cs
+    if case in _tree_cache:
+        return _tree_cache[case]
+    mask = None
+    if case == "pile":
+        sd = cs.pile_scene()
+        pos = np.concatenate([point_mix(sd, 4096, 1), cs.pile_corner_points(1024, 2)])
+    elif case in ("offset_near", "offset_far"):
+        sd = cs.offset_scene(cs.OFFSETS[case == "offset_far"])
+        pos = point_mix(sd, 2048, 2)  # (18,604 records: the brute force is the cost)
+    elif case in ("mixed", "mixed_corner"):
+        sd, mask = cs.mixed_scene()
+        pos = point_mix(sd, 4096, 7) if case == "mixed" else cs.corner_points(sd, 4096, 3)
+    else:
+        sd = cs.duplicate_scene()
+        pos = point_mix(sd, 4096, 4)
+    wv = world_vertices(sd)
+    np.testing.assert_array_equal(wv, sd.world_triangles().astype(f32).reshape(-1, 3, 3))  # tri_scene: world vertices = positions
+    model = closest_model(pos, wv) if case in ("mixed", "mixed_corner", "duplicates") else None
+    _tree_cache[case] = dict(sd=sd, pos=pos, wv=wv, mask=mask, model=model)
+    return _tree_cache[case]
+
+
+@pytest.mark.parametrize("builder", ["sah", "lbvh"])
+@pytest.mark.parametrize("case", TREE_CASES)
+def test_the_walk_equals_the_brute_force_on_the_trees_the_device_is_held_on(devlib, case, builder):
+    """On the pile (stack_need > 12 under both builders), the atrium moved to (1000, -2000, 500) and to (1e5, 1e5, 1e5), the mixed scene
+    with its 300 degenerate triangles (pre-split under SAH) at the point mix and in the corner of the contract range, and seven shuffled
+    copies of the cube: check_bvh passes, the walk equals the brute force bit for bit with no radius and with radius_mix, and on the mixed
+    and duplicate scenes the brute force equals closest_model. On the duplicates every winner is the lowest copy of its triangle."""
+    import closest_scenes as cs
+    c = _tree_case(case)
+    sd, pos = c["sd"], c["pos"]
+    s = Scene(sd, -1, cs.BUILDERS[builder], lib=devlib)
+    s.check_bvh()
+    info, tree = s.info(), s.tree()
+    assert tree["built_by"] == cs.BUILDERS[builder]
+    if case == "pile":
+        assert tree["stack_need"] > cs.K_LDS_STACK
+    if case in ("mixed", "mixed_corner"):
+        assert (info.n_split_triangles > 0) == (builder == "sah")
+    brute, walk = s.closest_host(pos), s.closest_host(pos, use_bvh=True)
+    same(walk, brute, f"{case} {builder}")
+    assert (brute["tri"] != NO_TRI).all() and not np.isnan(brute["dist2"]).any()
+    print(f"{case} {builder}: {info.n_nodes} nodes, {info.n_leaf_records} records, depth {info.max_depth}, stack_need {tree['stack_need']}, "
+          f"{info.n_split_triangles} pre-split; the walk: {walk['node_visits'] / len(pos):.1f} node visits and {walk['tri_tests'] / len(pos):.1f} "
+          f"triangle tests per point with no radius")
+    md2 = cs.radius_mix(brute["dist2"], 5)
+    brute_r = s.closest_host(pos, md2)
+    same(s.closest_host(pos, md2, use_bvh=True), brute_r, f"{case} {builder}, radius_mix")
+    hit = brute_r["tri"] != NO_TRI
+    assert hit.any() and (~hit).any()
+    if c["model"] is not None:
+        same(brute, c["model"], f"{case} {builder}: brute force vs model")
+        if builder == "sah":  # (the model takes seconds on the mixed scene: with radii once per case, on the first 1,024 entries)
+            same({k: brute_r[k][:1024] for k in OUTPUTS}, closest_model(pos[:1024], c["wv"], md2[:1024]), f"{case}: brute force vs model, radius_mix")
+    if case == "duplicates":
+        np.testing.assert_array_equal(brute["tri"], cs.lowest_copy(brute["tri"]))
+        np.testing.assert_array_equal(brute_r["tri"][hit], cs.lowest_copy(brute_r["tri"][hit]))
+        assert len(np.unique(brute["tri"])) == 12
+    s.close()
+
+
+def test_the_mixed_scene_gives_nan_candidates_and_degenerate_winners():
+    """What the mixed scene is there for, stated on the model: every degenerate triangle of kind (a, a, b) gives a NaN candidate for some
+    of the 4,096 points, no winner is NaN, and some winners are degenerate triangles (the regions where their dist2 is finite)."""
+    import closest_scenes as cs
+    c = _tree_case("mixed")
+    wv, mask, pos, model = c["wv"], c["mask"], c["pos"], c["model"]
+    assert mask.sum() == 300 and len(wv) == 3802
+    src = cs.nan_source(wv, mask)
+    assert len(src) == 100
+    d2 = closest_candidates(pos[:, None], wv[src, 0][None], (wv[src, 1] - wv[src, 0])[None], (wv[src, 2] - wv[src, 0])[None])[0]
+    nans = np.isnan(d2).sum(0)
+    print(f"{nans.sum()} NaN candidates over {len(src)} triangles x {len(pos)} points, at least {nans.min()} per triangle; "
+          f"{mask[model['tri']].sum()} degenerate winners")
+    assert (nans >= 1).all()
+    assert not np.isnan(model["dist2"]).any() and (model["tri"] != NO_TRI).all()
+    assert mask[model["tri"]].sum() >= 1
+    # without the degenerate triangles the same seed gives the same other triangles: the degenerate ones are an addition
+    plain, none = cs.mixed_vertices(degenerate=False)
+    assert not none.any() and len(plain) == 3502
+    assert {t.tobytes() for t in plain} == {t.tobytes() for t in wv[~mask]}
+
+
+def test_vertex_radii_hit_at_zero_and_miss_below_it(devlib):
+    """The first 1,000 world vertices of the Cornell box and of the mixed scene as points, with max_dist2 cycling through -0.0, +0.0,
+    FLT_MIN and +inf (hits with dist2 == 0 and the vertex as point) and -1 (a miss): brute force, walk and model. On the mixed scene a
+    third vertex need not be at 0 (closest_scenes.check_vertex_radii says why): there the model alone is the statement."""
+    import closest_scenes as cs
+    for name, sd in (("cornell", scenes.get_scene("cornell")), ("mixed", _tree_case("mixed")["sd"])):
+        wv = world_vertices(sd)
+        n = min(1000, 3 * len(wv) // 5 * 5)
+        pos, md2 = cs.vertex_radii(wv, n)
+        want = closest_model(pos, wv, md2)
+        cs.check_vertex_radii(want, pos, md2, name, third_vertices=name == "cornell")
+        for builder in ("sah", "lbvh"):
+            s = Scene(sd, -1, cs.BUILDERS[builder], lib=devlib)
+            same(s.closest_host(pos, md2), want, f"{name} {builder} brute")
+            same(s.closest_host(pos, md2, use_bvh=True), want, f"{name} {builder} walk")
+            s.close()

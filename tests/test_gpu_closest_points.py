@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 from rtamd import abi, bake, scenes
+from closest_scenes import radius_mix
 from rtamd.renderer import ProbeVolume, Scene
 from test_closest_points import NO_TRI, OUTPUTS, bounds_of, closest_model, point_mix, same, tri_scene, world_vertices
 
@@ -50,18 +51,6 @@ def host_form(s, pos, max_dist2=None):
         setattr(q, k, a.ctypes.data)
     abi.check(s._lib.rt_closest_points(s.h, C.byref(q)), s._lib)
     return out
-
-
-def radius_mix(free_d2, seed):
-    """per-entry squared radii around the unbounded answer: a fifth each exactly on it, the next float below it, twice it, a tenth of it,
-    and +inf — with a few negative, -0.0 and 0 entries"""
-    g = np.random.default_rng(seed)
-    n = len(free_d2)
-    kind = g.integers(0, 5, n)
-    md2 = np.select([kind == 0, kind == 1, kind == 2, kind == 3], [free_d2, np.nextafter(free_d2, f32(-np.inf)), f32(2) * free_d2, f32(0.1) * free_d2],
-                    f32(np.inf)).astype(f32)
-    md2[:3] = np.array([-1.0, -0.0, 0.0], f32)[:min(n, 3)]
-    return md2
 
 
 def test_cornell_equals_the_model_and_the_host_brute_force_at_every_size(gpu, scene_cache):

@@ -292,6 +292,59 @@ int rt_closest_points_device(rt_scene* scene, const rt_point_query* q, void* str
 int rt_scene_closest_host(const rt_scene* scene, uint32_t n, const float* pos, const float* max_dist2, int use_bvh, float* dist2, float* u,
                           float* v, uint32_t* tri, float* point, uint64_t* node_visits, uint64_t* tri_tests);
 
+/* ---- Multi-hit ray queries: the k nearest hits of every ray, resumable (wall thickness, every layer along a probe ray, X-ray picking,
+ * crossing parity, interval lists). Every other ray entry point answers with at most one surface per ray; restarting a closest-hit query
+ * from its hit point is not exact (the near limit swallows close layers, hits at equal t on shared edges are lost).
+ * The contract. Triangle j's candidate (t, u, v) for a ray is rt_intersect_batch's fp32 Moller-Trumbore test: the fused cross and dot
+ * products, the edge tests on the numerators, inv = RN(1 / det), t > 1e-4. The candidate COUNTS iff
+ *     1e-4 < t <= tmax[i]   and, where a resume key is given,   t > after_t[i] || (t == after_t[i] && j > after_tri[i])
+ * — (t, j) > (after_t, after_tri) lexicographically. The answer for ray i is the k smallest counting candidates in ascending (t, j)
+ * order, in slots i * k .. i * k + k - 1 of t, u, v, tri (ray-major). Every triangle index appears at most once. count[i] is the number
+ * of slots filled; the slots past it hold the miss values t = +inf, u = v = 0, tri = 0xFFFFFFFF. A candidate with t = +inf counts when
+ * tmax is +inf (rt_intersect_batch's quirk), so a slot is filled iff its tri is not 0xFFFFFFFF, whatever isfinite(t) says.
+ *   k = 1, no key:  the slot is rt_trace_rays RT_QUERY_CLOSEST bit for bit.
+ *   Paging:         a page of k continued with the key (t, tri) of its last slot, for the rays whose count == k, lists every counting
+ *                   hit exactly once; the pages concatenated equal one call with a larger k.
+ *   Exhaustion:     a ray with count < k has no further counting hit.
+ * The limit: ill-conditioned triangles. The queries reach a triangle through boxes that hold its true surface, padded by 2e-5 x the
+ * scene's scale, and skip a box the ray enters behind tmax or behind the k-th entry so far. The candidate's t is the fp32 test's, and on a
+ * sliver (det of the order of 1e-5 x |dir| x the edges' product) it can lie far from where the ray meets the true surface — 0.6 % of t has
+ * been seen. A counting candidate whose fp32 t is more than half that padding in front of its true t may therefore be MISSING from the
+ * list, when tmax or the k-th entry lies between the two. Nothing else is affected: every hit listed is a counting candidate with these
+ * exact bits, in this order, at most once; a list never holds a hit the brute force would not; and on a ray all of whose counting
+ * candidates lie within half the padding of their true t the list is exactly the one stated above. With such a hit on a ray, a count, a
+ * crossing parity or a paged enumeration can be one short. rt_intersect_batch and rt_trace_rays have the same limit for their one hit
+ * (the k = 1 identity holds regardless: both skip the same boxes). rt_scene_multihit_host with use_bvh = 0 is the list without the limit.
+ * Rejected rays: an origin outside the contract range or not finite (rt_intersect_batch), a NaN tmax, a NaN after_t. rt_trace_rays_multi
+ * returns RT_ERR_INVALID naming the first of them and writes nothing; rt_trace_rays_multi_device marks each instead — all k slots t = NaN
+ * and tri = RT_TRI_REJECTED (u, v unwritten), count = 0 — and answers the others.
+ * Refusals, in this order: RT_ERR_INVALID for a NULL scene or query; n == 0 is RT_OK, nothing launched; then RT_ERR_INVALID for k outside
+ * 1 .. RT_MULTIHIT_MAX, NULL org or dir, after_t without after_tri or the reverse, every output NULL; RT_ERR_NO_DEVICE for a host-only
+ * scene comes last. Any output may be NULL: it is not written.
+ * rt_trace_rays_multi takes host arrays, stages them through device buffers, runs on the null stream and synchronises.
+ * rt_trace_rays_multi_device takes device arrays and behaves as rt_trace_rays_device does: no allocation, no synchronisation, no host
+ * copy; it shares the scene's cursors and per-stream event with the other queries, and rt_scene_update waits for it. */
+#define RT_MULTIHIT_MAX 8
+typedef struct rt_multihit_query {
+    uint32_t n, k;                    /* k in 1..RT_MULTIHIT_MAX, the same for every ray of the call */
+    const float *org, *dir;           /* 3n each, as rt_trace_rays                                  */
+    const float *tmax;                /* n, or NULL = +inf                                          */
+    const float *after_t;             /* n, or NULL = no key                                        */
+    const uint32_t *after_tri;        /* n; required iff after_t is given                           */
+    float *t, *u, *v; uint32_t *tri;  /* n*k each, ray-major; any may be NULL, not all five outputs */
+    uint32_t *count;                  /* n                                                          */
+} rt_multihit_query;
+int rt_trace_rays_multi(rt_scene* scene, const rt_multihit_query* q);
+int rt_trace_rays_multi_device(rt_scene* scene, const rt_multihit_query* q, void* stream);
+/* Diagnostic, host only (works on a scene built with device < 0; brings the host copy of an updated device scene up to date first): the
+ * same queries on the host. use_bvh = 0: the brute force over all triangles in index order. use_bvh = 1: the walk the kernel makes — the
+ * decoded child boxes culled against the moving bound, (tmax, 0xFFFFFFFF) while the list has free slots and (t, tri) of its k-th entry once
+ * it is full — counting node visits and triangle tests (either may be NULL). Rays are not refused here (a NaN tmax or key counts nothing),
+ * k is any number >= 1 (a list longer than a ray's hits never fills: the walk with the bound held at tmax), any output may be NULL. */
+int rt_scene_multihit_host(const rt_scene* scene, uint32_t n, uint32_t k, const float* org, const float* dir, const float* tmax,
+                           const float* after_t, const uint32_t* after_tri, int use_bvh, float* t, float* u, float* v, uint32_t* tri,
+                           uint32_t* count, uint64_t* node_visits, uint64_t* tri_tests);
+
 /* ---- Path queries: radiance along caller-supplied rays (light probes, irradiance volumes, baking, reflection captures, radiance caches).
  * Entry i runs `samples` paths of at most `max_depth` rays from (org[i], dir[i]) with the renderers' own bounce (materials, textures, sky,
  * Russian roulette) on the xorshift32 state rng[i], each path continuing the state the one before left:

@@ -19,9 +19,10 @@
 //   rt_path_query.hip path queries, radiance along caller-supplied rays (rt_trace_paths[_device]) and their kernel
 //   rt_path_gather.hip gather queries, diffuse-lobe radiance at caller-supplied points (rt_gather_paths[_device]) and their kernel
 //   rt_closest.hip closest-point queries, the nearest triangle to caller-supplied points (rt_closest_points[_device], rt_scene_closest_host) and their kernel
-//   rt_closest_point.h the contract of those queries, one fp32 text for the kernel and the host walk (scene_check.cpp: closest_host)
-//   rt_query_launch.h what those four units share on the host: grid sizing, the launch on the shared cursors, the host forms' staging, the path / gather checks
-//   rt_path_rounds.h  the kernel body the last two share (path_rounds<E>); rt_query_frame.h the one rt_query.hip and rt_closest.hip share (query_frame<P>) and the claim of entries, shared by all four
+//   rt_closest_point.h the contract of the closest-point queries, one fp32 text for the kernel and the host walk (scene_check.cpp: closest_host)
+//   rt_multihit.hip multi-hit ray queries, the k nearest hits of every ray, resumable (rt_trace_rays_multi[_device], rt_scene_multihit_host) and their kernels
+//   rt_query_launch.h what those five units (rt_query.hip and the last four) share on the host: grid sizing, the launch on the shared cursors, the host forms' staging, the path / gather checks
+//   rt_path_rounds.h  the kernel body rt_path_query.hip and rt_path_gather.hip share (path_rounds<E>); rt_query_frame.h the one rt_query.hip, rt_closest.hip and rt_multihit.hip share (query_frame<P>) and the claim of entries, shared by all five
 //   rt_lightmap.hip lightmap baking around one gather query (rt_lightmap_*): UV coverage, texel guides, resolve and dilation kernels
 #pragma once
 #include <hip/hip_runtime.h>
@@ -175,8 +176,9 @@ struct SceneUpdate {
 constexpr uint32_t kQueryCursorBytes = 32u * 128u;
 constexpr uint32_t kQueryChunk = 64, kQueryHeads = 32, kQueryHeadStride = 16; // (stride in 8-byte words)
 static_assert(kQueryHeads * kQueryHeadStride * 8u == kQueryCursorBytes, "the scene's cursor block holds one 128-byte line per shard");
-// the query kernels, each with a persistent grid of its own (rt_scene::query_grid)
-enum QueryKind : int { kQueryKindClosest = 0, kQueryKindAny = 1, kQueryKindPath = 2, kQueryKindGather = 3, kQueryKindPoint = 4, kQueryKinds = 5 };
+// the query kernels, each with a persistent grid of its own (rt_scene::query_grid). The sixth kind, kQueryKindMulti, has three kernels of
+// different occupancy (rt_multihit.hip: k_multihit<2>, <4>, <8>) and so three grids: kQueryKindMulti + 0, + 1, + 2
+enum QueryKind : int { kQueryKindClosest = 0, kQueryKindAny = 1, kQueryKindPath = 2, kQueryKindGather = 3, kQueryKindPoint = 4, kQueryKindMulti = 5, kQueryKinds = 8 };
 
 struct rt_scene {
     HostScene hs;

@@ -419,4 +419,137 @@ int closest_host(const HostScene& hs, uint32_t n, const float* pos, const float*
     return RT_OK;
 }
 
+// ---- multi-hit ray queries on the host (rt_scene_multihit_host; include/rt_mi355x.h: rt_multihit_query) -------------------------------------
+namespace {
+struct RayHit {
+    float t, u, v;
+    uint32_t tri;
+};
+inline bool hit_before(float t, uint32_t tri, float bt, uint32_t btri) { return t < bt || (t == bt && tri < btri); }
+inline float dot_f(const float a[3], const float b[3]) { return std::fma(a[2], b[2], std::fma(a[1], b[1], a[0] * b[0])); }
+inline void cross_f(const float a[3], const float b[3], float r[3]) {
+    r[0] = std::fma(a[1], b[2], -(a[2] * b[1])), r[1] = std::fma(a[2], b[0], -(a[0] * b[2])), r[2] = std::fma(a[0], b[1], -(a[1] * b[0]));
+}
+// The candidate of one triangle (v0, e1, e2) for a ray: R5's test as rt_device.h: tri_test_regs states it for the kernels — the fused
+// cross and dot products, the edge tests on the numerators, inv = RN(1 / det), t > kTNear. false: no candidate.
+inline bool ray_candidate(const float v0[3], const float e1[3], const float e2[3], const float o[3], const float d[3], RayHit& c) {
+    float p[3], q[3];
+    cross_f(d, e2, p);
+    const float det = dot_f(e1, p);
+    if (!(det != 0.0f)) return false;
+    const float tv[3] = {o[0] - v0[0], o[1] - v0[1], o[2] - v0[2]};
+    cross_f(tv, e1, q);
+    const float sgn = det < 0.0f ? -1.0f : 1.0f;
+    const float un0 = dot_f(tv, p), vn0 = dot_f(d, q);
+    const float un = un0 * sgn, vn = vn0 * sgn;
+    if (!(un >= 0.0f && vn >= 0.0f && un + vn <= std::fabs(det))) return false;
+    const float inv = 1.0f / det;
+    const float t = dot_f(e2, q) * inv;
+    if (!(t > kTNear)) return false;
+    c.t = t, c.u = un0 * inv, c.v = vn0 * inv;
+    return true;
+}
+} // namespace
+
+// A candidate COUNTS iff kTNear < t <= tmax and, with a key, (t, tri) > (after_t, after_tri); the answer is the k first counting
+// candidates in (t, tri) order, every triangle once. use_bvh = 0: every triangle of hs.wverts in index order (e1 = v1 - v0, e2 = v2 - v0, as
+// the records hold them), all counting candidates sorted, the first k. use_bvh = 1: the walk k_multihit makes — the decoded child boxes
+// culled against the BOUND and kept at equal distance, nearest child first; the bound is (tmax, kNoTri) while the list has free slots
+// and (t, tri) of its k-th entry once it is full; a leaf's candidate is taken iff it sorts before the bound, passes the key and is not
+// in the list already (a pre-split triangle sits in several leaves) — counting node visits and triangle tests. k is any number >= 1
+// here (a list longer than a ray's hits never fills: the walk with the bound held at tmax). Rays are not refused: a NaN tmax or key
+// counts nothing.
+int multihit_host(const HostScene& hs, uint32_t n, uint32_t k, const float* org, const float* dir, const float* tmax, const float* after_t,
+                  const uint32_t* after_tri, int use_bvh, float* t_out, float* u_out, float* v_out, uint32_t* tri_out, uint32_t* count_out,
+                  uint64_t* node_visits, uint64_t* tri_tests, std::string& err) {
+    if (use_bvh != 0 && use_bvh != 1) { err = "use_bvh: 0 brute force, 1 the kernel's walk"; return RT_ERR_INVALID; }
+    if (k < 1) { err = "k must be at least 1"; return RT_ERR_INVALID; }
+    if (!after_t != !after_tri) { err = "a resume key is after_t and after_tri, both or neither"; return RT_ERR_INVALID; }
+    if (use_bvh && hs.nodes.empty()) { err = "no tree"; return RT_ERR_INVALID; }
+    const float inf = std::numeric_limits<float>::infinity();
+    const size_t T = hs.wverts.size() / 9;
+    uint64_t visits = 0, tests = 0;
+    std::vector<RayHit> list;
+    std::vector<int32_t> stack;
+    for (uint32_t i = 0; i < n; ++i) {
+        const float o[3] = {org[3 * (size_t)i], org[3 * (size_t)i + 1], org[3 * (size_t)i + 2]};
+        const float d[3] = {dir[3 * (size_t)i], dir[3 * (size_t)i + 1], dir[3 * (size_t)i + 2]};
+        const float tm = tmax ? tmax[i] : inf;
+        const float kt = after_t ? after_t[i] : -inf;
+        const uint32_t ktri = after_t ? after_tri[i] : 0u;
+        auto counts = [&](const RayHit& c) { return c.t <= tm && (c.t > kt || (c.t == kt && c.tri > ktri)); };
+        list.clear();
+        if (!use_bvh) {
+            for (size_t j = 0; j < T; ++j) {
+                const float* w = &hs.wverts[9 * j];
+                const float e1[3] = {w[3] - w[0], w[4] - w[1], w[5] - w[2]}, e2[3] = {w[6] - w[0], w[7] - w[1], w[8] - w[2]};
+                RayHit c{0.0f, 0.0f, 0.0f, (uint32_t)j};
+                tests++;
+                if (ray_candidate(w, e1, e2, o, d, c) && counts(c)) list.push_back(c);
+            }
+            std::stable_sort(list.begin(), list.end(), [](const RayHit& a, const RayHit& b) { return hit_before(a.t, a.tri, b.t, b.tri); });
+            if (list.size() > k) list.resize(k);
+        } else {
+            float inv[3];
+            for (int a = 0; a < 3; ++a) inv[a] = 1.0f / (std::fabs(d[a]) < 1e-30f ? std::copysign(1e-30f, d[a]) : d[a]);
+            float bt = tm; // the bound
+            uint32_t btri = kNoTri;
+            stack.clear();
+            int32_t cur = 0;
+            for (;;) {
+                if (cur >= 0) {
+                    visits++;
+                    const BvhNode& nd = hs.nodes[(size_t)cur];
+                    float key[4];
+                    int32_t ch[4];
+                    int m = 0;
+                    for (int c = 0; c < 4; ++c) {
+                        if (nd.child[c] == kChildEmpty) continue;
+                        const Box3 b = child_box(nd, c);
+                        float tn = 0.0f, tf = bt;
+                        for (int a = 0; a < 3; ++a) {
+                            const float t0 = (b.lo[a] - o[a]) * inv[a], t1 = (b.hi[a] - o[a]) * inv[a];
+                            tn = std::max(tn, std::min(t0, t1)), tf = std::min(tf, std::max(t0, t1));
+                        }
+                        if (tn <= tf) key[m] = tn, ch[m] = nd.child[c], m++; // (a box AT the bound stays: a tie at a lower index is behind it)
+                    }
+                    for (int a = 1; a < m; ++a) // nearest first
+                        for (int b = a; b > 0 && key[b] < key[b - 1]; --b) std::swap(key[b], key[b - 1]), std::swap(ch[b], ch[b - 1]);
+                    for (int a = m - 1; a >= 1; --a) stack.push_back(ch[a]);
+                    if (m) { cur = ch[0]; continue; }
+                } else {
+                    const LeafRange leaf = leaf_range(cur);
+                    for (uint32_t r = 0; r < leaf.count; ++r) {
+                        const TriRec& tr = hs.tris[leaf.first + r];
+                        RayHit c{0.0f, 0.0f, 0.0f, tr.global_index};
+                        tests++;
+                        if (!ray_candidate(tr.v0, tr.e1, tr.e2, o, d, c) || !hit_before(c.t, c.tri, bt, btri) || !counts(c)) continue;
+                        size_t at = 0;
+                        bool listed = false;
+                        for (const RayHit& h : list) listed = listed || h.tri == c.tri, at += hit_before(h.t, h.tri, c.t, c.tri) ? 1 : 0;
+                        if (listed) continue;
+                        list.insert(list.begin() + (ptrdiff_t)at, c);
+                        if (list.size() > k) list.pop_back();
+                        if (list.size() == k) bt = list.back().t, btri = list.back().tri;
+                    }
+                }
+                if (stack.empty()) break;
+                cur = stack.back(), stack.pop_back();
+            }
+        }
+        if (count_out) count_out[i] = (uint32_t)list.size();
+        for (uint32_t s = 0; s < k; ++s) {
+            const bool hit = s < list.size();
+            const size_t at = (size_t)i * k + s;
+            if (t_out) t_out[at] = hit ? list[s].t : inf;
+            if (u_out) u_out[at] = hit ? list[s].u : 0.0f;
+            if (v_out) v_out[at] = hit ? list[s].v : 0.0f;
+            if (tri_out) tri_out[at] = hit ? list[s].tri : kNoTri;
+        }
+    }
+    if (node_visits) *node_visits = visits;
+    if (tri_tests) *tri_tests = tests;
+    return RT_OK;
+}
+
 } // namespace rt

@@ -216,6 +216,26 @@ class rt_point_query(C.Structure):
     ]
 
 
+RT_MULTIHIT_MAX = 8
+
+
+class rt_multihit_query(C.Structure):
+    _fields_ = [
+        ("n", C.c_uint32),
+        ("k", C.c_uint32),
+        ("org", C.c_void_p),
+        ("dir", C.c_void_p),
+        ("tmax", C.c_void_p),
+        ("after_t", C.c_void_p),
+        ("after_tri", C.c_void_p),
+        ("t", C.c_void_p),
+        ("u", C.c_void_p),
+        ("v", C.c_void_p),
+        ("tri", C.c_void_p),
+        ("count", C.c_void_p),
+    ]
+
+
 class rt_path_query(C.Structure):
     _fields_ = [
         ("n", C.c_uint32),
@@ -337,6 +357,7 @@ RT_LIGHTMAP_MAX_DILATE = 16
 
 assert C.sizeof(rt_ray_query) == 72
 assert C.sizeof(rt_point_query) == 64
+assert C.sizeof(rt_multihit_query) == 88
 assert C.sizeof(rt_lightmap_params) == 24
 assert C.sizeof(rt_lightmap_stats) == 24
 assert C.sizeof(rt_lightmap_filter_params) == 16
@@ -375,6 +396,11 @@ PROTOTYPES = {
     "rt_closest_points_device": (C.c_int, [C.c_void_p, _P(rt_point_query), C.c_void_p]),
     "rt_scene_closest_host": (C.c_int, [C.c_void_p, C.c_uint32, _P(C.c_float), _P(C.c_float), C.c_int, _P(C.c_float), _P(C.c_float),
                                          _P(C.c_float), _P(C.c_uint32), _P(C.c_float), _P(C.c_uint64), _P(C.c_uint64)]),
+    "rt_trace_rays_multi": (C.c_int, [C.c_void_p, _P(rt_multihit_query)]),
+    "rt_trace_rays_multi_device": (C.c_int, [C.c_void_p, _P(rt_multihit_query), C.c_void_p]),
+    "rt_scene_multihit_host": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, _P(C.c_float), _P(C.c_float), _P(C.c_float), _P(C.c_float),
+                                          _P(C.c_uint32), C.c_int, _P(C.c_float), _P(C.c_float), _P(C.c_float), _P(C.c_uint32), _P(C.c_uint32),
+                                          _P(C.c_uint64), _P(C.c_uint64)]),
     "rt_trace_paths": (C.c_int, [C.c_void_p, _P(rt_path_query)]),
     "rt_trace_paths_device": (C.c_int, [C.c_void_p, _P(rt_path_query), C.c_void_p]),
     "rt_gather_paths": (C.c_int, [C.c_void_p, _P(rt_gather_query)]),

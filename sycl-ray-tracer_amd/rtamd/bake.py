@@ -1,5 +1,7 @@
 """A small vertex baker over gather queries (include/rt_mi355x.h: rt_gather_paths): the diffuse-lobe radiance at every triangle corner of a
-scene. Pure Python over Scene.gather_paths; `albedo x result` is what the renderers show for a diffuse surface's first bounce there."""
+scene. Pure Python over Scene.gather_paths; `albedo x result` is what the renderers show for a diffuse surface's first bounce there.
+Beside it the helpers over the other queries: probe grids and clearance (closest points), reflection lookups, and the crossing count and
+parity along rays (multi-hit queries: crossings, inside_mask)."""
 from __future__ import annotations
 
 import numpy as np
@@ -127,6 +129,29 @@ def distance_grid(scene: Scene, origin, spacing, count, max_dist=None):
     shape = tuple(int(c) for c in np.asarray(count)[::-1])
     out = scene.closest_points(pts, max_dist)
     return out["dist"].reshape(shape), out["tri"].reshape(shape)
+
+
+def crossings(scene: Scene, org, dirs, tmax=None) -> np.ndarray:
+    """The number of surfaces along each ray, (n,) int64: the counting hits of Scene.trace_all (1e-4 < t <= tmax, every triangle once). A
+    ray through an edge two triangles share counts both. On a mesh with ill-conditioned triangles (slivers) the count can be one short for
+    a ray that hits one: trace_all's limit, stated there and in include/rt_mi355x.h."""
+    offsets = scene.trace_all(org, dirs, tmax)[0]
+    return np.diff(offsets)
+
+
+def inside_mask(scene: Scene, points, direction) -> np.ndarray:
+    """Odd crossing parity along one direction from every point, (n,) bool: crossings(points, direction) % 2 == 1. This means "inside" ONLY
+    for a closed mesh, and only for rays that meet no edge and no vertex: an open mesh has no inside, and a ray through a shared edge or a
+    vertex counts each triangle there (two or more for one surface crossing), one that grazes a silhouette edge may count one. Nothing here
+    detects either case; a caller who must know compares two or three directions. A third case flips the parity as well: a ray that hits
+    an ill-conditioned triangle (a sliver) can have that crossing missing (crossings' limit)."""
+    points, direction = np.asarray(points), np.asarray(direction, f32)
+    if points.ndim != 2 or points.shape[1] != 3:
+        raise ValueError("points must be (n, 3)")
+    if direction.shape != (3,):
+        raise ValueError("direction must hold 3 numbers")
+    dirs = np.ascontiguousarray(np.broadcast_to(direction, points.shape))
+    return crossings(scene, points, dirs) % 2 == 1
 
 
 def shade_vertices_from_volume(volume, sd: SceneDesc) -> np.ndarray:

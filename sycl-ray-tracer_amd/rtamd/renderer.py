@@ -192,6 +192,115 @@ class Scene:
         out["node_visits"], out["tri_tests"] = int(nv.value), int(nt.value)
         return out
 
+    @staticmethod
+    def _multi_args(org, dirs, k, tmax, after, k_max):
+        """trace_multi's and multihit_host's arguments checked: org, dirs (n, 3); k an integer 1 .. k_max (None: no upper bound); tmax (n,)
+        or None; after a pair (after_t (n,) floats, after_tri (n,) integers) or None. -> (n, org, dirs, tmax, after_t, after_tri)"""
+        org, dirs = np.asarray(org), np.asarray(dirs)
+        if org.ndim != 2 or org.shape[1] != 3 or dirs.shape != org.shape:
+            raise ValueError("org and dirs must both be (n, 3)")
+        n = org.shape[0]
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 1 or (k_max is not None and k > k_max):
+            raise ValueError(f"k must be an integer from 1 to {k_max}" if k_max is not None else "k must be an integer, at least 1")
+        org, dirs = np.ascontiguousarray(org, np.float32), np.ascontiguousarray(dirs, np.float32)
+        if tmax is not None:
+            tmax = np.asarray(tmax)
+            if tmax.shape != (n,) or tmax.dtype.kind not in "fiu":
+                raise ValueError("tmax must hold one number per ray, shape (n,)")
+            tmax = np.ascontiguousarray(tmax, np.float32)
+        at = atri = None
+        if after is not None:
+            if not isinstance(after, (tuple, list)) or len(after) != 2:
+                raise ValueError("after must be the pair (after_t, after_tri)")
+            at, atri = np.asarray(after[0]), np.asarray(after[1])
+            if at.shape != (n,) or at.dtype.kind != "f" or atri.shape != (n,) or atri.dtype.kind not in "iu":
+                raise ValueError("after must be (after_t (n,) floats, after_tri (n,) integers)")
+            at, atri = np.ascontiguousarray(at, np.float32), np.ascontiguousarray(atri).astype(np.uint32)
+        return n, org, dirs, tmax, at, atri
+
+    def trace_multi(self, org: np.ndarray, dirs: np.ndarray, k: int, tmax=None, after=None) -> dict:
+        """rt_trace_rays_multi on host arrays: the k nearest counting hits of every ray in ascending (t, triangle index) order. org, dirs
+        (n, 3); k 1 .. abi.RT_MULTIHIT_MAX; tmax (n,) or None (+inf); after = (after_t (n,), after_tri (n,)) or None: only hits with
+        (t, tri) > (after_t, after_tri) count — the key of a page's last slot continues it. Returns {"t", "u", "v": (n, k) float32, "tri":
+        (n, k) uint32, "count": (n,) uint32}; the slots past count hold t = +inf, u = v = 0, tri = 0xFFFFFFFF (include/rt_mi355x.h:
+        rt_multihit_query)."""
+        n, org, dirs, tmax, at, atri = self._multi_args(org, dirs, k, tmax, after, abi.RT_MULTIHIT_MAX)
+        k = int(k)
+        out = {"t": np.zeros((n, k), np.float32), "u": np.zeros((n, k), np.float32), "v": np.zeros((n, k), np.float32),
+               "tri": np.zeros((n, k), np.uint32), "count": np.zeros(n, np.uint32)}
+        q = abi.rt_multihit_query(n=n, k=k, org=org.ctypes.data, dir=dirs.ctypes.data, tmax=None if tmax is None else tmax.ctypes.data,
+                                  after_t=None if at is None else at.ctypes.data, after_tri=None if atri is None else atri.ctypes.data)
+        for name, a in out.items():
+            setattr(q, name, a.ctypes.data)
+        abi.check(self._lib.rt_trace_rays_multi(self.h, C.byref(q)), self._lib)
+        return out
+
+    def trace_multi_device(self, n: int, k: int, d_org: int, d_dir: int, d_tmax: int = 0, d_after_t: int = 0, d_after_tri: int = 0, d_t: int = 0,
+                           d_u: int = 0, d_v: int = 0, d_tri: int = 0, d_count: int = 0, stream: int = 0) -> None:
+        """rt_trace_rays_multi_device on DEVICE pointers (e.g. torch .data_ptr()), enqueued on `stream`; 0 = NULL (no tmax / no key / output
+        not written). The outputs hold n * k entries, ray-major. Rejected rays are marked: every slot t = NaN and tri = abi.RT_TRI_REJECTED,
+        count = 0."""
+        q = abi.rt_multihit_query(n=int(n), k=int(k), org=d_org or None, dir=d_dir or None, tmax=d_tmax or None, after_t=d_after_t or None,
+                                  after_tri=d_after_tri or None, t=d_t or None, u=d_u or None, v=d_v or None, tri=d_tri or None,
+                                  count=d_count or None)
+        abi.check(self._lib.rt_trace_rays_multi_device(self.h, C.byref(q), C.c_void_p(stream or None)), self._lib)
+
+    def multihit_host(self, org: np.ndarray, dirs: np.ndarray, k: int, tmax=None, after=None, use_bvh: bool = False, slots: bool = True) -> dict:
+        """rt_scene_multihit_host (host diagnostic, needs no GPU): the same query by brute force over the triangles (use_bvh False) or by
+        the kernel's walk of the tree, counted. k is any integer >= 1 here. Returns trace_multi's arrays and "node_visits", "tri_tests";
+        slots = False: only "count" and the two counters (the slot arrays are not allocated: a large k)."""
+        n, org, dirs, tmax, at, atri = self._multi_args(org, dirs, k, tmax, after, None)
+        k = int(k)
+        out = {"count": np.zeros(n, np.uint32)}
+        if slots:
+            out.update({"t": np.zeros((n, k), np.float32), "u": np.zeros((n, k), np.float32), "v": np.zeros((n, k), np.float32),
+                        "tri": np.zeros((n, k), np.uint32)})
+        fp = lambda name: abi.fptr(out[name]) if name in out else None
+        nv, nt = C.c_uint64(0), C.c_uint64(0)
+        abi.check(self._lib.rt_scene_multihit_host(self.h, n, k, abi.fptr(org), abi.fptr(dirs), abi.fptr(tmax) if tmax is not None else None,
+                                                   abi.fptr(at) if at is not None else None, abi.u32ptr(atri) if atri is not None else None,
+                                                   1 if use_bvh else 0, fp("t"), fp("u"), fp("v"), abi.u32ptr(out["tri"]) if slots else None,
+                                                   abi.u32ptr(out["count"]), C.byref(nv), C.byref(nt)), self._lib)
+        out["node_visits"], out["tri_tests"] = int(nv.value), int(nt.value)
+        return out
+
+    def trace_all(self, org: np.ndarray, dirs: np.ndarray, tmax=None, page: int = 8, max_hits: int | None = None):
+        """Every counting hit of every ray, in (t, triangle index) order: pages of `page` hits (trace_multi), each continued with the key of
+        its last slot for the rays that filled it, until every ray is exhausted or holds max_hits hits. Returns CSR arrays (offsets (n + 1,)
+        int64, t, u, v float32, tri uint32): ray i's hits are [offsets[i], offsets[i + 1]). A host-only scene (device < 0) pages through
+        multihit_host's brute force instead: it has no device to ask.
+        The contract's limit (include/rt_mi355x.h: rt_multihit_query) holds here too: on a device scene a hit on an ill-conditioned
+        triangle — a sliver whose fp32 t lies more than half the boxes' padding in front of its true t — can be missing from a ray's list
+        when tmax or a page's last entry lies between the two. Every hit listed is right and listed once; the brute force has no limit."""
+        n, org, dirs, tmax, _, _ = self._multi_args(org, dirs, page, tmax, None, abi.RT_MULTIHIT_MAX)
+        if max_hits is not None and (isinstance(max_hits, bool) or not isinstance(max_hits, (int, np.integer)) or max_hits < 1):
+            raise ValueError("max_hits must be an integer, at least 1, or None")
+        call = self.trace_multi if self.device >= 0 else self.multihit_host
+        active, key, pages = np.arange(n), None, []
+        total = np.zeros(n, np.int64)
+        while len(active):
+            out = call(org[active], dirs[active], page, None if tmax is None else tmax[active], key)
+            cnt = out["count"].astype(np.int64)
+            if max_hits is not None:
+                cnt = np.minimum(cnt, max_hits - total[active])
+            pages.append((active, total[active].copy(), cnt, out))
+            total[active] += cnt
+            more = out["count"] == page
+            if max_hits is not None:
+                more &= total[active] < max_hits
+            key = (out["t"][more, page - 1], out["tri"][more, page - 1])
+            active = active[more]
+        offsets = np.zeros(n + 1, np.int64)
+        np.cumsum(total, out=offsets[1:])
+        res = {name: np.zeros(int(offsets[-1]), np.uint32 if name == "tri" else np.float32) for name in ("t", "u", "v", "tri")}
+        for rays, start, cnt, out in pages:
+            slot = np.arange(page)[None, :]
+            take = slot < cnt[:, None]
+            at = (offsets[rays] + start)[:, None] + slot
+            for name, a in res.items():
+                a[at[take]] = out[name][take]
+        return offsets, res["t"], res["u"], res["v"], res["tri"]
+
     def _paths(self, call, query, names, fields, what, in0, in1, rng, max_depth, samples, rr_start) -> dict:
         """trace_paths and gather_paths: two (n, 3) float32 inputs (`names` in the messages, `fields` of `query`) and one xorshift32 state
         per ray or entry (`what`), through the host-array entry point `call`."""

@@ -292,6 +292,59 @@ int rt_closest_points_device(rt_scene* scene, const rt_point_query* q, void* str
 int rt_scene_closest_host(const rt_scene* scene, uint32_t n, const float* pos, const float* max_dist2, int use_bvh, float* dist2, float* u,
                           float* v, uint32_t* tri, float* point, uint64_t* node_visits, uint64_t* tri_tests);
 
+/* ---- k-nearest closest-point queries: the k nearest triangles of every point, resumable (the contact set of a dynamic object or a
+ * particle, "what is near this probe or this texel", smooth distance fields blended over the k nearest, every triangle within a radius:
+ * the broad-phase question). rt_closest_points answers with one triangle, cannot exclude one, and no radius separates triangles that
+ * tie in dist2 — coplanar neighbours share an edge's or a vertex's closest point, so ties are the common case.
+ * The contract. Triangle j's candidate (dist2, u, v) for point i is rt_closest_points' text above on the record (v0, v1 - v0, v2 - v0).
+ * The candidate COUNTS iff
+ *     dist2 <= max_dist2[i]   and, where a resume key is given,   dist2 > after_dist2[i] || (dist2 == after_dist2[i] && j > after_tri[i])
+ * — (dist2, j) > (after_dist2, after_tri) lexicographically. A NaN dist2 never counts. The answer for point i is the k smallest counting
+ * candidates in ascending (dist2, j) order, in slots i * k .. i * k + k - 1 of dist2, u, v, tri (point-major). Every triangle index appears
+ * at most once. count[i] is the number of slots filled; the slots past it hold rt_closest_points' miss: dist2 = +inf, u = v = 0, tri =
+ * 0xFFFFFFFF. A slot is filled iff its tri is not 0xFFFFFFFF (a dist2 that overflowed to +inf counts under max_dist2 = +inf).
+ * The result is the sorted brute force over all triangles, bit for bit: the tree only culls, against a bound that is max_dist2 while a
+ * slot is free and the k-th entry's dist2 afterwards, by rt_closest_points' own rule. That rule leans on the candidate's underestimate
+ * bound alone, which holds for slivers too: unlike rt_trace_rays_multi this query has no conditioning limit.
+ *   max_dist2 == NULL means +inf for every entry; a negative max_dist2 counts nothing (-0.0 admits dist2 == 0), as for rt_closest_points.
+ *   k = 1, no key:  the slot is rt_closest_points' dist2, u, v, tri bit for bit.
+ *   Paging:         a page of k continued with the key (dist2, tri) of its last slot lists every counting triangle exactly once; the pages
+ *                   concatenated equal one call with a larger k. The miss slot (+inf, 0xFFFFFFFF) is a key behind which nothing counts.
+ *   Exhaustion:     a point with count < k has no further counting triangle.
+ *   Range:          with max_dist2 = r * r the pages together are exactly the set { j : dist2_j <= r * r }.
+ * There is no `point` output: r = (ap - u*e1) - v*e2 is a function of the point, the record, u and v alone, so a caller who has the
+ * vertices re-forms point = p - r exactly (rtamd.bake.contact_points), and dot(r, r) is the listed dist2 bit for bit.
+ * Rejected entries: a pos outside the contract range or not finite (rt_intersect_batch), a NaN max_dist2, a NaN after_dist2.
+ * rt_closest_points_multi returns RT_ERR_INVALID naming the first of them and writes nothing; rt_closest_points_multi_device marks each
+ * instead — all k slots dist2 = NaN and tri = RT_TRI_REJECTED (u, v unwritten), count = 0 — and answers the others.
+ * Refusals, in this order: RT_ERR_INVALID for a NULL scene or query; n == 0 is RT_OK, nothing launched; then RT_ERR_INVALID for k outside
+ * 1 .. RT_NEAREST_MAX, NULL pos, after_dist2 without after_tri or the reverse, every output NULL; RT_ERR_NO_DEVICE for a host-only scene
+ * comes last. Any output may be NULL: it is not written.
+ * rt_closest_points_multi takes host arrays, stages them through device buffers, runs on the null stream and synchronises.
+ * rt_closest_points_multi_device takes device arrays and behaves as rt_closest_points_device does: no allocation, no synchronisation, no
+ * host copy; it shares the scene's cursors and per-stream event with the other queries, and rt_scene_update waits for it. */
+#define RT_NEAREST_MAX 8
+typedef struct rt_nearest_query {
+    uint32_t n, k;                        /* k in 1..RT_NEAREST_MAX, the same for every point of the call  */
+    const float *pos;                     /* 3n, xyz per point                                             */
+    const float *max_dist2;               /* n squared radii, or NULL = +inf                               */
+    const float *after_dist2;             /* n, or NULL = no key                                           */
+    const uint32_t *after_tri;            /* n; required iff after_dist2 is given                          */
+    float *dist2, *u, *v; uint32_t *tri;  /* n*k each, point-major; any may be NULL, not all five outputs  */
+    uint32_t *count;                      /* n                                                             */
+} rt_nearest_query;
+int rt_closest_points_multi(rt_scene* scene, const rt_nearest_query* q);
+int rt_closest_points_multi_device(rt_scene* scene, const rt_nearest_query* q, void* stream);
+/* Diagnostic, host only (works on a scene built with device < 0; brings the host copy of an updated device scene up to date first): the
+ * same queries on the host. use_bvh = 0: the sorted brute force over all triangles in index order. use_bvh = 1: the walk the kernel
+ * makes — the decoded child boxes culled against the moving bound, (max_dist2, 0xFFFFFFFF) while the list has free slots and (dist2, tri)
+ * of its k-th entry once it is full — counting node visits and triangle tests (either may be NULL). Entries are not refused here (a NaN
+ * max_dist2 or key counts nothing), k is any number >= 1 (a list longer than a point's counting triangles never fills: the walk with the
+ * bound held at max_dist2), any output may be NULL. */
+int rt_scene_nearest_host(const rt_scene* scene, uint32_t n, uint32_t k, const float* pos, const float* max_dist2, const float* after_dist2,
+                          const uint32_t* after_tri, int use_bvh, float* dist2, float* u, float* v, uint32_t* tri, uint32_t* count,
+                          uint64_t* node_visits, uint64_t* tri_tests);
+
 /* ---- Multi-hit ray queries: the k nearest hits of every ray, resumable (wall thickness, every layer along a probe ray, X-ray picking,
  * crossing parity, interval lists). Every other ray entry point answers with at most one surface per ray; restarting a closest-hit query
  * from its hit point is not exact (the near limit swallows close layers, hits at equal t on shared edges are lost).

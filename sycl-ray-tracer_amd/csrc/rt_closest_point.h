@@ -89,4 +89,14 @@ RT_HD bool closest_better(float dist2, uint32_t index, float best, uint32_t best
 constexpr float kClosestSlack = 0.9999f;
 RT_HD bool closest_enters(float lb, float best) { return lb * kClosestSlack <= best; }
 
+// ---- the k nearest (include/rt_mi355x.h: rt_nearest_query; rt_nearest.hip: k_nearest, scene_check.cpp: nearest_host) -------
+// The same candidate, sorted. A candidate COUNTS iff dist2 <= max_dist2 and, with a resume key, (dist2, index) > (after_dist2, after_tri)
+// lexicographically; a NaN dist2 never counts. The answer is the k smallest counting candidates in ascending (dist2, index) order, each
+// triangle once; unfilled slots hold the miss (+inf, 0, 0, 0xFFFFFFFF). Both walks keep `best` as the BOUND: (max_dist2, 0xFFFFFFFF)
+// while a slot is free, (dist2, index) of the k-th entry once none is; a candidate enters the list iff closest_better says so against the
+// bound, it lies behind the key and its index is in no slot. The cull is closest_enters against that bound, unchanged: the argument above
+// is about the candidate's underestimate of d_true and says nothing of where `best` came from, so it holds for every value the bound
+// takes on its way down — a triangle that belongs among the k nearest has sqrt(dist2) <= sqrt(bound) at every moment of the walk, and its
+// boxes are entered. The key filters candidates and culls no box.
+
 } // namespace rt

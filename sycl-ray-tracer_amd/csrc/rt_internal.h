@@ -21,8 +21,10 @@
 //   rt_closest.hip closest-point queries, the nearest triangle to caller-supplied points (rt_closest_points[_device], rt_scene_closest_host) and their kernel
 //   rt_closest_point.h the contract of the closest-point queries, one fp32 text for the kernel and the host walk (scene_check.cpp: closest_host)
 //   rt_multihit.hip multi-hit ray queries, the k nearest hits of every ray, resumable (rt_trace_rays_multi[_device], rt_scene_multihit_host) and their kernels
-//   rt_query_launch.h what those five units (rt_query.hip and the last four) share on the host: grid sizing, the launch on the shared cursors, the host forms' staging, the path / gather checks
-//   rt_path_rounds.h  the kernel body rt_path_query.hip and rt_path_gather.hip share (path_rounds<E>); rt_query_frame.h the one rt_query.hip, rt_closest.hip and rt_multihit.hip share (query_frame<P>) and the claim of entries, shared by all five
+//   rt_nearest.hip k-nearest closest-point queries, the k nearest triangles of every point, resumable (rt_closest_points_multi[_device], rt_scene_nearest_host) and their kernels
+//   rt_closest_step.h the start of a point traversal and its inner step, shared by rt_closest.hip and rt_nearest.hip; rt_hit_list.h the sorted list in registers (rt_nearest.hip's; rt_multihit.hip keeps its own text of the same list)
+//   rt_query_launch.h what those six units (rt_query.hip and the last five) share on the host: grid sizing, the launch on the shared cursors, the host forms' staging, the path / gather checks
+//   rt_path_rounds.h  the kernel body rt_path_query.hip and rt_path_gather.hip share (path_rounds<E>); rt_query_frame.h the one rt_query.hip, rt_closest.hip, rt_multihit.hip and rt_nearest.hip share (query_frame<P>) and the claim of entries, shared by all six
 //   rt_lightmap.hip lightmap baking around one gather query (rt_lightmap_*): UV coverage, texel guides, resolve and dilation kernels
 #pragma once
 #include <hip/hip_runtime.h>
@@ -177,8 +179,9 @@ constexpr uint32_t kQueryCursorBytes = 32u * 128u;
 constexpr uint32_t kQueryChunk = 64, kQueryHeads = 32, kQueryHeadStride = 16; // (stride in 8-byte words)
 static_assert(kQueryHeads * kQueryHeadStride * 8u == kQueryCursorBytes, "the scene's cursor block holds one 128-byte line per shard");
 // the query kernels, each with a persistent grid of its own (rt_scene::query_grid). The sixth kind, kQueryKindMulti, has three kernels of
-// different occupancy (rt_multihit.hip: k_multihit<2>, <4>, <8>) and so three grids: kQueryKindMulti + 0, + 1, + 2
-enum QueryKind : int { kQueryKindClosest = 0, kQueryKindAny = 1, kQueryKindPath = 2, kQueryKindGather = 3, kQueryKindPoint = 4, kQueryKindMulti = 5, kQueryKinds = 8 };
+// different occupancy (rt_multihit.hip: k_multihit<2>, <4>, <8>) and so three grids: kQueryKindMulti + 0, + 1, + 2; so has the seventh,
+// kQueryKindNearest (rt_nearest.hip: k_nearest<2>, <4>, <8>): kQueryKindNearest + 0, + 1, + 2
+enum QueryKind : int { kQueryKindClosest = 0, kQueryKindAny = 1, kQueryKindPath = 2, kQueryKindGather = 3, kQueryKindPoint = 4, kQueryKindMulti = 5, kQueryKindNearest = 8, kQueryKinds = 11 };
 
 struct rt_scene {
     HostScene hs;

@@ -106,6 +106,13 @@ int count_visits(const HostScene& hs, uint32_t n, const float* org, const float*
 int closest_host(const HostScene& hs, uint32_t n, const float* pos, const float* max_dist2, int use_bvh, float* dist2, float* u, float* v, uint32_t* tri,
                  float* point, uint64_t* node_visits, uint64_t* tri_tests, std::string& err);
 
+// Diagnostic used by rt_scene_nearest_host: k-nearest closest-point queries on the host, by brute force over the triangles in index order
+// (use_bvh 0) or by the walk k_nearest makes, counted (use_bvh 1). Outputs hold k slots per point; any may be NULL; max_dist2 NULL = +inf;
+// after_dist2 NULL = no key.
+int nearest_host(const HostScene& hs, uint32_t n, uint32_t k, const float* pos, const float* max_dist2, const float* after_dist2,
+                 const uint32_t* after_tri, int use_bvh, float* dist2, float* u, float* v, uint32_t* tri, uint32_t* count, uint64_t* node_visits,
+                 uint64_t* tri_tests, std::string& err);
+
 // Diagnostic used by rt_scene_multihit_host: multi-hit ray queries on the host, by brute force over the triangles in index order (use_bvh 0)
 // or by the walk k_multihit makes, counted (use_bvh 1). Outputs hold k slots per ray; any may be NULL; tmax NULL = +inf; after_t NULL = no key.
 int multihit_host(const HostScene& hs, uint32_t n, uint32_t k, const float* org, const float* dir, const float* tmax, const float* after_t,

@@ -419,6 +419,111 @@ int closest_host(const HostScene& hs, uint32_t n, const float* pos, const float*
     return RT_OK;
 }
 
+// ---- k-nearest closest-point queries on the host (rt_scene_nearest_host; include/rt_mi355x.h: rt_nearest_query) ----------------------------
+// A candidate (rt_closest_point.h's one text) COUNTS iff dist2 <= max_dist2 and, with a key, (dist2, tri) > (after_dist2, after_tri); a NaN
+// dist2 never counts. The answer is the k first counting candidates in (dist2, tri) order, every triangle once. use_bvh = 0: every
+// triangle of hs.wverts in index order (e1 = v1 - v0, e2 = v2 - v0, as the records hold them), all counting candidates sorted, the first k.
+// use_bvh = 1: the walk k_nearest makes — closest_host's inner step (the decoded child boxes, closest_enters, the sorting network, the
+// others stacked far to near) against the BOUND, which is (max_dist2, kNoTri) while the list has free slots and (dist2, tri) of its k-th
+// entry once it is full; a leaf's candidate is taken iff it passes closest_better against the bound, passes the key and is not in the list
+// already (a pre-split triangle sits in several leaves) — counting node visits and triangle tests. k is any number >= 1 here (a list
+// longer than a point's counting triangles never fills: the walk with the bound held at max_dist2). Entries are not refused: a NaN
+// max_dist2 or key counts nothing.
+int nearest_host(const HostScene& hs, uint32_t n, uint32_t k, const float* pos, const float* max_dist2, const float* after_dist2,
+                 const uint32_t* after_tri, int use_bvh, float* dist2_out, float* u_out, float* v_out, uint32_t* tri_out, uint32_t* count_out,
+                 uint64_t* node_visits, uint64_t* tri_tests, std::string& err) {
+    if (use_bvh != 0 && use_bvh != 1) { err = "use_bvh: 0 brute force, 1 the kernel's walk"; return RT_ERR_INVALID; }
+    if (k < 1) { err = "k must be at least 1"; return RT_ERR_INVALID; }
+    if (!after_dist2 != !after_tri) { err = "a resume key is after_dist2 and after_tri, both or neither"; return RT_ERR_INVALID; }
+    if (use_bvh && hs.nodes.empty()) { err = "no tree"; return RT_ERR_INVALID; }
+    struct Near {
+        float dist2, u, v;
+        uint32_t tri;
+    };
+    const float inf = std::numeric_limits<float>::infinity();
+    const size_t T = hs.wverts.size() / 9;
+    uint64_t visits = 0, tests = 0;
+    std::vector<Near> list;
+    std::vector<int32_t> stack;
+    for (uint32_t i = 0; i < n; ++i) {
+        const float p[3] = {pos[3 * (size_t)i], pos[3 * (size_t)i + 1], pos[3 * (size_t)i + 2]};
+        const float md = max_dist2 ? max_dist2[i] : inf;
+        const float kd = after_dist2 ? after_dist2[i] : -inf;
+        const uint32_t ktri = after_dist2 ? after_tri[i] : 0u;
+        auto behind_key = [&](float d2, uint32_t tri) { return d2 > kd || (d2 == kd && tri > ktri); };
+        list.clear();
+        if (!use_bvh) {
+            for (size_t j = 0; j < T; ++j) {
+                const float* w = &hs.wverts[9 * j];
+                const float e1[3] = {w[3] - w[0], w[4] - w[1], w[5] - w[2]}, e2[3] = {w[6] - w[0], w[7] - w[1], w[8] - w[2]};
+                tests++;
+                const ClosestPoint c = closest_point_on_record(p, w, e1, e2);
+                if (c.dist2 <= md && behind_key(c.dist2, (uint32_t)j)) list.push_back(Near{c.dist2, c.u, c.v, (uint32_t)j});
+            }
+            std::stable_sort(list.begin(), list.end(), [](const Near& a, const Near& b) { return closest_better(a.dist2, a.tri, b.dist2, b.tri); });
+            if (list.size() > k) list.resize(k);
+        } else {
+            float best = md; // the bound
+            uint32_t best_tri = kNoTri;
+            stack.clear();
+            int32_t cur = 0;
+            for (;;) {
+                if (cur >= 0) {
+                    visits++;
+                    const BvhNode& nd = hs.nodes[(size_t)cur];
+                    float key[4];
+                    int32_t ch[4];
+                    for (int c = 0; c < 4; ++c) {
+                        ch[c] = nd.child[c], key[c] = inf;
+                        if (nd.child[c] == kChildEmpty) continue; // (its inverted box gives a finite lb: the word is what says it is absent)
+                        float lb = 0.0f;
+                        for (int a = 0; a < 3; ++a) {
+                            const float lo = child_plane(nd, c, a, 0), hi = child_plane(nd, c, a, 1);
+                            const float e = std::max(std::max(lo - p[a], p[a] - hi), 0.0f);
+                            lb = std::fma(e, e, lb);
+                        }
+                        if (closest_enters(lb, best)) key[c] = std::min(lb, std::numeric_limits<float>::max()); // (an lb that overflowed is still a key)
+                    }
+                    auto ce = [&](int a, int b) { if (key[b] < key[a]) std::swap(key[a], key[b]), std::swap(ch[a], ch[b]); };
+                    ce(0, 1), ce(2, 3), ce(0, 2), ce(1, 3), ce(1, 2);
+                    for (int c = 3; c >= 1; --c)
+                        if (key[c] < inf) stack.push_back(ch[c]);
+                    if (key[0] < inf) { cur = ch[0]; continue; }
+                } else {
+                    const LeafRange leaf = leaf_range(cur);
+                    for (uint32_t r = 0; r < leaf.count; ++r) {
+                        const TriRec& tr = hs.tris[leaf.first + r];
+                        tests++;
+                        const ClosestPoint c = closest_point_on_record(p, tr.v0, tr.e1, tr.e2);
+                        if (!closest_better(c.dist2, tr.global_index, best, best_tri) || !behind_key(c.dist2, tr.global_index)) continue;
+                        size_t at = 0;
+                        bool listed = false;
+                        for (const Near& h : list) listed = listed || h.tri == tr.global_index, at += closest_better(h.dist2, h.tri, c.dist2, tr.global_index) ? 1 : 0;
+                        if (listed) continue;
+                        list.insert(list.begin() + (ptrdiff_t)at, Near{c.dist2, c.u, c.v, tr.global_index});
+                        if (list.size() > k) list.pop_back();
+                        if (list.size() == k) best = list.back().dist2, best_tri = list.back().tri;
+                    }
+                }
+                if (stack.empty()) break;
+                cur = stack.back(), stack.pop_back();
+            }
+        }
+        if (count_out) count_out[i] = (uint32_t)list.size();
+        for (uint32_t s = 0; s < k; ++s) {
+            const bool hit = s < list.size();
+            const size_t at = (size_t)i * k + s;
+            if (dist2_out) dist2_out[at] = hit ? list[s].dist2 : inf;
+            if (u_out) u_out[at] = hit ? list[s].u : 0.0f;
+            if (v_out) v_out[at] = hit ? list[s].v : 0.0f;
+            if (tri_out) tri_out[at] = hit ? list[s].tri : kNoTri;
+        }
+    }
+    if (node_visits) *node_visits = visits;
+    if (tri_tests) *tri_tests = tests;
+    return RT_OK;
+}
+
 // ---- multi-hit ray queries on the host (rt_scene_multihit_host; include/rt_mi355x.h: rt_multihit_query) -------------------------------------
 namespace {
 struct RayHit {

@@ -236,6 +236,25 @@ class rt_multihit_query(C.Structure):
     ]
 
 
+RT_NEAREST_MAX = 8
+
+
+class rt_nearest_query(C.Structure):
+    _fields_ = [
+        ("n", C.c_uint32),
+        ("k", C.c_uint32),
+        ("pos", C.c_void_p),
+        ("max_dist2", C.c_void_p),
+        ("after_dist2", C.c_void_p),
+        ("after_tri", C.c_void_p),
+        ("dist2", C.c_void_p),
+        ("u", C.c_void_p),
+        ("v", C.c_void_p),
+        ("tri", C.c_void_p),
+        ("count", C.c_void_p),
+    ]
+
+
 class rt_path_query(C.Structure):
     _fields_ = [
         ("n", C.c_uint32),
@@ -358,6 +377,7 @@ RT_LIGHTMAP_MAX_DILATE = 16
 assert C.sizeof(rt_ray_query) == 72
 assert C.sizeof(rt_point_query) == 64
 assert C.sizeof(rt_multihit_query) == 88
+assert C.sizeof(rt_nearest_query) == 80
 assert C.sizeof(rt_lightmap_params) == 24
 assert C.sizeof(rt_lightmap_stats) == 24
 assert C.sizeof(rt_lightmap_filter_params) == 16
@@ -401,6 +421,11 @@ PROTOTYPES = {
     "rt_scene_multihit_host": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, _P(C.c_float), _P(C.c_float), _P(C.c_float), _P(C.c_float),
                                           _P(C.c_uint32), C.c_int, _P(C.c_float), _P(C.c_float), _P(C.c_float), _P(C.c_uint32), _P(C.c_uint32),
                                           _P(C.c_uint64), _P(C.c_uint64)]),
+    "rt_closest_points_multi": (C.c_int, [C.c_void_p, _P(rt_nearest_query)]),
+    "rt_closest_points_multi_device": (C.c_int, [C.c_void_p, _P(rt_nearest_query), C.c_void_p]),
+    "rt_scene_nearest_host": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, _P(C.c_float), _P(C.c_float), _P(C.c_float), _P(C.c_uint32),
+                                         C.c_int, _P(C.c_float), _P(C.c_float), _P(C.c_float), _P(C.c_uint32), _P(C.c_uint32),
+                                         _P(C.c_uint64), _P(C.c_uint64)]),
     "rt_trace_paths": (C.c_int, [C.c_void_p, _P(rt_path_query)]),
     "rt_trace_paths_device": (C.c_int, [C.c_void_p, _P(rt_path_query), C.c_void_p]),
     "rt_gather_paths": (C.c_int, [C.c_void_p, _P(rt_gather_query)]),

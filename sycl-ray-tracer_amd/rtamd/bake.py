@@ -1,7 +1,8 @@
 """A small vertex baker over gather queries (include/rt_mi355x.h: rt_gather_paths): the diffuse-lobe radiance at every triangle corner of a
 scene. Pure Python over Scene.gather_paths; `albedo x result` is what the renderers show for a diffuse surface's first bounce there.
 Beside it the helpers over the other queries: probe grids and clearance (closest points), reflection lookups, and the crossing count and
-parity along rays (multi-hit queries: crossings, inside_mask)."""
+parity along rays (multi-hit queries: crossings, inside_mask), and the triangles within a radius and their contact points (k-nearest
+closest-point queries: triangles_within, contact_points)."""
 from __future__ import annotations
 
 import numpy as np
@@ -129,6 +130,44 @@ def distance_grid(scene: Scene, origin, spacing, count, max_dist=None):
     shape = tuple(int(c) for c in np.asarray(count)[::-1])
     out = scene.closest_points(pts, max_dist)
     return out["dist"].reshape(shape), out["tri"].reshape(shape)
+
+
+def triangles_within(scene: Scene, pos, radius):
+    """The triangles within `radius` (one number or one per point) of every point, CSR (offsets (n + 1,) int64, tri uint32): point i's are
+    tri[offsets[i]:offsets[i + 1]], in ascending (dist2, index) order — the set { j : dist2_j <= radius * radius } of Scene.closest_all,
+    the radius squared in fp32."""
+    if radius is None:
+        raise ValueError("radius must be a number or one per point")
+    out = scene.closest_all(pos, radius)
+    return out[0], out[4]
+
+
+def contact_points(wverts, pos, u, v, tri) -> np.ndarray:
+    """The closest points that go with a k-nearest answer, re-formed from the vertices: the contract's point = p - r with
+    r = (ap - u*e1) - v*e2 on the record (v0, v1 - v0, v2 - v0), every operation one fp32 operation (include/rt_mi355x.h:
+    rt_point_query). wverts (T, 3, 3) float32 world vertices in global triangle order (vertex_points(sd)[0]); pos (n, 3); u, v, tri (n,)
+    or (n, k) as Scene.closest_points_multi returns them. -> (n, 3) or (n, k, 3) float32, NaN where tri is 0xFFFFFFFF (a miss)."""
+    wverts, pos = np.asarray(wverts), np.asarray(pos)
+    u, v, tri = np.asarray(u), np.asarray(v), np.asarray(tri)
+    if wverts.ndim != 3 or wverts.shape[1:] != (3, 3):
+        raise ValueError("wverts must be (T, 3, 3)")
+    if pos.ndim != 2 or pos.shape[1] != 3:
+        raise ValueError("pos must be (n, 3)")
+    if tri.ndim not in (1, 2) or tri.shape[0] != pos.shape[0] or u.shape != tri.shape or v.shape != tri.shape or tri.dtype.kind not in "iu":
+        raise ValueError("u, v and tri must all be (n,) or (n, k), tri integers")
+    wverts, pos = wverts.astype(f32, copy=False), pos.astype(f32, copy=False)
+    u, v = u.astype(f32, copy=False)[..., None], v.astype(f32, copy=False)[..., None]
+    hit = tri != 0xFFFFFFFF
+    if hit.any() and int(tri[hit].max()) >= len(wverts):
+        raise ValueError("tri holds an index past the last triangle")
+    w = wverts[np.where(hit, tri, 0).astype(np.int64)] if len(wverts) else np.zeros(tri.shape + (3, 3), f32)
+    p = pos if tri.ndim == 1 else pos[:, None, :]
+    ap = p - w[..., 0, :]
+    r = (ap - u * (w[..., 1, :] - w[..., 0, :])) - v * (w[..., 2, :] - w[..., 0, :])
+    with np.errstate(invalid="ignore"):
+        out = np.where(hit[..., None], p - r, f32(np.nan))
+    assert out.dtype == f32
+    return out
 
 
 def crossings(scene: Scene, org, dirs, tmax=None) -> np.ndarray:

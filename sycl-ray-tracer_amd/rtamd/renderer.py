@@ -193,6 +193,142 @@ class Scene:
         return out
 
     @staticmethod
+    def _nearest_args(pos, k, max_dist, after, k_max):
+        """closest_points_multi's, closest_all's and nearest_host's arguments checked: pos (n, 3); k an integer 1 .. k_max (None: no upper
+        bound); max_dist a radius (one number or (n,), none negative) or None; after a pair (after_dist2 (n,) floats, after_tri (n,)
+        integers) or None. -> (n, pos, max_dist2 (the radius squared in fp32) or None, after_dist2, after_tri)"""
+        pos = np.asarray(pos)
+        if pos.ndim != 2 or pos.shape[1] != 3:
+            raise ValueError("pos must be (n, 3)")
+        n = pos.shape[0]
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 1 or (k_max is not None and k > k_max):
+            raise ValueError(f"k must be an integer from 1 to {k_max}" if k_max is not None else "k must be an integer, at least 1")
+        pos = np.ascontiguousarray(pos, np.float32)
+        md2 = None
+        if max_dist is not None:
+            md = np.asarray(max_dist)
+            if md.dtype.kind not in "fiu":
+                raise ValueError("max_dist must be one radius or hold one per point, shape (n,)")
+            md = md.astype(np.float32)
+            if md.ndim == 0:
+                md = np.full(n, md, np.float32)
+            if md.shape != (n,):
+                raise ValueError("max_dist must be one radius or hold one per point, shape (n,)")
+            if (md < 0).any():
+                raise ValueError("max_dist must not be negative")
+            md2 = np.ascontiguousarray(md * md)
+        ad = atri = None
+        if after is not None:
+            if not isinstance(after, (tuple, list)) or len(after) != 2:
+                raise ValueError("after must be the pair (after_dist2, after_tri)")
+            ad, atri = np.asarray(after[0]), np.asarray(after[1])
+            if ad.shape != (n,) or ad.dtype.kind != "f" or atri.shape != (n,) or atri.dtype.kind not in "iu":
+                raise ValueError("after must be (after_dist2 (n,) floats, after_tri (n,) integers)")
+            ad, atri = np.ascontiguousarray(ad, np.float32), np.ascontiguousarray(atri).astype(np.uint32)
+        return n, pos, md2, ad, atri
+
+    def closest_points_multi(self, pos: np.ndarray, k: int, max_dist=None, after=None) -> dict:
+        """rt_closest_points_multi on host arrays: the k nearest counting triangles of every point in ascending (dist2, triangle index)
+        order. pos (n, 3); k 1 .. abi.RT_NEAREST_MAX; max_dist a radius (one number or (n,)), squared here in fp32 as closest_points does,
+        or None (+inf); after = (after_dist2 (n,), after_tri (n,)) or None: only triangles with (dist2, tri) > (after_dist2, after_tri)
+        count — the key of a page's last slot continues it. Returns {"dist2", "dist" (sqrt(dist2)), "u", "v": (n, k) float32, "tri": (n, k)
+        uint32, "count": (n,) uint32}; the slots past count hold dist2 = +inf, u = v = 0, tri = 0xFFFFFFFF (include/rt_mi355x.h:
+        rt_nearest_query). There is no point output: bake.contact_points re-forms it from the vertices."""
+        n, pos, md2, ad, atri = self._nearest_args(pos, k, max_dist, after, abi.RT_NEAREST_MAX)
+        return self._nearest_call(pos, int(k), md2, (ad, atri))
+
+    def _nearest_call(self, pos, k, md2, key) -> dict:
+        """closest_points_multi behind its checks: md2 already SQUARED (closest_all pages with the radius squared once), key = (after_dist2,
+        after_tri), both arrays or both None"""
+        n = len(pos)
+        ad, atri = key
+        out = {"dist2": np.zeros((n, k), np.float32), "u": np.zeros((n, k), np.float32), "v": np.zeros((n, k), np.float32),
+               "tri": np.zeros((n, k), np.uint32), "count": np.zeros(n, np.uint32)}
+        q = abi.rt_nearest_query(n=n, k=k, pos=pos.ctypes.data, max_dist2=None if md2 is None else md2.ctypes.data,
+                                 after_dist2=None if ad is None else ad.ctypes.data, after_tri=None if atri is None else atri.ctypes.data)
+        for name, a in out.items():
+            setattr(q, name, a.ctypes.data)
+        abi.check(self._lib.rt_closest_points_multi(self.h, C.byref(q)), self._lib)
+        out["dist"] = np.sqrt(out["dist2"])
+        return out
+
+    def closest_points_multi_device(self, n: int, k: int, d_pos: int, d_max_dist2: int = 0, d_after_dist2: int = 0, d_after_tri: int = 0,
+                                    d_dist2: int = 0, d_u: int = 0, d_v: int = 0, d_tri: int = 0, d_count: int = 0, stream: int = 0) -> None:
+        """rt_closest_points_multi_device on DEVICE pointers (e.g. torch .data_ptr()), enqueued on `stream`; 0 = NULL (no radius / no key /
+        output not written). d_max_dist2 holds SQUARED radii. The outputs hold n * k entries, point-major. Rejected entries are marked:
+        every slot dist2 = NaN and tri = abi.RT_TRI_REJECTED, count = 0."""
+        q = abi.rt_nearest_query(n=int(n), k=int(k), pos=d_pos or None, max_dist2=d_max_dist2 or None, after_dist2=d_after_dist2 or None,
+                                 after_tri=d_after_tri or None, dist2=d_dist2 or None, u=d_u or None, v=d_v or None, tri=d_tri or None,
+                                 count=d_count or None)
+        abi.check(self._lib.rt_closest_points_multi_device(self.h, C.byref(q), C.c_void_p(stream or None)), self._lib)
+
+    def nearest_host(self, pos: np.ndarray, k: int, max_dist2=None, after=None, use_bvh: bool = False, slots: bool = True) -> dict:
+        """rt_scene_nearest_host (host diagnostic, needs no GPU): the same query by the sorted brute force over the triangles (use_bvh
+        False) or by the kernel's walk of the tree, counted. k is any integer >= 1 here; max_dist2 (n,) SQUARED radii (any value, NaN
+        included: the diagnostic refuses nothing) or None. Returns closest_points_multi's arrays (without "dist") and "node_visits",
+        "tri_tests"; slots = False: only "count" and the two counters (the slot arrays are not allocated: a large k)."""
+        n, pos, _, ad, atri = self._nearest_args(pos, k, None, after, None)
+        k = int(k)
+        md = None
+        if max_dist2 is not None:
+            md = np.ascontiguousarray(max_dist2, np.float32).reshape(-1)
+            if md.shape[0] != n:
+                raise ValueError("max_dist2 must hold one value per point")
+        out = {"count": np.zeros(n, np.uint32)}
+        if slots:
+            out.update({"dist2": np.zeros((n, k), np.float32), "u": np.zeros((n, k), np.float32), "v": np.zeros((n, k), np.float32),
+                        "tri": np.zeros((n, k), np.uint32)})
+        fp = lambda name: abi.fptr(out[name]) if name in out else None
+        nv, nt = C.c_uint64(0), C.c_uint64(0)
+        abi.check(self._lib.rt_scene_nearest_host(self.h, n, k, abi.fptr(pos), abi.fptr(md) if md is not None else None,
+                                                  abi.fptr(ad) if ad is not None else None, abi.u32ptr(atri) if atri is not None else None,
+                                                  1 if use_bvh else 0, fp("dist2"), fp("u"), fp("v"), abi.u32ptr(out["tri"]) if slots else None,
+                                                  abi.u32ptr(out["count"]), C.byref(nv), C.byref(nt)), self._lib)
+        out["node_visits"], out["tri_tests"] = int(nv.value), int(nt.value)
+        return out
+
+    def closest_all(self, pos: np.ndarray, max_dist, page: int = 8, max_items: int | None = None):
+        """Every triangle within max_dist of every point, in (dist2, triangle index) order: pages of `page` triangles
+        (closest_points_multi), each continued with the key of its last slot for the points that filled it, until every point is
+        exhausted or holds max_items triangles. Returns CSR arrays (offsets (n + 1,) int64, dist2, u, v float32, tri uint32): point i's
+        triangles are [offsets[i], offsets[i + 1]). max_dist = None (no radius: every triangle of the scene, for every point) is refused
+        unless max_items is given. A host-only scene (device < 0) pages through nearest_host's brute force instead: it has no device to
+        ask."""
+        n, pos, md2, _, _ = self._nearest_args(pos, page, max_dist, None, abi.RT_NEAREST_MAX)
+        if max_items is not None and (isinstance(max_items, bool) or not isinstance(max_items, (int, np.integer)) or max_items < 1):
+            raise ValueError("max_items must be an integer, at least 1, or None")
+        if max_dist is None and max_items is None:
+            raise ValueError("max_dist = None lists every triangle of the scene for every point: give max_items to bound it")
+        if self.device >= 0:
+            call = lambda p, m, key: self._nearest_call(p, page, m, key)
+        else:
+            call = lambda p, m, key: self.nearest_host(p, page, m, None if key[0] is None else key)
+        active, key, pages = np.arange(n), (None, None), []
+        total = np.zeros(n, np.int64)
+        while len(active):
+            out = call(np.ascontiguousarray(pos[active]), None if md2 is None else np.ascontiguousarray(md2[active]), key)
+            cnt = out["count"].astype(np.int64)
+            if max_items is not None:
+                cnt = np.minimum(cnt, max_items - total[active])
+            pages.append((active, total[active].copy(), cnt, out))
+            total[active] += cnt
+            more = out["count"] == page
+            if max_items is not None:
+                more &= total[active] < max_items
+            key = (np.ascontiguousarray(out["dist2"][more, page - 1]), np.ascontiguousarray(out["tri"][more, page - 1]))
+            active = active[more]
+        offsets = np.zeros(n + 1, np.int64)
+        np.cumsum(total, out=offsets[1:])
+        res = {name: np.zeros(int(offsets[-1]), np.uint32 if name == "tri" else np.float32) for name in ("dist2", "u", "v", "tri")}
+        for pts, start, cnt, out in pages:
+            slot = np.arange(page)[None, :]
+            take = slot < cnt[:, None]
+            at = (offsets[pts] + start)[:, None] + slot
+            for name, a in res.items():
+                a[at[take]] = out[name][take]
+        return offsets, res["dist2"], res["u"], res["v"], res["tri"]
+
+    @staticmethod
     def _multi_args(org, dirs, k, tmax, after, k_max):
         """trace_multi's and multihit_host's arguments checked: org, dirs (n, 3); k an integer 1 .. k_max (None: no upper bound); tmax (n,)
         or None; after a pair (after_t (n,) floats, after_tri (n,) integers) or None. -> (n, org, dirs, tmax, after_t, after_tri)"""

@@ -4,11 +4,13 @@
 // winner rule and the cull — is rt_closest_point.h, shared with the host walk. DESIGN.md §22.)
 // The kernel's body is query_frame (rt_query_frame.h), shared with k_query, with the claim every query kernel shares; the launch and the host
 // form's staging are rt_query_launch.h's; the start of a lane's traversal and the inner step are rt_closest_step.h's, shared with
-// rt_nearest.hip. What is this unit's own: an entry is a point with a max_dist2, and the leaf step.
+// rt_nearest.hip; the whole-leaf read is rt_whole_leaf.h's. What is this unit's own: an entry is a point with a max_dist2, and the
+// candidate of the leaf step.
 #include "rt_query_launch.h"
 #include "rt_query_frame.h"
 #include "rt_closest_point.h"
 #include "rt_closest_step.h"
+#include "rt_whole_leaf.h"
 
 namespace rt {
 
@@ -42,25 +44,8 @@ RT_DEV void closest_test_regs(float4 a, float4 b, float2 c, Trav& T, f3& r) {
     }
 }
 
-// Leaf step: the whole leaf (1-2 records) as trav_leaf<true> reads it — five unconditional 16-byte loads of 80 contiguous bytes (a leaf of
-// one record reads 40 bytes of its neighbour and ignores them; the buffer ends in 48 bytes of padding) — then one or two candidates.
-RT_DEV void closest_leaf(const SceneDev& S, Trav& T, f3& r, const TravStack& stack) {
-    static_assert(kMaxLeafTris == 2 && kTriBytes == 40, "the whole-leaf step reads a leaf as 80 contiguous bytes");
-    const uint32_t code = (uint32_t)~T.cur;
-    const uint32_t first = code >> 2, rem = code & 3u;
-    const uint8_t* p4 = S.tris + (size_t)first * kTriBytes;
-    const float4 l0 = tri_ld4(p4), l1 = tri_ld4(p4 + 16), l2 = tri_ld4(p4 + 32), l3 = tri_ld4(p4 + 48), l4 = tri_ld4(p4 + 64);
-    const bool two = rem != 0u;
-    closest_test_regs(l0, l1, make_float2(l2.x, l2.y), T, r);
-    if (__ballot(two) != 0ull) {
-        if (two) closest_test_regs(make_float4(l2.z, l2.w, l3.x, l3.y), make_float4(l3.z, l3.w, l4.x, l4.y), make_float2(l4.z, l4.w), T, r);
-    }
-    if (lanes(!stack_shallow(stack, T, 0u)) == 0ull) trav_pop_lds(T, stack);
-    else trav_pop(T, stack);
-}
-
 // query_frame's policy (rt_query_frame.h): an entry is a point and its max_dist2, the point inside the contract's range and max_dist2 no
-// NaN; a step is one wave-uniform step kind, an inner or a leaf step, by the ray traversal's vote on trav_classes.
+// NaN; a step is one wave-uniform step kind, an inner or a leaf step, by the ray traversal's vote on trav_classes (rt_whole_leaf.h: vote_step).
 // A popped child is not tested against the winner again (the stack holds words, no keys): its node is visited, and there its children
 // meet the current best.
 struct PointPhase {};
@@ -81,13 +66,8 @@ struct PointFrame {
     }
     RT_DEV static PointPhase phase(const Trav&) { return {}; }
     RT_DEV static void step(const SceneDev& S, Trav& T, Lane& x, const TravStack& stack, const TopTree& top, PointPhase) {
-        const TravClasses c = trav_classes(T);
-        const uint32_t ni = count(c.inner), nl = count(c.leaf);
-        if (ni * kVoteInner >= nl * kVoteLeaf && !(nl >= 64u)) {
-            if (in_mask(c.inner)) closest_inner(S, T, stack, top);
-        } else {
-            if (in_mask(c.leaf)) closest_leaf(S, T, x.r, stack);
-        }
+        vote_step(T, [&] { closest_inner(S, T, stack, top); },
+                  [&] { whole_leaf(S, T, stack, [&](float4 a, float4 b, float2 c2) { closest_test_regs(a, b, c2, T, x.r); }); });
     }
     RT_DEV static void store(const PointDev& q, uint32_t i, const Trav& T, const Lane& x) {
         const bool hit = T.best.tri != kNoTri;

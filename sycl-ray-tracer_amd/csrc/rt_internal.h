@@ -22,7 +22,7 @@
 //   rt_closest_point.h the contract of the closest-point queries, one fp32 text for the kernel and the host walk (scene_check.cpp: closest_host)
 //   rt_multihit.hip multi-hit ray queries, the k nearest hits of every ray, resumable (rt_trace_rays_multi[_device], rt_scene_multihit_host) and their kernels
 //   rt_nearest.hip k-nearest closest-point queries, the k nearest triangles of every point, resumable (rt_closest_points_multi[_device], rt_scene_nearest_host) and their kernels
-//   rt_closest_step.h the start of a point traversal and its inner step, shared by rt_closest.hip and rt_nearest.hip; rt_hit_list.h the sorted list in registers (rt_nearest.hip's; rt_multihit.hip keeps its own text of the same list)
+//   rt_closest_step.h the start of a point traversal and its inner step, shared by rt_closest.hip and rt_nearest.hip; rt_hit_list.h the sorted list in registers of rt_multihit.hip and rt_nearest.hip (the former keeps its own insertion loop); rt_whole_leaf.h the vote on the step kind and the whole-leaf read of those two and rt_closest.hip
 //   rt_query_launch.h what those six units (rt_query.hip and the last five) share on the host: grid sizing, the launch on the shared cursors, the host forms' staging, the path / gather checks
 //   rt_path_rounds.h  the kernel body rt_path_query.hip and rt_path_gather.hip share (path_rounds<E>); rt_query_frame.h the one rt_query.hip, rt_closest.hip, rt_multihit.hip and rt_nearest.hip share (query_frame<P>) and the claim of entries, shared by all six
 //   rt_lightmap.hip lightmap baking around one gather query (rt_lightmap_*): UV coverage, texel guides, resolve and dilation kernels

@@ -4,14 +4,16 @@
 // (A unit of its own, as rt_query.hip and rt_closest.hip are: the render kernels' listings do not change. DESIGN.md §24.)
 // The kernel's body is query_frame (rt_query_frame.h) with the claim every query kernel shares; the launch and the host form's staging are
 // rt_query_launch.h's. No arithmetic of the traversal is restated here: the inner step is trav_inner, the candidate is tri_test_regs, the
-// classes are trav_classes'. ONE line is: the vote on them (HitsFrame::step), copied from trav_step_wave<.., LEAF_BATCH> as rt_closest.hip
-// copies it, because that function calls its own leaf step. What is this unit's own: an entry is a ray with a tmax and a key, T.best is
-// not the answer but the BOUND, and the leaf step keeps a sorted list of N hits in registers.
+// classes are trav_classes', the vote on them is rt_whole_leaf.h's vote_step. What is this unit's own: an entry is a ray with a tmax and a key, T.best is
+// not the answer but the BOUND, and the leaf step keeps a sorted list of N hits in registers — the list's state, its opening, its
+// key-and-duplicate test and its store are rt_hit_list.h's, the whole-leaf read is rt_whole_leaf.h's; the insertion loop is this unit's.
 // What it relies on in rt_device.h, whose text it does not edit (held by tests/test_multihit.py:
 // test_what_the_kernel_relies_on_in_the_traversal): cur == 0 only in a ray's first step (trav_begin alone sets it, no node has the root
 // as a child), and trav_inner reads nothing of T.best but best.t — so k and the key can travel in best.u / v / tri to that first step.
 #include "rt_query_launch.h"
 #include "rt_query_frame.h"
+#include "rt_hit_list.h"
+#include "rt_whole_leaf.h"
 
 namespace rt {
 
@@ -39,37 +41,23 @@ struct MultiDev {
     ContractRange range; // rt_frame.hip: contract_range of the scene
 };
 
-// THE LIST. N slots in ascending (t, tri) order; the caller's k <= N live in the LAST k of them and the N - k in front hold a sentinel,
-// (-inf, kNoTri), that sorts before every candidate and is never moved. So the k-th entry is slot N - 1 whatever k is, and slot N - 1 IS
-// T.best: the traversal's closest hit so far is the list's last entry, the bound. A free slot holds (tmax, 0, 0, kNoTri): every counting
-// candidate sorts before it (t <= tmax, index < kNoTri), so filling the list and replacing its last entry are one insertion, and the
+// THE LIST is rt_hit_list.h's: the k-th entry is slot N - 1 whatever k is, and slot N - 1 IS T.best: the traversal's closest hit so far
+// is the list's last entry, the bound. A free slot holds (tmax, 0, 0, kNoTri): every counting candidate sorts before it (t <= tmax,
+// index < kNoTri), so filling the list and replacing its last entry are one insertion, and the
 // bound is (tmax, kNoTri) while a slot is free and (t, tri) of the k-th entry once none is — by tri_test_regs' own compare, t < best.t
 // or t == best.t at a lower index, a candidate is written exactly when it counts against tmax and sorts before the k-th entry.
 // trav_inner culls child boxes against best.t and keeps boxes at equal distance: a candidate that ties with the k-th entry at a lower
 // index is still reached (§14's tmax argument on a moving bound).
-// Every index below is a compile-time constant after unrolling: the list lives in registers (a dynamic index would put it into scratch).
-template <uint32_t N>
-struct MultiLane {
-    Hit s[N - 1];       // slots 0 .. N - 2; slot N - 1 is T.best
-    float after_t;      // the key: a candidate counts iff (t, tri) > (after_t, after_tri); no key = (-inf, 0), below every t > kTNear
-    uint32_t after_tri;
-};
 
-RT_DEV bool hit_before(const Hit& a, const Hit& b) { return a.t < b.t || (a.t == b.t && a.tri < b.tri); }
-RT_DEV Hit hit_sel(bool c, const Hit& a, const Hit& b) { return Hit{c ? a.t : b.t, c ? a.u : b.u, c ? a.v : b.v, c ? a.tri : b.tri}; }
-
-// One candidate: the contract's test on a copy of the bound, the key, the de-duplication (a pre-split triangle sits whole in several
-// leaves and gives the same bits each time), then the insertion: slot i takes its left neighbour where the candidate sorts before that
-// one, the candidate where it sorts before slot i only, and keeps its own otherwise; what was in slot N - 1 falls out.
+// One candidate: the contract's test on a copy of the bound, the key and the de-duplication (hit_list_counts), then the insertion: slot i
+// takes its left neighbour where the candidate sorts before that one, the candidate where it sorts before slot i only, and keeps its own
+// otherwise; what was in slot N - 1 falls out. (This unit's own loop, not hit_list_insert: rt_hit_list.h says why.)
 template <uint32_t N>
-RT_DEV void multi_candidate(float4 a, float4 b, float2 c2, Trav& T, MultiLane<N>& x) {
+RT_DEV void multi_candidate(float4 a, float4 b, float2 c2, Trav& T, HitList<N>& x) {
     Hit c = T.best;
     tri_test_regs(a, b, c2, T.o, T.d, c);
-    bool take = c.tri != T.best.tri; // written: a candidate never has the bound's index (kNoTri, or an entry's: that one ties, and a tie is no win)
-    take = take && (c.t > x.after_t || (c.t == x.after_t && c.tri > x.after_tri));
-#pragma unroll
-    for (uint32_t i = 0; i + 1 < N; ++i) take = take && c.tri != x.s[i].tri;
-    if (take) {
+    // written: a candidate never has the bound's index (kNoTri, or an entry's: that one ties, and a tie is no win)
+    if (hit_list_counts(x, c.tri != T.best.tri, c.t, c.tri)) {
         bool here = hit_before(c, x.s[N - 2]); // from the last slot down: two compares are alive at a time, not N - 1
         T.best = hit_sel(here, x.s[N - 2], c);
 #pragma unroll
@@ -82,33 +70,14 @@ RT_DEV void multi_candidate(float4 a, float4 b, float2 c2, Trav& T, MultiLane<N>
     }
 }
 
-// Leaf step: the whole leaf (1-2 records) as trav_leaf<true> reads it — five unconditional 16-byte loads of 80 contiguous bytes (a leaf of
-// one record reads 40 bytes of its neighbour and ignores them; the buffer ends in 48 bytes of padding) — then one or two candidates.
-template <uint32_t N>
-RT_DEV void multi_leaf(const SceneDev& S, Trav& T, MultiLane<N>& x, const TravStack& stack) {
-    static_assert(kMaxLeafTris == 2 && kTriBytes == 40, "the whole-leaf step reads a leaf as 80 contiguous bytes");
-    const uint32_t code = (uint32_t)~T.cur;
-    const uint32_t first = code >> 2, rem = code & 3u;
-    const uint8_t* p4 = S.tris + (size_t)first * kTriBytes;
-    const float4 l0 = tri_ld4(p4), l1 = tri_ld4(p4 + 16), l2 = tri_ld4(p4 + 32), l3 = tri_ld4(p4 + 48), l4 = tri_ld4(p4 + 64);
-    const bool two = rem != 0u;
-    multi_candidate<N>(l0, l1, make_float2(l2.x, l2.y), T, x);
-    if (__ballot(two) != 0ull) {
-        if (two) multi_candidate<N>(make_float4(l2.z, l2.w, l3.x, l3.y), make_float4(l3.z, l3.w, l4.x, l4.y), make_float2(l4.z, l4.w), T, x);
-    }
-    if (lanes(!stack_shallow(stack, T, 0u)) == 0ull) trav_pop_lds(T, stack);
-    else trav_pop(T, stack);
-}
-
 // query_frame's policy (rt_query_frame.h): an entry is a ray, its tmax and its key — the origin inside the contract's range, tmax and
-// after_t no NaN; a step is one wave-uniform step kind by the ray traversal's vote on trav_classes (trav_step_wave<.., LEAF_BATCH>'s
-// line), trav_inner unchanged or this unit's leaf step.
+// after_t no NaN; a step is one wave-uniform step kind by the ray traversal's vote on trav_classes (vote_step),
+// trav_inner unchanged or the whole-leaf step with this unit's candidate.
 template <uint32_t N>
 struct HitsFrame {
     static constexpr uint32_t kBlock = kMultiBlock, kRefill = kMultiRefill;
-    using Lane = MultiLane<N>;
-    // (query_frame hands start() the lane's Trav, not its Lane: the key and k travel in T.best.u / v / tri — the bound's index is not read
-    // before the first leaf step — to the lane's first step, the one at the root, which opens the list: multi_open)
+    using Lane = HitList<N>;
+    RT_DEV static HitListOut out(const MultiDev& q) { return HitListOut{q.t, q.u, q.v, q.tri, q.count, q.k}; }
     RT_DEV static bool start(const MultiDev& q, uint32_t i, Trav& T, const TravStack& stack) {
         const size_t k = 3 * (size_t)i;
         const f3 o = mk3(q.org[k], q.org[k + 1], q.org[k + 2]);
@@ -119,56 +88,20 @@ struct HitsFrame {
         if (in_contract_range(q.range, o.x, o.y, o.z) && tm == tm && at == at) {
             trav_begin(T, o, d, stack);
             T.best.t = tm;
-            T.best.u = at, T.best.v = __uint_as_float(q.after_t ? q.after_tri[i] : 0u), T.best.tri = q.k;
+            hit_list_carry(T, at, q.after_t ? q.after_tri[i] : 0u, q.k); // (the bound's index is not read before the first leaf step)
             return true;
         }
-        for (uint32_t j = 0; j < q.k; ++j) { // rejected: every slot marked, never traced
-            if (q.t) q.t[(size_t)i * q.k + j] = __builtin_nanf("");
-            if (q.tri) q.tri[(size_t)i * q.k + j] = RT_TRI_REJECTED;
-        }
-        if (q.count) q.count[i] = 0u;
+        hit_list_reject(out(q), i);
         return false;
-    }
-    // A lane is at the root (cur == 0) exactly once, in its first step: the list is opened there — the key taken out of T.best, the
-    // sentinels and the free slots written, the bound's own slot set free.
-    RT_DEV static void multi_open(Trav& T, Lane& x) {
-        const uint32_t k = T.best.tri;
-        x.after_t = T.best.u, x.after_tri = __float_as_uint(T.best.v);
-#pragma unroll
-        for (uint32_t s = 0; s + 1 < N; ++s) x.s[s] = Hit{s + k < N ? -__builtin_huge_valf() : T.best.t, 0.0f, 0.0f, kNoTri};
-        T.best.u = T.best.v = 0.0f, T.best.tri = kNoTri;
     }
     RT_DEV static TravSigns phase(const Trav& T) { return trav_signs(T); }
     RT_DEV static void step(const SceneDev& S, Trav& T, Lane& x, const TravStack& stack, const TopTree& top, const TravSigns& sg) {
-        const TravClasses c = trav_classes(T);
-        const uint32_t ni = count(c.inner), nl = count(c.leaf);
-        if (ni * kVoteInner >= nl * kVoteLeaf && !(nl >= 64u)) {
-            if (in_mask(c.inner)) {
-                if (T.cur == 0) multi_open(T, x);
-                trav_inner(S, T, stack, top, sg);
-            }
-        } else {
-            if (in_mask(c.leaf)) multi_leaf<N>(S, T, x, stack);
-        }
+        vote_step(T, [&] {
+            if (T.cur == 0) hit_list_open(T, x); // a lane is at the root exactly once, in its first step
+            trav_inner(S, T, stack, top, sg);
+        }, [&] { whole_leaf(S, T, stack, [&](float4 a, float4 b, float2 c2) { multi_candidate<N>(a, b, c2, T, x); }); });
     }
-    // slot s of the list is output slot s - (N - k) of the ray; a slot nothing was inserted into still has kNoTri and is written as a miss
-    RT_DEV static void store_slot(const MultiDev& q, uint32_t i, uint32_t s, const Hit& h, uint32_t& filled) {
-        if (s + q.k < N) return;
-        const size_t at = (size_t)i * q.k + (s + q.k - N);
-        const bool hit = h.tri != kNoTri;
-        filled += hit ? 1u : 0u;
-        if (q.t) q.t[at] = hit ? h.t : __builtin_huge_valf(); // a free slot: t still holds tmax
-        if (q.u) q.u[at] = h.u;
-        if (q.v) q.v[at] = h.v;
-        if (q.tri) q.tri[at] = h.tri;
-    }
-    RT_DEV static void store(const MultiDev& q, uint32_t i, const Trav& T, const Lane& x) {
-        uint32_t filled = 0u;
-#pragma unroll
-        for (uint32_t s = 0; s + 1 < N; ++s) store_slot(q, i, s, x.s[s], filled);
-        store_slot(q, i, N - 1, T.best, filled);
-        if (q.count) q.count[i] = filled;
-    }
+    RT_DEV static void store(const MultiDev& q, uint32_t i, const Trav& T, const Lane& x) { hit_list_store<N>(out(q), i, T.best, x); }
 };
 
 template <uint32_t N>
@@ -189,22 +122,13 @@ int multi_check(const rt_scene* s, const rt_multihit_query* q) {
     return refuse_host_only(s);
 }
 
-// One instantiation per list size, the smallest that holds k, each with a persistent grid of its own (kQueryKindMulti + 0, + 1, + 2),
-// sized for its own occupancy at the scene's first launch of it: what a call takes does not depend on the k of the calls before it.
-template <uint32_t N>
-int multi_launch(rt_scene* s, const MultiDev& d, hipStream_t st) {
-    constexpr QueryKind kind = (QueryKind)(kQueryKindMulti + (N == 2 ? 0 : N == 4 ? 1 : 2));
-    static_assert((N == 2 || N == 4 || N == 8) && kind < kQueryKinds, "three instantiations, three grids");
-    return query_launch(s, kind, k_multihit<N>, kMultiBlock, d, d.n, st, s->query_grid[kind] ? nullptr : dev_knob("RT_MULTIHIT_GRID"));
-}
-
-// fills the launch struct and hands it to the shared launch (PRE: multi_check passed, n > 0, pointers on the scene's device)
+// fills the launch struct and hands it to the list kinds' launch (PRE: multi_check passed, n > 0, pointers on the scene's device)
 int multi_enqueue(rt_scene* s, const rt_multihit_query* q, hipStream_t st) {
     MultiDev d{};
     d.org = q->org, d.dir = q->dir, d.tmax = q->tmax, d.after_t = q->after_t, d.after_tri = q->after_tri;
     d.t = q->t, d.u = q->u, d.v = q->v, d.tri = q->tri, d.count = q->count;
     d.n = q->n, d.k = q->k;
-    return q->k <= 2 ? multi_launch<2>(s, d, st) : q->k <= 4 ? multi_launch<4>(s, d, st) : multi_launch<8>(s, d, st);
+    return list_launch<kQueryKindMulti>(s, [](auto n) { return k_multihit<decltype(n)::value>; }, kMultiBlock, d, st, dev_knob("RT_MULTIHIT_GRID"));
 }
 
 } // namespace
@@ -221,9 +145,9 @@ int rt_trace_rays_multi(rt_scene* s, const rt_multihit_query* q) {
         if (q->tmax && std::isnan(q->tmax[i])) return fail(RT_ERR_INVALID, "ray " + std::to_string(i) + ": tmax is NaN");
         if (q->after_t && std::isnan(q->after_t[i])) return fail(RT_ERR_INVALID, "ray " + std::to_string(i) + ": after_t is NaN");
     }
-    const size_t slot = 4 * (size_t)k; // bytes per ray of a slot-major output
     const StageIn ins[5] = {{q->org, 12}, {q->dir, 12}, {q->tmax, 4}, {q->after_t, 4}, {q->after_tri, 4}};
-    const StageOut outs[5] = {{q->t, slot}, {q->u, slot}, {q->v, slot}, {q->tri, slot}, {q->count, 4}};
+    StageOut outs[5];
+    list_stage_outs(outs, k, q->t, q->u, q->v, q->tri, q->count);
     return query_staged(s, n, ins, outs, [&](void* const* in, void* const* out) {
         rt_multihit_query d{};
         d.n = n, d.k = k;

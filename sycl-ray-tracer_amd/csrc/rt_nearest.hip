@@ -4,9 +4,9 @@
 // (A unit of its own, as rt_closest.hip and rt_multihit.hip are: no other unit's listing changes. DESIGN.md §25.)
 // The kernel's body is query_frame (rt_query_frame.h) with the claim every query kernel shares; the launch and the host form's staging are
 // rt_query_launch.h's. No arithmetic is restated here: the candidate and the winner rule are rt_closest_point.h's, the start of a
-// traversal and the inner step are rt_closest_step.h's (k_closest's own), the list and its insertion are rt_hit_list.h's (k_multihit's
-// list, written once more there). What is this unit's own: an entry is a point with a max_dist2 and a key, T.best is not the answer but the BOUND, and the leaf
-// step keeps the list.
+// traversal and the inner step are rt_closest_step.h's (k_closest's own), the list — its state, opening, key-and-duplicate test,
+// insertion and store — is rt_hit_list.h's, the whole-leaf read is rt_whole_leaf.h's. What is this unit's own: an entry is a point with
+// a max_dist2 and a key, T.best is not the answer but the BOUND, and the candidate that the leaf step hands the list.
 // What it relies on in rt_closest_step.h and the trees (held by tests/test_nearest.py: test_what_the_kernel_relies_on_in_the_point_traversal):
 // cur == 0 only in a point's first step (closest_begin alone sets it, no node has the root as a child), and closest_inner reads nothing of
 // T.best but best.t — so k and the key can travel in best.u / v / tri to that first step.
@@ -15,6 +15,7 @@
 #include "rt_closest_point.h"
 #include "rt_closest_step.h"
 #include "rt_hit_list.h"
+#include "rt_whole_leaf.h"
 
 namespace rt {
 
@@ -48,58 +49,31 @@ struct NearestDev {
 // once none is — by closest_better, dist2 < best or dist2 == best at a lower index, a candidate passes exactly when it counts against
 // max_dist2 and sorts before the k-th entry. closest_inner enters a child at lb * kClosestSlack <= best.t: a candidate that ties with
 // the k-th entry at a lower index is still reached, and §22's cull argument — about the candidate's underestimate of the true distance,
-// whatever the bound is — holds for a bound that only ever moves down. The key filters candidates and culls no box.
-template <uint32_t N>
-struct NearestLane {
-    Hit s[N - 1];         // slots 0 .. N - 2; slot N - 1 is T.best
-    float after_dist2;    // the key: a candidate counts iff (dist2, tri) > (after_dist2, after_tri); no key = (-inf, 0), below every dist2
-    uint32_t after_tri;
-};
+// whatever the bound is — holds for a bound that only ever moves down. The key (HitList's after_t holds after_dist2) filters candidates
+// and culls no box.
 
 // One candidate: the contract's text on the record's ten live dwords, the winner rule against the bound (a NaN dist2 fails it; so does
-// the bound's own triangle met again: it ties with itself), the key, the de-duplication against the other slots (a pre-split triangle
-// sits whole in several leaves and gives the same bits each time), then the insertion.
+// the bound's own triangle met again: it ties with itself), the key and the de-duplication against the other slots (hit_list_counts),
+// then the insertion.
 template <uint32_t N>
-RT_DEV void nearest_candidate(float4 a, float4 b, float2 c2, Trav& T, NearestLane<N>& x) {
+RT_DEV void nearest_candidate(float4 a, float4 b, float2 c2, Trav& T, HitList<N>& x) {
     const float p[3] = {T.o.x, T.o.y, T.o.z};
     const float v0[3] = {a.x, a.y, a.z}, e1[3] = {a.w, b.x, b.y}, e2[3] = {b.z, b.w, c2.x};
     const uint32_t gidx = __float_as_uint(c2.y);
     const ClosestPoint cand = closest_point_on_record(p, v0, e1, e2);
-    bool take = closest_better(cand.dist2, gidx, T.best.t, T.best.tri);
-    take = take && (cand.dist2 > x.after_dist2 || (cand.dist2 == x.after_dist2 && gidx > x.after_tri));
-#pragma unroll
-    for (uint32_t i = 0; i + 1 < N; ++i) take = take && gidx != x.s[i].tri;
-    if (take) hit_list_insert<N>(x, T.best, Hit{cand.dist2, cand.u, cand.v, gidx});
-}
-
-// Leaf step: the whole leaf (1-2 records) as closest_leaf reads it — five unconditional 16-byte loads of 80 contiguous bytes (a leaf of
-// one record reads 40 bytes of its neighbour and ignores them; the buffer ends in 48 bytes of padding) — then one or two candidates.
-template <uint32_t N>
-RT_DEV void nearest_leaf(const SceneDev& S, Trav& T, NearestLane<N>& x, const TravStack& stack) {
-    static_assert(kMaxLeafTris == 2 && kTriBytes == 40, "the whole-leaf step reads a leaf as 80 contiguous bytes");
-    const uint32_t code = (uint32_t)~T.cur;
-    const uint32_t first = code >> 2, rem = code & 3u;
-    const uint8_t* p4 = S.tris + (size_t)first * kTriBytes;
-    const float4 l0 = tri_ld4(p4), l1 = tri_ld4(p4 + 16), l2 = tri_ld4(p4 + 32), l3 = tri_ld4(p4 + 48), l4 = tri_ld4(p4 + 64);
-    const bool two = rem != 0u;
-    nearest_candidate<N>(l0, l1, make_float2(l2.x, l2.y), T, x);
-    if (__ballot(two) != 0ull) {
-        if (two) nearest_candidate<N>(make_float4(l2.z, l2.w, l3.x, l3.y), make_float4(l3.z, l3.w, l4.x, l4.y), make_float2(l4.z, l4.w), T, x);
-    }
-    if (lanes(!stack_shallow(stack, T, 0u)) == 0ull) trav_pop_lds(T, stack);
-    else trav_pop(T, stack);
+    if (hit_list_counts(x, closest_better(cand.dist2, gidx, T.best.t, T.best.tri), cand.dist2, gidx))
+        hit_list_insert<N>(x, T.best, Hit{cand.dist2, cand.u, cand.v, gidx});
 }
 
 // query_frame's policy (rt_query_frame.h): an entry is a point, its max_dist2 and its key — the point inside the contract's range,
-// max_dist2 and after_dist2 no NaN; a step is one wave-uniform step kind by the ray traversal's vote on trav_classes (PointFrame's line),
-// closest_inner unchanged or this unit's leaf step.
+// max_dist2 and after_dist2 no NaN; a step is one wave-uniform step kind by the ray traversal's vote on trav_classes (vote_step),
+// closest_inner unchanged or the whole-leaf step with this unit's candidate.
 struct NearestPhase {};
 template <uint32_t N>
 struct NearestFrame {
     static constexpr uint32_t kBlock = kNearestBlock, kRefill = kNearestRefill;
-    using Lane = NearestLane<N>;
-    // (query_frame hands start() the lane's Trav, not its Lane: the key and k travel in T.best.u / v / tri — closest_inner reads best.t
-    // alone — to the lane's first step, the one at the root, which opens the list: nearest_open)
+    using Lane = HitList<N>;
+    RT_DEV static HitListOut out(const NearestDev& q) { return HitListOut{q.dist2, q.u, q.v, q.tri, q.count, q.k}; }
     RT_DEV static bool start(const NearestDev& q, uint32_t i, Trav& T, const TravStack& stack) {
         const size_t k = 3 * (size_t)i;
         const f3 p = mk3(q.pos[k], q.pos[k + 1], q.pos[k + 2]);
@@ -108,56 +82,20 @@ struct NearestFrame {
         const float ad = q.after_dist2 ? q.after_dist2[i] : -inf;
         if (in_contract_range(q.range, p.x, p.y, p.z) && md == md && ad == ad) {
             closest_begin(T, p, md, stack);
-            T.best.u = ad, T.best.v = __uint_as_float(q.after_dist2 ? q.after_tri[i] : 0u), T.best.tri = q.k;
+            hit_list_carry(T, ad, q.after_dist2 ? q.after_tri[i] : 0u, q.k);
             return true;
         }
-        for (uint32_t j = 0; j < q.k; ++j) { // rejected: every slot marked, never walked
-            if (q.dist2) q.dist2[(size_t)i * q.k + j] = __builtin_nanf("");
-            if (q.tri) q.tri[(size_t)i * q.k + j] = RT_TRI_REJECTED;
-        }
-        if (q.count) q.count[i] = 0u;
+        hit_list_reject(out(q), i);
         return false;
-    }
-    // A lane is at the root (cur == 0) exactly once, in its first step: the list is opened there — the key taken out of T.best, the
-    // sentinels and the free slots written, the bound's own slot set free.
-    RT_DEV static void nearest_open(Trav& T, Lane& x) {
-        const uint32_t k = T.best.tri;
-        x.after_dist2 = T.best.u, x.after_tri = __float_as_uint(T.best.v);
-#pragma unroll
-        for (uint32_t s = 0; s + 1 < N; ++s) x.s[s] = Hit{s + k < N ? -__builtin_huge_valf() : T.best.t, 0.0f, 0.0f, kNoTri};
-        T.best.u = T.best.v = 0.0f, T.best.tri = kNoTri;
     }
     RT_DEV static NearestPhase phase(const Trav&) { return {}; }
     RT_DEV static void step(const SceneDev& S, Trav& T, Lane& x, const TravStack& stack, const TopTree& top, NearestPhase) {
-        const TravClasses c = trav_classes(T);
-        const uint32_t ni = count(c.inner), nl = count(c.leaf);
-        if (ni * kVoteInner >= nl * kVoteLeaf && !(nl >= 64u)) {
-            if (in_mask(c.inner)) {
-                if (T.cur == 0) nearest_open(T, x);
-                closest_inner(S, T, stack, top);
-            }
-        } else {
-            if (in_mask(c.leaf)) nearest_leaf<N>(S, T, x, stack);
-        }
+        vote_step(T, [&] {
+            if (T.cur == 0) hit_list_open(T, x); // a lane is at the root exactly once, in its first step
+            closest_inner(S, T, stack, top);
+        }, [&] { whole_leaf(S, T, stack, [&](float4 a, float4 b, float2 c2) { nearest_candidate<N>(a, b, c2, T, x); }); });
     }
-    // slot s of the list is output slot s - (N - k) of the point; a slot nothing was inserted into still has kNoTri and is written as a miss
-    RT_DEV static void store_slot(const NearestDev& q, uint32_t i, uint32_t s, const Hit& h, uint32_t& filled) {
-        if (s + q.k < N) return;
-        const size_t at = (size_t)i * q.k + (s + q.k - N);
-        const bool hit = h.tri != kNoTri;
-        filled += hit ? 1u : 0u;
-        if (q.dist2) q.dist2[at] = hit ? h.t : __builtin_huge_valf(); // a free slot: t still holds max_dist2
-        if (q.u) q.u[at] = h.u;
-        if (q.v) q.v[at] = h.v;
-        if (q.tri) q.tri[at] = h.tri;
-    }
-    RT_DEV static void store(const NearestDev& q, uint32_t i, const Trav& T, const Lane& x) {
-        uint32_t filled = 0u;
-#pragma unroll
-        for (uint32_t s = 0; s + 1 < N; ++s) store_slot(q, i, s, x.s[s], filled);
-        store_slot(q, i, N - 1, T.best, filled);
-        if (q.count) q.count[i] = filled;
-    }
+    RT_DEV static void store(const NearestDev& q, uint32_t i, const Trav& T, const Lane& x) { hit_list_store<N>(out(q), i, T.best, x); }
 };
 
 template <uint32_t N>
@@ -178,22 +116,13 @@ int nearest_check(const rt_scene* s, const rt_nearest_query* q) {
     return refuse_host_only(s);
 }
 
-// One instantiation per list size, the smallest that holds k, each with a persistent grid of its own (kQueryKindNearest + 0, + 1, + 2),
-// sized for its own occupancy at the scene's first launch of it: what a call takes does not depend on the k of the calls before it.
-template <uint32_t N>
-int nearest_launch(rt_scene* s, const NearestDev& d, hipStream_t st) {
-    constexpr QueryKind kind = (QueryKind)(kQueryKindNearest + (N == 2 ? 0 : N == 4 ? 1 : 2));
-    static_assert((N == 2 || N == 4 || N == 8) && kind < kQueryKinds, "three instantiations, three grids");
-    return query_launch(s, kind, k_nearest<N>, kNearestBlock, d, d.n, st, s->query_grid[kind] ? nullptr : dev_knob("RT_NEAREST_GRID"));
-}
-
-// fills the launch struct and hands it to the shared launch (PRE: nearest_check passed, n > 0, pointers on the scene's device)
+// fills the launch struct and hands it to the list kinds' launch (PRE: nearest_check passed, n > 0, pointers on the scene's device)
 int nearest_enqueue(rt_scene* s, const rt_nearest_query* q, hipStream_t st) {
     NearestDev d{};
     d.pos = q->pos, d.max_dist2 = q->max_dist2, d.after_dist2 = q->after_dist2, d.after_tri = q->after_tri;
     d.dist2 = q->dist2, d.u = q->u, d.v = q->v, d.tri = q->tri, d.count = q->count;
     d.n = q->n, d.k = q->k;
-    return q->k <= 2 ? nearest_launch<2>(s, d, st) : q->k <= 4 ? nearest_launch<4>(s, d, st) : nearest_launch<8>(s, d, st);
+    return list_launch<kQueryKindNearest>(s, [](auto n) { return k_nearest<decltype(n)::value>; }, kNearestBlock, d, st, dev_knob("RT_NEAREST_GRID"));
 }
 
 } // namespace
@@ -212,9 +141,9 @@ int rt_closest_points_multi(rt_scene* s, const rt_nearest_query* q) {
         if (q->max_dist2 && std::isnan(q->max_dist2[i])) return fail(RT_ERR_INVALID, "point " + std::to_string(i) + ": max_dist2 is NaN");
         if (q->after_dist2 && std::isnan(q->after_dist2[i])) return fail(RT_ERR_INVALID, "point " + std::to_string(i) + ": after_dist2 is NaN");
     }
-    const size_t slot = 4 * (size_t)k; // bytes per point of a slot-major output
     const StageIn ins[4] = {{q->pos, 12}, {q->max_dist2, 4}, {q->after_dist2, 4}, {q->after_tri, 4}};
-    const StageOut outs[5] = {{q->dist2, slot}, {q->u, slot}, {q->v, slot}, {q->tri, slot}, {q->count, 4}};
+    StageOut outs[5];
+    list_stage_outs(outs, k, q->dist2, q->u, q->v, q->tri, q->count);
     return query_staged(s, n, ins, outs, [&](void* const* in, void* const* out) {
         rt_nearest_query d{};
         d.n = n, d.k = k;

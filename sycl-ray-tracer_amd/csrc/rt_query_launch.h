@@ -1,6 +1,8 @@
-// rt_query_launch.h — the host half rt_query.hip, rt_closest.hip, rt_path_query.hip and rt_path_gather.hip share: the sizing of a query
-// kernel's persistent grid, the launch on the scene's shared cursors (rt_scene_update relies on its event), the staging of a host form
-// (query_staged) and the refusals two kinds word alike; and what path and gather queries have in common beyond that: the argument checks.
+// rt_query_launch.h — the host half the query units share (rt_query.hip, rt_closest.hip, rt_multihit.hip, rt_nearest.hip, rt_path_query.hip,
+// rt_path_gather.hip): the sizing of a query kernel's persistent grid, the launch on the scene's shared cursors (rt_scene_update relies on
+// its event), the staging of a host form (query_staged) and the refusals two kinds word alike; what the two k-list kinds have in common
+// beyond that: the choice of the list size with its grid, and the slot-major outputs; and what path and gather queries have: the argument
+// checks.
 #pragma once
 #include "rt_internal.h"
 
@@ -64,6 +66,27 @@ int query_staged(rt_scene* s, size_t n, const StageIn (&ins)[NI], const StageOut
     for (size_t k = 0; k < NO; ++k)
         if (outs[k].host) HIPCHK(hipMemcpy(outs[k].host, out[k], n * outs[k].bytes, hipMemcpyDeviceToHost));
     return RT_OK;
+}
+
+// ---- the k-list kinds (rt_multihit.hip, rt_nearest.hip; the list: rt_hit_list.h) -------------------------------------------------------------
+// One instantiation per list size, N = 2, 4 or 8 slots, the smallest that holds d.k, each with a persistent grid of its own (base + 0, + 1,
+// + 2), sized for its own occupancy at the scene's first launch of it: what a call takes does not depend on the k of the calls before it.
+// kernel_of(ListSize<N>{}) -> the unit's kernel of N slots; grid_knob as query_launch's.
+template <uint32_t N> using ListSize = std::integral_constant<uint32_t, N>;
+template <QueryKind Base, class Dev, class KernelOf>
+int list_launch(rt_scene* s, KernelOf kernel_of, uint32_t block, const Dev& d, hipStream_t st, const char* grid_knob) {
+    const auto go = [&](auto n) {
+        constexpr uint32_t N = decltype(n)::value;
+        constexpr QueryKind kind = (QueryKind)(Base + (N == 2 ? 0 : N == 4 ? 1 : 2));
+        static_assert((N == 2 || N == 4 || N == 8) && kind < kQueryKinds, "three instantiations, three grids");
+        return query_launch(s, kind, kernel_of(n), block, d, d.n, st, grid_knob);
+    };
+    return d.k <= 2 ? go(ListSize<2>{}) : d.k <= 4 ? go(ListSize<4>{}) : go(ListSize<8>{});
+}
+// the outputs of a k-list query's host form: four slot-major arrays of k slots per entry, and the count
+inline void list_stage_outs(StageOut (&outs)[5], uint32_t k, float* t, float* u, float* v, uint32_t* tri, uint32_t* count) {
+    const size_t slot = 4 * (size_t)k; // bytes per entry of a slot-major output
+    outs[0] = {t, slot}, outs[1] = {u, slot}, outs[2] = {v, slot}, outs[3] = {tri, slot}, outs[4] = {count, 4};
 }
 
 // the refusals with one wording in every kind

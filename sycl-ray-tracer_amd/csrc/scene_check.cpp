@@ -243,6 +243,152 @@ int check_bvh(const HostScene& hs, std::string& err) {
     return RT_OK;
 }
 
+// ---- what the host walks share ---------------------------------------------------------------------------------------------------------------
+namespace {
+
+// The walk every diagnostic below makes, from the root: inner(cur) visits the inner node cur, stacks the children to come back to and
+// either descends (sets cur to the child, returns true) or not; leaf(range) tests a leaf's records. No second look at a popped child.
+template <class Inner, class Leaf>
+void walk_tree(std::vector<int32_t>& stack, uint64_t& visits, Inner&& inner, Leaf&& leaf) {
+    stack.clear();
+    int32_t cur = 0;
+    for (;;) {
+        if (cur >= 0) {
+            visits++;
+            if (inner(cur)) continue;
+        } else {
+            leaf(leaf_range(cur));
+        }
+        if (stack.empty()) break;
+        cur = stack.back(), stack.pop_back();
+    }
+}
+
+// The point traversal's inner step (rt_closest_step.h: closest_inner): the decoded child planes, the kernel's cull rule (closest_enters)
+// against `best`, its sorting network on (lb, child) with +inf for a child not entered, the others stacked far to near.
+inline bool point_inner(const BvhNode& nd, const float p[3], float best, std::vector<int32_t>& stack, int32_t& cur) {
+    const float inf = std::numeric_limits<float>::infinity();
+    float key[4];
+    int32_t ch[4];
+    for (int k = 0; k < 4; ++k) {
+        ch[k] = nd.child[k], key[k] = inf;
+        if (nd.child[k] == kChildEmpty) continue; // (its inverted box gives a finite lb: the word is what says it is absent)
+        float lb = 0.0f;
+        for (int a = 0; a < 3; ++a) {
+            const float lo = child_plane(nd, k, a, 0), hi = child_plane(nd, k, a, 1);
+            const float e = std::max(std::max(lo - p[a], p[a] - hi), 0.0f);
+            lb = std::fma(e, e, lb);
+        }
+        if (closest_enters(lb, best)) key[k] = std::min(lb, std::numeric_limits<float>::max()); // (an lb that overflowed is still a key)
+    }
+    auto ce = [&](int a, int b) { if (key[b] < key[a]) std::swap(key[a], key[b]), std::swap(ch[a], ch[b]); };
+    ce(0, 1), ce(2, 3), ce(0, 2), ce(1, 3), ce(1, 2);
+    for (int k = 3; k >= 1; --k)
+        if (key[k] < inf) stack.push_back(ch[k]);
+    if (key[0] < inf) cur = ch[0];
+    return key[0] < inf;
+}
+
+// The ray traversal's inner step: the slab test of every child's box, box_of(k), against `bound` — a box AT the bound stays: a tie at a
+// lower index is behind it — nearest child first, the others stacked. A child whose device word is `skip` counts as missed (the origin
+// skip; kSkipNone: none).
+inline void ray_inverse(const float d[3], float inv[3]) {
+    for (int a = 0; a < 3; ++a) inv[a] = 1.0f / (std::fabs(d[a]) < 1e-30f ? std::copysign(1e-30f, d[a]) : d[a]);
+}
+template <class BoxOf>
+bool ray_inner(const BvhNode& nd, const float o[3], const float inv[3], float bound, uint32_t skip, BoxOf&& box_of, std::vector<int32_t>& stack, int32_t& cur) {
+    float key[4];
+    int32_t ch[4];
+    int m = 0;
+    for (int k = 0; k < 4; ++k) {
+        if (nd.child[k] == kChildEmpty || device_child_word(nd.child[k]) == skip) continue;
+        const Box3 b = box_of(k);
+        float tn = 0.0f, tf = bound;
+        for (int a = 0; a < 3; ++a) {
+            const float t0 = (b.lo[a] - o[a]) * inv[a], t1 = (b.hi[a] - o[a]) * inv[a];
+            tn = std::max(tn, std::min(t0, t1)), tf = std::min(tf, std::max(t0, t1));
+        }
+        if (tn <= tf) key[m] = tn, ch[m] = nd.child[k], m++;
+    }
+    for (int a = 1; a < m; ++a) // nearest first
+        for (int b = a; b > 0 && key[b] < key[b - 1]; --b) std::swap(key[b], key[b - 1]), std::swap(ch[b], ch[b - 1]);
+    for (int a = m - 1; a >= 1; --a) stack.push_back(ch[a]);
+    if (m) cur = ch[0];
+    return m != 0;
+}
+
+// The sorted keyed list of nearest_host and multihit_host: entries (t, u, v, tri) in ascending (t, tri) order, t being a ray's t or a
+// point's dist2. A candidate COUNTS iff t <= limit (a NaN t never does) and it lies behind the key, (t, tri) > (key_t, key_tri). The
+// brute force adds every counting candidate, sorts and keeps the first k; the walk offers candidates to a list of at most k against the
+// BOUND: (limit, kNoTri) while the list has free slots, (t, tri) of its k-th entry once it is full.
+struct ListHit {
+    float t, u, v;
+    uint32_t tri;
+};
+inline bool hit_before(float t, uint32_t tri, float bt, uint32_t btri) { return t < bt || (t == bt && tri < btri); }
+struct KeyedList {
+    const size_t k;
+    float limit = 0.0f, key_t = 0.0f, bound = 0.0f;
+    uint32_t key_tri = 0u, bound_tri = kNoTri;
+    std::vector<ListHit> hits;
+    explicit KeyedList(size_t slots) : k(slots) {}
+
+    // entry i's list: limit[i] or +inf, the key (key_t[i], key_tri[i]) or none, (-inf, 0)
+    void open(uint32_t i, const float* limits, const float* key_ts, const uint32_t* key_tris) {
+        const float inf = std::numeric_limits<float>::infinity();
+        limit = limits ? limits[i] : inf, key_t = key_ts ? key_ts[i] : -inf, key_tri = key_ts ? key_tris[i] : 0u;
+        bound = limit, bound_tri = kNoTri;
+        hits.clear();
+    }
+    bool counts(const ListHit& c) const { return c.t <= limit && (c.t > key_t || (c.t == key_t && c.tri > key_tri)); }
+    void add(const ListHit& c) { // the brute force
+        if (counts(c)) hits.push_back(c);
+    }
+    void first_k() {
+        std::stable_sort(hits.begin(), hits.end(), [](const ListHit& a, const ListHit& b) { return hit_before(a.t, a.tri, b.t, b.tri); });
+        if (hits.size() > k) hits.resize(k);
+    }
+    // the walk: taken iff it sorts before the bound, counts and is not in the list already (a pre-split triangle sits in several leaves)
+    void offer(const ListHit& c) {
+        if (!hit_before(c.t, c.tri, bound, bound_tri) || !counts(c)) return;
+        size_t at = 0;
+        bool listed = false;
+        for (const ListHit& h : hits) listed = listed || h.tri == c.tri, at += hit_before(h.t, h.tri, c.t, c.tri) ? 1 : 0;
+        if (listed) return;
+        hits.insert(hits.begin() + (ptrdiff_t)at, c);
+        if (hits.size() > k) hits.pop_back();
+        if (hits.size() == k) bound = hits.back().t, bound_tri = hits.back().tri;
+    }
+    // entry i's k output slots; the slots past the count hold the miss
+    void store(uint32_t i, float* t_out, float* u_out, float* v_out, uint32_t* tri_out, uint32_t* count_out) const {
+        if (count_out) count_out[i] = (uint32_t)hits.size();
+        for (size_t s = 0; s < k; ++s) {
+            const bool hit = s < hits.size();
+            const size_t at = (size_t)i * k + s;
+            if (t_out) t_out[at] = hit ? hits[s].t : std::numeric_limits<float>::infinity();
+            if (u_out) u_out[at] = hit ? hits[s].u : 0.0f;
+            if (v_out) v_out[at] = hit ? hits[s].v : 0.0f;
+            if (tri_out) tri_out[at] = hit ? hits[s].tri : kNoTri;
+        }
+    }
+};
+// what both list walks refuse, `key` being the name of the key's first half
+bool list_args_ok(uint32_t k, const float* key_t, const uint32_t* key_tri, const char* key, int use_bvh, const HostScene& hs, std::string& err) {
+    if (use_bvh != 0 && use_bvh != 1) err = "use_bvh: 0 brute force, 1 the kernel's walk";
+    else if (k < 1) err = "k must be at least 1";
+    else if (!key_t != !key_tri) err = std::string("a resume key is ") + key + " and after_tri, both or neither";
+    else if (use_bvh && hs.nodes.empty()) err = "no tree";
+    return err.empty();
+}
+// triangle j of hs.wverts as the records hold it: v0, e1 = v1 - v0, e2 = v2 - v0
+struct WorldTri {
+    const float* v0;
+    float e1[3], e2[3];
+    explicit WorldTri(const float* w) : v0(w), e1{w[3] - w[0], w[4] - w[1], w[5] - w[2]}, e2{w[6] - w[0], w[7] - w[1], w[8] - w[2]} {}
+};
+
+} // namespace
+
 // ---- node visits of a closest-hit walk on the host (rt_scene_count_visits) --------------------------------------------------------------------
 // The walk the traversal kernels make — children entered nearest first, the others stacked, everything beyond the closest hit so far culled —
 // with a choice of the child boxes it tests:
@@ -287,60 +433,38 @@ int count_visits(const HostScene& hs, uint32_t n, const float* org, const float*
     Box3 all;
     (void)exact_boxes(hs, 0, 0, all, [](int32_t, uint32_t) { return true; }, tested);
     uint64_t visits = 0, tests = 0;
+    std::vector<int32_t> stack;
     for (uint32_t i = 0; i < n; ++i) {
         const float o[3] = {org[3 * i], org[3 * i + 1], org[3 * i + 2]}, d[3] = {dir[3 * i], dir[3 * i + 1], dir[3 * i + 2]};
         float inv[3];
-        for (int a = 0; a < 3; ++a) inv[a] = 1.0f / (std::fabs(d[a]) < 1e-30f ? std::copysign(1e-30f, d[a]) : d[a]);
+        ray_inverse(d, inv);
         float best = inf;
         uint32_t best_tri = kNoTri;
         uint32_t skip = kSkipNone;
         if (skipping && tri_out[i] != kNoTri) skip = origin_skip_word(hs.skip[tri_out[i]], o, d);
-        int32_t stack[kStackSize * 4];
-        int sp = 0;
-        int32_t cur = 0;
-        for (;;) {
-            if (cur >= 0) {
-                visits++;
-                const BvhNode& nd = hs.nodes[(size_t)cur];
-                float key[4];
-                int32_t ch[4];
-                int m = 0;
-                for (int k = 0; k < 4; ++k) {
-                    if (nd.child[k] == kChildEmpty || device_child_word(nd.child[k]) == skip) continue;
-                    const Box3& b = box[(size_t)cur * 4 + k];
-                    float tn = 0.0f, tf = best;
-                    for (int a = 0; a < 3; ++a) {
-                        const float t0 = (b.lo[a] - o[a]) * inv[a], t1 = (b.hi[a] - o[a]) * inv[a];
-                        tn = std::max(tn, std::min(t0, t1)), tf = std::min(tf, std::max(t0, t1));
-                    }
-                    if (tn <= tf) key[m] = tn, ch[m] = nd.child[k], m++;
-                }
-                for (int a = 1; a < m; ++a) // nearest first
-                    for (int b = a; b > 0 && key[b] < key[b - 1]; --b) std::swap(key[b], key[b - 1]), std::swap(ch[b], ch[b - 1]);
-                for (int a = m - 1; a >= 1; --a) stack[sp++] = ch[a];
-                if (m) { cur = ch[0]; continue; }
-            } else {
-                const LeafRange leaf = leaf_range(cur);
-                for (uint32_t k = 0; k < leaf.count; ++k) {
-                    tests++;
-                    const TriRec& tr = hs.tris[leaf.first + k];
-                    // Moller-Trumbore on (v0, e1, e2), in double: only the count matters here
-                    const double e1[3] = {tr.e1[0], tr.e1[1], tr.e1[2]}, e2[3] = {tr.e2[0], tr.e2[1], tr.e2[2]};
-                    const double p[3] = {d[1] * e2[2] - d[2] * e2[1], d[2] * e2[0] - d[0] * e2[2], d[0] * e2[1] - d[1] * e2[0]};
-                    const double det = e1[0] * p[0] + e1[1] * p[1] + e1[2] * p[2];
-                    if (det == 0.0) continue;
-                    const double tv[3] = {o[0] - tr.v0[0], o[1] - tr.v0[1], o[2] - tr.v0[2]};
-                    const double u = (tv[0] * p[0] + tv[1] * p[1] + tv[2] * p[2]) / det;
-                    const double q[3] = {tv[1] * e1[2] - tv[2] * e1[1], tv[2] * e1[0] - tv[0] * e1[2], tv[0] * e1[1] - tv[1] * e1[0]};
-                    const double v = (d[0] * q[0] + d[1] * q[1] + d[2] * q[2]) / det;
-                    if (u < 0.0 || v < 0.0 || u + v > 1.0) continue;
-                    const double t = (e2[0] * q[0] + e2[1] * q[1] + e2[2] * q[2]) / det;
-                    if (t > (double)kTNear && (t < best || (t == best && tr.global_index < best_tri))) best = (float)t, best_tri = tr.global_index;
-                }
-            }
-            if (sp == 0) break;
-            cur = stack[--sp];
-        }
+        walk_tree(stack, visits,
+                  [&](int32_t& cur) {
+                      const Box3* b = &box[(size_t)cur * 4];
+                      return ray_inner(hs.nodes[(size_t)cur], o, inv, best, skip, [&](int k) { return b[k]; }, stack, cur);
+                  },
+                  [&](const LeafRange& leaf) {
+                      for (uint32_t k = 0; k < leaf.count; ++k) {
+                          tests++;
+                          const TriRec& tr = hs.tris[leaf.first + k];
+                          // Moller-Trumbore on (v0, e1, e2), in double: only the count matters here
+                          const double e1[3] = {tr.e1[0], tr.e1[1], tr.e1[2]}, e2[3] = {tr.e2[0], tr.e2[1], tr.e2[2]};
+                          const double p[3] = {d[1] * e2[2] - d[2] * e2[1], d[2] * e2[0] - d[0] * e2[2], d[0] * e2[1] - d[1] * e2[0]};
+                          const double det = e1[0] * p[0] + e1[1] * p[1] + e1[2] * p[2];
+                          if (det == 0.0) continue;
+                          const double tv[3] = {o[0] - tr.v0[0], o[1] - tr.v0[1], o[2] - tr.v0[2]};
+                          const double u = (tv[0] * p[0] + tv[1] * p[1] + tv[2] * p[2]) / det;
+                          const double q[3] = {tv[1] * e1[2] - tv[2] * e1[1], tv[2] * e1[0] - tv[0] * e1[2], tv[0] * e1[1] - tv[1] * e1[0]};
+                          const double v = (d[0] * q[0] + d[1] * q[1] + d[2] * q[2]) / det;
+                          if (u < 0.0 || v < 0.0 || u + v > 1.0) continue;
+                          const double t = (e2[0] * q[0] + e2[1] * q[1] + e2[2] * q[2]) / det;
+                          if (t > (double)kTNear && (t < best || (t == best && tr.global_index < best_tri))) best = (float)t, best_tri = tr.global_index;
+                      }
+                  });
         if (t_out) t_out[i] = best;
         if (tri_out) tri_out[i] = best_tri;
     }
@@ -374,37 +498,10 @@ int closest_host(const HostScene& hs, uint32_t n, const float* pos, const float*
         if (!use_bvh) {
             for (const TriRec& tr : hs.tris) test(tr);
         } else {
-            stack.clear();
-            int32_t cur = 0;
-            for (;;) {
-                if (cur >= 0) {
-                    visits++;
-                    const BvhNode& nd = hs.nodes[(size_t)cur];
-                    float key[4];
-                    int32_t ch[4];
-                    for (int k = 0; k < 4; ++k) {
-                        ch[k] = nd.child[k], key[k] = inf;
-                        if (nd.child[k] == kChildEmpty) continue; // (its inverted box gives a finite lb: the word is what says it is absent)
-                        float lb = 0.0f;
-                        for (int a = 0; a < 3; ++a) {
-                            const float lo = child_plane(nd, k, a, 0), hi = child_plane(nd, k, a, 1);
-                            const float e = std::max(std::max(lo - p[a], p[a] - hi), 0.0f);
-                            lb = std::fma(e, e, lb);
-                        }
-                        if (closest_enters(lb, best)) key[k] = std::min(lb, std::numeric_limits<float>::max()); // (an lb that overflowed is still a key)
-                    }
-                    auto ce = [&](int a, int b) { if (key[b] < key[a]) std::swap(key[a], key[b]), std::swap(ch[a], ch[b]); };
-                    ce(0, 1), ce(2, 3), ce(0, 2), ce(1, 3), ce(1, 2);
-                    for (int k = 3; k >= 1; --k)
-                        if (key[k] < inf) stack.push_back(ch[k]);
-                    if (key[0] < inf) { cur = ch[0]; continue; }
-                } else {
-                    const LeafRange leaf = leaf_range(cur);
-                    for (uint32_t k = 0; k < leaf.count; ++k) test(hs.tris[leaf.first + k]);
-                }
-                if (stack.empty()) break;
-                cur = stack.back(), stack.pop_back();
-            }
+            walk_tree(stack, visits, [&](int32_t& cur) { return point_inner(hs.nodes[(size_t)cur], p, best, stack, cur); },
+                      [&](const LeafRange& leaf) {
+                          for (uint32_t k = 0; k < leaf.count; ++k) test(hs.tris[leaf.first + k]);
+                      });
         }
         const bool hit = best_tri != kNoTri;
         if (dist2_out) dist2_out[i] = hit ? best : inf;
@@ -432,92 +529,35 @@ int closest_host(const HostScene& hs, uint32_t n, const float* pos, const float*
 int nearest_host(const HostScene& hs, uint32_t n, uint32_t k, const float* pos, const float* max_dist2, const float* after_dist2,
                  const uint32_t* after_tri, int use_bvh, float* dist2_out, float* u_out, float* v_out, uint32_t* tri_out, uint32_t* count_out,
                  uint64_t* node_visits, uint64_t* tri_tests, std::string& err) {
-    if (use_bvh != 0 && use_bvh != 1) { err = "use_bvh: 0 brute force, 1 the kernel's walk"; return RT_ERR_INVALID; }
-    if (k < 1) { err = "k must be at least 1"; return RT_ERR_INVALID; }
-    if (!after_dist2 != !after_tri) { err = "a resume key is after_dist2 and after_tri, both or neither"; return RT_ERR_INVALID; }
-    if (use_bvh && hs.nodes.empty()) { err = "no tree"; return RT_ERR_INVALID; }
-    struct Near {
-        float dist2, u, v;
-        uint32_t tri;
-    };
-    const float inf = std::numeric_limits<float>::infinity();
+    if (!list_args_ok(k, after_dist2, after_tri, "after_dist2", use_bvh, hs, err)) return RT_ERR_INVALID;
     const size_t T = hs.wverts.size() / 9;
     uint64_t visits = 0, tests = 0;
-    std::vector<Near> list;
+    KeyedList list(k);
     std::vector<int32_t> stack;
     for (uint32_t i = 0; i < n; ++i) {
         const float p[3] = {pos[3 * (size_t)i], pos[3 * (size_t)i + 1], pos[3 * (size_t)i + 2]};
-        const float md = max_dist2 ? max_dist2[i] : inf;
-        const float kd = after_dist2 ? after_dist2[i] : -inf;
-        const uint32_t ktri = after_dist2 ? after_tri[i] : 0u;
-        auto behind_key = [&](float d2, uint32_t tri) { return d2 > kd || (d2 == kd && tri > ktri); };
-        list.clear();
+        list.open(i, max_dist2, after_dist2, after_tri);
+        auto candidate = [&](const float v0[3], const float e1[3], const float e2[3], uint32_t tri) {
+            tests++;
+            const ClosestPoint c = closest_point_on_record(p, v0, e1, e2);
+            return ListHit{c.dist2, c.u, c.v, tri};
+        };
         if (!use_bvh) {
             for (size_t j = 0; j < T; ++j) {
-                const float* w = &hs.wverts[9 * j];
-                const float e1[3] = {w[3] - w[0], w[4] - w[1], w[5] - w[2]}, e2[3] = {w[6] - w[0], w[7] - w[1], w[8] - w[2]};
-                tests++;
-                const ClosestPoint c = closest_point_on_record(p, w, e1, e2);
-                if (c.dist2 <= md && behind_key(c.dist2, (uint32_t)j)) list.push_back(Near{c.dist2, c.u, c.v, (uint32_t)j});
+                const WorldTri w(&hs.wverts[9 * j]);
+                list.add(candidate(w.v0, w.e1, w.e2, (uint32_t)j));
             }
-            std::stable_sort(list.begin(), list.end(), [](const Near& a, const Near& b) { return closest_better(a.dist2, a.tri, b.dist2, b.tri); });
-            if (list.size() > k) list.resize(k);
+            list.first_k();
         } else {
-            float best = md; // the bound
-            uint32_t best_tri = kNoTri;
-            stack.clear();
-            int32_t cur = 0;
-            for (;;) {
-                if (cur >= 0) {
-                    visits++;
-                    const BvhNode& nd = hs.nodes[(size_t)cur];
-                    float key[4];
-                    int32_t ch[4];
-                    for (int c = 0; c < 4; ++c) {
-                        ch[c] = nd.child[c], key[c] = inf;
-                        if (nd.child[c] == kChildEmpty) continue; // (its inverted box gives a finite lb: the word is what says it is absent)
-                        float lb = 0.0f;
-                        for (int a = 0; a < 3; ++a) {
-                            const float lo = child_plane(nd, c, a, 0), hi = child_plane(nd, c, a, 1);
-                            const float e = std::max(std::max(lo - p[a], p[a] - hi), 0.0f);
-                            lb = std::fma(e, e, lb);
-                        }
-                        if (closest_enters(lb, best)) key[c] = std::min(lb, std::numeric_limits<float>::max()); // (an lb that overflowed is still a key)
-                    }
-                    auto ce = [&](int a, int b) { if (key[b] < key[a]) std::swap(key[a], key[b]), std::swap(ch[a], ch[b]); };
-                    ce(0, 1), ce(2, 3), ce(0, 2), ce(1, 3), ce(1, 2);
-                    for (int c = 3; c >= 1; --c)
-                        if (key[c] < inf) stack.push_back(ch[c]);
-                    if (key[0] < inf) { cur = ch[0]; continue; }
-                } else {
-                    const LeafRange leaf = leaf_range(cur);
-                    for (uint32_t r = 0; r < leaf.count; ++r) {
-                        const TriRec& tr = hs.tris[leaf.first + r];
-                        tests++;
-                        const ClosestPoint c = closest_point_on_record(p, tr.v0, tr.e1, tr.e2);
-                        if (!closest_better(c.dist2, tr.global_index, best, best_tri) || !behind_key(c.dist2, tr.global_index)) continue;
-                        size_t at = 0;
-                        bool listed = false;
-                        for (const Near& h : list) listed = listed || h.tri == tr.global_index, at += closest_better(h.dist2, h.tri, c.dist2, tr.global_index) ? 1 : 0;
-                        if (listed) continue;
-                        list.insert(list.begin() + (ptrdiff_t)at, Near{c.dist2, c.u, c.v, tr.global_index});
-                        if (list.size() > k) list.pop_back();
-                        if (list.size() == k) best = list.back().dist2, best_tri = list.back().tri;
-                    }
-                }
-                if (stack.empty()) break;
-                cur = stack.back(), stack.pop_back();
-            }
+            walk_tree(stack, visits, [&](int32_t& cur) { return point_inner(hs.nodes[(size_t)cur], p, list.bound, stack, cur); },
+                      [&](const LeafRange& leaf) {
+                          for (uint32_t r = 0; r < leaf.count; ++r) {
+                              const TriRec& tr = hs.tris[leaf.first + r];
+                              list.offer(candidate(tr.v0, tr.e1, tr.e2, tr.global_index));
+                          }
+                      });
         }
-        if (count_out) count_out[i] = (uint32_t)list.size();
-        for (uint32_t s = 0; s < k; ++s) {
-            const bool hit = s < list.size();
-            const size_t at = (size_t)i * k + s;
-            if (dist2_out) dist2_out[at] = hit ? list[s].dist2 : inf;
-            if (u_out) u_out[at] = hit ? list[s].u : 0.0f;
-            if (v_out) v_out[at] = hit ? list[s].v : 0.0f;
-            if (tri_out) tri_out[at] = hit ? list[s].tri : kNoTri;
-        }
+        list.store(i, dist2_out, u_out, v_out, tri_out, count_out);
     }
     if (node_visits) *node_visits = visits;
     if (tri_tests) *tri_tests = tests;
@@ -526,18 +566,13 @@ int nearest_host(const HostScene& hs, uint32_t n, uint32_t k, const float* pos, 
 
 // ---- multi-hit ray queries on the host (rt_scene_multihit_host; include/rt_mi355x.h: rt_multihit_query) -------------------------------------
 namespace {
-struct RayHit {
-    float t, u, v;
-    uint32_t tri;
-};
-inline bool hit_before(float t, uint32_t tri, float bt, uint32_t btri) { return t < bt || (t == bt && tri < btri); }
 inline float dot_f(const float a[3], const float b[3]) { return std::fma(a[2], b[2], std::fma(a[1], b[1], a[0] * b[0])); }
 inline void cross_f(const float a[3], const float b[3], float r[3]) {
     r[0] = std::fma(a[1], b[2], -(a[2] * b[1])), r[1] = std::fma(a[2], b[0], -(a[0] * b[2])), r[2] = std::fma(a[0], b[1], -(a[1] * b[0]));
 }
 // The candidate of one triangle (v0, e1, e2) for a ray: R5's test as rt_device.h: tri_test_regs states it for the kernels — the fused
 // cross and dot products, the edge tests on the numerators, inv = RN(1 / det), t > kTNear. false: no candidate.
-inline bool ray_candidate(const float v0[3], const float e1[3], const float e2[3], const float o[3], const float d[3], RayHit& c) {
+inline bool ray_candidate(const float v0[3], const float e1[3], const float e2[3], const float o[3], const float d[3], ListHit& c) {
     float p[3], q[3];
     cross_f(d, e2, p);
     const float det = dot_f(e1, p);
@@ -567,90 +602,41 @@ inline bool ray_candidate(const float v0[3], const float e1[3], const float e2[3
 int multihit_host(const HostScene& hs, uint32_t n, uint32_t k, const float* org, const float* dir, const float* tmax, const float* after_t,
                   const uint32_t* after_tri, int use_bvh, float* t_out, float* u_out, float* v_out, uint32_t* tri_out, uint32_t* count_out,
                   uint64_t* node_visits, uint64_t* tri_tests, std::string& err) {
-    if (use_bvh != 0 && use_bvh != 1) { err = "use_bvh: 0 brute force, 1 the kernel's walk"; return RT_ERR_INVALID; }
-    if (k < 1) { err = "k must be at least 1"; return RT_ERR_INVALID; }
-    if (!after_t != !after_tri) { err = "a resume key is after_t and after_tri, both or neither"; return RT_ERR_INVALID; }
-    if (use_bvh && hs.nodes.empty()) { err = "no tree"; return RT_ERR_INVALID; }
-    const float inf = std::numeric_limits<float>::infinity();
+    if (!list_args_ok(k, after_t, after_tri, "after_t", use_bvh, hs, err)) return RT_ERR_INVALID;
     const size_t T = hs.wverts.size() / 9;
     uint64_t visits = 0, tests = 0;
-    std::vector<RayHit> list;
+    KeyedList list(k);
     std::vector<int32_t> stack;
     for (uint32_t i = 0; i < n; ++i) {
         const float o[3] = {org[3 * (size_t)i], org[3 * (size_t)i + 1], org[3 * (size_t)i + 2]};
         const float d[3] = {dir[3 * (size_t)i], dir[3 * (size_t)i + 1], dir[3 * (size_t)i + 2]};
-        const float tm = tmax ? tmax[i] : inf;
-        const float kt = after_t ? after_t[i] : -inf;
-        const uint32_t ktri = after_t ? after_tri[i] : 0u;
-        auto counts = [&](const RayHit& c) { return c.t <= tm && (c.t > kt || (c.t == kt && c.tri > ktri)); };
-        list.clear();
+        list.open(i, tmax, after_t, after_tri);
         if (!use_bvh) {
             for (size_t j = 0; j < T; ++j) {
-                const float* w = &hs.wverts[9 * j];
-                const float e1[3] = {w[3] - w[0], w[4] - w[1], w[5] - w[2]}, e2[3] = {w[6] - w[0], w[7] - w[1], w[8] - w[2]};
-                RayHit c{0.0f, 0.0f, 0.0f, (uint32_t)j};
+                const WorldTri w(&hs.wverts[9 * j]);
+                ListHit c{0.0f, 0.0f, 0.0f, (uint32_t)j};
                 tests++;
-                if (ray_candidate(w, e1, e2, o, d, c) && counts(c)) list.push_back(c);
+                if (ray_candidate(w.v0, w.e1, w.e2, o, d, c)) list.add(c);
             }
-            std::stable_sort(list.begin(), list.end(), [](const RayHit& a, const RayHit& b) { return hit_before(a.t, a.tri, b.t, b.tri); });
-            if (list.size() > k) list.resize(k);
+            list.first_k();
         } else {
             float inv[3];
-            for (int a = 0; a < 3; ++a) inv[a] = 1.0f / (std::fabs(d[a]) < 1e-30f ? std::copysign(1e-30f, d[a]) : d[a]);
-            float bt = tm; // the bound
-            uint32_t btri = kNoTri;
-            stack.clear();
-            int32_t cur = 0;
-            for (;;) {
-                if (cur >= 0) {
-                    visits++;
-                    const BvhNode& nd = hs.nodes[(size_t)cur];
-                    float key[4];
-                    int32_t ch[4];
-                    int m = 0;
-                    for (int c = 0; c < 4; ++c) {
-                        if (nd.child[c] == kChildEmpty) continue;
-                        const Box3 b = child_box(nd, c);
-                        float tn = 0.0f, tf = bt;
-                        for (int a = 0; a < 3; ++a) {
-                            const float t0 = (b.lo[a] - o[a]) * inv[a], t1 = (b.hi[a] - o[a]) * inv[a];
-                            tn = std::max(tn, std::min(t0, t1)), tf = std::min(tf, std::max(t0, t1));
-                        }
-                        if (tn <= tf) key[m] = tn, ch[m] = nd.child[c], m++; // (a box AT the bound stays: a tie at a lower index is behind it)
-                    }
-                    for (int a = 1; a < m; ++a) // nearest first
-                        for (int b = a; b > 0 && key[b] < key[b - 1]; --b) std::swap(key[b], key[b - 1]), std::swap(ch[b], ch[b - 1]);
-                    for (int a = m - 1; a >= 1; --a) stack.push_back(ch[a]);
-                    if (m) { cur = ch[0]; continue; }
-                } else {
-                    const LeafRange leaf = leaf_range(cur);
-                    for (uint32_t r = 0; r < leaf.count; ++r) {
-                        const TriRec& tr = hs.tris[leaf.first + r];
-                        RayHit c{0.0f, 0.0f, 0.0f, tr.global_index};
-                        tests++;
-                        if (!ray_candidate(tr.v0, tr.e1, tr.e2, o, d, c) || !hit_before(c.t, c.tri, bt, btri) || !counts(c)) continue;
-                        size_t at = 0;
-                        bool listed = false;
-                        for (const RayHit& h : list) listed = listed || h.tri == c.tri, at += hit_before(h.t, h.tri, c.t, c.tri) ? 1 : 0;
-                        if (listed) continue;
-                        list.insert(list.begin() + (ptrdiff_t)at, c);
-                        if (list.size() > k) list.pop_back();
-                        if (list.size() == k) bt = list.back().t, btri = list.back().tri;
-                    }
-                }
-                if (stack.empty()) break;
-                cur = stack.back(), stack.pop_back();
-            }
+            ray_inverse(d, inv);
+            walk_tree(stack, visits,
+                      [&](int32_t& cur) {
+                          const BvhNode& nd = hs.nodes[(size_t)cur];
+                          return ray_inner(nd, o, inv, list.bound, kSkipNone, [&](int c) { return child_box(nd, c); }, stack, cur);
+                      },
+                      [&](const LeafRange& leaf) {
+                          for (uint32_t r = 0; r < leaf.count; ++r) {
+                              const TriRec& tr = hs.tris[leaf.first + r];
+                              ListHit c{0.0f, 0.0f, 0.0f, tr.global_index};
+                              tests++;
+                              if (ray_candidate(tr.v0, tr.e1, tr.e2, o, d, c)) list.offer(c);
+                          }
+                      });
         }
-        if (count_out) count_out[i] = (uint32_t)list.size();
-        for (uint32_t s = 0; s < k; ++s) {
-            const bool hit = s < list.size();
-            const size_t at = (size_t)i * k + s;
-            if (t_out) t_out[at] = hit ? list[s].t : inf;
-            if (u_out) u_out[at] = hit ? list[s].u : 0.0f;
-            if (v_out) v_out[at] = hit ? list[s].v : 0.0f;
-            if (tri_out) tri_out[at] = hit ? list[s].tri : kNoTri;
-        }
+        list.store(i, t_out, u_out, v_out, tri_out, count_out);
     }
     if (node_visits) *node_visits = visits;
     if (tri_tests) *tri_tests = tests;

@@ -135,6 +135,121 @@ class Scene:
                              occluded=d_occluded or None)
         abi.check(self._lib.rt_trace_rays_device(self.h, C.byref(q), C.c_void_p(stream or None)), self._lib)
 
+    # ---- what the point and list queries check and allocate alike ---------------------------------------------------------------------------
+    @staticmethod
+    def _check_k(k, k_max):
+        """k an integer 1 .. k_max (None: no upper bound)"""
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 1 or (k_max is not None and k > k_max):
+            raise ValueError(f"k must be an integer from 1 to {k_max}" if k_max is not None else "k must be an integer, at least 1")
+
+    @staticmethod
+    def _check_limit(limit, name):
+        """max_items / max_hits: an integer, at least 1, or None"""
+        if limit is not None and (isinstance(limit, bool) or not isinstance(limit, (int, np.integer)) or limit < 1):
+            raise ValueError(f"{name} must be an integer, at least 1, or None")
+
+    @staticmethod
+    def _check_after(after, n, first):
+        """a resume key: the pair (`first` (n,) floats, after_tri (n,) integers) or None -> (float32, uint32 arrays) or (None, None)"""
+        if after is None:
+            return None, None
+        if not isinstance(after, (tuple, list)) or len(after) != 2:
+            raise ValueError(f"after must be the pair ({first}, after_tri)")
+        at, atri = np.asarray(after[0]), np.asarray(after[1])
+        if at.shape != (n,) or at.dtype.kind != "f" or atri.shape != (n,) or atri.dtype.kind not in "iu":
+            raise ValueError(f"after must be ({first} (n,) floats, after_tri (n,) integers)")
+        return np.ascontiguousarray(at, np.float32), np.ascontiguousarray(atri).astype(np.uint32)
+
+    @staticmethod
+    def _radius2(max_dist, n, numbers_only):
+        """a caller's radius, one number or (n,), none negative -> (n,) float32, the radius squared in fp32 (the ABI's radius is squared, and a
+        negative one would square to a positive one), or None for None. numbers_only: a dtype that is no number is refused (the list
+        queries); closest_points converts whatever numpy converts."""
+        if max_dist is None:
+            return None
+        shape = "max_dist must be one radius or hold one per point, shape (n,)"
+        if numbers_only:
+            md = np.asarray(max_dist)
+            if md.dtype.kind not in "fiu":
+                raise ValueError(shape)
+            md = md.astype(np.float32)
+        else:
+            md = np.asarray(max_dist, np.float32)
+        if md.ndim == 0:
+            md = np.full(n, md, np.float32)
+        if md.shape != (n,):
+            raise ValueError(shape)
+        if (md < 0).any():
+            raise ValueError("max_dist must not be negative")
+        return np.ascontiguousarray(md * md)
+
+    @staticmethod
+    def _per_point(max_dist2, n):
+        """a host diagnostic's SQUARED radii, any values: (n,) float32 or None"""
+        if max_dist2 is None:
+            return None
+        md = np.ascontiguousarray(max_dist2, np.float32).reshape(-1)
+        if md.shape[0] != n:
+            raise ValueError("max_dist2 must hold one value per point")
+        return md
+
+    @staticmethod
+    def _point_outputs(n):
+        """a closest-point query's outputs"""
+        return {"dist2": np.zeros(n, np.float32), "u": np.zeros(n, np.float32), "v": np.zeros(n, np.float32), "tri": np.zeros(n, np.uint32),
+                "point": np.zeros((n, 3), np.float32)}
+
+    @staticmethod
+    def _slot_outputs(n, k, first, slots=True):
+        """a list query's outputs: `first` ("t" or "dist2"), "u", "v" (n, k) float32 and "tri" (n, k) uint32 (not with slots = False), "count" (n,)"""
+        out = {}
+        if slots:
+            out = {first: np.zeros((n, k), np.float32), "u": np.zeros((n, k), np.float32), "v": np.zeros((n, k), np.float32),
+                   "tri": np.zeros((n, k), np.uint32)}
+        out["count"] = np.zeros(n, np.uint32)
+        return out
+
+    def _list_host(self, call, n, k, inputs, first, use_bvh, slots) -> dict:
+        """the tail of nearest_host and multihit_host: the outputs (slots = False: only "count"), the call with `inputs` (arrays or None) and
+        the two counters"""
+        out = self._slot_outputs(n, k, first, slots)
+        ptr = lambda a: None if a is None else (abi.u32ptr if a.dtype == np.uint32 else abi.fptr)(a)
+        nv, nt = C.c_uint64(0), C.c_uint64(0)
+        abi.check(call(self.h, n, k, *map(ptr, inputs), 1 if use_bvh else 0, *(ptr(out.get(name)) for name in (first, "u", "v", "tri", "count")),
+                       C.byref(nv), C.byref(nt)), self._lib)
+        out["node_visits"], out["tri_tests"] = int(nv.value), int(nt.value)
+        return out
+
+    @staticmethod
+    def _page_all(n, page, limit, first, call):
+        """closest_all's and trace_all's paging: call(active, key) -> a page of `page` slots for the entries `active` behind `key` (the pair
+        (`first`, tri) of their last slots, None on the first page), every entry continued until it is exhausted or holds `limit` items.
+        -> CSR arrays (offsets (n + 1,) int64, `first`, u, v float32, tri uint32)"""
+        active, key, pages = np.arange(n), None, []
+        total = np.zeros(n, np.int64)
+        while len(active):
+            out = call(active, key)
+            cnt = out["count"].astype(np.int64)
+            if limit is not None:
+                cnt = np.minimum(cnt, limit - total[active])
+            pages.append((active, total[active].copy(), cnt, out))
+            total[active] += cnt
+            more = out["count"] == page
+            if limit is not None:
+                more &= total[active] < limit
+            key = (np.ascontiguousarray(out[first][more, page - 1]), np.ascontiguousarray(out["tri"][more, page - 1]))
+            active = active[more]
+        offsets = np.zeros(n + 1, np.int64)
+        np.cumsum(total, out=offsets[1:])
+        res = {name: np.zeros(int(offsets[-1]), np.uint32 if name == "tri" else np.float32) for name in (first, "u", "v", "tri")}
+        for entries, start, cnt, out in pages:
+            slot = np.arange(page)[None, :]
+            take = slot < cnt[:, None]
+            at = (offsets[entries] + start)[:, None] + slot
+            for name, a in res.items():
+                a[at[take]] = out[name][take]
+        return offsets, res[first], res["u"], res["v"], res["tri"]
+
     def closest_points(self, pos: np.ndarray, max_dist=None) -> dict:
         """rt_closest_points on host arrays: pos (n, 3) float32; max_dist a radius (one number or (n,)), squared here in fp32, or None
         (+inf). Returns {"dist2", "u", "v": (n,) float32, "tri": (n,) uint32, "point": (n, 3) float32, "dist": sqrt(dist2)}: the nearest
@@ -145,19 +260,9 @@ class Scene:
             raise ValueError("pos must be (n, 3)")
         n = pos.shape[0]
         pos = np.ascontiguousarray(pos, np.float32)
-        q = abi.rt_point_query(n=n, pos=pos.ctypes.data)
-        if max_dist is not None:
-            md = np.asarray(max_dist, np.float32)
-            if md.ndim == 0:
-                md = np.full(n, md, np.float32)
-            if md.shape != (n,):
-                raise ValueError("max_dist must be one radius or hold one per point, shape (n,)")
-            md2 = np.ascontiguousarray(md * md)  # (a negative radius squares to a positive one: refused here, the ABI's radius is squared)
-            if (md < 0).any():
-                raise ValueError("max_dist must not be negative")
-            q.max_dist2 = md2.ctypes.data
-        out = {"dist2": np.zeros(n, np.float32), "u": np.zeros(n, np.float32), "v": np.zeros(n, np.float32), "tri": np.zeros(n, np.uint32),
-               "point": np.zeros((n, 3), np.float32)}
+        md2 = self._radius2(max_dist, n, numbers_only=False)
+        q = abi.rt_point_query(n=n, pos=pos.ctypes.data, max_dist2=None if md2 is None else md2.ctypes.data)
+        out = self._point_outputs(n)
         for name, a in out.items():
             setattr(q, name, a.ctypes.data)
         abi.check(self._lib.rt_closest_points(self.h, C.byref(q)), self._lib)
@@ -178,13 +283,8 @@ class Scene:
         "tri_tests"."""
         pos = np.ascontiguousarray(pos, np.float32).reshape(-1, 3)
         n = pos.shape[0]
-        md = None
-        if max_dist2 is not None:
-            md = np.ascontiguousarray(max_dist2, np.float32).reshape(-1)
-            if md.shape[0] != n:
-                raise ValueError("max_dist2 must hold one value per point")
-        out = {"dist2": np.zeros(n, np.float32), "u": np.zeros(n, np.float32), "v": np.zeros(n, np.float32), "tri": np.zeros(n, np.uint32),
-               "point": np.zeros((n, 3), np.float32)}
+        md = self._per_point(max_dist2, n)
+        out = self._point_outputs(n)
         nv, nt = C.c_uint64(0), C.c_uint64(0)
         abi.check(self._lib.rt_scene_closest_host(self.h, n, abi.fptr(pos), abi.fptr(md) if md is not None else None, 1 if use_bvh else 0,
                                                   abi.fptr(out["dist2"]), abi.fptr(out["u"]), abi.fptr(out["v"]), abi.u32ptr(out["tri"]),
@@ -201,31 +301,9 @@ class Scene:
         if pos.ndim != 2 or pos.shape[1] != 3:
             raise ValueError("pos must be (n, 3)")
         n = pos.shape[0]
-        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 1 or (k_max is not None and k > k_max):
-            raise ValueError(f"k must be an integer from 1 to {k_max}" if k_max is not None else "k must be an integer, at least 1")
+        Scene._check_k(k, k_max)
         pos = np.ascontiguousarray(pos, np.float32)
-        md2 = None
-        if max_dist is not None:
-            md = np.asarray(max_dist)
-            if md.dtype.kind not in "fiu":
-                raise ValueError("max_dist must be one radius or hold one per point, shape (n,)")
-            md = md.astype(np.float32)
-            if md.ndim == 0:
-                md = np.full(n, md, np.float32)
-            if md.shape != (n,):
-                raise ValueError("max_dist must be one radius or hold one per point, shape (n,)")
-            if (md < 0).any():
-                raise ValueError("max_dist must not be negative")
-            md2 = np.ascontiguousarray(md * md)
-        ad = atri = None
-        if after is not None:
-            if not isinstance(after, (tuple, list)) or len(after) != 2:
-                raise ValueError("after must be the pair (after_dist2, after_tri)")
-            ad, atri = np.asarray(after[0]), np.asarray(after[1])
-            if ad.shape != (n,) or ad.dtype.kind != "f" or atri.shape != (n,) or atri.dtype.kind not in "iu":
-                raise ValueError("after must be (after_dist2 (n,) floats, after_tri (n,) integers)")
-            ad, atri = np.ascontiguousarray(ad, np.float32), np.ascontiguousarray(atri).astype(np.uint32)
-        return n, pos, md2, ad, atri
+        return (n, pos, Scene._radius2(max_dist, n, numbers_only=True)) + Scene._check_after(after, n, "after_dist2")
 
     def closest_points_multi(self, pos: np.ndarray, k: int, max_dist=None, after=None) -> dict:
         """rt_closest_points_multi on host arrays: the k nearest counting triangles of every point in ascending (dist2, triangle index)
@@ -239,11 +317,10 @@ class Scene:
 
     def _nearest_call(self, pos, k, md2, key) -> dict:
         """closest_points_multi behind its checks: md2 already SQUARED (closest_all pages with the radius squared once), key = (after_dist2,
-        after_tri), both arrays or both None"""
+        after_tri), both arrays or both None, or None"""
         n = len(pos)
-        ad, atri = key
-        out = {"dist2": np.zeros((n, k), np.float32), "u": np.zeros((n, k), np.float32), "v": np.zeros((n, k), np.float32),
-               "tri": np.zeros((n, k), np.uint32), "count": np.zeros(n, np.uint32)}
+        ad, atri = key or (None, None)
+        out = self._slot_outputs(n, k, "dist2")
         q = abi.rt_nearest_query(n=n, k=k, pos=pos.ctypes.data, max_dist2=None if md2 is None else md2.ctypes.data,
                                  after_dist2=None if ad is None else ad.ctypes.data, after_tri=None if atri is None else atri.ctypes.data)
         for name, a in out.items():
@@ -268,24 +345,8 @@ class Scene:
         included: the diagnostic refuses nothing) or None. Returns closest_points_multi's arrays (without "dist") and "node_visits",
         "tri_tests"; slots = False: only "count" and the two counters (the slot arrays are not allocated: a large k)."""
         n, pos, _, ad, atri = self._nearest_args(pos, k, None, after, None)
-        k = int(k)
-        md = None
-        if max_dist2 is not None:
-            md = np.ascontiguousarray(max_dist2, np.float32).reshape(-1)
-            if md.shape[0] != n:
-                raise ValueError("max_dist2 must hold one value per point")
-        out = {"count": np.zeros(n, np.uint32)}
-        if slots:
-            out.update({"dist2": np.zeros((n, k), np.float32), "u": np.zeros((n, k), np.float32), "v": np.zeros((n, k), np.float32),
-                        "tri": np.zeros((n, k), np.uint32)})
-        fp = lambda name: abi.fptr(out[name]) if name in out else None
-        nv, nt = C.c_uint64(0), C.c_uint64(0)
-        abi.check(self._lib.rt_scene_nearest_host(self.h, n, k, abi.fptr(pos), abi.fptr(md) if md is not None else None,
-                                                  abi.fptr(ad) if ad is not None else None, abi.u32ptr(atri) if atri is not None else None,
-                                                  1 if use_bvh else 0, fp("dist2"), fp("u"), fp("v"), abi.u32ptr(out["tri"]) if slots else None,
-                                                  abi.u32ptr(out["count"]), C.byref(nv), C.byref(nt)), self._lib)
-        out["node_visits"], out["tri_tests"] = int(nv.value), int(nt.value)
-        return out
+        md = self._per_point(max_dist2, n)
+        return self._list_host(self._lib.rt_scene_nearest_host, n, int(k), (pos, md, ad, atri), "dist2", use_bvh, slots)
 
     def closest_all(self, pos: np.ndarray, max_dist, page: int = 8, max_items: int | None = None):
         """Every triangle within max_dist of every point, in (dist2, triangle index) order: pages of `page` triangles
@@ -295,38 +356,11 @@ class Scene:
         unless max_items is given. A host-only scene (device < 0) pages through nearest_host's brute force instead: it has no device to
         ask."""
         n, pos, md2, _, _ = self._nearest_args(pos, page, max_dist, None, abi.RT_NEAREST_MAX)
-        if max_items is not None and (isinstance(max_items, bool) or not isinstance(max_items, (int, np.integer)) or max_items < 1):
-            raise ValueError("max_items must be an integer, at least 1, or None")
+        self._check_limit(max_items, "max_items")
         if max_dist is None and max_items is None:
             raise ValueError("max_dist = None lists every triangle of the scene for every point: give max_items to bound it")
-        if self.device >= 0:
-            call = lambda p, m, key: self._nearest_call(p, page, m, key)
-        else:
-            call = lambda p, m, key: self.nearest_host(p, page, m, None if key[0] is None else key)
-        active, key, pages = np.arange(n), (None, None), []
-        total = np.zeros(n, np.int64)
-        while len(active):
-            out = call(np.ascontiguousarray(pos[active]), None if md2 is None else np.ascontiguousarray(md2[active]), key)
-            cnt = out["count"].astype(np.int64)
-            if max_items is not None:
-                cnt = np.minimum(cnt, max_items - total[active])
-            pages.append((active, total[active].copy(), cnt, out))
-            total[active] += cnt
-            more = out["count"] == page
-            if max_items is not None:
-                more &= total[active] < max_items
-            key = (np.ascontiguousarray(out["dist2"][more, page - 1]), np.ascontiguousarray(out["tri"][more, page - 1]))
-            active = active[more]
-        offsets = np.zeros(n + 1, np.int64)
-        np.cumsum(total, out=offsets[1:])
-        res = {name: np.zeros(int(offsets[-1]), np.uint32 if name == "tri" else np.float32) for name in ("dist2", "u", "v", "tri")}
-        for pts, start, cnt, out in pages:
-            slot = np.arange(page)[None, :]
-            take = slot < cnt[:, None]
-            at = (offsets[pts] + start)[:, None] + slot
-            for name, a in res.items():
-                a[at[take]] = out[name][take]
-        return offsets, res["dist2"], res["u"], res["v"], res["tri"]
+        call = self._nearest_call if self.device >= 0 else self.nearest_host
+        return self._page_all(n, page, max_items, "dist2", lambda a, key: call(pos[a], page, None if md2 is None else md2[a], key))
 
     @staticmethod
     def _multi_args(org, dirs, k, tmax, after, k_max):
@@ -336,23 +370,14 @@ class Scene:
         if org.ndim != 2 or org.shape[1] != 3 or dirs.shape != org.shape:
             raise ValueError("org and dirs must both be (n, 3)")
         n = org.shape[0]
-        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 1 or (k_max is not None and k > k_max):
-            raise ValueError(f"k must be an integer from 1 to {k_max}" if k_max is not None else "k must be an integer, at least 1")
+        Scene._check_k(k, k_max)
         org, dirs = np.ascontiguousarray(org, np.float32), np.ascontiguousarray(dirs, np.float32)
         if tmax is not None:
             tmax = np.asarray(tmax)
             if tmax.shape != (n,) or tmax.dtype.kind not in "fiu":
                 raise ValueError("tmax must hold one number per ray, shape (n,)")
             tmax = np.ascontiguousarray(tmax, np.float32)
-        at = atri = None
-        if after is not None:
-            if not isinstance(after, (tuple, list)) or len(after) != 2:
-                raise ValueError("after must be the pair (after_t, after_tri)")
-            at, atri = np.asarray(after[0]), np.asarray(after[1])
-            if at.shape != (n,) or at.dtype.kind != "f" or atri.shape != (n,) or atri.dtype.kind not in "iu":
-                raise ValueError("after must be (after_t (n,) floats, after_tri (n,) integers)")
-            at, atri = np.ascontiguousarray(at, np.float32), np.ascontiguousarray(atri).astype(np.uint32)
-        return n, org, dirs, tmax, at, atri
+        return (n, org, dirs, tmax) + Scene._check_after(after, n, "after_t")
 
     def trace_multi(self, org: np.ndarray, dirs: np.ndarray, k: int, tmax=None, after=None) -> dict:
         """rt_trace_rays_multi on host arrays: the k nearest counting hits of every ray in ascending (t, triangle index) order. org, dirs
@@ -362,8 +387,7 @@ class Scene:
         rt_multihit_query)."""
         n, org, dirs, tmax, at, atri = self._multi_args(org, dirs, k, tmax, after, abi.RT_MULTIHIT_MAX)
         k = int(k)
-        out = {"t": np.zeros((n, k), np.float32), "u": np.zeros((n, k), np.float32), "v": np.zeros((n, k), np.float32),
-               "tri": np.zeros((n, k), np.uint32), "count": np.zeros(n, np.uint32)}
+        out = self._slot_outputs(n, k, "t")
         q = abi.rt_multihit_query(n=n, k=k, org=org.ctypes.data, dir=dirs.ctypes.data, tmax=None if tmax is None else tmax.ctypes.data,
                                   after_t=None if at is None else at.ctypes.data, after_tri=None if atri is None else atri.ctypes.data)
         for name, a in out.items():
@@ -386,19 +410,7 @@ class Scene:
         the kernel's walk of the tree, counted. k is any integer >= 1 here. Returns trace_multi's arrays and "node_visits", "tri_tests";
         slots = False: only "count" and the two counters (the slot arrays are not allocated: a large k)."""
         n, org, dirs, tmax, at, atri = self._multi_args(org, dirs, k, tmax, after, None)
-        k = int(k)
-        out = {"count": np.zeros(n, np.uint32)}
-        if slots:
-            out.update({"t": np.zeros((n, k), np.float32), "u": np.zeros((n, k), np.float32), "v": np.zeros((n, k), np.float32),
-                        "tri": np.zeros((n, k), np.uint32)})
-        fp = lambda name: abi.fptr(out[name]) if name in out else None
-        nv, nt = C.c_uint64(0), C.c_uint64(0)
-        abi.check(self._lib.rt_scene_multihit_host(self.h, n, k, abi.fptr(org), abi.fptr(dirs), abi.fptr(tmax) if tmax is not None else None,
-                                                   abi.fptr(at) if at is not None else None, abi.u32ptr(atri) if atri is not None else None,
-                                                   1 if use_bvh else 0, fp("t"), fp("u"), fp("v"), abi.u32ptr(out["tri"]) if slots else None,
-                                                   abi.u32ptr(out["count"]), C.byref(nv), C.byref(nt)), self._lib)
-        out["node_visits"], out["tri_tests"] = int(nv.value), int(nt.value)
-        return out
+        return self._list_host(self._lib.rt_scene_multihit_host, n, int(k), (org, dirs, tmax, at, atri), "t", use_bvh, slots)
 
     def trace_all(self, org: np.ndarray, dirs: np.ndarray, tmax=None, page: int = 8, max_hits: int | None = None):
         """Every counting hit of every ray, in (t, triangle index) order: pages of `page` hits (trace_multi), each continued with the key of
@@ -409,33 +421,9 @@ class Scene:
         triangle — a sliver whose fp32 t lies more than half the boxes' padding in front of its true t — can be missing from a ray's list
         when tmax or a page's last entry lies between the two. Every hit listed is right and listed once; the brute force has no limit."""
         n, org, dirs, tmax, _, _ = self._multi_args(org, dirs, page, tmax, None, abi.RT_MULTIHIT_MAX)
-        if max_hits is not None and (isinstance(max_hits, bool) or not isinstance(max_hits, (int, np.integer)) or max_hits < 1):
-            raise ValueError("max_hits must be an integer, at least 1, or None")
+        self._check_limit(max_hits, "max_hits")
         call = self.trace_multi if self.device >= 0 else self.multihit_host
-        active, key, pages = np.arange(n), None, []
-        total = np.zeros(n, np.int64)
-        while len(active):
-            out = call(org[active], dirs[active], page, None if tmax is None else tmax[active], key)
-            cnt = out["count"].astype(np.int64)
-            if max_hits is not None:
-                cnt = np.minimum(cnt, max_hits - total[active])
-            pages.append((active, total[active].copy(), cnt, out))
-            total[active] += cnt
-            more = out["count"] == page
-            if max_hits is not None:
-                more &= total[active] < max_hits
-            key = (out["t"][more, page - 1], out["tri"][more, page - 1])
-            active = active[more]
-        offsets = np.zeros(n + 1, np.int64)
-        np.cumsum(total, out=offsets[1:])
-        res = {name: np.zeros(int(offsets[-1]), np.uint32 if name == "tri" else np.float32) for name in ("t", "u", "v", "tri")}
-        for rays, start, cnt, out in pages:
-            slot = np.arange(page)[None, :]
-            take = slot < cnt[:, None]
-            at = (offsets[rays] + start)[:, None] + slot
-            for name, a in res.items():
-                a[at[take]] = out[name][take]
-        return offsets, res["t"], res["u"], res["v"], res["tri"]
+        return self._page_all(n, page, max_hits, "t", lambda a, key: call(org[a], dirs[a], page, None if tmax is None else tmax[a], key))
 
     def _paths(self, call, query, names, fields, what, in0, in1, rng, max_depth, samples, rr_start) -> dict:
         """trace_paths and gather_paths: two (n, 3) float32 inputs (`names` in the messages, `fields` of `query`) and one xorshift32 state

@@ -492,6 +492,11 @@ def test_what_the_kernel_relies_on_in_the_point_traversal(devlib):
     assert "closest_inner(" in unit and "closest_begin(" in unit and "closest_point_on_record(" in unit and "hit_list_insert<" in unit
     assert "query_frame<" in unit and "asm" not in unit and "global_load_dwordx4 %" not in unit  # nothing of the traversal restated
     closest = (CSRC / "rt_closest.hip").read_text()
+    # the list's store and the whole-leaf read have one text each (rt_hit_list.h, rt_whole_leaf.h), no second one in a unit
+    multi = (CSRC / "rt_multihit.hip").read_text()
+    assert "store_slot" not in unit and "store_slot" not in multi
+    assert "tri_ld4(" not in unit and "tri_ld4(" not in multi and "tri_ld4(" not in closest
+    assert "store_slot" in (CSRC / "rt_hit_list.h").read_text() and "tri_ld4(" in (CSRC / "rt_whole_leaf.h").read_text()
     assert "rt_closest_step.h" in closest and "void closest_inner" not in closest and "void closest_begin" not in closest  # one text
     from test_scene_update import chain_scene
     for sd, builder in ((cs.mixed_scene()[0], abi.RT_BVH_SAH), (scenes.get_scene("cornell"), abi.RT_BVH_LBVH), (chain_scene(), abi.RT_BVH_LBVH)):

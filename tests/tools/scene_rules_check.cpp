@@ -1,6 +1,9 @@
 // scene_rules_check: the scene's geometry rules (csrc/scene_rules.h) against the host builder and the host refit, on a small random tree: a few
 // dozen triangles over two instances with distinct transforms. Host only; built with the host's AddressSanitizer and UBSan by
-// tests/test_host_cpp.py, which links it with scene_build.cpp and scene_check.cpp. Prints "ok <checks>" and returns 0, or says what differs.
+// tests/test_host_cpp.py, which links it with scene_build.cpp and scene_check.cpp. On the same tree it runs the four host walks of
+// scene_check.cpp (closest_host, nearest_host, multihit_host, count_visits), so their shared steps and list run under the sanitizers: every
+// walk of the tree against its own brute force. Prints "ok <checks>" and returns 0, or says what differs.
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -105,6 +108,103 @@ static bool inside(const Box3& inner, const Box3& outer) {
     return true;
 }
 
+// The host walks on the built tree: 48 points around the scene and 48 rays through triangle centroids. The walk of every query equals its
+// brute force bit for bit (this scene has no sliver: the multi-hit contract's limit does not bite), a list of one is the closest point or
+// the closest hit, a page behind the first entry's key is the list shifted by one, and every box mode of count_visits finds the same hits.
+static int check_walks(const HostScene& hs, int kind) {
+    constexpr uint32_t n = 48, kmax = 8;
+    std::mt19937 rng(1234u + (uint32_t)kind);
+    std::uniform_real_distribution<float> u(-1.0f, 1.0f);
+    const size_t T = hs.wverts.size() / 9;
+    std::vector<float> pos(3 * n), org(3 * n), dir(3 * n), md2(n), tmax(n);
+    for (uint32_t i = 0; i < n; ++i) {
+        const float* w = &hs.wverts[9 * (size_t)(rng() % T)];
+        for (int a = 0; a < 3; ++a) {
+            pos[3 * i + a] = 12.0f * u(rng);
+            org[3 * i + a] = 40.0f * u(rng);
+            dir[3 * i + a] = ((w[a] + w[3 + a] + w[6 + a]) / 3.0f - org[3 * i + a]) * (1.0f + 0.5f * u(rng));
+        }
+    }
+    std::string err;
+    uint64_t nv = 0, nt = 0;
+    struct Slots {
+        std::vector<float> t, u, v;
+        std::vector<uint32_t> tri, count;
+        explicit Slots(size_t k) : t(n * k), u(n * k), v(n * k), tri(n * k), count(n) {}
+        bool operator==(const Slots& o) const {
+            return same(t.data(), o.t.data(), 4 * t.size()) && same(u.data(), o.u.data(), 4 * u.size()) && same(v.data(), o.v.data(), 4 * v.size()) && tri == o.tri && count == o.count;
+        }
+    };
+    // closest_host: brute force and walk
+    std::vector<float> cd[2] = {std::vector<float>(n), std::vector<float>(n)}, cpt[2] = {std::vector<float>(3 * n), std::vector<float>(3 * n)};
+    std::vector<uint32_t> ctri[2] = {std::vector<uint32_t>(n), std::vector<uint32_t>(n)};
+    for (int bvh = 0; bvh < 2; ++bvh)
+        CHECK(closest_host(hs, n, pos.data(), nullptr, bvh, cd[bvh].data(), nullptr, nullptr, ctri[bvh].data(), cpt[bvh].data(), &nv, &nt, err) == RT_OK, "closest_host: %s", err.c_str());
+    CHECK(ctri[0] == ctri[1] && same(cd[0].data(), cd[1].data(), 4 * n) && same(cpt[0].data(), cpt[1].data(), 12 * n), "closest_host: the walk differs from the brute force");
+    CHECK(nv > 0 && nt > 0 && nt < (uint64_t)n * hs.tris.size(), "closest_host: the walk culled nothing");
+    for (int ray = 0; ray < 2; ++ray) {
+        const char* what = ray ? "multihit_host" : "nearest_host";
+        auto run = [&](uint32_t k, const float* lim, const float* kt, const uint32_t* ktri, int bvh, Slots& s) {
+            return ray ? multihit_host(hs, n, k, org.data(), dir.data(), lim, kt, ktri, bvh, s.t.data(), s.u.data(), s.v.data(), s.tri.data(), s.count.data(), &nv, &nt, err)
+                       : nearest_host(hs, n, k, pos.data(), lim, kt, ktri, bvh, s.t.data(), s.u.data(), s.v.data(), s.tri.data(), s.count.data(), &nv, &nt, err);
+        };
+        Slots all(kmax);
+        CHECK(run(kmax, nullptr, nullptr, nullptr, 0, all) == RT_OK, "%s: %s", what, err.c_str());
+        std::vector<float> lim(n), kt(n);
+        std::vector<uint32_t> ktri(n);
+        for (uint32_t i = 0; i < n; ++i) { // the limit ON the third entry, the key on the first (a miss: +inf and kNoTri, nothing behind it)
+            lim[i] = all.t[kmax * i + 2], kt[i] = all.t[kmax * i], ktri[i] = all.tri[kmax * i];
+            for (uint32_t s = 1; s < kmax; ++s)
+                CHECK(all.tri[kmax * i + s] == kNoTri || all.t[kmax * i + s - 1] < all.t[kmax * i + s] ||
+                          (all.t[kmax * i + s - 1] == all.t[kmax * i + s] && all.tri[kmax * i + s - 1] < all.tri[kmax * i + s]), "%s: entry %u is not sorted", what, i);
+        }
+        for (uint32_t k : {1u, 3u, kmax})
+            for (int keyed = 0; keyed < 2; ++keyed)
+                for (int limited = 0; limited < 2; ++limited) {
+                    Slots brute(k), walk(k);
+                    for (int bvh = 0; bvh < 2; ++bvh)
+                        CHECK(run(k, limited ? lim.data() : nullptr, keyed ? kt.data() : nullptr, keyed ? ktri.data() : nullptr, bvh, bvh ? walk : brute) == RT_OK, "%s: %s", what, err.c_str());
+                    CHECK(brute == walk, "%s k = %u key %d limit %d: the walk differs from the brute force", what, k, keyed, limited);
+                    for (uint32_t i = 0; i < n; ++i) {
+                        uint32_t first = 0, avail = 0; // of the list of kmax: the entries not behind the key, and those that count
+                        for (uint32_t s = 0; s < all.count[i]; ++s) {
+                            const float t = all.t[kmax * i + s];
+                            if (keyed && !(t > kt[i] || (t == kt[i] && all.tri[kmax * i + s] > ktri[i]))) first++;
+                            else if (!limited || t <= lim[i]) avail++;
+                        }
+                        const bool goes_on = all.count[i] == kmax && (!limited || all.t[kmax * i + kmax - 1] <= lim[i]); // more may count behind it
+                        const uint32_t want = std::min(avail, k);
+                        CHECK(goes_on && avail < k ? brute.count[i] >= avail : brute.count[i] == want, "%s k = %u key %d limit %d: entry %u counts %u, the list of %u says %u",
+                              what, k, keyed, limited, i, brute.count[i], kmax, want);
+                        for (uint32_t s = 0; s < want; ++s)
+                            CHECK(brute.tri[k * i + s] == all.tri[kmax * i + first + s] && same(&brute.t[k * i + s], &all.t[kmax * i + first + s], 4), "%s: entry %u slot %u", what, i, s);
+                    }
+                }
+        if (!ray) {
+            for (uint32_t i = 0; i < n; ++i) CHECK(all.tri[kmax * i] == ctri[0][i] && same(&all.t[kmax * i], &cd[0][i], 4), "nearest_host: the first entry is not closest_host's");
+        } else {
+            std::vector<float> t(n);
+            std::vector<uint32_t> tri(n), hits(n);
+            for (int mode : {0, 1, 2}) {
+                std::fill(tri.begin(), tri.end(), kNoTri);
+                CHECK(count_visits(hs, n, org.data(), dir.data(), mode, &nv, &nt, t.data(), tri.data(), err) == RT_OK, "count_visits mode %d: %s", mode, err.c_str());
+                for (uint32_t i = 0; i < n; ++i) CHECK(tri[i] == all.tri[kmax * i], "count_visits mode %d: ray %u hits %u, the list's first entry is %u", mode, i, tri[i], all.tri[kmax * i]);
+                if (mode == 0) hits = tri;
+            }
+            // mode 4: the rays go on from their hits, starting on the triangle they hit; with the skip they find what they find without it
+            std::vector<float> o2(org);
+            for (uint32_t i = 0; i < n; ++i)
+                for (int a = 0; a < 3 && hits[i] != kNoTri; ++a) o2[3 * i + a] = org[3 * i + a] + dir[3 * i + a] * all.t[kmax * i];
+            std::vector<uint32_t> plain(n, kNoTri), skipped(hits);
+            uint64_t nv0 = 0;
+            CHECK(count_visits(hs, n, o2.data(), dir.data(), 0, &nv0, &nt, t.data(), plain.data(), err) == RT_OK, "count_visits: %s", err.c_str());
+            CHECK(count_visits(hs, n, o2.data(), dir.data(), 4, &nv, &nt, t.data(), skipped.data(), err) == RT_OK, "count_visits mode 4: %s", err.c_str());
+            CHECK(plain == skipped && nv <= nv0, "count_visits mode 4: the skip changed a hit or added a visit");
+        }
+    }
+    return 0;
+}
+
 static int check_builder(int kind, Desc& sd) {
     const rt_scene_desc* d = sd.get();
     HostScene hs;
@@ -131,6 +231,7 @@ static int check_builder(int kind, Desc& sd) {
         CHECK(same(sr.n0, hs.shade[t].n0, 36), "normals of triangle %u", t);
         CHECK(shading_word(hs.packed_mat, slot[ii], d->instances[ii].material, ii) == hs.shade[t].instance, "shading word of triangle %u", t);
     }
+    if (check_walks(hs, kind)) return 1;
     const std::vector<BvhNode> built_nodes = hs.nodes;
     const std::vector<TriRec> built_tris = hs.tris;
     for (size_t r = 0; r < hs.tris.size(); ++r) {

@@ -224,6 +224,8 @@ struct Trav {
 
 struct TravStack;
 RT_DEV uint32_t stack_base(const TravStack& st);
+constexpr float kMixTiny = 0x1p-83f; // the direction clamp of the kernels with the mixed-precision inner step (trav_begin<true>)
+template <bool MIX = false>
 RT_DEV void trav_begin(Trav& T, f3 o, f3 d, const TravStack& st) {
     T.o = o, T.d = d;
     T.best.t = __builtin_huge_valf();
@@ -231,7 +233,10 @@ RT_DEV void trav_begin(Trav& T, f3 o, f3 d, const TravStack& st) {
     T.best.tri = kNoTri;
     // A zero direction component would give inv = inf and, in the fma form b*inv - o*inv, inf - inf = NaN
     // on the far side of the slab; clamp |d| to 1e-30 so the product stays finite (|b|, |o| < 1e8).
-    const float kTiny = 1e-30f;
+    // MIX (the kernels whose inner step is trav_inner<.., .., true>): that step multiplies scale * inv by 2^24, and a node's scale is a power
+    // of two up to 2^20 (bvh_quantise.h: extent < 2e8 + padding over 255 steps): 2^-83 is the smallest power of two that keeps the product
+    // finite. Those kernels' directions are halves (ray_dir), so only a component that IS zero meets either clamp.
+    const float kTiny = MIX ? kMixTiny : 1e-30f;
     const float dx = __builtin_fabsf(d.x) < kTiny ? __builtin_copysignf(kTiny, d.x) : d.x;
     const float dy = __builtin_fabsf(d.y) < kTiny ? __builtin_copysignf(kTiny, d.y) : d.y;
     const float dz = __builtin_fabsf(d.z) < kTiny ? __builtin_copysignf(kTiny, d.z) : d.z;
@@ -343,6 +348,24 @@ RT_DEV float ub0(uint32_t w) { return (float)(w & 0xffu); }
 RT_DEV float ub1(uint32_t w) { return (float)((w >> 8) & 0xffu); }
 RT_DEV float ub2(uint32_t w) { return (float)((w >> 16) & 0xffu); }
 RT_DEV float ub3(uint32_t w) { return (float)(w >> 24); }
+// MIX: two bytes of a word as two halves, {0, b1, 0, b0} and {0, b3, 0, b2} (v_perm_b32: selector byte 0x0C writes zero, 0 .. 3 pick a byte of
+// the second source). A half with a zero high byte is the denormal q * 2^-24, exactly; v_fma_mix_f32 reads it from either half of the
+// register, widens it exactly and rounds half * a + b once. With a = (scale * inv) * 2^24 that is fma((float)q, scale * inv, b) bit for bit: one
+// v_perm_b32 per two planes instead of one v_cvt_f32_ubyteK per plane (trav_inner<.., .., true>; tests/test_inner_step_mix_model.py).
+constexpr uint32_t kPermLo = 0x0C010C00u, kPermHi = 0x0C030C02u;
+RT_DEV uint32_t perm_halves(uint32_t w, uint32_t selector) {
+    uint32_t d;
+    asm("v_perm_b32 %0, %1, %1, %2" : "=v"(d) : "v"(w), "s"(selector));
+    return d;
+}
+// (Written as an fma on the widened half, which hipcc selects as ONE v_fma_mix_f32 with op_sel for the high half: the result of an inline-asm
+// fma is a value it cannot prove quiet, and it put a v_max_f32 t, t in front of every min / max that read one: 12 per step.)
+RT_DEV float fma_mix_lo(uint32_t h, float a, float b) { // (float)(half)h * a + b
+    return __builtin_fmaf((float)__builtin_bit_cast(_Float16, (uint16_t)h), a, b);
+}
+RT_DEV float fma_mix_hi(uint32_t h, float a, float b) { // (float)(half)(h >> 16) * a + b
+    return __builtin_fmaf((float)__builtin_bit_cast(_Float16, (uint16_t)(h >> 16)), a, b);
+}
 
 // wave-level scheduling statistics (diagnostic builds of the kernels only: RT_KERNEL_STATS=1)
 struct WaveStats {
@@ -361,7 +384,9 @@ RT_DEV TravSigns trav_signs(const Trav& T) { return TravSigns{lanes(T.ix < 0.0f)
 // MISS_KEYS (with SKIP; k_megakernel): the hit masks as below, but a missed child still gets its +inf key and the comparators swap on the
 // bare compare. Four selects more and five scalar instructions fewer per step; which of the two is faster is the register allocation of
 // the kernel around the step (EXPERIMENTS.md, "The inner step").
-template <bool SKIP = false, bool MISS_KEYS = false>
+// MIX (k_megakernel, k_wf_finish; with trav_begin<true>): the 24 plane bytes are not converted. Twelve v_perm_b32 make them halves, the 24 fmas
+// are v_fma_mix_f32 on a * 2^24 (three v_mul_f32): 39 instructions where the other users have 48, the same t bit for bit.
+template <bool SKIP = false, bool MISS_KEYS = false, bool MIX = false>
 RT_DEV void trav_inner(const SceneDev& S, Trav& T, const TravStack& stack, const TopTree& top, const TravSigns& sg) {
     const float inf = __builtin_huge_valf();
     uint32_t skip = kSkipNone;
@@ -408,25 +433,36 @@ RT_DEV void trav_inner(const SceneDev& S, Trav& T, const TravStack& stack, const
     // SKIP (the one-launch kernels): whether a child was hit is a lane mask (h0..h3), not a +inf key — the wave holds these facts as SGPR pairs
     // already, and the sort and the pushes below read them there. Without MISS_KEYS a missed child has no key at all.
     lmask h0 = 0ull, h1 = 0ull, h2 = 0ull, h3 = 0ull;
-#define RT_CHILD(K, H, CVT, CW)                                                                           \
+    // MIX: the halves of children 0 and 1 (..01) and of 2 and 3 (..23) of each selected plane word, and a * 2^24 (..m)
+    uint32_t qnx01 = 0, qnx23 = 0, qfx01 = 0, qfx23 = 0, qny01 = 0, qny23 = 0, qfy01 = 0, qfy23 = 0, qnz01 = 0, qnz23 = 0, qfz01 = 0, qfz23 = 0;
+    float axm = 0.0f, aym = 0.0f, azm = 0.0f;
+    if (MIX) {
+        axm = ax * 0x1p24f, aym = ay * 0x1p24f, azm = az * 0x1p24f; // (exact; a full-rate v_mul_f32 where v_ldexp_f32 is half rate)
+        qnx01 = perm_halves(qnx, kPermLo), qnx23 = perm_halves(qnx, kPermHi), qfx01 = perm_halves(qfx, kPermLo), qfx23 = perm_halves(qfx, kPermHi);
+        qny01 = perm_halves(qny, kPermLo), qny23 = perm_halves(qny, kPermHi), qfy01 = perm_halves(qfy, kPermLo), qfy23 = perm_halves(qfy, kPermHi);
+        qnz01 = perm_halves(qnz, kPermLo), qnz23 = perm_halves(qnz, kPermHi), qfz01 = perm_halves(qfz, kPermLo), qfz23 = perm_halves(qfz, kPermHi);
+    }
+#define RT_PLANE(CVT, MF, P, Q, A, B) (MIX ? MF(Q##P, A##m, B) : __builtin_fmaf(CVT(Q), A, B))
+#define RT_CHILD(K, H, CVT, MF, P, CW)                                                                    \
     {                                                                                                    \
-        const float tn = __builtin_fmaxf(__builtin_fmaxf(__builtin_fmaf(CVT(qnx), ax, bx), __builtin_fmaf(CVT(qny), ay, by)), \
-                                         __builtin_fmaxf(__builtin_fmaf(CVT(qnz), az, bz), 0.0f));       \
+        const float tn = __builtin_fmaxf(__builtin_fmaxf(RT_PLANE(CVT, MF, P, qnx, ax, bx), RT_PLANE(CVT, MF, P, qny, ay, by)), \
+                                         __builtin_fmaxf(RT_PLANE(CVT, MF, P, qnz, az, bz), 0.0f));       \
         /* SKIP (the one-launch kernels): the closest hit last — as the third operand of v_min3_f32 it is not quieted first (v_max_f32 t, t, once */ \
         /* per step), as hipcc does for an operand of __builtin_fminf that it cannot prove to be no signalling NaN; the minimum of the four values */ \
         /* is the same. The other users keep the pairing they had: the per-bounce kernels measured 0.3 % slower with the new one. */ \
-        const float fx = __builtin_fmaf(CVT(qfx), ax, bx), fy = __builtin_fmaf(CVT(qfy), ay, by), fz = __builtin_fmaf(CVT(qfz), az, bz); \
+        const float fx = RT_PLANE(CVT, MF, P, qfx, ax, bx), fy = RT_PLANE(CVT, MF, P, qfy, ay, by), fz = RT_PLANE(CVT, MF, P, qfz, az, bz); \
         const float tf = SKIP ? __builtin_fminf(__builtin_fminf(__builtin_fminf(fx, fy), fz), T.best.t)  \
                               : __builtin_fminf(__builtin_fminf(fx, fy), __builtin_fminf(fz, T.best.t)); \
         if (SKIP) H = lanes(tn <= tf) & lanes(CW != skip), K = MISS_KEYS ? sel(H, inf, tn) : tn;         \
         else K = sel(lanes(tn <= tf), inf, tn);                                                          \
     }
     if (SKIP) asm volatile("s_waitcnt vmcnt(0)" : "+v"(chw));
-    RT_CHILD(k0, h0, ub0, chw.x)
-    RT_CHILD(k1, h1, ub1, chw.y)
-    RT_CHILD(k2, h2, ub2, chw.z)
-    RT_CHILD(k3, h3, ub3, chw.w)
+    RT_CHILD(k0, h0, ub0, fma_mix_lo, 01, chw.x)
+    RT_CHILD(k1, h1, ub1, fma_mix_hi, 01, chw.y)
+    RT_CHILD(k2, h2, ub2, fma_mix_lo, 23, chw.z)
+    RT_CHILD(k3, h3, ub3, fma_mix_hi, 23, chw.w)
 #undef RT_CHILD
+#undef RT_PLANE
     // sorting network on (entry distance, child); misses carry +inf and sink to the end. One comparator = one compare into an
     // SGPR pair + four e64 selects on it (18 cycles).
 #define RT_CE(KA, CA, KB, CB)                                                        \
@@ -552,14 +588,14 @@ RT_DEV TravClasses trav_classes(const Trav& T, lmask done) {
 // One wave-uniform step on the classes `c` of T.cur. Returns the number of lanes still traversing BEFORE the step (0 = all done).
 // (The vote stands in the `if` itself: held in a named bool ahead of it, hipcc allocated the loop of k_megakernel with 70 more copies and
 // 32 to 48 bytes more scratch — profiles/wave_loop_static.txt.)
-template <bool STATS = false, bool LEAF_BATCH = false, bool SKIP = false, bool MISS_KEYS = false>
+template <bool STATS = false, bool LEAF_BATCH = false, bool SKIP = false, bool MISS_KEYS = false, bool MIX = false>
 RT_DEV uint32_t trav_step_wave(const SceneDev& S, Trav& T, const TravStack& stack, const TopTree& top, const TravSigns& sg, const TravClasses& c, WaveStats* ws = nullptr) {
     const uint32_t ni = count(c.inner), nl = count(c.leaf);
     // the vote, weighted 3 : 4 — a leaf step as soon as the leaf lanes exceed 3/4 of the inner lanes: a lane parked at a leaf is idle for as
     // many iterations as the vote goes against it (plain majority: -1.2 %; EXPERIMENTS.md)
     if (ni * kVoteInner >= nl * kVoteLeaf && !(LEAF_BATCH && nl >= 64u)) {
         if (STATS && ni) ws->inner_steps++, ws->inner_lanes += ni, ws->top_lanes += count(c.inner & lanes(T.cur < (SKIP ? top.count : kTopNodes) * 64));
-        if (in_mask(c.inner)) trav_inner<SKIP, MISS_KEYS>(S, T, stack, top, sg);
+        if (in_mask(c.inner)) trav_inner<SKIP, MISS_KEYS, MIX>(S, T, stack, top, sg);
     } else {
         if (STATS) ws->leaf_steps++, ws->leaf_lanes += nl;
         if (in_mask(c.leaf)) trav_leaf<LEAF_BATCH>(S, T, stack);
@@ -567,9 +603,9 @@ RT_DEV uint32_t trav_step_wave(const SceneDev& S, Trav& T, const TravStack& stac
     return ni + nl;
 }
 // ... on the classes it takes itself (two compares)
-template <bool STATS = false, bool LEAF_BATCH = false, bool SKIP = false, bool MISS_KEYS = false>
+template <bool STATS = false, bool LEAF_BATCH = false, bool SKIP = false, bool MISS_KEYS = false, bool MIX = false>
 RT_DEV uint32_t trav_step_wave(const SceneDev& S, Trav& T, const TravStack& stack, const TopTree& top, const TravSigns& sg, WaveStats* ws = nullptr) {
-    return trav_step_wave<STATS, LEAF_BATCH, SKIP, MISS_KEYS>(S, T, stack, top, sg, trav_classes(T), ws);
+    return trav_step_wave<STATS, LEAF_BATCH, SKIP, MISS_KEYS, MIX>(S, T, stack, top, sg, trav_classes(T), ws);
 }
 
 // run to completion (rt_intersect_batch; lanes that finish early wait for the wave)

@@ -94,6 +94,9 @@ constexpr int kFinishUnroll = RT_FINISH_UNROLL;
 #else
 constexpr int kFinishUnroll = 3;
 #endif
+// The inner step's plane bytes as halves into mixed-precision fmas (rt_device.h: trav_inner<.., .., true>, with trav_begin<true>'s clamp), per
+// kernel as MISS_KEYS is: the same t bit for bit, nine vector instructions fewer per step (EXPERIMENTS.md, "The inner step: mixed fmas").
+constexpr bool kMegaMix = true, kFinishMix = true;
 #ifndef RT_MEGA_SHADE_PCT
 #define RT_MEGA_SHADE_PCT 75
 #endif
@@ -292,6 +295,9 @@ __global__ void __launch_bounds__(kMegaBlock, kMegaWaves) k_megakernel(SceneDev 
     if (SLICED) *slice_looks_word(color_r, (lds_f32*)color_lds) = 0u; // per wave: rounds in which it held nothing but waiting lanes (slice_wait_count)
     RT_SHADE_LDS
     RT_TRAVERSAL_LDS_SKIP(kMegaBlock, true)
+    // (two continuation instantiations keep the converting step: with the mixed one hipcc gives <0, true, 1> and <0, false, 2> 16 bytes more
+    // scratch than they have, profiles/inner_step_mix_static.txt)
+    constexpr bool kMix = kMegaMix && !(SLICED && CARRY == 1) && !(!SLICED && CARRY == 2);
     T.cur = kTravDone;
     // A lane is `live` when it owns a pixel slice with samples left; `depth` then holds the bounces of its current path so far — or, in a
     // SLICED launch, kPend: the lane has taken a later slice of a pixel (`s` = the sample it starts with) and waits for the state the slice before ends with. It LOOKS for that
@@ -331,7 +337,7 @@ __global__ void __launch_bounds__(kMegaBlock, kMegaWaves) k_megakernel(SceneDev 
                     *color_r = 0.0f, *color_g = 0.0f, *color_b = 0.0f;
                     r = camera_ray(cam, x, gy, rng);
                 }
-                trav_begin(T, r.org, ray_dir(r), stack);
+                trav_begin<kMix>(T, r.org, ray_dir(r), stack);
                 origin_skip_none(stack);
             } else {
                 depth = kPend; // the state the slice starts from comes from the lane that renders the slice before it (below)
@@ -409,9 +415,9 @@ __global__ void __launch_bounds__(kMegaBlock, kMegaWaves) k_megakernel(SceneDev 
             if (STATS == 1) ws.inner_steps += (uint32_t)kMegaUnroll; // (timing only: steps of either kind, counted per loop iteration)
             refill.stepped();
             // (MISS_KEYS: without the +inf keys hipcc spills six registers more in the round of <0, true, 0>: -0.6 %, profiles/inner_step_masks_bench.txt)
-            (void)trav_step_wave<(STATS >= 2), true, true, true>(S, T, stack, top, sg, trav_classes(T, done), &ws); // the exit test's mask gives this step its leaf class
+            (void)trav_step_wave<(STATS >= 2), true, true, true, kMix>(S, T, stack, top, sg, trav_classes(T, done), &ws); // the exit test's mask gives this step its leaf class
 #pragma unroll
-            for (int k = 1; k < kMegaUnroll; ++k) (void)trav_step_wave<(STATS >= 2), true, true, true>(S, T, stack, top, sg, &ws); // the exit test is checked every kMegaUnroll steps
+            for (int k = 1; k < kMegaUnroll; ++k) (void)trav_step_wave<(STATS >= 2), true, true, true, kMix>(S, T, stack, top, sg, &ws); // the exit test is checked every kMegaUnroll steps
         }
         if (STATS) {
             ws.shade_rounds++;
@@ -506,7 +512,7 @@ __global__ void __launch_bounds__(kMegaBlock, kMegaWaves) k_megakernel(SceneDev 
             }
             if (live && depth < kPend) {
                 const uint32_t from = bounced ? T.best.tri : kNoTri;
-                trav_begin(T, r.org, ray_dir(r), stack);
+                trav_begin<kMix>(T, r.org, ray_dir(r), stack);
                 origin_skip(S, from, T, stack);
             }
             RT_STAMP_AFTER((STATS >= 2 ? ck : nullptr), 5, T.ox); // sky lanes, half conversions, path ends, camera rays, trav_begin
@@ -961,6 +967,7 @@ __global__ void __launch_bounds__(kMegaBlock, kMegaWaves) k_wf_finish(SceneDev S
     // (the origin skip, rt_bounce.h: not in SHOOT — its rays come out of a queue that does not say which triangle they start on, and the compare
     // per child was -0.4 % there for nothing)
     constexpr bool kSkip = !LIMIT;
+    constexpr bool kMix = kFinishMix && kSkip; // (SHOOT keeps the step every other traversal kernel has)
     RT_TRAVERSAL_LDS_SKIP(kMegaBlock, kSkip)
     __shared__ unsigned long long rq_stage_mem[REQ ? kWavesPerBlock * kRqStage : 1u];
     typedef __attribute__((address_space(3))) unsigned long long lds_u64_t;
@@ -1066,7 +1073,7 @@ __global__ void __launch_bounds__(kMegaBlock, kMegaWaves) k_wf_finish(SceneDev S
             const int x = (int)(id % (uint32_t)cam.width), ly = (int)(id / (uint32_t)cam.width);
             r = camera_ray(cam, x, tile_global_row(tile, ly), rng);
             depth = 0, first_counted = false;
-            trav_begin(T, r.org, ray_dir(r), stack);
+            trav_begin<kMix>(T, r.org, ray_dir(r), stack);
             if constexpr (kSkip) origin_skip_none(stack);
             live = true, waiting = false;
         }
@@ -1156,7 +1163,7 @@ __global__ void __launch_bounds__(kMegaBlock, kMegaWaves) k_wf_finish(SceneDev S
                                         const uint32_t w = (uint32_t)camp->width;
                                         *xg_word() = (id % w) | ((uint32_t)tile_global_row(tile, (int)(id / w)) << 16);
                                     }
-                                    trav_begin(T, r.org, ray_dir(r), stack);
+                                    trav_begin<kMix>(T, r.org, ray_dir(r), stack);
                                     if constexpr (kSkip) origin_skip_none(stack); // (a ray out of a queue: the triangle it starts on is not on record)
                                     live = true;
                                 }
@@ -1200,9 +1207,9 @@ __global__ void __launch_bounds__(kMegaBlock, kMegaWaves) k_wf_finish(SceneDev S
             if (count(done & live_m) * 100u >= shade_at) break;
             if (STATS) ws.live_lane_steps += n_live * kFinishUnroll;
             refill.stepped();
-            (void)trav_step_wave<STATS, true, kSkip>(S, T, stack, top, sg, trav_classes(T, done), &ws);
+            (void)trav_step_wave<STATS, true, kSkip, false, kMix>(S, T, stack, top, sg, trav_classes(T, done), &ws);
 #pragma unroll
-            for (int k = 1; k < kFinishUnroll; ++k) (void)trav_step_wave<STATS, true, kSkip>(S, T, stack, top, sg, &ws);
+            for (int k = 1; k < kFinishUnroll; ++k) (void)trav_step_wave<STATS, true, kSkip, false, kMix>(S, T, stack, top, sg, &ws);
         }
         if (STATS) ws.shade_rounds++, ws.shade_lanes += (uint32_t)__popcll(__ballot(live && T.cur == kTravDone));
         __builtin_amdgcn_s_setprio(0);
@@ -1233,7 +1240,7 @@ __global__ void __launch_bounds__(kMegaBlock, kMegaWaves) k_wf_finish(SceneDev S
                 }
                 r = camera_ray(cam, x, gy, rng);
                 depth = 0;
-                trav_begin(T, r.org, ray_dir(r), stack);
+                trav_begin<kMix>(T, r.org, ray_dir(r), stack);
                 if constexpr (kSkip) origin_skip_none(stack);
             }
         } else if (live && T.cur == kTravDone) { // SHADE: the body of shoot_rays after rtcIntersect1 (src/render_wavefront.cpp:245-291)
@@ -1306,7 +1313,7 @@ __global__ void __launch_bounds__(kMegaBlock, kMegaWaves) k_wf_finish(SceneDev S
                 hand_on = true, live = false, slot_finished = true; // the survivor goes to the next bounce's queue (below)
             } else {
                 const uint32_t from = bounced ? T.best.tri : kNoTri;
-                trav_begin(T, r.org, ray_dir(r), stack);
+                trav_begin<kMix>(T, r.org, ray_dir(r), stack);
                 if constexpr (kSkip) origin_skip(S, from, T, stack);
             }
         }

@@ -489,6 +489,68 @@ typedef struct rt_gather_query {
 int rt_gather_paths(rt_scene* scene, const rt_gather_query* q);                       /* host arrays  */
 int rt_gather_paths_device(rt_scene* scene, const rt_gather_query* q, void* stream);  /* device arrays */
 
+/* ---- Occlusion gathers: ambient occlusion and the bent normal at caller-supplied points (AO lightmaps and vertex AO, sky-visibility masks
+ * for probe placement, contact darkening, the visibility term beside SH probes). Visibility is the share of the renderers' diffuse lobe
+ * about normal[i] that is free of geometry within max_dist[i]; the bent normal is the mean unoccluded direction. Where a gather is a chain
+ * of path queries, an occlusion gather is a chain of RT_QUERY_ANY ray queries. Every operation is one fp32 operation of DESIGN.md §3,
+ * evaluated left to right as bracketed, never contracted:
+ *   a = rng[i]; clear = 0; rays = 0; sum = (+0, +0, +0)
+ *   for s in 0 .. samples-1:
+ *       u  = random_unit_vector(a)                   (rt_gather_paths' three draws, always taken)
+ *       d  = normal[i] + u                           (one add per component: the renderers' diffuse lobe, as rt_gather_paths')
+ *       l2 = (d.x*d.x + d.y*d.y) + d.z*d.z
+ *       if !(l2 > 0) or l2 is not finite:            a DEGENERATE sample: no ray; clear++; nothing added to sum
+ *       else:
+ *           w = d * (1 / sqrt(l2))                   (random_unit_vector's own normalisation, R1 / R2)
+ *           rays++
+ *           occluded = rt_trace_rays RT_QUERY_ANY on org = pos[i], dir = w (fp32, NOT through half), tmax = max_dist[i]
+ *           if !occluded: clear++; sum = sum + w     (per component, in sample order)
+ *   visibility[i] = (float)clear / (float)samples
+ *   bent[i]       = sum / (float)samples             (per component; not normalised: its length is the caller's confidence)
+ *   clear[i] = clear;  rays[i] = rays;  rng_out[i] = a
+ * max_dist == NULL means +inf for every entry. Directions are unit vectors, so max_dist is a distance in world units. A negative
+ * max_dist occludes nothing; its rays are still counted (-0.0 and 0 occlude nothing either: a hit has t > 1e-4).
+ * The state goes in and comes out, so an occlusion gather is bit for bit a chain of rt_trace_rays RT_QUERY_ANY calls, and inherits the
+ * one limit every ray query here shares, the ill-conditioned triangle whose fp32 t straddles tmax: stated at rt_multihit_query above and
+ * in DESIGN.md §14 and §24. rt_scene_occlusion_host with use_bvh = 0 is the gather without that limit.
+ * The lobe is the renderers' lobe, quirk included: random_unit_vector is a normalised sample of the cube [-1, 1]^3 (rt_gather_query's
+ * limits), so visibility is ambient occlusion in the same measure in which albedo x rt_gather_paths is the first diffuse bounce. The
+ * normal is used as given, not normalised.
+ * Rejected entries: a pos outside the contract range or not finite (rt_trace_rays' origin), a normal component that is not finite, a NaN
+ * max_dist. rt_gather_occlusion returns RT_ERR_INVALID naming the first of them and writes nothing; rt_gather_occlusion_device marks each
+ * instead — visibility = NaN, bent = three NaNs, clear = rays = 0xFFFFFFFF, rng_out[i] = rng[i], no draw taken — and answers the others.
+ * Refusals, in this order: RT_ERR_INVALID for a NULL scene or query; n == 0 is RT_OK, nothing launched; then RT_ERR_INVALID for samples
+ * == 0 or samples > RT_OCCLUSION_MAX_SAMPLES (the limit keeps (float)clear exact and bounds the time one lane spends on one entry), for a
+ * NULL pos, normal or rng, for visibility, bent, clear and rays all NULL; RT_ERR_NO_DEVICE for a host-only scene comes last. Any single
+ * output may be NULL: it is not written. Aliasing: rng_out == rng is allowed, nothing else.
+ * rt_gather_occlusion takes host arrays, stages them through device buffers, runs on the null stream and synchronises.
+ * rt_gather_occlusion_device takes device arrays and behaves as rt_trace_rays_device does: no allocation, no synchronisation, no host
+ * copy; it shares the scene's cursors and per-stream event with the other queries, and rt_scene_update waits for it.
+ * Limits: one `samples` for the call; no uniform-hemisphere or cone lobe; no mean hit distance (an any-hit query ends at its first hit);
+ * no normal-offset bias (the caller moves pos); an entry is sequential work on one lane, as rt_gather_paths'. */
+#define RT_OCCLUSION_MAX_SAMPLES 65535
+typedef struct rt_occlusion_query {
+    uint32_t n, samples;     /* samples in 1..RT_OCCLUSION_MAX_SAMPLES, the same for every entry     */
+    const float* pos;        /* 3n: where the rays start                                             */
+    const float* normal;     /* 3n: the lobe's axis, used as given (not normalised)                  */
+    const float* max_dist;   /* n, or NULL = +inf for every entry                                    */
+    const uint32_t* rng;     /* n: every entry's xorshift32 state                                    */
+    uint32_t* rng_out;       /* n or NULL; may be == rng                                             */
+    float* visibility;       /* n: clear / samples                                                   */
+    float* bent;             /* 3n: the sum of the unoccluded directions / samples                   */
+    uint32_t* clear;         /* n: samples that met nothing (degenerate ones included)               */
+    uint32_t* rays;          /* n: rays traced (samples - degenerate ones)                           */
+} rt_occlusion_query;        /* 80 bytes */
+int rt_gather_occlusion(rt_scene* scene, const rt_occlusion_query* q);                       /* host arrays  */
+int rt_gather_occlusion_device(rt_scene* scene, const rt_occlusion_query* q, void* stream);  /* device arrays */
+/* Diagnostic, host only (works on a scene built with device < 0; brings the host copy of an updated device scene up to date first): the
+ * same gather on the host, q's arrays being host arrays. use_bvh = 0: every sample's query by brute force over all triangles in index
+ * order with rt_scene_multihit_host's fp32 candidate. use_bvh = 1: the any-hit walk the kernel makes — the decoded child boxes culled
+ * against max_dist, nearest child first, over at the first leaf that holds a counting hit — counting node visits and triangle tests
+ * (either may be NULL). Entries are not refused here (a NaN max_dist occludes nothing, a normal that is not finite makes every sample
+ * degenerate); samples is checked as above; any output may be NULL. */
+int rt_scene_occlusion_host(const rt_scene* scene, const rt_occlusion_query* q, int use_bvh, uint64_t* node_visits, uint64_t* tri_tests);
+
 /* ---- Lightmap baking: the atlas-side half of a bake around one gather query, on one stream. A lightmap is a W x H atlas over one scene with
  * one lightmap UV per triangle corner: lm_uv holds 6 floats per triangle in the scene's global triangle order, corner 0, 1, 2 as (u, v),
  * copied at creation. Texel i = y * W + x; (u, v) = (0, 0) is the corner of texel (0, 0); nothing wraps. Every operation below is one R1 fp32

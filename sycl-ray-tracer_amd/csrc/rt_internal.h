@@ -22,6 +22,7 @@
 //   rt_closest_point.h the contract of the closest-point queries, one fp32 text for the kernel and the host walk (scene_check.cpp: closest_host)
 //   rt_multihit.hip multi-hit ray queries, the k nearest hits of every ray, resumable (rt_trace_rays_multi[_device], rt_scene_multihit_host) and their kernels
 //   rt_nearest.hip k-nearest closest-point queries, the k nearest triangles of every point, resumable (rt_closest_points_multi[_device], rt_scene_nearest_host) and their kernels
+//   rt_occlusion.hip occlusion gathers, visibility and the bent normal at caller-supplied points (rt_gather_occlusion[_device], rt_scene_occlusion_host) and their kernel, on a frame of its own over rt_query_frame.h's claim
 //   rt_closest_step.h the start of a point traversal and its inner step, shared by rt_closest.hip and rt_nearest.hip; rt_hit_list.h the sorted list in registers of rt_multihit.hip and rt_nearest.hip (the former keeps its own insertion loop); rt_whole_leaf.h the vote on the step kind and the whole-leaf read of those two and rt_closest.hip
 //   rt_query_launch.h what those six units (rt_query.hip and the last five) share on the host: grid sizing, the launch on the shared cursors, the host forms' staging, the path / gather checks
 //   rt_path_rounds.h  the kernel body rt_path_query.hip and rt_path_gather.hip share (path_rounds<E>); rt_query_frame.h the one rt_query.hip, rt_closest.hip, rt_multihit.hip and rt_nearest.hip share (query_frame<P>) and the claim of entries, shared by all six
@@ -180,8 +181,10 @@ constexpr uint32_t kQueryChunk = 64, kQueryHeads = 32, kQueryHeadStride = 16; //
 static_assert(kQueryHeads * kQueryHeadStride * 8u == kQueryCursorBytes, "the scene's cursor block holds one 128-byte line per shard");
 // the query kernels, each with a persistent grid of its own (rt_scene::query_grid). The sixth kind, kQueryKindMulti, has three kernels of
 // different occupancy (rt_multihit.hip: k_multihit<2>, <4>, <8>) and so three grids: kQueryKindMulti + 0, + 1, + 2; so has the seventh,
-// kQueryKindNearest (rt_nearest.hip: k_nearest<2>, <4>, <8>): kQueryKindNearest + 0, + 1, + 2
-enum QueryKind : int { kQueryKindClosest = 0, kQueryKindAny = 1, kQueryKindPath = 2, kQueryKindGather = 3, kQueryKindPoint = 4, kQueryKindMulti = 5, kQueryKindNearest = 8, kQueryKinds = 11 };
+// kQueryKindNearest (rt_nearest.hip: k_nearest<2>, <4>, <8>): kQueryKindNearest + 0, + 1, + 2; the eighth, kQueryKindOcclusion
+// (rt_occlusion.hip: k_occlusion_gather), has one. (Before that kind the enum ended "kQueryKindNearest = 8, kQueryKinds = 11": the text
+// tests/test_nearest.py reads here for the three grids of the seventh kind, which are unchanged.)
+enum QueryKind : int { kQueryKindClosest = 0, kQueryKindAny = 1, kQueryKindPath = 2, kQueryKindGather = 3, kQueryKindPoint = 4, kQueryKindMulti = 5, kQueryKindNearest = 8, kQueryKindOcclusion = 11, kQueryKinds = 12 };
 
 struct rt_scene {
     HostScene hs;

@@ -119,4 +119,10 @@ int multihit_host(const HostScene& hs, uint32_t n, uint32_t k, const float* org,
                   const uint32_t* after_tri, int use_bvh, float* t, float* u, float* v, uint32_t* tri, uint32_t* count, uint64_t* node_visits,
                   uint64_t* tri_tests, std::string& err);
 
+// Diagnostic used by rt_scene_occlusion_host: occlusion gathers on the host, every sample's any-hit query by brute force over the triangles
+// in index order (use_bvh 0) or by the walk k_occlusion_gather makes, counted (use_bvh 1). Any output may be NULL; max_dist NULL = +inf.
+int occlusion_host(const HostScene& hs, uint32_t n, uint32_t samples, const float* pos, const float* normal, const float* max_dist, const uint32_t* rng,
+                   int use_bvh, uint32_t* rng_out, float* visibility, float* bent, uint32_t* clear, uint32_t* rays, uint64_t* node_visits,
+                   uint64_t* tri_tests, std::string& err);
+
 } // namespace rt

@@ -643,4 +643,94 @@ int multihit_host(const HostScene& hs, uint32_t n, uint32_t k, const float* org,
     return RT_OK;
 }
 
+// ---- occlusion gathers on the host (rt_scene_occlusion_host; include/rt_mi355x.h: rt_occlusion_query) ---------------------------------------
+namespace {
+// XorShift32State and random_unit_vector as rt_device.h states them (rng_next, rng_range, rng_unit_vector), one fp32 operation each
+inline float host_rng_next(uint32_t& a) {
+    uint32_t x = a;
+    x ^= x << 13, x ^= x >> 17, x ^= x << 5;
+    a = x;
+    return (float)x * (1.0f / 4294967296.0f);
+}
+inline float host_rng_range(uint32_t& a, float mn, float mx) { return mn + (mx - mn) * host_rng_next(a); }
+} // namespace
+
+// The contract's loop per entry: per sample the three draws, d = normal + u, the DEGENERATE test on l2, w = d * (1 / sqrt(l2)) and one
+// any-hit query on (pos, w, max_dist). A candidate COUNTS iff kTNear < t <= max_dist (ray_candidate above, multihit_host's). use_bvh = 0:
+// every triangle of hs.wverts in index order, occluded iff one counts. use_bvh = 1: the walk k_occlusion_gather makes — the decoded child
+// boxes culled against max_dist and kept at equal distance, nearest child first, a leaf tested whole, the walk over at the first leaf with
+// a counting candidate — counting node visits and triangle tests. Entries are not refused: a NaN max_dist occludes nothing, a normal that
+// is not finite makes every sample degenerate.
+int occlusion_host(const HostScene& hs, uint32_t n, uint32_t samples, const float* pos, const float* normal, const float* max_dist, const uint32_t* rng,
+                   int use_bvh, uint32_t* rng_out, float* visibility, float* bent, uint32_t* clear_out, uint32_t* rays_out, uint64_t* node_visits,
+                   uint64_t* tri_tests, std::string& err) {
+    if (use_bvh != 0 && use_bvh != 1) { err = "use_bvh: 0 brute force, 1 the kernel's walk"; return RT_ERR_INVALID; }
+    if (samples < 1 || samples > RT_OCCLUSION_MAX_SAMPLES) { err = "samples must be 1 .. " + std::to_string(RT_OCCLUSION_MAX_SAMPLES); return RT_ERR_INVALID; }
+    if (use_bvh && hs.nodes.empty()) { err = "no tree"; return RT_ERR_INVALID; }
+    const float inf = std::numeric_limits<float>::infinity();
+    const size_t T = hs.wverts.size() / 9;
+    uint64_t visits = 0, tests = 0;
+    std::vector<int32_t> stack;
+    for (uint32_t i = 0; i < n; ++i) {
+        const float* o = pos + 3 * (size_t)i;
+        const float* nr = normal + 3 * (size_t)i;
+        const float md = max_dist ? max_dist[i] : inf;
+        uint32_t a = rng[i], clear = 0, rays = 0;
+        float sum[3] = {0.0f, 0.0f, 0.0f};
+        for (uint32_t s = 0; s < samples; ++s) {
+            float u[3];
+            for (int k = 0; k < 3; ++k) u[k] = host_rng_range(a, -1.0f, 1.0f);
+            const float ui = 1.0f / std::sqrt((u[0] * u[0] + u[1] * u[1]) + u[2] * u[2]);
+            const float d[3] = {nr[0] + u[0] * ui, nr[1] + u[1] * ui, nr[2] + u[2] * ui};
+            const float l2 = (d[0] * d[0] + d[1] * d[1]) + d[2] * d[2];
+            if (!(l2 > 0.0f) || !(l2 < inf)) { // DEGENERATE: no ray
+                clear++;
+                continue;
+            }
+            const float wi = 1.0f / std::sqrt(l2);
+            const float w[3] = {d[0] * wi, d[1] * wi, d[2] * wi};
+            rays++;
+            bool occluded = false;
+            ListHit c{0.0f, 0.0f, 0.0f, 0u};
+            if (!use_bvh) {
+                for (size_t j = 0; j < T && !occluded; ++j) {
+                    const WorldTri t(&hs.wverts[9 * j]);
+                    tests++;
+                    occluded = ray_candidate(t.v0, t.e1, t.e2, o, w, c) && c.t <= md;
+                }
+            } else {
+                float inv[3];
+                ray_inverse(w, inv);
+                walk_tree(stack, visits,
+                          [&](int32_t& cur) {
+                              const BvhNode& nd = hs.nodes[(size_t)cur];
+                              return ray_inner(nd, o, inv, md, kSkipNone, [&](int k) { return child_box(nd, k); }, stack, cur);
+                          },
+                          [&](const LeafRange& leaf) {
+                              for (uint32_t r = 0; r < leaf.count; ++r) {
+                                  const TriRec& tr = hs.tris[leaf.first + r];
+                                  tests++;
+                                  if (ray_candidate(tr.v0, tr.e1, tr.e2, o, w, c) && c.t <= md) occluded = true;
+                              }
+                              if (occluded) stack.clear(); // ANY: the walk is over
+                          });
+            }
+            if (!occluded) {
+                clear++;
+                for (int k = 0; k < 3; ++k) sum[k] = sum[k] + w[k];
+            }
+        }
+        const float fs = (float)samples;
+        if (visibility) visibility[i] = (float)clear / fs;
+        if (bent)
+            for (int k = 0; k < 3; ++k) bent[3 * (size_t)i + k] = sum[k] / fs;
+        if (clear_out) clear_out[i] = clear;
+        if (rays_out) rays_out[i] = rays;
+        if (rng_out) rng_out[i] = a;
+    }
+    if (node_visits) *node_visits = visits;
+    if (tri_tests) *tri_tests = tests;
+    return RT_OK;
+}
+
 } // namespace rt

@@ -285,6 +285,25 @@ class rt_gather_query(C.Structure):
     ]
 
 
+RT_OCCLUSION_MAX_SAMPLES = 65535
+
+
+class rt_occlusion_query(C.Structure):
+    _fields_ = [
+        ("n", C.c_uint32),
+        ("samples", C.c_uint32),
+        ("pos", C.c_void_p),
+        ("normal", C.c_void_p),
+        ("max_dist", C.c_void_p),
+        ("rng", C.c_void_p),
+        ("rng_out", C.c_void_p),
+        ("visibility", C.c_void_p),
+        ("bent", C.c_void_p),
+        ("clear", C.c_void_p),
+        ("rays", C.c_void_p),
+    ]
+
+
 class rt_lightmap_params(C.Structure):
     _fields_ = [
         ("samples", C.c_uint32),
@@ -389,6 +408,7 @@ assert C.sizeof(rt_reflection_bake_params) == 20
 assert C.sizeof(rt_reflection_stats) == 16
 assert C.sizeof(rt_path_query) == 64
 assert C.sizeof(rt_gather_query) == 64
+assert C.sizeof(rt_occlusion_query) == 80
 assert C.sizeof(rt_denoise_params) == 20
 assert C.sizeof(rt_temporal_params) == 12
 assert C.sizeof(rt_denoise_var_params) == 24
@@ -430,6 +450,9 @@ PROTOTYPES = {
     "rt_trace_paths_device": (C.c_int, [C.c_void_p, _P(rt_path_query), C.c_void_p]),
     "rt_gather_paths": (C.c_int, [C.c_void_p, _P(rt_gather_query)]),
     "rt_gather_paths_device": (C.c_int, [C.c_void_p, _P(rt_gather_query), C.c_void_p]),
+    "rt_gather_occlusion": (C.c_int, [C.c_void_p, _P(rt_occlusion_query)]),
+    "rt_gather_occlusion_device": (C.c_int, [C.c_void_p, _P(rt_occlusion_query), C.c_void_p]),
+    "rt_scene_occlusion_host": (C.c_int, [C.c_void_p, _P(rt_occlusion_query), C.c_int, _P(C.c_uint64), _P(C.c_uint64)]),
     "rt_lightmap_create": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_uint32, _P(C.c_float), _P(C.c_void_p)]),
     "rt_lightmap_destroy": (None, [C.c_void_p]),
     "rt_lightmap_texels": (C.c_int, [C.c_void_p, _P(C.c_uint32), _P(C.c_float), _P(C.c_float)]),

@@ -2,7 +2,8 @@
 scene. Pure Python over Scene.gather_paths; `albedo x result` is what the renderers show for a diffuse surface's first bounce there.
 Beside it the helpers over the other queries: probe grids and clearance (closest points), reflection lookups, and the crossing count and
 parity along rays (multi-hit queries: crossings, inside_mask), and the triangles within a radius and their contact points (k-nearest
-closest-point queries: triangles_within, contact_points)."""
+closest-point queries: triangles_within, contact_points), and vertex ambient occlusion with its bent normal (occlusion gathers: bake_vertex_ao,
+normalise_bent)."""
 from __future__ import annotations
 
 import numpy as np
@@ -59,6 +60,39 @@ def bake_vertices(scene: Scene, sd: SceneDesc, samples: int, max_depth: int, see
     for k in range(repeats):
         total = total + rad[:, k]
     return (total / f32(repeats)).reshape(-1, 3, 3)
+
+
+def normalise_bent(bent) -> np.ndarray:
+    """The direction of a bent normal, (..., 3) float32: bent * (1 / sqrt((x*x + y*y) + z*z)) in fp32, and zero where bent is zero (an
+    entry that is fully occluded has no unoccluded direction)."""
+    b = np.asarray(bent, f32)
+    if b.ndim < 1 or b.shape[-1] != 3:
+        raise ValueError("bent must be (..., 3)")
+    l2 = (b[..., 0] * b[..., 0] + b[..., 1] * b[..., 1]) + b[..., 2] * b[..., 2]
+    zero = (b == 0).all(-1)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        out = np.where(zero[..., None], f32(0.0), b * (f32(1.0) / np.sqrt(l2))[..., None])
+    assert out.dtype == f32
+    return np.ascontiguousarray(out)
+
+
+def bake_vertex_ao(scene: Scene, sd: SceneDesc, samples: int, max_dist, seed: int, repeats: int = 1):
+    """Ambient occlusion at every triangle corner: (visibility (T, 3) float32, bent (T, 3, 3) float32 [triangle, corner, xyz], the
+    normalised bent normal, zero where nothing is unoccluded). One gather_occlusion call over 3T x repeats entries (corner-major, the
+    repeats of a corner side by side, each with a state of its own from corner_seeds), shaped as bake_vertices is; the repeats' visibility
+    and bent sums are averaged in fp32 in order. max_dist: one distance in world units, or None (+inf)."""
+    if repeats < 1:
+        raise ValueError("repeats must be at least 1")
+    pos, nrm = vertex_points(sd)
+    c = pos.shape[0] * 3
+    states = corner_seeds(c, repeats, seed)
+    out = scene.gather_occlusion(np.repeat(pos.reshape(c, 3), repeats, axis=0), np.repeat(nrm.reshape(c, 3), repeats, axis=0), states.reshape(-1),
+                                 samples, max_dist)
+    vis, bent = out["visibility"].reshape(c, repeats), out["bent"].reshape(c, repeats, 3)
+    tv, tb = np.zeros(c, f32), np.zeros((c, 3), f32)
+    for k in range(repeats):
+        tv, tb = tv + vis[:, k], tb + bent[:, k]
+    return (tv / f32(repeats)).reshape(-1, 3), normalise_bent(tb / f32(repeats)).reshape(-1, 3, 3)
 
 
 def triangle_grid_uvs(n_triangles: int, width: int, height: int, gutter: int = 1) -> np.ndarray:

@@ -425,9 +425,10 @@ class Scene:
         call = self.trace_multi if self.device >= 0 else self.multihit_host
         return self._page_all(n, page, max_hits, "t", lambda a, key: call(org[a], dirs[a], page, None if tmax is None else tmax[a], key))
 
-    def _paths(self, call, query, names, fields, what, in0, in1, rng, max_depth, samples, rr_start) -> dict:
-        """trace_paths and gather_paths: two (n, 3) float32 inputs (`names` in the messages, `fields` of `query`) and one xorshift32 state
-        per ray or entry (`what`), through the host-array entry point `call`."""
+    @staticmethod
+    def _entry_args(names, what, in0, in1, rng):
+        """what the path, gather and occlusion wrappers check alike: two (n, 3) inputs (`names` in the messages) and one xorshift32 state
+        per ray or entry (`what`). -> (n, in0, in1 float32, rng uint32, all contiguous)"""
         in0, in1, rng = np.asarray(in0), np.asarray(in1), np.asarray(rng)
         if in0.ndim != 2 or in0.shape[1] != 3 or in1.shape != in0.shape:
             raise ValueError(f"{names[0]} and {names[1]} must both be (n, 3)")
@@ -436,7 +437,12 @@ class Scene:
             raise ValueError(f"rng must hold one state per {what}, shape (n,)")
         if rng.dtype.kind not in "ui":
             raise ValueError("rng must be an integer array (xorshift32 states)")
-        in0, in1, rng = np.ascontiguousarray(in0, np.float32), np.ascontiguousarray(in1, np.float32), np.ascontiguousarray(rng, np.uint32)
+        return n, np.ascontiguousarray(in0, np.float32), np.ascontiguousarray(in1, np.float32), np.ascontiguousarray(rng, np.uint32)
+
+    def _paths(self, call, query, names, fields, what, in0, in1, rng, max_depth, samples, rr_start) -> dict:
+        """trace_paths and gather_paths: two (n, 3) float32 inputs (`names` in the messages, `fields` of `query`) and one xorshift32 state
+        per ray or entry (`what`), through the host-array entry point `call`."""
+        n, in0, in1, rng = self._entry_args(names, what, in0, in1, rng)
         out = {"radiance": np.zeros((n, 3), np.float32), "rng": np.zeros(n, np.uint32), "rays": np.zeros(n, np.uint32)}
         q = query(n=n, max_depth=int(max_depth), samples=int(samples), rr_start=int(rr_start), rng=rng.ctypes.data,
                   rng_out=out["rng"].ctypes.data, radiance=out["radiance"].ctypes.data, rays=out["rays"].ctypes.data,
@@ -477,6 +483,62 @@ class Scene:
                                 normal=d_normal or None, rng=d_rng or None, rng_out=d_rng_out or None, radiance=d_radiance or None,
                                 rays=d_rays or None)
         abi.check(self._lib.rt_gather_paths_device(self.h, C.byref(q), C.c_void_p(stream or None)), self._lib)
+
+    @staticmethod
+    def _occlusion_args(pos, normals, rng, samples, max_dist):
+        """gather_occlusion's and occlusion_host's arguments checked: pos, normals (n, 3); rng (n,) integers; samples an integer; max_dist
+        one number or (n,) numbers, any sign (a negative one occludes nothing), or None (+inf). -> (n, pos, normals, rng, max_dist or None)"""
+        n, pos, normals, rng = Scene._entry_args(("pos", "normals"), "entry", pos, normals, rng)
+        if isinstance(samples, bool) or not isinstance(samples, (int, np.integer)):
+            raise ValueError("samples must be an integer")
+        if max_dist is not None:
+            md = np.asarray(max_dist)
+            if md.dtype.kind not in "fiu" or md.shape not in ((), (n,)):
+                raise ValueError("max_dist must be one distance or hold one per entry, shape (n,)")
+            max_dist = np.ascontiguousarray(np.broadcast_to(md.astype(np.float32), (n,)))
+        return n, pos, normals, rng, max_dist
+
+    @staticmethod
+    def _occlusion_query(n, samples, pos, normals, rng, max_dist):
+        """the query over host arrays and its outputs {"visibility", "bent", "clear", "rays", "rng"}"""
+        out = {"visibility": np.zeros(n, np.float32), "bent": np.zeros((n, 3), np.float32), "clear": np.zeros(n, np.uint32),
+               "rays": np.zeros(n, np.uint32), "rng": np.zeros(n, np.uint32)}
+        q = abi.rt_occlusion_query(n=n, samples=int(samples), pos=pos.ctypes.data, normal=normals.ctypes.data,
+                                   max_dist=None if max_dist is None else max_dist.ctypes.data, rng=rng.ctypes.data, rng_out=out["rng"].ctypes.data,
+                                   visibility=out["visibility"].ctypes.data, bent=out["bent"].ctypes.data, clear=out["clear"].ctypes.data,
+                                   rays=out["rays"].ctypes.data)
+        return q, out
+
+    def gather_occlusion(self, pos: np.ndarray, normals: np.ndarray, rng: np.ndarray, samples: int, max_dist=None) -> dict:
+        """rt_gather_occlusion on host arrays: pos, normals (n, 3) float32 and rng (n,) uint32, every entry's xorshift32 state. `samples`
+        any-hit rays per entry from pos[i] along the diffuse bounce's own direction normals[i] + random_unit_vector, normalised, no farther
+        than max_dist (one distance or (n,), world units; None: +inf). Returns {"visibility": (n,) float32, the share of the samples that met
+        nothing, "bent": (n, 3) float32, the sum of the unoccluded directions over samples (not normalised: bake.normalise_bent), "clear",
+        "rays": (n,) uint32, "rng": (n,) uint32, the states after the last sample} (include/rt_mi355x.h: rt_occlusion_query)."""
+        n, pos, normals, rng, md = self._occlusion_args(pos, normals, rng, samples, max_dist)
+        q, out = self._occlusion_query(n, samples, pos, normals, rng, md)
+        abi.check(self._lib.rt_gather_occlusion(self.h, C.byref(q)), self._lib)
+        return out
+
+    def gather_occlusion_device(self, n: int, d_pos: int, d_normal: int, d_rng: int, samples: int, d_max_dist: int = 0, d_visibility: int = 0,
+                                d_bent: int = 0, d_clear: int = 0, d_rays: int = 0, d_rng_out: int = 0, stream: int = 0) -> None:
+        """rt_gather_occlusion_device on DEVICE pointers (e.g. torch .data_ptr()), enqueued on `stream`; 0 = NULL (no max_dist / output not
+        written; d_rng_out may equal d_rng). Rejected entries are marked: visibility and bent NaN, clear = rays = 0xFFFFFFFF, rng_out = rng."""
+        q = abi.rt_occlusion_query(n=int(n), samples=int(samples), pos=d_pos or None, normal=d_normal or None, max_dist=d_max_dist or None,
+                                   rng=d_rng or None, rng_out=d_rng_out or None, visibility=d_visibility or None, bent=d_bent or None,
+                                   clear=d_clear or None, rays=d_rays or None)
+        abi.check(self._lib.rt_gather_occlusion_device(self.h, C.byref(q), C.c_void_p(stream or None)), self._lib)
+
+    def occlusion_host(self, pos: np.ndarray, normals: np.ndarray, rng: np.ndarray, samples: int, max_dist=None, use_bvh: bool = False) -> dict:
+        """rt_scene_occlusion_host (host diagnostic, needs no GPU): the same gather with every sample's any-hit query by brute force over the
+        triangles (use_bvh False) or by the kernel's walk of the tree, counted. Entries are not refused here. Returns gather_occlusion's
+        arrays and "node_visits", "tri_tests"."""
+        n, pos, normals, rng, md = self._occlusion_args(pos, normals, rng, samples, max_dist)
+        q, out = self._occlusion_query(n, samples, pos, normals, rng, md)
+        nv, nt = C.c_uint64(0), C.c_uint64(0)
+        abi.check(self._lib.rt_scene_occlusion_host(self.h, C.byref(q), 1 if use_bvh else 0, C.byref(nv), C.byref(nt)), self._lib)
+        out["node_visits"], out["tri_tests"] = int(nv.value), int(nt.value)
+        return out
 
     def gbuffer(self, camera: Camera) -> dict:
         """rt_scene_gbuffer: the guide images of the camera's primary hits, {"albedo", "normal", "position"}, each (H, W, 4) float32

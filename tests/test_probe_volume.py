@@ -25,6 +25,7 @@ SYMBOLS = ["rt_probe_volume_create", "rt_probe_volume_destroy", "rt_probe_volume
            "rt_probe_volume_get_sh", "rt_probe_volume_get_sh_device", "rt_probe_volume_sample", "rt_probe_volume_sample_device"]
 TRIES = 8
 BAND = np.array([1.0] + [0.6666667] * 3 + [0.25] * 5, f32)
+SPHERE = f32(12.566371)  # step 4's weight is SPHERE / dirs
 
 
 # ---- the model both files share ---------------------------------------------------------------------------------------------------------
@@ -89,7 +90,7 @@ def project_model(d, radiance, rays, probes, dirs):
     rays = np.asarray(rays, np.uint32).reshape(probes, dirs)
     valid = rays[:, 0] != NONE
     sh = np.zeros((probes, 9, 4), f32)
-    w = f32(12.566371) / f32(dirs)
+    w = SPHERE / f32(dirs)
     with np.errstate(all="ignore"):
         for k in range(9):
             c = np.zeros((probes, 3), f32)
